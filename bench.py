@@ -30,6 +30,15 @@ Output    = ONE JSON line (rank 0) with `roofline` (derivative kernel: algorithm
             `cpu_baseline` (the CPU oracle, kind "port", timed on a bounded sample of the same pairs).  Side measurements, never `value`:
             `value_host_pointers` (both clouds of every pair over PCIe inside the step: pageable, page-locked, page-locked + two batches in
             flight), `gpu_split_ms_per_step`, `pipeline_shape`, `config2_gicp`, `pcl_ndt`, `config3_shard` (+ `two_batches_in_flight`), `soak_over_bar`.
+Plain run = `python bench.py --gpus 1 --steps K --warmup W` does what the headline needs and nothing else: it generates the inputs, warms up,
+            times the K steps, writes the outputs (--dump-outputs) and prints the line; `roofline` then comes from the timed region's HIP events.
+            Everything else above — the same K steps one at a time, the fused kernel's variant alone, the single-pair latency, the CPU baseline
+            and the parity check, the soak, the side measurements and the config[3] leg, the digest of the raw inputs — runs with --full
+            (each leg still has its own --no-* switch there).  --mode shard and --inproc are other workloads, chosen explicitly; --full does not
+            change them.
+--dump-outputs DIR  the records the timed path returned in its last step (the arrays a caller receives: one 384-byte record per pair) as
+            DIR/<field>.npy — T (column-major 4 x 4, float32), H, fitness, trans_probability (float64), converged, iterations, evaluations,
+            pair_id (integers, as float64).  The inputs are seeded: the same arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -127,6 +136,25 @@ def spawn_ranks(n: int) -> int:
 # ------------------------------------------------------------------------------------------------------------------------
 # workloads (host side, before the process touches the GPU: the scans are ray-cast on a pool of forked workers)
 # ------------------------------------------------------------------------------------------------------------------------
+def ray_cast_workers() -> int:
+    """Worker processes for the ray-caster: the CPUs this job may use — the affinity mask, capped by a cgroup CPU quota and by OMP_NUM_THREADS
+    where they are set (on a shared host cpu_count() is the whole machine's, and a pool sized by it only slows itself down), shared by the ranks
+    of the node that ray-cast at the same time.  The scans do not depend on it."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, -(-int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "").split(",")[0] or n))
+    except ValueError:
+        pass
+    n //= max(1, int(os.environ.get("LOCAL_WORLD_SIZE", os.environ.get("WORLD_SIZE", "1"))))
+    return max(1, min(n, 64))
+
+
 def make_workload(n_distinct: int, batch: int, rank: int, prefilter_mode: str):
     """BASELINE config[1] shape. Returns (scene, poses, raw scans): n_distinct + 1 consecutive scans; pair k = (scan k, scan k + 1)."""
     from mrg_slam_amd import synth
@@ -151,7 +179,7 @@ def make_workload(n_distinct: int, batch: int, rank: int, prefilter_mode: str):
     scene = synth.street_scene(seed=1234 + rank, x_range=(-120.0, float(max(420, n_distinct + 140))))
     poses = synth.weave_trajectory(n_distinct + 1)
     seeds = [synth.BASE_SEED + 100000 * rank + k for k in range(n_distinct + 1)]
-    scans = synth.synth_lidar_many(scene, poses, "VLP64", seeds, cache_tag=f"street_r{rank}_n{n_distinct + 1}")
+    scans = synth.synth_lidar_many(scene, poses, "VLP64", seeds, workers=ray_cast_workers(), cache_tag=f"street_r{rank}_n{n_distinct + 1}")
     return scene, poses, scans
 
 
@@ -164,7 +192,8 @@ def make_loop_workload(n_keyframes: int = 64, n_pairs: int = 256, radius: float 
 
     scene = synth.loop_scene(radius=radius)
     poses = synth.loop_trajectory(n_keyframes, radius)
-    scans = synth.synth_lidar_many(scene, poses, "VLP64", [synth.BASE_SEED + 5000 + k for k in range(n_keyframes)], cache_tag=f"loop_k{n_keyframes}_r{int(radius)}")
+    scans = synth.synth_lidar_many(scene, poses, "VLP64", [synth.BASE_SEED + 5000 + k for k in range(n_keyframes)], workers=ray_cast_workers(),
+                                   cache_tag=f"loop_k{n_keyframes}_r{int(radius)}")
     rng = np.random.default_rng(seed)
     cand = [(a, b) for a in range(n_keyframes) for b in range(n_keyframes)
             if a != b and np.hypot(*(poses[a][:2, 3] - poses[b][:2, 3])) <= 15.0]
@@ -206,6 +235,17 @@ def sha16(arrays) -> str:
     for a in arrays:
         h.update(np.ascontiguousarray(a).tobytes())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(out_dir: str, records: np.ndarray) -> None:
+    """--dump-outputs: the records of the timed path's last step, one `out_dir/<field>.npy` per field of the result record (float32 and float64
+    fields as they are, the integer fields as float64), so that two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name in records.dtype.names:
+        a = records[name]
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -692,6 +732,8 @@ def run_inproc(args, loop_raw, loop_pairs):
         res, best = step()
         step_ms.append(1e3 * (time.perf_counter() - ts))
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
     digest = hashlib.sha256(res["T"].tobytes() + res["fitness"].tobytes() + res["converged"].tobytes()).hexdigest()[:16]
     in_digest = hashlib.sha256(b"".join(np.ascontiguousarray(c).tobytes() for c in l_host)).hexdigest()[:16]
     err = [float(np.linalg.norm(np.asarray(res[i]["T"]).reshape(4, 4).T[:3, 3] - loop_pairs[i][3][:3, 3])) for i in range(len(loop_pairs))]
@@ -742,9 +784,19 @@ def main():
                                                               "the compact line (< 4 KB) on stdout, the full record on stderr and in bench_extras.json")
     ap.add_argument("--no-latency", action="store_true", help="skip the single-pair setInputTarget + align latency behind the timed region (profiling runs: it adds differently "
                                                                "sized launches of the same kernels, so the trace averages would no longer describe the timed workload)")
+    ap.add_argument("--full", action="store_true", help="the default mode's side measurements and checks as well: the steps one at a time, the fused kernel's variant "
+                                                        "alone, the side legs (--no-extras), the config[3] leg (--shard-steps), the single-pair latency, the CPU baseline, "
+                                                        "parity and soak (--no-cpu), the raw-input digest; without it a run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the records the timed path returned in its last step as DIR/<field>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.distinct <= 0:
         args.distinct = args.batch
+    if args.mode == "weak" and not args.full:
+        # a plain run: setup, warm-up, the timed steps, the outputs, the line — every leg beside the timed region is switched off
+        args.no_seq = args.no_extras = args.no_latency = args.no_cpu = True
+        args.shard_steps = 0
 
     if args.inproc:
         if args.mode != "shard":
@@ -881,7 +933,7 @@ def main():
         return elapsed, step_ms, last
 
     # ---- config[3]: 256 loop-closure candidate pairs sharded over the ranks ------------------------------------------------
-    def run_shard(steps, warmup):
+    def run_shard(steps, warmup, dump=None):
         l_host, l_dev = to_hbm(loop_raw)
         n_pairs = len(loop_pairs)
         fake_world = args.shard_of if (args.shard_of > 1 and world == 1) else 0
@@ -942,6 +994,8 @@ def main():
 
         bm.timing(reset=True)
         elapsed, step_ms, (full, best) = timed(step, steps, warmup)
+        if dump and rank == 0:
+            dump_outputs(dump, full)
         us_per_candidate = bm.timing()["average_time_per_candidate_us"]  # the reference's own statistic (apps/mrg_slam_component.cpp:1032-1037) over the timed steps + warm-up
         if phases:
             print("[bench] step phases, median ms: queue the batch %.3f, align %.3f, records + best candidate %.3f" % tuple(1e3 * np.median(np.array(phases[-steps:]), axis=0)), file=sys.stderr)
@@ -1111,7 +1165,7 @@ def main():
                 "per_step_ms": [round(v, 2) for v in step_ms], "roofline": roof, "roofline_fitness": roof_fit}
 
     if args.mode == "shard":
-        r = run_shard(args.steps, args.warmup)
+        r = run_shard(args.steps, args.warmup, args.dump_outputs)
         if rank == 0:
             out = {"metric": METRIC, "value": r["alignments_per_s"], "unit": "alignments/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                    "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32 per-pair terms, f64 accumulation",
@@ -1136,7 +1190,7 @@ def main():
         cold = args.cold_every > 0 and b % args.cold_every == args.cold_every - 1
         guess = np.eye(4) if cold else synth.warm_guess(rels[k], 1000 * rank + b)
         pairs.append((k, k + 1, guess, rels[k], cold))
-    raw_digest = sha16(raw)
+    raw_digest = sha16(raw) if args.full else None
     n_pts = float(np.mean([len(scans[p[1]]) for p in pairs]))
     n_src_per_step = float(sum(len(scans[p[1]]) for p in pairs)) / args.batch  # mean source points per alignment
     hbm_input_bytes = 16.0 * sum(len(scans[p[0]]) + len(scans[p[1]]) for p in pairs)
@@ -1234,11 +1288,13 @@ def main():
     print(f"[bench rank {rank}] per-step ms: " + " ".join(f"{v:.2f}" for v in step_ms), file=sys.stderr)
     total_pairs = world * args.batch * args.steps
     value = total_pairs / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
     # the score + gradient + Hessian variant on its own (round 1 / 2 reported it as the dominant kernel): two extra, UNTIMED steps with one
     # launch per variant, so that its launches can be told from the others' — listed beside the fused kernel's figures, never `value`
     alone = None
-    if lib().mrgfe_dbg_set_fused_launch(-1) == 1:
+    if args.full and lib().mrgfe_dbg_set_fused_launch(-1) == 1:
         lib().mrgfe_dbg_set_fused_launch(0)
         m0 = np.zeros(3)
         step()
@@ -1686,7 +1742,7 @@ def main():
         "parity_vs_oracle": parity,
         "soak_over_bar": soak,
         "raw_inputs_sha256_16": raw_digest,
-        "raw_inputs_as_in_the_build_container": (raw_digest == EXPECTED_RAW_INPUTS["config1_rank0_257_scans"]) if (EXPECTED_RAW_INPUTS["config1_rank0_257_scans"] and rank == 0 and args.distinct == 256 and scene is not None) else None,
+        "raw_inputs_as_in_the_build_container": (raw_digest == EXPECTED_RAW_INPUTS["config1_rank0_257_scans"]) if (raw_digest and EXPECTED_RAW_INPUTS["config1_rank0_257_scans"] and rank == 0 and args.distinct == 256 and scene is not None) else None,
         "evaluations_per_alignment": evals / (args.batch * args.steps),
         "evaluations_launched_per_alignment": float(launched[0] / (n_src_per_step * args.batch * args.steps)) if n_src_per_step else None,
         "iterations_per_alignment": iters / (args.batch * args.steps),

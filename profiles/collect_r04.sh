@@ -17,7 +17,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 git_rev=${3:-unknown}   # the snapshot on the GPU box has no .git: the caller passes `git rev-parse --short HEAD`
 python3 bench.py --prepare-only && python3 bench.py --mode shard --prepare-only || exit 1
-C1="python3 bench.py --no-cpu --no-extras --shard-steps 0"
+C1="python3 bench.py --full --no-cpu --no-extras --shard-steps 0"
 C3="python3 bench.py --mode shard --no-cpu --no-extras --steps 6 --warmup 2"
 C38="python3 bench.py --mode shard --no-cpu --no-extras --shard-of 8 --steps 12 --warmup 3"
 GB="python3 profiles/gicp_profile.py batch"

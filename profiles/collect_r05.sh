@@ -15,9 +15,10 @@ tag=${2:-r05}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 git_rev=${3:-unknown}
+out=$(python3 -c 'import sys; sys.path.insert(0, "profiles"); import summarize; print(summarize.OUT)')  # the folder profiles/summarize.py reads
 python3 bench.py --prepare-only && python3 bench.py --mode shard --prepare-only || exit 1
-C1="python3 bench.py --no-cpu --no-extras --shard-steps 0 --in-flight 1"
-C1P="python3 bench.py --no-cpu --no-extras --shard-steps 0 --in-flight 2 --no-seq --steps 10"
+C1="python3 bench.py --full --no-cpu --no-extras --shard-steps 0 --in-flight 1"
+C1P="python3 bench.py --full --no-cpu --no-extras --shard-steps 0 --in-flight 2 --no-seq --steps 10"
 C3="python3 bench.py --mode shard --no-cpu --no-extras --steps 6 --warmup 2"
 C38="python3 bench.py --mode shard --no-cpu --no-extras --shard-of 8 --steps 12 --warmup 3"
 GB="python3 profiles/gicp_profile.py batch"
@@ -39,7 +40,7 @@ if [ "$part" = trace ]; then
     echo "GICP traces done"
     python3 tests/extra_measurements.py > gpurun_out/extra_$tag.json 2> gpurun_out/extra_$tag.err
     echo "extra measurements done"
-    python3 bench.py --no-cpu --no-extras --shard-steps 0 --steps 20 2>/dev/null | tail -1 > gpurun_out/bench_$tag.json
+    python3 bench.py --full --no-cpu --no-extras --shard-steps 0 --steps 20 2>/dev/null | tail -1 > "$out/bench_$tag.json"
     $C3 2>/dev/null | tail -1 > gpurun_out/bench_shard_$tag.json
     $C38 2>/dev/null | tail -1 > gpurun_out/bench_shard8_$tag.json
     : > gpurun_out/inproc_$tag.jsonl

@@ -5,11 +5,11 @@ under profiles/ (gpurun_out/ is scratch and ignored by git).
     python profiles/summarize.py r01            # reads gpurun_out/{prof,pmc_fetch,pmc_write,pmc_sq}_*, writes profiles/r01_*
 
 Commands that produced the inputs (run on the GPU box from /tmp with TMPDIR=/tmp, program directly after `--`):
-    rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_r01 -o r01 -- python3 bench.py --no-cpu
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -o f -- python3 bench.py --no-cpu --steps 1 --warmup 0
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -o w -- python3 bench.py --no-cpu --steps 1 --warmup 0
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT/prof_r01 -o r01 -- python3 bench.py --full --no-cpu
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT/pmc_fetch -o f -- python3 bench.py --full --no-cpu --steps 1 --warmup 0
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT/pmc_write -o w -- python3 bench.py --full --no-cpu --steps 1 --warmup 0
     rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES GRBM_GUI_ACTIVE --kernel-trace \
-              --output-format csv -d gpurun_out/pmc_sq -o s -- python3 bench.py --no-cpu --steps 1 --warmup 0
+              --output-format csv -d OUT/pmc_sq -o s -- python3 bench.py --full --no-cpu --steps 1 --warmup 0
 HBM traffic follows MI355X_MICROARCH.md §HBM: FETCH_SIZE / WRITE_SIZE are in KiB, collected in separate passes; on gfx950
 FETCH_SIZE reports half of the bytes of wide coalesced reads, so it is doubled (an upper estimate for this kernel, whose
 reads are a mix of 16-byte streams and scattered 48-byte records).
