@@ -465,6 +465,52 @@ int mrgfe_batch_rounds(const mrgfe_batch* b);
 int mrgfe_batch_timing(const mrgfe_batch* b, double out[4]);
 int mrgfe_batch_timing_reset(mrgfe_batch* b);
 
+/* ---- floor detection (apps/floor_detection_component.cpp:100-183, FloorDetectionComponent::detect) ------------------------------------------ *
+ * Tilt compensation, the height band (PlaneClipper3D + ExtractIndices), the k = 10 normal filter (NormalEstimation on a KdTree), and
+ * RandomSampleConsensus<SampleConsensusModelPlane> with threshold 0.1 — all on the GPU.  Parameter names / defaults: the component's
+ * declare_parameter calls (:55-62) and config/mrg_slam.yaml:113-122.  The reference DECLARES enable_normal_filtering (:61) but READS
+ * use_normal_filtering (:120); this port has one field with the evident intent. */
+typedef struct mrgfe_floor_params {
+    double tilt_deg;                  /* 0.0   "tilt_deg"                                                        */
+    double sensor_height;             /* 2.0   "sensor_height"                                                   */
+    double height_clip_range;         /* 1.0   "height_clip_range"                                               */
+    int    floor_pts_thresh;          /* 512   "floor_pts_thresh"                                                */
+    double floor_normal_thresh_deg;   /* 10.0  "floor_normal_thresh_deg"                                         */
+    int    use_normal_filtering;      /* 1     "enable_normal_filtering" (:61; read as "use_normal_filtering" :120) */
+    double normal_filter_thresh_deg;  /* 20.0  "normal_filter_thresh_deg"                                        */
+} mrgfe_floor_params;
+void mrgfe_floor_default_params(mrgfe_floor_params* out);
+/* why detect() returned what it returned */
+enum mrgfe_floor_reason {
+    MRGFE_FLOOR_FOUND = 0,
+    MRGFE_FLOOR_EMPTY_INPUT = 1,        /* cloud_callback returns before detect() (:79-82)                       */
+    MRGFE_FLOOR_NONE_AFTER_CLIP = 2,    /* no point in the height band (:115-118)                                */
+    MRGFE_FLOOR_TOO_FEW_FILTERED = 3,   /* filtered->size() < floor_pts_thresh (:134-136)                        */
+    MRGFE_FLOOR_NO_MODEL = 4,           /* RandomSampleConsensus found no model (fewer than 3 points, no non-collinear sample) */
+    MRGFE_FLOOR_TOO_FEW_INLIERS = 5,    /* inliers < floor_pts_thresh (:148)                                     */
+    MRGFE_FLOOR_NOT_VERTICAL = 6        /* |n . (tilt^-1 z)| < cos(floor_normal_thresh_deg) (:153-162)           */
+};
+typedef struct mrgfe_floor_result {
+    int32_t  found;        /* 1: coeffs is the boost::optional<Vector4f> detect() returns; 0: boost::none          */
+    int32_t  reason;       /* enum mrgfe_floor_reason                                                             */
+    float    coeffs[4];    /* a, b, c, d with the normal pointing up (:164-167); set when a model was found        */
+    uint32_t n_clipped;    /* points in the height band                                                          */
+    uint32_t n_filtered;   /* points after the normal filter (= n_clipped without it): floor_filtered_points       */
+    uint32_t n_inliers;    /* RANSAC inliers of the winning plane: floor_points                                  */
+    int32_t  iterations;   /* RandomSampleConsensus::iterations_ at the end of computeModel                       */
+    int32_t  skipped;      /* samples whose coefficients could not be computed                                    */
+    int32_t  reserved;
+} mrgfe_floor_result;
+/* replaces detect(cloud) (:100-183) — and what the component publishes next to it: out_filtered (nullable, capacity n packed points) receives
+ * floor_filtered_points (:126-131: the RANSAC input, back in the sensor frame), out_inliers (nullable, capacity n) floor_points (:169-180: the
+ * inliers of the accepted plane, written only when found).  Returns MRGFE_OK whether or not a floor was found. */
+int  mrgfe_floor_detect(mrgfe_ctx* ctx, const mrgfe_floor_params* params, const float* xyzi, size_t n, size_t stride_bytes, mrgfe_floor_result* result,
+                        float* out_filtered, float* out_inliers);
+/* the same for a cloud already in device memory (packed float4): the output of mrgfe_prefilter_device — prefiltering/filtered_points, the topic
+ * the component subscribes to — without a round trip through the host */
+int  mrgfe_floor_detect_device(mrgfe_ctx* ctx, const mrgfe_floor_params* params, const void* d_xyzi, size_t n, mrgfe_floor_result* result,
+                               float* out_filtered, float* out_inliers);
+
 /* Diagnostic entry points (alternative paths of the same arithmetic, primitives, the optimiser stepped by hand) are declared in mrgfe_debug.h; the two
  * fault injectors there exist only in a library built with -DMRGFE_TESTING (mrg_slam_amd/libmrgfe_testing.so): the shipped libmrgfe.so has neither. */
 

@@ -84,6 +84,18 @@ void mrgfe_dbg_sincosf(const float* x, size_t n, float* sin_out, float* cos_out)
  * tests/test_glibc_exp.py holds the host build against the C library and regenerates the table; tests/test_gpu_primitives.py holds the device against the host. */
 int mrgfe_dbg_exp(mrgfe_ctx* ctx, const double* x, size_t n, int on_device, double* out);
 int mrgfe_dbg_ctl_math(mrgfe_ctx* ctx, const double* cases48, int n, int on_device, float* M16, double* tables69, double* x6);
+/* ---- floor detection stages (tests/test_gpu_floor.py; csrc/floor.hip) ------------------------------------------------------------------- */
+/* RandomSampleConsensus<SampleConsensusModelPlane> alone on a cloud (floor_detection_component.cpp:139-145): *has_model, the coefficients of the
+ * winning sample, the inlier indices (capacity n, ascending), their count, iterations_ and the skipped samples.  `threshold` = setDistanceThreshold. */
+int mrgfe_dbg_floor_ransac(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride_bytes, double threshold, int* has_model, float coeffs[4], int32_t* inliers,
+                           size_t* n_inliers, int32_t* iterations, int32_t* skipped);
+/* normal_filtering (:216-243) alone: per point the eigen33 vector of NormalEstimation with setKSearch(10) (normals_xyz, 3 floats; NaN with fewer
+ * than three neighbours) and the keep flag |n.z| / |n| > cos(normal_filter_thresh_deg) */
+int mrgfe_dbg_floor_normals(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride_bytes, double normal_filter_thresh_deg, float* normals_xyz, uint8_t* keep);
+/* the last floor detection on this context: out[0..3] HIP-event milliseconds of the band stage (tilt, clip, compaction), the normal stage (grid,
+ * k-NN, eigen33, compaction, back-transform), RANSAC (all waves) and the inlier pass; out[4] host waits; out[5] RANSAC waves; out[6] hypotheses drawn */
+int mrgfe_dbg_floor_stats(mrgfe_ctx* ctx, double out[8]);
+
 typedef struct mrgfe_dbg_ctl mrgfe_dbg_ctl;
 int  mrgfe_dbg_ctl_create(const mrgfe_reg_params* params, const float guess[16], uint32_t n_src, mrgfe_dbg_ctl** out);
 void mrgfe_dbg_ctl_destroy(mrgfe_dbg_ctl* h);

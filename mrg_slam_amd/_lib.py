@@ -43,6 +43,23 @@ class PrefilterParams(C.Structure):
                 ("radius_min_neighbors", C.c_int), ("statistical_mean_k", C.c_int), ("statistical_stddev", C.c_double)]
 
 
+class FloorParams(C.Structure):
+    """struct mrgfe_floor_params (the floor_detection_component ROS parameters, apps/floor_detection_component.cpp:55-62, config/mrg_slam.yaml:113-122)."""
+
+    _fields_ = [("tilt_deg", C.c_double), ("sensor_height", C.c_double), ("height_clip_range", C.c_double), ("floor_pts_thresh", C.c_int),
+                ("floor_normal_thresh_deg", C.c_double), ("use_normal_filtering", C.c_int), ("normal_filter_thresh_deg", C.c_double)]
+
+
+class FloorResult(C.Structure):
+    """struct mrgfe_floor_result: what detect() returned and why, with the point counts of its stages."""
+
+    _fields_ = [("found", C.c_int32), ("reason", C.c_int32), ("coeffs", C.c_float * 4), ("n_clipped", C.c_uint32), ("n_filtered", C.c_uint32),
+                ("n_inliers", C.c_uint32), ("iterations", C.c_int32), ("skipped", C.c_int32), ("reserved", C.c_int32)]
+
+
+FLOOR_REASONS = ("found", "empty_input", "none_after_clip", "too_few_filtered", "no_model", "too_few_inliers", "not_vertical")
+
+
 class InfParams(C.Structure):
     """struct mrgfe_inf_params (InformationMatrixCalculator's ROS parameters, config/mrg_slam.yaml:216-223,173)."""
 
@@ -134,6 +151,9 @@ SIGNATURES = {
     "mrgfe_prefilter_default_params": (None, [C.POINTER(PrefilterParams)]),
     "mrgfe_prefilter": (C.c_int, [_vp, C.POINTER(PrefilterParams), _fp, C.c_size_t, C.c_size_t, _fp, C.POINTER(C.c_size_t)]),
     "mrgfe_prefilter_device": (C.c_int, [_vp, C.POINTER(PrefilterParams), _fp, C.c_size_t, C.c_size_t, _vp, C.POINTER(C.c_size_t)]),
+    "mrgfe_floor_default_params": (None, [C.POINTER(FloorParams)]),
+    "mrgfe_floor_detect": (C.c_int, [_vp, C.POINTER(FloorParams), _fp, C.c_size_t, C.c_size_t, C.POINTER(FloorResult), _fp, _fp]),
+    "mrgfe_floor_detect_device": (C.c_int, [_vp, C.POINTER(FloorParams), _vp, C.c_size_t, C.POINTER(FloorResult), _fp, _fp]),
     "mrgfe_knn": (C.c_int, [_vp, _fp, C.c_size_t, _fp, C.c_size_t, C.c_size_t, C.c_int, _ip, _fp]),
     "mrgfe_pclgicp_evaluate": (C.c_int, [_vp, _fp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     "mrgfe_gicp_linearize": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _ip]),
@@ -215,6 +235,9 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_set_ndt_reference_order": (C.c_int, [C.c_int]),
     "mrgfe_dbg_set_fit_sweep": (C.c_int, [C.c_int]),
     "mrgfe_dbg_set_prefilter_device_driven": (C.c_int, [C.c_int]),
+    "mrgfe_dbg_floor_ransac": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(C.c_int), _fp, _ip, _szp, _ip, _ip]),
+    "mrgfe_dbg_floor_normals": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, C.c_double, _fp, C.POINTER(C.c_uint8)]),
+    "mrgfe_dbg_floor_stats": (C.c_int, [_vp, _dp]),
     "mrgfe_dbg_set_pclgicp_reference_order": (C.c_int, [C.c_int]),
     "mrgfe_dbg_set_fit_stats": (C.c_int, [C.c_int]),
     "mrgfe_dbg_sincosf": (None, [_fp, C.c_size_t, _fp, _fp]),

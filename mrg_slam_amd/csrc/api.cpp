@@ -19,6 +19,7 @@
 #include "common.h"
 #include "glibc_exp.h"
 #include "filters.h"
+#include "floor.h"
 #include "mapcloud.h"
 #include "gicp_engine.h"
 #include "ndt_derivatives.h"
@@ -1867,6 +1868,115 @@ int mrgfe_dbg_ctl_final(const mrgfe_dbg_ctl* h, float T[16], int* converged, int
     if (converged) *converged = h->c.converged() ? 1 : 0;
     if (iterations) *iterations = h->c.iterations();
     if (evaluations) *evaluations = h->c.evaluations();
+    return MRGFE_OK;
+}
+
+// ---- floor detection (floor.hip) ---------------------------------------------------------------------------------------------------------------
+void mrgfe_floor_default_params(mrgfe_floor_params* p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->tilt_deg = 0.0;                  // apps/floor_detection_component.cpp:55, config/mrg_slam.yaml:116
+    p->sensor_height = 2.0;             // :56, yaml :117
+    p->height_clip_range = 1.0;         // :57, yaml :118
+    p->floor_pts_thresh = 512;          // :59, yaml :119
+    p->floor_normal_thresh_deg = 10.0;  // :60, yaml :120
+    p->use_normal_filtering = 1;        // enable_normal_filtering :61, yaml :121
+    p->normal_filter_thresh_deg = 20.0; // :62, yaml :122
+}
+static int floor_check(const mrgfe_floor_params* p, const char* fn)
+{
+    if (!std::isfinite(p->tilt_deg) || !std::isfinite(p->sensor_height) || !std::isfinite(p->height_clip_range) || !std::isfinite(p->floor_normal_thresh_deg) ||
+        !std::isfinite(p->normal_filter_thresh_deg)) {
+        set_error("%s: non-finite parameter", fn);
+        return MRGFE_ERR_INVALID;
+    }
+    return MRGFE_OK;
+}
+int mrgfe_floor_detect(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const float* xyzi, size_t n, size_t stride, mrgfe_floor_result* res, float* out_filtered,
+                       float* out_inliers)
+{
+    MRGFE_TRY(check_count(n, "mrgfe_floor_detect"));
+    if (!ctx || !p || !res || (n && !xyzi)) { set_error("mrgfe_floor_detect: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_TRY(floor_check(p, "mrgfe_floor_detect"));
+    MRGFE_LOCK(ctx);
+    MRGFE_TRY(ctx->bind());
+    DevBuf& din = ctx->fl_buf[10];
+    MRGFE_TRY(din.ensure(std::max<size_t>(n, 1) * 16));
+    if (n) MRGFE_TRY(upload_cloud(ctx, xyzi, n, stride, din.p));
+    return floor_detect(ctx, p, din.as<float4>(), n, res, out_filtered, out_inliers);
+}
+int mrgfe_floor_detect_device(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const void* d_xyzi, size_t n, mrgfe_floor_result* res, float* out_filtered,
+                              float* out_inliers)
+{
+    MRGFE_TRY(check_count(n, "mrgfe_floor_detect_device"));
+    if (!ctx || !p || !res || (n && !d_xyzi)) { set_error("mrgfe_floor_detect_device: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_TRY(floor_check(p, "mrgfe_floor_detect_device"));
+    MRGFE_LOCK(ctx);
+    MRGFE_TRY(ctx->bind());
+    return floor_detect(ctx, p, static_cast<const float4*>(d_xyzi), n, res, out_filtered, out_inliers);
+}
+int mrgfe_dbg_floor_ransac(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, double threshold, int* has_model, float coeffs[4], int32_t* inliers,
+                           size_t* n_inliers, int32_t* iterations, int32_t* skipped)
+{
+    MRGFE_TRY(check_count(n, "mrgfe_dbg_floor_ransac"));
+    if (!ctx || !has_model || !coeffs || !n_inliers || !iterations || !skipped || (n && (!xyzi || !inliers))) {
+        set_error("mrgfe_dbg_floor_ransac: NULL argument");
+        return MRGFE_ERR_INVALID;
+    }
+    MRGFE_LOCK(ctx);
+    MRGFE_TRY(ctx->bind());
+    DevBuf &din = ctx->fl_buf[10], &dfl = ctx->fl_buf[1];
+    MRGFE_TRY(din.ensure(std::max<size_t>(n, 1) * 16));
+    MRGFE_TRY(dfl.ensure(std::max<size_t>(n, 1) * 4));
+    if (n) MRGFE_TRY(upload_cloud(ctx, xyzi, n, stride, din.p));
+    FloorRansacOut r;
+    MRGFE_TRY(floor_ransac_device(ctx, din.as<float4>(), static_cast<uint32_t>(n), threshold, dfl.as<uint32_t>(), &r));
+    *has_model = r.has_model;
+    for (int j = 0; j < 4; ++j) coeffs[j] = r.coeffs[j];
+    *iterations = r.iterations;
+    *skipped = r.skipped;
+    *n_inliers = 0;
+    if (r.has_model && n) {
+        std::vector<uint32_t> fl(n);
+        MRGFE_HIP_CHECK(hipMemcpyAsync(fl.data(), dfl.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        size_t m = 0;
+        for (size_t i = 0; i < n; ++i)
+            if (fl[i]) inliers[m++] = static_cast<int32_t>(i);
+        *n_inliers = m;
+    }
+    return MRGFE_OK;
+}
+int mrgfe_dbg_floor_normals(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, double normal_filter_thresh_deg, float* normals_xyz, uint8_t* keep)
+{
+    MRGFE_TRY(check_count(n, "mrgfe_dbg_floor_normals"));
+    if (!ctx || (n && (!xyzi || !normals_xyz || !keep))) { set_error("mrgfe_dbg_floor_normals: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(ctx);
+    MRGFE_TRY(ctx->bind());
+    if (n == 0) return MRGFE_OK;
+    DevBuf &din = ctx->fl_buf[10], &dfl = ctx->fl_buf[1], &dnr = ctx->fl_buf[0];
+    MRGFE_TRY(din.ensure(n * 16));
+    MRGFE_TRY(dfl.ensure(n * 4));
+    MRGFE_TRY(dnr.ensure(n * 16));
+    MRGFE_TRY(upload_cloud(ctx, xyzi, n, stride, din.p));
+    MRGFE_TRY(floor_normals_device(ctx, din.as<float4>(), static_cast<uint32_t>(n), normal_filter_thresh_deg, dnr.as<float4>(), dfl.as<uint32_t>()));
+    std::vector<float>    nr(n * 4);
+    std::vector<uint32_t> fl(n);
+    MRGFE_HIP_CHECK(hipMemcpyAsync(nr.data(), dnr.p, n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    MRGFE_HIP_CHECK(hipMemcpyAsync(fl.data(), dfl.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; ++i) {
+        for (int j = 0; j < 3; ++j) normals_xyz[i * 3 + j] = nr[i * 4 + j];
+        keep[i] = fl[i] ? 1 : 0;
+    }
+    return MRGFE_OK;
+}
+int mrgfe_dbg_floor_stats(mrgfe_ctx* ctx, double out[8])
+{
+    if (!ctx || !out) { set_error("mrgfe_dbg_floor_stats: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(ctx);
+    for (int j = 0; j < 8; ++j) out[j] = ctx->fl_stats[j];
     return MRGFE_OK;
 }
 

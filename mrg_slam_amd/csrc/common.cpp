@@ -492,6 +492,10 @@ void mrgfe_ctx_destroy(mrgfe_ctx* ctx)
     for (auto& b : ctx->pf_buf) b.release();
     ctx->pf_state.release();
     ctx->pf_status.release();
+    for (auto& b : ctx->fl_buf) b.release();
+    ctx->fl_pin.release();
+    for (auto& e : ctx->fl_ev)
+        if (e) (void)hipEventDestroy(e);
     for (auto& b : ctx->scratch) b.release();
     ctx->sort_chunks.release();
     for (auto& b : ctx->pin) b.release();

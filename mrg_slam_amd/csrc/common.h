@@ -186,6 +186,10 @@ struct mrgfe_ctx {
     float        pf_out_box[6] = {0, 0, 0, 0, 0, 0};  // min xyz, max xyz
     bool         pf_out_valid = false;
     int          cu_count = 256;
+    mrgfe::DevBuf fl_buf[11];                   // floor detection (floor.hip): clouds, flags, k-NN lists, RANSAC state / hypotheses / counts
+    mrgfe::PinBuf fl_pin;                       // ... and the hypothesis records and counts the host reads after each RANSAC wave
+    hipEvent_t   fl_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // stage boundaries of the last floor detection (mrgfe_dbg_floor_stats)
+    double       fl_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     mrgfe::NnGrid* tmp_grid = nullptr;          // reusable exact-NN grid of the stateless filter / fitness calls (nn_grid.hip)
     std::recursive_mutex mu;                    // serialises API calls that share this context's stream / workspaces
     int          bind();                        // hipSetDevice(device)
