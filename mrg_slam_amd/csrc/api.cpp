@@ -271,6 +271,9 @@ int mrgfe_reg_set_target(mrgfe_reg* reg, const float* xyzi, size_t n, size_t str
     if (!reg || (n && !xyzi)) { set_error("mrgfe_reg_set_target: NULL argument"); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(reg->ctx);
     MRGFE_TRY(reg->ctx->bind());
+    // after source_becomes_target the source lives in reg->tgt: give that buffer back to the source (reg->d_src and the GICP engine's d_src_ keep
+    // pointing at it) and upload into the spare one, the only buffer that may be freed and regrown here
+    if (reg->d_src == reg->tgt.p && reg->tgt.p != nullptr) std::swap(reg->src, reg->tgt);
     MRGFE_TRY(reg->tgt.ensure(std::max<size_t>(n, 1) * 16));
     MRGFE_TRY(upload_cloud(reg->ctx, xyzi, n, stride_bytes, reg->tgt.p));
     reg->d_tgt = reg->tgt.p;

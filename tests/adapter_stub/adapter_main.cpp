@@ -137,6 +137,29 @@ int main(int argc, char** argv)
     registration->align(*aligned, Eigen::Matrix4f::Identity());
     const double self = registration->getFitnessScore();
     check(self < 1e-6, "source aligned onto itself after setInputTarget(source): fitness ~ 0");
+    // PCL's setInputTarget replaces the target only: after that hand-over, a new target without setInputSource aligns the same source
+    auto same_matrix = [](const Eigen::Matrix4f& a, const Eigen::Matrix4f& b) {
+        for (int i = 0; i < 16; ++i)
+            if (a.data()[i] != b.data()[i]) return false;
+        return true;
+    };
+    registration->setInputTarget(target);
+    registration->align(*aligned, Eigen::Matrix4f::Identity());
+    check(same_matrix(registration->getFinalTransformation(), T), "setInputTarget(target) after the hand-over keeps the source: the first alignment bit for bit");
+    // ... also when the new target is larger than any cloud the registration holds (its device buffer is regrown)
+    {
+        Cloud::Ptr big = make_room(3, 3 * n, 0.0f);
+        pcl::Registration<PointT, PointT>::Ptr plain(new mrgfe_pcl::HipRegistration<PointT, PointT>(prm));
+        Cloud::Ptr out(new Cloud);
+        plain->setInputTarget(big);
+        plain->setInputSource(source);
+        plain->align(*out, Eigen::Matrix4f::Identity());
+        registration->setInputTarget(source);
+        registration->setInputTarget(big);
+        registration->align(*aligned, Eigen::Matrix4f::Identity());
+        check(same_matrix(registration->getFinalTransformation(), plain->getFinalTransformation()),
+              "hand-over, then a larger target: the source is kept, the same alignment as a registration given that target and source");
+    }
     // a source that is not dense: PCL's getFitnessScore skips its non-finite points and never asks the search object about them
     {
         Cloud::Ptr holes(new Cloud(*make_room(2, n, 0.3f)));
