@@ -420,6 +420,39 @@ int  mrgfe_batch_largest_launch(const mrgfe_batch* b, double out[4]);
  * scored in waves beside the remaining alignment rounds, the rest afterwards): the layout of mrgfe_ctx_fitness_stats, out[10] = launches. */
 int  mrgfe_batch_fitness_stats(const mrgfe_batch* b, double out[11]);
 
+/* ---- bounded best-candidate selection (loop_detector.cpp:126-145, the fitness_score_thresh gate :156-160) ---------------------------------
+ * LoopDetector::matching consumes only the ARG-MIN of getFitnessScore over the converged candidates of one new keyframe:
+ *     if( !registration_->hasConverged() || score > best_score ) continue;  best_score = score; best_matched = candidate; ...
+ * mrgfe_batch_align_best aligns the batch exactly as mrgfe_batch_align does (T, H, trans_probability, converged, iterations, evaluations and
+ * pair_id bit for bit) and then scores exactly only the candidates that can still win.  Every pair has a group, group[i] = -1 (scored exactly,
+ * as mrgfe_batch_align would) or in [0, n_groups); within a group candidate order is pair order; groups need not be contiguous and may span
+ * targets.  The block and seed passes of getFitnessScore give every pair a certified interval lower <= fitness <= upper (bit-valid: the same
+ * slices and reduction tree as the exact sum over per-point bounds); a converged candidate whose lower bound is strictly above the least upper
+ * bound in its group is PRUNED, one whose lower bound exceeds score_cap is ABOVE_CAP, and only the rest run the exact passes.
+ * Per pair, fit_state[i] (nullable):
+ *   MRGFE_FIT_EXACT      fitness is bit-identical to mrgfe_batch_align's;
+ *   MRGFE_FIT_PRUNED     fitness holds a certified lower bound, strictly above the upper bound of a converged candidate of the same group;
+ *   MRGFE_FIT_ABOVE_CAP  fitness holds a certified lower bound > score_cap;
+ *   MRGFE_FIT_SKIPPED    not converged (grouped pairs), or an empty cloud: fitness = DBL_MAX.
+ * INVARIANT: the candidate attaining the least upper bound of a group is never pruned and is scored exactly, and every pruned value is strictly
+ * above its exact score, so the sequential rule (mrgfe_node_select_best, loop_closure.select_best, LoopDetector's best_of) returns the same winner
+ * and score on these records as on mrgfe_batch_align's — for every group and for any union of groups.  A group that holds a NaN bound is scored
+ * exactly throughout (the rule lets a NaN through and then accepts every later candidate).
+ * best[g] / best_score[g]: the rule's result on the full path's records — a pair index, or -1 when the group has no converged candidate; ties go
+ * to the LAST of equal scores, +inf never matches.  score_cap = DBL_MAX is off; otherwise best[g] = -2 exactly when the full rule's best score of a
+ * group with a converged candidate exceeds the cap (fitness_score_thresh: no loop from that group in the reference either), best_score[g] then
+ * being the least fitness in the group (> score_cap), and the result is identical to the full path's everywhere else.
+ * fitness_max_range: as mrgfe_batch_align, >= 0 (else MRGFE_ERR_INVALID; so is a group id outside [-1, n_groups)).  With a finite range a pair
+ * is pruned only when its counted point set is already certain.  One extra host wait per call.  No early fitness pass in this mode.
+ * mrgfe_batch_align_async and mrgfe_node_* have no selection mode. */
+enum mrgfe_fit_state { MRGFE_FIT_EXACT = 0, MRGFE_FIT_PRUNED = 1, MRGFE_FIT_ABOVE_CAP = 2, MRGFE_FIT_SKIPPED = 3 };
+int  mrgfe_batch_align_best(mrgfe_batch* b, double fitness_max_range, double score_cap, const int32_t* group /* n_pairs */, int n_groups,
+                            mrgfe_pair_result* results /* n_pairs */, int32_t* fit_state /* n_pairs, nullable */, int32_t* best /* n_groups */,
+                            double* best_score /* n_groups */);
+/* the last mrgfe_batch_align_best: out[0..3] = pairs EXACT / PRUNED / ABOVE_CAP / SKIPPED, out[4] / out[5] = queries left to the sweep / the
+ * pyramid walk after the selection, out[6] = host ms of the bound stage (block, seed, bound sums, selection), out[7] = of the contender stage */
+int  mrgfe_batch_select_stats(const mrgfe_batch* b, double out[8]);
+
 /* ---- the same batch over the GPUs of one node ---------------------------------------------------------------------------
  * LoopDetector::matching runs in ONE host process per robot (src/mrg_slam/loop_detector.cpp:104,126-145 under mrg_slam_component's main
  * thread mutex): a node object lets that process reach every GPU of the machine through this header.  It owns one MEMBER per entry of

@@ -103,6 +103,16 @@ int  mrgfe_dbg_ctl_request(const mrgfe_dbg_ctl* h, int* mode, float T[16], doubl
 int  mrgfe_dbg_ctl_result(mrgfe_dbg_ctl* h, double score, const double grad[6], const double hess[36], double neighbours);
 int  mrgfe_dbg_ctl_final(const mrgfe_dbg_ctl* h, float T[16], int* converged, int* iterations, int* evaluations);
 
+/* ---- bounded best-candidate selection (mrgfe_batch_align_best, loop_detector.cpp:126-145 and :156-160) ---------------------------- */
+/* per pair, the certified fitness interval lower <= getFitnessScore <= upper of the last mrgfe_batch_align_best on this pair list (0 / +inf: the
+ * pair's counted point set was not certain at the selection, so no interval; DBL_MAX / DBL_MAX: no job — not converged or an empty cloud).
+ * MRGFE_ERR_STATE when the last align was not an align_best. */
+int mrgfe_dbg_batch_fit_bounds(const mrgfe_batch* b, double* lower, double* upper);
+/* the product's host selection on given intervals, no GPU needed: state[i] = enum mrgfe_fit_state of every pair (group[i] -1 or in [0, n_groups),
+ * else MRGFE_ERR_INVALID).  A candidate without an upper bound passes upper = +inf. */
+int mrgfe_dbg_select_prune(int n_pairs, const double* lower, const double* upper, const int32_t* converged, const int32_t* group, int n_groups, double score_cap,
+                           int32_t* state);
+
 #ifdef MRGFE_TESTING
 /* hardening hook: the k-th device / pinned allocation of this process from now on (0 = the next one) fails as if the device were out of memory, every
  * later one works again; k < 0 switches the injector off (MRGFE_FAIL_ALLOC_AFTER sets the initial value).  Returns the number of allocations made

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("MRGFE_LIB") or os.path.join(_PKG, "libmrgfe.so")  # M
 
 MRGFE_OK, ERR_INVALID, ERR_HIP, ERR_OVERFLOW, ERR_EMPTY, ERR_STATE = 0, -1, -2, -3, -4, -5
 NDT_HIP, GICP_HIP, SMALL_GICP_HIP, VGICP_HIP, ICP_HIP, PCL_GICP_HIP, PCL_GICP_OMP_HIP, PCL_NDT_HIP = 0, 1, 2, 3, 4, 5, 6, 7
+FIT_EXACT, FIT_PRUNED, FIT_ABOVE_CAP, FIT_SKIPPED = 0, 1, 2, 3  # enum mrgfe_fit_state (mrgfe_batch_align_best)
 SEARCH = {"KDTREE": 0, "DIRECT26": 1, "DIRECT7": 2, "DIRECT1": 3}
 
 
@@ -198,6 +199,8 @@ SIGNATURES = {
     "mrgfe_batch_wait": (C.c_int, [_vp]),
     "mrgfe_batch_num_pairs": (C.c_int, [_vp]),
     "mrgfe_batch_fitness_stats": (C.c_int, [_vp, _dp]),
+    "mrgfe_batch_align_best": (C.c_int, [_vp, C.c_double, C.c_double, _ip, C.c_int, C.POINTER(PairResult), _ip, _ip, _dp]),
+    "mrgfe_batch_select_stats": (C.c_int, [_vp, _dp]),
     "mrgfe_batch_kernel_stats": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_int64), _dp]),
     "mrgfe_reg_kernel_stats": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_int64), _dp]),
     "mrgfe_batch_pair_counts": (C.c_int, [_vp, C.c_int, _dp, _dp]),
@@ -248,6 +251,8 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_ctl_request": (C.c_int, [_vp, C.POINTER(C.c_int), _fp, _dp]),
     "mrgfe_dbg_ctl_result": (C.c_int, [_vp, C.c_double, _dp, _dp, C.c_double]),
     "mrgfe_dbg_ctl_final": (C.c_int, [_vp, _fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mrgfe_dbg_batch_fit_bounds": (C.c_int, [_vp, _dp, _dp]),
+    "mrgfe_dbg_select_prune": (C.c_int, [C.c_int, _dp, _dp, _ip, _ip, C.c_int, C.c_double, _ip]),
 }
 # ... and its two fault injectors, which exist only in the -DMRGFE_TESTING build (libmrgfe_testing.so: tests/faultinject/ runs under MRGFE_LIB=that file)
 TESTING_SIGNATURES = {

@@ -1,5 +1,6 @@
 // csrc/api.cpp — the extern "C" surface declared in include/mrgfe.h.  Thin: argument checks, column-major <-> row-major
 // conversion, and dispatch into the engines.  Never throws; failures set the thread-local message.
+#include <algorithm>
 #include <atomic>
 #include <cfloat>
 #include <condition_variable>
@@ -25,6 +26,7 @@
 #include "ndt_derivatives.h"
 #include "ndt_engine.h"
 #include "nn_grid.h"
+#include "fit_select.h"
 
 using namespace mrgfe;
 
@@ -147,6 +149,8 @@ struct mrgfe_batch {
     std::unordered_map<uint64_t, Keyframe*> store;
     std::vector<uint64_t> pair_key;  // per pair; 0: not from the store
     FitStats   fit_total;             // getFitnessScore passes of the last align(), all waves added up
+    FitSelectStats select_stats;      // the last mrgfe_batch_align_best
+    std::vector<double> fit_lo, fit_hi;  // per pair: the fitness interval of the last mrgfe_batch_align_best (mrgfe_dbg_batch_fit_bounds)
     std::unique_ptr<NdtSnapshotPort> port;  // early fitness passes (mrgfe_batch_align)
     hipEvent_t uploads_done = nullptr;  // recorded on ctx->stream before helper streams read the batch's clouds (upload_cloud is stream-ordered only)
     uint64_t epoch = 1, tick = 0;
@@ -1320,17 +1324,82 @@ int mrgfe_batch_build_targets(mrgfe_batch* b)
 }
 int mrgfe_batch_num_pairs(const mrgfe_batch* b) { return b ? b->ndt->n_pairs() : 0; }
 
-static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results);
+// the selection arguments of mrgfe_batch_align_best
+struct BatchSelect {
+    double         score_cap;
+    const int32_t* group;
+    int            n_groups;
+    int32_t*       state;  // n_pairs
+};
+static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results, const BatchSelect* sel = nullptr);
+
+static int batch_align_timed(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results, const BatchSelect* sel);
 
 int mrgfe_batch_align(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results)
 {
     if (!b || !results) { set_error("mrgfe_batch_align: NULL argument"); return MRGFE_ERR_INVALID; }
+    return batch_align_timed(b, fitness_max_range, results, nullptr);
+}
+
+int mrgfe_batch_align_best(mrgfe_batch* b, double fitness_max_range, double score_cap, const int32_t* group, int n_groups, mrgfe_pair_result* results, int32_t* fit_state,
+                           int32_t* best, double* best_score)
+{
+    if (!b || !results || n_groups < 0 || (n_groups > 0 && (!best || !best_score))) { set_error("mrgfe_batch_align_best: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(b->ctx);
+    const int P = b->ndt->n_pairs();
+    if (P > 0 && !group) { set_error("mrgfe_batch_align_best: NULL group"); return MRGFE_ERR_INVALID; }
+    if (!(fitness_max_range >= 0) || std::isnan(score_cap)) { set_error("mrgfe_batch_align_best: fitness_max_range must be >= 0 and score_cap a number"); return MRGFE_ERR_INVALID; }
+    for (int i = 0; i < P; ++i)
+        if (group[i] < -1 || group[i] >= n_groups) { set_error("mrgfe_batch_align_best: group[%d] = %d is not -1 or in [0, %d)", i, group[i], n_groups); return MRGFE_ERR_INVALID; }
+    std::vector<int32_t> state(static_cast<size_t>(std::max(P, 1)), kFitSkipped);
+    BatchSelect sel{score_cap, group, n_groups, state.data()};
+    MRGFE_TRY(batch_align_timed(b, fitness_max_range, results, &sel));
+    std::vector<double>  fit(static_cast<size_t>(std::max(P, 1)));
+    std::vector<int32_t> conv(static_cast<size_t>(std::max(P, 1)));
+    for (int i = 0; i < P; ++i) { fit[i] = results[i].fitness; conv[i] = results[i].converged; }
+    fit_select_groups(P, fit.data(), conv.data(), group, n_groups, score_cap, best, best_score);
+    if (fit_state) std::memcpy(fit_state, state.data(), sizeof(int32_t) * static_cast<size_t>(P));
+    return MRGFE_OK;
+}
+
+int mrgfe_batch_select_stats(const mrgfe_batch* b, double out[8])
+{
+    if (!b || !out) { set_error("mrgfe_batch_select_stats: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(b->ctx);
+    const FitSelectStats& s = b->select_stats;
+    const double v[8] = {double(s.exact), double(s.pruned), double(s.above_cap), double(s.skipped), double(s.to_sweep), double(s.to_far), s.ms_bound, s.ms_contend};
+    std::memcpy(out, v, sizeof(v));
+    return MRGFE_OK;
+}
+
+int mrgfe_dbg_batch_fit_bounds(const mrgfe_batch* b, double* lower, double* upper)
+{
+    if (!b || !lower || !upper) { set_error("mrgfe_dbg_batch_fit_bounds: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(b->ctx);
+    if (b->fit_lo.size() != static_cast<size_t>(b->ndt->n_pairs())) { set_error("mrgfe_dbg_batch_fit_bounds: no mrgfe_batch_align_best on this pair list"); return MRGFE_ERR_STATE; }
+    std::copy(b->fit_lo.begin(), b->fit_lo.end(), lower);
+    std::copy(b->fit_hi.begin(), b->fit_hi.end(), upper);
+    return MRGFE_OK;
+}
+
+int mrgfe_dbg_select_prune(int n_pairs, const double* lower, const double* upper, const int32_t* converged, const int32_t* group, int n_groups, double score_cap, int32_t* state)
+{
+    if (n_pairs < 0 || n_groups < 0 || (n_pairs > 0 && (!lower || !upper || !converged || !group || !state))) { set_error("mrgfe_dbg_select_prune: bad argument"); return MRGFE_ERR_INVALID; }
+    if (std::isnan(score_cap)) { set_error("mrgfe_dbg_select_prune: score_cap is NaN"); return MRGFE_ERR_INVALID; }
+    for (int i = 0; i < n_pairs; ++i)
+        if (group[i] < -1 || group[i] >= n_groups) { set_error("mrgfe_dbg_select_prune: group[%d] = %d is not -1 or in [0, %d)", i, group[i], n_groups); return MRGFE_ERR_INVALID; }
+    fit_select_prune(n_pairs, lower, upper, converged, group, n_groups, score_cap, state);
+    return MRGFE_OK;
+}
+
+static int batch_align_timed(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results, const BatchSelect* sel)
+{
     MRGFE_LOCK(b->ctx);
     const auto t_start = b->t_queue_set ? b->t_queue : std::chrono::steady_clock::now();
     int st;
     {
-        TraceRange tr("mrgfe_batch_align");
-        st = batch_align_impl(b, fitness_max_range, results);
+        TraceRange tr(sel ? "mrgfe_batch_align_best" : "mrgfe_batch_align");
+        st = batch_align_impl(b, fitness_max_range, results, sel);
     }
     if (st == MRGFE_OK) {
         b->last_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count();
@@ -1351,7 +1420,7 @@ int mrgfe_batch_align(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_resul
     return st;
 }
 
-static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results)
+static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results, const BatchSelect* sel)
 {
     MRGFE_LOCK(b->ctx);
     NdtEngine& e = *b->ndt;
@@ -1359,6 +1428,7 @@ static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair
     const bool gicp = !is_ndt(b->params.method);
     std::vector<char> fit_built;   // targets whose fitness grid is built in this call
     std::vector<char> early_skip;  // pairs whose fitness score was computed beside the alignment rounds
+    if (!sel) { b->fit_lo.clear(); b->fit_hi.clear(); }  // mrgfe_dbg_batch_fit_bounds: intervals of an align_best only
     if (gicp) {
         // GICP_HIP: the candidates of a target share its covariances and correspondence grid, and all LM loops advance
         // together (GicpBatch: one launch per kernel and round for the pairs still running)
@@ -1430,7 +1500,8 @@ static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair
         if (const char* env = std::getenv("MRGFE_EARLY_FIT_MIN_PAIRS")) early_min_pairs = std::max(2, std::atoi(env));
         int early_div = 8;
         if (const char* env = std::getenv("MRGFE_EARLY_FIT_ACTIVE_DIV")) early_div = std::max(1, std::atoi(env));
-        const bool early_on = overlap && P >= early_min_pairs && std::getenv("MRGFE_NO_EARLY_FIT") == nullptr;
+        // (not in mrgfe_batch_align_best: the pass would score pairs exactly before their group's bounds are known)
+        const bool early_on = overlap && !sel && P >= early_min_pairs && std::getenv("MRGFE_NO_EARLY_FIT") == nullptr;
         if (!b->port) b->port.reset(new NdtSnapshotPort());
         NdtSnapshotPort& port = *b->port;  // (its pinned buffer is kept between calls)
         if (early_on) MRGFE_TRY(port.buf.ensure(sizeof(NdtSnapshotHead) + sizeof(NdtSnapshotRec) * size_t(P)));
@@ -1580,12 +1651,50 @@ static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair
         std::vector<NnFitnessJob> jobs;
         std::vector<int>          job_pair;
         int st = MRGFE_OK;
+        if (sel) {
+            for (int i = 0; i < P; ++i) sel->state[i] = kFitSkipped;
+            b->fit_lo.assign(P, DBL_MAX);
+            b->fit_hi.assign(P, DBL_MAX);
+        }
         for (int i = 0; i < P && st == MRGFE_OK; ++i) {
             const NdtPairInfo& p = e.pair(i);
             const NdtTargetInfo& t = e.target(p.target);
             if (t.n == 0 || p.n == 0 || (static_cast<size_t>(i) < early_skip.size() && early_skip[i])) continue;
+            if (sel && sel->group[i] >= 0 && !results[i].converged) continue;  // SKIPPED: never the best, no grid needed for it
             if (!built[p.target]) { st = grids[p.target].build(b->ctx, t.d_pts, t.n, 1.0f, NnGrid::kCrowding1nn, 1); built[p.target] = 1; }
             if (st == MRGFE_OK) { jobs.push_back(grids[p.target].make_fitness_job(p.d_src, p.n, gicp ? &b->gicp_final[size_t(i) * 16] : p.ctl.final_transformation())); job_pair.push_back(i); }
+        }
+        if (sel) {
+            // bounded selection: every job's interval, exact scores only for the candidates that can still win (nn_fitness_select)
+            const size_t J = jobs.size();
+            std::vector<int32_t> jgroup(J), jconv(J), jstate(J);
+            std::vector<double>  fit(J), lo(J), hi(J);
+            for (size_t j = 0; j < J; ++j) { jgroup[j] = sel->group[job_pair[j]]; jconv[j] = results[job_pair[j]].converged; }
+            if (st == MRGFE_OK)
+                st = nn_fitness_select(b->ctx, jobs.data(), J, fitness_max_range, jgroup.data(), sel->n_groups, jconv.data(), sel->score_cap, fit.data(), jstate.data(), lo.data(), hi.data(),
+                                       &b->select_stats);
+            if (st == MRGFE_OK) {
+                for (size_t j = 0; j < J; ++j) {
+                    const int i = job_pair[j];
+                    results[i].fitness = fit[j];
+                    sel->state[i] = jstate[j];
+                    b->fit_lo[i] = lo[j];
+                    b->fit_hi[i] = hi[j];
+                }
+                // pairs without a job are SKIPPED: fitness DBL_MAX (what the full path gives a pair with an empty cloud)
+                FitSelectStats& ss = b->select_stats;
+                ss.exact = ss.pruned = ss.above_cap = ss.skipped = 0;
+                for (int i = 0; i < P; ++i) {
+                    switch (sel->state[i]) {
+                        case kFitExact: ++ss.exact; break;
+                        case kFitPruned: ++ss.pruned; break;
+                        case kFitAboveCap: ++ss.above_cap; break;
+                        default: ++ss.skipped; results[i].fitness = DBL_MAX;
+                    }
+                }
+            }
+            MRGFE_TRY(st);
+            return MRGFE_OK;
         }
         if (st == MRGFE_OK && !jobs.empty()) {
             std::vector<double> fit(jobs.size());

@@ -146,6 +146,21 @@ int nn_fitness_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, dou
 // nearest to T * src[i] (ties: the lowest index) if its squared distance is < max_sq, else -1.  Enqueued on ctx->stream, no host wait.
 int nn_nearest_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_sq);
 
+// What the last nn_fitness_select did: jobs per state, queries left to the sweep / the pyramid walk after the selection, host milliseconds of
+// the bound stage (block, seed, bound sums, the selection) and of the contender stage (sweep, walk, sums).
+struct FitSelectStats {
+    uint64_t exact = 0, pruned = 0, above_cap = 0, skipped = 0, to_sweep = 0, to_far = 0;
+    double   ms_bound = 0, ms_contend = 0;
+};
+// getFitnessScore of every job, exact only where the best-candidate rule still needs it (mrgfe_batch_align_best).  Block pass and seed write a
+// per-query interval lo <= d <= hi (hi: the attained distance in the query's slot); the bound sums give every job [Σlo, Σhi] / count over the
+// same slices and reduction tree as the exact sum (bit-valid, no epsilon) when the counted point sets agree, else no bound; one host wait;
+// fit_select_prune decides per job (group[j] / converged[j], see fit_select.h); the queues of the jobs that need no exact score are emptied and
+// the sweep, the walk and the sum run for the rest.  out_fit[j]: the exact score (EXACT), the lower bound (PRUNED / ABOVE_CAP), DBL_MAX (SKIPPED);
+// out_lo / out_hi: the interval (0 / +inf: none certified).  Two host waits per call.
+int nn_fitness_select(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_range, const int32_t* group, int n_groups, const int32_t* converged, double score_cap,
+                      double* out_fit, int32_t* out_state, double* out_lo, double* out_hi, FitSelectStats* stats = nullptr);
+
 // far pass of the fitness score: 1 = seed + sweep (nn_fit_sweep_kernel), 0 = the pyramid walk for every queued query
 int nn_set_fit_sweep(int mode);
 // diagnostic counters of the seed + sweep pass: 0 off, 1 counters (FitStats::words ...), 2 also phase clocks and a line on stderr

@@ -4,6 +4,7 @@
 // ranges (16 B per candidate) out of a cloud that was reordered cell-major at build time, so neighbouring lanes —
 // which hold spatially neighbouring queries for a LiDAR scan — hit the same cache lines.  HBM/L2 bound, no MFMA.
 #include <atomic>
+#include <chrono>
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
@@ -12,6 +13,7 @@
 
 #include "dev_float.h"
 #include "dev_utils.h"
+#include "fit_select.h"
 #include "nn_device.h"
 #include "nn_grid.h"
 #include "bbox_device.h"
@@ -1082,16 +1084,47 @@ __device__ __forceinline__ void nn_job_transform(const float* __restrict__ T, ui
 // kIdx passes: is the candidate (d, i) better than (best_d, best_i)?  Ties go to the lower index.
 __device__ __forceinline__ unsigned long long nn_key(float d, int32_t i) { return static_cast<unsigned long long>(__float_as_uint(d)) << 32 | static_cast<uint32_t>(i); }
 
+// ---- interval bounds (nn_fitness_select) ---------------------------------------------------------------------------------------
+// A box bound b2 that the passes trust for pruning is trusted with their comparison slack: they skip a box only when b2 > lim * kNnPrune,
+// so the lower bound it certifies is b2 / kNnPrune, taken here as a product with a constant below 1 / kNnPrune = 0.99998 (the rounding of
+// the product is 0.5 ulp, 200 times smaller than the gap).
+constexpr float kNnPruneInvDown = 0.99997f;
+// Lower bound on the squared distance from (x, y, z) to every point outside the query's 3x3x3 block: the quantity finished(2) of
+// nn_level_search forms, ((2 - 1) cell + margin)^2, with the same margin of four binning slacks.
+__device__ __forceinline__ float nn_bound_outside_block(const NnGridDev& g, float x, float y, float z)
+{
+    int c[3];
+    nn_cell_of(g, x, y, z, c);
+    const float m = 4.0f * g.slack;
+    const float t[3] = {x - g.origin[0], y - g.origin[1], z - g.origin[2]};
+    float       margin = INFINITY;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float lo = static_cast<float>(c[a]) * g.cell;
+        margin = fminf(margin, fminf(fmaxf(t[a] - lo - m, 0.0f), fmaxf(lo + g.cell - t[a] - m, 0.0f)));
+    }
+    const float b = static_cast<float>(1) * g.cell + margin;
+    return (b * b) * kNnPruneInvDown;
+}
+
+// the lo array of a kBound pass (its one trailing kernel argument), nullptr without one
+__device__ __forceinline__ float* nn_bound_array() { return nullptr; }
+__device__ __forceinline__ float* nn_bound_array(float* lo) { return lo; }
+
 #ifndef MRGFE_BLOCK_GROUP
 #define MRGFE_BLOCK_GROUP 1
 #endif
 constexpr int kBlockGroup = MRGFE_BLOCK_GROUP;  // lanes per query in the block pass
 // kIdx (all four passes): the correspondence search of nn_nearest_batch — the index of the nearest point is carried beside its distance
 // (ties: the lowest index) in the job's idx_out, a query counts when its squared distance is < max_range (fast_gicp's test) instead of <=.
-template <bool kIdx, int G>
+// kBound (nn_fitness_select): lo[query] also receives a lower bound on the query's squared 1-NN distance — the distance itself for a settled
+// query, else the smaller of what the block found and the bound of everything outside the block (see nn_bound_outside_block).
+// `Lo` is empty without kBound (the kernels keep their arguments and their code) and `float*` with it.
+template <bool kIdx, int G, bool kBound = false, class... Lo>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void nn_fit_block_kernel(const NnFitnessJob* __restrict__ jobs, const uint32_t* __restrict__ job_off, double max_range, float* __restrict__ sqd,
-                                                            uint32_t* __restrict__ pend, uint32_t* __restrict__ pend_cnt)
+                                                            uint32_t* __restrict__ pend, uint32_t* __restrict__ pend_cnt, Lo... lo_arg)
 {
+    float* __restrict__ lo = nn_bound_array(lo_arg...);
     __shared__ NnFitnessJob s_job;
     __shared__ uint32_t     s_pend[kFitPendCap], s_np, s_base;
     nn_load_job(s_job, jobs + blockIdx.y);
@@ -1138,6 +1171,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void n
                     s_job.idx_out[i] = done ? (hit ? bi : -1) : bi;
                 } else {
                     sqd[off + i] = done ? ((bi >= 0 && static_cast<double>(bd) <= max_range) ? bd : kFitNone) : (bi >= 0 ? bd : INFINITY);
+                    if constexpr (kBound) {
+                        const float found = bi >= 0 ? bd : INFINITY;
+                        lo[off + i] = done ? ((bi >= 0 && static_cast<double>(bd) <= max_range) ? bd : kFitNone) : fminf(found, nn_bound_outside_block(g.level[0], x, y, z));
+                    }
                 }
             }
             queue = sub == 0 && !done;
@@ -1215,12 +1252,15 @@ __device__ __forceinline__ float nn_child_lb(const float t[3], int cx, int cy, i
 }
 
 // seed: one lane per queued query; sqd[query] becomes min(what the block gave, the nearest point of the seed cell) — attained —, or the
-// queue entry is flagged kNoSeed and appended to the second queue
-template <bool kIdx>
+// queue entry is flagged kNoSeed and appended to the second queue.
+// kBound (nn_fitness_select): lo[query] = max(lo[query], L), L the smaller of the least box bound over the non-empty nodes the seed inspected on
+// the level it was found on (or the three-block level when there is no seed) and the bound of everything outside those 27 nodes.
+template <bool kIdx, bool kBound = false, class... Lo>
 __global__ __launch_bounds__(256) void nn_fit_seed_kernel(const NnFitnessJob* __restrict__ jobs, const uint32_t* __restrict__ job_off, double max_range, uint32_t* __restrict__ pend,
                                                            const uint32_t* __restrict__ pend_cnt, float* __restrict__ sqd, uint32_t* __restrict__ pend2, uint32_t* __restrict__ pend2_cnt,
-                                                           unsigned long long* __restrict__ stats)
+                                                           unsigned long long* __restrict__ stats, Lo... lo_arg)
 {
+    float* __restrict__ lo = nn_bound_array(lo_arg...);
     const uint32_t np = pend_cnt[blockIdx.y];
     if (blockIdx.x * 256u >= np) return;
     const NnFitnessJob& J = jobs[blockIdx.y];  // uniform: scalar loads
@@ -1258,7 +1298,7 @@ __global__ __launch_bounds__(256) void nn_fit_seed_kernel(const NnFitnessJob* __
                 }
             };
             // candidates of one level: the non-empty children, within one node of the query's, of the parents that cover them; the nearest
-            auto seed_level = [&](const unsigned long long* __restrict__ words, const int pdim[3], int shift, const int cdim[3], float E, float h, int out[3]) {
+            auto seed_level = [&](const unsigned long long* __restrict__ words, const int pdim[3], int shift, const int cdim[3], float E, float h, int out[3], float& lb) {
                 int Ls[3], Hs[3];
 #pragma unroll
                 for (int a = 0; a < 3; ++a) { Ls[a] = max((c[a] >> shift) - 1, 0); Hs[a] = min((c[a] >> shift) + 1, cdim[a] - 1); }
@@ -1275,13 +1315,29 @@ __global__ __launch_bounds__(256) void nn_fit_seed_kernel(const NnFitnessJob* __
                                 if (lb < best) { best = lb; out[0] = cx; out[1] = cy; out[2] = cz; }
                             }
                         }
+                if constexpr (kBound) lb = best;
                 return best < INFINITY;
             };
+            // kBound: everything outside the 27 nodes of edge E (level `shift`) around the query's, cdim nodes per axis; INFINITY when they cover the grid
+            [[maybe_unused]] auto outside27 = [&](int shift, const int cdim[3], float E) {
+                float b = INFINITY;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const int n = c[a] >> shift;
+                    if (n - 1 > 0) b = fminf(b, t[a] - static_cast<float>(n - 1) * E);
+                    if (n + 1 < cdim[a] - 1) b = fminf(b, static_cast<float>(n + 2) * E - t[a]);
+                }
+                b = fmaxf(b - mg, 0.0f);
+                return b * b;
+            };
+            [[maybe_unused]] float L = INFINITY, lb1 = INFINITY, lb2 = INFINITY;
             int  br[3] = {0, 0, 0};  // the brick the seed cell is taken from
-            bool seeded = seed_level(g.occ1, d2, 2, d1, E1, h1, br);
+            bool seeded = seed_level(g.occ1, d2, 2, d1, E1, h1, br, lb1);
+            if constexpr (kBound) if (seeded) L = fminf(lb1, outside27(2, d1, E1));
             if (!seeded) {
                 int  sb[3] = {0, 0, 0};
-                bool found = seed_level(g.occ2, d3, 4, d2, E2, h2, sb);
+                bool found = seed_level(g.occ2, d3, 4, d2, E2, h2, sb, lb2);
+                if constexpr (kBound) if (found) L = fminf(lb2, outside27(4, d2, E2));
                 ++n_seed2;
                 if (!found) {  // blocks: no word above them, so the 27 around the query's one by one
                     ++n_seed3;
@@ -1294,6 +1350,7 @@ __global__ __launch_bounds__(256) void nn_fit_seed_kernel(const NnFitnessJob* __
                                 const float lb = nn_child_lb(t, kx, ky, kz, E3, h3);
                                 if (lb < best) { best = lb; bk[0] = kx; bk[1] = ky; bk[2] = kz; }
                             }
+                    if constexpr (kBound) L = fminf(best, outside27(6, d3, E3));
                     if (best < INFINITY) {
                         nearest_child(as_global(g.occ2)[(static_cast<uint32_t>(bk[2]) * d3[1] + bk[1]) * d3[0] + bk[0]], bk[0], bk[1], bk[2], E2, h2, sb);
                         found = true;
@@ -1334,6 +1391,7 @@ __global__ __launch_bounds__(256) void nn_fit_seed_kernel(const NnFitnessJob* __
                 // far outside the scene) is left to the pyramid walk, with the seed's distance as its bound
                 if (sqrtf(fminf(best, max_sq_f)) > 118.0f * E1) seeded = false;
             }
+            if constexpr (kBound) lo[off + qi] = fmaxf(lo[off + qi], L * kNnPruneInvDown);
             if (!seeded) {
                 noseed = true;
                 ++n_noseed;
@@ -1970,6 +2028,193 @@ int nn_fitness_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, dou
                              "from blocks %llu, none %llu; clocks (thread 0 of every workgroup) seed / bricks / cells / points: %llu %llu %llu %llu\n",
                      static_cast<unsigned long long>(fs.queued), h_stats[0], h_stats[1], h_stats[7], h_stats[8], h_stats[2], h_stats[3], h_stats[4], h_stats[5], h_stats[6], h_stats[9], h_stats[10],
                      h_stats[11], h_stats[12]);
+    return MRGFE_OK;
+}
+
+// ---- bounded best-candidate selection (mrgfe_batch_align_best) -------------------------------------------------------------------
+// The bound sums: nn_fit_sum_kernel's slices and per-thread order, wave_sum and the four-wave combination, over the two ends of every query's
+// interval (lo: the block / seed lower bound, hi: the attained distance in sqd).  An end is counted when it is >= 0 (kFitNone: settled out of
+// range) and <= max_range.  Rounded addition is monotone in each operand, so a fixed tree over lo_i <= d_i <= hi_i gives Σlo <= Σd <= Σhi bit
+// for bit whenever the three counted sets are the same — which the host knows when #lo == #hi, since {hi <= R} ⊆ {d <= R} ⊆ {lo <= R}.
+__global__ __launch_bounds__(256) void nn_fit_bound_sum_kernel(const NnFitnessJob* __restrict__ jobs, const uint32_t* __restrict__ job_off, const float* __restrict__ lo,
+                                                                const float* __restrict__ hi, double max_range, double* __restrict__ partial)
+{
+    __shared__ double   s_sum[2][4];
+    __shared__ uint32_t s_cnt[2][4];
+    const uint32_t n = jobs[blockIdx.y].n, off = job_off[blockIdx.y];
+    double   sum_lo = 0.0, sum_hi = 0.0;
+    uint32_t cnt_lo = 0, cnt_hi = 0;
+    for (uint32_t k = 0; k < kFitSumSlice / 256u; ++k) {
+        const uint32_t i = blockIdx.x * kFitSumSlice + k * 256u + threadIdx.x;
+        if (i < n) {
+            const float a = lo[off + i], b = hi[off + i];
+            if (a >= 0.0f && static_cast<double>(a) <= max_range) { sum_lo += static_cast<double>(a); ++cnt_lo; }
+            if (b >= 0.0f && static_cast<double>(b) <= max_range) { sum_hi += static_cast<double>(b); ++cnt_hi; }
+        }
+    }
+    sum_lo = wave_sum(sum_lo);
+    cnt_lo = wave_sum(cnt_lo);
+    sum_hi = wave_sum(sum_hi);
+    cnt_hi = wave_sum(cnt_hi);
+    if (lane_id() == 0) { s_sum[0][wave_id()] = sum_lo; s_cnt[0][wave_id()] = cnt_lo; s_sum[1][wave_id()] = sum_hi; s_cnt[1][wave_id()] = cnt_hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double* o = partial + 4 * (size_t(blockIdx.y) * gridDim.x + blockIdx.x);
+        o[0] = ((s_sum[0][0] + s_sum[0][1]) + s_sum[0][2]) + s_sum[0][3];
+        o[1] = static_cast<double>(s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3]);
+        o[2] = ((s_sum[1][0] + s_sum[1][1]) + s_sum[1][2]) + s_sum[1][3];
+        o[3] = static_cast<double>(s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3]);
+    }
+}
+
+// nn_fitness_final_kernel's tree over the four columns of the bound partials
+__global__ __launch_bounds__(256) void nn_fitness_bound_final_kernel(const double* __restrict__ partial, uint32_t nblk, double* __restrict__ out)
+{
+    __shared__ double s_v[4][4];
+    const double* part = partial + 4 * size_t(blockIdx.x) * nblk;
+    double v[4] = {0, 0, 0, 0};
+    for (uint32_t i = threadIdx.x; i < nblk; i += 256)
+        for (int c = 0; c < 4; ++c) v[c] += part[4 * i + c];
+    for (int c = 0; c < 4; ++c) v[c] = wave_sum(v[c]);
+    if (lane_id() == 0)
+        for (int c = 0; c < 4; ++c) s_v[c][wave_id()] = v[c];
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int c = 0; c < 4; ++c) out[4 * blockIdx.x + c] = ((s_v[c][0] + s_v[c][1]) + s_v[c][2]) + s_v[c][3];
+}
+
+// the jobs the selection dropped leave no queue behind: the unchanged sweep and walk launches exit at once on blockIdx.x * 256 >= np
+__global__ __launch_bounds__(256) void nn_fit_drop_kernel(const uint32_t* __restrict__ drop, uint32_t count, uint32_t* __restrict__ cnt0, uint32_t* __restrict__ cnt1)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j < count && drop[j]) { cnt0[j] = 0u; cnt1[j] = 0u; }
+}
+
+int nn_fitness_select(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_range, const int32_t* group, int n_groups, const int32_t* converged, double score_cap,
+                      double* out_fit, int32_t* out_state, double* out_lo, double* out_hi, FitSelectStats* stats)
+{
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    FitSelectStats ss;
+    for (size_t j = 0; j < count; ++j) { out_fit[j] = DBL_MAX; out_lo[j] = DBL_MAX; out_hi[j] = DBL_MAX; out_state[j] = kFitExact; }
+    if (stats) *stats = ss;
+    if (count == 0) return MRGFE_OK;
+    if (count > 65535) { set_error("nn_fitness_select: too many jobs"); return MRGFE_ERR_INVALID; }
+    hipStream_t st = ctx->stream;
+    // jobs that need nothing (grouped and not converged) are run with no queries: every pass skips them
+    std::vector<NnFitnessJob> hjobs(jobs, jobs + count);
+    for (size_t j = 0; j < count; ++j)
+        if (group[j] >= 0 && !converged[j]) hjobs[j].n = 0;
+    std::vector<uint32_t> off(count + 1, 0u);
+    uint32_t max_n = 0;
+    for (size_t j = 0; j < count; ++j) {
+        if (uint64_t(off[j]) + hjobs[j].n > 0xfffffff0ull) { set_error("nn_fitness_select: more than 2^32 queries"); return MRGFE_ERR_INVALID; }
+        off[j + 1] = off[j] + hjobs[j].n;
+        max_n = std::max(max_n, hjobs[j].n);
+    }
+    const size_t total = off[count];
+    // the geometry of nn_fitness_batch's launches
+    const bool     small = total < kFitSmallTotal;
+    const uint32_t per_blk = small ? 256u / 8u : 256u / kBlockGroup;
+    const uint32_t want = static_cast<uint32_t>(std::max<size_t>(1, (size_t(ctx->cu_count) * 128 + count - 1) / count));
+    const uint32_t nblk = std::max<uint32_t>(1, std::min<uint32_t>((std::max<uint32_t>(max_n, 1) + per_blk - 1) / per_blk, want));
+    const uint32_t nblk_sum = std::max<uint32_t>(1, (max_n + kFitSumSlice - 1) / kFitSumSlice);
+    // scratch 9: jobs, offsets, queue lengths, drop flags, partial sums (4 per slice: the bound sums; the exact sums use the first 2), results;
+    // 12: one float per query (hi, then the exact distance); 13: the two queues; 14: one float per query (lo)
+    DevBuf &dw = ctx->scratch[9], &dq = ctx->scratch[12], &dp = ctx->scratch[13], &dl = ctx->scratch[14];
+    const size_t jobs_bytes = (sizeof(NnFitnessJob) * count + 255) & ~size_t(255);
+    const size_t off_bytes = (sizeof(uint32_t) * 4 * (count + 1) + 255) & ~size_t(255);
+    MRGFE_TRY(dw.ensure(jobs_bytes + off_bytes + sizeof(double) * 4 * (size_t(nblk_sum) + 1) * count));
+    MRGFE_TRY(dq.ensure(sizeof(float) * std::max<size_t>(total, 1)));
+    MRGFE_TRY(dp.ensure(sizeof(uint32_t) * 2 * std::max<size_t>(total, 1)));
+    MRGFE_TRY(dl.ensure(sizeof(float) * std::max<size_t>(total, 1)));
+    NnFitnessJob* d_jobs = dw.as<NnFitnessJob>();
+    uint32_t*     d_off = reinterpret_cast<uint32_t*>(dw.as<char>() + jobs_bytes);
+    uint32_t*     d_cnt = d_off + count + 1;  // [2][count + 1] queue lengths
+    uint32_t*     d_drop = d_cnt + 2 * (count + 1);
+    double*       d_part = reinterpret_cast<double*>(dw.as<char>() + jobs_bytes + off_bytes);
+    double*       d_res = d_part + 4 * size_t(nblk_sum) * count;
+    uint32_t*     d_pend[2] = {dp.as<uint32_t>(), dp.as<uint32_t>() + total};
+    uint32_t*     d_cnts[2] = {d_cnt, d_cnt + (count + 1)};
+    float*        d_lo = dl.as<float>();
+    const bool    sweep = fit_sweep_mode() != 0;
+    const dim3    grid(nblk, static_cast<uint32_t>(count));
+    MRGFE_HIP_CHECK(hipMemcpyAsync(d_jobs, hjobs.data(), sizeof(NnFitnessJob) * count, hipMemcpyHostToDevice, st));
+    MRGFE_HIP_CHECK(hipMemcpyAsync(d_off, off.data(), sizeof(uint32_t) * (count + 1), hipMemcpyHostToDevice, st));
+    MRGFE_HIP_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * 2 * (count + 1), st));
+    // 1. bounds: block pass and seed, both writing lo beside sqd
+    if (max_n > 0) {
+        if (small) hipLaunchKernelGGL((nn_fit_block_kernel<false, 8, true, float*>), grid, dim3(256), 0, st, d_jobs, d_off, max_range, dq.as<float>(), d_pend[0], d_cnts[0], d_lo);
+        else       hipLaunchKernelGGL((nn_fit_block_kernel<false, kBlockGroup, true, float*>), grid, dim3(256), 0, st, d_jobs, d_off, max_range, dq.as<float>(), d_pend[0], d_cnts[0], d_lo);
+        if (sweep)
+            hipLaunchKernelGGL((nn_fit_seed_kernel<false, true, float*>), grid, dim3(256), 0, st, d_jobs, d_off, max_range, d_pend[0], d_cnts[0], dq.as<float>(), d_pend[1], d_cnts[1],
+                               static_cast<unsigned long long*>(nullptr), d_lo);
+        hipLaunchKernelGGL(nn_fit_bound_sum_kernel, dim3(nblk_sum, static_cast<uint32_t>(count)), dim3(256), 0, st, d_jobs, d_off, d_lo, dq.as<float>(), max_range, d_part);
+        hipLaunchKernelGGL(nn_fitness_bound_final_kernel, dim3(static_cast<uint32_t>(count)), dim3(256), 0, st, d_part, nblk_sum, d_res);
+        MRGFE_HIP_CHECK(hipGetLastError());
+    }
+    std::vector<double>   res(4 * count, 0.0);
+    std::vector<uint32_t> cnts(2 * (count + 1), 0u);
+    if (max_n > 0) {
+        MRGFE_HIP_CHECK(hipMemcpyAsync(res.data(), d_res, sizeof(double) * 4 * count, hipMemcpyDeviceToHost, st));
+        MRGFE_HIP_CHECK(hipMemcpyAsync(cnts.data(), d_cnt, sizeof(uint32_t) * 2 * (count + 1), hipMemcpyDeviceToHost, st));
+        MRGFE_HIP_CHECK(hipStreamSynchronize(st));  // the one extra host wait: the selection needs every job's interval
+    }
+    // 2. the per-job intervals and the selection
+    for (size_t j = 0; j < count; ++j) {
+        const double* r = &res[4 * j];
+        if (r[1] != r[3]) { out_lo[j] = 0.0; out_hi[j] = INFINITY; continue; }  // the counted point set is not certain yet: no bound
+        out_lo[j] = r[1] > 0 ? r[0] / r[1] : DBL_MAX;
+        out_hi[j] = r[3] > 0 ? r[2] / r[3] : DBL_MAX;
+    }
+    fit_select_prune(static_cast<int>(count), out_lo, out_hi, converged, group, n_groups, score_cap, out_state);
+    std::vector<uint32_t> drop(count, 0u);
+    bool any_exact = false;
+    for (size_t j = 0; j < count; ++j) {
+        switch (out_state[j]) {
+            case kFitPruned: out_fit[j] = out_lo[j]; ++ss.pruned; drop[j] = 1; break;
+            case kFitAboveCap: out_fit[j] = out_lo[j]; ++ss.above_cap; drop[j] = 1; break;
+            case kFitSkipped: ++ss.skipped; drop[j] = 1; break;
+            default:
+                ++ss.exact;
+                if (hjobs[j].n > 0) {
+                    any_exact = true;
+                    ss.to_far += sweep ? cnts[count + 1 + j] : cnts[j];
+                    ss.to_sweep += sweep ? cnts[j] - cnts[count + 1 + j] : 0;
+                }
+        }
+    }
+    const auto t1 = clk::now();
+    // 3. contenders: the passes and the sum of nn_fitness_batch, on the queues the selection left
+    if (any_exact) {
+        MRGFE_HIP_CHECK(hipMemcpyAsync(d_drop, drop.data(), sizeof(uint32_t) * count, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(nn_fit_drop_kernel, dim3(static_cast<uint32_t>((count + 255) / 256)), dim3(256), 0, st, d_drop, static_cast<uint32_t>(count), d_cnts[0], d_cnts[1]);
+        if (sweep) {
+            // the walk of the unseeded queries beside the sweep; the fork comes after the drop kernel, so the side stream sees the emptied queues
+            if (!ctx->side) MRGFE_TRY(ctx->make_stream(&ctx->side));
+            for (int e = 0; e < 4; ++e)
+                if (!ctx->ev_side[e]) MRGFE_HIP_CHECK((e == 1 || e == 2) ? hipEventCreate(&ctx->ev_side[e]) : hipEventCreateWithFlags(&ctx->ev_side[e], hipEventDisableTiming));
+            MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[0], st));
+            MRGFE_HIP_CHECK(hipStreamWaitEvent(ctx->side, ctx->ev_side[0], 0));
+            hipLaunchKernelGGL(nn_fit_far_kernel<false>, grid, dim3(256), 0, ctx->side, d_jobs, d_off, max_range, d_pend[1], d_cnts[1], dq.as<float>());
+            MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[3], ctx->side));
+            hipLaunchKernelGGL((nn_fit_sweep_kernel<false, 256, false>), grid, dim3(256), 0, st, d_jobs, d_off, max_range, d_pend[0], d_cnts[0], dq.as<float>(),
+                               static_cast<unsigned long long*>(nullptr), 0);
+            MRGFE_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_side[3], 0));
+        } else {
+            hipLaunchKernelGGL(nn_fit_far_kernel<false>, grid, dim3(256), 0, st, d_jobs, d_off, max_range, d_pend[0], d_cnts[0], dq.as<float>());
+        }
+        hipLaunchKernelGGL(nn_fit_sum_kernel, dim3(nblk_sum, static_cast<uint32_t>(count)), dim3(256), 0, st, d_jobs, d_off, dq.as<float>(), d_part);
+        hipLaunchKernelGGL(nn_fitness_final_kernel, dim3(static_cast<uint32_t>(count)), dim3(256), 0, st, d_part, nblk_sum, d_res);
+        MRGFE_HIP_CHECK(hipGetLastError());
+        MRGFE_HIP_CHECK(hipMemcpyAsync(res.data(), d_res, sizeof(double) * 2 * count, hipMemcpyDeviceToHost, st));
+        MRGFE_HIP_CHECK(hipStreamSynchronize(st));
+        for (size_t j = 0; j < count; ++j)
+            if (out_state[j] == kFitExact && hjobs[j].n > 0 && res[2 * j + 1] > 0) out_fit[j] = res[2 * j] / res[2 * j + 1];
+    }
+    ss.ms_bound = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    ss.ms_contend = std::chrono::duration<double, std::milli>(clk::now() - t1).count();
+    if (stats) *stats = ss;
     return MRGFE_OK;
 }
 

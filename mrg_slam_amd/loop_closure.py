@@ -118,14 +118,19 @@ def _select_best_table(records, idx, valid, groups):
     return [(int(last[k]), float(best[k])) if some[k] else (None, big) for k in range(len(groups))]
 
 
-def match_candidates(matcher_factory, target_cloud, candidate_clouds, guesses, fitness_max_range=float("inf"), group=None, candidate_keys=None):
+def match_candidates(matcher_factory, target_cloud, candidate_clouds, guesses, fitness_max_range=float("inf"), group=None, candidate_keys=None, select="full"):
     """Distributed candidate matching for one new keyframe.
 
     ``matcher_factory()`` returns a ``BatchMatcher`` bound to this rank's GPU (a fresh one, or — to profit from the keyframe
     store — the same cleared one every call); ``target_cloud`` is the new keyframe's cloud
     (registration_->setInputTarget(new_keyframe->cloud), :104), ``candidate_clouds[i]`` / ``guesses[i]`` the candidates and
     their initial guesses (:127-133).  ``candidate_keys[i]`` (optional, non-zero keyframe ids) keep the candidates' clouds
-    and GICP covariances resident on the rank that matched them.  Returns (records ordered by candidate, best index, best score)."""
+    and GICP covariances resident on the rank that matched them.  ``select="bounded"``: each rank scores exactly only the candidates of its
+    block that can still be its block's best (``BatchMatcher.align_best``); a pruned record holds a lower bound strictly above an exact score of
+    the same block, so ``select_best`` over the gathered records returns the same winner and score as with ``"full"``.
+    Returns (records ordered by candidate, best index, best score)."""
+    if select not in ("full", "bounded"):
+        raise ValueError(f"select must be 'full' or 'bounded', not {select!r}")
     import torch.distributed as dist
 
     n = len(candidate_clouds)
@@ -143,7 +148,10 @@ def match_candidates(matcher_factory, target_cloud, candidate_clouds, guesses, f
                 bm.add_pair(t, candidate_clouds[i], guesses[i])
             else:
                 bm.add_pair(t, candidate_clouds[i], guesses[i], key=int(candidate_keys[i]))
-        local = bm.align(fitness_max_range)
+        if select == "bounded":
+            local = bm.align_best(fitness_max_range, np.zeros(len(mine), dtype=np.int32))[0]
+        else:
+            local = bm.align(fitness_max_range)
         local["pair_id"] = mine.astype(np.int32)
     records = gather_records(local, n, group)
     best, score = select_best(records)

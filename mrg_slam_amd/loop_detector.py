@@ -36,6 +36,9 @@ DEFAULTS = {  # config/mrg_slam.yaml:169-179
     "accum_distance_thresh_other_robot": 5.0,
     "fitness_score_max_range": float("inf"),
     "fitness_score_thresh": 1.25,
+    # "bounded": batch 1 of detect_batched scores exactly only the candidates that can still be the best of their (new keyframe, SLAM instance)
+    # group (BatchMatcher.align_best, capped at fitness_score_thresh); the Loop list is the same as with "full"
+    "fitness_selection": "full",
     "use_planar_registration_guess": False,
     "enable_loop_closure_consistency_check": True,
     "loop_closure_consistency_max_delta_trans": 0.3,
@@ -234,7 +237,17 @@ class LoopDetector:
         # ---- batch 1: every (new keyframe, superset candidate) pair, aligned and scored
         pairs1 = [(k, c) for k, cands in enumerate(supersets) for c in cands]
         queue(pairs1)
-        rec1 = bm.align(p["fitness_score_max_range"])
+        if p["fitness_selection"] == "bounded":
+            # groups = (new keyframe, candidate's SLAM instance): the gates below drop whole instances, and within a group a pruned record holds a
+            # lower bound strictly above an exact score of the same group, so best_of over any union of groups is unchanged; a group whose best
+            # exceeds fitness_score_thresh (the cap) yields no loop either way
+            gid = {}
+            group = np.array([gid.setdefault((k, c.slam_uuid), len(gid)) for k, c in pairs1], dtype=np.int32)
+            rec1 = bm.align_best(p["fitness_score_max_range"], group, score_cap=p["fitness_score_thresh"])[0]
+        elif p["fitness_selection"] == "full":
+            rec1 = bm.align(p["fitness_score_max_range"])
+        else:
+            raise ValueError(f"fitness_selection must be 'full' or 'bounded', not {p['fitness_selection']!r}")
         first = np.cumsum([0] + [len(s) for s in supersets])
         results = [[(result_matrix(r), bool(r["converged"]), float(r["fitness"])) for r in rec1[first[k]:first[k + 1]]] for k in range(len(new_keyframes))]
 

@@ -484,6 +484,40 @@ class BatchMatcher:
         check(lib().mrgfe_batch_align(self._h, fitness_max_range, res))
         return results_to_numpy(res, n)
 
+    def align_best(self, max_range: float, group, score_cap: float | None = None):
+        """``mrgfe_batch_align_best``: align as :meth:`align`, then score exactly only the candidates that can still be the best of their group
+        (loop_detector.cpp:126-145).  ``group[i]`` is pair i's group (-1: scored exactly); ``score_cap`` (None: off) is the
+        fitness_score_thresh gate (:156-160).  Returns (records, state, best, best_score): ``state[i]`` one of FIT_EXACT / FIT_PRUNED /
+        FIT_ABOVE_CAP / FIT_SKIPPED, ``best[g]`` a pair index, -1 (no converged candidate) or -2 (the group's best exceeds the cap)."""
+        n = lib().mrgfe_batch_num_pairs(self._h)
+        grp = np.ascontiguousarray(np.asarray(group, dtype=np.int32).reshape(-1))
+        if grp.size != n:
+            raise ValueError(f"group has {grp.size} entries for {n} pairs")
+        n_groups = int(grp.max()) + 1 if n else 0
+        n_groups = max(n_groups, 0)
+        res = (PairResult * max(n, 1))()
+        state = np.empty(max(n, 1), dtype=np.int32)
+        best = np.empty(max(n_groups, 1), dtype=np.int32)
+        best_score = np.empty(max(n_groups, 1), dtype=np.float64)
+        cap = np.finfo(np.float64).max if score_cap is None else float(score_cap)
+        check(lib().mrgfe_batch_align_best(self._h, float(max_range), cap, grp.ctypes.data_as(_ip) if n else None, n_groups, res, state.ctypes.data_as(_ip),
+                                            best.ctypes.data_as(_ip), best_score.ctypes.data_as(_dp)))
+        return results_to_numpy(res, n), state[:n].copy(), best[:n_groups].copy(), best_score[:n_groups].copy()
+
+    def select_stats(self) -> dict:
+        """What the last :meth:`align_best` did (``mrgfe_batch_select_stats``)."""
+        v = (C.c_double * 8)()
+        check(lib().mrgfe_batch_select_stats(self._h, v))
+        keys = ("exact", "pruned", "above_cap", "skipped", "to_sweep", "to_far", "ms_bound", "ms_contend")
+        return dict(zip(keys, [float(x) for x in v]))
+
+    def fit_bounds(self):
+        """(lower, upper) per pair of the last :meth:`align_best` (``mrgfe_dbg_batch_fit_bounds``)."""
+        n = lib().mrgfe_batch_num_pairs(self._h)
+        lo, hi = np.empty(max(n, 1)), np.empty(max(n, 1))
+        check(lib().mrgfe_dbg_batch_fit_bounds(self._h, lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp)))
+        return lo[:n].copy(), hi[:n].copy()
+
     def align_async(self, fitness_max_range: float = -1.0):
         """``mrgfe_batch_align_async``: the align runs on the batch's worker thread; :meth:`wait` returns its records.  Keep two BatchMatchers on two
         contexts in flight to overlap one batch's build and straggler rounds with the other's derivative launches."""
