@@ -176,6 +176,15 @@ struct mrgfe_batch {
     std::unique_ptr<Async> async;
 };
 
+// release a stored keyframe's device buffers and drop it from the store; returns the next entry
+static decltype(mrgfe_batch::store)::iterator store_erase(mrgfe_batch* b, decltype(mrgfe_batch::store)::iterator it)
+{
+    it->second->cloud.release();
+    it->second->cov.release();
+    delete it->second;
+    return b->store.erase(it);
+}
+
 // drop least recently used keyframes that the current batch does not reference until `need` more bytes fit
 static void store_make_room(mrgfe_batch* b, size_t need)
 {
@@ -188,10 +197,7 @@ static void store_make_room(mrgfe_batch* b, size_t need)
         if (!victim) return;  // everything left is in use: the store grows past its cap for this batch
         auto it = b->store.find(victim);
         total -= it->second->bytes();
-        it->second->cloud.release();
-        it->second->cov.release();
-        delete it->second;
-        b->store.erase(it);
+        store_erase(b, it);
     }
 }
 
@@ -1157,11 +1163,11 @@ void mrgfe_batch_destroy(mrgfe_batch* b)
         if (b->early_ctx) mrgfe_ctx_destroy(b->early_ctx);
         if (b->uploads_done) (void)hipEventDestroy(b->uploads_done);
         if (b->port) b->port->buf.release();
-        for (auto& gp : b->gicp_pairs) { gp.cov.release(); gp.corr.release(); gp.mahal.release(); }
+        for (auto& gp : b->gicp_pairs) gp.release();
         delete b->gicp_batch;
         for (auto* g : b->gicp) delete g;
         delete b->ndt;
-        for (auto& kv : b->store) { kv.second->cloud.release(); kv.second->cov.release(); delete kv.second; }
+        for (auto it = b->store.begin(); it != b->store.end();) it = store_erase(b, it);
     }
     delete b;
 }
@@ -1249,10 +1255,7 @@ int mrgfe_batch_add_pair_keyed(mrgfe_batch* b, int target, uint64_t key, const f
         if (n && !xyzi) { set_error("mrgfe_batch_add_pair_keyed: key %llu is not in the store (or has another size) and no cloud was given", static_cast<unsigned long long>(key)); return MRGFE_ERR_INVALID; }
         if (it != b->store.end()) {  // same key, different cloud: replace — unless this batch already uses the old one
             if (it->second->last_epoch == b->epoch) { set_error("mrgfe_batch_add_pair_keyed: key %llu is already used in this batch with %u points", static_cast<unsigned long long>(key), it->second->n); return MRGFE_ERR_INVALID; }
-            it->second->cloud.release();
-            it->second->cov.release();
-            delete it->second;
-            b->store.erase(it);
+            store_erase(b, it);
         }
         store_make_room(b, n * 16 + (!is_ndt(b->params.method) ? n * 48 : 0));
         kf = new (std::nothrow) mrgfe_batch::Keyframe();
@@ -1299,10 +1302,7 @@ int mrgfe_batch_forget(mrgfe_batch* b, uint64_t key)
     for (auto it = b->store.begin(); it != b->store.end();) {
         if (key != 0 && it->first != key) { ++it; continue; }
         if (it->second->last_epoch == b->epoch && !b->pair_key.empty()) { set_error("mrgfe_batch_forget: key %llu is used by the current batch (clear it first)", static_cast<unsigned long long>(it->first)); return MRGFE_ERR_STATE; }
-        it->second->cloud.release();
-        it->second->cov.release();
-        delete it->second;
-        it = b->store.erase(it);
+        it = store_erase(b, it);
     }
     return MRGFE_OK;
 }
@@ -1420,105 +1420,130 @@ static int batch_align_timed(mrgfe_batch* b, double fitness_max_range, mrgfe_pai
     return st;
 }
 
-static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results, const BatchSelect* sel)
+// GICP_HIP: the candidates of a target share its covariances and correspondence grid, and all LM loops advance together (GicpBatch: one
+// launch per kernel and round for the pairs still running); then the records, fitness DBL_MAX until the fitness passes
+static int gicp_align_batch(mrgfe_batch* b, mrgfe_pair_result* results)
 {
-    MRGFE_LOCK(b->ctx);
     NdtEngine& e = *b->ndt;
     const int P = e.n_pairs();
-    const bool gicp = !is_ndt(b->params.method);
-    std::vector<char> fit_built;   // targets whose fitness grid is built in this call
-    std::vector<char> early_skip;  // pairs whose fitness score was computed beside the alignment rounds
-    if (!sel) { b->fit_lo.clear(); b->fit_hi.clear(); }  // mrgfe_dbg_batch_fit_bounds: intervals of an align_best only
-    if (gicp) {
-        // GICP_HIP: the candidates of a target share its covariances and correspondence grid, and all LM loops advance
-        // together (GicpBatch: one launch per kernel and round for the pairs still running)
-        MRGFE_TRY(b->ctx->bind());
-        if (b->gicp.size() < static_cast<size_t>(e.n_targets())) b->gicp.resize(e.n_targets(), nullptr);
-        if (!b->gicp_batch) b->gicp_batch = new GicpBatch(b->ctx);
-        for (size_t i = P; i < b->gicp_pairs.size(); ++i) { b->gicp_pairs[i].cov.release(); b->gicp_pairs[i].corr.release(); b->gicp_pairs[i].mahal.release(); }
-        b->gicp_pairs.resize(P);
-        for (int i = 0; i < P; ++i) {
-            const NdtPairInfo& p = e.pair(i);
-            const NdtTargetInfo& t = e.target(p.target);
-            GicpEngine*& g = b->gicp[p.target];
-            if (!g) {
-                g = new GicpEngine(b->ctx, gicp_params_from(b->params));
-                MRGFE_TRY(g->set_target(t.d_pts, t.n));
-            }
-            GicpBatchPair& bp = b->gicp_pairs[i];
-            bp.target = p.target;
-            bp.d_src = p.d_src;
-            bp.n = p.n;
-            bp.ext_cov = nullptr;
-            bp.ext_cov_k = nullptr;
-            if (static_cast<size_t>(i) < b->pair_key.size() && b->pair_key[i]) {
-                mrgfe_batch::Keyframe* kf = b->store.at(b->pair_key[i]);
-                bp.ext_cov = &kf->cov;
-                bp.ext_cov_k = &kf->cov_k;
-            }
-            std::memcpy(bp.guess, p.guess, sizeof(bp.guess));
+    MRGFE_TRY(b->ctx->bind());
+    if (b->gicp.size() < static_cast<size_t>(e.n_targets())) b->gicp.resize(e.n_targets(), nullptr);
+    if (!b->gicp_batch) b->gicp_batch = new GicpBatch(b->ctx);
+    for (size_t i = P; i < b->gicp_pairs.size(); ++i) b->gicp_pairs[i].release();
+    b->gicp_pairs.resize(P);
+    for (int i = 0; i < P; ++i) {
+        const NdtPairInfo& p = e.pair(i);
+        const NdtTargetInfo& t = e.target(p.target);
+        GicpEngine*& g = b->gicp[p.target];
+        if (!g) {
+            g = new GicpEngine(b->ctx, gicp_params_from(b->params));
+            MRGFE_TRY(g->set_target(t.d_pts, t.n));
         }
-        MRGFE_TRY(b->gicp_batch->align_all(b->gicp, b->gicp_pairs));
-        b->gicp_final.assign(size_t(P) * 16, 0.0f);
-        for (int i = 0; i < P; ++i) {
-            const GicpLmController& c = b->gicp_pairs[i].ctl;
-            mrgfe_pair_result& r = results[i];
-            c.final_transformation(&b->gicp_final[size_t(i) * 16]);
-            row2col(&b->gicp_final[size_t(i) * 16], r.T);
-            std::memcpy(r.H, c.hessian(), sizeof(r.H));
-            r.fitness = DBL_MAX;
-            r.trans_probability = 0.0;
-            r.converged = c.converged() ? 1 : 0;
-            r.iterations = c.iterations();
-            r.evaluations = c.evaluations();
-            r.pair_id = i;
+        GicpBatchPair& bp = b->gicp_pairs[i];
+        bp.target = p.target;
+        bp.d_src = p.d_src;
+        bp.n = p.n;
+        bp.ext_cov = nullptr;
+        bp.ext_cov_k = nullptr;
+        if (static_cast<size_t>(i) < b->pair_key.size() && b->pair_key[i]) {
+            mrgfe_batch::Keyframe* kf = b->store.at(b->pair_key[i]);
+            bp.ext_cov = &kf->cov;
+            bp.ext_cov_k = &kf->cov_k;
         }
-    } else {
-        // getFitnessScore needs an exact-NN grid per distinct target, and those depend on the target clouds only: they are built
-        // on a helper context by a second host thread WHILE the alignment rounds run (their small launches fill the tails of the
-        // derivative kernels), instead of one after the other behind the alignment (64 targets: ~10 ms of a 65 ms step)
-        // One grid is a dozen small launches and half a dozen host waits (bounding box, the adaptive cell size, the scan table): 64
-        // of them in a row took 30 ms of wall time for 4 ms of kernels and outlasted the 17 ms of alignment they were meant to
-        // hide behind.  The targets are dealt to up to four builder threads, each with its own context.
-        std::vector<std::thread> builders;
-        int          build_status = MRGFE_OK;
-        std::string  build_error;
-        std::mutex   build_mu;
-        std::vector<int> todo;  // (outlives the threads: they are joined below)
-        const bool   overlap = fitness_max_range >= 0 && P >= 2 && std::getenv("MRGFE_NO_FIT_OVERLAP") == nullptr;
-        std::unique_ptr<std::atomic<char>[]> grid_ready;  // per target: its fitness grid is complete (set by the builder that made it)
-        auto fail = [&](int st, const std::string& why) { std::lock_guard<std::mutex> g(build_mu); if (build_status == MRGFE_OK) { build_status = st; build_error = why; } };
-        // Everything that can fail with an early return happens BEFORE the first helper thread exists: a joinable std::thread
-        // destroyed by a return would end the process (the SLAM node) instead of reporting the error.
-        // Early fitness pass.  Round 4 ran a wave whenever a sixth of the pairs had finished: the chip is still full of derivative work then, and
-        // the waves only added their fixed costs (config[3], 256 pairs: 27.8 ms without them, 28.7 ms with).  What IS idle is the tail: a few
-        // stragglers line-searching through tens of small rounds (one pair: ~12 us of derivative work on a chip that holds twenty times that).
-        // So ONE pass, started when the pairs still running drop to an eighth of the batch (MRGFE_EARLY_FIT_ACTIVE_DIV), scores every finished
-        // pair on a helper context beside the stragglers' rounds; the stragglers are scored behind the last round as before.  The count comes
-        // from the round plans the device already publishes (no extra kernel until the one snapshot that carries the final transformations).
+        std::memcpy(bp.guess, p.guess, sizeof(bp.guess));
+    }
+    MRGFE_TRY(b->gicp_batch->align_all(b->gicp, b->gicp_pairs));
+    b->gicp_final.assign(size_t(P) * 16, 0.0f);
+    for (int i = 0; i < P; ++i) {
+        const GicpLmController& c = b->gicp_pairs[i].ctl;
+        mrgfe_pair_result& r = results[i];
+        c.final_transformation(&b->gicp_final[size_t(i) * 16]);
+        row2col(&b->gicp_final[size_t(i) * 16], r.T);
+        std::memcpy(r.H, c.hessian(), sizeof(r.H));
+        r.fitness = DBL_MAX;
+        r.trans_probability = 0.0;
+        r.converged = c.converged() ? 1 : 0;
+        r.iterations = c.iterations();
+        r.evaluations = c.evaluations();
+        r.pair_id = i;
+    }
+    return MRGFE_OK;
+}
+
+// The fitness work of an NDT batch that overlaps its alignment rounds.
+// Grid builders: getFitnessScore needs an exact-NN grid per distinct target, and those depend on the target clouds only: they are built on
+// helper contexts by extra host threads WHILE the alignment rounds run (their small launches fill the tails of the derivative kernels), instead
+// of one after the other behind the alignment (64 targets: ~10 ms of a 65 ms step).  One grid is a dozen small launches and half a dozen host
+// waits (bounding box, the adaptive cell size, the scan table): 64 of them in a row took 30 ms of wall time for 4 ms of kernels and outlasted
+// the 17 ms of alignment they were meant to hide behind.  So the targets are dealt to builder threads, each with its own context.
+// Early pass: the rounds of a batch end in a long tail — a few stragglers line-searching while most alignments have finished and the chip idles
+// between their small launches — and getFitnessScore of a finished pair needs nothing but its final transformation.  A second host thread asks
+// the aligning thread for a snapshot (NdtSnapshotPort) and runs the passes of the finished pairs with a complete grid on a helper context beside
+// the remaining rounds.  A pair's score does not depend on the launch it is computed in (nn_fit_sum_kernel's fixed slices), so the records are
+// the same.
+// The destructor joins every thread this object started: no return path can destroy a joinable std::thread, whose destructor would end the
+// process (the SLAM node) instead of reporting the error.
+struct FitOverlap {
+    mrgfe_batch*       b;
+    mrgfe_pair_result* results;
+    double             max_range;
+    bool               early_on = false;
+    std::vector<char>  built;       // per target: its fitness grid is built in this call
+    std::vector<char>  early_done;  // per pair: scored by the early pass
+    std::vector<int>   todo;        // the targets the builders make, in chunks
+    std::unique_ptr<std::atomic<char>[]> grid_ready;  // per target: its fitness grid is complete (set by the builder that made it)
+    std::vector<std::thread> threads;
+    std::mutex         mu;
+    int                status = MRGFE_OK;  // the first error a thread reported, and its text
+    std::string        error;
+
+    ~FitOverlap() { join(); }
+    void fail(int st, const std::string& why)
+    {
+        std::lock_guard<std::mutex> g(mu);
+        if (status == MRGFE_OK) { status = st; error = why; }
+    }
+    void join()
+    {
+        if (b->port) b->port->finished.store(1, std::memory_order_release);  // (align_all says so too when it returns): no snapshot comes
+        for (std::thread& t : threads) t.join();
+        threads.clear();
+    }
+    int start(bool select)
+    {
+        NdtEngine& e = *b->ndt;
+        const int  P = e.n_pairs();
+        const bool overlap = max_range >= 0 && P >= 2 && std::getenv("MRGFE_NO_FIT_OVERLAP") == nullptr;
+        // Round 4 ran an early wave whenever a sixth of the pairs had finished: the chip is still full of derivative work then, and the waves
+        // only added their fixed costs (config[3], 256 pairs: 27.8 ms without them, 28.7 ms with).  What IS idle is the tail: a few stragglers
+        // line-searching through tens of small rounds (one pair: ~12 us of derivative work on a chip that holds twenty times that).  So ONE pass,
+        // started when the pairs still running drop to an eighth of the batch (MRGFE_EARLY_FIT_ACTIVE_DIV), scores every finished pair beside the
+        // stragglers' rounds; the stragglers are scored behind the last round as before.  The count comes from the round plans the device
+        // already publishes (no extra kernel until the one snapshot that carries the final transformations).
         int early_min_pairs = 8;
         if (const char* env = std::getenv("MRGFE_EARLY_FIT_MIN_PAIRS")) early_min_pairs = std::max(2, std::atoi(env));
         int early_div = 8;
         if (const char* env = std::getenv("MRGFE_EARLY_FIT_ACTIVE_DIV")) early_div = std::max(1, std::atoi(env));
         // (not in mrgfe_batch_align_best: the pass would score pairs exactly before their group's bounds are known)
-        const bool early_on = overlap && !sel && P >= early_min_pairs && std::getenv("MRGFE_NO_EARLY_FIT") == nullptr;
+        early_on = overlap && !select && P >= early_min_pairs && std::getenv("MRGFE_NO_EARLY_FIT") == nullptr;
         if (!b->port) b->port.reset(new NdtSnapshotPort());
         NdtSnapshotPort& port = *b->port;  // (its pinned buffer is kept between calls)
         if (early_on) MRGFE_TRY(port.buf.ensure(sizeof(NdtSnapshotHead) + sizeof(NdtSnapshotRec) * size_t(P)));
         if (overlap) {
-            if (fit_built.size() < static_cast<size_t>(e.n_targets())) fit_built.resize(e.n_targets(), 0);
-            if (b->fit_grids.size() < static_cast<size_t>(e.n_targets())) b->fit_grids.resize(e.n_targets());
-            grid_ready.reset(new std::atomic<char>[std::max(1, e.n_targets())]);
-            for (int t = 0; t < e.n_targets(); ++t) grid_ready[t].store(0, std::memory_order_relaxed);
+            const int T = e.n_targets();
+            built.resize(T, 0);
+            if (b->fit_grids.size() < static_cast<size_t>(T)) b->fit_grids.resize(T);
+            grid_ready.reset(new std::atomic<char>[std::max(1, T)]);
+            for (int t = 0; t < T; ++t) grid_ready[t].store(0, std::memory_order_relaxed);
             for (int i = 0; i < P; ++i) {
                 const NdtPairInfo& p = e.pair(i);
-                if (e.target(p.target).n == 0 || p.n == 0 || fit_built[p.target]) continue;
-                fit_built[p.target] = 1;
+                if (e.target(p.target).n == 0 || p.n == 0 || built[p.target]) continue;
+                built[p.target] = 1;
                 todo.push_back(p.target);
             }
-            // ... and each thread builds its targets a chunk at a time, every step of the build one launch over the chunk (NnGridSet)
-            // ONE builder for up to eight chunks, two beyond: a chunk's build is a dozen launches over all its targets, and a second thread's launches only
-            // compete with the first's and with the rounds for the queues (config[3], 64 targets = 4 chunks: 25.9 - 26.2 ms per step with two builders,
+            // Each thread builds its targets a chunk at a time, every step of the build one launch over the chunk (NnGridSet).  ONE builder for up
+            // to eight chunks, two beyond: a chunk's build is a dozen launches over all its targets, and a second thread's launches only compete
+            // with the first's and with the rounds for the queues (config[3], 64 targets = 4 chunks: 25.9 - 26.2 ms per step with two builders,
             // 25.0 - 25.2 with one; the chunk size makes no difference from 8 to 64 targets)
             size_t n_builders = 0, chunk = 16;
             if (const char* env = std::getenv("MRGFE_FIT_BUILDERS")) n_builders = static_cast<size_t>(std::max(1, std::atoi(env)));
@@ -1533,8 +1558,8 @@ static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair
                 b->fit_ctxs.push_back(fc);
             }
             // the early fitness pass runs on a context of its own whose streams have the device's LOWEST priority: the stragglers' small launches
-            // on the batch's stream are dispatched ahead of the pass's workgroups as slots free up (at equal priority the tail's rounds took twice as
-            // long beside the pass: what the overlap gained, the rounds lost)
+            // on the batch's stream are dispatched ahead of the pass's workgroups as slots free up (at equal priority the tail's rounds took twice
+            // as long beside the pass: what the overlap gained, the rounds lost)
             if (early_on && !b->early_ctx && ctx_create_like(b->ctx, &b->early_ctx, -1) != MRGFE_OK) return MRGFE_ERR_HIP;
             // the target clouds reach the device by asynchronous copies (and gathers) on the batch's stream: the helper streams
             // must not read them before those have finished
@@ -1542,7 +1567,8 @@ static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair
             if (!b->uploads_done) MRGFE_HIP_CHECK(hipEventCreateWithFlags(&b->uploads_done, hipEventDisableTiming));
             MRGFE_HIP_CHECK(hipEventRecord(b->uploads_done, b->ctx->stream));
             for (size_t w = 0; w < n_builders; ++w)
-                builders.emplace_back([b, &e, &todo, w, n_builders, n_chunks, chunk, &fail, &grid_ready] {
+                threads.emplace_back([this, w, n_builders, n_chunks, chunk] {
+                    const NdtEngine& e = *b->ndt;
                     mrgfe_ctx* fc = b->fit_ctxs[w];
                     std::lock_guard<std::recursive_mutex> lock(fc->mu);
                     if (fc->bind() != MRGFE_OK) { fail(MRGFE_ERR_HIP, mrgfe_last_error()); return; }
@@ -1566,147 +1592,163 @@ static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair
                     if (hipStreamSynchronize(fc->stream) != hipSuccess) fail(MRGFE_ERR_HIP, "helper stream synchronisation failed");
                 });
         }
-        // Early fitness passes.  The rounds of a batch end in a long tail — a few stragglers line-searching while most alignments have
-        // finished and the chip idles between their small launches — and getFitnessScore of a finished pair needs nothing but its final
-        // transformation.  A second host thread asks the aligning thread for snapshots (NdtSnapshotPort), and whenever enough finished
-        // pairs with a complete grid have accumulated it runs their passes on a helper context beside the remaining rounds.  A pair's
-        // score does not depend on the launch it is computed in (nn_fit_sum_kernel's fixed slices), so the records are the same.
         port.want.store(0);
         port.issued.store(0);
         port.finished.store(0);
-        std::vector<char> early_done(P, 0);
-        std::thread early;
+        early_done.assign(P, 0);
         b->fit_total = FitStats();
-        if (early_on) {
-            port.head()->tag = 0;
-            port.n_active.store(static_cast<uint32_t>(P), std::memory_order_release);
-            early = std::thread([&, P, early_div] {
-                mrgfe_ctx* fc = b->early_ctx;
-                std::lock_guard<std::recursive_mutex> lock(fc->mu);
-                if (fc->bind() != MRGFE_OK) { fail(MRGFE_ERR_HIP, mrgfe_last_error()); return; }
-                const uint32_t threshold = static_cast<uint32_t>(std::max(1, P / early_div));
-                // wait for the tail (or the end of the alignment)
-                while (!port.finished.load(std::memory_order_acquire) && port.n_active.load(std::memory_order_acquire) > threshold) std::this_thread::sleep_for(std::chrono::microseconds(20));
-                if (port.finished.load(std::memory_order_acquire)) return;
-                port.want.store(1, std::memory_order_release);
-                while (port.issued.load(std::memory_order_acquire) == 0 && !port.finished.load(std::memory_order_acquire)) std::this_thread::sleep_for(std::chrono::microseconds(5));
-                const uint32_t tag = port.issued.load(std::memory_order_acquire);
-                if (tag == 0) return;  // finished without a snapshot
-                volatile NdtSnapshotHead* hd = port.head();
-                while (__atomic_load_n(&hd->tag, __ATOMIC_ACQUIRE) != tag) {
-                    if (port.finished.load(std::memory_order_acquire) && __atomic_load_n(&hd->tag, __ATOMIC_ACQUIRE) != tag) return;  // align_all failed before the kernel ran
-                    std::this_thread::sleep_for(std::chrono::microseconds(5));
-                }
-                std::vector<NnFitnessJob> jobs;
-                std::vector<int>          job_pair;
-                const NdtSnapshotRec* recs = port.recs();
-                for (int i = 0; i < P; ++i) {
-                    if (!recs[i].done) continue;
-                    const NdtPairInfo& p = e.pair(i);
-                    if (e.target(p.target).n == 0 || p.n == 0 || !grid_ready[p.target].load(std::memory_order_acquire)) continue;
-                    float T[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
-                    std::memcpy(T, recs[i].T12, sizeof(recs[i].T12));
-                    jobs.push_back(b->fit_grids[p.target].make_fitness_job(p.d_src, p.n, T));
-                    job_pair.push_back(i);
-                }
-                if (jobs.empty()) return;
-                std::vector<double> fit(jobs.size(), 0.0);
-                TraceRange tr("mrgfe early fitness pass");
-                const int st = nn_fitness_batch(fc, jobs.data(), jobs.size(), fitness_max_range, fit.data());
-                if (st != MRGFE_OK) { fail(st, mrgfe_last_error()); return; }
-                b->fit_total.add(fc->fit_stats);
-                for (size_t j = 0; j < jobs.size(); ++j) { results[job_pair[j]].fitness = fit[j]; early_done[job_pair[j]] = 1; }
-            });
+        if (!early_on) return MRGFE_OK;
+        port.head()->tag = 0;
+        port.n_active.store(static_cast<uint32_t>(P), std::memory_order_release);
+        threads.emplace_back([this, P, early_div] {
+            const NdtEngine& e = *b->ndt;
+            NdtSnapshotPort& port = *b->port;
+            mrgfe_ctx* fc = b->early_ctx;
+            std::lock_guard<std::recursive_mutex> lock(fc->mu);
+            if (fc->bind() != MRGFE_OK) { fail(MRGFE_ERR_HIP, mrgfe_last_error()); return; }
+            const uint32_t threshold = static_cast<uint32_t>(std::max(1, P / early_div));
+            // wait for the tail (or the end of the alignment)
+            while (!port.finished.load(std::memory_order_acquire) && port.n_active.load(std::memory_order_acquire) > threshold) std::this_thread::sleep_for(std::chrono::microseconds(20));
+            if (port.finished.load(std::memory_order_acquire)) return;
+            port.want.store(1, std::memory_order_release);
+            while (port.issued.load(std::memory_order_acquire) == 0 && !port.finished.load(std::memory_order_acquire)) std::this_thread::sleep_for(std::chrono::microseconds(5));
+            const uint32_t tag = port.issued.load(std::memory_order_acquire);
+            if (tag == 0) return;  // finished without a snapshot
+            volatile NdtSnapshotHead* hd = port.head();
+            while (__atomic_load_n(&hd->tag, __ATOMIC_ACQUIRE) != tag) {
+                if (port.finished.load(std::memory_order_acquire) && __atomic_load_n(&hd->tag, __ATOMIC_ACQUIRE) != tag) return;  // align_all failed before the kernel ran
+                std::this_thread::sleep_for(std::chrono::microseconds(5));
+            }
+            std::vector<NnFitnessJob> jobs;
+            std::vector<int>          job_pair;
+            const NdtSnapshotRec* recs = port.recs();
+            for (int i = 0; i < P; ++i) {
+                if (!recs[i].done) continue;
+                const NdtPairInfo& p = e.pair(i);
+                if (e.target(p.target).n == 0 || p.n == 0 || !grid_ready[p.target].load(std::memory_order_acquire)) continue;
+                float T[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
+                std::memcpy(T, recs[i].T12, sizeof(recs[i].T12));
+                jobs.push_back(b->fit_grids[p.target].make_fitness_job(p.d_src, p.n, T));
+                job_pair.push_back(i);
+            }
+            if (jobs.empty()) return;
+            std::vector<double> fit(jobs.size(), 0.0);
+            TraceRange tr("mrgfe early fitness pass");
+            const int st = nn_fitness_batch(fc, jobs.data(), jobs.size(), max_range, fit.data());
+            if (st != MRGFE_OK) { fail(st, mrgfe_last_error()); return; }
+            b->fit_total.add(fc->fit_stats);
+            for (size_t j = 0; j < jobs.size(); ++j) { results[job_pair[j]].fitness = fit[j]; early_done[job_pair[j]] = 1; }
+        });
+        return MRGFE_OK;
+    }
+};
+
+// NDT_HIP's records after the rounds; the pairs the early pass scored keep their fitness
+static void ndt_records(const NdtEngine& e, const std::vector<char>& early_done, mrgfe_pair_result* results)
+{
+    for (int i = 0; i < e.n_pairs(); ++i) {
+        const NdtController& c = e.pair(i).ctl;
+        mrgfe_pair_result& r = results[i];
+        row2col(c.final_transformation(), r.T);
+        std::memcpy(r.H, c.hessian(), sizeof(r.H));
+        if (!early_done[i]) r.fitness = DBL_MAX;
+        r.trans_probability = c.trans_probability();
+        r.converged = c.converged() ? 1 : 0;
+        r.iterations = c.iterations();
+        r.evaluations = c.evaluations();
+        r.pair_id = i;
+    }
+}
+
+// nn_fitness_select on the jobs (bounded selection: every job's interval, exact scores only for the candidates that can still win); the pairs
+// without a job are SKIPPED: fitness DBL_MAX (what the full path gives a pair with an empty cloud)
+static int select_fitness(mrgfe_batch* b, double max_range, mrgfe_pair_result* results, const BatchSelect& sel, const std::vector<NnFitnessJob>& jobs, const std::vector<int>& job_pair)
+{
+    const size_t J = jobs.size();
+    std::vector<int32_t> jgroup(J), jconv(J), jstate(J);
+    std::vector<double>  fit(J), lo(J), hi(J);
+    for (size_t j = 0; j < J; ++j) { jgroup[j] = sel.group[job_pair[j]]; jconv[j] = results[job_pair[j]].converged; }
+    MRGFE_TRY(nn_fitness_select(b->ctx, jobs.data(), J, max_range, jgroup.data(), sel.n_groups, jconv.data(), sel.score_cap, fit.data(), jstate.data(), lo.data(), hi.data(),
+                                &b->select_stats));
+    for (size_t j = 0; j < J; ++j) {
+        const int i = job_pair[j];
+        results[i].fitness = fit[j];
+        sel.state[i] = jstate[j];
+        b->fit_lo[i] = lo[j];
+        b->fit_hi[i] = hi[j];
+    }
+    FitSelectStats& ss = b->select_stats;
+    ss.exact = ss.pruned = ss.above_cap = ss.skipped = 0;
+    for (int i = 0; i < b->ndt->n_pairs(); ++i) {
+        switch (sel.state[i]) {
+            case kFitExact: ++ss.exact; break;
+            case kFitPruned: ++ss.pruned; break;
+            case kFitAboveCap: ++ss.above_cap; break;
+            default: ++ss.skipped; results[i].fitness = DBL_MAX;
         }
+    }
+    return MRGFE_OK;
+}
+
+// getFitnessScore of every pair the early pass did not score, in one launch: one exact-NN grid per distinct target (built here unless a builder
+// thread made it, `built`); with `sel` the bounded selection, where grouped pairs that did not converge are SKIPPED (never the best, no grid)
+static int batch_fitness(mrgfe_batch* b, double max_range, mrgfe_pair_result* results, const BatchSelect* sel, std::vector<char>& built, const std::vector<char>& early_skip)
+{
+    TraceRange tr("mrgfe fitness passes");
+    NdtEngine& e = *b->ndt;
+    const int P = e.n_pairs();
+    std::vector<NnGrid>& grids = b->fit_grids;
+    if (grids.size() < static_cast<size_t>(e.n_targets())) grids.resize(e.n_targets());
+    if (built.size() < static_cast<size_t>(e.n_targets())) built.resize(e.n_targets(), 0);
+    if (sel) {
+        std::fill(sel->state, sel->state + P, kFitSkipped);
+        b->fit_lo.assign(P, DBL_MAX);
+        b->fit_hi.assign(P, DBL_MAX);
+    }
+    std::vector<NnFitnessJob> jobs;
+    std::vector<int>          job_pair;
+    for (int i = 0; i < P; ++i) {
+        const NdtPairInfo& p = e.pair(i);
+        const NdtTargetInfo& t = e.target(p.target);
+        if (t.n == 0 || p.n == 0 || (static_cast<size_t>(i) < early_skip.size() && early_skip[i])) continue;
+        if (sel && sel->group[i] >= 0 && !results[i].converged) continue;
+        if (!built[p.target]) { built[p.target] = 1; MRGFE_TRY(grids[p.target].build(b->ctx, t.d_pts, t.n, 1.0f, NnGrid::kCrowding1nn, 1)); }
+        jobs.push_back(grids[p.target].make_fitness_job(p.d_src, p.n, is_ndt(b->params.method) ? p.ctl.final_transformation() : &b->gicp_final[size_t(i) * 16]));
+        job_pair.push_back(i);
+    }
+    if (sel) return select_fitness(b, max_range, results, *sel, jobs, job_pair);
+    if (jobs.empty()) return MRGFE_OK;
+    std::vector<double> fit(jobs.size());
+    MRGFE_TRY(nn_fitness_batch(b->ctx, jobs.data(), jobs.size(), max_range, fit.data()));
+    b->fit_total.add(b->ctx->fit_stats);
+    for (size_t j = 0; j < jobs.size(); ++j) results[job_pair[j]].fitness = fit[j];
+    return MRGFE_OK;
+}
+
+static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results, const BatchSelect* sel)
+{
+    MRGFE_LOCK(b->ctx);
+    std::vector<char> fit_built;   // targets whose fitness grid is built in this call
+    std::vector<char> early_skip;  // pairs whose fitness score was computed beside the alignment rounds
+    if (!sel) { b->fit_lo.clear(); b->fit_hi.clear(); }  // mrgfe_dbg_batch_fit_bounds: intervals of an align_best only
+    if (!is_ndt(b->params.method)) {
+        MRGFE_TRY(gicp_align_batch(b, results));
+    } else {
+        FitOverlap ov{b, results, fitness_max_range};
+        MRGFE_TRY(ov.start(sel != nullptr));
         int align_status;
         {
             TraceRange tr("mrgfe rounds (set_target + align_all)");
-            align_status = e.align_all(early_on ? &port : nullptr);
+            align_status = b->ndt->align_all(ov.early_on ? b->port.get() : nullptr);
         }
-        if (early.joinable()) early.join();
-        for (std::thread& t : builders) t.join();
+        ov.join();
         MRGFE_TRY(align_status);
-        if (build_status != MRGFE_OK) { set_error("%s", build_error.c_str()); return build_status; }
-        for (int i = 0; i < P; ++i) {
-            const NdtController& c = e.pair(i).ctl;
-            mrgfe_pair_result& r = results[i];
-            row2col(c.final_transformation(), r.T);
-            std::memcpy(r.H, c.hessian(), sizeof(r.H));
-            if (!early_done[i]) r.fitness = DBL_MAX;
-            r.trans_probability = c.trans_probability();
-            r.converged = c.converged() ? 1 : 0;
-            r.iterations = c.iterations();
-            r.evaluations = c.evaluations();
-            r.pair_id = i;
-        }
-        early_skip.swap(early_done);
+        if (ov.status != MRGFE_OK) { set_error("%s", ov.error.c_str()); return ov.status; }
+        ndt_records(*b->ndt, ov.early_done, results);
+        fit_built.swap(ov.built);
+        early_skip.swap(ov.early_done);
     }
-    if (fitness_max_range >= 0) {
-        TraceRange tr("mrgfe fitness passes");
-        // getFitnessScore of every pair in one launch: one exact-NN grid per distinct target
-        std::vector<NnGrid>& grids = b->fit_grids;
-        if (grids.size() < static_cast<size_t>(e.n_targets())) grids.resize(e.n_targets());
-        if (fit_built.size() < static_cast<size_t>(e.n_targets())) fit_built.resize(e.n_targets(), 0);
-        std::vector<char>&  built = fit_built;
-        std::vector<NnFitnessJob> jobs;
-        std::vector<int>          job_pair;
-        int st = MRGFE_OK;
-        if (sel) {
-            for (int i = 0; i < P; ++i) sel->state[i] = kFitSkipped;
-            b->fit_lo.assign(P, DBL_MAX);
-            b->fit_hi.assign(P, DBL_MAX);
-        }
-        for (int i = 0; i < P && st == MRGFE_OK; ++i) {
-            const NdtPairInfo& p = e.pair(i);
-            const NdtTargetInfo& t = e.target(p.target);
-            if (t.n == 0 || p.n == 0 || (static_cast<size_t>(i) < early_skip.size() && early_skip[i])) continue;
-            if (sel && sel->group[i] >= 0 && !results[i].converged) continue;  // SKIPPED: never the best, no grid needed for it
-            if (!built[p.target]) { st = grids[p.target].build(b->ctx, t.d_pts, t.n, 1.0f, NnGrid::kCrowding1nn, 1); built[p.target] = 1; }
-            if (st == MRGFE_OK) { jobs.push_back(grids[p.target].make_fitness_job(p.d_src, p.n, gicp ? &b->gicp_final[size_t(i) * 16] : p.ctl.final_transformation())); job_pair.push_back(i); }
-        }
-        if (sel) {
-            // bounded selection: every job's interval, exact scores only for the candidates that can still win (nn_fitness_select)
-            const size_t J = jobs.size();
-            std::vector<int32_t> jgroup(J), jconv(J), jstate(J);
-            std::vector<double>  fit(J), lo(J), hi(J);
-            for (size_t j = 0; j < J; ++j) { jgroup[j] = sel->group[job_pair[j]]; jconv[j] = results[job_pair[j]].converged; }
-            if (st == MRGFE_OK)
-                st = nn_fitness_select(b->ctx, jobs.data(), J, fitness_max_range, jgroup.data(), sel->n_groups, jconv.data(), sel->score_cap, fit.data(), jstate.data(), lo.data(), hi.data(),
-                                       &b->select_stats);
-            if (st == MRGFE_OK) {
-                for (size_t j = 0; j < J; ++j) {
-                    const int i = job_pair[j];
-                    results[i].fitness = fit[j];
-                    sel->state[i] = jstate[j];
-                    b->fit_lo[i] = lo[j];
-                    b->fit_hi[i] = hi[j];
-                }
-                // pairs without a job are SKIPPED: fitness DBL_MAX (what the full path gives a pair with an empty cloud)
-                FitSelectStats& ss = b->select_stats;
-                ss.exact = ss.pruned = ss.above_cap = ss.skipped = 0;
-                for (int i = 0; i < P; ++i) {
-                    switch (sel->state[i]) {
-                        case kFitExact: ++ss.exact; break;
-                        case kFitPruned: ++ss.pruned; break;
-                        case kFitAboveCap: ++ss.above_cap; break;
-                        default: ++ss.skipped; results[i].fitness = DBL_MAX;
-                    }
-                }
-            }
-            MRGFE_TRY(st);
-            return MRGFE_OK;
-        }
-        if (st == MRGFE_OK && !jobs.empty()) {
-            std::vector<double> fit(jobs.size());
-            st = nn_fitness_batch(b->ctx, jobs.data(), jobs.size(), fitness_max_range, fit.data());
-            if (st == MRGFE_OK) {
-                b->fit_total.add(b->ctx->fit_stats);
-                for (size_t j = 0; j < jobs.size(); ++j) results[job_pair[j]].fitness = fit[j];
-            }
-        }
-        MRGFE_TRY(st);
-    }
-    return MRGFE_OK;
+    return fitness_max_range >= 0 ? batch_fitness(b, fitness_max_range, results, sel, fit_built, early_skip) : MRGFE_OK;
 }
 
 int mrgfe_batch_fitness_stats(const mrgfe_batch* b, double out[11])

@@ -176,6 +176,7 @@ struct GicpBatchPair {
     DevBuf*       ext_cov = nullptr;
     int*          ext_cov_k = nullptr;
     GicpLmController ctl;
+    void release() { cov.release(); corr.release(); mahal.release(); }
 };
 class GicpBatch {
    public:

@@ -1836,201 +1836,6 @@ __global__ __launch_bounds__(256) void nn_fitness_final_kernel(const double* __r
     }
 }
 
-static std::atomic<int> g_fit_sweep{-1};  // -1: not read yet
-static int fit_sweep_mode()
-{
-    int v = g_fit_sweep.load(std::memory_order_relaxed);
-    if (v < 0) { const char* e = std::getenv("MRGFE_FIT_SWEEP"); v = e ? (std::atoi(e) != 0 ? 1 : 0) : 1; g_fit_sweep.store(v, std::memory_order_relaxed); }
-    return v;
-}
-int nn_set_fit_sweep(int mode)
-{
-    if (mode == 0 || mode == 1) g_fit_sweep.store(mode, std::memory_order_relaxed);
-    return fit_sweep_mode();
-}
-static std::atomic<int> g_fit_stats{-1};  // -1: not read yet; 0 off, 1 counters, 2 counters + phase clocks and a line on stderr
-static int fit_stats_mode()
-{
-    int v = g_fit_stats.load(std::memory_order_relaxed);
-    if (v < 0) { const char* e = std::getenv("MRGFE_FIT_STATS"); v = e ? std::max(0, std::min(2, std::atoi(e))) : 0; g_fit_stats.store(v, std::memory_order_relaxed); }
-    return v;
-}
-int nn_set_fit_stats(int mode)
-{
-    if (mode >= 0 && mode <= 2) g_fit_stats.store(mode, std::memory_order_relaxed);
-    return fit_stats_mode();
-}
-
-int nn_nearest_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_sq)
-{
-    if (count == 0) return MRGFE_OK;
-    if (count > 65535) { set_error("nn_nearest_batch: too many jobs"); return MRGFE_ERR_INVALID; }
-    hipStream_t st = ctx->stream;
-    std::vector<uint32_t> off(count + 1, 0u);
-    uint32_t max_n = 0;
-    for (size_t j = 0; j < count; ++j) {
-        if (uint64_t(off[j]) + jobs[j].n > 0xfffffff0ull) { set_error("nn_nearest_batch: more than 2^32 queries"); return MRGFE_ERR_INVALID; }
-        if (jobs[j].n && !jobs[j].idx_out) { set_error("nn_nearest_batch: job without an index array"); return MRGFE_ERR_INVALID; }
-        off[j + 1] = off[j] + jobs[j].n;
-        max_n = std::max(max_n, jobs[j].n);
-    }
-    const size_t total = off[count];
-    if (max_n == 0) return MRGFE_OK;
-    // One or a few clouds do not fill the chip with a lane per query (130k queries: 507 workgroups in the block pass, two wavefronts per SIMD
-    // working through dependent loads): eight lanes per query then (161 -> 85 us).  (The sweep stays as it is: 64-query tiles made it slower,
-    // 244 -> 312 us per 130k-query cloud — a launch lasts as long as its widest tile either way; round 4, a rank's shard of 32 pairs: 2.28 ms of
-    // fitness passes with tiles of 256, 2.46 with 128, 2.56 with 64.)
-    const bool     small = total < kFitSmallTotal;
-    const uint32_t per_blk = small ? 256u / 8u : 256u / kBlockGroup;
-    const uint32_t want = static_cast<uint32_t>(std::max<size_t>(1, (size_t(ctx->cu_count) * 128 + count - 1) / count));
-    const uint32_t nblk = std::max<uint32_t>(1, std::min<uint32_t>((max_n + per_blk - 1) / per_blk, want));
-    // the workspaces of nn_fitness_batch (scratch 9: jobs, offsets, queue lengths; 12: one float per query; 13: the two queues)
-    DevBuf &dw = ctx->scratch[9], &dq = ctx->scratch[12], &dp = ctx->scratch[13];
-    const size_t jobs_bytes = (sizeof(NnFitnessJob) * count + 255) & ~size_t(255);
-    const size_t off_bytes = (sizeof(uint32_t) * 3 * (count + 1) + 255) & ~size_t(255);
-    MRGFE_TRY(dw.ensure(jobs_bytes + off_bytes));
-    MRGFE_TRY(dq.ensure(sizeof(float) * total));
-    MRGFE_TRY(dp.ensure(sizeof(uint32_t) * 2 * total));
-    NnFitnessJob* d_jobs = dw.as<NnFitnessJob>();
-    uint32_t*     d_off = reinterpret_cast<uint32_t*>(dw.as<char>() + jobs_bytes);
-    uint32_t*     d_cnt = d_off + count + 1;
-    uint32_t*     d_pend[2] = {dp.as<uint32_t>(), dp.as<uint32_t>() + total};
-    uint32_t*     d_cnts[2] = {d_cnt, d_cnt + (count + 1)};
-    // this function does not wait on the host: the job records (the caller refills its array every round) and the local offset table
-    // go through the context's pinned staging ring, not straight from pageable memory that may be gone when the copy runs
-    MRGFE_TRY(ctx->stage_h2d(d_jobs, jobs, sizeof(NnFitnessJob) * count, st));
-    MRGFE_TRY(ctx->stage_h2d(d_off, off.data(), sizeof(uint32_t) * (count + 1), st));
-    MRGFE_HIP_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * 2 * (count + 1), st));
-    const dim3 grid(nblk, static_cast<uint32_t>(count));
-    if (small) hipLaunchKernelGGL((nn_fit_block_kernel<true, 8>), grid, dim3(256), 0, st, d_jobs, d_off, max_sq, dq.as<float>(), d_pend[0], d_cnts[0]);
-    else       hipLaunchKernelGGL((nn_fit_block_kernel<true, kBlockGroup>), grid, dim3(256), 0, st, d_jobs, d_off, max_sq, dq.as<float>(), d_pend[0], d_cnts[0]);
-    hipLaunchKernelGGL(nn_fit_seed_kernel<true>, grid, dim3(256), 0, st, d_jobs, d_off, max_sq, d_pend[0], d_cnts[0], dq.as<float>(), d_pend[1], d_cnts[1], static_cast<unsigned long long*>(nullptr));
-    // the unseeded queries' pyramid walk beside the sweep, as in nn_fitness_batch
-    if (!ctx->side) MRGFE_TRY(ctx->make_stream(&ctx->side));
-    for (int e = 0; e < 4; ++e)
-        if (!ctx->ev_side[e]) MRGFE_HIP_CHECK((e == 1 || e == 2) ? hipEventCreate(&ctx->ev_side[e]) : hipEventCreateWithFlags(&ctx->ev_side[e], hipEventDisableTiming));
-    MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[0], st));
-    MRGFE_HIP_CHECK(hipStreamWaitEvent(ctx->side, ctx->ev_side[0], 0));
-    hipLaunchKernelGGL(nn_fit_far_kernel<true>, grid, dim3(256), 0, ctx->side, d_jobs, d_off, max_sq, d_pend[1], d_cnts[1], dq.as<float>());
-    MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[3], ctx->side));
-    hipLaunchKernelGGL((nn_fit_sweep_kernel<true, 256, false>), grid, dim3(256), 0, st, d_jobs, d_off, max_sq, d_pend[0], d_cnts[0], dq.as<float>(), static_cast<unsigned long long*>(nullptr), 0);
-    MRGFE_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_side[3], 0));
-    MRGFE_HIP_CHECK(hipGetLastError());
-    return MRGFE_OK;
-}
-
-int nn_fitness_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_range, double* out)
-{
-    for (size_t j = 0; j < count; ++j) out[j] = DBL_MAX;
-    if (count == 0) return MRGFE_OK;
-    if (count > 65535) { set_error("nn_fitness_batch: too many jobs"); return MRGFE_ERR_INVALID; }
-    hipStream_t st = ctx->stream;
-    std::vector<uint32_t> off(count + 1, 0u);
-    uint32_t max_n = 0;
-    for (size_t j = 0; j < count; ++j) {
-        if (uint64_t(off[j]) + jobs[j].n > 0xfffffff0ull) { set_error("nn_fitness_batch: more than 2^32 queries"); return MRGFE_ERR_INVALID; }
-        off[j + 1] = off[j] + jobs[j].n;
-        max_n = std::max(max_n, jobs[j].n);
-    }
-    const size_t total = off[count];
-    if (max_n == 0) return MRGFE_OK;
-    // One or a few clouds do not fill the chip with a lane per query (130k queries: 507 workgroups in the block pass, two wavefronts per SIMD
-    // working through dependent loads): eight lanes per query then (161 -> 85 us).  (The sweep stays as it is: 64-query tiles made it slower,
-    // 244 -> 312 us per 130k-query cloud — a launch lasts as long as its widest tile either way.)
-    const bool     small = total < kFitSmallTotal;
-    const uint32_t per_blk = small ? 256u / 8u : 256u / kBlockGroup;
-    // enough blocks to fill the chip many times over (the far pass is ragged), few enough that each has a few trips
-    const uint32_t want = static_cast<uint32_t>(std::max<size_t>(1, (size_t(ctx->cu_count) * 128 + count - 1) / count));
-    const uint32_t nblk = std::max<uint32_t>(1, std::min<uint32_t>((max_n + per_blk - 1) / per_blk, want));
-    const uint32_t nblk_sum = (max_n + kFitSumSlice - 1) / kFitSumSlice;
-    // scratch 9: jobs, offsets, queue lengths, counters, partial sums; 12: one float per query; 13: the two queues (10 and 11 may
-    // hold the caller's clouds, see mrgfe_calc_fitness_score)
-    DevBuf &dw = ctx->scratch[9], &dq = ctx->scratch[12], &dp = ctx->scratch[13];
-    constexpr size_t kStatBytes = sizeof(unsigned long long) * kSweepStats;
-    const size_t jobs_bytes = (sizeof(NnFitnessJob) * count + 255) & ~size_t(255);
-    const size_t off_bytes = (sizeof(uint32_t) * 3 * (count + 1) + 8 + kStatBytes + 255) & ~size_t(255);
-    MRGFE_TRY(dw.ensure(jobs_bytes + off_bytes + sizeof(double) * 2 * (size_t(nblk_sum) + 1) * count));
-    MRGFE_TRY(dq.ensure(sizeof(float) * total));
-    MRGFE_TRY(dp.ensure(sizeof(uint32_t) * 2 * total));
-    NnFitnessJob* d_jobs = dw.as<NnFitnessJob>();
-    uint32_t*     d_off = reinterpret_cast<uint32_t*>(dw.as<char>() + jobs_bytes);
-    uint32_t*     d_cnt = d_off + count + 1;  // queue lengths after the block pass and after the sweep: [2][count + 1]
-    unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(dw.as<char>() + jobs_bytes + off_bytes - kStatBytes);  // 8-byte aligned
-    double*       d_part = reinterpret_cast<double*>(dw.as<char>() + jobs_bytes + off_bytes);
-    double*       d_res = d_part + 2 * size_t(nblk_sum) * count;
-    uint32_t*     d_pend[2] = {dp.as<uint32_t>(), dp.as<uint32_t>() + total};
-    uint32_t*     d_cnts[2] = {d_cnt, d_cnt + (count + 1)};
-    const bool    sweep = fit_sweep_mode() != 0, counters = fit_stats_mode() != 0;
-    for (auto& e : ctx->ev_fit)
-        if (!e) MRGFE_HIP_CHECK(hipEventCreate(&e));
-    MRGFE_HIP_CHECK(hipMemcpyAsync(d_jobs, jobs, sizeof(NnFitnessJob) * count, hipMemcpyHostToDevice, st));
-    MRGFE_HIP_CHECK(hipMemcpyAsync(d_off, off.data(), sizeof(uint32_t) * (count + 1), hipMemcpyHostToDevice, st));
-    MRGFE_HIP_CHECK(hipMemsetAsync(d_cnt, 0, off_bytes - sizeof(uint32_t) * (count + 1), st));  // the queue lengths and the counters behind them
-    const dim3 grid(nblk, static_cast<uint32_t>(count));
-    bool       side_far = false;
-    MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_fit[0], st));
-    if (small) hipLaunchKernelGGL((nn_fit_block_kernel<false, 8>), grid, dim3(256), 0, st, d_jobs, d_off, max_range, dq.as<float>(), d_pend[0], d_cnts[0]);
-    else       hipLaunchKernelGGL((nn_fit_block_kernel<false, kBlockGroup>), grid, dim3(256), 0, st, d_jobs, d_off, max_range, dq.as<float>(), d_pend[0], d_cnts[0]);
-    MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_fit[1], st));
-    if (sweep) {
-        hipLaunchKernelGGL(nn_fit_seed_kernel<false>, grid, dim3(256), 0, st, d_jobs, d_off, max_range, d_pend[0], d_cnts[0], dq.as<float>(), d_pend[1], d_cnts[1], counters ? d_stats : nullptr);
-        // The unseeded queries (a few hundred of millions: nothing within three blocks) walk the pyramid, a handful of long dependent walks
-        // that occupy a few wavefronts for ~0.25 ms: on a second stream beside the sweep, which leaves them alone (their queue entries are
-        // flagged), instead of behind it.
-        if (!ctx->side) MRGFE_TRY(ctx->make_stream(&ctx->side));
-        for (int e = 0; e < 4; ++e)
-            if (!ctx->ev_side[e]) MRGFE_HIP_CHECK((e == 1 || e == 2) ? hipEventCreate(&ctx->ev_side[e]) : hipEventCreateWithFlags(&ctx->ev_side[e], hipEventDisableTiming));
-        MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[0], st));
-        MRGFE_HIP_CHECK(hipStreamWaitEvent(ctx->side, ctx->ev_side[0], 0));
-        MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[1], ctx->side));
-        hipLaunchKernelGGL(nn_fit_far_kernel<false>, grid, dim3(256), 0, ctx->side, d_jobs, d_off, max_range, d_pend[1], d_cnts[1], dq.as<float>());
-        MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[2], ctx->side));
-        MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[3], ctx->side));
-        if (counters) hipLaunchKernelGGL((nn_fit_sweep_kernel<false, 256, true>), grid, dim3(256), 0, st, d_jobs, d_off, max_range, d_pend[0], d_cnts[0], dq.as<float>(), d_stats, fit_stats_mode() > 1 ? 1 : 0);
-        else          hipLaunchKernelGGL((nn_fit_sweep_kernel<false, 256, false>), grid, dim3(256), 0, st, d_jobs, d_off, max_range, d_pend[0], d_cnts[0], dq.as<float>(), static_cast<unsigned long long*>(nullptr), 0);
-        MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_fit[2], st));
-        MRGFE_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_side[3], 0));
-        side_far = true;
-    } else {
-        MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_fit[2], st));
-        hipLaunchKernelGGL(nn_fit_far_kernel<false>, grid, dim3(256), 0, st, d_jobs, d_off, max_range, d_pend[0], d_cnts[0], dq.as<float>());
-    }
-    MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_fit[3], st));
-    hipLaunchKernelGGL(nn_fit_sum_kernel, dim3(nblk_sum, static_cast<uint32_t>(count)), dim3(256), 0, st, d_jobs, d_off, dq.as<float>(), d_part);
-    hipLaunchKernelGGL(nn_fitness_final_kernel, dim3(static_cast<uint32_t>(count)), dim3(256), 0, st, d_part, nblk_sum, d_res);
-    MRGFE_HIP_CHECK(hipGetLastError());
-    std::vector<double>   res(2 * count);
-    std::vector<uint32_t> cnts(2 * (count + 1));
-    unsigned long long    h_stats[kSweepStats] = {0};
-    MRGFE_HIP_CHECK(hipMemcpyAsync(res.data(), d_res, sizeof(double) * 2 * count, hipMemcpyDeviceToHost, st));
-    MRGFE_HIP_CHECK(hipMemcpyAsync(cnts.data(), d_cnt, sizeof(uint32_t) * 2 * (count + 1), hipMemcpyDeviceToHost, st));
-    if (counters) MRGFE_HIP_CHECK(hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st));
-    MRGFE_HIP_CHECK(hipStreamSynchronize(st));
-    for (size_t j = 0; j < count; ++j)
-        if (res[2 * j + 1] > 0) out[j] = res[2 * j] / res[2 * j + 1];
-    FitStats& fs = ctx->fit_stats;
-    float ms[3] = {0, 0, 0};
-    for (int k = 0; k < 3; ++k) (void)hipEventElapsedTime(&ms[k], ctx->ev_fit[k], ctx->ev_fit[k + 1]);
-    if (side_far) (void)hipEventElapsedTime(&ms[2], ctx->ev_side[1], ctx->ev_side[2]);  // the walk ran beside the sweep: its own duration
-    fs.ms_block = ms[0];
-    fs.ms_sweep = ms[1];
-    fs.ms_far = ms[2];
-    fs.queries = total;
-    fs.queued = fs.queued_far = 0;
-    for (size_t j = 0; j < count; ++j) { fs.queued += cnts[j]; fs.queued_far += sweep ? cnts[count + 1 + j] : cnts[j]; }
-    fs.words = h_stats[0];
-    fs.tested = h_stats[1];
-    fs.cells = h_stats[2];
-    fs.points = h_stats[3];
-    ++fs.calls;
-    if (counters && fit_stats_mode() > 1)
-        std::fprintf(stderr, "[mrgfe] fitness sweep: %llu queued, %llu words, %llu boxes tested, %llu brick entries, %llu cells listed, %llu opened, %llu points; seeds from super-bricks %llu, "
-                             "from blocks %llu, none %llu; clocks (thread 0 of every workgroup) seed / bricks / cells / points: %llu %llu %llu %llu\n",
-                     static_cast<unsigned long long>(fs.queued), h_stats[0], h_stats[1], h_stats[7], h_stats[8], h_stats[2], h_stats[3], h_stats[4], h_stats[5], h_stats[6], h_stats[9], h_stats[10],
-                     h_stats[11], h_stats[12]);
-    return MRGFE_OK;
-}
-
 // ---- bounded best-candidate selection (mrgfe_batch_align_best) -------------------------------------------------------------------
 // The bound sums: nn_fit_sum_kernel's slices and per-thread order, wave_sum and the four-wave combination, over the two ends of every query's
 // interval (lo: the block / seed lower bound, hi: the attained distance in sqd).  An end is counted when it is >= 0 (kFitNone: settled out of
@@ -2090,6 +1895,230 @@ __global__ __launch_bounds__(256) void nn_fit_drop_kernel(const uint32_t* __rest
     if (j < count && drop[j]) { cnt0[j] = 0u; cnt1[j] = 0u; }
 }
 
+static std::atomic<int> g_fit_sweep{-1};  // -1: not read yet
+static int fit_sweep_mode()
+{
+    int v = g_fit_sweep.load(std::memory_order_relaxed);
+    if (v < 0) { const char* e = std::getenv("MRGFE_FIT_SWEEP"); v = e ? (std::atoi(e) != 0 ? 1 : 0) : 1; g_fit_sweep.store(v, std::memory_order_relaxed); }
+    return v;
+}
+int nn_set_fit_sweep(int mode)
+{
+    if (mode == 0 || mode == 1) g_fit_sweep.store(mode, std::memory_order_relaxed);
+    return fit_sweep_mode();
+}
+static std::atomic<int> g_fit_stats{-1};  // -1: not read yet; 0 off, 1 counters, 2 counters + phase clocks and a line on stderr
+static int fit_stats_mode()
+{
+    int v = g_fit_stats.load(std::memory_order_relaxed);
+    if (v < 0) { const char* e = std::getenv("MRGFE_FIT_STATS"); v = e ? std::max(0, std::min(2, std::atoi(e))) : 0; g_fit_stats.store(v, std::memory_order_relaxed); }
+    return v;
+}
+int nn_set_fit_stats(int mode)
+{
+    if (mode >= 0 && mode <= 2) g_fit_stats.store(mode, std::memory_order_relaxed);
+    return fit_stats_mode();
+}
+
+// The launch plan of the fitness passes, shared by nn_nearest_batch, nn_fitness_batch and nn_fitness_select: the job offset table, the geometry,
+// the workspaces and the launch sequences.  Scratch 9: jobs, offsets, queue lengths, sweep counters, drop flags, partial sums, results; 12: one
+// float per query; 13: the two queues; 14: one float per query (lo of the bound passes).  (10 and 11 may hold the caller's clouds, see
+// mrgfe_calc_fitness_score.)
+template <bool kIdx>
+struct FitPlan {
+    mrgfe_ctx*            ctx;
+    hipStream_t           st;
+    size_t                count, total = 0;
+    double                r;      // max_range (max_sq of the correspondence search)
+    bool                  sweep;  // seed + sweep with the walk of the unseeded queries beside it; else the walk of every queued query
+    bool                  diag = false;  // nn_fitness_batch's diagnostics: events ev_fit[0 .. 3] and ev_side[1] / [2], the counters zeroed on load
+    unsigned long long*   counters = nullptr;  // the seed's and the sweep's diagnostic counters (d_stats; fitness passes only)
+    int                   clocks = 0;          // ... and the sweep's phase clocks
+    std::vector<uint32_t> off;  // [count + 1]: each job's first query in the per-query arrays
+    uint32_t              max_n = 0, nblk = 1, nblk_sum = 1;
+    bool                  small = false;
+    NnFitnessJob*         d_jobs = nullptr;
+    uint32_t             *d_off = nullptr, *d_cnt = nullptr, *d_drop = nullptr, *d_pend[2] = {nullptr, nullptr};  // d_cnt: queue lengths [2][count + 1]
+    unsigned long long*   d_stats = nullptr;
+    double               *d_part = nullptr, *d_res = nullptr;
+    float                *d_sqd = nullptr, *d_lo = nullptr;
+
+    FitPlan(mrgfe_ctx* c, size_t n, double range, bool sw) : ctx(c), st(c->stream), count(n), r(range), sweep(sw), off(n + 1, 0u) {}
+    dim3      grid() const { return dim3(nblk, static_cast<uint32_t>(count)); }
+    uint32_t* cnt(int q) const { return d_cnt + size_t(q) * (count + 1); }
+
+    // the offsets and the geometry; `fn` names the caller in the error text
+    int plan(const char* fn, const NnFitnessJob* jobs)
+    {
+        if (count > 65535) { set_error("%s: too many jobs", fn); return MRGFE_ERR_INVALID; }
+        for (size_t j = 0; j < count; ++j) {
+            if (uint64_t(off[j]) + jobs[j].n > 0xfffffff0ull) { set_error("%s: more than 2^32 queries", fn); return MRGFE_ERR_INVALID; }
+            if (kIdx && jobs[j].n && !jobs[j].idx_out) { set_error("%s: job without an index array", fn); return MRGFE_ERR_INVALID; }
+            off[j + 1] = off[j] + jobs[j].n;
+            max_n = std::max(max_n, jobs[j].n);
+        }
+        total = off[count];
+        // One or a few clouds do not fill the chip with a lane per query (130k queries: 507 workgroups in the block pass, two wavefronts per SIMD
+        // working through dependent loads): eight lanes per query then (161 -> 85 us).  (The sweep stays as it is: 64-query tiles made it slower,
+        // 244 -> 312 us per 130k-query cloud — a launch lasts as long as its widest tile either way; round 4, a rank's shard of 32 pairs: 2.28 ms of
+        // fitness passes with tiles of 256, 2.46 with 128, 2.56 with 64.)
+        small = total < kFitSmallTotal;
+        const uint32_t per_blk = small ? 256u / 8u : 256u / kBlockGroup;
+        // enough blocks to fill the chip many times over (the far pass is ragged), few enough that each has a few trips
+        const uint32_t want = static_cast<uint32_t>(std::max<size_t>(1, (size_t(ctx->cu_count) * 128 + count - 1) / count));
+        nblk = std::max<uint32_t>(1, std::min<uint32_t>((std::max<uint32_t>(max_n, 1) + per_blk - 1) / per_blk, want));
+        nblk_sum = std::max<uint32_t>(1, (max_n + kFitSumSlice - 1) / kFitSumSlice);
+        return MRGFE_OK;
+    }
+    // the workspaces for `cols` partial sums per slice (0: no sums, 2: the exact sums, 4: the bound sums, which also need lo); then jobs and
+    // offsets to the device (`staged`: through the context's pinned staging ring), the queue lengths (and with `diag` the counters) zeroed
+    int load(const NnFitnessJob* jobs, int cols, bool staged)
+    {
+        const size_t jobs_bytes = (sizeof(NnFitnessJob) * count + 255) & ~size_t(255);
+        const size_t cnt_bytes = (sizeof(uint32_t) * 3 * (count + 1) + 7) & ~size_t(7);  // offsets, queue lengths; the counters behind are 8-byte aligned
+        const size_t off_bytes = (cnt_bytes + sizeof(unsigned long long) * kSweepStats + sizeof(uint32_t) * count + 255) & ~size_t(255);
+        DevBuf &dw = ctx->scratch[9], &dq = ctx->scratch[12], &dp = ctx->scratch[13], &dl = ctx->scratch[14];
+        MRGFE_TRY(dw.ensure(jobs_bytes + off_bytes + sizeof(double) * cols * (size_t(nblk_sum) + 1) * count));
+        MRGFE_TRY(dq.ensure(sizeof(float) * std::max<size_t>(total, 1)));
+        MRGFE_TRY(dp.ensure(sizeof(uint32_t) * 2 * std::max<size_t>(total, 1)));
+        if (cols == 4) MRGFE_TRY(dl.ensure(sizeof(float) * std::max<size_t>(total, 1)));
+        d_jobs = dw.as<NnFitnessJob>();
+        d_off = reinterpret_cast<uint32_t*>(dw.as<char>() + jobs_bytes);
+        d_cnt = d_off + count + 1;
+        d_stats = reinterpret_cast<unsigned long long*>(dw.as<char>() + jobs_bytes + cnt_bytes);
+        d_drop = reinterpret_cast<uint32_t*>(d_stats + kSweepStats);
+        d_part = reinterpret_cast<double*>(dw.as<char>() + jobs_bytes + off_bytes);
+        d_res = d_part + size_t(cols) * nblk_sum * count;
+        d_pend[0] = dp.as<uint32_t>();
+        d_pend[1] = d_pend[0] + total;
+        d_sqd = dq.as<float>();
+        d_lo = cols == 4 ? dl.as<float>() : nullptr;
+        if (staged) {
+            MRGFE_TRY(ctx->stage_h2d(d_jobs, jobs, sizeof(NnFitnessJob) * count, st));
+            MRGFE_TRY(ctx->stage_h2d(d_off, off.data(), sizeof(uint32_t) * (count + 1), st));
+        } else {
+            MRGFE_HIP_CHECK(hipMemcpyAsync(d_jobs, jobs, sizeof(NnFitnessJob) * count, hipMemcpyHostToDevice, st));
+            MRGFE_HIP_CHECK(hipMemcpyAsync(d_off, off.data(), sizeof(uint32_t) * (count + 1), hipMemcpyHostToDevice, st));
+        }
+        MRGFE_HIP_CHECK(hipMemsetAsync(d_cnt, 0, diag ? reinterpret_cast<char*>(d_part) - reinterpret_cast<char*>(d_cnt) : sizeof(uint32_t) * 2 * (count + 1), st));
+        return MRGFE_OK;
+    }
+    // the block pass, then (with the sweep) the seed; `lo`: nothing, or d_lo for their kBound forms
+    template <bool kBound = false, class... Lo>
+    int near(Lo... lo)
+    {
+        if (diag) MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_fit[0], st));
+        if (small) hipLaunchKernelGGL((nn_fit_block_kernel<kIdx, 8, kBound, Lo...>), grid(), dim3(256), 0, st, d_jobs, d_off, r, d_sqd, d_pend[0], cnt(0), lo...);
+        else       hipLaunchKernelGGL((nn_fit_block_kernel<kIdx, kBlockGroup, kBound, Lo...>), grid(), dim3(256), 0, st, d_jobs, d_off, r, d_sqd, d_pend[0], cnt(0), lo...);
+        if (diag) MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_fit[1], st));
+        if (sweep) hipLaunchKernelGGL((nn_fit_seed_kernel<kIdx, kBound, Lo...>), grid(), dim3(256), 0, st, d_jobs, d_off, r, d_pend[0], cnt(0), d_sqd, d_pend[1], cnt(1), counters, lo...);
+        return MRGFE_OK;
+    }
+    // What the block pass left.  Without the sweep: the pyramid walk of every queued query on the main stream.  With it (after the seed): the
+    // unseeded queries (a few hundred of millions: nothing within three blocks) walk the pyramid, a handful of long dependent walks that occupy a
+    // few wavefronts for ~0.25 ms: on ctx->side beside the sweep, which leaves them alone (their queue entries are flagged), instead of behind
+    // it; the main stream then joins the side stream.
+    int far()
+    {
+        if (kIdx && counters) { set_error("FitPlan: the correspondence sweep has no counter variant"); return MRGFE_ERR_INVALID; }
+        if (!sweep) {
+            if (diag) MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_fit[2], st));
+            hipLaunchKernelGGL(nn_fit_far_kernel<kIdx>, grid(), dim3(256), 0, st, d_jobs, d_off, r, d_pend[0], cnt(0), d_sqd);
+        } else {
+            if (!ctx->side) MRGFE_TRY(ctx->make_stream(&ctx->side));
+            for (int e = 0; e < 4; ++e)
+                if (!ctx->ev_side[e]) MRGFE_HIP_CHECK((e == 1 || e == 2) ? hipEventCreate(&ctx->ev_side[e]) : hipEventCreateWithFlags(&ctx->ev_side[e], hipEventDisableTiming));
+            MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[0], st));
+            MRGFE_HIP_CHECK(hipStreamWaitEvent(ctx->side, ctx->ev_side[0], 0));
+            if (diag) MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[1], ctx->side));
+            hipLaunchKernelGGL(nn_fit_far_kernel<kIdx>, grid(), dim3(256), 0, ctx->side, d_jobs, d_off, r, d_pend[1], cnt(1), d_sqd);
+            if (diag) MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[2], ctx->side));
+            MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[3], ctx->side));
+            if (!counters) hipLaunchKernelGGL((nn_fit_sweep_kernel<kIdx, 256, false>), grid(), dim3(256), 0, st, d_jobs, d_off, r, d_pend[0], cnt(0), d_sqd, counters, 0);
+            else if constexpr (!kIdx) hipLaunchKernelGGL((nn_fit_sweep_kernel<false, 256, true>), grid(), dim3(256), 0, st, d_jobs, d_off, r, d_pend[0], cnt(0), d_sqd, counters, clocks);
+            if (diag) MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_fit[2], st));
+            MRGFE_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_side[3], 0));
+        }
+        if (diag) MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_fit[3], st));
+        return MRGFE_OK;
+    }
+    // the per-job sums ((Σd, #d) with 2 columns, (Σlo, #lo, Σhi, #hi) with 4) to res[cols * count], the queue lengths to cnts[2 * (count + 1)]
+    // if not null and the counters to h_stats when they are on; one host wait
+    int sums(int cols, double* res, uint32_t* cnts, unsigned long long* h_stats = nullptr)
+    {
+        const dim3 g(nblk_sum, static_cast<uint32_t>(count)), g_final(static_cast<uint32_t>(count));
+        if (cols == 4) hipLaunchKernelGGL(nn_fit_bound_sum_kernel, g, dim3(256), 0, st, d_jobs, d_off, d_lo, d_sqd, r, d_part);
+        else           hipLaunchKernelGGL(nn_fit_sum_kernel, g, dim3(256), 0, st, d_jobs, d_off, d_sqd, d_part);
+        if (cols == 4) hipLaunchKernelGGL(nn_fitness_bound_final_kernel, g_final, dim3(256), 0, st, d_part, nblk_sum, d_res);
+        else           hipLaunchKernelGGL(nn_fitness_final_kernel, g_final, dim3(256), 0, st, d_part, nblk_sum, d_res);
+        MRGFE_HIP_CHECK(hipGetLastError());
+        MRGFE_HIP_CHECK(hipMemcpyAsync(res, d_res, sizeof(double) * cols * count, hipMemcpyDeviceToHost, st));
+        if (cnts) MRGFE_HIP_CHECK(hipMemcpyAsync(cnts, d_cnt, sizeof(uint32_t) * 2 * (count + 1), hipMemcpyDeviceToHost, st));
+        if (counters) MRGFE_HIP_CHECK(hipMemcpyAsync(h_stats, d_stats, sizeof(unsigned long long) * kSweepStats, hipMemcpyDeviceToHost, st));
+        MRGFE_HIP_CHECK(hipStreamSynchronize(st));
+        return MRGFE_OK;
+    }
+};
+
+int nn_nearest_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_sq)
+{
+    if (count == 0) return MRGFE_OK;
+    FitPlan<true> fp(ctx, count, max_sq, true);  // seed + sweep whatever fit_sweep_mode() says
+    MRGFE_TRY(fp.plan("nn_nearest_batch", jobs));
+    if (fp.max_n == 0) return MRGFE_OK;
+    // this function does not wait on the host: the job records (the caller refills its array every round) and the local offset table
+    // go through the context's pinned staging ring, not straight from pageable memory that may be gone when the copy runs
+    MRGFE_TRY(fp.load(jobs, 0, true));
+    MRGFE_TRY(fp.near());
+    MRGFE_TRY(fp.far());
+    MRGFE_HIP_CHECK(hipGetLastError());
+    return MRGFE_OK;
+}
+
+int nn_fitness_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_range, double* out)
+{
+    for (size_t j = 0; j < count; ++j) out[j] = DBL_MAX;
+    if (count == 0) return MRGFE_OK;
+    FitPlan<false> fp(ctx, count, max_range, fit_sweep_mode() != 0);
+    MRGFE_TRY(fp.plan("nn_fitness_batch", jobs));
+    if (fp.max_n == 0) return MRGFE_OK;
+    for (auto& e : ctx->ev_fit)
+        if (!e) MRGFE_HIP_CHECK(hipEventCreate(&e));
+    fp.diag = true;
+    MRGFE_TRY(fp.load(jobs, 2, false));
+    fp.counters = fit_stats_mode() != 0 ? fp.d_stats : nullptr;
+    fp.clocks = fit_stats_mode() > 1 ? 1 : 0;
+    MRGFE_TRY(fp.near());
+    MRGFE_TRY(fp.far());
+    std::vector<double>   res(2 * count);
+    std::vector<uint32_t> cnts(2 * (count + 1));
+    unsigned long long    h_stats[kSweepStats] = {0};
+    MRGFE_TRY(fp.sums(2, res.data(), cnts.data(), h_stats));
+    for (size_t j = 0; j < count; ++j)
+        if (res[2 * j + 1] > 0) out[j] = res[2 * j] / res[2 * j + 1];
+    FitStats& fs = ctx->fit_stats;
+    float ms[3] = {0, 0, 0};
+    for (int k = 0; k < 3; ++k) (void)hipEventElapsedTime(&ms[k], ctx->ev_fit[k], ctx->ev_fit[k + 1]);
+    if (fp.sweep) (void)hipEventElapsedTime(&ms[2], ctx->ev_side[1], ctx->ev_side[2]);  // the walk ran beside the sweep: its own duration
+    fs.ms_block = ms[0];
+    fs.ms_sweep = ms[1];
+    fs.ms_far = ms[2];
+    fs.queries = fp.total;
+    fs.queued = fs.queued_far = 0;
+    for (size_t j = 0; j < count; ++j) { fs.queued += cnts[j]; fs.queued_far += fp.sweep ? cnts[count + 1 + j] : cnts[j]; }
+    fs.words = h_stats[0];
+    fs.tested = h_stats[1];
+    fs.cells = h_stats[2];
+    fs.points = h_stats[3];
+    ++fs.calls;
+    if (fp.clocks)
+        std::fprintf(stderr, "[mrgfe] fitness sweep: %llu queued, %llu words, %llu boxes tested, %llu brick entries, %llu cells listed, %llu opened, %llu points; seeds from super-bricks %llu, "
+                             "from blocks %llu, none %llu; clocks (thread 0 of every workgroup) seed / bricks / cells / points: %llu %llu %llu %llu\n",
+                     static_cast<unsigned long long>(fs.queued), h_stats[0], h_stats[1], h_stats[7], h_stats[8], h_stats[2], h_stats[3], h_stats[4], h_stats[5], h_stats[6], h_stats[9], h_stats[10],
+                     h_stats[11], h_stats[12]);
+    return MRGFE_OK;
+}
+
 int nn_fitness_select(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_range, const int32_t* group, int n_groups, const int32_t* converged, double score_cap,
                       double* out_fit, int32_t* out_state, double* out_lo, double* out_hi, FitSelectStats* stats)
 {
@@ -2099,66 +2128,20 @@ int nn_fitness_select(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, do
     for (size_t j = 0; j < count; ++j) { out_fit[j] = DBL_MAX; out_lo[j] = DBL_MAX; out_hi[j] = DBL_MAX; out_state[j] = kFitExact; }
     if (stats) *stats = ss;
     if (count == 0) return MRGFE_OK;
-    if (count > 65535) { set_error("nn_fitness_select: too many jobs"); return MRGFE_ERR_INVALID; }
-    hipStream_t st = ctx->stream;
     // jobs that need nothing (grouped and not converged) are run with no queries: every pass skips them
     std::vector<NnFitnessJob> hjobs(jobs, jobs + count);
     for (size_t j = 0; j < count; ++j)
         if (group[j] >= 0 && !converged[j]) hjobs[j].n = 0;
-    std::vector<uint32_t> off(count + 1, 0u);
-    uint32_t max_n = 0;
-    for (size_t j = 0; j < count; ++j) {
-        if (uint64_t(off[j]) + hjobs[j].n > 0xfffffff0ull) { set_error("nn_fitness_select: more than 2^32 queries"); return MRGFE_ERR_INVALID; }
-        off[j + 1] = off[j] + hjobs[j].n;
-        max_n = std::max(max_n, hjobs[j].n);
-    }
-    const size_t total = off[count];
-    // the geometry of nn_fitness_batch's launches
-    const bool     small = total < kFitSmallTotal;
-    const uint32_t per_blk = small ? 256u / 8u : 256u / kBlockGroup;
-    const uint32_t want = static_cast<uint32_t>(std::max<size_t>(1, (size_t(ctx->cu_count) * 128 + count - 1) / count));
-    const uint32_t nblk = std::max<uint32_t>(1, std::min<uint32_t>((std::max<uint32_t>(max_n, 1) + per_blk - 1) / per_blk, want));
-    const uint32_t nblk_sum = std::max<uint32_t>(1, (max_n + kFitSumSlice - 1) / kFitSumSlice);
-    // scratch 9: jobs, offsets, queue lengths, drop flags, partial sums (4 per slice: the bound sums; the exact sums use the first 2), results;
-    // 12: one float per query (hi, then the exact distance); 13: the two queues; 14: one float per query (lo)
-    DevBuf &dw = ctx->scratch[9], &dq = ctx->scratch[12], &dp = ctx->scratch[13], &dl = ctx->scratch[14];
-    const size_t jobs_bytes = (sizeof(NnFitnessJob) * count + 255) & ~size_t(255);
-    const size_t off_bytes = (sizeof(uint32_t) * 4 * (count + 1) + 255) & ~size_t(255);
-    MRGFE_TRY(dw.ensure(jobs_bytes + off_bytes + sizeof(double) * 4 * (size_t(nblk_sum) + 1) * count));
-    MRGFE_TRY(dq.ensure(sizeof(float) * std::max<size_t>(total, 1)));
-    MRGFE_TRY(dp.ensure(sizeof(uint32_t) * 2 * std::max<size_t>(total, 1)));
-    MRGFE_TRY(dl.ensure(sizeof(float) * std::max<size_t>(total, 1)));
-    NnFitnessJob* d_jobs = dw.as<NnFitnessJob>();
-    uint32_t*     d_off = reinterpret_cast<uint32_t*>(dw.as<char>() + jobs_bytes);
-    uint32_t*     d_cnt = d_off + count + 1;  // [2][count + 1] queue lengths
-    uint32_t*     d_drop = d_cnt + 2 * (count + 1);
-    double*       d_part = reinterpret_cast<double*>(dw.as<char>() + jobs_bytes + off_bytes);
-    double*       d_res = d_part + 4 * size_t(nblk_sum) * count;
-    uint32_t*     d_pend[2] = {dp.as<uint32_t>(), dp.as<uint32_t>() + total};
-    uint32_t*     d_cnts[2] = {d_cnt, d_cnt + (count + 1)};
-    float*        d_lo = dl.as<float>();
-    const bool    sweep = fit_sweep_mode() != 0;
-    const dim3    grid(nblk, static_cast<uint32_t>(count));
-    MRGFE_HIP_CHECK(hipMemcpyAsync(d_jobs, hjobs.data(), sizeof(NnFitnessJob) * count, hipMemcpyHostToDevice, st));
-    MRGFE_HIP_CHECK(hipMemcpyAsync(d_off, off.data(), sizeof(uint32_t) * (count + 1), hipMemcpyHostToDevice, st));
-    MRGFE_HIP_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * 2 * (count + 1), st));
-    // 1. bounds: block pass and seed, both writing lo beside sqd
-    if (max_n > 0) {
-        if (small) hipLaunchKernelGGL((nn_fit_block_kernel<false, 8, true, float*>), grid, dim3(256), 0, st, d_jobs, d_off, max_range, dq.as<float>(), d_pend[0], d_cnts[0], d_lo);
-        else       hipLaunchKernelGGL((nn_fit_block_kernel<false, kBlockGroup, true, float*>), grid, dim3(256), 0, st, d_jobs, d_off, max_range, dq.as<float>(), d_pend[0], d_cnts[0], d_lo);
-        if (sweep)
-            hipLaunchKernelGGL((nn_fit_seed_kernel<false, true, float*>), grid, dim3(256), 0, st, d_jobs, d_off, max_range, d_pend[0], d_cnts[0], dq.as<float>(), d_pend[1], d_cnts[1],
-                               static_cast<unsigned long long*>(nullptr), d_lo);
-        hipLaunchKernelGGL(nn_fit_bound_sum_kernel, dim3(nblk_sum, static_cast<uint32_t>(count)), dim3(256), 0, st, d_jobs, d_off, d_lo, dq.as<float>(), max_range, d_part);
-        hipLaunchKernelGGL(nn_fitness_bound_final_kernel, dim3(static_cast<uint32_t>(count)), dim3(256), 0, st, d_part, nblk_sum, d_res);
-        MRGFE_HIP_CHECK(hipGetLastError());
-    }
+    FitPlan<false> fp(ctx, count, max_range, fit_sweep_mode() != 0);
+    const bool     sweep = fp.sweep;
+    MRGFE_TRY(fp.plan("nn_fitness_select", hjobs.data()));
+    MRGFE_TRY(fp.load(hjobs.data(), 4, false));  // sqd: hi, then the exact distance; the exact sums use the first 2 of the 4 columns
+    // 1. bounds: block pass and seed, both writing lo beside sqd; the one extra host wait: the selection needs every job's interval
     std::vector<double>   res(4 * count, 0.0);
     std::vector<uint32_t> cnts(2 * (count + 1), 0u);
-    if (max_n > 0) {
-        MRGFE_HIP_CHECK(hipMemcpyAsync(res.data(), d_res, sizeof(double) * 4 * count, hipMemcpyDeviceToHost, st));
-        MRGFE_HIP_CHECK(hipMemcpyAsync(cnts.data(), d_cnt, sizeof(uint32_t) * 2 * (count + 1), hipMemcpyDeviceToHost, st));
-        MRGFE_HIP_CHECK(hipStreamSynchronize(st));  // the one extra host wait: the selection needs every job's interval
+    if (fp.max_n > 0) {
+        MRGFE_TRY(fp.near<true>(fp.d_lo));
+        MRGFE_TRY(fp.sums(4, res.data(), cnts.data()));
     }
     // 2. the per-job intervals and the selection
     for (size_t j = 0; j < count; ++j) {
@@ -2185,30 +2168,13 @@ int nn_fitness_select(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, do
         }
     }
     const auto t1 = clk::now();
-    // 3. contenders: the passes and the sum of nn_fitness_batch, on the queues the selection left
+    // 3. contenders: the passes and the sum of nn_fitness_batch on the queues the selection left; the fork to the side stream comes after the
+    // drop kernel, so the walk sees the emptied queues
     if (any_exact) {
-        MRGFE_HIP_CHECK(hipMemcpyAsync(d_drop, drop.data(), sizeof(uint32_t) * count, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(nn_fit_drop_kernel, dim3(static_cast<uint32_t>((count + 255) / 256)), dim3(256), 0, st, d_drop, static_cast<uint32_t>(count), d_cnts[0], d_cnts[1]);
-        if (sweep) {
-            // the walk of the unseeded queries beside the sweep; the fork comes after the drop kernel, so the side stream sees the emptied queues
-            if (!ctx->side) MRGFE_TRY(ctx->make_stream(&ctx->side));
-            for (int e = 0; e < 4; ++e)
-                if (!ctx->ev_side[e]) MRGFE_HIP_CHECK((e == 1 || e == 2) ? hipEventCreate(&ctx->ev_side[e]) : hipEventCreateWithFlags(&ctx->ev_side[e], hipEventDisableTiming));
-            MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[0], st));
-            MRGFE_HIP_CHECK(hipStreamWaitEvent(ctx->side, ctx->ev_side[0], 0));
-            hipLaunchKernelGGL(nn_fit_far_kernel<false>, grid, dim3(256), 0, ctx->side, d_jobs, d_off, max_range, d_pend[1], d_cnts[1], dq.as<float>());
-            MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_side[3], ctx->side));
-            hipLaunchKernelGGL((nn_fit_sweep_kernel<false, 256, false>), grid, dim3(256), 0, st, d_jobs, d_off, max_range, d_pend[0], d_cnts[0], dq.as<float>(),
-                               static_cast<unsigned long long*>(nullptr), 0);
-            MRGFE_HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_side[3], 0));
-        } else {
-            hipLaunchKernelGGL(nn_fit_far_kernel<false>, grid, dim3(256), 0, st, d_jobs, d_off, max_range, d_pend[0], d_cnts[0], dq.as<float>());
-        }
-        hipLaunchKernelGGL(nn_fit_sum_kernel, dim3(nblk_sum, static_cast<uint32_t>(count)), dim3(256), 0, st, d_jobs, d_off, dq.as<float>(), d_part);
-        hipLaunchKernelGGL(nn_fitness_final_kernel, dim3(static_cast<uint32_t>(count)), dim3(256), 0, st, d_part, nblk_sum, d_res);
-        MRGFE_HIP_CHECK(hipGetLastError());
-        MRGFE_HIP_CHECK(hipMemcpyAsync(res.data(), d_res, sizeof(double) * 2 * count, hipMemcpyDeviceToHost, st));
-        MRGFE_HIP_CHECK(hipStreamSynchronize(st));
+        MRGFE_HIP_CHECK(hipMemcpyAsync(fp.d_drop, drop.data(), sizeof(uint32_t) * count, hipMemcpyHostToDevice, fp.st));
+        hipLaunchKernelGGL(nn_fit_drop_kernel, dim3(static_cast<uint32_t>((count + 255) / 256)), dim3(256), 0, fp.st, fp.d_drop, static_cast<uint32_t>(count), fp.cnt(0), fp.cnt(1));
+        MRGFE_TRY(fp.far());
+        MRGFE_TRY(fp.sums(2, res.data(), nullptr));
         for (size_t j = 0; j < count; ++j)
             if (out_state[j] == kFitExact && hjobs[j].n > 0 && res[2 * j + 1] > 0) out_fit[j] = res[2 * j] / res[2 * j + 1];
     }

@@ -96,10 +96,27 @@ def test_config3_bounded_equals_full(config3):
     assert st["pruned"] == n_pruned and st["exact"] + st["pruned"] + st["above_cap"] + st["skipped"] == len(pairs)
 
 
-@pytest.mark.parametrize("max_range", [float("inf"), 1.0, 4.0])
-def test_bounds_hold_the_full_fitness(config3, max_range):
+def _set_sweep(mode):
+    from mrg_slam_amd._lib import lib
+
+    return lib().mrgfe_dbg_set_fit_sweep(mode)
+
+
+@pytest.fixture()
+def sweep_mode():
+    before = _set_sweep(-1)
+    yield
+    _set_sweep(before)
+
+
+# sweep_off: MRGFE_FIT_SWEEP=0 — no seed, no sweep; the bounds come from the block pass alone and every queued contender takes the pyramid walk
+@pytest.mark.parametrize("max_range,sweep_off", [(float("inf"), False), (1.0, False), (4.0, False), (float("inf"), True), (4.0, True)],
+                         ids=["inf", "1.0", "4.0", "inf-sweep_off", "4.0-sweep_off"])
+def test_bounds_hold_the_full_fitness(config3, sweep_mode, max_range, sweep_off):
     from mrg_slam_amd import BatchMatcher
 
+    if sweep_off:
+        assert _set_sweep(0) == 0
     scans, dev, pairs = config3
     ids = list(range(0, len(pairs), 2))
     news = sorted({pairs[i][0] for i in ids})
