@@ -118,6 +118,9 @@ int mrgfe_dbg_select_prune(int n_pairs, const double* lower, const double* upper
  * later one works again; k < 0 switches the injector off (MRGFE_FAIL_ALLOC_AFTER sets the initial value).  Returns the number of allocations made
  * since the previous call: a test sweeps k over a whole entry point and wants an error code from every k, then a correct answer. */
 long   mrgfe_dbg_fail_alloc_after(long k);
+/* the number of device buffers, pinned buffers and arena chunks of this process that are allocated and not yet freed: a test reads it before a sweep,
+ * destroys what the sweep made and wants the same number back ("no leak") */
+long   mrgfe_dbg_live_allocations(void);
 /* test hook: the next mrgfe_node_align fails on that member (the error path without an out-of-memory condition) */
 int    mrgfe_dbg_node_fail_member(mrgfe_node* node, int member);
 #endif /* MRGFE_TESTING */

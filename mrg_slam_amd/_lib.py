@@ -254,10 +254,11 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_batch_fit_bounds": (C.c_int, [_vp, _dp, _dp]),
     "mrgfe_dbg_select_prune": (C.c_int, [C.c_int, _dp, _dp, _ip, _ip, C.c_int, C.c_double, _ip]),
 }
-# ... and its two fault injectors, which exist only in the -DMRGFE_TESTING build (libmrgfe_testing.so: tests/faultinject/ runs under MRGFE_LIB=that file)
+# ... and its fault injectors and their allocation count, which exist only in the -DMRGFE_TESTING build (libmrgfe_testing.so: tests/faultinject/ runs under MRGFE_LIB=that file)
 TESTING_SIGNATURES = {
     "mrgfe_dbg_node_fail_member": (C.c_int, [_vp, C.c_int]),
     "mrgfe_dbg_fail_alloc_after": (C.c_long, [C.c_long]),
+    "mrgfe_dbg_live_allocations": (C.c_long, []),
 }
 TESTING_LIB_PATH = os.path.join(_PKG, "libmrgfe_testing.so")
 

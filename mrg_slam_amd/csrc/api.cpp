@@ -1,5 +1,7 @@
 // csrc/api.cpp — the extern "C" surface declared in include/mrgfe.h.  Thin: argument checks, column-major <-> row-major
-// conversion, and dispatch into the engines.  Never throws; failures set the thread-local message.
+// conversion, and dispatch into the engines.  Failures set the thread-local message and return a code.  No exception crosses the C boundary: the entry points
+// that construct engines, grow host containers or start threads run inside abi_guard (common.h), which turns one into MRGFE_ERR_INVALID and a message.
+// The handles below own their engines, grids and buffers: a *_destroy waits for the handle's worker, takes the context lock, binds the device and deletes.
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
@@ -106,8 +108,8 @@ int check_params(const mrgfe_reg_params* p)
 struct mrgfe_reg {
     mrgfe_ctx*       ctx = nullptr;
     mrgfe_reg_params params;
-    NdtEngine*       ndt = nullptr;
-    GicpEngine*      gicp = nullptr;
+    std::unique_ptr<NdtEngine>  ndt;
+    std::unique_ptr<GicpEngine> gicp;
     DevBuf           tgt, src;            // owned copies of host-supplied clouds
     const void*      d_tgt = nullptr;     // current clouds (owned buffer or caller's device memory)
     const void*      d_src = nullptr;
@@ -127,16 +129,18 @@ struct mrgfe_reg {
 struct mrgfe_batch {
     mrgfe_ctx*       ctx = nullptr;
     mrgfe_reg_params params;
-    NdtEngine*       ndt = nullptr;   // holds the clouds, targets and pairs of the batch for both methods; aligns them for NDT_HIP
-    std::vector<GicpEngine*> gicp;    // GICP_HIP: one engine per target (its covariances and correspondence grid are computed once)
+    // Members go in reverse order of declaration: the helper contexts stand before the engines and grids that were filled on their streams, so they go after
+    // them (every thread that used one has been joined by then: FitOverlap, and mrgfe_batch_destroy for the asynchronous worker).
+    CtxPtr              early_ctx;          // lowest-priority context of the early fitness pass (mrgfe_batch_align)
+    std::vector<CtxPtr> fit_ctxs;           // helper contexts (own stream and workspaces each): the grids are built on them by extra host
+                                            // thread while the alignment rounds run on the batch's context
+    std::unique_ptr<NdtEngine> ndt;   // holds the clouds, targets and pairs of the batch for both methods; aligns them for NDT_HIP
+    std::vector<std::unique_ptr<GicpEngine>> gicp;  // GICP_HIP: one engine per target (its covariances and correspondence grid are computed once)
     std::vector<float>  gicp_final;   // GICP_HIP: row-major final transformation of every pair
-    GicpBatch*          gicp_batch = nullptr;
+    std::unique_ptr<GicpBatch> gicp_batch;
     std::vector<GicpBatchPair> gicp_pairs;  // per-pair device buffers, kept between align calls
     std::vector<NnGrid> fit_grids;  // getFitnessScore grids, one per target; device buffers kept between align calls
     std::vector<std::unique_ptr<NnGridSet>> fit_sets;  // ... which are views into these when the grids were built a chunk of targets at a time
-    mrgfe_ctx* early_ctx = nullptr;         // lowest-priority context of the early fitness pass (mrgfe_batch_align)
-    std::vector<mrgfe_ctx*> fit_ctxs;       // helper contexts (own stream and workspaces each): the grids are built on them by extra host
-                                            // thread while the alignment rounds run on the batch's context
     // keyframe store (mrgfe_batch_add_pair_keyed): packed clouds and GICP covariances by caller-chosen key, resident across clears
     struct Keyframe {
         DevBuf   cloud, cov;
@@ -146,13 +150,13 @@ struct mrgfe_batch {
         uint64_t last_tick = 0;
         size_t   bytes() const { return cloud.cap + cov.cap; }
     };
-    std::unordered_map<uint64_t, Keyframe*> store;
+    std::unordered_map<uint64_t, std::unique_ptr<Keyframe>> store;
     std::vector<uint64_t> pair_key;  // per pair; 0: not from the store
     FitStats   fit_total;             // getFitnessScore passes of the last align(), all waves added up
     FitSelectStats select_stats;      // the last mrgfe_batch_align_best
     std::vector<double> fit_lo, fit_hi;  // per pair: the fitness interval of the last mrgfe_batch_align_best (mrgfe_dbg_batch_fit_bounds)
     std::unique_ptr<NdtSnapshotPort> port;  // early fitness passes (mrgfe_batch_align)
-    hipEvent_t uploads_done = nullptr;  // recorded on ctx->stream before helper streams read the batch's clouds (upload_cloud is stream-ordered only)
+    Event      uploads_done;  // recorded on ctx->stream before helper streams read the batch's clouds (upload_cloud is stream-ordered only)
     uint64_t epoch = 1, tick = 0;
     size_t   store_cap = size_t(16384) << 20;
     // mrgfe_batch_timing: the reference's per-candidate time (loop_detector.cpp:22-34): from the clear that starts queueing a batch to its records
@@ -176,15 +180,6 @@ struct mrgfe_batch {
     std::unique_ptr<Async> async;
 };
 
-// release a stored keyframe's device buffers and drop it from the store; returns the next entry
-static decltype(mrgfe_batch::store)::iterator store_erase(mrgfe_batch* b, decltype(mrgfe_batch::store)::iterator it)
-{
-    it->second->cloud.release();
-    it->second->cov.release();
-    delete it->second;
-    return b->store.erase(it);
-}
-
 // drop least recently used keyframes that the current batch does not reference until `need` more bytes fit
 static void store_make_room(mrgfe_batch* b, size_t need)
 {
@@ -197,7 +192,7 @@ static void store_make_room(mrgfe_batch* b, size_t need)
         if (!victim) return;  // everything left is in use: the store grows past its cap for this batch
         auto it = b->store.find(victim);
         total -= it->second->bytes();
-        store_erase(b, it);
+        b->store.erase(it);
     }
 }
 
@@ -224,23 +219,25 @@ void mrgfe_reg_default_params(int method, mrgfe_reg_params* out)
 
 int mrgfe_reg_create(mrgfe_ctx* ctx, const mrgfe_reg_params* params, mrgfe_reg** out)
 {
-    if (!ctx || !out) { set_error("mrgfe_reg_create: NULL argument"); return MRGFE_ERR_INVALID; }
-    *out = nullptr;
-    MRGFE_TRY(check_params(params));
-    mrgfe_reg* r = new (std::nothrow) mrgfe_reg();
-    if (!r) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-    r->ctx = ctx;
-    r->params = *params;
-    if (is_ndt(params->method)) {
-        r->ndt = new NdtEngine(ctx, ndt_params_from(*params));
-        if (const char* e = std::getenv("MRGFE_FORCE_HASH")) r->ndt->set_force_hash(e[0] == '1');
-    } else {
-        r->gicp = new GicpEngine(ctx, gicp_params_from(*params));
-    }
-    for (int i = 0; i < 16; ++i) r->final_rm[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    for (int i = 0; i < 36; ++i) r->hessian[i] = 0;
-    *out = r;
-    return MRGFE_OK;
+    return abi_guard("mrgfe_reg_create", [&]() -> int {
+        if (!ctx || !out) { set_error("mrgfe_reg_create: NULL argument"); return MRGFE_ERR_INVALID; }
+        *out = nullptr;
+        MRGFE_TRY(check_params(params));
+        std::unique_ptr<mrgfe_reg> r(new (std::nothrow) mrgfe_reg());
+        if (!r) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+        r->ctx = ctx;
+        r->params = *params;
+        if (is_ndt(params->method)) {
+            r->ndt = std::make_unique<NdtEngine>(ctx, ndt_params_from(*params));
+            if (const char* e = std::getenv("MRGFE_FORCE_HASH")) r->ndt->set_force_hash(e[0] == '1');
+        } else {
+            r->gicp = std::make_unique<GicpEngine>(ctx, gicp_params_from(*params));
+        }
+        for (int i = 0; i < 16; ++i) r->final_rm[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+        for (int i = 0; i < 36; ++i) r->hessian[i] = 0;
+        *out = r.release();
+        return MRGFE_OK;
+    });
 }
 
 void mrgfe_reg_destroy(mrgfe_reg* reg)
@@ -248,11 +245,6 @@ void mrgfe_reg_destroy(mrgfe_reg* reg)
     if (!reg) return;
     MRGFE_LOCK(reg->ctx);
     (void)hipSetDevice(reg->ctx->device);
-    delete reg->ndt;
-    delete reg->gicp;
-    reg->nn.release();
-    reg->tgt.release();
-    reg->src.release();
     delete reg;
 }
 
@@ -277,133 +269,147 @@ static int reg_target_changed(mrgfe_reg* reg)
 
 int mrgfe_reg_set_target(mrgfe_reg* reg, const float* xyzi, size_t n, size_t stride_bytes)
 {
-    MRGFE_TRY(check_count(n, "mrgfe_reg_set_target"));
-    if (!reg || (n && !xyzi)) { set_error("mrgfe_reg_set_target: NULL argument"); return MRGFE_ERR_INVALID; }
-    MRGFE_LOCK(reg->ctx);
-    MRGFE_TRY(reg->ctx->bind());
-    // after source_becomes_target the source lives in reg->tgt: give that buffer back to the source (reg->d_src and the GICP engine's d_src_ keep
-    // pointing at it) and upload into the spare one, the only buffer that may be freed and regrown here
-    if (reg->d_src == reg->tgt.p && reg->tgt.p != nullptr) std::swap(reg->src, reg->tgt);
-    MRGFE_TRY(reg->tgt.ensure(std::max<size_t>(n, 1) * 16));
-    MRGFE_TRY(upload_cloud(reg->ctx, xyzi, n, stride_bytes, reg->tgt.p));
-    reg->d_tgt = reg->tgt.p;
-    reg->n_tgt = n;
-    TraceRange tr("mrgfe_reg_set_target");
-    return reg_target_changed(reg);
+    return abi_guard("mrgfe_reg_set_target", [&]() -> int {
+        MRGFE_TRY(check_count(n, "mrgfe_reg_set_target"));
+        if (!reg || (n && !xyzi)) { set_error("mrgfe_reg_set_target: NULL argument"); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(reg->ctx);
+        MRGFE_TRY(reg->ctx->bind());
+        // after source_becomes_target the source lives in reg->tgt: give that buffer back to the source (reg->d_src and the GICP engine's d_src_ keep
+        // pointing at it) and upload into the spare one, the only buffer that may be freed and regrown here
+        if (reg->d_src == reg->tgt.p && reg->tgt.p != nullptr) std::swap(reg->src, reg->tgt);
+        MRGFE_TRY(reg->tgt.ensure(std::max<size_t>(n, 1) * 16));
+        MRGFE_TRY(upload_cloud(reg->ctx, xyzi, n, stride_bytes, reg->tgt.p));
+        reg->d_tgt = reg->tgt.p;
+        reg->n_tgt = n;
+        TraceRange tr("mrgfe_reg_set_target");
+        return reg_target_changed(reg);
+    });
 }
 
 int mrgfe_reg_set_target_device(mrgfe_reg* reg, const void* d_xyzi, size_t n)
 {
-    MRGFE_TRY(check_count(n, "mrgfe_reg_set_target_device"));
-    if (!reg || (n && !d_xyzi)) { set_error("mrgfe_reg_set_target_device: NULL argument"); return MRGFE_ERR_INVALID; }
-    MRGFE_LOCK(reg->ctx);
-    MRGFE_TRY(reg->ctx->bind());
-    reg->d_tgt = d_xyzi;
-    reg->n_tgt = n;
-    return reg_target_changed(reg);
+    return abi_guard("mrgfe_reg_set_target_device", [&]() -> int {
+        MRGFE_TRY(check_count(n, "mrgfe_reg_set_target_device"));
+        if (!reg || (n && !d_xyzi)) { set_error("mrgfe_reg_set_target_device: NULL argument"); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(reg->ctx);
+        MRGFE_TRY(reg->ctx->bind());
+        reg->d_tgt = d_xyzi;
+        reg->n_tgt = n;
+        return reg_target_changed(reg);
+    });
 }
 
 int mrgfe_reg_set_source(mrgfe_reg* reg, const float* xyzi, size_t n, size_t stride_bytes)
 {
-    MRGFE_TRY(check_count(n, "mrgfe_reg_set_source"));
-    if (!reg || (n && !xyzi)) { set_error("mrgfe_reg_set_source: NULL argument"); return MRGFE_ERR_INVALID; }
-    MRGFE_LOCK(reg->ctx);
-    MRGFE_TRY(reg->ctx->bind());
-    MRGFE_TRY(reg->src.ensure(std::max<size_t>(n, 1) * 16));
-    MRGFE_TRY(upload_cloud(reg->ctx, xyzi, n, stride_bytes, reg->src.p));
-    reg->d_src = reg->src.p;
-    reg->n_src = n;
-    reg->has_source = true;
-    if (reg->gicp) MRGFE_TRY(reg->gicp->set_source(reg->d_src, reg->n_src));
-    return MRGFE_OK;
+    return abi_guard("mrgfe_reg_set_source", [&]() -> int {
+        MRGFE_TRY(check_count(n, "mrgfe_reg_set_source"));
+        if (!reg || (n && !xyzi)) { set_error("mrgfe_reg_set_source: NULL argument"); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(reg->ctx);
+        MRGFE_TRY(reg->ctx->bind());
+        MRGFE_TRY(reg->src.ensure(std::max<size_t>(n, 1) * 16));
+        MRGFE_TRY(upload_cloud(reg->ctx, xyzi, n, stride_bytes, reg->src.p));
+        reg->d_src = reg->src.p;
+        reg->n_src = n;
+        reg->has_source = true;
+        if (reg->gicp) MRGFE_TRY(reg->gicp->set_source(reg->d_src, reg->n_src));
+        return MRGFE_OK;
+    });
 }
 
 int mrgfe_reg_set_source_device(mrgfe_reg* reg, const void* d_xyzi, size_t n)
 {
-    MRGFE_TRY(check_count(n, "mrgfe_reg_set_source_device"));
-    if (!reg || (n && !d_xyzi)) { set_error("mrgfe_reg_set_source_device: NULL argument"); return MRGFE_ERR_INVALID; }
-    MRGFE_LOCK(reg->ctx);
-    MRGFE_TRY(reg->ctx->bind());
-    reg->d_src = d_xyzi;
-    reg->n_src = n;
-    reg->has_source = true;
-    if (reg->gicp) MRGFE_TRY(reg->gicp->set_source(reg->d_src, reg->n_src));
-    return MRGFE_OK;
+    return abi_guard("mrgfe_reg_set_source_device", [&]() -> int {
+        MRGFE_TRY(check_count(n, "mrgfe_reg_set_source_device"));
+        if (!reg || (n && !d_xyzi)) { set_error("mrgfe_reg_set_source_device: NULL argument"); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(reg->ctx);
+        MRGFE_TRY(reg->ctx->bind());
+        reg->d_src = d_xyzi;
+        reg->n_src = n;
+        reg->has_source = true;
+        if (reg->gicp) MRGFE_TRY(reg->gicp->set_source(reg->d_src, reg->n_src));
+        return MRGFE_OK;
+    });
 }
 
 int mrgfe_reg_set_source_from_prefilter(mrgfe_reg* reg, const void* d_xyzi, size_t n)
 {
-    MRGFE_TRY(check_count(n, "mrgfe_reg_set_source_from_prefilter"));
-    if (!reg || (n && !d_xyzi)) { set_error("mrgfe_reg_set_source_from_prefilter: NULL argument"); return MRGFE_ERR_INVALID; }
-    MRGFE_LOCK(reg->ctx);
-    MRGFE_TRY(reg->ctx->bind());
-    reg->d_src = d_xyzi;
-    reg->n_src = n;
-    reg->has_source = true;
-    const mrgfe_ctx* c = reg->ctx;
-    const bool boxed = c->pf_out_valid && c->pf_out_ptr == d_xyzi && c->pf_out_n == n && n > 0;
-    if (reg->gicp) MRGFE_TRY(reg->gicp->set_source(reg->d_src, reg->n_src, boxed ? c->pf_out_box : nullptr));
-    return MRGFE_OK;
+    return abi_guard("mrgfe_reg_set_source_from_prefilter", [&]() -> int {
+        MRGFE_TRY(check_count(n, "mrgfe_reg_set_source_from_prefilter"));
+        if (!reg || (n && !d_xyzi)) { set_error("mrgfe_reg_set_source_from_prefilter: NULL argument"); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(reg->ctx);
+        MRGFE_TRY(reg->ctx->bind());
+        reg->d_src = d_xyzi;
+        reg->n_src = n;
+        reg->has_source = true;
+        const mrgfe_ctx* c = reg->ctx;
+        const bool boxed = c->pf_out_valid && c->pf_out_ptr == d_xyzi && c->pf_out_n == n && n > 0;
+        if (reg->gicp) MRGFE_TRY(reg->gicp->set_source(reg->d_src, reg->n_src, boxed ? c->pf_out_box : nullptr));
+        return MRGFE_OK;
+    });
 }
 
 int mrgfe_reg_source_becomes_target(mrgfe_reg* reg)
 {
-    if (!reg) { set_error("mrgfe_reg_source_becomes_target: NULL argument"); return MRGFE_ERR_INVALID; }
-    if (!reg->has_source) { set_error("mrgfe_reg_source_becomes_target: setInputSource first"); return MRGFE_ERR_STATE; }
-    MRGFE_LOCK(reg->ctx);
-    MRGFE_TRY(reg->ctx->bind());
-    TraceRange tr("mrgfe_reg_source_becomes_target");
-    // a cloud the library uploaded lives in reg->src: that buffer becomes the target's, the old target's takes the next source
-    if (reg->d_src == reg->src.p && reg->src.p != nullptr) std::swap(reg->src, reg->tgt);
-    reg->d_tgt = reg->d_src;
-    reg->n_tgt = reg->n_src;
-    if (reg->gicp) {
-        reg->has_target = true;
-        reg->nn_valid = false;
-        MRGFE_TRY(reg->gicp->source_becomes_target());
-        reg->target_status = MRGFE_OK;
-        return MRGFE_OK;
-    }
-    return reg_target_changed(reg);  // NDT: the voxel grid of the new target (a source has nothing to hand over)
+    return abi_guard("mrgfe_reg_source_becomes_target", [&]() -> int {
+        if (!reg) { set_error("mrgfe_reg_source_becomes_target: NULL argument"); return MRGFE_ERR_INVALID; }
+        if (!reg->has_source) { set_error("mrgfe_reg_source_becomes_target: setInputSource first"); return MRGFE_ERR_STATE; }
+        MRGFE_LOCK(reg->ctx);
+        MRGFE_TRY(reg->ctx->bind());
+        TraceRange tr("mrgfe_reg_source_becomes_target");
+        // a cloud the library uploaded lives in reg->src: that buffer becomes the target's, the old target's takes the next source
+        if (reg->d_src == reg->src.p && reg->src.p != nullptr) std::swap(reg->src, reg->tgt);
+        reg->d_tgt = reg->d_src;
+        reg->n_tgt = reg->n_src;
+        if (reg->gicp) {
+            reg->has_target = true;
+            reg->nn_valid = false;
+            MRGFE_TRY(reg->gicp->source_becomes_target());
+            reg->target_status = MRGFE_OK;
+            return MRGFE_OK;
+        }
+        return reg_target_changed(reg);  // NDT: the voxel grid of the new target (a source has nothing to hand over)
+    });
 }
 
 int mrgfe_reg_align(mrgfe_reg* reg, const float guess[16], float* aligned_xyzi)
 {
-    if (!reg || !guess) { set_error("mrgfe_reg_align: NULL argument"); return MRGFE_ERR_INVALID; }
-    if (!reg->has_target || !reg->has_source) { set_error("align: setInputTarget / setInputSource first"); return MRGFE_ERR_STATE; }
-    MRGFE_LOCK(reg->ctx);
-    MRGFE_TRY(reg->ctx->bind());
-    TraceRange tr("mrgfe_reg_align");
-    float g[16];
-    col2row(guess, g);
-    if (reg->ndt) {
-        NdtEngine& e = *reg->ndt;
-        e.clear_pairs();
-        int pi = e.add_pair_device(0, reg->d_src, reg->n_src, g);
-        if (pi < 0) return pi;
-        MRGFE_TRY(e.align_all());
-        const NdtController& c = e.pair(0).ctl;
-        std::memcpy(reg->final_rm, c.final_transformation(), sizeof(reg->final_rm));
-        reg->converged = c.converged();
-        reg->iterations = c.iterations();
-        reg->evaluations = c.evaluations();
-        reg->trans_probability = c.trans_probability();
-        std::memcpy(reg->hessian, c.hessian(), sizeof(reg->hessian));
-        reg->mean_neighbours = c.evaluations() ? c.neighbours_sum() / c.evaluations() : 0.0;
-        if (aligned_xyzi) MRGFE_TRY(e.aligned_cloud(0, aligned_xyzi));
-    } else {
-        GicpEngine& e = *reg->gicp;
-        MRGFE_TRY(e.align(g));
-        std::memcpy(reg->final_rm, e.final_transformation(), sizeof(reg->final_rm));
-        reg->converged = e.converged();
-        reg->iterations = e.iterations();
-        reg->evaluations = e.evaluations();
-        reg->trans_probability = 0;
-        std::memcpy(reg->hessian, e.hessian(), sizeof(reg->hessian));
-        if (aligned_xyzi) MRGFE_TRY(e.aligned_cloud(aligned_xyzi));
-    }
-    reg->aligned_once = true;
-    return MRGFE_OK;
+    return abi_guard("mrgfe_reg_align", [&]() -> int {
+        if (!reg || !guess) { set_error("mrgfe_reg_align: NULL argument"); return MRGFE_ERR_INVALID; }
+        if (!reg->has_target || !reg->has_source) { set_error("align: setInputTarget / setInputSource first"); return MRGFE_ERR_STATE; }
+        MRGFE_LOCK(reg->ctx);
+        MRGFE_TRY(reg->ctx->bind());
+        TraceRange tr("mrgfe_reg_align");
+        float g[16];
+        col2row(guess, g);
+        if (reg->ndt) {
+            NdtEngine& e = *reg->ndt;
+            e.clear_pairs();
+            int pi = e.add_pair_device(0, reg->d_src, reg->n_src, g);
+            if (pi < 0) return pi;
+            MRGFE_TRY(e.align_all());
+            const NdtController& c = e.pair(0).ctl;
+            std::memcpy(reg->final_rm, c.final_transformation(), sizeof(reg->final_rm));
+            reg->converged = c.converged();
+            reg->iterations = c.iterations();
+            reg->evaluations = c.evaluations();
+            reg->trans_probability = c.trans_probability();
+            std::memcpy(reg->hessian, c.hessian(), sizeof(reg->hessian));
+            reg->mean_neighbours = c.evaluations() ? c.neighbours_sum() / c.evaluations() : 0.0;
+            if (aligned_xyzi) MRGFE_TRY(e.aligned_cloud(0, aligned_xyzi));
+        } else {
+            GicpEngine& e = *reg->gicp;
+            MRGFE_TRY(e.align(g));
+            std::memcpy(reg->final_rm, e.final_transformation(), sizeof(reg->final_rm));
+            reg->converged = e.converged();
+            reg->iterations = e.iterations();
+            reg->evaluations = e.evaluations();
+            reg->trans_probability = 0;
+            std::memcpy(reg->hessian, e.hessian(), sizeof(reg->hessian));
+            if (aligned_xyzi) MRGFE_TRY(e.aligned_cloud(aligned_xyzi));
+        }
+        reg->aligned_once = true;
+        return MRGFE_OK;
+    });
 }
 
 int mrgfe_reg_has_converged(const mrgfe_reg* reg) { return reg && reg->converged ? 1 : 0; }
@@ -483,24 +489,22 @@ int mrgfe_knn(mrgfe_ctx* ctx, const float* cloud, size_t n, const float* query, 
     if (nq == 0) return MRGFE_OK;
     MRGFE_LOCK(ctx);
     MRGFE_TRY(ctx->bind());
-    DevBuf dc, dq, di, dd;
+    DevBuf dd, di, dq, dc;  // (freed at the return in reverse order, the grid first)
     NnGrid grid;
-    int rc = dc.ensure(std::max<size_t>(n, 1) * 16);
-    if (rc == MRGFE_OK) rc = dq.ensure(nq * 16);
-    if (rc == MRGFE_OK) rc = di.ensure(nq * k * 4);
-    if (rc == MRGFE_OK) rc = dd.ensure(nq * k * 4);
-    if (rc == MRGFE_OK && n) rc = upload_cloud(ctx, cloud, n, stride, dc.p);
-    if (rc == MRGFE_OK) rc = upload_cloud(ctx, query, nq, stride, dq.p);
-    if (rc == MRGFE_OK) rc = grid.build(ctx, dc.as<float4>(), n, 1.0f, NnGrid::kCrowdingKnn);
-    if (rc == MRGFE_OK) rc = grid.knn_device(ctx, dq.as<float4>(), nq, k, di.as<int32_t>(), dd.as<float>());
-    if (rc == MRGFE_OK && (hipMemcpyAsync(idx, di.p, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                           hipMemcpyAsync(sqd, dd.p, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)) {
+    MRGFE_TRY(dc.ensure(std::max<size_t>(n, 1) * 16));
+    MRGFE_TRY(dq.ensure(nq * 16));
+    MRGFE_TRY(di.ensure(nq * k * 4));
+    MRGFE_TRY(dd.ensure(nq * k * 4));
+    if (n) MRGFE_TRY(upload_cloud(ctx, cloud, n, stride, dc.p));
+    MRGFE_TRY(upload_cloud(ctx, query, nq, stride, dq.p));
+    MRGFE_TRY(grid.build(ctx, dc.as<float4>(), n, 1.0f, NnGrid::kCrowdingKnn));
+    MRGFE_TRY(grid.knn_device(ctx, dq.as<float4>(), nq, k, di.as<int32_t>(), dd.as<float>()));
+    if (hipMemcpyAsync(idx, di.p, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(sqd, dd.p, nq * k * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
         set_error("mrgfe_knn: device to host copy failed");
-        rc = MRGFE_ERR_HIP;
+        return MRGFE_ERR_HIP;
     }
-    grid.release();
-    dc.release(); dq.release(); di.release(); dd.release();
-    return rc;
+    return MRGFE_OK;
 }
 
 int mrgfe_dbg_set_gicp_corr_passes(int mode) { return gicp_set_corr_passes(mode); }
@@ -511,12 +515,12 @@ int mrgfe_dbg_grid_set_query(mrgfe_ctx* ctx, const float* const* clouds, const s
     if (k < 1 || k > 64) { set_error("mrgfe_dbg_grid_set_query: k must be in [1, 64]"); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(ctx);
     MRGFE_TRY(ctx->bind());
+    DevBuf     dd, di, dq;  // (freed in reverse order of declaration: the set, the clouds, then these)
     std::vector<DevBuf>        dc(count);
     std::vector<NnGrid>        grids(count);
     std::vector<NnGrid*>       gp(count);
     std::vector<const float4*> cp(count);
     std::vector<uint32_t>      nn(count);
-    DevBuf     dq, di, dd;
     NnGridSet  set;
     int rc = dq.ensure(nq * 16);
     if (rc == MRGFE_OK) rc = di.ensure(nq * k * 4);
@@ -541,10 +545,7 @@ int mrgfe_dbg_grid_set_query(mrgfe_ctx* ctx, const float* const* clouds, const s
         }
     }
     if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == MRGFE_OK) rc = MRGFE_ERR_HIP;
-    set.release();
-    for (auto& b : dc) b.release();
-    dq.release(); di.release(); dd.release();
-    return rc;
+    return rc;  // (every path waits for the stream above before the buffers go)
 }
 
 int mrgfe_gicp_linearize(mrgfe_reg* reg, const double T[16], double H[36], double b[6], double* sum_errors, int* n_correspondences)
@@ -789,60 +790,56 @@ static int map_cloud_finish(mrgfe_ctx* ctx, int K_all, const float4* d_cat, cons
 {
     const uint64_t total = off.back();
     size_t m = 0, unfiltered = 0;
-    int    rc = MRGFE_OK;
-    DevBuf dout;
+    DevBuf dout;  // (a fresh buffer per call, freed at the return: after the download)
     if (total) {
-        rc = dout.ensure(total * 16);
-        if (rc == MRGFE_OK)
-            rc = map_cloud_device(ctx, d_cat, off.data(), pose_f.data(), static_cast<int>(off.size()) - 1, resolution, min_points_per_voxel, distance_far_thresh, dout.as<float4>(), &m,
-                                  &unfiltered, kf_ptrs);
+        MRGFE_TRY(dout.ensure(total * 16));
+        MRGFE_TRY(map_cloud_device(ctx, d_cat, off.data(), pose_f.data(), static_cast<int>(off.size()) - 1, resolution, min_points_per_voxel, distance_far_thresh, dout.as<float4>(), &m,
+                                   &unfiltered, kf_ptrs));
     }
     // :57-60: the cloud BEFORE the voxel filter decides
-    if (rc == MRGFE_OK && unfiltered == 0 && K_all > 1) { set_error("cloud is empty after processing keyframes"); rc = MRGFE_ERR_EMPTY; }
-    if (rc == MRGFE_OK && m > capacity) { *out_n = m; set_error("map cloud: output needs %zu points, capacity is %zu", m, capacity); rc = MRGFE_ERR_INVALID; }
-    if (rc == MRGFE_OK && m) {
-        if (!out) { set_error("map cloud: NULL output"); rc = MRGFE_ERR_INVALID; }
-        else if (hipMemcpyAsync(out, dout.p, m * 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+    if (unfiltered == 0 && K_all > 1) { set_error("cloud is empty after processing keyframes"); return MRGFE_ERR_EMPTY; }
+    if (m > capacity) { *out_n = m; set_error("map cloud: output needs %zu points, capacity is %zu", m, capacity); return MRGFE_ERR_INVALID; }
+    if (m) {
+        if (!out) { set_error("map cloud: NULL output"); return MRGFE_ERR_INVALID; }
+        if (hipMemcpyAsync(out, dout.p, m * 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
             set_error("map cloud: device to host copy failed");
-            rc = MRGFE_ERR_HIP;
+            return MRGFE_ERR_HIP;
         }
     }
-    if (rc == MRGFE_OK) *out_n = m;
-    dout.release();
-    return rc;
+    *out_n = m;
+    return MRGFE_OK;
 }
 
 int mrgfe_map_cloud_generate(mrgfe_ctx* ctx, int K, const float* const* clouds, const size_t* n_points, size_t stride, const double* poses, const uint8_t* first_keyframe,
                              float resolution, int min_points_per_voxel, float distance_far_thresh, int skip_first_cloud, float* out, size_t capacity, size_t* out_n)
 {
-    if (!ctx || !out_n || (K > 0 && (!clouds || !n_points || !poses))) { set_error("mrgfe_map_cloud_generate: NULL argument"); return MRGFE_ERR_INVALID; }
-    *out_n = 0;
-    if (K <= 0) { set_error("keyframes are empty, cannot generate map cloud"); return MRGFE_ERR_EMPTY; }  // map_cloud_generator.cpp:19-22
-    MRGFE_LOCK(ctx);
-    MRGFE_TRY(ctx->bind());
-    std::vector<uint32_t> off(1, 0u);
-    std::vector<float>    pose_f;
-    std::vector<int>      used;
-    uint64_t total = 0;
-    for (int k = 0; k < K; ++k) {
-        if (first_keyframe && first_keyframe[k] && skip_first_cloud) continue;  // :32-34
-        if (n_points[k] && !clouds[k]) { set_error("mrgfe_map_cloud_generate: NULL cloud %d", k); return MRGFE_ERR_INVALID; }
-        total += n_points[k];
-        if (total > 0x7fffffffu) { set_error("mrgfe_map_cloud_generate: more than 2^31 points"); return MRGFE_ERR_INVALID; }
-        used.push_back(k);
-        off.push_back(static_cast<uint32_t>(total));
-        for (int t = 0; t < 16; ++t) pose_f.push_back(static_cast<float>(poses[16 * k + t]));  // pose.matrix().cast<float>()
-    }
-    int    rc = MRGFE_OK;
-    DevBuf dcat;
-    if (total) {
-        rc = dcat.ensure(total * 16);
-        for (size_t u = 0; u < used.size() && rc == MRGFE_OK; ++u)
-            if (n_points[used[u]]) rc = upload_cloud(ctx, clouds[used[u]], n_points[used[u]], stride, dcat.as<char>() + size_t(off[u]) * 16);
-    }
-    if (rc == MRGFE_OK) rc = map_cloud_finish(ctx, K, dcat.as<float4>(), nullptr, off, pose_f, resolution, min_points_per_voxel, distance_far_thresh, out, capacity, out_n);
-    dcat.release();
-    return rc;
+    return abi_guard("mrgfe_map_cloud_generate", [&]() -> int {
+        if (!ctx || !out_n || (K > 0 && (!clouds || !n_points || !poses))) { set_error("mrgfe_map_cloud_generate: NULL argument"); return MRGFE_ERR_INVALID; }
+        *out_n = 0;
+        if (K <= 0) { set_error("keyframes are empty, cannot generate map cloud"); return MRGFE_ERR_EMPTY; }  // map_cloud_generator.cpp:19-22
+        MRGFE_LOCK(ctx);
+        MRGFE_TRY(ctx->bind());
+        std::vector<uint32_t> off(1, 0u);
+        std::vector<float>    pose_f;
+        std::vector<int>      used;
+        uint64_t total = 0;
+        for (int k = 0; k < K; ++k) {
+            if (first_keyframe && first_keyframe[k] && skip_first_cloud) continue;  // :32-34
+            if (n_points[k] && !clouds[k]) { set_error("mrgfe_map_cloud_generate: NULL cloud %d", k); return MRGFE_ERR_INVALID; }
+            total += n_points[k];
+            if (total > 0x7fffffffu) { set_error("mrgfe_map_cloud_generate: more than 2^31 points"); return MRGFE_ERR_INVALID; }
+            used.push_back(k);
+            off.push_back(static_cast<uint32_t>(total));
+            for (int t = 0; t < 16; ++t) pose_f.push_back(static_cast<float>(poses[16 * k + t]));  // pose.matrix().cast<float>()
+        }
+        DevBuf dcat;  // (a fresh buffer per call, freed at the return: after map_cloud_finish has freed its own and the download is done)
+        if (total) {
+            MRGFE_TRY(dcat.ensure(total * 16));
+            for (size_t u = 0; u < used.size(); ++u)
+                if (n_points[used[u]]) MRGFE_TRY(upload_cloud(ctx, clouds[used[u]], n_points[used[u]], stride, dcat.as<char>() + size_t(off[u]) * 16));
+        }
+        return map_cloud_finish(ctx, K, dcat.as<float4>(), nullptr, off, pose_f, resolution, min_points_per_voxel, distance_far_thresh, out, capacity, out_n);
+    });
 }
 
 // ---- map store: keyframe clouds resident in HBM (include/mrgfe.h) --------------------------------------------------------
@@ -855,52 +852,52 @@ struct mrgfe_map_store {
     // exact-NN grids of the keyframes that were `cloud1` of a fitness score lately (graph edges of one keyframe come in bursts:
     // its odometry edge, then the loop edges of the same optimisation cycle), least recently used first out
     struct CachedGrid { uint64_t key = 0; uint64_t tick = 0; NnGrid grid; };
-    std::vector<CachedGrid*> grids;
+    std::vector<std::unique_ptr<CachedGrid>> grids;
     uint64_t tick = 0;
     size_t   max_grids = 8;
 };
 
 int mrgfe_map_store_create(mrgfe_ctx* ctx, mrgfe_map_store** out)
 {
-    if (!ctx || !out) { set_error("mrgfe_map_store_create: NULL argument"); return MRGFE_ERR_INVALID; }
-    mrgfe_map_store* s = new (std::nothrow) mrgfe_map_store();
-    if (!s) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-    s->ctx = ctx;
-    *out = s;
-    return MRGFE_OK;
+    return abi_guard("mrgfe_map_store_create", [&]() -> int {
+        if (!ctx || !out) { set_error("mrgfe_map_store_create: NULL argument"); return MRGFE_ERR_INVALID; }
+        mrgfe_map_store* s = new (std::nothrow) mrgfe_map_store();
+        if (!s) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+        s->ctx = ctx;
+        *out = s;
+        return MRGFE_OK;
+    });
 }
 void mrgfe_map_store_destroy(mrgfe_map_store* s)
 {
     if (!s) return;
-    {
-        MRGFE_LOCK(s->ctx);
-        (void)s->ctx->bind();
-        for (auto* g : s->grids) { g->grid.release(); delete g; }
-        s->arena.release();
-    }
+    MRGFE_LOCK(s->ctx);
+    (void)s->ctx->bind();
     delete s;
 }
 int mrgfe_map_store_add(mrgfe_map_store* s, uint64_t key, const float* xyzi, size_t n, size_t stride)
 {
-    MRGFE_TRY(check_count(n, "mrgfe_map_store_add"));
-    if (!s || key == 0 || (n && !xyzi)) { set_error("mrgfe_map_store_add: NULL store / cloud or key 0"); return MRGFE_ERR_INVALID; }
-    if (n > 0x7fffffffu) { set_error("cloud too large"); return MRGFE_ERR_INVALID; }
-    MRGFE_LOCK(s->ctx);
-    MRGFE_TRY(s->ctx->bind());
-    auto it = s->clouds.find(key);
-    if (it != s->clouds.end()) {
-        if (it->second.n == n) return MRGFE_OK;
-        set_error("mrgfe_map_store_add: keyframe %llu is stored with %u points, not %zu", static_cast<unsigned long long>(key), it->second.n, n);
-        return MRGFE_ERR_INVALID;
-    }
-    void* p = nullptr;
-    if (n) {
-        MRGFE_TRY(s->arena.alloc(n * 16, &p));
-        MRGFE_TRY(upload_cloud(s->ctx, xyzi, n, stride, p));
-    }
-    s->clouds[key] = {static_cast<const float4*>(p), static_cast<uint32_t>(n)};
-    s->bytes += n * 16;
-    return MRGFE_OK;
+    return abi_guard("mrgfe_map_store_add", [&]() -> int {
+        MRGFE_TRY(check_count(n, "mrgfe_map_store_add"));
+        if (!s || key == 0 || (n && !xyzi)) { set_error("mrgfe_map_store_add: NULL store / cloud or key 0"); return MRGFE_ERR_INVALID; }
+        if (n > 0x7fffffffu) { set_error("cloud too large"); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(s->ctx);
+        MRGFE_TRY(s->ctx->bind());
+        auto it = s->clouds.find(key);
+        if (it != s->clouds.end()) {
+            if (it->second.n == n) return MRGFE_OK;
+            set_error("mrgfe_map_store_add: keyframe %llu is stored with %u points, not %zu", static_cast<unsigned long long>(key), it->second.n, n);
+            return MRGFE_ERR_INVALID;
+        }
+        void* p = nullptr;
+        if (n) {
+            MRGFE_TRY(s->arena.alloc(n * 16, &p));
+            MRGFE_TRY(upload_cloud(s->ctx, xyzi, n, stride, p));
+        }
+        s->clouds[key] = {static_cast<const float4*>(p), static_cast<uint32_t>(n)};
+        s->bytes += n * 16;
+        return MRGFE_OK;
+    });
 }
 int mrgfe_map_store_has(const mrgfe_map_store* s, uint64_t key, size_t* n)
 {
@@ -920,53 +917,57 @@ size_t mrgfe_map_store_bytes(const mrgfe_map_store* s)
 int mrgfe_map_store_generate(mrgfe_map_store* s, int K, const uint64_t* keys, const double* poses, const uint8_t* first_keyframe, float resolution, int min_points_per_voxel,
                              float distance_far_thresh, int skip_first_cloud, float* out, size_t capacity, size_t* out_n)
 {
-    if (!s || !out_n || (K > 0 && (!keys || !poses))) { set_error("mrgfe_map_store_generate: NULL argument"); return MRGFE_ERR_INVALID; }
-    *out_n = 0;
-    if (K <= 0) { set_error("keyframes are empty, cannot generate map cloud"); return MRGFE_ERR_EMPTY; }  // map_cloud_generator.cpp:19-22
-    MRGFE_LOCK(s->ctx);
-    MRGFE_TRY(s->ctx->bind());
-    std::vector<uint32_t>      off(1, 0u);
-    std::vector<float>         pose_f;
-    std::vector<const float4*> ptrs;
-    uint64_t total = 0;
-    for (int k = 0; k < K; ++k) {
-        if (first_keyframe && first_keyframe[k] && skip_first_cloud) continue;  // :32-34
-        auto it = s->clouds.find(keys[k]);
-        if (it == s->clouds.end()) { set_error("mrgfe_map_store_generate: keyframe %llu is not in the store", static_cast<unsigned long long>(keys[k])); return MRGFE_ERR_INVALID; }
-        total += it->second.n;
-        if (total > 0x7fffffffu) { set_error("mrgfe_map_store_generate: more than 2^31 points"); return MRGFE_ERR_INVALID; }
-        ptrs.push_back(it->second.p);
-        off.push_back(static_cast<uint32_t>(total));
-        for (int t = 0; t < 16; ++t) pose_f.push_back(static_cast<float>(poses[16 * k + t]));
-    }
-    MRGFE_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));  // clouds added just before are still on their way up
-    return map_cloud_finish(s->ctx, K, nullptr, ptrs.data(), off, pose_f, resolution, min_points_per_voxel, distance_far_thresh, out, capacity, out_n);
+    return abi_guard("mrgfe_map_store_generate", [&]() -> int {
+        if (!s || !out_n || (K > 0 && (!keys || !poses))) { set_error("mrgfe_map_store_generate: NULL argument"); return MRGFE_ERR_INVALID; }
+        *out_n = 0;
+        if (K <= 0) { set_error("keyframes are empty, cannot generate map cloud"); return MRGFE_ERR_EMPTY; }  // map_cloud_generator.cpp:19-22
+        MRGFE_LOCK(s->ctx);
+        MRGFE_TRY(s->ctx->bind());
+        std::vector<uint32_t>      off(1, 0u);
+        std::vector<float>         pose_f;
+        std::vector<const float4*> ptrs;
+        uint64_t total = 0;
+        for (int k = 0; k < K; ++k) {
+            if (first_keyframe && first_keyframe[k] && skip_first_cloud) continue;  // :32-34
+            auto it = s->clouds.find(keys[k]);
+            if (it == s->clouds.end()) { set_error("mrgfe_map_store_generate: keyframe %llu is not in the store", static_cast<unsigned long long>(keys[k])); return MRGFE_ERR_INVALID; }
+            total += it->second.n;
+            if (total > 0x7fffffffu) { set_error("mrgfe_map_store_generate: more than 2^31 points"); return MRGFE_ERR_INVALID; }
+            ptrs.push_back(it->second.p);
+            off.push_back(static_cast<uint32_t>(total));
+            for (int t = 0; t < 16; ++t) pose_f.push_back(static_cast<float>(poses[16 * k + t]));
+        }
+        MRGFE_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));  // clouds added just before are still on their way up
+        return map_cloud_finish(s->ctx, K, nullptr, ptrs.data(), off, pose_f, resolution, min_points_per_voxel, distance_far_thresh, out, capacity, out_n);
+    });
 }
 
 int mrgfe_map_store_fitness(mrgfe_map_store* s, uint64_t key1, uint64_t key2, const double relpose[16], double max_range, double* out)
 {
-    if (!s || !relpose || !out) { set_error("mrgfe_map_store_fitness: NULL argument"); return MRGFE_ERR_INVALID; }
-    MRGFE_LOCK(s->ctx);
-    MRGFE_TRY(s->ctx->bind());
-    auto i1 = s->clouds.find(key1), i2 = s->clouds.find(key2);
-    if (i1 == s->clouds.end() || i2 == s->clouds.end()) {
-        set_error("mrgfe_map_store_fitness: keyframe %llu is not in the store", static_cast<unsigned long long>(i1 == s->clouds.end() ? key1 : key2));
-        return MRGFE_ERR_INVALID;
-    }
-    if (i1->second.n == 0 || i2->second.n == 0) { *out = DBL_MAX; return MRGFE_OK; }
-    mrgfe_map_store::CachedGrid* g = nullptr;
-    for (auto* c : s->grids) if (c->key == key1) g = c;
-    if (!g) {
-        if (s->grids.size() < s->max_grids) { g = new mrgfe_map_store::CachedGrid(); s->grids.push_back(g); }
-        else { g = s->grids[0]; for (auto* c : s->grids) if (c->tick < g->tick) g = c; }
-        g->key = 0;
-        MRGFE_TRY(g->grid.build(s->ctx, i1->second.p, i1->second.n, 1.0f, NnGrid::kCrowding1nn, 1));
-        g->key = key1;
-    }
-    g->tick = ++s->tick;
-    float T[16];  // relpose.cast<float>(), row-major
-    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T[r * 4 + c] = static_cast<float>(relpose[c * 4 + r]);
-    return g->grid.fitness(s->ctx, i2->second.p, i2->second.n, T, max_range, out);
+    return abi_guard("mrgfe_map_store_fitness", [&]() -> int {
+        if (!s || !relpose || !out) { set_error("mrgfe_map_store_fitness: NULL argument"); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(s->ctx);
+        MRGFE_TRY(s->ctx->bind());
+        auto i1 = s->clouds.find(key1), i2 = s->clouds.find(key2);
+        if (i1 == s->clouds.end() || i2 == s->clouds.end()) {
+            set_error("mrgfe_map_store_fitness: keyframe %llu is not in the store", static_cast<unsigned long long>(i1 == s->clouds.end() ? key1 : key2));
+            return MRGFE_ERR_INVALID;
+        }
+        if (i1->second.n == 0 || i2->second.n == 0) { *out = DBL_MAX; return MRGFE_OK; }
+        mrgfe_map_store::CachedGrid* g = nullptr;
+        for (auto& c : s->grids) if (c->key == key1) g = c.get();
+        if (!g) {
+            if (s->grids.size() < s->max_grids) { s->grids.push_back(std::make_unique<mrgfe_map_store::CachedGrid>()); g = s->grids.back().get(); }
+            else { g = s->grids[0].get(); for (auto& c : s->grids) if (c->tick < g->tick) g = c.get(); }
+            g->key = 0;
+            MRGFE_TRY(g->grid.build(s->ctx, i1->second.p, i1->second.n, 1.0f, NnGrid::kCrowding1nn, 1));
+            g->key = key1;
+        }
+        g->tick = ++s->tick;
+        float T[16];  // relpose.cast<float>(), row-major
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T[r * 4 + c] = static_cast<float>(relpose[c * 4 + r]);
+        return g->grid.fitness(s->ctx, i2->second.p, i2->second.n, T, max_range, out);
+    });
 }
 int mrgfe_map_store_information_matrix(mrgfe_map_store* s, const mrgfe_inf_params* p, uint64_t key1, uint64_t key2, const double relpose[16], double inf[36], double* fitness_out)
 {
@@ -987,20 +988,25 @@ int mrgfe_remove_points_near(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t
     if (n == 0) return MRGFE_OK;
     MRGFE_LOCK(ctx);
     MRGFE_TRY(ctx->bind());
-    DevBuf din, dk, dr;
-    int rc = din.ensure(n * 16);
-    if (rc == MRGFE_OK) rc = dk.ensure(n * 16);
-    if (rc == MRGFE_OK && removed) rc = dr.ensure(n * 16);
-    if (rc == MRGFE_OK) rc = upload_cloud(ctx, xyzi, n, stride, din.p);
+    DevBuf dr, dk, din;  // (freed at the return, `din` first)
     size_t nk = 0, nr = 0;
-    if (rc == MRGFE_OK) rc = remove_points_near_device(ctx, din.as<float4>(), n, centres, n_centres, radius_sqr, dk.as<float4>(), &nk, removed ? dr.as<float4>() : nullptr, &nr);
-    if (rc == MRGFE_OK && nk && hipMemcpyAsync(kept, dk.p, nk * 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = MRGFE_ERR_HIP;
-    if (rc == MRGFE_OK && removed && nr && hipMemcpyAsync(removed, dr.p, nr * 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = MRGFE_ERR_HIP;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == MRGFE_OK) rc = MRGFE_ERR_HIP;
+    auto run = [&]() -> int {
+        MRGFE_TRY(din.ensure(n * 16));
+        MRGFE_TRY(dk.ensure(n * 16));
+        if (removed) MRGFE_TRY(dr.ensure(n * 16));
+        MRGFE_TRY(upload_cloud(ctx, xyzi, n, stride, din.p));
+        MRGFE_TRY(remove_points_near_device(ctx, din.as<float4>(), n, centres, n_centres, radius_sqr, dk.as<float4>(), &nk, removed ? dr.as<float4>() : nullptr, &nr));
+        if (nk && hipMemcpyAsync(kept, dk.p, nk * 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return MRGFE_ERR_HIP;
+        if (removed && nr && hipMemcpyAsync(removed, dr.p, nr * 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return MRGFE_ERR_HIP;
+        return MRGFE_OK;
+    };
+    int rc = run();
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == MRGFE_OK) rc = MRGFE_ERR_HIP;  // (also on failure: nothing is in flight when the buffers go)
     if (rc == MRGFE_ERR_HIP) set_error("mrgfe_remove_points_near: device to host copy failed");
-    if (rc == MRGFE_OK) { *n_kept = nk; if (n_removed) *n_removed = nr; }
-    din.release(); dk.release(); dr.release();
-    return rc;
+    if (rc != MRGFE_OK) return rc;
+    *n_kept = nk;
+    if (n_removed) *n_removed = nr;
+    return MRGFE_OK;
 }
 
 int mrgfe_deskew(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, const float ang_v[3], double scan_period, float* out)
@@ -1010,17 +1016,16 @@ int mrgfe_deskew(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, con
     if (n == 0) return MRGFE_OK;
     MRGFE_LOCK(ctx);
     MRGFE_TRY(ctx->bind());
-    DevBuf din, dout;
-    int rc = din.ensure(n * 16);
-    if (rc == MRGFE_OK) rc = dout.ensure(n * 16);
-    if (rc == MRGFE_OK) rc = upload_cloud(ctx, xyzi, n, stride, din.p);
-    if (rc == MRGFE_OK) rc = deskew_device(ctx, din.as<float4>(), n, ang_v, scan_period, dout.as<float4>());
-    if (rc == MRGFE_OK && (hipMemcpyAsync(out, dout.p, n * 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)) {
+    DevBuf dout, din;  // (a fresh pair per call, freed at the return, `din` first)
+    MRGFE_TRY(din.ensure(n * 16));
+    MRGFE_TRY(dout.ensure(n * 16));
+    MRGFE_TRY(upload_cloud(ctx, xyzi, n, stride, din.p));
+    MRGFE_TRY(deskew_device(ctx, din.as<float4>(), n, ang_v, scan_period, dout.as<float4>()));
+    if (hipMemcpyAsync(out, dout.p, n * 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
         set_error("mrgfe_deskew: device to host copy failed");
-        rc = MRGFE_ERR_HIP;
+        return MRGFE_ERR_HIP;
     }
-    din.release(); dout.release();
-    return rc;
+    return MRGFE_OK;
 }
 
 int mrgfe_transform_cloud(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, const float T[16], float* out)
@@ -1032,37 +1037,38 @@ int mrgfe_transform_cloud(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t st
     MRGFE_TRY(ctx->bind());
     float Tr[16];
     col2row(T, Tr);
-    DevBuf din, dout;
-    int rc = din.ensure(n * 16);
-    if (rc == MRGFE_OK) rc = dout.ensure(n * 16);
-    if (rc == MRGFE_OK) rc = upload_cloud(ctx, xyzi, n, stride, din.p);
-    if (rc == MRGFE_OK) rc = transform_cloud_device(ctx, din.as<float4>(), n, Tr, dout.as<float4>());
-    if (rc == MRGFE_OK && (hipMemcpyAsync(out, dout.p, n * 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)) {
+    DevBuf dout, din;  // (a fresh pair per call, freed at the return, `din` first)
+    MRGFE_TRY(din.ensure(n * 16));
+    MRGFE_TRY(dout.ensure(n * 16));
+    MRGFE_TRY(upload_cloud(ctx, xyzi, n, stride, din.p));
+    MRGFE_TRY(transform_cloud_device(ctx, din.as<float4>(), n, Tr, dout.as<float4>()));
+    if (hipMemcpyAsync(out, dout.p, n * 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
         set_error("mrgfe_transform_cloud: device to host copy failed");
-        rc = MRGFE_ERR_HIP;
+        return MRGFE_ERR_HIP;
     }
-    din.release(); dout.release();
-    return rc;
+    return MRGFE_OK;
 }
 
 // ---- batch ------------------------------------------------------------------------------------------------------
 int mrgfe_batch_create(mrgfe_ctx* ctx, const mrgfe_reg_params* params, mrgfe_batch** out)
 {
-    if (!ctx || !out) { set_error("mrgfe_batch_create: NULL argument"); return MRGFE_ERR_INVALID; }
-    *out = nullptr;
-    MRGFE_TRY(check_params(params));
-    if (params->method == MRGFE_ICP_HIP || params->method == MRGFE_PCL_GICP_HIP || params->method == MRGFE_PCL_GICP_OMP_HIP) {
-        set_error("mrgfe_batch_create: ICP_HIP and PCL_GICP_HIP are offered for single registrations only");
-        return MRGFE_ERR_INVALID;
-    }
-    mrgfe_batch* b = new (std::nothrow) mrgfe_batch();
-    if (!b) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-    b->ctx = ctx;
-    b->params = *params;
-    b->ndt = new NdtEngine(ctx, ndt_params_from(*params));
-    if (const char* e = std::getenv("MRGFE_KEYFRAME_STORE_MB")) b->store_cap = static_cast<size_t>(std::max(0.0, std::atof(e))) << 20;
-    *out = b;
-    return MRGFE_OK;
+    return abi_guard("mrgfe_batch_create", [&]() -> int {
+        if (!ctx || !out) { set_error("mrgfe_batch_create: NULL argument"); return MRGFE_ERR_INVALID; }
+        *out = nullptr;
+        MRGFE_TRY(check_params(params));
+        if (params->method == MRGFE_ICP_HIP || params->method == MRGFE_PCL_GICP_HIP || params->method == MRGFE_PCL_GICP_OMP_HIP) {
+            set_error("mrgfe_batch_create: ICP_HIP and PCL_GICP_HIP are offered for single registrations only");
+            return MRGFE_ERR_INVALID;
+        }
+        std::unique_ptr<mrgfe_batch> b(new (std::nothrow) mrgfe_batch());
+        if (!b) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+        b->ctx = ctx;
+        b->params = *params;
+        b->ndt = std::make_unique<NdtEngine>(ctx, ndt_params_from(*params));
+        if (const char* e = std::getenv("MRGFE_KEYFRAME_STORE_MB")) b->store_cap = static_cast<size_t>(std::max(0.0, std::atof(e))) << 20;
+        *out = b.release();
+        return MRGFE_OK;
+    });
 }
 static void batch_async_main(mrgfe_batch* b)
 {
@@ -1082,16 +1088,9 @@ static void batch_async_main(mrgfe_batch* b)
                 a.state = 2;
             }
             a.cv.notify_all();
-            try {
-                st = mrgfe_batch_align(b, a.fitness_max_range, a.results);
-                if (st != MRGFE_OK) err = mrgfe_last_error();
-            } catch (const std::exception& e) {  // (a host container's bad_alloc: an error code for the waiter, never std::terminate)
-                st = MRGFE_ERR_INVALID;
-                err = std::string("mrgfe_batch_align_async: ") + e.what();
-            } catch (...) {
-                st = MRGFE_ERR_INVALID;
-                err = "mrgfe_batch_align_async: unknown exception";
-            }
+            // (an exception becomes an error code for the waiter, never std::terminate)
+            st = abi_guard("mrgfe_batch_align_async", [&] { return mrgfe_batch_align(b, a.fitness_max_range, a.results); });
+            if (st != MRGFE_OK) err = mrgfe_last_error();
         }
         {
             std::lock_guard<std::mutex> lk(a.mu);
@@ -1105,27 +1104,24 @@ static void batch_async_main(mrgfe_batch* b)
 
 int mrgfe_batch_align_async(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results)
 {
-    if (!b || !results) { set_error("mrgfe_batch_align_async: NULL argument"); return MRGFE_ERR_INVALID; }
-    if (!b->async) {
-        b->async.reset(new (std::nothrow) mrgfe_batch::Async());
-        if (!b->async) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-        try {
-            b->async->th = std::thread(batch_async_main, b);
-        } catch (const std::exception& e) {
-            b->async.reset();
-            set_error("mrgfe_batch_align_async: %s", e.what());
-            return MRGFE_ERR_INVALID;
+    return abi_guard("mrgfe_batch_align_async", [&]() -> int {
+        if (!b || !results) { set_error("mrgfe_batch_align_async: NULL argument"); return MRGFE_ERR_INVALID; }
+        if (!b->async) {
+            b->async.reset(new (std::nothrow) mrgfe_batch::Async());
+            if (!b->async) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+            const int st = abi_guard("mrgfe_batch_align_async", [&] { b->async->th = std::thread(batch_async_main, b); return MRGFE_OK; });
+            if (st != MRGFE_OK) { b->async.reset(); return st; }
         }
-    }
-    mrgfe_batch::Async& a = *b->async;
-    std::unique_lock<std::mutex> lk(a.mu);
-    if (a.state != 0) { set_error("mrgfe_batch_align_async: an align of this batch is %s: call mrgfe_batch_wait first", a.state == 3 ? "finished and not yet waited for" : "in flight"); return MRGFE_ERR_STATE; }
-    a.fitness_max_range = fitness_max_range;
-    a.results = results;
-    a.state = 1;
-    a.cv.notify_all();
-    a.cv.wait(lk, [&] { return a.state >= 2; });  // the worker holds the context lock now: later calls on this batch queue up behind the align
-    return MRGFE_OK;
+        mrgfe_batch::Async& a = *b->async;
+        std::unique_lock<std::mutex> lk(a.mu);
+        if (a.state != 0) { set_error("mrgfe_batch_align_async: an align of this batch is %s: call mrgfe_batch_wait first", a.state == 3 ? "finished and not yet waited for" : "in flight"); return MRGFE_ERR_STATE; }
+        a.fitness_max_range = fitness_max_range;
+        a.results = results;
+        a.state = 1;
+        a.cv.notify_all();
+        a.cv.wait(lk, [&] { return a.state >= 2; });  // the worker holds the context lock now: later calls on this batch queue up behind the align
+        return MRGFE_OK;
+    });
 }
 
 int mrgfe_batch_wait(mrgfe_batch* b)
@@ -1154,21 +1150,8 @@ void mrgfe_batch_destroy(mrgfe_batch* b)
         a.cv.notify_all();
         if (a.th.joinable()) a.th.join();
     }
-    {
-        MRGFE_LOCK(b->ctx);
-        (void)b->ctx->bind();
-        for (auto& g : b->fit_grids) g.release();
-        for (auto& gs : b->fit_sets) gs->release();
-        for (mrgfe_ctx* fc : b->fit_ctxs) mrgfe_ctx_destroy(fc);
-        if (b->early_ctx) mrgfe_ctx_destroy(b->early_ctx);
-        if (b->uploads_done) (void)hipEventDestroy(b->uploads_done);
-        if (b->port) b->port->buf.release();
-        for (auto& gp : b->gicp_pairs) gp.release();
-        delete b->gicp_batch;
-        for (auto* g : b->gicp) delete g;
-        delete b->ndt;
-        for (auto it = b->store.begin(); it != b->store.end();) it = store_erase(b, it);
-    }
+    MRGFE_LOCK(b->ctx);
+    (void)b->ctx->bind();
     delete b;
 }
 int mrgfe_batch_clear(mrgfe_batch* b)
@@ -1176,8 +1159,7 @@ int mrgfe_batch_clear(mrgfe_batch* b)
     if (!b) { set_error("NULL batch"); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(b->ctx);
     b->ndt->clear();
-    for (auto* g : b->gicp) delete g;  // their cached target state belongs to the clouds just forgotten
-    b->gicp.clear();
+    b->gicp.clear();  // their cached target state belongs to the clouds just forgotten
     b->pair_key.clear();
     ++b->epoch;  // stored keyframes stay; none is referenced by the (now empty) batch
     b->t_queue = std::chrono::steady_clock::now();  // mrgfe_batch_timing: the next align's time starts where its queueing starts
@@ -1186,96 +1168,108 @@ int mrgfe_batch_clear(mrgfe_batch* b)
 }
 int mrgfe_batch_add_target(mrgfe_batch* b, const float* xyzi, size_t n, size_t stride)
 {
-    MRGFE_TRY(check_count(n, "mrgfe_batch_add_target"));
-    if (!b) { set_error("NULL batch"); return MRGFE_ERR_INVALID; }
-    MRGFE_LOCK(b->ctx);
-    return b->ndt->add_target_host(xyzi, n, stride);
+    return abi_guard("mrgfe_batch_add_target", [&]() -> int {
+        MRGFE_TRY(check_count(n, "mrgfe_batch_add_target"));
+        if (!b) { set_error("NULL batch"); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(b->ctx);
+        return b->ndt->add_target_host(xyzi, n, stride);
+    });
 }
 int mrgfe_batch_add_target_device(mrgfe_batch* b, const void* d, size_t n)
 {
-    MRGFE_TRY(check_count(n, "mrgfe_batch_add_target_device"));
-    if (!b) { set_error("NULL batch"); return MRGFE_ERR_INVALID; }
-    MRGFE_LOCK(b->ctx);
-    return b->ndt->add_target_device(d, n);
+    return abi_guard("mrgfe_batch_add_target_device", [&]() -> int {
+        MRGFE_TRY(check_count(n, "mrgfe_batch_add_target_device"));
+        if (!b) { set_error("NULL batch"); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(b->ctx);
+        return b->ndt->add_target_device(d, n);
+    });
 }
 int mrgfe_batch_add_pair(mrgfe_batch* b, int target, const float* xyzi, size_t n, size_t stride, const float guess[16])
 {
-    MRGFE_TRY(check_count(n, "mrgfe_batch_add_pair"));
-    if (!b || !guess) { set_error("NULL argument"); return MRGFE_ERR_INVALID; }
-    MRGFE_LOCK(b->ctx);
-    float g[16];
-    col2row(guess, g);
-    return b->ndt->add_pair_host(target, xyzi, n, stride, g);
+    return abi_guard("mrgfe_batch_add_pair", [&]() -> int {
+        MRGFE_TRY(check_count(n, "mrgfe_batch_add_pair"));
+        if (!b || !guess) { set_error("NULL argument"); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(b->ctx);
+        float g[16];
+        col2row(guess, g);
+        return b->ndt->add_pair_host(target, xyzi, n, stride, g);
+    });
 }
 int mrgfe_batch_add_pair_device(mrgfe_batch* b, int target, const void* d, size_t n, const float guess[16])
 {
-    MRGFE_TRY(check_count(n, "mrgfe_batch_add_pair_device"));
-    if (!b || !guess) { set_error("NULL argument"); return MRGFE_ERR_INVALID; }
-    MRGFE_LOCK(b->ctx);
-    float g[16];
-    col2row(guess, g);
-    return b->ndt->add_pair_device(target, d, n, g);
+    return abi_guard("mrgfe_batch_add_pair_device", [&]() -> int {
+        MRGFE_TRY(check_count(n, "mrgfe_batch_add_pair_device"));
+        if (!b || !guess) { set_error("NULL argument"); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(b->ctx);
+        float g[16];
+        col2row(guess, g);
+        return b->ndt->add_pair_device(target, d, n, g);
+    });
 }
 int mrgfe_batch_add_device(mrgfe_batch* b, int n_targets, const void* const* d_targets, const size_t* target_points, int n_pairs, const int32_t* pair_target,
                            const void* const* d_sources, const size_t* source_points, const float* guesses)
 {
-    if (!b || n_targets < 0 || n_pairs < 0 || (n_targets && (!d_targets || !target_points)) || (n_pairs && (!pair_target || !d_sources || !source_points || !guesses))) {
-        set_error("mrgfe_batch_add_device: bad argument");
-        return MRGFE_ERR_INVALID;
-    }
-    MRGFE_LOCK(b->ctx);
-    const int t0 = b->ndt->n_targets(), p0 = b->ndt->n_pairs();
-    for (int i = 0; i < n_pairs; ++i)
-        if (pair_target[i] < 0 || pair_target[i] >= n_targets) { set_error("mrgfe_batch_add_device: pair %d names target %d of %d", i, pair_target[i], n_targets); return MRGFE_ERR_INVALID; }
-    for (int i = 0; i < n_targets; ++i) {
-        const int t = b->ndt->add_target_device(d_targets[i], target_points[i]);
-        if (t < 0) return t;
-    }
-    for (int i = 0; i < n_pairs; ++i) {
-        float g[16];
-        col2row(guesses + size_t(i) * 16, g);
-        const int pi = b->ndt->add_pair_device(t0 + pair_target[i], d_sources[i], source_points[i], g);
-        if (pi < 0) return pi;
-    }
-    return p0;
+    return abi_guard("mrgfe_batch_add_device", [&]() -> int {
+        if (!b || n_targets < 0 || n_pairs < 0 || (n_targets && (!d_targets || !target_points)) || (n_pairs && (!pair_target || !d_sources || !source_points || !guesses))) {
+            set_error("mrgfe_batch_add_device: bad argument");
+            return MRGFE_ERR_INVALID;
+        }
+        MRGFE_LOCK(b->ctx);
+        const int t0 = b->ndt->n_targets(), p0 = b->ndt->n_pairs();
+        for (int i = 0; i < n_pairs; ++i)
+            if (pair_target[i] < 0 || pair_target[i] >= n_targets) { set_error("mrgfe_batch_add_device: pair %d names target %d of %d", i, pair_target[i], n_targets); return MRGFE_ERR_INVALID; }
+        for (int i = 0; i < n_targets; ++i) {
+            const int t = b->ndt->add_target_device(d_targets[i], target_points[i]);
+            if (t < 0) return t;
+        }
+        for (int i = 0; i < n_pairs; ++i) {
+            float g[16];
+            col2row(guesses + size_t(i) * 16, g);
+            const int pi = b->ndt->add_pair_device(t0 + pair_target[i], d_sources[i], source_points[i], g);
+            if (pi < 0) return pi;
+        }
+        return p0;
+    });
 }
 int mrgfe_batch_add_pair_keyed(mrgfe_batch* b, int target, uint64_t key, const float* xyzi, size_t n, size_t stride, const float guess[16])
 {
-    MRGFE_TRY(check_count(n, "mrgfe_batch_add_pair_keyed"));
-    if (!b || !guess) { set_error("NULL argument"); return MRGFE_ERR_INVALID; }
-    if (key == 0) return mrgfe_batch_add_pair(b, target, xyzi, n, stride, guess);
-    MRGFE_LOCK(b->ctx);
-    MRGFE_TRY(b->ctx->bind());
-    if (n > 0x7fffffffu) { set_error("cloud too large"); return MRGFE_ERR_INVALID; }
-    mrgfe_batch::Keyframe* kf = nullptr;
-    auto it = b->store.find(key);
-    if (it != b->store.end() && it->second->n == n) {
-        kf = it->second;
-    } else {
-        if (n && !xyzi) { set_error("mrgfe_batch_add_pair_keyed: key %llu is not in the store (or has another size) and no cloud was given", static_cast<unsigned long long>(key)); return MRGFE_ERR_INVALID; }
-        if (it != b->store.end()) {  // same key, different cloud: replace — unless this batch already uses the old one
-            if (it->second->last_epoch == b->epoch) { set_error("mrgfe_batch_add_pair_keyed: key %llu is already used in this batch with %u points", static_cast<unsigned long long>(key), it->second->n); return MRGFE_ERR_INVALID; }
-            store_erase(b, it);
+    return abi_guard("mrgfe_batch_add_pair_keyed", [&]() -> int {
+        MRGFE_TRY(check_count(n, "mrgfe_batch_add_pair_keyed"));
+        if (!b || !guess) { set_error("NULL argument"); return MRGFE_ERR_INVALID; }
+        if (key == 0) return mrgfe_batch_add_pair(b, target, xyzi, n, stride, guess);
+        MRGFE_LOCK(b->ctx);
+        MRGFE_TRY(b->ctx->bind());
+        if (n > 0x7fffffffu) { set_error("cloud too large"); return MRGFE_ERR_INVALID; }
+        mrgfe_batch::Keyframe* kf = nullptr;
+        auto it = b->store.find(key);
+        if (it != b->store.end() && it->second->n == n) {
+            kf = it->second.get();
+        } else {
+            if (n && !xyzi) { set_error("mrgfe_batch_add_pair_keyed: key %llu is not in the store (or has another size) and no cloud was given", static_cast<unsigned long long>(key)); return MRGFE_ERR_INVALID; }
+            if (it != b->store.end()) {  // same key, different cloud: replace — unless this batch already uses the old one
+                if (it->second->last_epoch == b->epoch) { set_error("mrgfe_batch_add_pair_keyed: key %llu is already used in this batch with %u points", static_cast<unsigned long long>(key), it->second->n); return MRGFE_ERR_INVALID; }
+                b->store.erase(it);
+            }
+            store_make_room(b, n * 16 + (!is_ndt(b->params.method) ? n * 48 : 0));
+            std::unique_ptr<mrgfe_batch::Keyframe> fresh(new (std::nothrow) mrgfe_batch::Keyframe());
+            if (!fresh) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+            MRGFE_TRY(fresh->cloud.ensure(std::max<size_t>(n, 1) * 16));
+            if (n) MRGFE_TRY(upload_cloud(b->ctx, xyzi, n, stride, fresh->cloud.p));
+            fresh->n = static_cast<uint32_t>(n);
+            kf = fresh.get();
+            b->store[key] = std::move(fresh);
         }
-        store_make_room(b, n * 16 + (!is_ndt(b->params.method) ? n * 48 : 0));
-        kf = new (std::nothrow) mrgfe_batch::Keyframe();
-        if (!kf) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-        int rc = kf->cloud.ensure(std::max<size_t>(n, 1) * 16);
-        if (rc == MRGFE_OK && n) rc = upload_cloud(b->ctx, xyzi, n, stride, kf->cloud.p);
-        if (rc != MRGFE_OK) { kf->cloud.release(); delete kf; return rc; }
-        kf->n = static_cast<uint32_t>(n);
-        b->store[key] = kf;
-    }
-    kf->last_epoch = b->epoch;
-    kf->last_tick = ++b->tick;
-    float g[16];
-    col2row(guess, g);
-    const int pair = b->ndt->add_pair_device(target, kf->cloud.p, n, g);
-    if (pair >= 0) {
-        if (b->pair_key.size() <= static_cast<size_t>(pair)) b->pair_key.resize(pair + 1, 0);
-        b->pair_key[pair] = key;
-    }
-    return pair;
+        kf->last_epoch = b->epoch;
+        kf->last_tick = ++b->tick;
+        float g[16];
+        col2row(guess, g);
+        const int pair = b->ndt->add_pair_device(target, kf->cloud.p, n, g);
+        if (pair >= 0) {
+            if (b->pair_key.size() <= static_cast<size_t>(pair)) b->pair_key.resize(pair + 1, 0);
+            b->pair_key[pair] = key;
+        }
+        return pair;
+    });
 }
 int mrgfe_batch_has_cloud(const mrgfe_batch* b, uint64_t key, size_t* n)
 {
@@ -1302,7 +1296,7 @@ int mrgfe_batch_forget(mrgfe_batch* b, uint64_t key)
     for (auto it = b->store.begin(); it != b->store.end();) {
         if (key != 0 && it->first != key) { ++it; continue; }
         if (it->second->last_epoch == b->epoch && !b->pair_key.empty()) { set_error("mrgfe_batch_forget: key %llu is used by the current batch (clear it first)", static_cast<unsigned long long>(it->first)); return MRGFE_ERR_STATE; }
-        it = store_erase(b, it);
+        it = b->store.erase(it);
     }
     return MRGFE_OK;
 }
@@ -1337,29 +1331,33 @@ static int batch_align_timed(mrgfe_batch* b, double fitness_max_range, mrgfe_pai
 
 int mrgfe_batch_align(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results)
 {
-    if (!b || !results) { set_error("mrgfe_batch_align: NULL argument"); return MRGFE_ERR_INVALID; }
-    return batch_align_timed(b, fitness_max_range, results, nullptr);
+    return abi_guard("mrgfe_batch_align", [&]() -> int {
+        if (!b || !results) { set_error("mrgfe_batch_align: NULL argument"); return MRGFE_ERR_INVALID; }
+        return batch_align_timed(b, fitness_max_range, results, nullptr);
+    });
 }
 
 int mrgfe_batch_align_best(mrgfe_batch* b, double fitness_max_range, double score_cap, const int32_t* group, int n_groups, mrgfe_pair_result* results, int32_t* fit_state,
                            int32_t* best, double* best_score)
 {
-    if (!b || !results || n_groups < 0 || (n_groups > 0 && (!best || !best_score))) { set_error("mrgfe_batch_align_best: NULL argument"); return MRGFE_ERR_INVALID; }
-    MRGFE_LOCK(b->ctx);
-    const int P = b->ndt->n_pairs();
-    if (P > 0 && !group) { set_error("mrgfe_batch_align_best: NULL group"); return MRGFE_ERR_INVALID; }
-    if (!(fitness_max_range >= 0) || std::isnan(score_cap)) { set_error("mrgfe_batch_align_best: fitness_max_range must be >= 0 and score_cap a number"); return MRGFE_ERR_INVALID; }
-    for (int i = 0; i < P; ++i)
-        if (group[i] < -1 || group[i] >= n_groups) { set_error("mrgfe_batch_align_best: group[%d] = %d is not -1 or in [0, %d)", i, group[i], n_groups); return MRGFE_ERR_INVALID; }
-    std::vector<int32_t> state(static_cast<size_t>(std::max(P, 1)), kFitSkipped);
-    BatchSelect sel{score_cap, group, n_groups, state.data()};
-    MRGFE_TRY(batch_align_timed(b, fitness_max_range, results, &sel));
-    std::vector<double>  fit(static_cast<size_t>(std::max(P, 1)));
-    std::vector<int32_t> conv(static_cast<size_t>(std::max(P, 1)));
-    for (int i = 0; i < P; ++i) { fit[i] = results[i].fitness; conv[i] = results[i].converged; }
-    fit_select_groups(P, fit.data(), conv.data(), group, n_groups, score_cap, best, best_score);
-    if (fit_state) std::memcpy(fit_state, state.data(), sizeof(int32_t) * static_cast<size_t>(P));
-    return MRGFE_OK;
+    return abi_guard("mrgfe_batch_align_best", [&]() -> int {
+        if (!b || !results || n_groups < 0 || (n_groups > 0 && (!best || !best_score))) { set_error("mrgfe_batch_align_best: NULL argument"); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(b->ctx);
+        const int P = b->ndt->n_pairs();
+        if (P > 0 && !group) { set_error("mrgfe_batch_align_best: NULL group"); return MRGFE_ERR_INVALID; }
+        if (!(fitness_max_range >= 0) || std::isnan(score_cap)) { set_error("mrgfe_batch_align_best: fitness_max_range must be >= 0 and score_cap a number"); return MRGFE_ERR_INVALID; }
+        for (int i = 0; i < P; ++i)
+            if (group[i] < -1 || group[i] >= n_groups) { set_error("mrgfe_batch_align_best: group[%d] = %d is not -1 or in [0, %d)", i, group[i], n_groups); return MRGFE_ERR_INVALID; }
+        std::vector<int32_t> state(static_cast<size_t>(std::max(P, 1)), kFitSkipped);
+        BatchSelect sel{score_cap, group, n_groups, state.data()};
+        MRGFE_TRY(batch_align_timed(b, fitness_max_range, results, &sel));
+        std::vector<double>  fit(static_cast<size_t>(std::max(P, 1)));
+        std::vector<int32_t> conv(static_cast<size_t>(std::max(P, 1)));
+        for (int i = 0; i < P; ++i) { fit[i] = results[i].fitness; conv[i] = results[i].converged; }
+        fit_select_groups(P, fit.data(), conv.data(), group, n_groups, score_cap, best, best_score);
+        if (fit_state) std::memcpy(fit_state, state.data(), sizeof(int32_t) * static_cast<size_t>(P));
+        return MRGFE_OK;
+    });
 }
 
 int mrgfe_batch_select_stats(const mrgfe_batch* b, double out[8])
@@ -1427,16 +1425,15 @@ static int gicp_align_batch(mrgfe_batch* b, mrgfe_pair_result* results)
     NdtEngine& e = *b->ndt;
     const int P = e.n_pairs();
     MRGFE_TRY(b->ctx->bind());
-    if (b->gicp.size() < static_cast<size_t>(e.n_targets())) b->gicp.resize(e.n_targets(), nullptr);
-    if (!b->gicp_batch) b->gicp_batch = new GicpBatch(b->ctx);
-    for (size_t i = P; i < b->gicp_pairs.size(); ++i) b->gicp_pairs[i].release();
-    b->gicp_pairs.resize(P);
+    if (b->gicp.size() < static_cast<size_t>(e.n_targets())) b->gicp.resize(e.n_targets());
+    if (!b->gicp_batch) b->gicp_batch = std::make_unique<GicpBatch>(b->ctx);
+    b->gicp_pairs.resize(P);  // (pairs beyond P free their buffers)
     for (int i = 0; i < P; ++i) {
         const NdtPairInfo& p = e.pair(i);
         const NdtTargetInfo& t = e.target(p.target);
-        GicpEngine*& g = b->gicp[p.target];
+        std::unique_ptr<GicpEngine>& g = b->gicp[p.target];
         if (!g) {
-            g = new GicpEngine(b->ctx, gicp_params_from(b->params));
+            g = std::make_unique<GicpEngine>(b->ctx, gicp_params_from(b->params));
             MRGFE_TRY(g->set_target(t.d_pts, t.n));
         }
         GicpBatchPair& bp = b->gicp_pairs[i];
@@ -1446,7 +1443,7 @@ static int gicp_align_batch(mrgfe_batch* b, mrgfe_pair_result* results)
         bp.ext_cov = nullptr;
         bp.ext_cov_k = nullptr;
         if (static_cast<size_t>(i) < b->pair_key.size() && b->pair_key[i]) {
-            mrgfe_batch::Keyframe* kf = b->store.at(b->pair_key[i]);
+            mrgfe_batch::Keyframe* kf = b->store.at(b->pair_key[i]).get();
             bp.ext_cov = &kf->cov;
             bp.ext_cov_k = &kf->cov_k;
         }
@@ -1555,12 +1552,17 @@ struct FitOverlap {
             while (b->fit_ctxs.size() < n_builders) {
                 mrgfe_ctx* fc = nullptr;
                 if (ctx_create_like(b->ctx, &fc) != MRGFE_OK) return MRGFE_ERR_HIP;  // (same compute-unit mask as the batch's own context)
-                b->fit_ctxs.push_back(fc);
+                CtxPtr owned(fc);
+                b->fit_ctxs.push_back(std::move(owned));
             }
             // the early fitness pass runs on a context of its own whose streams have the device's LOWEST priority: the stragglers' small launches
             // on the batch's stream are dispatched ahead of the pass's workgroups as slots free up (at equal priority the tail's rounds took twice
             // as long beside the pass: what the overlap gained, the rounds lost)
-            if (early_on && !b->early_ctx && ctx_create_like(b->ctx, &b->early_ctx, -1) != MRGFE_OK) return MRGFE_ERR_HIP;
+            if (early_on && !b->early_ctx) {
+                mrgfe_ctx* ec = nullptr;
+                if (ctx_create_like(b->ctx, &ec, -1) != MRGFE_OK) return MRGFE_ERR_HIP;
+                b->early_ctx.reset(ec);
+            }
             // the target clouds reach the device by asynchronous copies (and gathers) on the batch's stream: the helper streams
             // must not read them before those have finished
             MRGFE_TRY(b->ctx->bind());
@@ -1569,7 +1571,7 @@ struct FitOverlap {
             for (size_t w = 0; w < n_builders; ++w)
                 threads.emplace_back([this, w, n_builders, n_chunks, chunk] {
                     const NdtEngine& e = *b->ndt;
-                    mrgfe_ctx* fc = b->fit_ctxs[w];
+                    mrgfe_ctx* fc = b->fit_ctxs[w].get();
                     std::lock_guard<std::recursive_mutex> lock(fc->mu);
                     if (fc->bind() != MRGFE_OK) { fail(MRGFE_ERR_HIP, mrgfe_last_error()); return; }
                     if (hipStreamWaitEvent(fc->stream, b->uploads_done, 0) != hipSuccess) { fail(MRGFE_ERR_HIP, "helper stream could not wait for the uploads"); return; }
@@ -1603,7 +1605,7 @@ struct FitOverlap {
         threads.emplace_back([this, P, early_div] {
             const NdtEngine& e = *b->ndt;
             NdtSnapshotPort& port = *b->port;
-            mrgfe_ctx* fc = b->early_ctx;
+            mrgfe_ctx* fc = b->early_ctx.get();
             std::lock_guard<std::recursive_mutex> lock(fc->mu);
             if (fc->bind() != MRGFE_OK) { fail(MRGFE_ERR_HIP, mrgfe_last_error()); return; }
             const uint32_t threshold = static_cast<uint32_t>(std::max(1, P / early_div));
@@ -1928,7 +1930,7 @@ int mrgfe_dbg_exp(mrgfe_ctx* ctx, const double* x, size_t n, int on_device, doub
     }
     MRGFE_LOCK(ctx);
     MRGFE_TRY(ctx->bind());
-    DevBuf dx, dout;
+    DevBuf dout, dx;  // (freed at the return, `dx` first)
     MRGFE_TRY(dx.ensure(std::max<size_t>(n, 1) * 8));
     int st = dout.ensure(std::max<size_t>(n, 1) * 8);
     if (st == MRGFE_OK && n) {
@@ -1938,8 +1940,6 @@ int mrgfe_dbg_exp(mrgfe_ctx* ctx, const double* x, size_t n, int on_device, doub
         if (hipStreamSynchronize(ctx->stream) != hipSuccess && st == MRGFE_OK) st = MRGFE_ERR_HIP;
         if (st == MRGFE_ERR_HIP) set_error("mrgfe_dbg_exp: a HIP call failed");
     }
-    dx.release();
-    dout.release();
     return st;
 }
 
@@ -1975,6 +1975,7 @@ int mrgfe_dbg_ctl_math(mrgfe_ctx* ctx, const double* cases48, int n, int on_devi
 }
 #ifdef MRGFE_TESTING
 long mrgfe_dbg_fail_alloc_after(long k) { return fail_alloc_after(k); }
+long mrgfe_dbg_live_allocations(void) { return live_allocations(); }
 #endif
 
 int mrgfe_batch_rounds(const mrgfe_batch* b) { return b && b->ndt ? b->ndt->rounds() : 0; }
@@ -2050,25 +2051,29 @@ static int floor_check(const mrgfe_floor_params* p, const char* fn)
 int mrgfe_floor_detect(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const float* xyzi, size_t n, size_t stride, mrgfe_floor_result* res, float* out_filtered,
                        float* out_inliers)
 {
-    MRGFE_TRY(check_count(n, "mrgfe_floor_detect"));
-    if (!ctx || !p || !res || (n && !xyzi)) { set_error("mrgfe_floor_detect: NULL argument"); return MRGFE_ERR_INVALID; }
-    MRGFE_TRY(floor_check(p, "mrgfe_floor_detect"));
-    MRGFE_LOCK(ctx);
-    MRGFE_TRY(ctx->bind());
-    DevBuf& din = ctx->fl_buf[10];
-    MRGFE_TRY(din.ensure(std::max<size_t>(n, 1) * 16));
-    if (n) MRGFE_TRY(upload_cloud(ctx, xyzi, n, stride, din.p));
-    return floor_detect(ctx, p, din.as<float4>(), n, res, out_filtered, out_inliers);
+    return abi_guard("mrgfe_floor_detect", [&]() -> int {
+        MRGFE_TRY(check_count(n, "mrgfe_floor_detect"));
+        if (!ctx || !p || !res || (n && !xyzi)) { set_error("mrgfe_floor_detect: NULL argument"); return MRGFE_ERR_INVALID; }
+        MRGFE_TRY(floor_check(p, "mrgfe_floor_detect"));
+        MRGFE_LOCK(ctx);
+        MRGFE_TRY(ctx->bind());
+        DevBuf& din = ctx->fl_buf[10];
+        MRGFE_TRY(din.ensure(std::max<size_t>(n, 1) * 16));
+        if (n) MRGFE_TRY(upload_cloud(ctx, xyzi, n, stride, din.p));
+        return floor_detect(ctx, p, din.as<float4>(), n, res, out_filtered, out_inliers);
+    });
 }
 int mrgfe_floor_detect_device(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const void* d_xyzi, size_t n, mrgfe_floor_result* res, float* out_filtered,
                               float* out_inliers)
 {
-    MRGFE_TRY(check_count(n, "mrgfe_floor_detect_device"));
-    if (!ctx || !p || !res || (n && !d_xyzi)) { set_error("mrgfe_floor_detect_device: NULL argument"); return MRGFE_ERR_INVALID; }
-    MRGFE_TRY(floor_check(p, "mrgfe_floor_detect_device"));
-    MRGFE_LOCK(ctx);
-    MRGFE_TRY(ctx->bind());
-    return floor_detect(ctx, p, static_cast<const float4*>(d_xyzi), n, res, out_filtered, out_inliers);
+    return abi_guard("mrgfe_floor_detect_device", [&]() -> int {
+        MRGFE_TRY(check_count(n, "mrgfe_floor_detect_device"));
+        if (!ctx || !p || !res || (n && !d_xyzi)) { set_error("mrgfe_floor_detect_device: NULL argument"); return MRGFE_ERR_INVALID; }
+        MRGFE_TRY(floor_check(p, "mrgfe_floor_detect_device"));
+        MRGFE_LOCK(ctx);
+        MRGFE_TRY(ctx->bind());
+        return floor_detect(ctx, p, static_cast<const float4*>(d_xyzi), n, res, out_filtered, out_inliers);
+    });
 }
 int mrgfe_dbg_floor_ransac(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, double threshold, int* has_model, float coeffs[4], int32_t* inliers,
                            size_t* n_inliers, int32_t* iterations, int32_t* skipped)

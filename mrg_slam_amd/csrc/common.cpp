@@ -8,6 +8,7 @@
 #include <unistd.h>
 #endif
 #include "ingest.h"
+#include "nn_grid.h"
 
 #include <algorithm>
 #include <condition_variable>
@@ -47,6 +48,9 @@ static bool poison_allocations() { static const bool v = std::getenv("MRGFE_POIS
 #ifdef MRGFE_TESTING
 static std::atomic<long> g_fail_alloc_in{[] { const char* e = std::getenv("MRGFE_FAIL_ALLOC_AFTER"); return e ? std::atol(e) : -1L; }()};
 static std::atomic<long> g_allocs{0};
+static std::atomic<long> g_live{0};  // device buffers, pinned buffers and arena chunks that exist now (mrgfe_dbg_live_allocations)
+static inline void count_live(long d) { g_live.fetch_add(d, std::memory_order_relaxed); }
+long live_allocations() { return g_live.load(std::memory_order_relaxed); }
 static bool inject_alloc_failure()
 {
     g_allocs.fetch_add(1, std::memory_order_relaxed);
@@ -89,6 +93,7 @@ static const bool g_abrt_installed = [] {
 }();
 #else
 static inline bool inject_alloc_failure() { return false; }
+static inline void count_live(long) {}
 #endif
 
 // ---- roctx ranges -------------------------------------------------------------------------------------------------------------------
@@ -120,16 +125,17 @@ int DevBuf::ensure(size_t bytes)
     size_t want = cap ? cap : 4096;
     while (want < bytes) want += want / 2 + 4096;
     want = (want + 255) & ~size_t(255);
-    if (p) { MRGFE_HIP_CHECK(hipFree(p)); p = nullptr; cap = 0; }
+    if (p) { MRGFE_HIP_CHECK(hipFree(p)); p = nullptr; cap = 0; count_live(-1); }
     if (inject_alloc_failure()) return MRGFE_ERR_HIP;
     MRGFE_HIP_CHECK(hipMalloc(&p, want));
+    count_live(+1);
     cap = want;
     if (poison_allocations()) { MRGFE_HIP_CHECK(hipMemset(p, 0xCD, want)); MRGFE_HIP_CHECK(hipDeviceSynchronize()); }
     return MRGFE_OK;
 }
 void DevBuf::release()
 {
-    if (p) (void)hipFree(p);
+    if (p) { (void)hipFree(p); count_live(-1); }
     p = nullptr;
     cap = 0;
 }
@@ -138,16 +144,17 @@ int PinBuf::ensure(size_t bytes)
     if (bytes <= cap) return MRGFE_OK;
     size_t want = cap ? cap : 4096;
     while (want < bytes) want += want / 2 + 4096;
-    if (p) { MRGFE_HIP_CHECK(hipHostFree(p)); p = nullptr; cap = 0; }
+    if (p) { MRGFE_HIP_CHECK(hipHostFree(p)); p = nullptr; cap = 0; count_live(-1); }
     if (inject_alloc_failure()) return MRGFE_ERR_HIP;
     MRGFE_HIP_CHECK(hipHostMalloc(&p, want, hipHostMallocDefault));
+    count_live(+1);
     cap = want;
     if (poison_allocations()) std::memset(p, 0xCD, want);
     return MRGFE_OK;
 }
 void PinBuf::release()
 {
-    if (p) (void)hipHostFree(p);
+    if (p) { (void)hipHostFree(p); count_live(-1); }
     p = nullptr;
     cap = 0;
 }
@@ -168,6 +175,7 @@ int Arena::alloc(size_t bytes, void** out)
     c.p = nullptr;
     if (inject_alloc_failure()) return MRGFE_ERR_HIP;
     MRGFE_HIP_CHECK(hipMalloc(&c.p, c.cap));
+    count_live(+1);
     if (poison_allocations()) { MRGFE_HIP_CHECK(hipMemset(c.p, 0xCD, c.cap)); MRGFE_HIP_CHECK(hipDeviceSynchronize()); }
     *out = c.p;
     c.used = bytes;
@@ -180,7 +188,7 @@ void Arena::reset()
 }
 void Arena::release()
 {
-    for (auto& c : chunks) (void)hipFree(c.p);
+    for (auto& c : chunks) { (void)hipFree(c.p); count_live(-1); }
     chunks.clear();
 }
 
@@ -377,6 +385,9 @@ void drain_caller_dma(mrgfe_ctx* ctx)
 
 }  // namespace mrgfe
 
+mrgfe_ctx::mrgfe_ctx() = default;
+mrgfe_ctx::~mrgfe_ctx() = default;
+
 int mrgfe_ctx::bind()
 {
     MRGFE_HIP_CHECK(hipSetDevice(device));
@@ -488,33 +499,7 @@ void mrgfe_ctx_destroy(mrgfe_ctx* ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    mrgfe::ctx_tmp_grid_free(ctx);
-    for (auto& b : ctx->pf_buf) b.release();
-    ctx->pf_state.release();
-    ctx->pf_status.release();
-    for (auto& b : ctx->fl_buf) b.release();
-    ctx->fl_pin.release();
-    for (auto& e : ctx->fl_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& b : ctx->scratch) b.release();
-    ctx->sort_chunks.release();
-    for (auto& b : ctx->pin) b.release();
-    for (auto& b : ctx->up_pin) b.release();
-    ctx->up_raw.release();
-    ctx->up_out.release();
-    for (auto& e : ctx->up_ev) if (e) (void)hipEventDestroy(e);
-    for (auto& b : ctx->stage_pin) b.release();
-    for (auto& e : ctx->stage_ev) if (e) (void)hipEventDestroy(e);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    for (auto& pr : ctx->ev_mode) for (auto& e : pr) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->ev_fit) if (e) (void)hipEventDestroy(e);
-    for (auto& e : ctx->ev_side) if (e) (void)hipEventDestroy(e);
-    if (ctx->side) (void)hipStreamDestroy(ctx->side);
-    for (auto& e : ctx->knn_stats.ev) if (e) (void)hipEventDestroy(e);
-    ctx->knn_stats.counter.release();
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;  // the members free themselves, `stream` last (common.h)
 }
 
 int mrgfe_pin_host_buffer(mrgfe_ctx* ctx, void* p, size_t bytes)

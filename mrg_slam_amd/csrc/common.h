@@ -7,9 +7,14 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <exception>
 #include <functional>
+#include <memory>
 #include <mutex>
+#include <new>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/mrgfe.h"
@@ -20,6 +25,7 @@ namespace mrgfe {
 void set_error(const char* fmt, ...);
 #ifdef MRGFE_TESTING
 long fail_alloc_after(long k);  // allocation-failure injector (common.cpp): the k-th allocation from now fails (k < 0: off); returns the allocations counted since the last call
+long live_allocations();      // device buffers, pinned buffers and arena chunks allocated and not yet freed
 #endif
 
 #define MRGFE_HIP_CHECK(expr)                                                                                   \
@@ -37,12 +43,21 @@ long fail_alloc_after(long k);  // allocation-failure injector (common.cpp): the
         if (_s != MRGFE_OK) return _s; \
     } while (0)
 
+// Every device / pinned allocation and every event / stream of the library lives in one of the move-only owners below: the destructor frees, a
+// move empties its source, and nothing is copied.  Each owner is a member of (or is reachable from) a handle that an explicit *_destroy call frees with
+// its device bound; none has static or thread-local lifetime, where its destructor would run after the HIP runtime has shut down.
 // grow-only device buffer (avoids a hipMalloc per scan: SURVEY.md §8b "Ownership")
 struct DevBuf {
     void*  p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~DevBuf() { release(); }
     int    ensure(size_t bytes);
-    void   release();
+    void   release();  // free now (the HIP status is ignored, as in the destructor)
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
@@ -50,10 +65,34 @@ struct DevBuf {
 struct PinBuf {
     void*  p = nullptr;
     size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    PinBuf(PinBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    PinBuf& operator=(PinBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~PinBuf() { release(); }
     int    ensure(size_t bytes);
     void   release();
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
+
+// An event / a stream that is destroyed with its owner.  It converts to the raw handle, and `&owner` is the address of that handle, so create, record
+// and launch sites read as they do with a raw handle; the handle is created where it is first needed, as before.
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(const Handle&) = delete;
+    Handle& operator=(const Handle&) = delete;
+    Handle(Handle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Handle& operator=(Handle&& o) noexcept { if (this != std::addressof(o)) { reset(); h = o.h; o.h = nullptr; } return *this; }
+    ~Handle() { reset(); }
+    void reset() { if (h) (void)Destroy(h); h = nullptr; }
+    operator H() const { return h; }
+    H* operator&() { return &h; }
+};
+using Event = Handle<hipEvent_t, hipEventDestroy>;
+using Stream = Handle<hipStream_t, hipStreamDestroy>;
 
 // Wait for a record a kernel writes into pinned host memory (system-scope release store of its last word): `done()` reads it.  A bounded spin with
 // a pause instruction between the loads (the poll saves ~10 us per round over a stream wait, which is what a single registration's latency is made
@@ -100,13 +139,42 @@ void host_parallel_hot(bool hot);
 
 // bump allocator over a few large device chunks; pointers stay valid until reset()
 struct Arena {
-    struct Chunk { void* p; size_t cap; size_t used; };
+    struct Chunk { void* p; size_t cap; size_t used; };  // (a plain record: the arena owns the memory)
     std::vector<Chunk> chunks;
     size_t chunk_bytes = size_t(64) << 20;
+    Arena() = default;
+    Arena(const Arena&) = delete;
+    Arena& operator=(const Arena&) = delete;
+    Arena(Arena&& o) noexcept : chunks(std::move(o.chunks)), chunk_bytes(o.chunk_bytes) { o.chunks.clear(); }
+    Arena& operator=(Arena&& o) noexcept { if (this != &o) { release(); chunks = std::move(o.chunks); chunk_bytes = o.chunk_bytes; o.chunks.clear(); } return *this; }
+    ~Arena() { release(); }
     int  alloc(size_t bytes, void** out);
     void reset();    // keep chunks, forget allocations
     void release();  // free chunks
 };
+
+static_assert(!std::is_copy_constructible<DevBuf>::value && std::is_nothrow_move_constructible<DevBuf>::value, "DevBuf is a move-only owner");
+static_assert(!std::is_copy_constructible<PinBuf>::value && std::is_nothrow_move_constructible<PinBuf>::value, "PinBuf is a move-only owner");
+static_assert(!std::is_copy_constructible<Arena>::value && std::is_nothrow_move_constructible<Arena>::value, "Arena is a move-only owner");
+static_assert(!std::is_copy_constructible<Event>::value && std::is_nothrow_move_constructible<Event>::value, "Event is a move-only owner");
+static_assert(!std::is_copy_constructible<Stream>::value && std::is_nothrow_move_constructible<Stream>::value, "Stream is a move-only owner");
+
+// The one exception boundary of the C ABI: entry points that construct engines, grow host containers or start threads run their body through this, so that
+// a C++ exception becomes an error code and a message, never std::terminate or an exception in the caller's frames.
+template <class F>
+int abi_guard(const char* fn, F&& body) noexcept
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        set_error("%s: out of host memory", fn);
+    } catch (const std::exception& e) {
+        set_error("%s: %s", fn, e.what());
+    } catch (...) {
+        set_error("%s: unknown exception", fn);
+    }
+    return MRGFE_ERR_INVALID;
+}
 
 }  // namespace mrgfe
 
@@ -116,8 +184,8 @@ struct Arena {
 
 struct mrgfe_ctx;
 namespace mrgfe {
-class NnGrid;
-void ctx_tmp_grid_free(mrgfe_ctx* ctx);  // nn_grid.hip
+class NnGrid;             // nn_grid.h
+struct NnDeviceDrivenGrid;
 }
 
 namespace mrgfe {
@@ -137,7 +205,7 @@ struct FitStats {
 };
 // the last k-NN launch on a context (NnGrid::knn_device: GICP covariances, StatisticalOutlierRemoval, mrgfe_knn)
 struct KnnStats {
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Event      ev[2];
     DevBuf     counter;      // candidates measured (diagnostic counters on)
     uint64_t   queries = 0, launches = 0;
     int        k = 0;
@@ -146,39 +214,42 @@ struct KnnStats {
 }  // namespace mrgfe
 
 struct mrgfe_ctx {
+    mrgfe_ctx();
+    ~mrgfe_ctx();  // (both in common.cpp, where the grid types are complete)
     int          device = 0;
-    hipStream_t  stream = nullptr;
-    hipEvent_t   ev0 = nullptr, ev1 = nullptr;  // timing of the dominant kernel on `stream`
-    hipEvent_t   ev_mode[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};  // per NDT kernel variant
+    // Members go in reverse order of declaration: `stream` stands first so that every buffer, every event and the `side` stream are gone before it is.
+    mrgfe::Stream stream;
+    mrgfe::Event ev0, ev1;                      // timing of the dominant kernel on `stream`
+    mrgfe::Event ev_mode[3][2];                 // per NDT kernel variant
     mrgfe::DevBuf scratch[15];                  // named by the algorithms that use them
     mrgfe::DevBuf sort_chunks;                  // radix_sort_pairs: digit counts per chunk of 64 tiles (sorts of thousands of tiles: the map cloud)
     mrgfe::PinBuf pin[4];
     mrgfe::PinBuf up_pin[2];                    // upload_cloud staging ring: the host packs cloud k + 1 while cloud k is on the wire
     mrgfe::DevBuf up_raw, up_out;               // raw strided records waiting for the device gather / packed result of mrgfe_ingest_pointcloud2
-    hipEvent_t   up_ev[2] = {nullptr, nullptr};
+    mrgfe::Event up_ev[2];
     bool         up_busy[2] = {false, false};
     int          up_next = 0;
     bool         dma_from_caller = false;     // a zero-copy upload was queued since the last wait for the stream (drain_caller_dma on error paths)
     bool         zero_copy_uploads = false;   // mrgfe_ctx_set_zero_copy_uploads: clouds in page-locked host memory go up by DMA from the caller's buffer
-    hipEvent_t   ev_fit[4] = {nullptr, nullptr, nullptr, nullptr};  // around the passes of nn_fitness_batch
+    mrgfe::Event ev_fit[4];                     // around the passes of nn_fitness_batch
     int          priority = 0;                  // > 0: streams at the device's highest priority, < 0: at its lowest (throughput work beside latency-critical rounds)
     std::vector<uint32_t> cu_mask;              // non-empty: every stream of this context is confined to these compute units (mrgfe_ctx_create_reserving)
     int          make_stream(hipStream_t* st) const;  // a further stream of this context: same compute-unit mask
-    hipStream_t  side = nullptr;                // second stream of nn_fitness_batch: the pyramid walk of the unseeded queries beside the sweep
-    hipEvent_t   ev_side[4] = {nullptr, nullptr, nullptr, nullptr};  // fork, start and end of the side work, join
+    mrgfe::Stream side;                         // second stream of nn_fitness_batch: the pyramid walk of the unseeded queries beside the sweep
+    mrgfe::Event ev_side[4];                    // fork, start and end of the side work, join
     mrgfe::FitStats fit_stats;                  // of the last nn_fitness_batch on this context
     mrgfe::KnnStats knn_stats;                  // of the last k-NN launch on this context
     // descriptor staging ring: small host tables (job records, offsets, slice tables) whose owner does not outlive the call that
     // enqueues their copy go through one of these pinned slots; a slot is reused only after the event behind its copy has passed
     static constexpr int kStageSlots = 8;
     mrgfe::PinBuf stage_pin[kStageSlots];
-    hipEvent_t   stage_ev[kStageSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    mrgfe::Event stage_ev[kStageSlots];
     bool         stage_busy[kStageSlots] = {false, false, false, false, false, false, false, false};
     int          stage_next = 0;
     int          stage_h2d(void* d_dst, const void* src, size_t bytes, hipStream_t st);  // stream-ordered copy; `src` is free on return
     mrgfe::DevBuf pf_buf[2], pf_state;          // prefilter chain: ping-pong clouds and the device-resident state record (filters.hip)
     mrgfe::PinBuf pf_status;                    // ... and the few words the host reads at the chain's single wait
-    void*        pf_grid = nullptr;             // NnDeviceDrivenGrid of the radius filter (nn_grid.h), created on first use
+    std::unique_ptr<mrgfe::NnDeviceDrivenGrid> pf_grid;  // of the radius filter (nn_grid.h), created on first use
     // what the last mrgfe_prefilter_device of the device-driven chain left in the caller's buffer: the cloud, its size and a box that ENCLOSES it (the box of the
     // voxel centroids before the outlier filter, read with the chain's status words) — mrgfe_reg_set_source_from_prefilter builds the source's search grid on it
     const void*  pf_out_ptr = nullptr;
@@ -188,9 +259,9 @@ struct mrgfe_ctx {
     int          cu_count = 256;
     mrgfe::DevBuf fl_buf[11];                   // floor detection (floor.hip): clouds, flags, k-NN lists, RANSAC state / hypotheses / counts
     mrgfe::PinBuf fl_pin;                       // ... and the hypothesis records and counts the host reads after each RANSAC wave
-    hipEvent_t   fl_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // stage boundaries of the last floor detection (mrgfe_dbg_floor_stats)
+    mrgfe::Event fl_ev[5];                      // stage boundaries of the last floor detection (mrgfe_dbg_floor_stats)
     double       fl_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    mrgfe::NnGrid* tmp_grid = nullptr;          // reusable exact-NN grid of the stateless filter / fitness calls (nn_grid.hip)
+    std::unique_ptr<mrgfe::NnGrid> tmp_grid;    // reusable exact-NN grid of the stateless filter / fitness calls (nn_grid.hip)
     std::recursive_mutex mu;                    // serialises API calls that share this context's stream / workspaces
     int          bind();                        // hipSetDevice(device)
 };
@@ -212,5 +283,8 @@ struct TraceRange {
 int decode_layout(size_t layout, uint32_t* stride, uint32_t* xyz_off, int32_t* intensity_off);
 // a helper context of `parent` (builder threads of a batch, GICP lanes): same device, same compute-unit mask
 int ctx_create_like(const mrgfe_ctx* parent, mrgfe_ctx** out, int priority = 0);  // priority: see mrgfe_ctx::priority
+// ... and its owner: a member declared BEFORE the buffers that were filled on the helper's stream goes after them
+struct CtxDestroy { void operator()(mrgfe_ctx* c) const { mrgfe_ctx_destroy(c); } };
+using CtxPtr = std::unique_ptr<mrgfe_ctx, CtxDestroy>;
 
 }  // namespace mrgfe

@@ -378,15 +378,12 @@ int filter_statistical_outlier_device(mrgfe_ctx* ctx, const float4* d_in, size_t
     const uint32_t nn = static_cast<uint32_t>(n);
     const int      k1 = mean_k + 1;
     NnGrid& grid = ctx_tmp_grid(ctx);
-    int     rc = grid.build(ctx, d_in, n, 1.0f, NnGrid::kCrowdingKnn);
-    if (rc != MRGFE_OK) return rc;
-    DevBuf knn_i, knn_d, ddist;
-    auto cleanup = [&]() { knn_i.release(); knn_d.release(); ddist.release(); };
-    rc = knn_i.ensure(n * k1 * 4);
-    if (rc == MRGFE_OK) rc = knn_d.ensure(n * k1 * 4);
-    if (rc == MRGFE_OK) rc = ddist.ensure(n * 8);
-    if (rc == MRGFE_OK) rc = grid.knn_device(ctx, d_in, n, k1, knn_i.as<int32_t>(), knn_d.as<float>());
-    if (rc != MRGFE_OK) { cleanup(); return rc; }
+    MRGFE_TRY(grid.build(ctx, d_in, n, 1.0f, NnGrid::kCrowdingKnn));
+    DevBuf ddist, knn_d, knn_i;  // (per-call buffers, freed at the return, `knn_i` first)
+    MRGFE_TRY(knn_i.ensure(n * k1 * 4));
+    MRGFE_TRY(knn_d.ensure(n * k1 * 4));
+    MRGFE_TRY(ddist.ensure(n * 8));
+    MRGFE_TRY(grid.knn_device(ctx, d_in, n, k1, knn_i.as<int32_t>(), knn_d.as<float>()));
     float*    d_dist = ddist.as<float>();
     uint32_t* d_valid = reinterpret_cast<uint32_t*>(d_dist + n);
     hipLaunchKernelGGL(sor_mean_dist_kernel, dim3((nn + 255) / 256), dim3(256), 0, st, knn_d.as<float>(), nn, k1, d_dist, d_valid);
@@ -395,7 +392,6 @@ int filter_statistical_outlier_device(mrgfe_ctx* ctx, const float4* d_in, size_t
     std::vector<uint32_t> h_valid(n);
     if (hipMemcpyAsync(h_dist.data(), d_dist, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(h_valid.data(), d_valid, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess) {
-        cleanup();
         set_error("statistical outlier: device to host copy failed");
         return MRGFE_ERR_HIP;
     }
@@ -411,14 +407,11 @@ int filter_statistical_outlier_device(mrgfe_ctx* ctx, const float4* d_in, size_t
     const double variance = (sq_sum - sum * sum / static_cast<double>(valid)) / (static_cast<double>(valid) - 1);
     const double thr = mean + stddev_mul * std::sqrt(variance);
     DevBuf& dfl = ctx->scratch[7];
-    rc = dfl.ensure(n * 4);
-    if (rc == MRGFE_OK) {
-        hipLaunchKernelGGL(sor_flags_kernel, dim3((nn + 255) / 256), dim3(256), 0, st, d_dist, nn, thr, dfl.as<uint32_t>());
-        uint32_t kept = 0;
-        rc = compact_by_flags(ctx, d_in, nn, dfl.as<uint32_t>(), d_out, &kept);
-        *out_n = kept;
-    }
-    cleanup();
+    MRGFE_TRY(dfl.ensure(n * 4));
+    hipLaunchKernelGGL(sor_flags_kernel, dim3((nn + 255) / 256), dim3(256), 0, st, d_dist, nn, thr, dfl.as<uint32_t>());
+    uint32_t kept = 0;
+    const int rc = compact_by_flags(ctx, d_in, nn, dfl.as<uint32_t>(), d_out, &kept);
+    *out_n = kept;
     return rc;
 }
 
@@ -428,17 +421,15 @@ static int host_wrap(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride,
 {
     *out_n = 0;
     if (n == 0) return MRGFE_OK;
-    DevBuf din, dout;  // per-call buffers: the scratch slots are all in use by the algorithms
-    int rc = din.ensure(n * 16);
-    if (rc == MRGFE_OK) rc = dout.ensure(n * 16);
-    if (rc == MRGFE_OK) rc = upload_cloud(ctx, xyzi, n, stride, din.p);
+    DevBuf dout, din;  // per-call buffers (the scratch slots are all in use by the algorithms), freed at the return, `din` first
+    MRGFE_TRY(din.ensure(n * 16));
+    MRGFE_TRY(dout.ensure(n * 16));
+    MRGFE_TRY(upload_cloud(ctx, xyzi, n, stride, din.p));
     size_t m = 0;
-    if (rc == MRGFE_OK) rc = f(din.as<float4>(), dout.as<float4>(), &m);
-    if (rc == MRGFE_OK) rc = download(ctx, dout.p, m, out);
-    if (rc == MRGFE_OK) *out_n = m;
-    din.release();
-    dout.release();
-    return rc;
+    MRGFE_TRY(f(din.as<float4>(), dout.as<float4>(), &m));
+    MRGFE_TRY(download(ctx, dout.p, m, out));
+    *out_n = m;
+    return MRGFE_OK;
 }
 
 // ---- the chain with its counts on the device (round 4) --------------------------------------------------------------------------------
@@ -691,8 +682,8 @@ int prefilter_set_device_driven(int mode)
 
 static NnDeviceDrivenGrid& pf_grid(mrgfe_ctx* ctx)
 {
-    if (!ctx->pf_grid) ctx->pf_grid = new NnDeviceDrivenGrid();
-    return *static_cast<NnDeviceDrivenGrid*>(ctx->pf_grid);
+    if (!ctx->pf_grid) ctx->pf_grid.reset(new NnDeviceDrivenGrid());
+    return *ctx->pf_grid;
 }
 
 // returns MRGFE_OK with *used = true when the device-driven chain produced the output, *used = false when the caller has to run the host-driven one

@@ -892,16 +892,7 @@ GicpPose make_pose(const double T[16], int variant)
 
 GicpEngine::~GicpEngine()
 {
-    if (ctx_) (void)hipSetDevice(ctx_->device);
-    tgt_grid_.release();
-    cov_grid_.release();
-    cur_grid_.release();
-    d_knn_i_.release(); d_knn_d_.release();
-    d_tgt_cov_.release(); d_src_cov_.release(); d_corr_.release(); d_mahal_.release(); d_partial_.release(); d_T_.release();
-    d_vox_.release(); d_vox_runs_.release(); d_cur_.release();
-    h_rec_.release();
-    d_terms_.release();
-    d_chunk_bounds_.release();
+    if (ctx_) (void)hipSetDevice(ctx_->device);  // the members free themselves on the engine's device
 }
 
 int GicpEngine::set_target(const void* d, size_t n)
@@ -923,7 +914,7 @@ int GicpEngine::set_source(const void* d, size_t n, const float* enclosing_box)
 int GicpEngine::source_becomes_target()
 {
     if (!src_cov_valid_ || n_src_ == 0) return set_target(d_src_, n_src_);  // nothing computed yet (an empty source has no grid): an ordinary target, prepared by the next align
-    std::swap(tgt_grid_, cov_grid_);  // (plain structs of device pointers: the buffers travel with them, the old target's are reused for the next source)
+    std::swap(tgt_grid_, cov_grid_);  // (the buffers travel with them, the old target's are reused for the next source)
     std::swap(d_tgt_cov_, d_src_cov_);
     d_tgt_ = d_src_;
     n_tgt_ = n_src_;
@@ -1780,18 +1771,10 @@ int GicpEngine::aligned_cloud(float* out)
 // ---- batched LM rounds -------------------------------------------------------------------------------------------------
 GicpBatch::~GicpBatch()
 {
-    if (ctx_) (void)hipSetDevice(ctx_->device);
-    for (Lane* l : lanes_) {
-        l->set.release(); l->views.clear(); l->knn_i.release(); l->knn_d.release();
-        mrgfe_ctx_destroy(l->ctx);
-        delete l;
-    }
-    d_pairs_.release(); d_evals_.release(); d_grids_.release(); d_partials_.release();
-    h_evals_.release(); h_results_.release();
-    if (done_) (void)hipEventDestroy(done_);
+    if (ctx_) (void)hipSetDevice(ctx_->device);  // the members free themselves on the batch's device
 }
 
-int GicpBatch::align_all(std::vector<GicpEngine*>& engines, std::vector<GicpBatchPair>& pairs)
+int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std::vector<GicpBatchPair>& pairs)
 {
     MRGFE_TRY(ctx_->bind());
     const int P = static_cast<int>(pairs.size());
@@ -1822,9 +1805,11 @@ int GicpBatch::align_all(std::vector<GicpEngine*>& engines, std::vector<GicpBatc
         if (const char* e = std::getenv("MRGFE_GICP_LANES")) want = std::atoi(e);
         const int n_lanes = std::max(1, std::min(std::min(want, 8), P));
         while (static_cast<int>(lanes_.size()) < n_lanes) {
-            Lane* l = new Lane();
-            if (ctx_create_like(ctx_, &l->ctx) != MRGFE_OK) { delete l; return MRGFE_ERR_HIP; }
-            lanes_.push_back(l);
+            auto l = std::make_unique<Lane>();
+            mrgfe_ctx* lc = nullptr;
+            if (ctx_create_like(ctx_, &lc) != MRGFE_OK) return MRGFE_ERR_HIP;
+            l->ctx.reset(lc);
+            lanes_.push_back(std::move(l));
         }
         std::vector<int> status(n_lanes, MRGFE_OK);
         std::vector<std::string> message(n_lanes);
@@ -1864,11 +1849,11 @@ int GicpBatch::align_all(std::vector<GicpEngine*>& engines, std::vector<GicpBatc
                     sizes.push_back(pairs[todo[w]].n);
                     views.push_back(&l.views[w - w0]);
                 }
-                int rc = l.set.build(l.ctx, clouds.data(), sizes.data(), static_cast<int>(w1 - w0), 1.0f, NnGrid::kCrowdingKnn, kNnMaxLevels, views.data());
+                int rc = l.set.build(l.ctx.get(), clouds.data(), sizes.data(), static_cast<int>(w1 - w0), 1.0f, NnGrid::kCrowdingKnn, kNnMaxLevels, views.data());
                 for (size_t w = w0; w < w1 && rc == MRGFE_OK; ++w) {
                     GicpBatchPair& p = pairs[todo[w]];
                     const int k = engines[p.target]->params().k_correspondences;
-                    rc = gicp_covariances_on_grid(l.ctx, k, p.d_src, p.n, p.ext_cov ? *p.ext_cov : p.cov, l.views[w - w0], l.knn_i, l.knn_d, false);
+                    rc = gicp_covariances_on_grid(l.ctx.get(), k, p.d_src, p.n, p.ext_cov ? *p.ext_cov : p.cov, l.views[w - w0], l.knn_i, l.knn_d, false);
                     if (rc == MRGFE_OK && p.ext_cov) *p.ext_cov_k = k;
                 }
                 if (rc != MRGFE_OK) { status[li] = rc; message[li] = mrgfe_last_error(); break; }
@@ -1887,7 +1872,7 @@ int GicpBatch::align_all(std::vector<GicpEngine*>& engines, std::vector<GicpBatc
     uint32_t part = 0, max_n = 0;
     for (int i = 0; i < P; ++i) {
         GicpBatchPair& p = pairs[i];
-        GicpEngine*    e = engines[p.target];
+        GicpEngine*    e = engines[p.target].get();
         MRGFE_TRY(p.corr.ensure(std::max<size_t>(p.n, 1) * 4));
         MRGFE_TRY(p.mahal.ensure(std::max<size_t>(p.n, 1) * 72));
         GicpPairDev d;

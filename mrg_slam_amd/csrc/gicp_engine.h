@@ -176,23 +176,22 @@ struct GicpBatchPair {
     DevBuf*       ext_cov = nullptr;
     int*          ext_cov_k = nullptr;
     GicpLmController ctl;
-    void release() { cov.release(); corr.release(); mahal.release(); }
 };
 class GicpBatch {
    public:
     explicit GicpBatch(mrgfe_ctx* ctx) : ctx_(ctx) {}
     ~GicpBatch();
     // engines[t] holds target t (set_target done); pairs: target index, device source cloud, guess (row-major)
-    int align_all(std::vector<GicpEngine*>& engines, std::vector<GicpBatchPair>& pairs);
+    int align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std::vector<GicpBatchPair>& pairs);
 
    private:
     mrgfe_ctx* ctx_;
     // helper streams + workspaces for the source covariances (created on first use, kept)
-    struct Lane { mrgfe_ctx* ctx = nullptr; NnGridSet set; std::vector<NnGrid> views; DevBuf knn_i, knn_d; };
-    std::vector<Lane*> lanes_;
+    struct Lane { CtxPtr ctx; NnGridSet set; std::vector<NnGrid> views; DevBuf knn_i, knn_d; };  // (ctx first: the helper context goes last)
+    std::vector<std::unique_ptr<Lane>> lanes_;
     DevBuf d_pairs_, d_evals_, d_grids_, d_partials_;
     PinBuf h_evals_, h_results_;
-    hipEvent_t done_ = nullptr;
+    Event  done_;
 };
 
 // PCL_GICP_HIP: 1 the cost / gradient sums in the reference's (point) order, 0 in a tree; other values query

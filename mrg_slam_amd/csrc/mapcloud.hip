@@ -209,13 +209,11 @@ int map_cloud_device(mrgfe_ctx* ctx, const float4* d_cat, const uint32_t* kf_off
     const uint32_t n = kf_off[K];
     if (n == 0) return MRGFE_OK;
     hipStream_t st = ctx->stream;
-    DevBuf dtab, dtrans, dfl;  // per-call buffers: the scratch slots are in use by the voxel-grid pass below
-    auto cleanup = [&]() { dtab.release(); dtrans.release(); dfl.release(); };
+    DevBuf dcomp, dfl, dtrans, dtab;  // per-call buffers (the scratch slots are in use by the voxel-grid pass below), freed at the return, `dtab` first
     const size_t ptr_at = (sizeof(uint32_t) * (K + 1) + sizeof(float) * 16 * K + 15) & ~size_t(15);
-    int rc = dtab.ensure(ptr_at + sizeof(void*) * K);
-    if (rc == MRGFE_OK) rc = dtrans.ensure(size_t(n) * 16);
-    if (rc == MRGFE_OK) rc = dfl.ensure(size_t(n) * 4);
-    if (rc != MRGFE_OK) { cleanup(); return rc; }
+    MRGFE_TRY(dtab.ensure(ptr_at + sizeof(void*) * K));
+    MRGFE_TRY(dtrans.ensure(size_t(n) * 16));
+    MRGFE_TRY(dfl.ensure(size_t(n) * 4));
     uint32_t* d_off = dtab.as<uint32_t>();
     float*    d_pose = reinterpret_cast<float*>(d_off + (K + 1));
     const float4* const* d_ptrs = kf_ptrs ? reinterpret_cast<const float4* const*>(dtab.as<char>() + ptr_at) : nullptr;
@@ -223,25 +221,23 @@ int map_cloud_device(mrgfe_ctx* ctx, const float4* d_cat, const uint32_t* kf_off
     if ((kf_ptrs && hipMemcpyAsync(dtab.as<char>() + ptr_at, kf_ptrs, sizeof(void*) * K, hipMemcpyHostToDevice, st) != hipSuccess) ||
         hipMemcpyAsync(d_off, kf_off, sizeof(uint32_t) * (K + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(d_pose, poses_f, sizeof(float) * 16 * K, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        cleanup();
         set_error("map cloud: table upload failed");
         return MRGFE_ERR_HIP;
     }
     hipLaunchKernelGGL(map_transform_kernel, dim3((n + 255) / 256), dim3(256), 0, st, kf_ptrs ? nullptr : d_cat, d_ptrs, n, d_off, d_pose, K, use_far ? 1 : 0, far_thresh * far_thresh, dtrans.as<float4>(),
                        dfl.as<uint32_t>());
-    if (hipGetLastError() != hipSuccess) { cleanup(); set_error("map cloud: transform kernel launch failed"); return MRGFE_ERR_HIP; }
+    if (hipGetLastError() != hipSuccess) { set_error("map cloud: transform kernel launch failed"); return MRGFE_ERR_HIP; }
     const float4* d_cloud = dtrans.as<float4>();
     size_t        total = n;
-    DevBuf        dcomp;
     if (use_far) {
-        rc = dcomp.ensure(size_t(n) * 16);
+        MRGFE_TRY(dcomp.ensure(size_t(n) * 16));
         uint32_t kept = 0;
-        if (rc == MRGFE_OK) rc = compact_by_flags(ctx, dtrans.as<float4>(), n, dfl.as<uint32_t>(), dcomp.as<float4>(), &kept);
-        if (rc != MRGFE_OK) { cleanup(); dcomp.release(); return rc; }
+        MRGFE_TRY(compact_by_flags(ctx, dtrans.as<float4>(), n, dfl.as<uint32_t>(), dcomp.as<float4>(), &kept));
         d_cloud = dcomp.as<float4>();
         total = kept;
     }
     *n_unfiltered = total;
+    int rc = MRGFE_OK;
     if (resolution <= 0.0f) {  // :66-70: the unfiltered cloud
         if (total && hipMemcpyAsync(d_out, d_cloud, total * 16, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = MRGFE_ERR_HIP;
         if (hipStreamSynchronize(st) != hipSuccess) rc = MRGFE_ERR_HIP;
@@ -251,8 +247,6 @@ int map_cloud_device(mrgfe_ctx* ctx, const float4* d_cat, const uint32_t* kf_off
         // float(count), count threshold; only the output order differs (ascending cell instead of the reference's hash-map order)
         rc = mean_voxelgrid_device(ctx, d_cloud, total, resolution, min_pts, d_out, out_n);
     }
-    cleanup();
-    dcomp.release();
     return rc;
 }
 
@@ -288,19 +282,14 @@ int remove_points_near_device(mrgfe_ctx* ctx, const float4* d_in, size_t n, cons
     const uint32_t nn = static_cast<uint32_t>(n);
     Centres c{};
     for (int k = 0; k < K; ++k) for (int a = 0; a < 3; ++a) c.xyz[k][a] = centres[3 * k + a];
-    DevBuf dk, dd;
-    int rc = dk.ensure(n * 4);
-    if (rc == MRGFE_OK) rc = dd.ensure(n * 4);
-    if (rc == MRGFE_OK) {
-        hipLaunchKernelGGL(near_flags_kernel, dim3((nn + 255) / 256), dim3(256), 0, ctx->stream, d_in, nn, c, K, radius_sqr, dk.as<uint32_t>(), dd.as<uint32_t>());
-        if (hipGetLastError() != hipSuccess) { set_error("remove_points_near: kernel launch failed"); rc = MRGFE_ERR_HIP; }
-    }
+    DevBuf dd, dk;  // (per-call flags, freed at the return, `dk` first)
+    MRGFE_TRY(dk.ensure(n * 4));
+    MRGFE_TRY(dd.ensure(n * 4));
+    hipLaunchKernelGGL(near_flags_kernel, dim3((nn + 255) / 256), dim3(256), 0, ctx->stream, d_in, nn, c, K, radius_sqr, dk.as<uint32_t>(), dd.as<uint32_t>());
+    if (hipGetLastError() != hipSuccess) { set_error("remove_points_near: kernel launch failed"); return MRGFE_ERR_HIP; }
     uint32_t kept = 0, gone = 0;
-    if (rc == MRGFE_OK) rc = compact_by_flags(ctx, d_in, nn, dk.as<uint32_t>(), d_kept, &kept);
-    if (rc == MRGFE_OK && d_removed) rc = compact_by_flags(ctx, d_in, nn, dd.as<uint32_t>(), d_removed, &gone);
-    dk.release();
-    dd.release();
-    if (rc != MRGFE_OK) return rc;
+    MRGFE_TRY(compact_by_flags(ctx, d_in, nn, dk.as<uint32_t>(), d_kept, &kept));
+    if (d_removed) MRGFE_TRY(compact_by_flags(ctx, d_in, nn, dd.as<uint32_t>(), d_removed, &gone));
     *n_kept = kept;
     if (n_removed) *n_removed = d_removed ? gone : nn - kept;
     return MRGFE_OK;

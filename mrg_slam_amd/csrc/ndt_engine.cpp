@@ -42,13 +42,7 @@ static bool one_wait_build_allowed();
 
 NdtEngine::~NdtEngine()
 {
-    if (ctx_) (void)hipSetDevice(ctx_->device);
-    cloud_arena_.release();
-    grid_arena_.release();
-    for (auto& e : ev_pool_) if (e) (void)hipEventDestroy(e);
-    d_grids_.release(); d_pairs_.release(); d_evals_.release(); d_partials_.release(); d_T12_.release(); d_aligned_.release(); d_states_.release(); d_ticket_.release();
-    d_ref_rec_.release(); d_ref_cnt_.release(); d_ref_jobs_.release();
-    h_evals_.release(); h_results_.release(); h_states_.release(); h_info_.release();
+    if (ctx_) (void)hipSetDevice(ctx_->device);  // the members free themselves on the engine's device
 }
 
 void NdtEngine::clear()
@@ -483,9 +477,9 @@ uint32_t NdtEngine::derivative_grid(int mode) const
 int NdtEngine::ensure_events(size_t rounds)
 {
     while (ev_pool_.size() < rounds * 6) {
-        hipEvent_t e = nullptr;
+        Event e;
         MRGFE_HIP_CHECK(hipEventCreate(&e));
-        ev_pool_.push_back(e);
+        ev_pool_.push_back(std::move(e));
     }
     return MRGFE_OK;
 }

@@ -134,7 +134,7 @@ class NdtEngine {
     uint32_t* d_plan() const { return reinterpret_cast<uint32_t*>(d_evals_.as<char>() + evals_bytes_); }
     std::vector<uint32_t> plan_scratch_;
     void host_plan(std::vector<uint32_t>& plan, uint32_t wg_target, uint32_t max_ppt) const;
-    std::vector<hipEvent_t> ev_pool_;     // [round][variant][begin, end]
+    std::vector<Event> ev_pool_;          // [round][variant][begin, end]
     int    rounds_ = 0;
     int      key_bits_hint_ = 0;   // key width of this engine's last single-target build + 1 (0: none yet): lets the next one sort before the host has seen its box
     uint64_t result_tag_ = 0;  // host-stepped single registration: the value its next reduction stores behind the record

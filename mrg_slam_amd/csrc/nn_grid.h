@@ -8,6 +8,8 @@
 // Points are sorted by cell (stable radix sort, so ascending index inside a cell); cell rows along x are contiguous,
 // so a query walks a few contiguous ranges per ring.  Ties at equal distance resolve to the lowest index.
 #pragma once
+#include <new>
+#include <utility>
 #include <vector>
 
 #include "cellsort.h"
@@ -55,6 +57,10 @@ struct NnFitnessJob {
 
 class NnGrid {
    public:
+    NnGrid() = default;
+    NnGrid(NnGrid&&) noexcept = default;  // (containers of grids grow; an event moved away leaves nothing to wait for)
+    NnGrid& operator=(NnGrid&& o) noexcept { if (this != &o) { this->~NnGrid(); new (this) NnGrid(std::move(o)); } return *this; }  // waits like the destructor
+    ~NnGrid() { settle_crowding(); }      // the buffers and the event free themselves
     // (re)build over a packed float4 device cloud. `cell_size` is the largest cell edge; with `crowding_target` > 0 the
     // edge is halved (at most four times) while the population of the cell an average point sits in exceeds the target,
     // so a walk over the 27 cells around a query touches tens, not thousands, of candidates on dense clouds.
@@ -64,7 +70,7 @@ class NnGrid {
     // known_box (min xyz, max xyz): a box the caller KNOWS to enclose the cloud, all of whose points are finite — the bounding-box pass and its stream wait are
     // skipped (search results do not depend on the box, only on its enclosing the points)
     int build(mrgfe_ctx* ctx, const float4* d_pts, size_t n, float cell_size, double crowding_target = kCrowding1nn, int max_levels = kNnMaxLevels, const float* known_box = nullptr);
-    void release();
+    void release();  // free the device arrays now (adopt); the cell-edge hints stay
     bool valid() const { return built_; }
     const NnGridDev&  dev() const { return h_.level[0]; }  // radius queries walk the finest level only
     const NnGrid2Dev& dev2() const { return h_; }
@@ -95,8 +101,9 @@ class NnGrid {
     // search results do not depend on the edge, only the time does, so a cloud that has outgrown the hint costs one slower search, not a stream wait per build
     PinBuf      crowd_box_;
     bool        crowd_pending_ = false;
-    hipEvent_t  crowd_event_ = nullptr;
+    Event       crowd_event_;
     uint32_t    crowd_n_finite_ = 0;
+    void settle_crowding();  // the copy into crowd_box_ must have landed before the box goes
     int build_levels_together(mrgfe_ctx* ctx, const float4* d_pts, uint32_t nn, const BBox& bb, const float* cell, int n_levels, double* crowding, unsigned long long* h_slots_async = nullptr);
     int count_level(mrgfe_ctx* ctx, const float4* d_pts, uint32_t nn, const BBox& bb, float cell, DevBuf& d_cells, double* crowding);
 };
@@ -110,7 +117,6 @@ class NnGrid {
 class NnGridSet {
    public:
     int  build(mrgfe_ctx* ctx, const float4* const* d_clouds, const uint32_t* n, int count, float cell_size, double crowding_target, int max_levels, NnGrid* const* out);
-    void release();
 
    private:
     DevBuf d_cells_[kNnMaxLevels], d_sorted_[kNnMaxLevels];
@@ -136,7 +142,7 @@ int nn_build_device_driven(mrgfe_ctx* ctx, const float4* const* d_cloud_ptr, con
 // the grid and the count read from device memory
 int nn_radius_flags_device_driven(mrgfe_ctx* ctx, const NnDeviceDrivenGrid& g, const float4* d_q, const Slice* d_slice, uint32_t n_cap, double r2, int need, float cell, uint32_t* d_flags);
 
-// the context's reusable grid (created on first use; buffers grow only) and its disposal in mrgfe_ctx_destroy
+// the context's reusable grid (created on first use; buffers grow only; freed with the context)
 NnGrid& ctx_tmp_grid(mrgfe_ctx* ctx);
 
 // all jobs in one launch (blockIdx.y = job); out[j] = mean squared distance or DBL_MAX when nothing is in range

@@ -522,27 +522,19 @@ int NnGrid::build(mrgfe_ctx* ctx, const float4* d_pts, size_t n, float cell_size
 
 NnGrid& ctx_tmp_grid(mrgfe_ctx* ctx)
 {
-    if (!ctx->tmp_grid) ctx->tmp_grid = new NnGrid();
+    if (!ctx->tmp_grid) ctx->tmp_grid.reset(new NnGrid());
     return *ctx->tmp_grid;
 }
-void ctx_tmp_grid_free(mrgfe_ctx* ctx)
-{
-    if (ctx->pf_grid) {
-        NnDeviceDrivenGrid* g = static_cast<NnDeviceDrivenGrid*>(ctx->pf_grid);
-        g->cells.release(); g->sorted.release(); g->desc.release();
-        delete g;
-        ctx->pf_grid = nullptr;
-    }
-    if (!ctx->tmp_grid) return;
-    ctx->tmp_grid->release();
-    delete ctx->tmp_grid;
-    ctx->tmp_grid = nullptr;
-}
 
+void NnGrid::settle_crowding()
+{
+    if (crowd_pending_ && crowd_event_) (void)hipEventSynchronize(crowd_event_);
+    crowd_pending_ = false;
+}
 void NnGrid::release()
 {
-    if (crowd_pending_) { (void)hipEventSynchronize(crowd_event_); crowd_pending_ = false; }  // the copy into crowd_box_ must have landed before the box goes
-    if (crowd_event_) { (void)hipEventDestroy(crowd_event_); crowd_event_ = nullptr; }
+    settle_crowding();
+    crowd_event_.reset();
     crowd_box_.release();
     for (auto& b : d_cell_start_) b.release();
     for (auto& b : d_sorted_) b.release();
@@ -550,13 +542,6 @@ void NnGrid::release()
 }
 
 // ---- NnGridSet ---------------------------------------------------------------------------------------------------
-void NnGridSet::release()
-{
-    for (auto& b : d_cells_) b.release();
-    for (auto& b : d_sorted_) b.release();
-    hint_cell_.clear();
-}
-
 int NnGridSet::build(mrgfe_ctx* ctx, const float4* const* d_clouds, const uint32_t* n, int count, float cell_size, double crowding_target, int max_levels, NnGrid* const* out)
 {
     if (count <= 0) return MRGFE_OK;

@@ -88,15 +88,16 @@ struct ResidentCloud {
 };
 
 enum Job { JOB_NONE = 0, JOB_ALIGN = 1, JOB_QUIT = 2 };
+struct BatchDestroy { void operator()(mrgfe_batch* b) const { mrgfe_batch_destroy(b); } };
 
 }  // namespace
 
 struct mrgfe_node {
     struct Member {
+        ~Member() { if (ctx) (void)hipSetDevice(device); }  // the members below free themselves on this device, in reverse order: the batch first, the context last
         int          index = 0, device = 0;
-        mrgfe_ctx*   ctx = nullptr;
-        mrgfe_batch* batch = nullptr;
-        std::thread  th;
+        CtxPtr       ctx;
+        std::thread  th;                                        // (joined by mrgfe_node_destroy before the member goes)
         std::mutex   mu;
         std::condition_variable cv;
         Job          job = JOB_NONE;
@@ -105,14 +106,15 @@ struct mrgfe_node {
         std::string  error;
         int          first = 0, count = 0;  // this member's block of the pair list
         std::vector<mrgfe_pair_result> local;
-        std::unordered_map<uint64_t, ResidentCloud*> targets;  // keyed target clouds resident on this member's device
+        std::unordered_map<uint64_t, std::unique_ptr<ResidentCloud>> targets;  // keyed target clouds resident on this member's device
         uint64_t     align_serial = 0;
         size_t       target_cap = size_t(16) << 30;             // bytes of keyed targets kept resident (MRGFE_KEYFRAME_STORE_MB, the batch store's cap), LRU beyond it
         DevBuf       d_send, d_recv;                            // RCCL gather
         int          fail_next = 0;                             // test hook
+        std::unique_ptr<mrgfe_batch, BatchDestroy> batch;
     };
     mrgfe_reg_params         params;
-    std::vector<Member*>     members;
+    std::vector<std::unique_ptr<Member>> members;
     std::vector<TargetDecl>  targets;
     std::vector<PairDecl>    pairs;
     double                   fitness_max_range = -1.0;
@@ -148,7 +150,7 @@ int member_align(mrgfe_node* node, Member& m)
 #endif
     if (m.count == 0) return MRGFE_OK;
     ++m.align_serial;
-    int st = mrgfe_batch_clear(m.batch);
+    int st = mrgfe_batch_clear(m.batch.get());
     if (st != MRGFE_OK) return member_fail(m, st);
     std::unordered_map<int, int> local_target;
     for (int i = m.first; i < m.first + m.count; ++i) {
@@ -159,8 +161,8 @@ int member_align(mrgfe_node* node, Member& m)
             int ti;
             if (t.key) {
                 // a keyed target stays resident on this member's device: uploaded once, found again by the next batches that name it
-                ResidentCloud*& rc = m.targets[t.key];
-                if (!rc) rc = new (std::nothrow) ResidentCloud();
+                std::unique_ptr<ResidentCloud>& rc = m.targets[t.key];
+                if (!rc) rc.reset(new (std::nothrow) ResidentCloud());
                 if (!rc) { set_error("out of host memory"); return member_fail(m, MRGFE_ERR_INVALID); }
                 rc->last_use = m.align_serial;
                 if (rc->n != t.n || !rc->buf.p) {
@@ -178,26 +180,24 @@ int member_align(mrgfe_node* node, Member& m)
                             if (jt->second->last_use < m.align_serial && jt->second->buf.p && (victim == m.targets.end() || jt->second->last_use < victim->second->last_use)) victim = jt;
                         if (victim == m.targets.end()) break;  // everything left is named by this call: the block's own working set may exceed the cap
                         held -= victim->second->buf.cap;
-                        victim->second->buf.release();
-                        delete victim->second;
                         m.targets.erase(victim);
                     }
                     if ((st = rc->buf.ensure(std::max<size_t>(t.n, 1) * 16)) != MRGFE_OK) return member_fail(m, st);
-                    if ((st = upload_cloud(m.ctx, t.xyzi, t.n, t.stride, rc->buf.p)) != MRGFE_OK) return member_fail(m, st);
+                    if ((st = upload_cloud(m.ctx.get(), t.xyzi, t.n, t.stride, rc->buf.p)) != MRGFE_OK) return member_fail(m, st);
                     rc->n = t.n;
                 }
-                ti = mrgfe_batch_add_target_device(m.batch, rc->buf.p, rc->n);
+                ti = mrgfe_batch_add_target_device(m.batch.get(), rc->buf.p, rc->n);
             } else {
-                ti = mrgfe_batch_add_target(m.batch, t.xyzi, t.n, t.stride);
+                ti = mrgfe_batch_add_target(m.batch.get(), t.xyzi, t.n, t.stride);
             }
             if (ti < 0) return member_fail(m, ti);
             it = local_target.emplace(p.target, ti).first;
         }
-        const int pi = p.key ? mrgfe_batch_add_pair_keyed(m.batch, it->second, p.key, p.xyzi, p.n, p.stride, p.guess)
-                             : mrgfe_batch_add_pair(m.batch, it->second, p.xyzi, p.n, p.stride, p.guess);
+        const int pi = p.key ? mrgfe_batch_add_pair_keyed(m.batch.get(), it->second, p.key, p.xyzi, p.n, p.stride, p.guess)
+                             : mrgfe_batch_add_pair(m.batch.get(), it->second, p.xyzi, p.n, p.stride, p.guess);
         if (pi < 0) return member_fail(m, pi);
     }
-    st = mrgfe_batch_align(m.batch, node->fitness_max_range, m.local.data());
+    st = mrgfe_batch_align(m.batch.get(), node->fitness_max_range, m.local.data());
     if (st != MRGFE_OK) return member_fail(m, st);
     for (int k = 0; k < m.count; ++k) m.local[static_cast<size_t>(k)].pair_id = m.first + k;  // the GLOBAL pair index
     return MRGFE_OK;
@@ -213,21 +213,13 @@ void member_main(mrgfe_node* node, Member* m)
             job = m->job;
         }
         if (job == JOB_QUIT) return;
-        int st;
-        try {
-            st = member_align(node, *m);
-        } catch (const std::exception& e) {  // (std::bad_alloc of a host container: an error code, never std::terminate)
-            m->status = st = MRGFE_ERR_INVALID;
-            m->error = std::string("member ") + std::to_string(m->index) + ": " + e.what();
-        } catch (...) {
-            m->status = st = MRGFE_ERR_INVALID;
-            m->error = "member " + std::to_string(m->index) + ": unknown exception";
-        }
+        const int st = abi_guard("mrgfe_node_align member", [&] { return member_align(node, *m); });
+        if (st != MRGFE_OK && m->status == MRGFE_OK) member_fail(*m, st);  // an exception: member_align did not get to record it
         if (st != MRGFE_OK) {
             // the member's clouds go up by DMA out of the caller's page-locked buffers (zero-copy uploads are always on for members) and a failing
             // block may have queued copies it never waited for: mrgfe_node_align hands the buffers back only after they have drained
             MRGFE_LOCK(m->ctx);
-            drain_caller_dma(m->ctx);
+            drain_caller_dma(m->ctx.get());
         }
         {
             std::lock_guard<std::mutex> lk(m->mu);
@@ -280,7 +272,7 @@ int rccl_setup(mrgfe_node* node)
     Rccl& r = rccl();
     if (!r.ok()) { set_error("librccl could not be loaded"); return MRGFE_ERR_STATE; }
     std::vector<int> devs;
-    for (Member* m : node->members) devs.push_back(m->device);
+    for (auto& m : node->members) devs.push_back(m->device);
     node->comms.assign(devs.size(), nullptr);
     const int rc = r.CommInitAll(node->comms.data(), static_cast<int>(devs.size()), devs.data());
     if (rc != 0) {
@@ -298,7 +290,7 @@ int rccl_gather(mrgfe_node* node, int per, mrgfe_pair_result* results, int n_pai
     const size_t G = node->members.size();
     const size_t rec = sizeof(mrgfe_pair_result), bytes = rec * static_cast<size_t>(per);
     std::vector<mrgfe_pair_result> pad(static_cast<size_t>(per));
-    for (Member* m : node->members) {
+    for (auto& m : node->members) {
         MRGFE_LOCK(m->ctx);
         MRGFE_TRY(m->ctx->bind());
         MRGFE_TRY(m->d_send.ensure(bytes));
@@ -311,7 +303,7 @@ int rccl_gather(mrgfe_node* node, int per, mrgfe_pair_result* results, int n_pai
     }
     int rc = r.GroupStart();
     for (size_t g = 0; g < G && rc == 0; ++g) {
-        Member* m = node->members[g];
+        Member* m = node->members[g].get();
         (void)hipSetDevice(m->device);
         rc = r.AllGather(m->d_send.p, m->d_recv.p, bytes, kNcclChar, node->comms[g], m->ctx->stream);
     }
@@ -320,14 +312,14 @@ int rccl_gather(mrgfe_node* node, int per, mrgfe_pair_result* results, int n_pai
     if (rc != 0) { set_error("ncclAllGather failed: %s", r.GetErrorString ? r.GetErrorString(rc) : "?"); return MRGFE_ERR_HIP; }
     std::vector<mrgfe_pair_result> all(static_cast<size_t>(per) * G);
     {
-        Member* m0 = node->members[0];
+        Member* m0 = node->members[0].get();
         MRGFE_LOCK(m0->ctx);
         MRGFE_TRY(m0->ctx->bind());
         MRGFE_HIP_CHECK(hipMemcpyAsync(all.data(), m0->d_recv.p, bytes * G, hipMemcpyDeviceToHost, m0->ctx->stream));
         MRGFE_HIP_CHECK(hipStreamSynchronize(m0->ctx->stream));
     }
     for (size_t g = 1; g < G; ++g) {  // every member's collective has to have finished before its buffers are reused
-        Member* m = node->members[g];
+        Member* m = node->members[g].get();
         MRGFE_LOCK(m->ctx);
         MRGFE_TRY(m->ctx->bind());
         MRGFE_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
@@ -349,67 +341,62 @@ extern "C" {
 
 int mrgfe_node_create(int n_members, const int* device_ids, const mrgfe_reg_params* params, mrgfe_node** out)
 {
-    if (!out || !params || n_members < 1 || n_members > 64 || !device_ids) { set_error("mrgfe_node_create: bad argument"); return MRGFE_ERR_INVALID; }
-    *out = nullptr;
-    mrgfe_node* node = new (std::nothrow) mrgfe_node();
-    if (!node) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-    node->params = *params;
-    int st = MRGFE_OK;
-    for (int i = 0; i < n_members && st == MRGFE_OK; ++i) {
-        Member* m = new (std::nothrow) Member();
-        if (!m) { set_error("out of host memory"); st = MRGFE_ERR_INVALID; break; }
-        m->index = i;
-        m->device = device_ids[i];
-        if (const char* e = std::getenv("MRGFE_KEYFRAME_STORE_MB")) m->target_cap = static_cast<size_t>(std::max(0.0, std::atof(e))) << 20;
-        node->members.push_back(m);
-        st = mrgfe_ctx_create(m->device, &m->ctx);
-        // (the node's clouds are declared by pointer and uploaded inside mrgfe_node_align, which returns after the members have finished: page-locked
-        // ones can always go up by DMA from where they lie)
-        if (st == MRGFE_OK) st = mrgfe_ctx_set_zero_copy_uploads(m->ctx, 1);
-        if (st == MRGFE_OK) st = mrgfe_batch_create(m->ctx, params, &m->batch);
-    }
-    if (st != MRGFE_OK) {
-        const std::string msg = mrgfe_last_error();
-        mrgfe_node_destroy(node);
-        set_error("%s", msg.c_str());
-        return st;
-    }
-    try {
-        for (Member* m : node->members) m->th = std::thread(member_main, node, m);
-    } catch (const std::exception& e) {  // std::system_error (thread limit): an error code, never an exception across the C boundary
-        const std::string msg = e.what();
-        mrgfe_node_destroy(node);  // joins the members that did start
-        set_error("mrgfe_node_create: could not start a member thread: %s", msg.c_str());
-        return MRGFE_ERR_STATE;
-    }
-    *out = node;
-    return MRGFE_OK;
+    return abi_guard("mrgfe_node_create", [&]() -> int {
+        if (!out || !params || n_members < 1 || n_members > 64 || !device_ids) { set_error("mrgfe_node_create: bad argument"); return MRGFE_ERR_INVALID; }
+        *out = nullptr;
+        std::unique_ptr<mrgfe_node> owned(new (std::nothrow) mrgfe_node());
+        mrgfe_node* node = owned.get();
+        if (!node) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+        node->params = *params;
+        int st = MRGFE_OK;
+        for (int i = 0; i < n_members && st == MRGFE_OK; ++i) {
+            std::unique_ptr<Member> fresh(new (std::nothrow) Member());
+            if (!fresh) { set_error("out of host memory"); st = MRGFE_ERR_INVALID; break; }
+            node->members.push_back(std::move(fresh));
+            Member* m = node->members.back().get();
+            m->index = i;
+            m->device = device_ids[i];
+            if (const char* e = std::getenv("MRGFE_KEYFRAME_STORE_MB")) m->target_cap = static_cast<size_t>(std::max(0.0, std::atof(e))) << 20;
+            mrgfe_ctx*   ctx = nullptr;
+            mrgfe_batch* batch = nullptr;
+            st = mrgfe_ctx_create(m->device, &ctx);
+            m->ctx.reset(ctx);
+            // (the node's clouds are declared by pointer and uploaded inside mrgfe_node_align, which returns after the members have finished: page-locked
+            // ones can always go up by DMA from where they lie)
+            if (st == MRGFE_OK) st = mrgfe_ctx_set_zero_copy_uploads(ctx, 1);
+            if (st == MRGFE_OK) st = mrgfe_batch_create(ctx, params, &batch);
+            m->batch.reset(batch);
+        }
+        // std::system_error (thread limit): an error code, never an exception across the C boundary
+        if (st == MRGFE_OK && abi_guard("mrgfe_node_create: could not start a member thread", [&] {
+                for (auto& m : node->members) m->th = std::thread(member_main, node, m.get());
+                return MRGFE_OK;
+            }) != MRGFE_OK)
+            st = MRGFE_ERR_STATE;
+        if (st != MRGFE_OK) {
+            const std::string msg = mrgfe_last_error();
+            mrgfe_node_destroy(owned.release());  // joins the members that did start
+            set_error("%s", msg.c_str());
+            return st;
+        }
+        *out = owned.release();
+        return MRGFE_OK;
+    });
 }
 
 void mrgfe_node_destroy(mrgfe_node* node)
 {
     if (!node) return;
-    for (Member* m : node->members) {
+    for (auto& m : node->members) {
         if (m->th.joinable()) {
-            wait_done(m);
-            post(m, JOB_QUIT);
+            wait_done(m.get());
+            post(m.get(), JOB_QUIT);
             m->th.join();
         }
     }
     if (!node->comms.empty() && rccl().ok())
         for (nccl_comm_t c : node->comms) if (c) (void)rccl().CommDestroy(c);
-    for (Member* m : node->members) {
-        if (m->batch) mrgfe_batch_destroy(m->batch);
-        if (m->ctx) {
-            (void)hipSetDevice(m->device);
-            for (auto& kv : m->targets) { kv.second->buf.release(); delete kv.second; }
-            m->d_send.release();
-            m->d_recv.release();
-            mrgfe_ctx_destroy(m->ctx);
-        }
-        delete m;
-    }
-    delete node;
+    delete node;  // every member frees what it holds on its own device (Member)
 }
 
 int mrgfe_node_num_members(const mrgfe_node* node) { return node ? static_cast<int>(node->members.size()) : MRGFE_ERR_INVALID; }
@@ -417,11 +404,13 @@ int mrgfe_node_num_pairs(const mrgfe_node* node) { return node ? static_cast<int
 
 int mrgfe_node_clear(mrgfe_node* node)
 {
-    if (!node) { set_error("mrgfe_node_clear: NULL node"); return MRGFE_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(node->api_mu);
-    node->targets.clear();
-    node->pairs.clear();
-    return MRGFE_OK;
+    return abi_guard("mrgfe_node_clear", [&]() -> int {
+        if (!node) { set_error("mrgfe_node_clear: NULL node"); return MRGFE_ERR_INVALID; }
+        std::lock_guard<std::mutex> lk(node->api_mu);
+        node->targets.clear();
+        node->pairs.clear();
+        return MRGFE_OK;
+    });
 }
 
 int mrgfe_node_add_target_keyed(mrgfe_node* node, uint64_t cloud_key, const float* xyzi, size_t n, size_t stride_bytes)
@@ -431,10 +420,10 @@ int mrgfe_node_add_target_keyed(mrgfe_node* node, uint64_t cloud_key, const floa
     uint32_t s; uint32_t xo; int32_t io;
     if (decode_layout(stride_bytes, &s, &xo, &io) != MRGFE_OK) return MRGFE_ERR_INVALID;
     std::lock_guard<std::mutex> lk(node->api_mu);
-    try {
+    return abi_guard("mrgfe_node_add_target", [&] {
         node->targets.push_back(TargetDecl{cloud_key, xyzi, n, stride_bytes});
-    } catch (const std::bad_alloc&) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-    return static_cast<int>(node->targets.size()) - 1;
+        return static_cast<int>(node->targets.size()) - 1;
+    });
 }
 int mrgfe_node_add_target(mrgfe_node* node, const float* xyzi, size_t n, size_t stride_bytes) { return mrgfe_node_add_target_keyed(node, 0, xyzi, n, stride_bytes); }
 
@@ -449,10 +438,10 @@ int mrgfe_node_add_pair_keyed(mrgfe_node* node, int target_index, uint64_t cloud
     PairDecl p;
     p.target = target_index; p.key = cloud_key; p.xyzi = src_xyzi; p.n = n; p.stride = stride_bytes;
     std::memcpy(p.guess, guess, sizeof(p.guess));
-    try {
+    return abi_guard("mrgfe_node_add_pair", [&] {
         node->pairs.push_back(p);
-    } catch (const std::bad_alloc&) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-    return static_cast<int>(node->pairs.size()) - 1;
+        return static_cast<int>(node->pairs.size()) - 1;
+    });
 }
 int mrgfe_node_add_pair(mrgfe_node* node, int target_index, const float* src_xyzi, size_t n, size_t stride_bytes, const float guess[16])
 {
@@ -461,40 +450,42 @@ int mrgfe_node_add_pair(mrgfe_node* node, int target_index, const float* src_xyz
 
 int mrgfe_node_align(mrgfe_node* node, double fitness_max_range, mrgfe_pair_result* results)
 {
-    if (!node) { set_error("mrgfe_node_align: NULL node"); return MRGFE_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(node->api_mu);
-    const int n = static_cast<int>(node->pairs.size()), G = static_cast<int>(node->members.size());
-    if (n && !results) { set_error("mrgfe_node_align: NULL results"); return MRGFE_ERR_INVALID; }
-    node->fitness_max_range = fitness_max_range;
-    // contiguous blocks, sizes differing by at most one, the first n mod G blocks the longer ones
-    const int base = n / G, extra = n % G;
-    for (int g = 0; g < G; ++g) {
-        Member* m = node->members[static_cast<size_t>(g)];
-        m->first = g * base + std::min(g, extra);
-        m->count = base + (g < extra ? 1 : 0);
-    }
-    {
-        TraceRange tr("mrgfe_node_align members");
-        for (Member* m : node->members) post(m, JOB_ALIGN);
-        for (Member* m : node->members) wait_done(m);
-    }
-    for (Member* m : node->members)
-        if (m->status != MRGFE_OK) {  // the first member that failed names the error; the others have finished their blocks and are idle again
-            set_error("mrgfe_node_align: member %d (device %d): %s", m->index, m->device, m->error.c_str());
-            return m->status;
+    return abi_guard("mrgfe_node_align", [&]() -> int {
+        if (!node) { set_error("mrgfe_node_align: NULL node"); return MRGFE_ERR_INVALID; }
+        std::lock_guard<std::mutex> lk(node->api_mu);
+        const int n = static_cast<int>(node->pairs.size()), G = static_cast<int>(node->members.size());
+        if (n && !results) { set_error("mrgfe_node_align: NULL results"); return MRGFE_ERR_INVALID; }
+        node->fitness_max_range = fitness_max_range;
+        // contiguous blocks, sizes differing by at most one, the first n mod G blocks the longer ones
+        const int base = n / G, extra = n % G;
+        for (int g = 0; g < G; ++g) {
+            Member* m = node->members[static_cast<size_t>(g)].get();
+            m->first = g * base + std::min(g, extra);
+            m->count = base + (g < extra ? 1 : 0);
         }
-    if (n == 0) return MRGFE_OK;
-    node->last_gather = 0;
-    if (want_rccl(node) && rccl_setup(node) == MRGFE_OK) {
-        const int per = (n + G - 1) / G;
-        TraceRange tr("mrgfe_node_align record gather (RCCL)");
-        const int st = rccl_gather(node, per, results, n);
-        if (st == MRGFE_OK) { node->last_gather = 1; return MRGFE_OK; }
-        if (const char* e = std::getenv("MRGFE_NODE_GATHER")) if (std::strcmp(e, "rccl") == 0) return st;  // asked for: do not hide the failure
-    }
-    for (Member* m : node->members)
-        if (m->count) std::memcpy(results + m->first, m->local.data(), sizeof(mrgfe_pair_result) * static_cast<size_t>(m->count));
-    return MRGFE_OK;
+        {
+            TraceRange tr("mrgfe_node_align members");
+            for (auto& m : node->members) post(m.get(), JOB_ALIGN);
+            for (auto& m : node->members) wait_done(m.get());
+        }
+        for (auto& m : node->members)
+            if (m->status != MRGFE_OK) {  // the first member that failed names the error; the others have finished their blocks and are idle again
+                set_error("mrgfe_node_align: member %d (device %d): %s", m->index, m->device, m->error.c_str());
+                return m->status;
+            }
+        if (n == 0) return MRGFE_OK;
+        node->last_gather = 0;
+        if (want_rccl(node) && rccl_setup(node) == MRGFE_OK) {
+            const int per = (n + G - 1) / G;
+            TraceRange tr("mrgfe_node_align record gather (RCCL)");
+            const int st = rccl_gather(node, per, results, n);
+            if (st == MRGFE_OK) { node->last_gather = 1; return MRGFE_OK; }
+            if (const char* e = std::getenv("MRGFE_NODE_GATHER")) if (std::strcmp(e, "rccl") == 0) return st;  // asked for: do not hide the failure
+        }
+        for (auto& m : node->members)
+            if (m->count) std::memcpy(results + m->first, m->local.data(), sizeof(mrgfe_pair_result) * static_cast<size_t>(m->count));
+        return MRGFE_OK;
+    });
 }
 
 int mrgfe_node_shard(const mrgfe_node* node, int member, int* first_pair, int* n_pairs)
@@ -509,29 +500,31 @@ int mrgfe_node_last_gather(const mrgfe_node* node) { return node ? node->last_ga
 
 int mrgfe_node_forget(mrgfe_node* node, uint64_t cloud_key)
 {
-    if (!node) { set_error("mrgfe_node_forget: NULL node"); return MRGFE_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(node->api_mu);
-    for (Member* m : node->members) {
-        {
-            MRGFE_LOCK(m->ctx);
-            (void)m->ctx->bind();
-            for (auto it = m->targets.begin(); it != m->targets.end();) {
-                if (cloud_key == 0 || it->first == cloud_key) { it->second->buf.release(); delete it->second; it = m->targets.erase(it); }
-                else ++it;
+    return abi_guard("mrgfe_node_forget", [&]() -> int {
+        if (!node) { set_error("mrgfe_node_forget: NULL node"); return MRGFE_ERR_INVALID; }
+        std::lock_guard<std::mutex> lk(node->api_mu);
+        for (auto& m : node->members) {
+            {
+                MRGFE_LOCK(m->ctx);
+                (void)m->ctx->bind();
+                for (auto it = m->targets.begin(); it != m->targets.end();) {
+                    if (cloud_key == 0 || it->first == cloud_key) it = m->targets.erase(it);
+                    else ++it;
+                }
             }
+            MRGFE_TRY(mrgfe_batch_clear(m->batch.get()));  // the member's last block still references its clouds; the node's own list is re-declared per call anyway
+            MRGFE_TRY(mrgfe_batch_forget(m->batch.get(), cloud_key));
         }
-        MRGFE_TRY(mrgfe_batch_clear(m->batch));  // the member's last block still references its clouds; the node's own list is re-declared per call anyway
-        MRGFE_TRY(mrgfe_batch_forget(m->batch, cloud_key));
-    }
-    return MRGFE_OK;
+        return MRGFE_OK;
+    });
 }
 
 size_t mrgfe_node_store_bytes(const mrgfe_node* node)
 {
     if (!node) return 0;
     size_t total = 0;
-    for (Member* m : node->members) {
-        total += mrgfe_batch_store_bytes(m->batch);
+    for (auto& m : node->members) {
+        total += mrgfe_batch_store_bytes(m->batch.get());
         for (auto& kv : m->targets) total += kv.second->buf.cap;
     }
     return total;

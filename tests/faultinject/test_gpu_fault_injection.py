@@ -1,9 +1,11 @@
 """GPU, run under the -DMRGFE_TESTING build of the library (MRGFE_LIB=mrg_slam_amd/libmrgfe_testing.so; started as ONE child process by
 tests/test_gpu_hardening.py::test_fault_injection_suite_under_the_testing_library): the allocation-failure injector (mrgfe_dbg_fail_alloc_after) swept
 over whole entry points — mrgfe_batch_align (NDT and GICP), mrgfe_prefilter, mrgfe_map_store_generate, mrgfe_node_align — shows every path unwinding
-with an error code: no crash, no std::terminate from a joinable helper thread, and the next call (injector off) gives the right answer; a member made
+with an error code: no crash, no std::terminate from a joinable helper thread, no leak (the library's count of live device / pinned allocations,
+mrgfe_dbg_live_allocations, is back where it started once the sweep's objects are destroyed), and the next call (injector off) gives the right answer; a member made
 to fail (mrgfe_dbg_node_fail_member) names itself and leaves the node usable; a failing align drains the zero-copy uploads it had queued."""
 import ctypes as C
+import gc
 
 import numpy as np
 import pytest
@@ -20,9 +22,25 @@ def test_this_process_runs_the_testing_library():
 
     assert os.path.basename(_lib.LIB_PATH) == "libmrgfe_testing.so"
     assert hasattr(_lib.lib(), "mrgfe_dbg_fail_alloc_after") and hasattr(_lib.lib(), "mrgfe_dbg_node_fail_member")
+    assert hasattr(_lib.lib(), "mrgfe_dbg_live_allocations")
 
 
 def _sweep(make, run, check_ok, max_k=400):
+    """_sweep_objects, and no leak: every object the sweep made is destroyed when it returns (the wrappers free in their finalisers, hence the collections), and
+    the library then holds exactly the device / pinned allocations it held before"""
+    from mrg_slam_amd._lib import lib
+
+    gc.collect()
+    live_before = lib().mrgfe_dbg_live_allocations()
+    failures = _sweep_objects(make, run, check_ok, max_k)
+    gc.collect()
+    live_after = lib().mrgfe_dbg_live_allocations()
+    print(f"live allocations: {live_before} before the sweep, {live_after} after ({failures} injected failures)")
+    assert live_after == live_before, f"{live_after - live_before} device / pinned allocations leaked over {failures} injected failures"
+    return failures
+
+
+def _sweep_objects(make, run, check_ok, max_k):
     """fresh objects per k (grow-only workspaces would hide later allocations); every k must fail cleanly until one passes"""
     from mrg_slam_amd import MrgfeError
     from mrg_slam_amd._lib import lib

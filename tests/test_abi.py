@@ -45,7 +45,7 @@ def test_debug_header_and_the_testing_variant():
     _lib.build()
     diag, inject = _declared_symbols("mrgfe_debug.h", testing=False), _declared_symbols("mrgfe_debug.h", testing=True)
     assert sorted(_lib.DEBUG_SIGNATURES) == diag and all(s.startswith("mrgfe_dbg_") for s in diag) and len(diag) >= 15
-    assert sorted(_lib.TESTING_SIGNATURES) == inject == ["mrgfe_dbg_fail_alloc_after", "mrgfe_dbg_node_fail_member"]
+    assert sorted(_lib.TESTING_SIGNATURES) == inject == ["mrgfe_dbg_fail_alloc_after", "mrgfe_dbg_live_allocations", "mrgfe_dbg_node_fail_member"]
     shipped = C.CDLL(os.path.join(ROOT, "mrg_slam_amd", "libmrgfe.so"))
     testing = C.CDLL(_lib.TESTING_LIB_PATH)
     for s in diag:
