@@ -250,6 +250,37 @@ int  mrgfe_prefilter(mrgfe_ctx* ctx, const mrgfe_prefilter_params* params, const
  * mrgfe_batch_add_*_device: the filtered scan goes from the prefiltering callback to the scan matcher without leaving HBM */
 int  mrgfe_prefilter_device(mrgfe_ctx* ctx, const mrgfe_prefilter_params* params, const float* xyzi, size_t n, size_t stride_bytes, void* d_out_xyzi, size_t* out_n);
 
+/* ---- the scan callback in one call (PrefilteringComponent::cloud_callback, apps/prefiltering_component.cpp:116-156) --- */
+/* pcl::fromROSMsg (:119-120) -> deskewing (:125, :231-295) -> pcl_ros::transformPointCloud into base_link_frame (:141-146) -> distance_filter ->
+ * downsample -> outlier_removal (:149-151) on the byte payload of a sensor_msgs/PointCloud2.  The payload goes up ONCE as it is; one kernel reads
+ * the records, deskews, transforms, stores the packed cloud and (on the usual chain) is the distance filter's first pass; nothing comes down but
+ * the chain's status words and, for the host form, the filtered cloud; the usual chain (VOXELGRID + RADIUS) waits for the device once.
+ * The output equals, bit for bit and in order, mrgfe_ingest_pointcloud2 -> mrgfe_deskew (if `deskew`) -> mrgfe_transform_cloud (if `transform`)
+ * -> mrgfe_prefilter[_device] for the same inputs.  The reference's quirks are kept: deskewing counts i and n = width * height over the UNFILTERED
+ * cloud (:286), non-finite points included; the transform leaves non-finite points as they are; the distance filter is what drops them. */
+typedef struct mrgfe_scan_params {
+    /* the message's layout, as for mrgfe_ingest_pointcloud2 (little-endian FLOAT32 fields; offsets multiples of 4 inside point_step) */
+    uint32_t width, height, point_step, row_step;   /* row_step 0: width * point_step                                      */
+    uint32_t off_x, off_y, off_z;
+    int32_t  off_intensity;                         /* < 0: no such field, intensity 0                                     */
+    int      deskew;                                /* 0: imu_queue_ was empty (:234-236), the cloud is not deskewed        */
+    float    ang_v[3];                              /* imu_msg->angular_velocity, NOT negated (the call negates it, :275)  */
+    double   scan_period;                           /* 0.1                                                                 */
+    int      transform;                             /* 0: base_link_frame is empty (:129)                                  */
+    float    T[16];                                 /* column-major Matrix4f of the tf transform                           */
+    mrgfe_prefilter_params filters;
+} mrgfe_scan_params;
+/* height 1, the packed 16-byte layout (offsets 0/4/8/12), no deskewing (scan_period 0.1), no transform (T = identity), mrgfe_prefilter_default_params;
+ * `width` is left 0 for the caller */
+void   mrgfe_scan_default_params(mrgfe_scan_params* out);
+size_t mrgfe_scan_params_size(void); /* sizeof(mrgfe_scan_params) as the library was compiled: a binding checks its mirror of the struct against it */
+/* `data`: (height - 1) * row_step + width * point_step bytes (no length argument, as for mrgfe_ingest_pointcloud2); out_xyzi: room for
+ * width * height packed points.  An empty message (width * height == 0) is MRGFE_OK with *out_n = 0: the reference returns early (:121-123). */
+int    mrgfe_scan_callback(mrgfe_ctx* ctx, const mrgfe_scan_params* params, const uint8_t* data, float* out_xyzi, size_t* out_n);
+/* the same with the filtered scan left in device memory (packed float4, room for width * height points): what mrgfe_prefilter_device leaves,
+ * mrgfe_reg_set_source_from_prefilter(reg, d_out_xyzi, *out_n) included */
+int    mrgfe_scan_callback_device(mrgfe_ctx* ctx, const mrgfe_scan_params* params, const uint8_t* data, void* d_out_xyzi, size_t* out_n);
+
 /* replaces PrefilteringComponent::distance_filter (:206-229): keep iff near < |p| < far */
 int mrgfe_distance_filter(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride_bytes, double near_thresh, double far_thresh,
                           float* out_xyzi, size_t* out_n);

@@ -44,6 +44,15 @@ class PrefilterParams(C.Structure):
                 ("radius_min_neighbors", C.c_int), ("statistical_mean_k", C.c_int), ("statistical_stddev", C.c_double)]
 
 
+class ScanParams(C.Structure):
+    """struct mrgfe_scan_params: the layout of a sensor_msgs/PointCloud2 payload, what ``cloud_callback`` does to the scan before its filters
+    (deskewing, the transform into base_link_frame) and the prefilter parameters."""
+
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("point_step", C.c_uint32), ("row_step", C.c_uint32), ("off_x", C.c_uint32), ("off_y", C.c_uint32),
+                ("off_z", C.c_uint32), ("off_intensity", C.c_int32), ("deskew", C.c_int), ("ang_v", C.c_float * 3), ("scan_period", C.c_double), ("transform", C.c_int),
+                ("T", C.c_float * 16), ("filters", PrefilterParams)]
+
+
 class FloorParams(C.Structure):
     """struct mrgfe_floor_params (the floor_detection_component ROS parameters, apps/floor_detection_component.cpp:55-62, config/mrg_slam.yaml:113-122)."""
 
@@ -152,6 +161,10 @@ SIGNATURES = {
     "mrgfe_prefilter_default_params": (None, [C.POINTER(PrefilterParams)]),
     "mrgfe_prefilter": (C.c_int, [_vp, C.POINTER(PrefilterParams), _fp, C.c_size_t, C.c_size_t, _fp, C.POINTER(C.c_size_t)]),
     "mrgfe_prefilter_device": (C.c_int, [_vp, C.POINTER(PrefilterParams), _fp, C.c_size_t, C.c_size_t, _vp, C.POINTER(C.c_size_t)]),
+    "mrgfe_scan_default_params": (None, [C.POINTER(ScanParams)]),
+    "mrgfe_scan_params_size": (C.c_size_t, []),
+    "mrgfe_scan_callback": (C.c_int, [_vp, C.POINTER(ScanParams), C.POINTER(C.c_uint8), _fp, C.POINTER(C.c_size_t)]),
+    "mrgfe_scan_callback_device": (C.c_int, [_vp, C.POINTER(ScanParams), C.POINTER(C.c_uint8), _vp, C.POINTER(C.c_size_t)]),
     "mrgfe_floor_default_params": (None, [C.POINTER(FloorParams)]),
     "mrgfe_floor_detect": (C.c_int, [_vp, C.POINTER(FloorParams), _fp, C.c_size_t, C.c_size_t, C.POINTER(FloorResult), _fp, _fp]),
     "mrgfe_floor_detect_device": (C.c_int, [_vp, C.POINTER(FloorParams), _vp, C.c_size_t, C.POINTER(FloorResult), _fp, _fp]),

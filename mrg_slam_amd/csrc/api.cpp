@@ -9,6 +9,7 @@
 #include <chrono>
 #include <memory>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -25,6 +26,7 @@
 #include "floor.h"
 #include "mapcloud.h"
 #include "gicp_engine.h"
+#include "ingest.h"
 #include "ndt_derivatives.h"
 #include "ndt_engine.h"
 #include "nn_grid.h"
@@ -689,13 +691,11 @@ int mrgfe_prefilter_device(mrgfe_ctx* ctx, const mrgfe_prefilter_params* p, cons
     MRGFE_TRY(check_count(n, "mrgfe_prefilter_device"));
     return prefilter_impl(ctx, p, xyzi, n, stride, d_out, out_n, true);
 }
-static int prefilter_impl(mrgfe_ctx* ctx, const mrgfe_prefilter_params* p, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool on_device)
+// the ROS parameters -> the chain's switches; MRGFE_ERR_INVALID (message set, `fn` named) for what the component's constructor would not accept
+static int chain_from_params(const char* fn, const mrgfe_prefilter_params* p, PrefilterChain* out)
 {
-    if (!ctx || !p || !out_n || (n && (!xyzi || !out))) { set_error("mrgfe_prefilter: NULL argument"); return MRGFE_ERR_INVALID; }
-    if (p->downsample_method < 0 || p->downsample_method > 2 || p->outlier_removal_method < 0 || p->outlier_removal_method > 2) { set_error("mrgfe_prefilter: unknown method"); return MRGFE_ERR_INVALID; }
-    if (p->downsample_method >= 1 && !(p->downsample_resolution > 0)) { set_error("mrgfe_prefilter: downsample_resolution must be > 0"); return MRGFE_ERR_INVALID; }
-    MRGFE_LOCK(ctx);
-    MRGFE_TRY(ctx->bind());
+    if (p->downsample_method < 0 || p->downsample_method > 2 || p->outlier_removal_method < 0 || p->outlier_removal_method > 2) { set_error("%s: unknown method", fn); return MRGFE_ERR_INVALID; }
+    if (p->downsample_method >= 1 && !(p->downsample_resolution > 0)) { set_error("%s: downsample_resolution must be > 0", fn); return MRGFE_ERR_INVALID; }
     PrefilterChain ch;
     ch.distance = p->enable_distance_filter != 0;
     ch.near_t = p->distance_near_thresh;
@@ -709,7 +709,66 @@ static int prefilter_impl(mrgfe_ctx* ctx, const mrgfe_prefilter_params* p, const
     ch.radius_min_neighbors = p->radius_min_neighbors;
     ch.mean_k = p->statistical_mean_k;
     ch.stddev_mul = p->statistical_stddev;
+    *out = ch;
+    return MRGFE_OK;
+}
+static int prefilter_impl(mrgfe_ctx* ctx, const mrgfe_prefilter_params* p, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool on_device)
+{
+    if (!ctx || !p || !out_n || (n && (!xyzi || !out))) { set_error("mrgfe_prefilter: NULL argument"); return MRGFE_ERR_INVALID; }
+    PrefilterChain ch;
+    MRGFE_TRY(chain_from_params("mrgfe_prefilter", p, &ch));
+    MRGFE_LOCK(ctx);
+    MRGFE_TRY(ctx->bind());
     return filter_chain(ctx, ch, xyzi, n, stride, out, out_n, on_device);
+}
+
+// ---- the scan callback: PointCloud2 bytes -> filtered scan (PrefilteringComponent::cloud_callback :116-156 in one call) -----------------------------
+static_assert(sizeof(mrgfe_scan_params) == 200 && offsetof(mrgfe_scan_params, filters) == 128, "mrgfe_scan_params: the layout the bindings mirror");
+size_t mrgfe_scan_params_size(void) { return sizeof(mrgfe_scan_params); }
+void mrgfe_scan_default_params(mrgfe_scan_params* p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->height = 1;  // (width: the caller's point count)
+    p->point_step = 16;  // the replay scripts' layout: python_scripts/kitti_singlerobot_processor.py:164-185
+    p->off_x = 0; p->off_y = 4; p->off_z = 8; p->off_intensity = 12;
+    p->scan_period = 0.1;  // config/mrg_slam.yaml:45
+    p->T[0] = p->T[5] = p->T[10] = p->T[15] = 1.0f;
+    mrgfe_prefilter_default_params(&p->filters);
+}
+static int scan_callback_impl(const char* fn, mrgfe_ctx* ctx, const mrgfe_scan_params* p, const uint8_t* data, void* out, size_t* out_n, bool on_device)
+{
+    return abi_guard(fn, [&]() -> int {
+        if (!ctx || !p || !out_n) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        *out_n = 0;
+        PrefilterChain ch;
+        MRGFE_TRY(chain_from_params(fn, &p->filters, &ch));
+        if (size_t(p->width) * p->height == 0) return MRGFE_OK;  // where the reference returns early (:121-123)
+        if (!data || !out) { set_error("%s: NULL data / output", fn); return MRGFE_ERR_INVALID; }
+        ScanHead h;
+        h.data = data;
+        h.width = p->width; h.height = p->height; h.point_step = p->point_step; h.row_step = p->row_step;
+        h.off_x = p->off_x; h.off_y = p->off_y; h.off_z = p->off_z; h.off_intensity = p->off_intensity;
+        MRGFE_TRY(check_pointcloud2_layout(fn, h.width, h.height, h.point_step, &h.row_step, h.off_x, h.off_y, h.off_z, h.off_intensity));
+        h.deskew = p->deskew != 0;
+        for (int k = 0; k < 3; ++k) h.ang_v[k] = p->ang_v[k];
+        h.scan_period = p->scan_period;
+        h.transform = p->transform != 0;
+        float Tr[16];
+        col2row(p->T, Tr);
+        std::memcpy(h.T, Tr, sizeof(h.T));
+        MRGFE_LOCK(ctx);
+        MRGFE_TRY(ctx->bind());
+        return scan_chain(ctx, ch, h, out, out_n, on_device);
+    });
+}
+int mrgfe_scan_callback(mrgfe_ctx* ctx, const mrgfe_scan_params* p, const uint8_t* data, float* out_xyzi, size_t* out_n)
+{
+    return scan_callback_impl("mrgfe_scan_callback", ctx, p, data, out_xyzi, out_n, false);
+}
+int mrgfe_scan_callback_device(mrgfe_ctx* ctx, const mrgfe_scan_params* p, const uint8_t* data, void* d_out_xyzi, size_t* out_n)
+{
+    return scan_callback_impl("mrgfe_scan_callback_device", ctx, p, data, d_out_xyzi, out_n, true);
 }
 int mrgfe_calc_fitness_score(mrgfe_ctx* ctx, const float* cloud1, size_t n1, const float* cloud2, size_t n2, size_t stride, const double relpose[16], double max_range, double* out)
 {

@@ -37,6 +37,24 @@ int prefilter_set_device_driven(int mode);
 // the three passes back to back on the device (one upload, one download)
 int filter_chain(mrgfe_ctx* ctx, const PrefilterChain& chain, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool out_on_device = false);
 
+// What PrefilteringComponent::cloud_callback does to a scan BEFORE its filters (apps/prefiltering_component.cpp:119-146), as the scan head kernel's work
+// order: read the x / y / z / intensity fields out of the wire records of a sensor_msgs/PointCloud2 (validated: ingest.h check_pointcloud2_layout),
+// deskew, transform into base_link_frame.
+struct ScanHead {
+    const uint8_t* data = nullptr;  // host payload, (height - 1) * row_step + width * point_step bytes
+    uint32_t width = 0, height = 0, point_step = 16, row_step = 0, off_x = 0, off_y = 4, off_z = 8;
+    int32_t  off_intensity = 12;    // < 0: no such field, intensity 0
+    bool     deskew = false;
+    float    ang_v[3] = {0, 0, 0};  // as the IMU message gives it (negated on the way to the kernel, :275)
+    double   scan_period = 0.1;
+    bool     transform = false;
+    float    T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};  // row-major 3x4
+};
+// the same chain fed by the wire records of a scan: they go up once, and the scan head kernel writes the chain's packed input (and, in front of the
+// device-driven chain, the distance filter's flags and tile counts with it) — same output as mrgfe_ingest_pointcloud2 -> mrgfe_deskew ->
+// mrgfe_transform_cloud -> filter_chain, bit for bit
+int scan_chain(mrgfe_ctx* ctx, const PrefilterChain& chain, const ScanHead& head, void* out, size_t* out_n, bool out_on_device);
+
 int filter_distance(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, double near_t, double far_t, float* out, size_t* out_n);
 int filter_voxelgrid(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, float leaf, int min_pts, float* out, size_t* out_n, int* overflow);
 int filter_approx_voxelgrid(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, float leaf, float* out, size_t* out_n);

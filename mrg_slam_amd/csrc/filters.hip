@@ -15,8 +15,10 @@
 #include "cellsort.h"
 #include "dev_float.h"
 #include "dev_utils.h"
+#include "ingest.h"
 #include "ndt_build.h"
 #include "nn_grid.h"
+#include "scan_point.h"
 
 namespace mrgfe {
 
@@ -59,15 +61,18 @@ static int download(mrgfe_ctx* ctx, const void* d_src, size_t n, float* out)
 }
 
 // ---- distance filter -------------------------------------------------------------------------------------------
+// p.getVector3fMap().norm(): float sqrt((x*x + y*y) + z*z), compared as double with strict inequalities (a non-finite point fails them)
+__device__ __forceinline__ uint32_t distance_keep(const float4& p, double near_t, double far_t)
+{
+    const float  s = dot3f(p.x, p.x, p.y, p.y, p.z, p.z);
+    const double d = static_cast<double>(sqrtf(s));
+    return (d > near_t && d < far_t) ? 1u : 0u;
+}
 __global__ __launch_bounds__(256) void distance_flags_kernel(const float4* __restrict__ in, uint32_t n, double near_t, double far_t, uint32_t* __restrict__ flags)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const float4 p = in[i];
-    // p.getVector3fMap().norm(): float sqrt((x*x + y*y) + z*z), compared as double with strict inequalities
-    const float  s = dot3f(p.x, p.x, p.y, p.y, p.z, p.z);
-    const double d = static_cast<double>(sqrtf(s));
-    flags[i] = (d > near_t && d < far_t) ? 1u : 0u;
+    flags[i] = distance_keep(in[i], near_t, far_t);
 }
 
 int filter_distance_device(mrgfe_ctx* ctx, const float4* d_in, size_t n, double near_t, double far_t, float4* d_out, size_t* out_n)
@@ -491,11 +496,7 @@ __global__ __launch_bounds__(256) void pf_distance_tiles_kernel(const float4* __
     for (int k = 0; k < kTile / 256; ++k) {
         const uint32_t i = base + k * 256 + threadIdx.x;
         if (i < n) {
-            const float4 p = in[i];
-            // (distance_flags_kernel's test)
-            const float  s = dot3f(p.x, p.x, p.y, p.y, p.z, p.z);
-            const double d = static_cast<double>(sqrtf(s));
-            const uint32_t f = (d > near_t && d < far_t) ? 1u : 0u;
+            const uint32_t f = distance_keep(in[i], near_t, far_t);
             flags[i] = f;
             cnt += f;
         }
@@ -505,6 +506,83 @@ __global__ __launch_bounds__(256) void pf_distance_tiles_kernel(const float4* __
     if (lane_id() == 0) sw[wave_id()] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) blk[blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
+}
+// The scan head: PrefilteringComponent::cloud_callback up to its distance test (apps/prefiltering_component.cpp:119-149) in one pass over the wire
+// records of a scan.  Per point: the strided record is read (pcl::fromROSMsg), deskewed (kDeskew), transformed into base_link_frame (kTransform) —
+// scan_point.h, the bodies of gather_points_kernel, deskew_kernel and transform_cloud_kernel — and stored as the packed float4 the chain reads; with
+// kFlags the kernel is also the chain's distance filter (pf_distance_tiles_kernel's flags, tile counts and first state).  Same tile shape as that
+// kernel: one workgroup per 2048 points.  The three switches are compile-time: a variant carries only the registers of what it does.
+struct ScanHeadArgs {
+    const uint8_t* raw;
+    float4*        out;
+    uint32_t       n, width, row_step, point_step, ox, oy, oz;
+    int32_t        oi;
+    float          av[3];  // negated angular velocity
+    double         scan_period;
+    float          T[12];
+    double         near_t, far_t;
+    uint32_t*      flags;
+    uint32_t*      blk;
+    PfState*       st;
+    const float4  *cp0, *cp1;
+};
+template <bool kDeskew, bool kTransform, bool kFlags>
+__global__ __launch_bounds__(256) void scan_head_kernel(const ScanHeadArgs a)
+{
+    if (kFlags && blockIdx.x == 0 && threadIdx.x == 0) pf_state_init(a.st, a.cp0, a.cp1, a.n);
+    const uint32_t base = blockIdx.x * kTile;
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int k = 0; k < kTile / 256; ++k) {
+        const uint32_t i = base + k * 256 + threadIdx.x;
+        if (i < a.n) {
+            float4 p = load_point_record(a.raw, i, a.width, a.row_step, a.point_step, a.ox, a.oy, a.oz, a.oi);
+            if (kDeskew) p = deskew_point(p, i, a.n, a.av[0], a.av[1], a.av[2], a.scan_period);
+            if (kTransform) p = transform_finite_point(a.T, p);
+            a.out[i] = p;
+            if (kFlags) {
+                const uint32_t f = distance_keep(p, a.near_t, a.far_t);
+                a.flags[i] = f;
+                cnt += f;
+            }
+        }
+    }
+    if (!kFlags) return;
+    __shared__ uint32_t sw[4];
+    cnt = wave_sum(cnt);
+    if (lane_id() == 0) sw[wave_id()] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) a.blk[blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
+}
+// What the head needs besides the scan when it is also the chain's distance filter
+struct ScanHeadFlags {
+    double        near_t, far_t;
+    uint32_t*     flags;
+    uint32_t*     blk;
+    PfState*      st;
+    const float4 *cp0, *cp1;
+};
+static int launch_scan_head(mrgfe_ctx* ctx, const ScanHead& h, const void* d_raw, float4* d_out, const ScanHeadFlags* fl)
+{
+    ScanHeadArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.raw = static_cast<const uint8_t*>(d_raw);
+    a.out = d_out;
+    a.n = h.width * h.height;
+    a.width = h.width; a.row_step = h.row_step; a.point_step = h.point_step;
+    a.ox = h.off_x; a.oy = h.off_y; a.oz = h.off_z; a.oi = h.off_intensity;
+    for (int k = 0; k < 3; ++k) a.av[k] = h.ang_v[k] * -1.0f;  // ang_v *= -1 (:275), as deskew_device does
+    a.scan_period = h.scan_period;
+    std::memcpy(a.T, h.T, sizeof(a.T));
+    if (fl) { a.near_t = fl->near_t; a.far_t = fl->far_t; a.flags = fl->flags; a.blk = fl->blk; a.st = fl->st; a.cp0 = fl->cp0; a.cp1 = fl->cp1; }
+    using Kernel = void (*)(const ScanHeadArgs);
+    static const Kernel variants[8] = {scan_head_kernel<false, false, false>, scan_head_kernel<false, false, true>, scan_head_kernel<false, true, false>,
+                                       scan_head_kernel<false, true, true>,   scan_head_kernel<true, false, false>, scan_head_kernel<true, false, true>,
+                                       scan_head_kernel<true, true, false>,   scan_head_kernel<true, true, true>};
+    const Kernel kern = variants[(h.deskew ? 4 : 0) | (h.transform ? 2 : 0) | (fl ? 1 : 0)];
+    hipLaunchKernelGGL(kern, dim3((a.n + kTile - 1) / kTile), dim3(256), 0, ctx->stream, a);
+    MRGFE_HIP_CHECK(hipGetLastError());
+    return MRGFE_OK;
 }
 // Order-preserving compaction of the chain in ONE launch behind the tile counts: a workgroup adds up the counts of the tiles before its own
 // (and of all tiles) itself, ranks its tile's kept elements by ballots and moves them; workgroup 0 records the kept count in the chain's state, and (kWhich 0 and 1) every workgroup leaves the bounding box of what it kept for the stage that reads the output — the
@@ -686,11 +764,19 @@ static NnDeviceDrivenGrid& pf_grid(mrgfe_ctx* ctx)
     return *ctx->pf_grid;
 }
 
-// returns MRGFE_OK with *used = true when the device-driven chain produced the output, *used = false when the caller has to run the host-driven one
-static int filter_chain_device_driven(mrgfe_ctx* ctx, const PrefilterChain& ch, const float4* d_in, uint32_t n, float4* d_work, float4* d_final, size_t* out_n, bool* used)
+// the chains the device-driven form serves (the others, and its anomalies, go through the host-driven passes)
+static bool device_driven_applies(const PrefilterChain& ch, uint32_t n)
+{
+    return prefilter_device_driven_mode() && !ch.approx_voxelgrid && ch.voxelgrid && ch.outlier == 1 && n != 0 && ch.leaf > 0;
+}
+
+// A chain the device-driven form serves (device_driven_applies).  The packed input is in d_in already, or — `head` and its uploaded records `d_raw` —
+// the scan head kernel writes it there as the chain's first launch.  Returns MRGFE_OK with *used = true when it produced the output, *used = false
+// (an anomaly) when the caller has to run the host-driven passes over d_in.
+static int filter_chain_device_driven(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHead* head, const void* d_raw, float4* d_in, uint32_t n, float4* d_work, float4* d_final,
+                                      size_t* out_n, bool* used)
 {
     *used = false;
-    if (!prefilter_device_driven_mode() || ch.approx_voxelgrid || !ch.voxelgrid || ch.outlier != 1 || n == 0 || !(ch.leaf > 0)) return MRGFE_OK;
     hipStream_t st = ctx->stream;
     SliceTable  tab;
     tab.build(&n, 1);
@@ -715,8 +801,12 @@ static int filter_chain_device_driven(mrgfe_ctx* ctx, const PrefilterChain& ch, 
     const float4* vox_in = ch.distance ? d_work : d_in;
     const dim3    gtiles(std::max<uint32_t>(1, tab.total_blks));
     uint32_t*     d_blk = dblk.as<uint32_t>();
+    if (head) {  // (with the distance filter on, the head is pf_distance_tiles_kernel too)
+        const ScanHeadFlags fl{ch.near_t, ch.far_t, dfl.as<uint32_t>(), d_blk, d_st, vox_in, d_final};
+        MRGFE_TRY(launch_scan_head(ctx, *head, d_raw, d_in, ch.distance ? &fl : nullptr));
+    }
     if (ch.distance) {
-        hipLaunchKernelGGL(pf_distance_tiles_kernel, gtiles, b256, 0, st, d_in, n, ch.near_t, ch.far_t, dfl.as<uint32_t>(), d_blk, d_st, vox_in, d_final);
+        if (!head) hipLaunchKernelGGL(pf_distance_tiles_kernel, gtiles, b256, 0, st, d_in, n, ch.near_t, ch.far_t, dfl.as<uint32_t>(), d_blk, d_st, vox_in, d_final);
         hipLaunchKernelGGL(pf_compact_kernel<0>, gtiles, b256, 0, st, d_in, dfl.as<uint32_t>(), d_blk, n, d_work, d_st, h_status, d_part);
     } else {
         hipLaunchKernelGGL(pf_init_kernel, dim3(1), dim3(1), 0, st, d_st, vox_in, d_final, n);
@@ -760,17 +850,29 @@ static int filter_chain_device_driven(mrgfe_ctx* ctx, const PrefilterChain& ch, 
     return MRGFE_OK;  // the result is in d_work
 }
 
-int filter_chain(mrgfe_ctx* ctx, const PrefilterChain& ch, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool out_on_device)
+// Where the chain's packed input comes from — the only difference between the two entry families: a host cloud in one of the C ABI's layouts
+// (upload_cloud puts it into the first buffer), or the wire records of a scan (they go up as they are and the scan head kernel writes the buffer).
+struct ChainInput {
+    const float*    xyzi = nullptr;
+    size_t          stride = 16;
+    const ScanHead* head = nullptr;
+};
+
+static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const ChainInput& in, size_t n, void* out, size_t* out_n, bool out_on_device)
 {
     *out_n = 0;
     ctx->pf_out_valid = false;
     if (n == 0) return MRGFE_OK;
     if (n > 0x7fffffffu) { set_error("prefilter: cloud too large"); return MRGFE_ERR_INVALID; }
     DevBuf &a = ctx->pf_buf[0], &b = ctx->pf_buf[1];  // ping-pong, kept between calls (grow-only: a hipMalloc / hipFree pair per scan is a device-wide wait)
+    const void* d_raw = nullptr;
+    const bool  device_driven = device_driven_applies(ch, static_cast<uint32_t>(n));
     int rc = a.ensure(n * 16);
     if (rc == MRGFE_OK) rc = b.ensure(n * 16);
-    if (rc == MRGFE_OK) rc = upload_cloud(ctx, xyzi, n, stride, a.p);
-    if (rc == MRGFE_OK) {
+    if (rc == MRGFE_OK && !in.head) rc = upload_cloud(ctx, in.xyzi, n, in.stride, a.p);
+    if (rc == MRGFE_OK && in.head) rc = upload_raw_records(ctx, in.head->data, size_t(in.head->height - 1) * in.head->row_step + size_t(in.head->width) * in.head->point_step, &d_raw);
+    if (rc == MRGFE_OK && in.head && !device_driven) rc = launch_scan_head(ctx, *in.head, d_raw, a.as<float4>(), nullptr);  // (the device-driven chain launches it itself)
+    if (rc == MRGFE_OK && device_driven) {
         // the usual chain with its counts on the device: input a, work buffer = the caller's device buffer (capacity n) or b, result in the work buffer
         bool   used = false;
         size_t m = 0;
@@ -778,7 +880,7 @@ int filter_chain(mrgfe_ctx* ctx, const PrefilterChain& ch, const float* xyzi, si
         float4* final_buf = out_on_device ? b.as<float4>() : nullptr;
         DevBuf& c = ctx->scratch[13];
         if (!out_on_device) { rc = c.ensure(n * 16); final_buf = c.as<float4>(); }
-        if (rc == MRGFE_OK) rc = filter_chain_device_driven(ctx, ch, a.as<float4>(), static_cast<uint32_t>(n), work, final_buf, &m, &used);
+        if (rc == MRGFE_OK) rc = filter_chain_device_driven(ctx, ch, in.head, d_raw, a.as<float4>(), static_cast<uint32_t>(n), work, final_buf, &m, &used);
         if (rc != MRGFE_OK) return rc;
         if (used) {
             if (!out_on_device) ctx->pf_out_valid = false;  // (the cloud went to the host: nothing of the caller's stays on the device)
@@ -810,6 +912,20 @@ int filter_chain(mrgfe_ctx* ctx, const PrefilterChain& ch, const float* xyzi, si
     }
     if (rc == MRGFE_OK) *out_n = m;
     return rc;
+}
+
+int filter_chain(mrgfe_ctx* ctx, const PrefilterChain& ch, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool out_on_device)
+{
+    ChainInput in;
+    in.xyzi = xyzi;
+    in.stride = stride;
+    return filter_chain_from(ctx, ch, in, n, out, out_n, out_on_device);
+}
+int scan_chain(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHead& head, void* out, size_t* out_n, bool out_on_device)
+{
+    ChainInput in;
+    in.head = &head;
+    return filter_chain_from(ctx, ch, in, size_t(head.width) * head.height, out, out_n, out_on_device);
 }
 
 int filter_distance(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, double near_t, double far_t, float* out, size_t* out_n)

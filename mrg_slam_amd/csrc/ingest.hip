@@ -10,6 +10,7 @@
 // repacking loop) and gathered there: one lane per point, four 4-byte loads, one 16-byte store.
 #include "common.h"
 #include "ingest.h"
+#include "scan_point.h"
 
 namespace mrgfe {
 
@@ -18,14 +19,7 @@ __global__ __launch_bounds__(256) void gather_points_kernel(const uint8_t* __res
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const uint32_t row = i / width, col = i - row * width;
-    const uint8_t* p = raw + size_t(row) * row_step + size_t(col) * point_step;
-    float4 o;
-    o.x = *reinterpret_cast<const float*>(p + ox);
-    o.y = *reinterpret_cast<const float*>(p + oy);
-    o.z = *reinterpret_cast<const float*>(p + oz);
-    o.w = oi >= 0 ? *reinterpret_cast<const float*>(p + oi) : 0.0f;  // pcl::fromROSMsg leaves a missing field at PointXYZI's default (0)
-    dst[i] = o;
+    dst[i] = load_point_record(raw, i, width, row_step, point_step, ox, oy, oz, oi);  // (scan_point.h: the scan head kernel reads records the same way)
 }
 
 int launch_gather_points(mrgfe_ctx* ctx, const void* d_raw, float4* d_dst, size_t n, uint32_t width, uint32_t row_step, uint32_t point_step, uint32_t ox, uint32_t oy, uint32_t oz,
@@ -38,11 +32,9 @@ int launch_gather_points(mrgfe_ctx* ctx, const void* d_raw, float4* d_dst, size_
     return MRGFE_OK;
 }
 
-// raw host bytes -> device scratch (contiguous copy through the staging ring) -> gather into d_dst
-int upload_gathered(mrgfe_ctx* ctx, const void* raw, size_t raw_bytes, size_t n, uint32_t width, uint32_t row_step, uint32_t point_step, uint32_t ox, uint32_t oy, uint32_t oz,
-                    int32_t oi, void* d_dst)
+// raw host bytes -> the context's raw record buffer: one contiguous copy through the staging ring, stream-ordered (`raw` is free on return)
+int upload_raw_records(mrgfe_ctx* ctx, const void* raw, size_t raw_bytes, const void** d_raw)
 {
-    if (n == 0) return MRGFE_OK;
     const int slot = ctx->up_next;
     ctx->up_next ^= 1;
     if (!ctx->up_ev[slot]) MRGFE_HIP_CHECK(hipEventCreateWithFlags(&ctx->up_ev[slot], hipEventDisableTiming));
@@ -50,12 +42,37 @@ int upload_gathered(mrgfe_ctx* ctx, const void* raw, size_t raw_bytes, size_t n,
     PinBuf& pb = ctx->up_pin[slot];
     MRGFE_TRY(pb.ensure(raw_bytes));
     std::memcpy(pb.p, raw, raw_bytes);
-    // the raw device buffer is reused by the next gathered upload: stream order (copy k+1 after gather k) keeps that safe
+    // the raw device buffer is reused by the next upload of records: stream order (copy k+1 after the kernel that reads copy k) keeps that safe
     MRGFE_TRY(ctx->up_raw.ensure(raw_bytes));
     MRGFE_HIP_CHECK(hipMemcpyAsync(ctx->up_raw.p, pb.p, raw_bytes, hipMemcpyHostToDevice, ctx->stream));
     MRGFE_HIP_CHECK(hipEventRecord(ctx->up_ev[slot], ctx->stream));
     ctx->up_busy[slot] = true;
-    return launch_gather_points(ctx, ctx->up_raw.p, static_cast<float4*>(d_dst), n, width, row_step, point_step, ox, oy, oz, oi);
+    *d_raw = ctx->up_raw.p;
+    return MRGFE_OK;
+}
+
+// raw host bytes -> device scratch -> gather into d_dst
+int upload_gathered(mrgfe_ctx* ctx, const void* raw, size_t raw_bytes, size_t n, uint32_t width, uint32_t row_step, uint32_t point_step, uint32_t ox, uint32_t oy, uint32_t oz,
+                    int32_t oi, void* d_dst)
+{
+    if (n == 0) return MRGFE_OK;
+    const void* d_raw = nullptr;
+    MRGFE_TRY(upload_raw_records(ctx, raw, raw_bytes, &d_raw));
+    return launch_gather_points(ctx, d_raw, static_cast<float4*>(d_dst), n, width, row_step, point_step, ox, oy, oz, oi);
+}
+
+// the layout rules of a PointCloud2 payload with FLOAT32 x / y / z / intensity fields: shared by every entry point that reads one (`fn` names it in the message)
+int check_pointcloud2_layout(const char* fn, uint32_t width, uint32_t height, uint32_t point_step, uint32_t* row_step, uint32_t off_x, uint32_t off_y, uint32_t off_z,
+                             int32_t off_intensity)
+{
+    if (uint64_t(width) * point_step > 0xffffffffull) { set_error("%s: width %u x point_step %u does not fit a row", fn, width, point_step); return MRGFE_ERR_INVALID; }
+    if (*row_step == 0) *row_step = width * point_step;
+    const uint32_t offs[4] = {off_x, off_y, off_z, off_intensity >= 0 ? static_cast<uint32_t>(off_intensity) : 0u};
+    for (uint32_t o : offs)
+        if ((o % 4) != 0 || uint64_t(o) + 4 > point_step) { set_error("%s: FLOAT32 field offset %u does not fit point_step %u (offsets must be multiples of 4)", fn, o, point_step); return MRGFE_ERR_INVALID; }
+    if ((point_step % 4) != 0 || (*row_step % 4) != 0 || uint64_t(width) * point_step > *row_step) { set_error("%s: bad point_step %u / row_step %u", fn, point_step, *row_step); return MRGFE_ERR_INVALID; }
+    if (size_t(width) * height > 0x7fffffffu) { set_error("%s: cloud too large", fn); return MRGFE_ERR_INVALID; }
+    return MRGFE_OK;
 }
 
 }  // namespace mrgfe
@@ -69,13 +86,7 @@ extern "C" int mrgfe_ingest_pointcloud2(mrgfe_ctx* ctx, const uint8_t* data, uin
     const size_t n = size_t(width) * height;
     if (n == 0) return MRGFE_OK;
     if (!data || (!out_xyzi && !d_out_xyzi)) { set_error("mrgfe_ingest_pointcloud2: NULL data / no output"); return MRGFE_ERR_INVALID; }
-    if (uint64_t(width) * point_step > 0xffffffffull) { set_error("mrgfe_ingest_pointcloud2: width %u x point_step %u does not fit a row", width, point_step); return MRGFE_ERR_INVALID; }
-    if (row_step == 0) row_step = width * point_step;
-    const uint32_t offs[4] = {off_x, off_y, off_z, off_intensity >= 0 ? static_cast<uint32_t>(off_intensity) : 0u};
-    for (uint32_t o : offs)
-        if ((o % 4) != 0 || o + 4 > point_step) { set_error("mrgfe_ingest_pointcloud2: FLOAT32 field offset %u does not fit point_step %u (offsets must be multiples of 4)", o, point_step); return MRGFE_ERR_INVALID; }
-    if ((point_step % 4) != 0 || (row_step % 4) != 0 || uint64_t(width) * point_step > row_step) { set_error("mrgfe_ingest_pointcloud2: bad point_step %u / row_step %u", point_step, row_step); return MRGFE_ERR_INVALID; }
-    if (n > 0x7fffffffu) { set_error("mrgfe_ingest_pointcloud2: cloud too large"); return MRGFE_ERR_INVALID; }
+    MRGFE_TRY(check_pointcloud2_layout("mrgfe_ingest_pointcloud2", width, height, point_step, &row_step, off_x, off_y, off_z, off_intensity));
     MRGFE_LOCK(ctx);
     MRGFE_TRY(ctx->bind());
     void* d_dst = d_out_xyzi;

@@ -16,6 +16,7 @@
 #include "dev_float.h"
 #include "dev_utils.h"
 #include "filters.h"
+#include "scan_point.h"
 
 namespace mrgfe {
 
@@ -298,22 +299,9 @@ int remove_points_near_device(mrgfe_ctx* ctx, const float4* d_in, size_t n, cons
 // ---- deskewing ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void deskew_kernel(const float4* __restrict__ in, uint32_t n, float avx, float avy, float avz, double scan_period, float4* __restrict__ out)
 {
-#pragma clang fp contract(off)
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const float4 p = in[i];
-    const double delta_t = scan_period * static_cast<double>(i) / static_cast<double>(n);  // prefiltering_component.cpp:289
-    const float  qw = 1.0f;
-    const float  qx = static_cast<float>(delta_t / 2.0 * static_cast<double>(avx)), qy = static_cast<float>(delta_t / 2.0 * static_cast<double>(avy)),
-                 qz = static_cast<float>(delta_t / 2.0 * static_cast<double>(avz));
-    float n2 = qx * qx + qy * qy;  // delta_q.inverse() = conjugate / squaredNorm
-    n2 = n2 + qz * qz;
-    n2 = n2 + qw * qw;
-    const float ix = -qx / n2, iy = -qy / n2, iz = -qz / n2, iw = qw / n2;
-    float uvx = iy * p.z - iz * p.y, uvy = iz * p.x - ix * p.z, uvz = ix * p.y - iy * p.x;  // uv = 2 * vec x v
-    uvx = uvx + uvx; uvy = uvy + uvy; uvz = uvz + uvz;
-    const float cx = iy * uvz - iz * uvy, cy = iz * uvx - ix * uvz, cz = ix * uvy - iy * uvx;
-    out[i] = make_float4((p.x + iw * uvx) + cx, (p.y + iw * uvy) + cy, (p.z + iw * uvz) + cz, p.w);
+    out[i] = deskew_point(in[i], i, n, avx, avy, avz, scan_period);  // (scan_point.h: the scan head kernel runs the same body)
 }
 
 int deskew_device(mrgfe_ctx* ctx, const float4* d_in, size_t n, const float ang_v[3], double scan_period, float4* d_out)
@@ -332,13 +320,7 @@ __global__ __launch_bounds__(256) void transform_cloud_kernel(const float4* __re
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    float4 p = in[i];
-    if (finite3(p.x, p.y, p.z)) {  // pcl::transformPointCloud leaves the non-finite points of a non-dense cloud as they are
-        float x, y, z;
-        transform_point(T.m, p.x, p.y, p.z, x, y, z);
-        p.x = x; p.y = y; p.z = z;
-    }
-    out[i] = p;
+    out[i] = transform_finite_point(T.m, in[i]);  // pcl::transformPointCloud leaves the non-finite points of a non-dense cloud as they are (scan_point.h)
 }
 
 int transform_cloud_device(mrgfe_ctx* ctx, const float4* d_in, size_t n, const float T_rowmajor[16], float4* d_out)

@@ -1,0 +1,57 @@
+// csrc/scan_point.h — the per-point work of PrefilteringComponent::cloud_callback before its filters (apps/prefiltering_component.cpp:119-146),
+// shared by the standalone kernels (ingest.hip: gather_points_kernel; mapcloud.hip: deskew_kernel, transform_cloud_kernel) and the scan head kernel
+// (filters.hip): ONE body each, so the fused call cannot round differently from the separate calls.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "dev_float.h"
+#include "dev_utils.h"
+
+namespace mrgfe {
+
+// pcl::fromROSMsg for point i of a PointCloud2 payload (:119-120): four 4-byte loads at the FLOAT32 field offsets of the strided record; a missing
+// intensity field (oi < 0) stays at PointXYZI's default, 0.  Offsets and steps are multiples of 4 (check_pointcloud2_layout).
+__device__ __forceinline__ float4 load_point_record(const uint8_t* __restrict__ raw, uint32_t i, uint32_t width, uint32_t row_step, uint32_t point_step, uint32_t ox, uint32_t oy,
+                                                    uint32_t oz, int32_t oi)
+{
+    const uint32_t row = i / width, col = i - row * width;
+    const uint8_t* p = raw + size_t(row) * row_step + size_t(col) * point_step;
+    float4 o;
+    o.x = *reinterpret_cast<const float*>(p + ox);
+    o.y = *reinterpret_cast<const float*>(p + oy);
+    o.z = *reinterpret_cast<const float*>(p + oz);
+    o.w = oi >= 0 ? *reinterpret_cast<const float*>(p + oi) : 0.0f;
+    return o;
+}
+
+// PrefilteringComponent::deskewing (:272-290) for point i of a cloud of n points (n counts the non-finite points too): the point is rotated by the
+// inverse of Quaternionf(1, dt/2 * w) with dt = scan_period * i / n; `av*` is the angular velocity ALREADY negated (:275).
+__device__ __forceinline__ float4 deskew_point(float4 p, uint32_t i, uint32_t n, float avx, float avy, float avz, double scan_period)
+{
+#pragma clang fp contract(off)
+    const double delta_t = scan_period * static_cast<double>(i) / static_cast<double>(n);  // prefiltering_component.cpp:289
+    const float  qw = 1.0f;
+    const float  qx = static_cast<float>(delta_t / 2.0 * static_cast<double>(avx)), qy = static_cast<float>(delta_t / 2.0 * static_cast<double>(avy)),
+                 qz = static_cast<float>(delta_t / 2.0 * static_cast<double>(avz));
+    float n2 = qx * qx + qy * qy;  // delta_q.inverse() = conjugate / squaredNorm
+    n2 = n2 + qz * qz;
+    n2 = n2 + qw * qw;
+    const float ix = -qx / n2, iy = -qy / n2, iz = -qz / n2, iw = qw / n2;
+    float uvx = iy * p.z - iz * p.y, uvy = iz * p.x - ix * p.z, uvz = ix * p.y - iy * p.x;  // uv = 2 * vec x v
+    uvx = uvx + uvx; uvy = uvy + uvy; uvz = uvz + uvz;
+    const float cx = iy * uvz - iz * uvy, cy = iz * uvx - ix * uvz, cz = ix * uvy - iy * uvx;
+    return make_float4((p.x + iw * uvx) + cx, (p.y + iw * uvy) + cy, (p.z + iw * uvz) + cz, p.w);
+}
+
+// pcl::transformPointCloud on one point of a non-dense cloud: a non-finite point is left as it is, the intensity is copied.  T: row-major 3x4.
+__device__ __forceinline__ float4 transform_finite_point(const float* __restrict__ T, float4 p)
+{
+    if (finite3(p.x, p.y, p.z)) {
+        float x, y, z;
+        transform_point(T, p.x, p.y, p.z, x, y, z);
+        p.x = x; p.y = y; p.z = z;
+    }
+    return p;
+}
+
+}  // namespace mrgfe

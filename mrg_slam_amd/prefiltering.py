@@ -30,10 +30,24 @@ DEFAULTS = {  # config/mrg_slam.yaml:43-68 (the component's declare_parameter de
 
 
 class HipOps:
-    """The point operations on the GPU (``libmrgfe``): the three filters go through one fused call (one upload, one download)."""
+    """The point operations on the GPU (``libmrgfe``).  ``scan`` is the whole callback in one call (``mrgfe_scan_callback``: one upload, one
+    kernel for deskewing + transform + the distance test, one download); ``deskew`` / ``transform`` / ``filters`` are the same steps as
+    separate calls, the three filters through one fused call."""
 
     def __init__(self, ctx=None):
         self.ctx = ctx
+
+    def scan(self, cloud, ang_v, scan_period, T, p, dev_ptr: int = 0):
+        """deskew (``ang_v`` None: not) -> transform (``T`` None: not) -> filters of a packed [n, 4] cloud; with ``dev_ptr`` (room for n points)
+        the result stays on the device and the count is returned."""
+        return self.scan_pointcloud2(memoryview(cloud).cast("B"), len(cloud), 1, 16, {"x": 0, "y": 4, "z": 8, "intensity": 12}, 0, ang_v, scan_period, T, p, dev_ptr)
+
+    def scan_pointcloud2(self, data, width, height, point_step, fields, row_step, ang_v, scan_period, T, p, dev_ptr: int = 0):
+        from .filters import scan_callback, scan_callback_to_device
+
+        if dev_ptr:
+            return scan_callback_to_device(data, width, height, point_step, fields, dev_ptr, int(width) * int(height), row_step, ang_v, scan_period, T, p, ctx=self.ctx)
+        return scan_callback(data, width, height, point_step, fields, row_step, ang_v, scan_period, T, p, ctx=self.ctx)
 
     def deskew(self, cloud, ang_v, scan_period):
         from .map_cloud import deskew
@@ -95,11 +109,12 @@ class PrefilteringComponent:
         if self.p["enable_deskewing"]:
             self.imu_queue.append((float(stamp), np.asarray(angular_velocity, dtype=np.float32).reshape(3)))
 
-    def deskewing(self, cloud: np.ndarray, stamp: float) -> np.ndarray:
-        """:231-292.  The IMU message used is the first one newer than the scan, or the last one of the queue when none is; everything
-        before it leaves the queue (:262-270)."""
+    def _take_imu(self, stamp: float):
+        """The angular velocity ``deskewing`` uses for a scan stamped ``stamp`` (:234-270), or None when the queue is empty (the cloud is not
+        deskewed).  The IMU message used is the first one newer than the scan, or the last one of the queue when none is; everything before it
+        leaves the queue (:262-270)."""
         if not self.imu_queue:
-            return cloud
+            return None
         loc = 0
         ang_v = self.imu_queue[0][1]
         while loc < len(self.imu_queue):
@@ -108,7 +123,22 @@ class PrefilteringComponent:
                 break
             loc += 1
         del self.imu_queue[:loc]
-        return self.ops.deskew(cloud, ang_v, self.p["scan_period"])
+        return ang_v
+
+    def deskewing(self, cloud: np.ndarray, stamp: float) -> np.ndarray:
+        """:231-292."""
+        ang_v = self._take_imu(stamp)
+        return cloud if ang_v is None else self.ops.deskew(cloud, ang_v, self.p["scan_period"])
+
+    def _lookup(self, frame_id: str):
+        """(ok, T): the transform into base_link_frame (:126-146) — T None when there is none to apply, ok False where the reference warns and
+        returns early (tf2::TransformException, :133-138)."""
+        if not (self.p["base_link_frame"] and self.lookup_transform is not None):
+            return True, None
+        try:
+            return True, self.lookup_transform(self.p["base_link_frame"], frame_id)
+        except Exception:  # noqa: BLE001
+            return False, None
 
     def cloud_callback(self, cloud, stamp: float = 0.0, frame_id: str = ""):
         """:116-149.  Returns the filtered cloud (what ``points_pub_`` publishes), or None where the reference returns early (empty input,
@@ -116,11 +146,27 @@ class PrefilteringComponent:
         src = np.ascontiguousarray(np.asarray(cloud, dtype=np.float32).reshape(-1, 4))
         if len(src) == 0:
             return None
+        if hasattr(self.ops, "scan"):  # the point operations of the whole callback in one call; the control flow around them is the same
+            ang_v = self._take_imu(stamp)
+            ok, T = self._lookup(frame_id)
+            return self.ops.scan(src, ang_v, self.p["scan_period"], T, self.p) if ok else None
         src = self.deskewing(src, stamp)
-        if self.p["base_link_frame"] and self.lookup_transform is not None:
-            try:
-                T = self.lookup_transform(self.p["base_link_frame"], frame_id)
-            except Exception:  # noqa: BLE001 - tf2::TransformException: warn and return early (:133-138)
-                return None
+        ok, T = self._lookup(frame_id)
+        if not ok:
+            return None
+        if T is not None:
             src = self.ops.transform(src, T)
         return self.ops.filters(src, self.p)
+
+    def pointcloud2_callback(self, data, width: int, height: int, point_step: int, fields: dict, row_step: int = 0, stamp: float = 0.0, frame_id: str = "",
+                             dev_ptr: int = 0):
+        """``cloud_callback`` from the wire message (the payload and layout of a sensor_msgs/PointCloud2): pcl::fromROSMsg happens in the same
+        GPU call as the rest.  Returns the filtered cloud, or — with ``dev_ptr`` (device memory for width * height packed points) — leaves it
+        there and returns its point count; None where the reference returns early.  Needs point operations with ``scan_pointcloud2`` (HipOps)."""
+        if int(width) * int(height) == 0:
+            return None
+        ang_v = self._take_imu(stamp)
+        ok, T = self._lookup(frame_id)
+        if not ok:
+            return None
+        return self.ops.scan_pointcloud2(data, width, height, point_step, fields, row_step, ang_v, self.p["scan_period"], T, self.p, dev_ptr)
