@@ -191,6 +191,28 @@ int  mrgfe_reg_final_transformation(const mrgfe_reg* reg, float out[16]);
 int  mrgfe_reg_fitness(mrgfe_reg* reg, double max_range, double* out);
 /* replaces getSearchMethodTarget()->nearestKSearch(pt, 1, ..): scan_matching_odometry_component.cpp:405-417 (batched) */
 int  mrgfe_reg_nn1_target(mrgfe_reg* reg, const float* query_xyzi, size_t n, size_t stride_bytes, int32_t* idx, float* sqdist);
+/* replaces ScanMatchingOdometryComponent::publish_scan_matching_status (scan_matching_odometry_component.cpp:391-431), the call the odometry makes after
+ * every align while its status topic has a subscriber: the fields of mrg_slam_msgs/ScanMatchingStatus from ONE fitness pass over the source and one host
+ * wait.  The grid of mrgfe_reg_fitness / mrgfe_reg_nn1_target is searched; no cloud is uploaded or downloaded.  matching_error has the bits of
+ * mrgfe_reg_fitness with max_range = DBL_MAX; num_inliers counts the source points whose squared 1-NN distance (float, promoted to double) is strictly
+ * below max_correspondence_dist squared (:413; the reference uses 0.5).  msf_delta (column-major 4x4, may be NULL): the prediction of :393; with NULL,
+ * prediction_error is zero and has_prediction 0.  Errors as mrgfe_reg_fitness; an empty target or source gives matching_error = DBL_MAX and no inliers. */
+typedef struct mrgfe_matching_status {
+    int32_t  has_converged;       /* hasConverged()                                                                               :402 */
+    uint32_t n_points;            /* aligned->size(): the source's point count                                                         */
+    uint32_t num_inliers;         /*                                                                                          :407-416 */
+    float    inlier_fraction;     /* static_cast<float>(num_inliers) / n_points (n_points == 0: NaN, as 0.0f / 0)                 :417 */
+    double   matching_error;      /* getFitnessScore(), max_range = DBL_MAX                                                       :403 */
+    double   relative_pose[7];    /* isometry2pose(Isometry3f(final).cast<double>()): position x y z, orientation x y z w         :419 */
+    double   prediction_error[7]; /* isometry2pose((Isometry3f(final).inverse() * msf_delta).cast<double>())                  :426-427 */
+    int32_t  has_prediction;      /* msf_delta was given                                                                               */
+    int32_t  reserved;
+} mrgfe_matching_status;          /* 144 bytes */
+size_t mrgfe_matching_status_size(void); /* sizeof(mrgfe_matching_status) as the library was compiled */
+int    mrgfe_reg_matching_status(mrgfe_reg* reg, double max_correspondence_dist, const float* msf_delta, mrgfe_matching_status* out);
+/* The two poses of the status alone, pure host arithmetic (no context, no GPU): relative_pose from the column-major final transformation, and, when
+ * msf_delta is not NULL, prediction_error (else left untouched; may then be NULL).  The inverse and the product are float, the quaternions double. */
+int    mrgfe_status_poses(const float final_transformation[16], const float* msf_delta, double relative_pose[7], double prediction_error[7]);
 /* extra read-outs (pcl: getFinalNumIteration / ndt: getTransformationProbability; 6x6 Hessian for the pose gather of §8e) */
 int    mrgfe_reg_iterations(const mrgfe_reg* reg);
 int    mrgfe_reg_evaluations(const mrgfe_reg* reg); /* derivative (NDT) / linearize+error (GICP) passes of the last align */

@@ -284,6 +284,19 @@ class HipRegistration : public pcl::Registration<PointSource, PointTarget, float
         mrgfe_reg_fitness(reg_, max_range, &out);
         return out;
     }
+    // ScanMatchingOdometryComponent::publish_scan_matching_status (apps/scan_matching_odometry_component.cpp:391-431) for the last align: matching error,
+    // inlier count and the poses from one device pass and one wait, without the aligned cloud leaving or re-entering the device.  msf_delta: the
+    // prediction (:393), or nullptr when msf_source is empty.  On an error (see mrgfe_last_error) has_converged is 0 and matching_error DBL_MAX.
+    mrgfe_matching_status matchingStatus(double max_correspondence_dist = 0.5, const Eigen::Matrix4f* msf_delta = nullptr)
+    {
+        mrgfe_matching_status s{};
+        if (mrgfe_reg_matching_status(reg_, max_correspondence_dist, msf_delta ? msf_delta->data() /* column-major */ : nullptr, &s) != MRGFE_OK) {
+            PCL_ERROR("[%s::matchingStatus] %s\n", this->reg_name_.c_str(), mrgfe_last_error());
+            s = mrgfe_matching_status{};
+            s.matching_error = std::numeric_limits<double>::max();
+        }
+        return s;
+    }
     int getFinalNumIteration() const { return mrgfe_reg_iterations(reg_); }
     std::array<double, 36> getFinalHessian() const  // 6x6, row-major
     {

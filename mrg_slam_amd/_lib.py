@@ -67,6 +67,14 @@ class FloorResult(C.Structure):
                 ("n_inliers", C.c_uint32), ("iterations", C.c_int32), ("skipped", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MatchingStatus(C.Structure):
+    """struct mrgfe_matching_status: the fields of mrg_slam_msgs/ScanMatchingStatus that ``publish_scan_matching_status`` fills
+    (apps/scan_matching_odometry_component.cpp:391-431); poses are position x y z, orientation x y z w."""
+
+    _fields_ = [("has_converged", C.c_int32), ("n_points", C.c_uint32), ("num_inliers", C.c_uint32), ("inlier_fraction", C.c_float), ("matching_error", C.c_double),
+                ("relative_pose", C.c_double * 7), ("prediction_error", C.c_double * 7), ("has_prediction", C.c_int32), ("reserved", C.c_int32)]
+
+
 FLOOR_REASONS = ("found", "empty_input", "none_after_clip", "too_few_filtered", "no_model", "too_few_inliers", "not_vertical")
 
 
@@ -146,6 +154,9 @@ SIGNATURES = {
     "mrgfe_reg_final_transformation": (C.c_int, [_vp, _fp]),
     "mrgfe_reg_fitness": (C.c_int, [_vp, C.c_double, _dp]),
     "mrgfe_reg_nn1_target": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, _ip, _fp]),
+    "mrgfe_matching_status_size": (C.c_size_t, []),
+    "mrgfe_reg_matching_status": (C.c_int, [_vp, C.c_double, _fp, C.POINTER(MatchingStatus)]),
+    "mrgfe_status_poses": (C.c_int, [_fp, _fp, _dp, _dp]),
     "mrgfe_reg_iterations": (C.c_int, [_vp]),
     "mrgfe_reg_evaluations": (C.c_int, [_vp]),
     "mrgfe_reg_trans_probability": (C.c_double, [_vp]),
@@ -318,6 +329,8 @@ def lib() -> C.CDLL:
             if hasattr(L, name):
                 f = getattr(L, name)
                 f.restype, f.argtypes = res, args
+        if hasattr(L, "mrgfe_matching_status_size") and L.mrgfe_matching_status_size() != C.sizeof(MatchingStatus):
+            raise RuntimeError(f"libmrgfe.so was built with a mrgfe_matching_status of {L.mrgfe_matching_status_size()} bytes, the binding mirrors {C.sizeof(MatchingStatus)}")
         _lib = L
     return _lib
 

@@ -455,6 +455,98 @@ int mrgfe_reg_nn1_target(mrgfe_reg* reg, const float* q, size_t n, size_t stride
     return reg->nn.nearest_host(reg->ctx, q, n, stride_bytes, idx, sqd);
 }
 
+// ---- scan-matching status (ScanMatchingOdometryComponent::publish_scan_matching_status, apps/scan_matching_odometry_component.cpp:391-431) ----
+// isometry2pose (src/ros_utils.cpp:52-66) of a double isometry given as rotation R (row-major) and translation t: position, then Eigen::Quaterniond(R) as
+// x y z w.  [UPSTREAM-RECALL] Eigen 3.3 Geometry/Quaternion.h, quaternionbase_assign_impl<Other, 3, 3>: the algorithm odometry.quat_w restates in float,
+// here in double and for all four components; the trace is summed (m00 + m11) + m22 as there.
+static void isometry2pose(const double R[3][3], const double t[3], double pose[7])
+{
+    double q[4];  // x y z w
+    double tr = (R[0][0] + R[1][1]) + R[2][2];
+    if (tr > 0.0) {
+        tr = std::sqrt(tr + 1.0);
+        q[3] = 0.5 * tr;
+        tr = 0.5 / tr;
+        q[0] = (R[2][1] - R[1][2]) * tr;
+        q[1] = (R[0][2] - R[2][0]) * tr;
+        q[2] = (R[1][0] - R[0][1]) * tr;
+    } else {
+        int i = 0;
+        if (R[1][1] > R[0][0]) i = 1;
+        if (R[2][2] > R[i][i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        tr = std::sqrt(R[i][i] - R[j][j] - R[k][k] + 1.0);
+        q[i] = 0.5 * tr;
+        tr = 0.5 / tr;
+        q[3] = (R[k][j] - R[j][k]) * tr;
+        q[j] = (R[j][i] + R[i][j]) * tr;
+        q[k] = (R[k][i] + R[i][k]) * tr;
+    }
+    pose[0] = t[0]; pose[1] = t[1]; pose[2] = t[2];
+    pose[3] = q[0]; pose[4] = q[1]; pose[5] = q[2]; pose[6] = q[3];
+}
+
+int mrgfe_status_poses(const float final_transformation[16], const float* msf_delta, double relative_pose[7], double prediction_error[7])
+{
+    if (!final_transformation || !relative_pose || (msf_delta && !prediction_error)) { set_error("mrgfe_status_poses: NULL argument"); return MRGFE_ERR_INVALID; }
+    const float* F = final_transformation;  // column-major: element (r, c) at [4 c + r]
+    double R[3][3], t[3];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) R[r][c] = static_cast<double>(F[4 * c + r]);  // Isometry3f(final).cast<double>(): floats widened exactly (:419)
+        t[r] = static_cast<double>(F[12 + r]);
+    }
+    isometry2pose(R, t, relative_pose);
+    if (!msf_delta) return MRGFE_OK;
+    // Isometry3f(final).inverse() * msf_delta (:426), all in float.  [UPSTREAM-RECALL] Eigen 3.3 Geometry/Transform.h: the inverse of an Isometry is
+    // (R^T, -R^T t); the product of two isometries is (R1 R2, R1 t2 + t1); three-term sums left to right.
+    const float* D = msf_delta;
+    float Ri[3][3], ti[3], Re[3][3], te[3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Ri[r][c] = F[4 * r + c];
+    for (int r = 0; r < 3; ++r) ti[r] = ((-Ri[r][0]) * F[12] + (-Ri[r][1]) * F[13]) + (-Ri[r][2]) * F[14];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) Re[r][c] = (Ri[r][0] * D[4 * c] + Ri[r][1] * D[4 * c + 1]) + Ri[r][2] * D[4 * c + 2];
+        te[r] = ((Ri[r][0] * D[12] + Ri[r][1] * D[13]) + Ri[r][2] * D[14]) + ti[r];
+    }
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) R[r][c] = static_cast<double>(Re[r][c]);
+        t[r] = static_cast<double>(te[r]);
+    }
+    isometry2pose(R, t, prediction_error);  // error.cast<double>() (:427)
+    return MRGFE_OK;
+}
+
+size_t mrgfe_matching_status_size(void) { return sizeof(mrgfe_matching_status); }
+
+int mrgfe_reg_matching_status(mrgfe_reg* reg, double max_correspondence_dist, const float* msf_delta, mrgfe_matching_status* out)
+{
+    return abi_guard("mrgfe_reg_matching_status", [&]() -> int {
+        if (!reg || !out) { set_error("mrgfe_reg_matching_status: NULL argument"); return MRGFE_ERR_INVALID; }
+        if (!reg->has_target || !reg->has_source) { set_error("matching status: target / source not set"); return MRGFE_ERR_STATE; }
+        MRGFE_LOCK(reg->ctx);
+        MRGFE_TRY(reg->ctx->bind());
+        TraceRange tr("mrgfe_reg_matching_status");
+        double res[3] = {DBL_MAX, 0.0, 0.0};
+        if (reg->n_tgt > 0 && reg->n_src > 0) MRGFE_TRY(reg_ensure_nn(reg));
+        if (reg->n_tgt > 0 && reg->n_src > 0 && reg->nn.dev().n > 0) {  // (a target without a finite point: nothing to match, as NnGrid::fitness)
+            const NnFitnessJob job = reg->nn.make_fitness_job(static_cast<const float4*>(reg->d_src), reg->n_src, reg->final_rm);
+            MRGFE_TRY(nn_status_batch(reg->ctx, &job, 1, max_correspondence_dist * max_correspondence_dist, res));  // :413
+        }
+        mrgfe_matching_status s{};
+        s.has_converged = reg->converged ? 1 : 0;
+        s.n_points = static_cast<uint32_t>(reg->n_src);
+        s.num_inliers = static_cast<uint32_t>(res[2]);
+        s.inlier_fraction = static_cast<float>(s.num_inliers) / static_cast<float>(reg->n_src);  // :417 (float / size_t: the size converts to float)
+        s.matching_error = res[0];
+        float final_cm[16];
+        row2col(reg->final_rm, final_cm);
+        s.has_prediction = msf_delta ? 1 : 0;
+        MRGFE_TRY(mrgfe_status_poses(final_cm, msf_delta, s.relative_pose, s.prediction_error));
+        *out = s;
+        return MRGFE_OK;
+    });
+}
+
 int    mrgfe_reg_iterations(const mrgfe_reg* reg) { return reg ? reg->iterations : 0; }
 int    mrgfe_reg_evaluations(const mrgfe_reg* reg) { return reg ? reg->evaluations : 0; }
 double mrgfe_reg_trans_probability(const mrgfe_reg* reg) { return reg ? reg->trans_probability : 0.0; }

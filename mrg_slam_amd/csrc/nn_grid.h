@@ -148,6 +148,11 @@ NnGrid& ctx_tmp_grid(mrgfe_ctx* ctx);
 // all jobs in one launch (blockIdx.y = job); out[j] = mean squared distance or DBL_MAX when nothing is in range
 int nn_fitness_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_range, double* out);
 
+// The scan-matching status of every job (ScanMatchingOdometryComponent::publish_scan_matching_status, apps/scan_matching_odometry_component.cpp:403-417):
+// nn_fitness_batch's passes with max_range = DBL_MAX, then out[3 j .. 3 j + 2] = (getFitnessScore: the same bits as nn_fitness_batch, or DBL_MAX when
+// nothing was counted; the number of counted queries; the number of them whose squared distance, promoted to double, is < inlier_sq).  One host wait.
+int nn_status_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double inlier_sq, double* out);
+
 // The same passes as a correspondence search (fast_gicp / small_gicp update_correspondences): jobs[j].idx_out[i] = index of the target point
 // nearest to T * src[i] (ties: the lowest index) if its squared distance is < max_sq, else -1.  Enqueued on ctx->stream, no host wait.
 int nn_nearest_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_sq);

@@ -1821,6 +1821,59 @@ __global__ __launch_bounds__(256) void nn_fitness_final_kernel(const double* __r
     }
 }
 
+// ---- scan-matching status (mrgfe_reg_matching_status) -----------------------------------------------------------------------------
+// nn_fit_sum_kernel with a third column: the slices, the per-thread order, wave_sum, the four-wave combination and the zeros of a block past the
+// job's end are the same, so columns 0 and 1 hold the bits nn_fit_sum_kernel writes.  Column 2 counts the counted queries whose distance,
+// promoted to double, is strictly below inlier_sq (scan_matching_odometry_component.cpp:413); the count is summed as uint32_t and carried
+// exactly (a slice holds at most 1024).
+__global__ __launch_bounds__(256) void nn_fit_status_sum_kernel(const NnFitnessJob* __restrict__ jobs, const uint32_t* __restrict__ job_off, const float* __restrict__ sqd,
+                                                                 double inlier_sq, double* __restrict__ partial)
+{
+    __shared__ double   s_sum[4];
+    __shared__ uint32_t s_cnt[2][4];
+    const uint32_t n = jobs[blockIdx.y].n, off = job_off[blockIdx.y];
+    double   sum = 0.0;
+    uint32_t cnt = 0, inl = 0;
+    for (uint32_t k = 0; k < kFitSumSlice / 256u; ++k) {
+        const uint32_t i = blockIdx.x * kFitSumSlice + k * 256u + threadIdx.x;
+        if (i < n) {
+            const float d = sqd[off + i];
+            if (d >= 0.0f) {
+                sum += static_cast<double>(d);
+                ++cnt;
+                if (static_cast<double>(d) < inlier_sq) ++inl;
+            }
+        }
+    }
+    sum = wave_sum(sum);
+    cnt = wave_sum(cnt);
+    inl = wave_sum(inl);
+    if (lane_id() == 0) { s_sum[wave_id()] = sum; s_cnt[0][wave_id()] = cnt; s_cnt[1][wave_id()] = inl; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double* o = partial + 3 * (size_t(blockIdx.y) * gridDim.x + blockIdx.x);
+        o[0] = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
+        o[1] = static_cast<double>(s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3]);
+        o[2] = static_cast<double>(s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3]);
+    }
+}
+
+// nn_fitness_final_kernel's tree over the three columns of the status partials (the two counts are integers below 2^32: exact in f64 in any order)
+__global__ __launch_bounds__(256) void nn_fit_status_final_kernel(const double* __restrict__ partial, uint32_t nblk, double* __restrict__ out)
+{
+    __shared__ double s_v[3][4];
+    const double* part = partial + 3 * size_t(blockIdx.x) * nblk;
+    double v[3] = {0, 0, 0};
+    for (uint32_t i = threadIdx.x; i < nblk; i += 256)
+        for (int c = 0; c < 3; ++c) v[c] += part[3 * i + c];
+    for (int c = 0; c < 3; ++c) v[c] = wave_sum(v[c]);
+    if (lane_id() == 0)
+        for (int c = 0; c < 3; ++c) s_v[c][wave_id()] = v[c];
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int c = 0; c < 3; ++c) out[3 * blockIdx.x + c] = ((s_v[c][0] + s_v[c][1]) + s_v[c][2]) + s_v[c][3];
+}
+
 // ---- bounded best-candidate selection (mrgfe_batch_align_best) -------------------------------------------------------------------
 // The bound sums: nn_fit_sum_kernel's slices and per-thread order, wave_sum and the four-wave combination, over the two ends of every query's
 // interval (lo: the block / seed lower bound, hi: the attained distance in sqd).  An end is counted when it is >= 0 (kFitNone: settled out of
@@ -1915,6 +1968,7 @@ struct FitPlan {
     hipStream_t           st;
     size_t                count, total = 0;
     double                r;      // max_range (max_sq of the correspondence search)
+    double                inlier_sq = 0;  // the status sums' third column: counted queries with a squared distance below it
     bool                  sweep;  // seed + sweep with the walk of the unseeded queries beside it; else the walk of every queued query
     bool                  diag = false;  // nn_fitness_batch's diagnostics: events ev_fit[0 .. 3] and ev_side[1] / [2], the counters zeroed on load
     unsigned long long*   counters = nullptr;  // the seed's and the sweep's diagnostic counters (d_stats; fitness passes only)
@@ -1955,7 +2009,7 @@ struct FitPlan {
         nblk_sum = std::max<uint32_t>(1, (max_n + kFitSumSlice - 1) / kFitSumSlice);
         return MRGFE_OK;
     }
-    // the workspaces for `cols` partial sums per slice (0: no sums, 2: the exact sums, 4: the bound sums, which also need lo); then jobs and
+    // the workspaces for `cols` partial sums per slice (0: no sums, 2: the exact sums, 3: the status sums, 4: the bound sums, which also need lo); then jobs and
     // offsets to the device (`staged`: through the context's pinned staging ring), the queue lengths (and with `diag` the counters) zeroed
     int load(const NnFitnessJob* jobs, int cols, bool staged)
     {
@@ -2027,15 +2081,17 @@ struct FitPlan {
         if (diag) MRGFE_HIP_CHECK(hipEventRecord(ctx->ev_fit[3], st));
         return MRGFE_OK;
     }
-    // the per-job sums ((Σd, #d) with 2 columns, (Σlo, #lo, Σhi, #hi) with 4) to res[cols * count], the queue lengths to cnts[2 * (count + 1)]
+    // the per-job sums ((Σd, #d) with 2 columns, (Σd, #d, #{d < inlier_sq}) with 3, (Σlo, #lo, Σhi, #hi) with 4) to res[cols * count], the queue lengths to cnts[2 * (count + 1)]
     // if not null and the counters to h_stats when they are on; one host wait
     int sums(int cols, double* res, uint32_t* cnts, unsigned long long* h_stats = nullptr)
     {
         const dim3 g(nblk_sum, static_cast<uint32_t>(count)), g_final(static_cast<uint32_t>(count));
-        if (cols == 4) hipLaunchKernelGGL(nn_fit_bound_sum_kernel, g, dim3(256), 0, st, d_jobs, d_off, d_lo, d_sqd, r, d_part);
-        else           hipLaunchKernelGGL(nn_fit_sum_kernel, g, dim3(256), 0, st, d_jobs, d_off, d_sqd, d_part);
-        if (cols == 4) hipLaunchKernelGGL(nn_fitness_bound_final_kernel, g_final, dim3(256), 0, st, d_part, nblk_sum, d_res);
-        else           hipLaunchKernelGGL(nn_fitness_final_kernel, g_final, dim3(256), 0, st, d_part, nblk_sum, d_res);
+        if (cols == 4)      hipLaunchKernelGGL(nn_fit_bound_sum_kernel, g, dim3(256), 0, st, d_jobs, d_off, d_lo, d_sqd, r, d_part);
+        else if (cols == 3) hipLaunchKernelGGL(nn_fit_status_sum_kernel, g, dim3(256), 0, st, d_jobs, d_off, d_sqd, inlier_sq, d_part);
+        else                hipLaunchKernelGGL(nn_fit_sum_kernel, g, dim3(256), 0, st, d_jobs, d_off, d_sqd, d_part);
+        if (cols == 4)      hipLaunchKernelGGL(nn_fitness_bound_final_kernel, g_final, dim3(256), 0, st, d_part, nblk_sum, d_res);
+        else if (cols == 3) hipLaunchKernelGGL(nn_fit_status_final_kernel, g_final, dim3(256), 0, st, d_part, nblk_sum, d_res);
+        else                hipLaunchKernelGGL(nn_fitness_final_kernel, g_final, dim3(256), 0, st, d_part, nblk_sum, d_res);
         MRGFE_HIP_CHECK(hipGetLastError());
         MRGFE_HIP_CHECK(hipMemcpyAsync(res, d_res, sizeof(double) * cols * count, hipMemcpyDeviceToHost, st));
         if (cnts) MRGFE_HIP_CHECK(hipMemcpyAsync(cnts, d_cnt, sizeof(uint32_t) * 2 * (count + 1), hipMemcpyDeviceToHost, st));
@@ -2060,27 +2116,27 @@ int nn_nearest_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, dou
     return MRGFE_OK;
 }
 
-int nn_fitness_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_range, double* out)
+// The exact passes behind nn_fitness_batch (cols 2) and nn_status_batch (cols 3): block -> seed -> sweep / far, the sums, one host wait, the
+// context's FitStats.  res[cols * count] receives the per-job columns; *ran = false (and nothing launched) when no job has a query.
+static int fit_exact_passes(mrgfe_ctx* ctx, const char* fn, const NnFitnessJob* jobs, size_t count, double max_range, int cols, double inlier_sq, double* res, bool* ran)
 {
-    for (size_t j = 0; j < count; ++j) out[j] = DBL_MAX;
-    if (count == 0) return MRGFE_OK;
+    *ran = false;
     FitPlan<false> fp(ctx, count, max_range, fit_sweep_mode() != 0);
-    MRGFE_TRY(fp.plan("nn_fitness_batch", jobs));
+    fp.inlier_sq = inlier_sq;
+    MRGFE_TRY(fp.plan(fn, jobs));
     if (fp.max_n == 0) return MRGFE_OK;
     for (auto& e : ctx->ev_fit)
         if (!e) MRGFE_HIP_CHECK(hipEventCreate(&e));
     fp.diag = true;
-    MRGFE_TRY(fp.load(jobs, 2, false));
+    MRGFE_TRY(fp.load(jobs, cols, false));
     fp.counters = fit_stats_mode() != 0 ? fp.d_stats : nullptr;
     fp.clocks = fit_stats_mode() > 1 ? 1 : 0;
     MRGFE_TRY(fp.near());
     MRGFE_TRY(fp.far());
-    std::vector<double>   res(2 * count);
     std::vector<uint32_t> cnts(2 * (count + 1));
     unsigned long long    h_stats[kSweepStats] = {0};
-    MRGFE_TRY(fp.sums(2, res.data(), cnts.data(), h_stats));
-    for (size_t j = 0; j < count; ++j)
-        if (res[2 * j + 1] > 0) out[j] = res[2 * j] / res[2 * j + 1];
+    MRGFE_TRY(fp.sums(cols, res, cnts.data(), h_stats));
+    *ran = true;
     FitStats& fs = ctx->fit_stats;
     float ms[3] = {0, 0, 0};
     for (int k = 0; k < 3; ++k) (void)hipEventElapsedTime(&ms[k], ctx->ev_fit[k], ctx->ev_fit[k + 1]);
@@ -2101,6 +2157,35 @@ int nn_fitness_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, dou
                              "from blocks %llu, none %llu; clocks (thread 0 of every workgroup) seed / bricks / cells / points: %llu %llu %llu %llu\n",
                      static_cast<unsigned long long>(fs.queued), h_stats[0], h_stats[1], h_stats[7], h_stats[8], h_stats[2], h_stats[3], h_stats[4], h_stats[5], h_stats[6], h_stats[9], h_stats[10],
                      h_stats[11], h_stats[12]);
+    return MRGFE_OK;
+}
+
+int nn_fitness_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_range, double* out)
+{
+    for (size_t j = 0; j < count; ++j) out[j] = DBL_MAX;
+    if (count == 0) return MRGFE_OK;
+    std::vector<double> res(2 * count);
+    bool                ran = false;
+    MRGFE_TRY(fit_exact_passes(ctx, "nn_fitness_batch", jobs, count, max_range, 2, 0.0, res.data(), &ran));
+    if (!ran) return MRGFE_OK;
+    for (size_t j = 0; j < count; ++j)
+        if (res[2 * j + 1] > 0) out[j] = res[2 * j] / res[2 * j + 1];
+    return MRGFE_OK;
+}
+
+int nn_status_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double inlier_sq, double* out)
+{
+    for (size_t j = 0; j < count; ++j) { out[3 * j] = DBL_MAX; out[3 * j + 1] = out[3 * j + 2] = 0.0; }
+    if (count == 0) return MRGFE_OK;
+    std::vector<double> res(3 * count);
+    bool                ran = false;
+    MRGFE_TRY(fit_exact_passes(ctx, "nn_status_batch", jobs, count, DBL_MAX, 3, inlier_sq, res.data(), &ran));
+    if (!ran) return MRGFE_OK;
+    for (size_t j = 0; j < count; ++j) {
+        if (res[3 * j + 1] > 0) out[3 * j] = res[3 * j] / res[3 * j + 1];
+        out[3 * j + 1] = res[3 * j + 1];
+        out[3 * j + 2] = res[3 * j + 2];
+    }
     return MRGFE_OK;
 }
 

@@ -68,6 +68,15 @@ class ScanMatchingOdometry:
         self.keyframes = 0  # how many times a cloud became the keyframe
         self.last_converged = True
 
+    def status(self, msf_delta=None, max_correspondence_dist: float = 0.5):
+        """``publish_scan_matching_status`` (:391-431) for the last ``matching()`` frame through the registration's ``matchingStatus`` (one device pass);
+        ``msf_delta`` is the prediction that frame was given.  The component publishes right after ``align`` (:268), before the keyframe decision; this reads
+        the registration as ``matching()`` left it, so for a frame that became the keyframe (``keyframes`` grew) the matching error and the inliers are
+        taken against the new keyframe.  The registration raises when no source has been set yet."""
+        if not hasattr(self.reg, "matchingStatus"):
+            raise NotImplementedError("the registration has no matchingStatus()")
+        return self.reg.matchingStatus(max_correspondence_dist, None if msf_delta is None else np.asarray(msf_delta, dtype=np.float32))
+
     def matching(self, stamp: float, cloud, msf_delta=None) -> np.ndarray:
         """Returns the odometry pose (float 4 x 4) of this frame."""
         if self.keyframe_cloud is None:  # :197-205

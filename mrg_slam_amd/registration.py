@@ -13,6 +13,7 @@ the C ABI's column-major layout here).
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -33,6 +34,29 @@ def _cloud(a) -> np.ndarray:
 
 def _colmajor(M) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(M, dtype=np.float32).T)
+
+
+@dataclass
+class MatchingStatus:
+    """The fields ``publish_scan_matching_status`` fills (apps/scan_matching_odometry_component.cpp:399-428); poses are 7-vectors,
+    position x y z then orientation x y z w.  ``prediction_error`` is None when no ``msf_delta`` was given."""
+
+    has_converged: bool
+    n_points: int
+    num_inliers: int
+    inlier_fraction: np.float32
+    matching_error: float
+    relative_pose: np.ndarray
+    prediction_error: np.ndarray | None
+
+
+def status_poses(final_transformation, msf_delta=None):
+    """``mrgfe_status_poses``: (relative_pose, prediction_error or None) of a row-major 4 x 4 final transformation; host arithmetic only."""
+    rel, err = np.zeros(7), np.zeros(7)
+    d = None if msf_delta is None else _colmajor(msf_delta)
+    check(lib().mrgfe_status_poses(_colmajor(final_transformation).ctypes.data_as(_fp), None if d is None else d.ctypes.data_as(_fp), rel.ctypes.data_as(_dp),
+                                   err.ctypes.data_as(_dp)))
+    return rel, (None if d is None else err)
 
 
 def default_params(method: int) -> RegParams:
@@ -130,6 +154,15 @@ class HipRegistration:
         sqd = np.empty(len(q), dtype=np.float32)
         check(lib().mrgfe_reg_nn1_target(self._h, q.ctypes.data_as(_fp), len(q), 16, idx.ctypes.data_as(_ip), sqd.ctypes.data_as(_fp)))
         return idx, sqd
+
+    def matchingStatus(self, max_correspondence_dist: float = 0.5, msf_delta=None) -> MatchingStatus:
+        """``publish_scan_matching_status`` (scan_matching_odometry_component.cpp:391-431) for the last ``align``: one fitness pass on the device and one
+        wait give the matching error, the inlier count and the poses; ``msf_delta`` (4 x 4) is the prediction the error is taken against."""
+        s = _lib.MatchingStatus()
+        d = None if msf_delta is None else _colmajor(msf_delta)
+        check(lib().mrgfe_reg_matching_status(self._h, float(max_correspondence_dist), None if d is None else d.ctypes.data_as(_fp), C.byref(s)))
+        return MatchingStatus(bool(s.has_converged), int(s.n_points), int(s.num_inliers), np.float32(s.inlier_fraction), float(s.matching_error),
+                              np.array(s.relative_pose, dtype=np.float64), np.array(s.prediction_error, dtype=np.float64) if s.has_prediction else None)
 
     def getFinalNumIteration(self) -> int:
         return lib().mrgfe_reg_iterations(self._h)
