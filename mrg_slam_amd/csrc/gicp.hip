@@ -1095,7 +1095,10 @@ int GicpEngine::covariances(int which, double* out9)
     if (!out9) return MRGFE_OK;  // (callers that only want the covariances, grid and buffers in place)
     const size_t n = which == 0 ? n_src_ : n_tgt_;
     std::vector<double> c6(n * 6);
-    if (n) MRGFE_HIP_CHECK(hipMemcpy(c6.data(), (which == 0 ? d_src_cov_ : d_tgt_cov_).p, n * 48, hipMemcpyDeviceToHost));
+    if (n) {  // on the engine's stream: it is non-blocking, so a copy on the null stream does not wait for the covariance kernels ensure_ready() just queued
+        MRGFE_HIP_CHECK(hipMemcpyAsync(c6.data(), (which == 0 ? d_src_cov_ : d_tgt_cov_).p, n * 48, hipMemcpyDeviceToHost, ctx_->stream));
+        MRGFE_HIP_CHECK(hipStreamSynchronize(ctx_->stream));
+    }
     for (size_t i = 0; i < n; ++i) {
         const double* c = &c6[i * 6];
         double* o = out9 + i * 9;
