@@ -387,6 +387,32 @@ int mrgfe_map_store_information_matrix(mrgfe_map_store* store, const mrgfe_inf_p
  * distance to one of the centres (sensor frame, <= 64) is < radius_sqr; kept / removed (may be NULL) keep the input order */
 int mrgfe_remove_points_near(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride_bytes, const float* centres_xyz, int n_centres, float radius_sqr,
                              float* kept_xyzi, size_t* n_kept, float* removed_xyzi, size_t* n_removed);
+/* ---- the keyframe callback in one call (MrgSlamComponent::cloud_callback, apps/mrg_slam_component.cpp:358-456, once KeyframeUpdater::update said yes) ---- */
+/* pcl::fromROSMsg (:372) -> the other-robot point removal (:396-430) -> the keyframe's cloud (:446) on the byte payload of a sensor_msgs/PointCloud2,
+ * with the kept cloud left in the map store as keyframe `key`: the payload goes up ONCE as it is, one kernel reads the records, stores the packed cloud
+ * and flags every point inside a sphere (the test of mrgfe_remove_points_near), a second one splits the cloud into kept and removed points in input
+ * order, and the kept cloud is where mrgfe_map_store_generate / _fitness / _information_matrix and the mrgfe_batch_*_from_store calls below read it.
+ * Kept and removed clouds and both counts equal, bit for bit and in order, mrgfe_ingest_pointcloud2 -> mrgfe_remove_points_near for the same inputs.
+ * The layout of the message, as for mrgfe_ingest_pointcloud2 / mrgfe_scan_params: */
+typedef struct mrgfe_keyframe_params {
+    uint32_t width, height, point_step, row_step;   /* row_step 0: width * point_step                                      */
+    uint32_t off_x, off_y, off_z;                   /* little-endian FLOAT32 fields; offsets multiples of 4 inside point_step */
+    int32_t  off_intensity;                         /* < 0: no such field, intensity 0                                     */
+} mrgfe_keyframe_params;
+/* height 1, the packed 16-byte layout (offsets 0/4/8/12); `width` is left 0 for the caller */
+void   mrgfe_keyframe_default_params(mrgfe_keyframe_params* out);
+size_t mrgfe_keyframe_params_size(void); /* sizeof(mrgfe_keyframe_params) as the library was compiled */
+/* `data`: data_bytes >= (height - 1) * row_step + width * point_step bytes of the message (less is MRGFE_ERR_INVALID); centres_xyz: n_centres <= 64
+ * positions in the sensor frame (NULL with n_centres 0: nothing is removed, the kernel is a plain gather into the store and nothing has to come down —
+ * the reference keeps the original message there, :396,436); kept_xyzi / removed_xyzi: room for width * height packed 16-byte points each, either may
+ * be NULL (not downloaded; the counts are still returned); n_removed may be NULL.  mrgfe_map_store_bytes grows by exactly 16 * *n_kept.
+ * The call returns only after the store's stream has been waited for (at most twice: the counts, then the downloads; once without centres), so the
+ * stored cloud is complete and immutable for every other stream.  MRGFE_ERR_INVALID: key 0, more than 64 centres, a bad layout, a short payload;
+ * MRGFE_ERR_STATE: `key` is already stored.  After any failure the store has no new entry and its byte count is unchanged. */
+int    mrgfe_keyframe_callback(mrgfe_map_store* store, uint64_t key, const mrgfe_keyframe_params* layout, const void* data, size_t data_bytes,
+                               const float* centres_xyz, int n_centres, float radius_sqr, float* kept_xyzi, size_t* n_kept, float* removed_xyzi,
+                               size_t* n_removed);
+
 /* replaces PrefilteringComponent::deskewing (apps/prefiltering_component.cpp:231-292): point i is rotated by the inverse of
  * Quaternionf(1, dt/2 * -w) with dt = scan_period * i / n and w the IMU angular velocity */
 int mrgfe_deskew(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride_bytes, const float ang_v_xyz[3], double scan_period, float* out_xyzi);
@@ -440,6 +466,17 @@ int  mrgfe_batch_add_pair_keyed(mrgfe_batch* b, int target_index, uint64_t cloud
 int  mrgfe_batch_has_cloud(const mrgfe_batch* b, uint64_t cloud_key, size_t* n);
 size_t mrgfe_batch_store_bytes(const mrgfe_batch* b);
 int  mrgfe_batch_forget(mrgfe_batch* b, uint64_t cloud_key);
+/* A target / a pair whose cloud is keyframe `key` of a map store (mrgfe_keyframe_callback, mrgfe_map_store_add) on the SAME device: the batch reads
+ * the store's memory — nothing is uploaded or copied, the keyframe lives in HBM once.  The store is append-only, so the pointer stays valid; like
+ * caller device memory handed to mrgfe_batch_add_*_device, the STORE MUST OUTLIVE the batch's use of it (destroy the batch, or clear it, first).
+ * The key is looked up and the store's stream waited for under the store's lock alone (mrgfe_map_store_add uploads asynchronously), which is released
+ * before the batch's lock is taken.  For the GICP methods the pair is entered in the batch's keyframe store under `key` with an empty cloud: its k-NN
+ * covariances are cached there as for mrgfe_batch_add_pair_keyed (mrgfe_batch_store_bytes counts the covariances only; mrgfe_batch_has_cloud does not
+ * report such an entry), and mrgfe_batch_forget / mrgfe_batch_clear treat it like a keyed pair.  Records are those of the same batch fed from host
+ * memory, bit for bit.  Return the target / pair index (>= 0) or an error (< 0): MRGFE_ERR_INVALID for a key the store does not hold or a store on
+ * another device.  mrgfe_node_* has no such form: its members sit on other devices than the store. */
+int  mrgfe_batch_add_target_from_store(mrgfe_batch* b, mrgfe_map_store* store, uint64_t key);
+int  mrgfe_batch_add_pair_from_store(mrgfe_batch* b, int target_index, mrgfe_map_store* store, uint64_t key, const float guess[16]);
 int  mrgfe_batch_set_guess(mrgfe_batch* b, int pair_index, const float guess[16]);
 /* build every target grid (setInputTarget), then align every pair; fitness_max_range < 0 skips getFitnessScore */
 int  mrgfe_batch_build_targets(mrgfe_batch* b);

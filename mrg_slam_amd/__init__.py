@@ -7,5 +7,6 @@ from .map_cloud import KeyFrameSnapshot, MapCloudGenerator, MapCloudStore, deske
 from .registration import BatchMatcher, GicpHip, IcpHip, NdtHip, NodeMatcher, PclGicpHip, PclNdtHip, SmallGicpHip, VgicpHip, select_registration_method  # noqa: F401
 from .loop_detector import KeyFrame, LoopDetector  # noqa: F401,E402
 from .odometry import ScanMatchingOdometry  # noqa: F401,E402
+from .keyframes import KeyframeCallback, KeyframeUpdater  # noqa: F401,E402
 from .prefiltering import PrefilteringComponent  # noqa: F401,E402
 from .floor_detection import FloorDetection, FloorDetectionComponent  # noqa: F401,E402

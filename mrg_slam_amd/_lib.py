@@ -53,6 +53,13 @@ class ScanParams(C.Structure):
                 ("T", C.c_float * 16), ("filters", PrefilterParams)]
 
 
+class KeyframeParams(C.Structure):
+    """struct mrgfe_keyframe_params: the layout of the sensor_msgs/PointCloud2 payload ``mrgfe_keyframe_callback`` reads."""
+
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("point_step", C.c_uint32), ("row_step", C.c_uint32), ("off_x", C.c_uint32), ("off_y", C.c_uint32),
+                ("off_z", C.c_uint32), ("off_intensity", C.c_int32)]
+
+
 class FloorParams(C.Structure):
     """struct mrgfe_floor_params (the floor_detection_component ROS parameters, apps/floor_detection_component.cpp:55-62, config/mrg_slam.yaml:113-122)."""
 
@@ -169,6 +176,9 @@ SIGNATURES = {
     "mrgfe_map_store_bytes": (C.c_size_t, [_vp]),
     "mrgfe_map_store_generate": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64), _dp, C.POINTER(C.c_uint8), C.c_float, C.c_int, C.c_float, C.c_int, _fp, C.c_size_t,
                                            C.POINTER(C.c_size_t)]),
+    "mrgfe_keyframe_default_params": (None, [C.POINTER(KeyframeParams)]),
+    "mrgfe_keyframe_params_size": (C.c_size_t, []),
+    "mrgfe_keyframe_callback": (C.c_int, [_vp, C.c_uint64, C.POINTER(KeyframeParams), _vp, C.c_size_t, _fp, C.c_int, C.c_float, _fp, _szp, _fp, _szp]),
     "mrgfe_prefilter_default_params": (None, [C.POINTER(PrefilterParams)]),
     "mrgfe_prefilter": (C.c_int, [_vp, C.POINTER(PrefilterParams), _fp, C.c_size_t, C.c_size_t, _fp, C.POINTER(C.c_size_t)]),
     "mrgfe_prefilter_device": (C.c_int, [_vp, C.POINTER(PrefilterParams), _fp, C.c_size_t, C.c_size_t, _vp, C.POINTER(C.c_size_t)]),
@@ -216,6 +226,8 @@ SIGNATURES = {
     "mrgfe_batch_has_cloud": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_size_t)]),
     "mrgfe_batch_store_bytes": (C.c_size_t, [_vp]),
     "mrgfe_batch_forget": (C.c_int, [_vp, C.c_uint64]),
+    "mrgfe_batch_add_target_from_store": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "mrgfe_batch_add_pair_from_store": (C.c_int, [_vp, C.c_int, _vp, C.c_uint64, _fp]),
     "mrgfe_batch_set_guess": (C.c_int, [_vp, C.c_int, _fp]),
     "mrgfe_batch_build_targets": (C.c_int, [_vp]),
     "mrgfe_batch_align": (C.c_int, [_vp, C.c_double, C.POINTER(PairResult)]),
@@ -331,6 +343,8 @@ def lib() -> C.CDLL:
                 f.restype, f.argtypes = res, args
         if hasattr(L, "mrgfe_matching_status_size") and L.mrgfe_matching_status_size() != C.sizeof(MatchingStatus):
             raise RuntimeError(f"libmrgfe.so was built with a mrgfe_matching_status of {L.mrgfe_matching_status_size()} bytes, the binding mirrors {C.sizeof(MatchingStatus)}")
+        if hasattr(L, "mrgfe_keyframe_params_size") and L.mrgfe_keyframe_params_size() != C.sizeof(KeyframeParams):
+            raise RuntimeError(f"libmrgfe.so was built with a mrgfe_keyframe_params of {L.mrgfe_keyframe_params_size()} bytes, the binding mirrors {C.sizeof(KeyframeParams)}")
         _lib = L
     return _lib
 

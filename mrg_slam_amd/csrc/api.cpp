@@ -30,6 +30,7 @@
 #include "ndt_derivatives.h"
 #include "ndt_engine.h"
 #include "nn_grid.h"
+#include "scan_point.h"
 #include "fit_select.h"
 
 using namespace mrgfe;
@@ -1129,6 +1130,75 @@ int mrgfe_map_store_information_matrix(mrgfe_map_store* s, const mrgfe_inf_param
     return mrgfe_inf_matrix_from_fitness(p, fit, inf);
 }
 
+// ---- the keyframe callback: PointCloud2 bytes -> keyframe `key` of the store (MrgSlamComponent::cloud_callback :372-446 in one call) ----------------
+static_assert(sizeof(mrgfe_keyframe_params) == 32, "mrgfe_keyframe_params: the layout the bindings mirror");
+size_t mrgfe_keyframe_params_size(void) { return sizeof(mrgfe_keyframe_params); }
+void mrgfe_keyframe_default_params(mrgfe_keyframe_params* p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->height = 1;  // (width: the caller's point count)
+    p->point_step = 16;  // the replay scripts' layout: python_scripts/kitti_singlerobot_processor.py:164-185
+    p->off_x = 0; p->off_y = 4; p->off_z = 8; p->off_intensity = 12;
+}
+int mrgfe_keyframe_callback(mrgfe_map_store* s, uint64_t key, const mrgfe_keyframe_params* lay, const void* data, size_t data_bytes, const float* centres, int n_centres,
+                            float radius_sqr, float* kept, size_t* n_kept, float* removed, size_t* n_removed)
+{
+    static const char* fn = "mrgfe_keyframe_callback";
+    return abi_guard(fn, [&]() -> int {
+        if (!s || !lay || !n_kept) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        *n_kept = 0;
+        if (n_removed) *n_removed = 0;
+        if (key == 0) { set_error("%s: key 0", fn); return MRGFE_ERR_INVALID; }
+        if (n_centres < 0 || n_centres > kMaxCentres || (n_centres > 0 && !centres)) { set_error("%s: %d centres (0 to %d, and their positions)", fn, n_centres, kMaxCentres); return MRGFE_ERR_INVALID; }
+        KeyframeLayout l{lay->width, lay->height, lay->point_step, lay->row_step, lay->off_x, lay->off_y, lay->off_z, lay->off_intensity};
+        MRGFE_TRY(check_pointcloud2_layout(fn, l.width, l.height, l.point_step, &l.row_step, l.off_x, l.off_y, l.off_z, l.off_intensity));
+        const size_t n = size_t(l.width) * l.height;
+        const size_t raw_bytes = n ? size_t(l.height - 1) * l.row_step + size_t(l.width) * l.point_step : 0;
+        if (n && !data) { set_error("%s: NULL data", fn); return MRGFE_ERR_INVALID; }
+        if (data_bytes < raw_bytes) { set_error("%s: the payload has %zu bytes, the layout needs %zu", fn, data_bytes, raw_bytes); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(s->ctx);
+        MRGFE_TRY(s->ctx->bind());
+        if (s->clouds.count(key)) { set_error("%s: keyframe %llu is already stored", fn, static_cast<unsigned long long>(key)); return MRGFE_ERR_STATE; }
+        size_t nk = 0, nr = 0;
+        void*  p = nullptr;
+        if (n) {
+            mrgfe_ctx* ctx = s->ctx;
+            MRGFE_TRY(s->arena.alloc(n * 16, &p));  // room for every point; what the removal does not keep is handed back below
+            DevBuf& drem = ctx->scratch[2];
+            auto run = [&]() -> int {
+                const void* d_raw = nullptr;
+                MRGFE_TRY(upload_raw_records(ctx, data, raw_bytes, &d_raw));
+                if (n_centres == 0) {
+                    MRGFE_TRY(keyframe_gather_device(ctx, d_raw, l, static_cast<float4*>(p)));
+                    nk = n;
+                } else {
+                    if (removed) MRGFE_TRY(drem.ensure(n * 16));
+                    MRGFE_TRY(keyframe_split_device(ctx, d_raw, l, centres, n_centres, radius_sqr, static_cast<float4*>(p), &nk, removed ? drem.as<float4>() : nullptr, &nr));  // (the first wait)
+                    if (!((kept && nk) || (removed && nr))) return MRGFE_OK;  // nothing to bring down: the stream is idle
+                }
+                if (kept && nk) MRGFE_HIP_CHECK(hipMemcpyAsync(kept, p, nk * 16, hipMemcpyDeviceToHost, ctx->stream));
+                if (removed && nr) MRGFE_HIP_CHECK(hipMemcpyAsync(removed, drem.p, nr * 16, hipMemcpyDeviceToHost, ctx->stream));
+                MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // without centres the only wait, else the second
+                return MRGFE_OK;
+            };
+            const int rc = run();
+            if (rc != MRGFE_OK) {
+                (void)hipStreamSynchronize(ctx->stream);  // nothing is in flight when the room goes back
+                s->arena.shrink_last(p, n * 16, 0);
+                return rc;
+            }
+            s->arena.shrink_last(p, n * 16, nk * 16);
+            if (nk == 0) p = nullptr;
+        }
+        s->clouds[key] = {static_cast<const float4*>(p), static_cast<uint32_t>(nk)};
+        s->bytes += nk * 16;
+        *n_kept = nk;
+        if (n_removed) *n_removed = nr;
+        return MRGFE_OK;
+    });
+}
+
 int mrgfe_remove_points_near(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, const float* centres, int n_centres, float radius_sqr, float* kept, size_t* n_kept,
                              float* removed, size_t* n_removed)
 {
@@ -1393,7 +1463,7 @@ int mrgfe_batch_add_pair_keyed(mrgfe_batch* b, int target, uint64_t key, const f
         if (n > 0x7fffffffu) { set_error("cloud too large"); return MRGFE_ERR_INVALID; }
         mrgfe_batch::Keyframe* kf = nullptr;
         auto it = b->store.find(key);
-        if (it != b->store.end() && it->second->n == n) {
+        if (it != b->store.end() && it->second->n == n && it->second->cloud.p) {  // (an entry of mrgfe_batch_add_pair_from_store holds covariances and no cloud)
             kf = it->second.get();
         } else {
             if (n && !xyzi) { set_error("mrgfe_batch_add_pair_keyed: key %llu is not in the store (or has another size) and no cloud was given", static_cast<unsigned long long>(key)); return MRGFE_ERR_INVALID; }
@@ -1427,7 +1497,7 @@ int mrgfe_batch_has_cloud(const mrgfe_batch* b, uint64_t key, size_t* n)
     if (!b || key == 0) return 0;
     MRGFE_LOCK(b->ctx);
     auto it = b->store.find(key);
-    if (it == b->store.end()) return 0;
+    if (it == b->store.end() || !it->second->cloud.p) return 0;  // (no cloud: an entry of mrgfe_batch_add_pair_from_store)
     if (n) *n = it->second->n;
     return 1;
 }
@@ -1450,6 +1520,72 @@ int mrgfe_batch_forget(mrgfe_batch* b, uint64_t key)
         it = b->store.erase(it);
     }
     return MRGFE_OK;
+}
+// Keyframe `key` of a map store for a batch on the same device: looked up, and the store's stream waited for (mrgfe_map_store_add uploads asynchronously), under
+// the store's lock ALONE — it is released before the caller takes the batch's lock, so no thread ever holds both context locks.
+static int store_lookup(const char* fn, const mrgfe_batch* b, mrgfe_map_store* s, uint64_t key, const float4** p, size_t* n)
+{
+    if (s->ctx->device != b->ctx->device) { set_error("%s: the store is on device %d, the batch on device %d", fn, s->ctx->device, b->ctx->device); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(s->ctx);
+    MRGFE_TRY(s->ctx->bind());
+    auto it = s->clouds.find(key);
+    if (it == s->clouds.end()) { set_error("%s: keyframe %llu is not in the store", fn, static_cast<unsigned long long>(key)); return MRGFE_ERR_INVALID; }
+    MRGFE_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
+    *p = it->second.p;
+    *n = it->second.n;
+    return MRGFE_OK;
+}
+int mrgfe_batch_add_target_from_store(mrgfe_batch* b, mrgfe_map_store* s, uint64_t key)
+{
+    static const char* fn = "mrgfe_batch_add_target_from_store";
+    return abi_guard(fn, [&]() -> int {
+        if (!b || !s) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        const float4* p = nullptr;
+        size_t n = 0;
+        MRGFE_TRY(store_lookup(fn, b, s, key, &p, &n));
+        MRGFE_LOCK(b->ctx);
+        return b->ndt->add_target_device(p, n);
+    });
+}
+int mrgfe_batch_add_pair_from_store(mrgfe_batch* b, int target, mrgfe_map_store* s, uint64_t key, const float guess[16])
+{
+    static const char* fn = "mrgfe_batch_add_pair_from_store";
+    return abi_guard(fn, [&]() -> int {
+        if (!b || !s || !guess) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        const float4* p = nullptr;
+        size_t n = 0;
+        MRGFE_TRY(store_lookup(fn, b, s, key, &p, &n));
+        MRGFE_LOCK(b->ctx);
+        MRGFE_TRY(b->ctx->bind());
+        if (target < 0 || target >= b->ndt->n_targets()) { set_error("%s: target index %d out of range", fn, target); return MRGFE_ERR_INVALID; }
+        mrgfe_batch::Keyframe* kf = nullptr;
+        if (!is_ndt(b->params.method)) {  // the covariances of the keyframe are cached under its key, next to no cloud (the store has it)
+            auto it = b->store.find(key);
+            if (it != b->store.end() && it->second->n != n) {
+                if (it->second->last_epoch == b->epoch) { set_error("%s: key %llu is already used in this batch with %u points", fn, static_cast<unsigned long long>(key), it->second->n); return MRGFE_ERR_INVALID; }
+                b->store.erase(it);
+                it = b->store.end();
+            }
+            if (it == b->store.end()) {
+                store_make_room(b, n * 48);
+                std::unique_ptr<mrgfe_batch::Keyframe> fresh(new (std::nothrow) mrgfe_batch::Keyframe());
+                if (!fresh) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+                fresh->n = static_cast<uint32_t>(n);
+                it = b->store.emplace(key, std::move(fresh)).first;
+            }
+            kf = it->second.get();
+        }
+        float g[16];
+        col2row(guess, g);
+        const int pair = b->ndt->add_pair_device(target, p, n, g);
+        if (pair >= 0 && kf) {
+            kf->last_epoch = b->epoch;
+            kf->last_tick = ++b->tick;
+            if (b->pair_key.size() <= static_cast<size_t>(pair)) b->pair_key.resize(pair + 1, 0);
+            b->pair_key[pair] = key;
+        }
+        return pair;
+    });
 }
 int mrgfe_batch_set_guess(mrgfe_batch* b, int pair, const float guess[16])
 {

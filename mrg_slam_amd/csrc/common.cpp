@@ -182,6 +182,18 @@ int Arena::alloc(size_t bytes, void** out)
     chunks.push_back(c);
     return MRGFE_OK;
 }
+void Arena::shrink_last(void* p, size_t bytes, size_t keep)
+{
+    bytes = (bytes + 255) & ~size_t(255);
+    if (bytes == 0) bytes = 256;
+    keep = (keep + 255) & ~size_t(255);
+    if (keep >= bytes) return;
+    for (auto& c : chunks)
+        if (static_cast<char*>(p) + bytes == static_cast<char*>(c.p) + c.used && p >= c.p) {  // (nothing was allocated behind it)
+            c.used -= bytes - keep;
+            return;
+        }
+}
 void Arena::reset()
 {
     for (auto& c : chunks) c.used = 0;

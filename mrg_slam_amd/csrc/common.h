@@ -149,6 +149,7 @@ struct Arena {
     Arena& operator=(Arena&& o) noexcept { if (this != &o) { release(); chunks = std::move(o.chunks); chunk_bytes = o.chunk_bytes; o.chunks.clear(); } return *this; }
     ~Arena() { release(); }
     int  alloc(size_t bytes, void** out);
+    void shrink_last(void* p, size_t bytes, size_t keep);  // `p` = the LATEST alloc(bytes) of its chunk: give back all but its first `keep` bytes (0: all of it)
     void reset();    // keep chunks, forget allocations
     void release();  // free chunks
 };

@@ -17,6 +17,16 @@ int map_cloud_device(mrgfe_ctx* ctx, const float4* d_cat, const uint32_t* kf_off
 int remove_points_near_device(mrgfe_ctx* ctx, const float4* d_in, size_t n, const float* centres_xyz, int n_centres, float radius_sqr, float4* d_kept, size_t* n_kept,
                               float4* d_removed, size_t* n_removed);
 
+// The point work of MrgSlamComponent::cloud_callback (apps/mrg_slam_component.cpp:372, 396-430) on the wire records of a PointCloud2 already on
+// the device (ingest.h upload_raw_records; the layout was checked by check_pointcloud2_layout).
+struct KeyframeLayout { uint32_t width, height, point_step, row_step, off_x, off_y, off_z; int32_t off_intensity; };
+// no other robot: the records are gathered straight into d_cloud (width * height packed points); one launch, no wait
+int keyframe_gather_device(mrgfe_ctx* ctx, const void* d_raw, const KeyframeLayout& lay, float4* d_cloud);
+// with centres (1 <= n_centres <= 64): two launches — records -> packed cloud + keep flags + tile counts, then the stable two-way partition into
+// d_kept / d_removed (room for width * height points each; d_removed may be nullptr) — and ONE wait for the two totals
+int keyframe_split_device(mrgfe_ctx* ctx, const void* d_raw, const KeyframeLayout& lay, const float* centres_xyz, int n_centres, float radius_sqr, float4* d_kept,
+                          size_t* n_kept, float4* d_removed, size_t* n_removed);
+
 // PrefilteringComponent::deskewing (apps/prefiltering_component.cpp:231-292)
 int deskew_device(mrgfe_ctx* ctx, const float4* d_in, size_t n, const float ang_v[3], double scan_period, float4* d_out);
 // pcl::transformPointCloud(in, out, Matrix4f): the float arithmetic of dev_float.h's transform_point, intensity copied

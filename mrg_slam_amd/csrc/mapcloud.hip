@@ -3,6 +3,7 @@
 //   MapCloudGenerator::generate         /root/reference/src/mrg_slam/map_cloud_generator.cpp:14-86
 //   pcl::ApproximateMeanVoxelGrid       /root/reference/include/pcl/filters/ApproximateMeanVoxelGrid.hpp:63-126
 //   other-robot point removal           /root/reference/apps/mrg_slam_component.cpp:396-429
+//   the keyframe callback's point work  apps/mrg_slam_component.cpp:372,396-430 (wire records -> kept / removed clouds)
 //   PrefilteringComponent::deskewing    /root/reference/apps/prefiltering_component.cpp:231-292
 // Float expressions run in the order documented in oracle/mapcloud.cpp (left to right, no FMA).
 #include "mapcloud.h"
@@ -252,23 +253,13 @@ int map_cloud_device(mrgfe_ctx* ctx, const float4* d_cat, const uint32_t* kf_off
 }
 
 // ---- other-robot point removal -----------------------------------------------------------------------------------
-constexpr int kMaxCentres = 64;
-struct Centres { float xyz[kMaxCentres][3]; };
-
+// (the sphere test itself: scan_point.h near_a_centre, shared with the keyframe head kernel below)
 __global__ __launch_bounds__(256) void near_flags_kernel(const float4* __restrict__ in, uint32_t n, Centres c, int K, float radius_sqr, uint32_t* __restrict__ keep,
                                                           uint32_t* __restrict__ drop)
 {
-#pragma clang fp contract(off)
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const float4 p = in[i];
-    uint32_t gone = 0u;
-    for (int k = 0; k < K; ++k) {
-        const float dx = p.x - c.xyz[k][0], dy = p.y - c.xyz[k][1], dz = p.z - c.xyz[k][2];
-        float s = dx * dx + dy * dy;  // (point - other).squaredNorm()
-        s = s + dz * dz;
-        if (s < radius_sqr) { gone = 1u; break; }  // mrg_slam_component.cpp:413
-    }
+    const uint32_t gone = near_a_centre(in[i], c, K, radius_sqr);  // mrg_slam_component.cpp:413
     keep[i] = gone ^ 1u;
     drop[i] = gone;
 }
@@ -293,6 +284,161 @@ int remove_points_near_device(mrgfe_ctx* ctx, const float4* d_in, size_t n, cons
     if (d_removed) MRGFE_TRY(compact_by_flags(ctx, d_in, nn, dd.as<uint32_t>(), d_removed, &gone));
     *n_kept = kept;
     if (n_removed) *n_removed = d_removed ? gone : nn - kept;
+    return MRGFE_OK;
+}
+
+// ---- the keyframe callback: wire records -> kept / removed clouds (apps/mrg_slam_component.cpp:372, 396-430) ----------------------
+// The head: pcl::fromROSMsg and the other-robot test in one pass over the wire records.  Per point: the strided record is read (scan_point.h
+// load_point_record, the body of gather_points_kernel) and stored as the packed float4; with kCentres the point is held against the spheres
+// (near_a_centre, the body of near_flags_kernel), its keep flag is written and the tile's kept count is left for the partition.  Same tile shape
+// as scan_head_kernel / pf_distance_tiles_kernel: one workgroup per 2048 points.  The switch is compile-time: without centres the kernel is a plain
+// gather (no flags, no counts, no centre table in registers) that writes straight into the store's buffer.
+struct KeyframeHeadArgs {
+    const uint8_t* raw;
+    float4*        out;
+    uint32_t       n, width, row_step, point_step, ox, oy, oz;
+    int32_t        oi;
+    uint32_t*      flags;  // kCentres: 1 = kept
+    uint32_t*      blk;    // kCentres: kept points per tile
+    int            K;
+    float          radius_sqr;
+};
+template <bool kCentres>
+__global__ __launch_bounds__(256) void keyframe_head_kernel(const KeyframeHeadArgs a, const Centres c)
+{
+    const uint32_t base = blockIdx.x * kTile;
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int k = 0; k < kTile / 256; ++k) {
+        const uint32_t i = base + k * 256 + threadIdx.x;
+        if (i < a.n) {
+            const float4 p = load_point_record(a.raw, i, a.width, a.row_step, a.point_step, a.ox, a.oy, a.oz, a.oi);
+            a.out[i] = p;
+            if (kCentres) {
+                const uint32_t f = near_a_centre(p, c, a.K, a.radius_sqr) ^ 1u;
+                a.flags[i] = f;
+                cnt += f;
+            }
+        }
+    }
+    if (!kCentres) return;
+    __shared__ uint32_t sw[4];
+    cnt = wave_sum(cnt);
+    if (lane_id() == 0) sw[wave_id()] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) a.blk[blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
+}
+// Stable two-way partition in ONE launch behind the tile counts (pf_compact_kernel's scheme, filters.hip): a workgroup adds up the counts of the tiles
+// before its own (and of all tiles) itself and ranks its tile's kept points by wave ballots; point i with `rank` kept points before it goes to
+// kept[rank] when its flag is set and to removed[i - rank] otherwise, so both outputs are in input order.  Workgroup 0 leaves both totals for the host.
+// On this route it stands for near_flags_kernel, two exclusive scans and two scatters.  Launched with ceil(n / 2048) workgroups, n > 0.
+__global__ __launch_bounds__(256) void keyframe_partition_kernel(const float4* __restrict__ in, const uint32_t* __restrict__ flags, const uint32_t* __restrict__ blk, uint32_t n,
+                                                                  float4* __restrict__ kept, float4* __restrict__ removed /* nullable */, uint32_t* __restrict__ totals)
+{
+    const uint32_t nblk = (n + kTile - 1) / kTile;
+    __shared__ uint32_t s_red[2][4];
+    __shared__ uint32_t s_cnt[kTile / 256][4], s_off[kTile / 256][4];
+    uint32_t before = 0, total = 0;
+    for (uint32_t b = threadIdx.x; b < nblk; b += 256) {
+        const uint32_t v = blk[b];
+        total += v;
+        before += b < blockIdx.x ? v : 0u;
+    }
+    before = wave_sum(before);
+    total = wave_sum(total);
+    const int lane = lane_id(), w = wave_id();
+    if (lane == 0) { s_red[0][w] = before; s_red[1][w] = total; }
+    __syncthreads();
+    before = s_red[0][0] + s_red[0][1] + s_red[0][2] + s_red[0][3];
+    total = s_red[1][0] + s_red[1][1] + s_red[1][2] + s_red[1][3];
+    if (blockIdx.x == 0 && threadIdx.x == 0) { totals[0] = total; totals[1] = n - total; }
+    // kept points before point i = kept points of earlier tiles + of earlier rounds and wavefronts of the tile + kept lanes below its own
+    const uint32_t base = blockIdx.x * kTile;
+    uint32_t f[kTile / 256], lr[kTile / 256];
+#pragma unroll
+    for (int k = 0; k < kTile / 256; ++k) {
+        const uint32_t i = base + k * 256 + threadIdx.x;
+        f[k] = i < n ? flags[i] : 0u;
+        const uint64_t m = __ballot(f[k] != 0u);
+        lr[k] = static_cast<uint32_t>(__popcll(m & ((1ull << lane) - 1ull)));
+        if (lane == 0) s_cnt[k][w] = static_cast<uint32_t>(__popcll(m));
+    }
+    __syncthreads();
+    if (threadIdx.x < (kTile / 256) * 4) {  // 32 lanes of wavefront 0: exclusive prefix in (round, wavefront) order
+        const uint32_t v = s_cnt[threadIdx.x / 4][threadIdx.x % 4];
+        uint32_t incl = v;
+#pragma unroll
+        for (int off = 1; off < (kTile / 256) * 4; off <<= 1) {
+            const uint32_t t = __shfl_up(incl, off, kWave);
+            if (lane >= off) incl += t;
+        }
+        s_off[threadIdx.x / 4][threadIdx.x % 4] = incl - v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kTile / 256; ++k) {
+        const uint32_t i = base + k * 256 + threadIdx.x;
+        if (i >= n) continue;
+        const uint32_t rank = before + s_off[k][w] + lr[k];  // <= i, and < total when the point is kept
+        if (f[k]) kept[rank] = in[i];
+        else if (removed) removed[i - rank] = in[i];
+    }
+}
+
+static KeyframeHeadArgs keyframe_head_args(const void* d_raw, const KeyframeLayout& lay, float4* d_out)
+{
+    KeyframeHeadArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.raw = static_cast<const uint8_t*>(d_raw);
+    a.out = d_out;
+    a.n = lay.width * lay.height;
+    a.width = lay.width; a.row_step = lay.row_step; a.point_step = lay.point_step;
+    a.ox = lay.off_x; a.oy = lay.off_y; a.oz = lay.off_z; a.oi = lay.off_intensity;
+    return a;
+}
+
+int keyframe_gather_device(mrgfe_ctx* ctx, const void* d_raw, const KeyframeLayout& lay, float4* d_cloud)
+{
+    const KeyframeHeadArgs a = keyframe_head_args(d_raw, lay, d_cloud);
+    if (a.n == 0) return MRGFE_OK;
+    hipLaunchKernelGGL(keyframe_head_kernel<false>, dim3((a.n + kTile - 1) / kTile), dim3(256), 0, ctx->stream, a, Centres{});
+    MRGFE_HIP_CHECK(hipGetLastError());
+    return MRGFE_OK;
+}
+
+int keyframe_split_device(mrgfe_ctx* ctx, const void* d_raw, const KeyframeLayout& lay, const float* centres, int K, float radius_sqr, float4* d_kept, size_t* n_kept,
+                          float4* d_removed, size_t* n_removed)
+{
+    *n_kept = 0;
+    *n_removed = 0;
+    if (K < 1 || K > kMaxCentres) { set_error("keyframe callback: 1 to %d centres", kMaxCentres); return MRGFE_ERR_INVALID; }
+    DevBuf &dcloud = ctx->scratch[0], &dfl = ctx->scratch[1];
+    KeyframeHeadArgs a = keyframe_head_args(d_raw, lay, nullptr);
+    if (a.n == 0) return MRGFE_OK;
+    const uint32_t nblk = (a.n + kTile - 1) / kTile;
+    MRGFE_TRY(dcloud.ensure(size_t(a.n) * 16));
+    MRGFE_TRY(dfl.ensure(sizeof(uint32_t) * (size_t(a.n) + nblk + 2)));  // flags, tile counts, the two totals
+    PinBuf& hp = ctx->pin[1];
+    MRGFE_TRY(hp.ensure(2 * sizeof(uint32_t)));
+    a.out = dcloud.as<float4>();
+    a.flags = dfl.as<uint32_t>();
+    a.blk = a.flags + a.n;
+    a.K = K;
+    a.radius_sqr = radius_sqr;
+    uint32_t* d_tot = a.blk + nblk;
+    Centres c{};
+    for (int k = 0; k < K; ++k) for (int x = 0; x < 3; ++x) c.xyz[k][x] = centres[3 * k + x];
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(keyframe_head_kernel<true>, dim3(nblk), dim3(256), 0, st, a, c);
+    MRGFE_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(keyframe_partition_kernel, dim3(nblk), dim3(256), 0, st, a.out, a.flags, a.blk, a.n, d_kept, d_removed, d_tot);
+    MRGFE_HIP_CHECK(hipGetLastError());
+    uint32_t* h_tot = hp.as<uint32_t>();
+    MRGFE_HIP_CHECK(hipMemcpyAsync(h_tot, d_tot, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    MRGFE_HIP_CHECK(hipStreamSynchronize(st));
+    if (size_t(h_tot[0]) + h_tot[1] != a.n) { set_error("keyframe callback: the partition reported %u + %u of %u points", h_tot[0], h_tot[1], a.n); return MRGFE_ERR_HIP; }
+    *n_kept = h_tot[0];
+    *n_removed = h_tot[1];
     return MRGFE_OK;
 }
 

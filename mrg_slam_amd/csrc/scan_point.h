@@ -1,6 +1,7 @@
 // csrc/scan_point.h — the per-point work of PrefilteringComponent::cloud_callback before its filters (apps/prefiltering_component.cpp:119-146),
 // shared by the standalone kernels (ingest.hip: gather_points_kernel; mapcloud.hip: deskew_kernel, transform_cloud_kernel) and the scan head kernel
-// (filters.hip): ONE body each, so the fused call cannot round differently from the separate calls.
+// (filters.hip): ONE body each, so the fused call cannot round differently from the separate calls.  Likewise the other-robot test of
+// MrgSlamComponent::cloud_callback (apps/mrg_slam_component.cpp:412-423), shared by near_flags_kernel and the keyframe head kernel (mapcloud.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,6 +53,23 @@ __device__ __forceinline__ float4 transform_finite_point(const float* __restrict
         p.x = x; p.y = y; p.z = z;
     }
     return p;
+}
+
+// The other-robot test of MrgSlamComponent::cloud_callback for one point (apps/mrg_slam_component.cpp:412-423): 1 when the point lies inside the sphere of
+// one of the K centres (sensor frame) — (point - centre).squaredNorm() < radius_sqr in float, unfused, the first hit ends the loop.  A non-finite point
+// compares false against every centre and is kept.  The centres travel by value in the kernel's arguments.
+constexpr int kMaxCentres = 64;
+struct Centres { float xyz[kMaxCentres][3]; };
+__device__ __forceinline__ uint32_t near_a_centre(float4 p, const Centres& c, int K, float radius_sqr)
+{
+#pragma clang fp contract(off)
+    for (int k = 0; k < K; ++k) {
+        const float dx = p.x - c.xyz[k][0], dy = p.y - c.xyz[k][1], dz = p.z - c.xyz[k][2];
+        float s = dx * dx + dy * dy;  // (point - other).squaredNorm()
+        s = s + dz * dz;
+        if (s < radius_sqr) return 1u;  // :417-421
+    }
+    return 0u;
 }
 
 }  // namespace mrgfe

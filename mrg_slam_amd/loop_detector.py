@@ -171,9 +171,12 @@ def angular_distance_to_identity(R) -> float:
 
 
 class LoopDetector:
-    def __init__(self, params: dict | None = None, registration=None, matcher=None):
+    def __init__(self, params: dict | None = None, registration=None, matcher=None, store=None):
         if (registration is None) == (matcher is None):
             raise ValueError("give either a registration object (the reference's sequential loop) or a BatchMatcher (all candidates at once)")
+        if store is not None and matcher is None:
+            raise ValueError("store= names keyframes for a BatchMatcher (matcher=)")
+        self.store = store  # a MapCloudStore: keyframes whose store_key() it holds are queued by key and read where they are (no upload, no second copy)
         self.p = dict(DEFAULTS)
         self.p.update(params or {})
         self.registration, self.matcher = registration, matcher
@@ -225,13 +228,8 @@ class LoopDetector:
             tid = {}
             for k, kf in pairs:
                 if k not in tid:
-                    tid[k] = bm.add_target(new_keyframes[k].cloud)  # registration_->setInputTarget(new_keyframe->cloud), :104
-                key = kf.store_key()
-                old = kf.retired_store_key()
-                if old is not None and old != key:
-                    bm.forget(old)
-                have = bm.has_cloud(key) == len(kf.cloud)
-                bm.add_pair(tid[k], None if have else kf.cloud, self._guess(new_est[k], kf), key=key)
+                    tid[k] = self._queue_target(new_keyframes[k])  # registration_->setInputTarget(new_keyframe->cloud), :104
+                self._queue_pair(tid[k], kf, self._guess(new_est[k], kf))
             self.alignments += len(pairs)
 
         # ---- batch 1: every (new keyframe, superset candidate) pair, aligned and scored
@@ -355,6 +353,27 @@ class LoopDetector:
             g[2, 3] = 0.0
         return g
 
+    # ---- queueing on the BatchMatcher: by key out of the shared store where the keyframe is there, from host memory otherwise
+    def _in_store(self, kf: KeyFrame, key: int) -> bool:
+        return self.store is not None and self.store.has(key) == len(kf.cloud)
+
+    def _queue_target(self, new_keyframe: KeyFrame) -> int:
+        key = new_keyframe.store_key()
+        if self._in_store(new_keyframe, key):
+            return self.matcher.add_target_from_store(self.store, key)
+        return self.matcher.add_target(new_keyframe.cloud)
+
+    def _queue_pair(self, target: int, kf: KeyFrame, guess) -> int:
+        bm = self.matcher
+        key = kf.store_key()  # (slam_uuid, id, content): an equal-length replacement or another robot's same id is another entry
+        old = kf.retired_store_key()
+        if old is not None and old != key:
+            bm.forget(old)  # the replaced cloud's resident copy (the batch was just cleared: nothing references it)
+        if self._in_store(kf, key):
+            return bm.add_pair_from_store(target, self.store, key, guess)
+        have = bm.has_cloud(key) == len(kf.cloud)
+        return bm.add_pair(target, None if have else kf.cloud, guess, key=key)
+
     # ---- the alignments: (final transformation, converged, fitness) per source against the new keyframe's cloud
     def _align_all(self, new_keyframe: KeyFrame, sources, guesses, want_fitness: bool):
         self.alignments += len(sources)
@@ -371,14 +390,9 @@ class LoopDetector:
 
         bm = self.matcher
         bm.clear()
-        t = bm.add_target(new_keyframe.cloud)
+        t = self._queue_target(new_keyframe)
         for kf, g in zip(sources, guesses):
-            key = kf.store_key()  # (slam_uuid, id, content): an equal-length replacement or another robot's same id is another entry
-            old = kf.retired_store_key()
-            if old is not None and old != key:
-                bm.forget(old)  # the replaced cloud's resident copy (the batch was just cleared: nothing references it)
-            have = bm.has_cloud(key) == len(kf.cloud)
-            bm.add_pair(t, None if have else kf.cloud, g, key=key)
+            self._queue_pair(t, kf, g)
         res = bm.align(max_range if want_fitness else -1.0)
         return [(result_matrix(r), bool(r["converged"]), float(r["fitness"]) if want_fitness else None) for r in res]
 

@@ -13,8 +13,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import Context, MrgfeError, check, default_context, lib
+from ._lib import Context, KeyframeParams, MrgfeError, check, default_context, lib
 from .filters import _cloud
+from .io import pointcloud2_from_xyzi
 
 _fp = C.POINTER(C.c_float)
 ERR_EMPTY = -4  # MRGFE_ERR_EMPTY (include/mrgfe.h)
@@ -27,6 +28,17 @@ class KeyFrameSnapshot:
     pose: np.ndarray  # 4 x 4, Eigen::Isometry3d
     cloud: np.ndarray  # N x 4 float32 (x, y, z, intensity)
     first_keyframe: bool = False
+
+
+def keyframe_params(msg: dict) -> KeyframeParams:
+    """struct mrgfe_keyframe_params of a PointCloud2 given as a dict (``width``, ``height``, ``point_step``, ``fields``, optionally ``row_step``)."""
+    p = KeyframeParams()
+    lib().mrgfe_keyframe_default_params(C.byref(p))
+    f = msg["fields"]
+    p.width, p.height, p.point_step, p.row_step = int(msg["width"]), int(msg.get("height", 1)), int(msg["point_step"]), int(msg.get("row_step", 0) or 0)
+    p.off_x, p.off_y, p.off_z = int(f["x"]), int(f["y"]), int(f["z"])
+    p.off_intensity = int(f["intensity"]) if f.get("intensity") is not None else -1
+    return p
 
 
 class MapCloudStore:
@@ -55,6 +67,28 @@ class MapCloudStore:
     def add(self, key: int, cloud) -> None:
         c = _cloud(cloud)
         check(lib().mrgfe_map_store_add(self._h, key, c.ctypes.data_as(_fp), len(c), 16))
+
+    def keyframe_callback(self, key: int, payload_or_msg, centres_sensor=None, radius: float = 2.0, want_kept: bool = True, want_removed: bool = True):
+        """``mrgfe_keyframe_callback``: the point work of MrgSlamComponent::cloud_callback (apps/mrg_slam_component.cpp:372, 396-430) on a
+        sensor_msgs/PointCloud2 — a dict with ``data``, ``width``, ``height``, ``point_step``, ``fields`` (name -> byte offset) and optionally
+        ``row_step``, or a packed [n, 4] float32 cloud — in one call: the payload goes up once, every point closer than ``radius`` to one of
+        ``centres_sensor`` (K x 3, sensor frame, K <= 64; robot_radius_sqr is float(radius * radius), :406-407) is split off, and the kept cloud
+        becomes keyframe ``key`` of this store.  Returns ``(kept, removed)``; an output that is not wanted is None and is not downloaded."""
+        msg = payload_or_msg if isinstance(payload_or_msg, dict) else pointcloud2_from_xyzi(payload_or_msg)
+        p = keyframe_params(msg)
+        n = int(p.width) * int(p.height)
+        buf = np.frombuffer(msg["data"], dtype=np.uint8) if n else np.zeros(0, dtype=np.uint8)
+        ctr = np.ascontiguousarray(np.asarray(centres_sensor if centres_sensor is not None else np.zeros((0, 3)), dtype=np.float32).reshape(-1, 3))
+        kept = np.empty((n, 4), dtype=np.float32) if want_kept else None
+        removed = np.empty((n, 4), dtype=np.float32) if want_removed and len(ctr) else None
+        nk, nr = C.c_size_t(0), C.c_size_t(0)
+        check(lib().mrgfe_keyframe_callback(self._h, int(key), C.byref(p), buf.ctypes.data_as(C.c_void_p) if n else None, buf.nbytes,
+                                            ctr.ctypes.data_as(_fp) if len(ctr) else None, len(ctr), float(np.float32(float(radius) * float(radius))),
+                                            kept.ctypes.data_as(_fp) if kept is not None else None, C.byref(nk),
+                                            removed.ctypes.data_as(_fp) if removed is not None else None, C.byref(nr)))
+        if want_removed and removed is None:
+            removed = np.empty((0, 4), dtype=np.float32)  # (no other robot: nothing was removed)
+        return (kept[: nk.value] if kept is not None else None), (removed[: nr.value] if removed is not None else None)
 
     def has(self, key: int):
         n = C.c_size_t(0)

@@ -465,6 +465,17 @@ class BatchMatcher:
         c = _cloud(source)
         return check(lib().mrgfe_batch_add_pair(self._h, target, c.ctypes.data_as(_fp), len(c), 16, g.ctypes.data_as(_fp)))
 
+    def add_target_from_store(self, store, key: int) -> int:
+        """The target is keyframe ``key`` of a :class:`MapCloudStore` on the same device (``mrgfe_batch_add_target_from_store``): the batch reads
+        the store's memory, nothing is uploaded.  The store must outlive the batch's use of it."""
+        return check(lib().mrgfe_batch_add_target_from_store(self._h, store._h, int(key)))
+
+    def add_pair_from_store(self, target: int, store, key: int, guess=None) -> int:
+        """A candidate that is keyframe ``key`` of a :class:`MapCloudStore` (``mrgfe_batch_add_pair_from_store``); for the GICP methods its
+        covariances are cached in the batch under ``key``, as for ``add_pair(..., key=)``."""
+        g = _colmajor(np.eye(4) if guess is None else guess)
+        return check(lib().mrgfe_batch_add_pair_from_store(self._h, target, store._h, int(key), g.ctypes.data_as(_fp)))
+
     def has_cloud(self, key: int):
         """Point count of the stored keyframe ``key``, or None."""
         n = C.c_size_t(0)
