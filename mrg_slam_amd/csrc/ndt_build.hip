@@ -340,8 +340,9 @@ __global__ __launch_bounds__(256) void ndt_leaf_finalize_kernel(const LeafSlice*
         for (int k = 0; k < 9; ++k) cov[k] *= f;
         double w[3], V[9];
         dl_sym_eig3(cov, w, V);
-        const double neg_tol = ls.pcl_eigen_rule ? kPclVgcNegativeEigenTolerance : 0.0;
-        if (w[0] < -neg_tol || w[1] < -neg_tol || w[2] <= 0) {
+        const double noise   = ls.pcl_eigen_rule ? kPclVgcEigenNoiseMult * 2.220446049250313e-16 * fmax(a[3], fmax(a[6], a[8])) : 0.0;
+        const double neg_tol = ls.pcl_eigen_rule ? fmax(kPclVgcNegativeEigenTolerance, noise) : 0.0;
+        if (w[0] < -neg_tol || w[1] < -neg_tol || w[2] <= noise) {
             npts = -1;
         } else {
             const double min_ev = kNdtMinCovarEigMult * w[2];

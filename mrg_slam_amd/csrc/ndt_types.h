@@ -19,6 +19,11 @@ constexpr double   kNdtMinCovarEigMult   = 0.01;   // min_covar_eigvalue_mult_
 // a leaf is invalid when one of its two smaller covariance eigenvalues is below minus this: 0 in ndt_omp's filter (forked from PCL 1.8), dummy_precision() = 1e-12
 // in pcl::VoxelGridCovariance of PCL >= 1.11, which PCL_NDT_HIP's targets follow: an exactly planar voxel (eigenvalue ~ -1e-18) is inflated and kept there
 constexpr double   kPclVgcNegativeEigenTolerance = 1e-12;
+// a deliberate departure from PCL 1.12 on the PCL_NDT_HIP path: that bound is absolute while the single-pass covariance carries rounding noise of up to
+// 1.5 eps max_r(sum x_r^2) — 1e-9 forty metres out, 1e-6 at 3 km, where PCL's rule drops half of the exactly planar voxels it means to keep, and keeps a voxel of
+// identical points whose covariance is pure noise.  noise = kPclVgcEigenNoiseMult * eps * max_r(sum x_r^2): the two smaller eigenvalues may go down to
+// -max(1e-12, noise), the largest must exceed the noise.  pclomp's rule (NDT_HIP) is untouched.  Same constant in oracle/quirks.h.
+constexpr double   kPclVgcEigenNoiseMult = 4.0;
 constexpr uint32_t kHashEmpty            = 0xFFFFFFFFu;
 constexpr uint32_t kDenseLookupMaxCells  = 1u << 22;
 

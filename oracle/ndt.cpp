@@ -108,7 +108,10 @@ int VoxelGridCovariance::build(const float* xyzi, int n, float leaf)
         for (int k = 0; k < 9; ++k) L.cov[k] *= f;
         double ev[3], evec[9];
         sym_eig3(L.cov, ev, evec);
-        if (ev[0] < -negative_eigen_tolerance || ev[1] < -negative_eigen_tolerance || ev[2] <= 0) { L.nr_points = -1; continue; }
+        // the rounding noise of the sums above (quirks.h; 0 under pclomp's rule, where this is `ev < 0 || ev[2] <= 0` as upstream has it)
+        const double noise   = eigen_noise_mult * std::numeric_limits<double>::epsilon() * std::max(a.cov[0], std::max(a.cov[4], a.cov[8]));
+        const double neg_tol = std::max(negative_eigen_tolerance, noise);
+        if (ev[0] < -neg_tol || ev[1] < -neg_tol || ev[2] <= noise) { L.nr_points = -1; continue; }
         double min_ev = quirks::kNdtMinCovarEigvalMult * ev[2];
         if (ev[0] < min_ev) {
             ev[0] = min_ev;

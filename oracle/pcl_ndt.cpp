@@ -35,6 +35,7 @@ int PclNdt::set_target(const float* xyzi, int n)
     // setInputTarget -> init(): target_cells_.setLeafSize(resolution_ x3); setInputCloud(target_); filter(true)
     target.assign(xyzi, xyzi + static_cast<size_t>(n) * 4);
     cells.negative_eigen_tolerance = quirks::kPclVgcNegativeEigenTolerance;  // pcl::VoxelGridCovariance of PCL 1.12, not ndt_omp's fork of it
+    cells.eigen_noise_mult = quirks::kPclVgcEigenNoiseMult;                   // ... with the rounding noise of the single-pass covariance in the rule (quirks.h)
     target_status = cells.build(target.data(), n, resolution);
     return target_status;
 }

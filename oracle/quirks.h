@@ -21,6 +21,13 @@ constexpr double kNdtMinCovarEigvalMult  = 0.01;  // min_covar_eigvalue_mult_
 // [UPSTREAM-RECALL, ADVICE r5: PCL is not in the image] — one edit here and in csrc/ndt_types.h (kPclVgcNegativeEigenTolerance) to correct.
 constexpr double kNdtNegativeEigenTolerance    = 0.0;    // pclomp::VoxelGridCovariance
 constexpr double kPclVgcNegativeEigenTolerance = 1e-12;  // pcl::VoxelGridCovariance (PCL 1.12)
+// DELIBERATE DEPARTURE from PCL 1.12 on that path (not a recollection): the -1e-12 is absolute, but the single-pass covariance carries rounding noise of up to
+// 1.5 eps max_r(sum x_r^2) (sequential sums of n terms, 3 x 3 spectral norm), which is 1e-9 forty metres out and 1e-6 at three kilometres — there PCL's rule drops
+// half of the exactly planar voxels it was written to keep, and at the origin it keeps a voxel of identical points whose covariance is pure noise (inverse 1e17).
+// The PCL path takes the noise level kPclVgcEigenNoiseMult * eps * max_r(sum x_r^2) into the rule: the two smaller eigenvalues may go down to
+// -max(1e-12, noise), and the largest must exceed the noise.  pclomp's rule (NDT_OMP) is untouched (multiplier 0).  Same constant in csrc/ndt_types.h.
+constexpr double kNdtEigenNoiseMult    = 0.0;
+constexpr double kPclVgcEigenNoiseMult = 4.0;
 
 // ---- pclomp::NormalDistributionsTransform defaults (ndt_omp_impl.hpp ctor) ---------------------------
 constexpr float  kNdtResolution          = 1.0f;

@@ -353,3 +353,37 @@ def test_kernels_match_the_first_principles_model(search):
         np.testing.assert_allclose(g0, ga, rtol=0, atol=1e-4 * np.abs(ga).max())
         np.testing.assert_allclose(H0, Ha, rtol=0, atol=1e-4 * np.abs(Ha).max())
         np.testing.assert_allclose(H2, Ha, rtol=0, atol=1e-11 * np.abs(Ha).max())
+
+
+@pytest.mark.parametrize("shifted", [False, True], ids=["origin", "shifted"])
+@pytest.mark.parametrize("search", ["DIRECT7", "DIRECT1", "DIRECT26", "KDTREE"])
+@pytest.mark.parametrize("res", [1.0, 0.5, 0.37, 2.0])
+def test_kernels_match_the_first_principles_model_off_the_unit_grid(res, search, shifted):
+    """the same model and tolerances at leaf sizes where inv_leaf, outlier_ratio / res^3, the neighbour offsets and floor(x / leaf) are not what they
+    are at 1.0 (the kernels take another path for leaf != 1), for every neighbourhood (KDTREE by a brute-force radius search over float centroids), on
+    a cloud at the origin and one shifted by (-37.3, 12.9, -2.2); the model is given the FLOAT resolution (tests/ndt_model_cases.py)"""
+    import ndt_model_cases
+    from mrg_slam_amd import NdtHip
+
+    ndt_model_cases.check_derivatives(NdtHip(resolution=res, search=search), res, search, shifted)
+
+
+@pytest.mark.parametrize("shifted", [False, True], ids=["origin", "shifted"])
+@pytest.mark.parametrize("search,res", [("DIRECT7", 0.5), ("DIRECT7", 0.37), ("KDTREE", 0.5), ("KDTREE", 0.37)])
+def test_kernels_match_the_model_end_to_end_from_raw_points(search, res, shifted):
+    """the leaves come from tests/ndt_leaves_model.py (raw target points -> cells, means, floored inverse covariances), not from g.leaves(): points ->
+    score / gradient / Hessian is independent end to end.  f64-Hessian tolerance: ndt_model_cases.check_derivatives."""
+    import ndt_model_cases
+    from mrg_slam_amd import NdtHip
+
+    ndt_model_cases.check_derivatives(NdtHip(resolution=res, search=search), res, search, shifted, model_leaves=True)
+
+
+@pytest.mark.parametrize("search", ["DIRECT1", "DIRECT7"])
+@pytest.mark.parametrize("res", [0.37, 0.7])
+def test_neighbourhood_lookup_follows_the_float_rule_on_cell_faces(res, search):
+    """the kernels' floorf(xt / leaf) for leaf != 1 on points AT cell faces (tests/ndt_model_cases.check_face_lookup)"""
+    import ndt_model_cases
+    from mrg_slam_amd import NdtHip
+
+    ndt_model_cases.check_face_lookup(NdtHip(resolution=res, search=search), res, search)

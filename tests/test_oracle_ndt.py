@@ -221,6 +221,36 @@ def test_derivatives_match_the_first_principles_model(search):
         assert np.abs(diff).max() <= 1e-11 * np.abs(Htrue).max()
 
 
+@pytest.mark.parametrize("shifted", [False, True], ids=["origin", "shifted"])
+@pytest.mark.parametrize("search", ["DIRECT7", "DIRECT1", "DIRECT26", "KDTREE"])
+@pytest.mark.parametrize("res", [1.0, 0.5, 0.37, 2.0])
+def test_derivatives_match_the_first_principles_model_off_the_unit_grid(res, search, shifted):
+    """the same model and tolerances at leaf sizes where inv_leaf, outlier_ratio / res^3, the neighbour offsets and floor(x / leaf) are not what they
+    are at 1.0, for every neighbourhood (KDTREE by a brute-force radius search over float centroids), on a cloud at the origin and one shifted by
+    (-37.3, 12.9, -2.2); the model is given the FLOAT resolution (tests/ndt_model_cases.py)"""
+    import ndt_model_cases
+
+    ndt_model_cases.check_derivatives(orc.Ndt(resolution=res, search=search, num_threads=2), res, search, shifted)
+
+
+@pytest.mark.parametrize("shifted", [False, True], ids=["origin", "shifted"])
+@pytest.mark.parametrize("search,res", [("DIRECT7", 0.5), ("DIRECT7", 0.37), ("KDTREE", 0.5), ("KDTREE", 0.37)])
+def test_derivatives_match_the_model_end_to_end_from_raw_points(search, res, shifted):
+    """the leaves come from tests/ndt_leaves_model.py (raw target points -> cells, means, floored inverse covariances), not from the oracle: points ->
+    score / gradient / Hessian is independent end to end.  f64-Hessian tolerance: ndt_model_cases.check_derivatives."""
+    import ndt_model_cases
+
+    ndt_model_cases.check_derivatives(orc.Ndt(resolution=res, search=search, num_threads=2), res, search, shifted, model_leaves=True)
+
+
+@pytest.mark.parametrize("search", ["DIRECT1", "DIRECT7"])
+@pytest.mark.parametrize("res", [0.37, 0.7])
+def test_neighbourhood_lookup_follows_the_float_rule_on_cell_faces(res, search):
+    import ndt_model_cases
+
+    ndt_model_cases.check_face_lookup(orc.Ndt(resolution=res, search=search, num_threads=2), res, search)
+
+
 def test_thread_sums_mode_agrees_with_point_order_sums(street_pair_vlp16):
     """The accumulation bench.py TIMES as cpu_baseline (ndt_omp's: one accumulator per OpenMP thread, added in thread order) against the
     checker's (per-point records added in point order): the same sums to rounding, the same alignment."""
