@@ -63,7 +63,7 @@ enum mrgfe_method {
     MRGFE_VGICP_HIP = 3, /* replaces "FAST_VGICP" (fast_gicp::FastVGICP, registrations.cpp:76-84) and the reference's own GPU slot
                             "FAST_VGICP_CUDA" (:65-75): voxelised GICP, target as a Gaussian voxel map of edge `resolution` */
     MRGFE_ICP_HIP = 4, /* replaces "ICP": pcl::IterativeClosestPoint (registrations.cpp:85-92), use_reciprocal_correspondences as in :91;
-                          single registrations only (not in mrgfe_batch_*) */
+                          also in mrgfe_batch_* / mrgfe_node_* (LoopDetector::matching with registration_method "ICP") */
     MRGFE_PCL_GICP_HIP = 5, /* replaces "GICP": pcl::GeneralizedIterativeClosestPoint (registrations.cpp:93-103): PCL's covariances, nearest-point
                                correspondences, inner BFGS with max_optimizer_iterations steps; single registrations only */
     MRGFE_PCL_GICP_OMP_HIP = 6, /* replaces "GICP_OMP": pclomp::GeneralizedIterativeClosestPoint (registrations.cpp:104-114): the same algorithm with
@@ -438,7 +438,11 @@ typedef struct mrgfe_batch mrgfe_batch;
  * advanced together, one launch per derivative evaluation for all pairs still running.  GICP_HIP / SMALL_GICP_HIP / VGICP_HIP:
  * the candidates of a target share its covariances and correspondence grid or voxel map (computed once, like the single
  * setInputTarget of loop_detector.cpp:104), the source covariances are computed on a few parallel streams (or taken from the
- * keyframe store below), and the Levenberg-Marquardt loops of all pairs advance together. */
+ * keyframe store below), and the Levenberg-Marquardt loops of all pairs advance together.  ICP_HIP: the candidates of a target share
+ * its exact-NN grid, and the ICP loops of all pairs advance in lock step — per round one correspondence + moment launch and one
+ * reduction over the pairs still running, one host wait for their 17-sum records, one transform launch; no covariances are computed
+ * and H of the records is all zero.  The records are those of a single ICP_HIP registration of the same pair, bit for bit.
+ * PCL_GICP_HIP and PCL_GICP_OMP_HIP are offered for single registrations only. */
 int  mrgfe_batch_create(mrgfe_ctx* ctx, const mrgfe_reg_params* params, mrgfe_batch** out);
 void mrgfe_batch_destroy(mrgfe_batch* b);
 int  mrgfe_batch_clear(mrgfe_batch* b);
@@ -456,7 +460,7 @@ int  mrgfe_batch_add_device(mrgfe_batch* b, int n_targets, const void* const* d_
 /* Keyframe store.  The candidates of LoopDetector::matching are old keyframes that come back call after call
  * (loop_detector.cpp:66-100 selects them from the same pool for every new keyframe), while the reference hands their
  * clouds to setInputSource from host memory each time (:128).  A pair added with a non-zero `cloud_key` (the keyframe id)
- * keeps its packed cloud — and, for the GICP methods, its k-NN covariances — resident in HBM inside the batch object,
+ * keeps its packed cloud — and, for the GICP methods (not ICP_HIP, which has none), its k-NN covariances — resident in HBM inside the batch object,
  * across mrgfe_batch_clear: the next pair with the same key and point count uses them and `src_xyzi` may be NULL.
  * The store is bounded (MRGFE_KEYFRAME_STORE_MB, default 16384; least recently used keyframes not referenced by the
  * current batch are dropped first); mrgfe_batch_forget drops one key (0: all).  Results are identical to the unkeyed call. */
@@ -470,7 +474,7 @@ int  mrgfe_batch_forget(mrgfe_batch* b, uint64_t cloud_key);
  * the store's memory — nothing is uploaded or copied, the keyframe lives in HBM once.  The store is append-only, so the pointer stays valid; like
  * caller device memory handed to mrgfe_batch_add_*_device, the STORE MUST OUTLIVE the batch's use of it (destroy the batch, or clear it, first).
  * The key is looked up and the store's stream waited for under the store's lock alone (mrgfe_map_store_add uploads asynchronously), which is released
- * before the batch's lock is taken.  For the GICP methods the pair is entered in the batch's keyframe store under `key` with an empty cloud: its k-NN
+ * before the batch's lock is taken.  For the GICP methods (not ICP_HIP: nothing is cached, the batch's store is untouched) the pair is entered in the batch's keyframe store under `key` with an empty cloud: its k-NN
  * covariances are cached there as for mrgfe_batch_add_pair_keyed (mrgfe_batch_store_bytes counts the covariances only; mrgfe_batch_has_cloud does not
  * report such an entry), and mrgfe_batch_forget / mrgfe_batch_clear treat it like a keyed pair.  Records are those of the same batch fed from host
  * memory, bit for bit.  Return the target / pair index (>= 0) or an error (< 0): MRGFE_ERR_INVALID for a key the store does not hold or a store on
@@ -580,7 +584,8 @@ size_t mrgfe_node_store_bytes(const mrgfe_node* node);
  * = records group_first[g] .. group_first[g + 1] - 1 (the candidates of one new keyframe, in candidate order); best[g] = position within the
  * group or -1, best_score[g] = its fitness or DBL_MAX.  Among equal scores the LAST candidate wins, as there. */
 int    mrgfe_node_select_best(const mrgfe_pair_result* results, int n_groups, const int32_t* group_first, int32_t* best, double* best_score);
-/* rounds (plan -> derivative launches -> reduce / controller step) of the last mrgfe_batch_align of an NDT_HIP batch */
+/* rounds (plan -> derivative launches -> reduce / controller step) of the last mrgfe_batch_align of an NDT_HIP batch; of an ICP_HIP batch its
+ * lock-step rounds (correspondences + sums -> reduce -> controller steps -> transform), which is the largest evaluation count of its pairs */
 int mrgfe_batch_rounds(const mrgfe_batch* b);
 /* The reference's own performance counters (loop_detector.cpp:22-34: per new keyframe with candidates the wall microseconds of find_candidates + matching
  * and the candidate count; apps/mrg_slam_component.cpp:1032-1037 writes their ratio as average_time_per_candidate_us) for this batch object:

@@ -102,6 +102,17 @@ void mrgfe_dbg_ctl_destroy(mrgfe_dbg_ctl* h);
 int  mrgfe_dbg_ctl_request(const mrgfe_dbg_ctl* h, int* mode, float T[16], double p[6]);
 int  mrgfe_dbg_ctl_result(mrgfe_dbg_ctl* h, double score, const double grad[6], const double hess[36], double neighbours);
 int  mrgfe_dbg_ctl_final(const mrgfe_dbg_ctl* h, float T[16], int* converged, int* iterations, int* evaluations);
+/* The ICP_HIP loop (csrc/gicp_engine.h IcpController: pcl::IterativeClosestPoint::computeTransformation with TransformationEstimationSVD and
+ * DefaultConvergenceCriteria) stepped by hand, no GPU involved — the one controller behind single registrations and batches.  Every step wants the
+ * same thing: the correspondences of the source AS TRANSFORMED SO FAR (by `guess`, then by every Tm returned) and their 17 sums: [0] their number,
+ * [1..3] sum of the source points, [4..6] sum of the target points, [7..15] sum of target * source^T (row-major), [16] sum of squared distances.
+ * _result takes them, sets *done, and gives the column-major float Tm to apply to the working copy next (the identity when the loop ended on fewer
+ * than 3 correspondences); MRGFE_ERR_STATE once the loop has ended.  n_src == 0 or n_tgt == 0: feed one all-zero record.  Matrices column-major. */
+typedef struct mrgfe_dbg_icp_ctl mrgfe_dbg_icp_ctl;
+int  mrgfe_dbg_icp_ctl_create(const mrgfe_reg_params* params, const float guess[16], uint32_t n_src, uint32_t n_tgt, mrgfe_dbg_icp_ctl** out);
+void mrgfe_dbg_icp_ctl_destroy(mrgfe_dbg_icp_ctl* h);
+int  mrgfe_dbg_icp_ctl_result(mrgfe_dbg_icp_ctl* h, const double sums[17], int* done, float Tm[16]);
+int  mrgfe_dbg_icp_ctl_final(const mrgfe_dbg_icp_ctl* h, float T[16], int* converged, int* iterations, int* evaluations);
 
 /* ---- bounded best-candidate selection (mrgfe_batch_align_best, loop_detector.cpp:126-145 and :156-160) ---------------------------- */
 /* per pair, the certified fitness interval lower <= getFitnessScore <= upper of the last mrgfe_batch_align_best on this pair list (0 / +inf: the

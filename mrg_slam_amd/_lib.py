@@ -287,6 +287,10 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_ctl_request": (C.c_int, [_vp, C.POINTER(C.c_int), _fp, _dp]),
     "mrgfe_dbg_ctl_result": (C.c_int, [_vp, C.c_double, _dp, _dp, C.c_double]),
     "mrgfe_dbg_ctl_final": (C.c_int, [_vp, _fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mrgfe_dbg_icp_ctl_create": (C.c_int, [C.POINTER(RegParams), _fp, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    "mrgfe_dbg_icp_ctl_destroy": (None, [_vp]),
+    "mrgfe_dbg_icp_ctl_result": (C.c_int, [_vp, _dp, C.POINTER(C.c_int), _fp]),
+    "mrgfe_dbg_icp_ctl_final": (C.c_int, [_vp, _fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mrgfe_dbg_batch_fit_bounds": (C.c_int, [_vp, _dp, _dp]),
     "mrgfe_dbg_select_prune": (C.c_int, [C.c_int, _dp, _dp, _ip, _ip, C.c_int, C.c_double, _ip]),
 }

@@ -183,6 +183,9 @@ struct mrgfe_batch {
     std::unique_ptr<Async> async;
 };
 
+// GICP_HIP, SMALL_GICP_HIP and VGICP_HIP keep the k-NN covariances of a stored keyframe (48 bytes per point) with it; NDT and ICP_HIP need the cloud alone
+static bool keeps_covariances(const mrgfe_reg_params& p) { return !is_ndt(p.method) && p.method != MRGFE_ICP_HIP; }
+
 // drop least recently used keyframes that the current batch does not reference until `need` more bytes fit
 static void store_make_room(mrgfe_batch* b, size_t need)
 {
@@ -1277,8 +1280,8 @@ int mrgfe_batch_create(mrgfe_ctx* ctx, const mrgfe_reg_params* params, mrgfe_bat
         if (!ctx || !out) { set_error("mrgfe_batch_create: NULL argument"); return MRGFE_ERR_INVALID; }
         *out = nullptr;
         MRGFE_TRY(check_params(params));
-        if (params->method == MRGFE_ICP_HIP || params->method == MRGFE_PCL_GICP_HIP || params->method == MRGFE_PCL_GICP_OMP_HIP) {
-            set_error("mrgfe_batch_create: ICP_HIP and PCL_GICP_HIP are offered for single registrations only");
+        if (params->method == MRGFE_PCL_GICP_HIP || params->method == MRGFE_PCL_GICP_OMP_HIP) {
+            set_error("mrgfe_batch_create: PCL_GICP_HIP and PCL_GICP_OMP_HIP are offered for single registrations only");
             return MRGFE_ERR_INVALID;
         }
         std::unique_ptr<mrgfe_batch> b(new (std::nothrow) mrgfe_batch());
@@ -1471,10 +1474,12 @@ int mrgfe_batch_add_pair_keyed(mrgfe_batch* b, int target, uint64_t key, const f
                 if (it->second->last_epoch == b->epoch) { set_error("mrgfe_batch_add_pair_keyed: key %llu is already used in this batch with %u points", static_cast<unsigned long long>(key), it->second->n); return MRGFE_ERR_INVALID; }
                 b->store.erase(it);
             }
-            store_make_room(b, n * 16 + (!is_ndt(b->params.method) ? n * 48 : 0));
+            store_make_room(b, n * 16 + (keeps_covariances(b->params) ? n * 48 : 0));
             std::unique_ptr<mrgfe_batch::Keyframe> fresh(new (std::nothrow) mrgfe_batch::Keyframe());
             if (!fresh) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-            MRGFE_TRY(fresh->cloud.ensure(std::max<size_t>(n, 1) * 16));
+            // (ICP_HIP keeps the cloud alone and the entry never grows: mrgfe_batch_store_bytes counts 16 bytes per point, no allocation headroom)
+            if (b->params.method == MRGFE_ICP_HIP) MRGFE_TRY(fresh->cloud.ensure_exact(std::max<size_t>(n, 1) * 16));
+            else                                   MRGFE_TRY(fresh->cloud.ensure(std::max<size_t>(n, 1) * 16));
             if (n) MRGFE_TRY(upload_cloud(b->ctx, xyzi, n, stride, fresh->cloud.p));
             fresh->n = static_cast<uint32_t>(n);
             kf = fresh.get();
@@ -1559,7 +1564,7 @@ int mrgfe_batch_add_pair_from_store(mrgfe_batch* b, int target, mrgfe_map_store*
         MRGFE_TRY(b->ctx->bind());
         if (target < 0 || target >= b->ndt->n_targets()) { set_error("%s: target index %d out of range", fn, target); return MRGFE_ERR_INVALID; }
         mrgfe_batch::Keyframe* kf = nullptr;
-        if (!is_ndt(b->params.method)) {  // the covariances of the keyframe are cached under its key, next to no cloud (the store has it)
+        if (keeps_covariances(b->params)) {  // the covariances of the keyframe are cached under its key, next to no cloud (the store has it)
             auto it = b->store.find(key);
             if (it != b->store.end() && it->second->n != n) {
                 if (it->second->last_epoch == b->epoch) { set_error("%s: key %llu is already used in this batch with %u points", fn, static_cast<unsigned long long>(key), it->second->n); return MRGFE_ERR_INVALID; }
@@ -1599,7 +1604,7 @@ int mrgfe_batch_build_targets(mrgfe_batch* b)
 {
     if (!b) { set_error("NULL batch"); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(b->ctx);
-    if (!is_ndt(b->params.method)) return MRGFE_OK;  // GICP variants: target covariances and grids are built by the first align
+    if (!is_ndt(b->params.method)) return MRGFE_OK;  // GICP variants and ICP: target covariances and grids are built by the first align
     TraceRange tr("mrgfe set_target (batch)");
     return b->ndt->build_targets();
 }
@@ -1735,6 +1740,24 @@ static int gicp_align_batch(mrgfe_batch* b, mrgfe_pair_result* results)
             bp.ext_cov_k = &kf->cov_k;
         }
         std::memcpy(bp.guess, p.guess, sizeof(bp.guess));
+    }
+    if (b->params.method == MRGFE_ICP_HIP) {  // lock-step ICP rounds: no covariances, no Hessian
+        MRGFE_TRY(b->gicp_batch->align_all_icp(b->gicp, b->gicp_pairs));
+        b->gicp_final.assign(size_t(P) * 16, 0.0f);
+        for (int i = 0; i < P; ++i) {
+            const IcpController& c = b->gicp_pairs[i].icp;
+            mrgfe_pair_result& r = results[i];
+            std::memcpy(&b->gicp_final[size_t(i) * 16], c.final_transformation(), sizeof(float) * 16);
+            row2col(&b->gicp_final[size_t(i) * 16], r.T);
+            std::memset(r.H, 0, sizeof(r.H));
+            r.fitness = DBL_MAX;
+            r.trans_probability = 0.0;
+            r.converged = c.converged() ? 1 : 0;
+            r.iterations = c.iterations();
+            r.evaluations = c.evaluations();
+            r.pair_id = i;
+        }
+        return MRGFE_OK;
     }
     MRGFE_TRY(b->gicp_batch->align_all(b->gicp, b->gicp_pairs));
     b->gicp_final.assign(size_t(P) * 16, 0.0f);
@@ -2265,7 +2288,12 @@ long mrgfe_dbg_fail_alloc_after(long k) { return fail_alloc_after(k); }
 long mrgfe_dbg_live_allocations(void) { return live_allocations(); }
 #endif
 
-int mrgfe_batch_rounds(const mrgfe_batch* b) { return b && b->ndt ? b->ndt->rounds() : 0; }
+int mrgfe_batch_rounds(const mrgfe_batch* b)
+{
+    if (!b) return 0;
+    if (b->params.method == MRGFE_ICP_HIP) return b->gicp_batch ? b->gicp_batch->rounds() : 0;
+    return b->ndt ? b->ndt->rounds() : 0;
+}
 
 
 int mrgfe_dbg_ctl_create(const mrgfe_reg_params* params, const float guess[16], uint32_t n_src, mrgfe_dbg_ctl** out)
@@ -2306,6 +2334,44 @@ int mrgfe_dbg_ctl_result(mrgfe_dbg_ctl* h, double score, const double grad[6], c
 int mrgfe_dbg_ctl_final(const mrgfe_dbg_ctl* h, float T[16], int* converged, int* iterations, int* evaluations)
 {
     if (!h || !T) { set_error("mrgfe_dbg_ctl_final: NULL argument"); return MRGFE_ERR_INVALID; }
+    row2col(h->c.final_transformation(), T);
+    if (converged) *converged = h->c.converged() ? 1 : 0;
+    if (iterations) *iterations = h->c.iterations();
+    if (evaluations) *evaluations = h->c.evaluations();
+    return MRGFE_OK;
+}
+
+// ---- the ICP loop stepped by hand (no GPU involved): tests/test_icp_controller_cpu.py feeds it moment sums computed in numpy -------------
+struct mrgfe_dbg_icp_ctl { IcpController c; };
+
+int mrgfe_dbg_icp_ctl_create(const mrgfe_reg_params* params, const float guess[16], uint32_t n_src, uint32_t n_tgt, mrgfe_dbg_icp_ctl** out)
+{
+    if (!params || !guess || !out) { set_error("mrgfe_dbg_icp_ctl_create: NULL argument"); return MRGFE_ERR_INVALID; }
+    if (params->method != MRGFE_ICP_HIP) { set_error("mrgfe_dbg_icp_ctl_create: ICP_HIP only"); return MRGFE_ERR_INVALID; }
+    MRGFE_TRY(check_params(params));
+    mrgfe_dbg_icp_ctl* h = new (std::nothrow) mrgfe_dbg_icp_ctl();
+    if (!h) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+    float g[16];
+    col2row(guess, g);
+    h->c.start(gicp_params_from(*params), g, n_src, n_tgt);
+    *out = h;
+    return MRGFE_OK;
+}
+void mrgfe_dbg_icp_ctl_destroy(mrgfe_dbg_icp_ctl* h) { delete h; }
+int mrgfe_dbg_icp_ctl_result(mrgfe_dbg_icp_ctl* h, const double sums[17], int* done, float Tm[16])
+{
+    if (!h || !sums) { set_error("mrgfe_dbg_icp_ctl_result: NULL argument"); return MRGFE_ERR_INVALID; }
+    if (h->c.done()) { set_error("mrgfe_dbg_icp_ctl_result: the loop has ended"); return MRGFE_ERR_STATE; }
+    double r[32] = {0};
+    std::memcpy(r, sums, sizeof(double) * 17);
+    h->c.on_result(r);
+    if (done) *done = h->c.done() ? 1 : 0;
+    if (Tm) row2col(h->c.step(), Tm);
+    return MRGFE_OK;
+}
+int mrgfe_dbg_icp_ctl_final(const mrgfe_dbg_icp_ctl* h, float T[16], int* converged, int* iterations, int* evaluations)
+{
+    if (!h || !T) { set_error("mrgfe_dbg_icp_ctl_final: NULL argument"); return MRGFE_ERR_INVALID; }
     row2col(h->c.final_transformation(), T);
     if (converged) *converged = h->c.converged() ? 1 : 0;
     if (iterations) *iterations = h->c.iterations();

@@ -125,6 +125,11 @@ int DevBuf::ensure(size_t bytes)
     size_t want = cap ? cap : 4096;
     while (want < bytes) want += want / 2 + 4096;
     want = (want + 255) & ~size_t(255);
+    return allocate(want);
+}
+int DevBuf::ensure_exact(size_t bytes) { return bytes <= cap ? MRGFE_OK : allocate(bytes); }
+int DevBuf::allocate(size_t want)
+{
     if (p) { MRGFE_HIP_CHECK(hipFree(p)); p = nullptr; cap = 0; count_live(-1); }
     if (inject_alloc_failure()) return MRGFE_ERR_HIP;
     MRGFE_HIP_CHECK(hipMalloc(&p, want));

@@ -57,8 +57,12 @@ struct DevBuf {
     DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
     ~DevBuf() { release(); }
     int    ensure(size_t bytes);
+    int    ensure_exact(size_t bytes);  // for a buffer that is filled once and never grows: cap == bytes, no headroom
     void   release();  // free now (the HIP status is ignored, as in the destructor)
     template <class T> T* as() const { return static_cast<T*>(p); }
+
+   private:
+    int allocate(size_t want);
 };
 
 // grow-only pinned host buffer

@@ -226,9 +226,10 @@ __global__ __launch_bounds__(256) void gicp_corr_kernel(NnGrid2Dev g, const floa
 // 130k-point frame unchanged); the answer is the exact nearest neighbour with ties to the lower index whatever the group size
 constexpr uint32_t kGicpWideGroupBelow = 65536;
 
+// one block of the ICP correspondence + moment pass: 32 queries, one partial record; shared by the single registration and the batch
 template <bool kReciprocal>
-__global__ __launch_bounds__(256) void icp_corr_sums_kernel(NnGrid2Dev g, NnGrid2Dev g_cur, const float4* __restrict__ cur, const float4* __restrict__ tgt, uint32_t n, double max_sq,
-                                                             double* __restrict__ partials)
+__device__ __forceinline__ void icp_corr_sums_block(const NnGrid2Dev& g, const NnGrid2Dev& g_cur, const float4* __restrict__ cur, const float4* __restrict__ tgt, uint32_t n, double max_sq,
+                                                    double* __restrict__ partials, uint32_t blk)
 {
 #pragma clang fp contract(off)
     double vals[29];
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(256) void icp_corr_sums_kernel(NnGrid2Dev g, NnGrid
     for (int k = 0; k < 29; ++k) vals[k] = 0.0;
     // eight lanes search one query; lane 0 of the group carries its contribution into the block sum
     constexpr uint32_t per_blk = 256u / kGicpGroup;
-    const uint32_t i = blockIdx.x * per_blk + threadIdx.x / kGicpGroup;
+    const uint32_t i = blk * per_blk + threadIdx.x / kGicpGroup;
     if (i < n) {
         const float4 p = cur[i];
         int32_t j = -1;
@@ -263,7 +264,14 @@ __global__ __launch_bounds__(256) void icp_corr_sums_kernel(NnGrid2Dev g, NnGrid
             vals[16] = sqd;
         }
     }
-    gicp_block_reduce(vals, partials + size_t(blockIdx.x) * kGicpStride, 17);
+    gicp_block_reduce(vals, partials + size_t(blk) * kGicpStride, 17);
+}
+
+template <bool kReciprocal>
+__global__ __launch_bounds__(256) void icp_corr_sums_kernel(NnGrid2Dev g, NnGrid2Dev g_cur, const float4* __restrict__ cur, const float4* __restrict__ tgt, uint32_t n, double max_sq,
+                                                             double* __restrict__ partials)
+{
+    icp_corr_sums_block<kReciprocal>(g, g_cur, cur, tgt, n, max_sq, partials, blockIdx.x);
 }
 
 // ---- PCL_GICP_HIP: pcl::GeneralizedIterativeClosestPoint (registrations.cpp:93-103) / pclomp::GICP (:104-114) -----------------------
@@ -792,6 +800,68 @@ __global__ __launch_bounds__(256) void gicp_reduce_batch_kernel(const GicpPairDe
     gicp_reduce_record(partials + size_t(pr.part_off) * kGicpStride, (pr.n + 255u) / 256u, results + size_t(blockIdx.x) * kGicpStride);
 }
 
+// ---- batched ICP: blockIdx.y = the y-th busy pair of the round ---------------------------------------------------------------
+struct IcpPairDev {  // per busy pair and round
+    float4*       cur;       // the pair's working copy of its source
+    const float4* tgt;
+    uint32_t      n;
+    uint32_t      part_off;  // first block-partial record of this pair
+    uint32_t      target;    // index into the grid array
+    uint32_t      pair;      // index of the pair in the batch: its record is results[pair]
+    NnGrid2Dev    g_cur;     // reciprocal correspondences: this round's exact-NN grid over `cur`
+};
+struct IcpMoveDev {  // one in-place transform of a working copy
+    float4*  cur;
+    uint32_t n;
+    uint32_t pad;
+    float    T12[12];
+};
+constexpr uint32_t kIcpPerBlock = 256u / kGicpGroup;
+
+__device__ __forceinline__ void icp_stage_grid(NnGrid2Dev* dst_grid, const NnGrid2Dev* src_grid)
+{
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(src_grid);
+    uint32_t*       dst = reinterpret_cast<uint32_t*>(dst_grid);
+    for (uint32_t w = threadIdx.x; w < sizeof(NnGrid2Dev) / 4; w += 256) dst[w] = src[w];
+}
+
+template <bool kReciprocal>
+__global__ __launch_bounds__(256) void icp_corr_sums_batch_kernel(const IcpPairDev* __restrict__ busy, const NnGrid2Dev* __restrict__ grids, double max_sq, double* __restrict__ partials)
+{
+    __shared__ NnGrid2Dev s_grid, s_cur;
+    const IcpPairDev* pr = busy + blockIdx.y;
+    const uint32_t    n = pr->n;
+    if (blockIdx.x * kIcpPerBlock >= n) return;  // uniform: past this pair's own blocks, its partials stay untouched
+    icp_stage_grid(&s_grid, grids + pr->target);
+    if (kReciprocal) icp_stage_grid(&s_cur, &pr->g_cur);
+    __syncthreads();
+    icp_corr_sums_block<kReciprocal>(s_grid, kReciprocal ? s_cur : s_grid, pr->cur, pr->tgt, n, max_sq, partials + size_t(pr->part_off) * kGicpStride, blockIdx.x);
+}
+
+// one workgroup per busy pair: the sum of gicp_reduce_kernel over the pair's block partials, written to (pinned host) results[pair][32]
+__global__ __launch_bounds__(256) void icp_reduce_batch_kernel(const IcpPairDev* __restrict__ busy, const double* __restrict__ partials, double* __restrict__ results)
+{
+    const IcpPairDev* pr = busy + blockIdx.x;
+    gicp_reduce_record(partials + size_t(pr->part_off) * kGicpStride, (pr->n + kIcpPerBlock - 1) / kIcpPerBlock, results + size_t(pr->pair) * kGicpStride);
+}
+
+__global__ __launch_bounds__(256) void icp_transform_batch_kernel(const IcpMoveDev* __restrict__ moves)
+{
+    __shared__ float s_T[12];
+    const IcpMoveDev* mv = moves + blockIdx.y;
+    const uint32_t    n = mv->n;
+    if (blockIdx.x * 256u >= n) return;  // uniform
+    if (threadIdx.x < 12) s_T[threadIdx.x] = mv->T12[threadIdx.x];
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    float4* cur = mv->cur;
+    float4 p = cur[i];
+    float  x, y, z;
+    transform_point(s_T, p.x, p.y, p.z, x, y, z);  // pcl::transformPointCloud
+    cur[i] = make_float4(x, y, z, p.w);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------
@@ -900,6 +970,7 @@ int GicpEngine::set_target(const void* d, size_t n)
     d_tgt_ = static_cast<const float4*>(d);
     n_tgt_ = n;
     tgt_grid_valid_ = tgt_cov_valid_ = false;
+    tgt_grid_view_ = false;
     return MRGFE_OK;
 }
 int GicpEngine::set_source(const void* d, size_t n, const float* enclosing_box)
@@ -1269,9 +1340,70 @@ void umeyama_rotation(const double sigma[9], double R[9])
 }
 }  // namespace
 
+// ---- the loop of pcl::IterativeClosestPoint::computeTransformation, one record at a time ------------------------------------------------
+void IcpController::start(const GicpParams& prm, const float guess[16], uint32_t n_src, uint32_t n_tgt)
+{
+    prm_ = prm;
+    n_src_ = n_src;
+    n_tgt_ = n_tgt;
+    std::memcpy(final_, guess, sizeof(final_));
+    for (int i = 0; i < 16; ++i) Tm_[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+    done_ = false;
+    converged_ = false;
+    nr_iterations_ = 0;
+    evaluations_ = 0;
+    prev_mse_ = std::numeric_limits<double>::max();
+}
+
+void IcpController::on_result(const double r[32])
+{
+    if (done_) return;
+    ++evaluations_;
+    const double rot_thr = 1.0 - prm_.trans_eps, trans_thr = prm_.trans_eps;
+    float* Tm = Tm_;
+    for (int i = 0; i < 16; ++i) Tm[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+    const double cnt = r[0];
+    if (cnt < 3) { converged_ = false; done_ = true; return; }  // "Not enough correspondences found"
+    double mu_s[3], mu_d[3], sigma[9], R[9];
+    for (int a = 0; a < 3; ++a) { mu_s[a] = r[1 + a] / cnt; mu_d[a] = r[4 + a] / cnt; }
+    for (int rr = 0; rr < 3; ++rr) for (int c = 0; c < 3; ++c) sigma[rr * 3 + c] = r[7 + rr * 3 + c] / cnt - mu_d[rr] * mu_s[c];
+    umeyama_rotation(sigma, R);
+    const float ms[3] = {static_cast<float>(mu_s[0]), static_cast<float>(mu_s[1]), static_cast<float>(mu_s[2])};
+    for (int rr = 0; rr < 3; ++rr) {
+        for (int c = 0; c < 3; ++c) Tm[rr * 4 + c] = static_cast<float>(R[rr * 3 + c]);
+        float s = Tm[rr * 4 + 0] * ms[0];  // Rt.col(3).head(3) = dst_mean - R * src_mean, in float
+        s = s + Tm[rr * 4 + 1] * ms[1];
+        s = s + Tm[rr * 4 + 2] * ms[2];
+        Tm[rr * 4 + 3] = static_cast<float>(mu_d[rr]) - s;
+    }
+    float nf[16];
+    for (int rr = 0; rr < 4; ++rr)
+        for (int c = 0; c < 4; ++c) { float s = 0; for (int k = 0; k < 4; ++k) s += Tm[rr * 4 + k] * final_[k * 4 + c]; nf[rr * 4 + c] = s; }
+    std::memcpy(final_, nf, sizeof(nf));
+    ++nr_iterations_;
+    if (nr_iterations_ >= prm_.max_iterations) { converged_ = true; done_ = true; return; }
+    const double cos_angle = 0.5 * (static_cast<double>(Tm[0]) + static_cast<double>(Tm[5]) + static_cast<double>(Tm[10]) - 1.0);
+    const double tsq = static_cast<double>(Tm[3]) * Tm[3] + static_cast<double>(Tm[7]) * Tm[7] + static_cast<double>(Tm[11]) * Tm[11];
+    if (cos_angle >= rot_thr && tsq <= trans_thr) { converged_ = true; done_ = true; return; }
+    const double mse = r[16] / cnt;
+    if (std::fabs(mse - prev_mse_) < 1e-12) { converged_ = true; done_ = true; return; }
+    prev_mse_ = mse;
+}
+
+int GicpEngine::prepare_icp_target()
+{
+    if (!d_tgt_ && n_tgt_) { set_error("ICP: no target"); return MRGFE_ERR_STATE; }
+    if (!tgt_grid_valid_) {
+        MRGFE_TRY(tgt_grid_.build(ctx_, d_tgt_, n_tgt_, 1.0f, NnGrid::kCrowding1nn, 1));
+        tgt_grid_valid_ = true;
+        tgt_grid_view_ = false;
+    }
+    return MRGFE_OK;
+}
+
 // pcl::IterativeClosestPoint::computeTransformation with TransformationEstimationSVD and DefaultConvergenceCriteria
-// (gicp_engine.h, variant 3).  Per iteration: one correspondence + moment kernel, a 17-double record to the host, a 3x3 SVD,
-// one in-place transform of the working copy of the source.
+// (gicp_engine.h, variant 3): IcpController, driven one record at a time.  Per iteration: one correspondence + moment kernel, a 17-double
+// record to the host, the controller's step (a 3x3 SVD), one in-place transform of the working copy of the source.
 int GicpEngine::align_icp(const float guess[16])
 {
     if (!d_tgt_ && n_tgt_) { set_error("ICP: no target"); return MRGFE_ERR_STATE; }
@@ -1283,10 +1415,7 @@ int GicpEngine::align_icp(const float guess[16])
     nr_iterations_ = 0;
     for (int t = 0; t < 36; ++t) final_hessian_[t] = 0.0;
     std::memcpy(final_, guess, sizeof(final_));
-    if (!tgt_grid_valid_) {
-        MRGFE_TRY(tgt_grid_.build(ctx_, d_tgt_, n_tgt_, 1.0f, NnGrid::kCrowding1nn, 1));
-        tgt_grid_valid_ = true;
-    }
+    MRGFE_TRY(prepare_icp_target());
     const uint32_t n = static_cast<uint32_t>(n_src_);
     constexpr uint32_t per_blk = 256u / kGicpGroup;
     const uint32_t nblk_t = (n + 255) / 256, nblk_c = (n + per_blk - 1) / per_blk;
@@ -1305,12 +1434,11 @@ int GicpEngine::align_icp(const float guess[16])
         MRGFE_HIP_CHECK(hipStreamSynchronize(st));  // d_T_ is rewritten below
     }
     const double max_sq = prm_.max_corr_dist * prm_.max_corr_dist;
-    const double rot_thr = 1.0 - prm_.trans_eps, trans_thr = prm_.trans_eps;
-    double prev_mse = std::numeric_limits<double>::max();
-    for (;;) {
-        ++n_linearize_;
+    IcpController ctl;
+    ctl.start(prm_, guess, n, static_cast<uint32_t>(n_tgt_));
+    while (!ctl.done()) {
         double r[kGicpStride] = {0};
-        if (n && n_tgt_) {
+        if (!ctl.degenerate()) {
             if (prm_.use_reciprocal) {
                 MRGFE_TRY(cur_grid_.build(ctx_, d_cur, n, 1.0f, NnGrid::kCrowding1nn, 1));
                 hipLaunchKernelGGL(icp_corr_sums_kernel<true>, dim3(nblk_c), dim3(256), 0, st, tgt_grid_.dev2(), cur_grid_.dev2(), d_cur, d_tgt_, n, max_sq, d_part);
@@ -1323,39 +1451,18 @@ int GicpEngine::align_icp(const float guess[16])
             MRGFE_HIP_CHECK(hipStreamSynchronize(st));
             kernel_launches += 1;
         }
-        const double cnt = r[0];
-        if (cnt < 3) { converged_ = false; break; }  // "Not enough correspondences found"
-        double mu_s[3], mu_d[3], sigma[9], R[9];
-        for (int a = 0; a < 3; ++a) { mu_s[a] = r[1 + a] / cnt; mu_d[a] = r[4 + a] / cnt; }
-        for (int rr = 0; rr < 3; ++rr) for (int c = 0; c < 3; ++c) sigma[rr * 3 + c] = r[7 + rr * 3 + c] / cnt - mu_d[rr] * mu_s[c];
-        umeyama_rotation(sigma, R);
-        float Tm[16];
-        for (int i = 0; i < 16; ++i) Tm[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-        const float ms[3] = {static_cast<float>(mu_s[0]), static_cast<float>(mu_s[1]), static_cast<float>(mu_s[2])};
-        for (int rr = 0; rr < 3; ++rr) {
-            for (int c = 0; c < 3; ++c) Tm[rr * 4 + c] = static_cast<float>(R[rr * 3 + c]);
-            float s = Tm[rr * 4 + 0] * ms[0];  // Rt.col(3).head(3) = dst_mean - R * src_mean, in float
-            s = s + Tm[rr * 4 + 1] * ms[1];
-            s = s + Tm[rr * 4 + 2] * ms[2];
-            Tm[rr * 4 + 3] = static_cast<float>(mu_d[rr]) - s;
-        }
-        MRGFE_HIP_CHECK(hipMemcpyAsync(d_T_.p, Tm, 48, hipMemcpyHostToDevice, st));
+        const int before = ctl.iterations();
+        ctl.on_result(r);
+        if (ctl.iterations() == before) break;  // fewer than 3 correspondences: no estimate, nothing to apply
+        MRGFE_HIP_CHECK(hipMemcpyAsync(d_T_.p, ctl.step(), 48, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(icp_transform_kernel, dim3(nblk_t), dim3(256), 0, st, d_cur, n, d_T_.as<float>());
         MRGFE_HIP_CHECK(hipGetLastError());
-        MRGFE_HIP_CHECK(hipStreamSynchronize(st));  // Tm is a local
-        float nf[16];
-        for (int rr = 0; rr < 4; ++rr)
-            for (int c = 0; c < 4; ++c) { float s = 0; for (int k = 0; k < 4; ++k) s += Tm[rr * 4 + k] * final_[k * 4 + c]; nf[rr * 4 + c] = s; }
-        std::memcpy(final_, nf, sizeof(nf));
-        ++nr_iterations_;
-        if (nr_iterations_ >= prm_.max_iterations) { converged_ = true; break; }
-        const double cos_angle = 0.5 * (static_cast<double>(Tm[0]) + static_cast<double>(Tm[5]) + static_cast<double>(Tm[10]) - 1.0);
-        const double tsq = static_cast<double>(Tm[3]) * Tm[3] + static_cast<double>(Tm[7]) * Tm[7] + static_cast<double>(Tm[11]) * Tm[11];
-        if (cos_angle >= rot_thr && tsq <= trans_thr) { converged_ = true; break; }
-        const double mse = r[16] / cnt;
-        if (std::fabs(mse - prev_mse) < 1e-12) { converged_ = true; break; }
-        prev_mse = mse;
+        MRGFE_HIP_CHECK(hipStreamSynchronize(st));  // the next step rewrites the controller's matrix
     }
+    n_linearize_ = ctl.evaluations();
+    converged_ = ctl.converged();
+    nr_iterations_ = ctl.iterations();
+    std::memcpy(final_, ctl.final_transformation(), sizeof(final_));
     return MRGFE_OK;
 }
 
@@ -1963,6 +2070,167 @@ int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std:
         }
     }
     set_error("GICP batch did not terminate within %d rounds", round_cap);
+    return MRGFE_ERR_STATE;
+}
+
+// ---- batched ICP rounds ------------------------------------------------------------------------------------------------------------------
+int GicpBatch::align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, std::vector<GicpBatchPair>& pairs)
+{
+    MRGFE_TRY(ctx_->bind());
+    rounds_ = 0;
+    const int P = static_cast<int>(pairs.size());
+    if (P == 0) return MRGFE_OK;
+    hipStream_t st = ctx_->stream;
+    if (!done_) MRGFE_HIP_CHECK(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
+    const GicpParams& prm = engines[pairs[0].target]->params();
+    const bool   reciprocal = prm.use_reciprocal;
+    const double max_sq = prm.max_corr_dist * prm.max_corr_dist;
+    // target grids: one exact-NN grid per distinct target, kept in its engine.  One new target builds its own; several are built together, and
+    // with them the targets that are views of the set's previous build (the set's arrays are rewritten)
+    {
+        std::vector<int> fresh, views;
+        for (size_t t = 0; t < engines.size(); ++t) {
+            if (!engines[t] || engines[t]->target_size() == 0) continue;  // (an empty target is never searched)
+            if (!engines[t]->icp_target_ready()) fresh.push_back(static_cast<int>(t));
+            else if (engines[t]->icp_target_is_view()) views.push_back(static_cast<int>(t));
+        }
+        if (fresh.size() == 1) {
+            MRGFE_TRY(engines[fresh[0]]->prepare_icp_target());
+        } else if (fresh.size() > 1) {
+            fresh.insert(fresh.end(), views.begin(), views.end());
+            std::vector<const float4*> clouds;
+            std::vector<uint32_t>      sizes;
+            std::vector<NnGrid*>       out;
+            if (tgt_views_.size() < fresh.size()) tgt_views_.resize(fresh.size());
+            for (size_t w = 0; w < fresh.size(); ++w) {
+                clouds.push_back(engines[fresh[w]]->target_points());
+                sizes.push_back(static_cast<uint32_t>(engines[fresh[w]]->target_size()));
+                out.push_back(&tgt_views_[w]);
+            }
+            MRGFE_TRY(tgt_set_.build(ctx_, clouds.data(), sizes.data(), static_cast<int>(fresh.size()), 1.0f, NnGrid::kCrowding1nn, 1, out.data()));
+            for (size_t w = 0; w < fresh.size(); ++w) engines[fresh[w]]->adopt_icp_target(tgt_views_[w].dev2());
+        }
+    }
+    std::vector<NnGrid2Dev> h_grids(std::max<size_t>(engines.size(), 1));
+    std::memset(static_cast<void*>(h_grids.data()), 0, sizeof(NnGrid2Dev) * h_grids.size());
+    for (size_t t = 0; t < engines.size(); ++t)
+        if (engines[t] && engines[t]->icp_target_ready()) h_grids[t] = engines[t]->target_grid();
+    // per pair: the working copy, its slice of the block partials, the controller
+    uint32_t part = 0, max_n = 0;
+    std::vector<uint32_t> part_off(P);
+    for (int i = 0; i < P; ++i) {
+        GicpBatchPair& p = pairs[i];
+        MRGFE_TRY(p.cur.ensure(std::max<size_t>(p.n, 1) * 16));
+        part_off[i] = part;
+        part += (p.n + kIcpPerBlock - 1) / kIcpPerBlock;
+        max_n = std::max(max_n, p.n);
+        p.icp.start(prm, p.guess, p.n, static_cast<uint32_t>(engines[p.target]->target_size()));
+    }
+    MRGFE_TRY(d_grids_.ensure(sizeof(NnGrid2Dev) * h_grids.size()));
+    MRGFE_TRY(d_partials_.ensure(sizeof(double) * kGicpStride * std::max<uint32_t>(part, 1)));
+    MRGFE_TRY(d_busy_.ensure(sizeof(IcpPairDev) * P));
+    MRGFE_TRY(d_moves_.ensure(sizeof(IcpMoveDev) * P));
+    MRGFE_TRY(h_busy_.ensure(sizeof(IcpPairDev) * P * 2));
+    MRGFE_TRY(h_moves_.ensure(sizeof(IcpMoveDev) * P * 2));
+    MRGFE_TRY(h_results_.ensure(sizeof(double) * kGicpStride * P));
+    MRGFE_HIP_CHECK(hipMemcpyAsync(d_grids_.p, h_grids.data(), sizeof(NnGrid2Dev) * h_grids.size(), hipMemcpyHostToDevice, st));
+    double*           hr = h_results_.as<double>();
+    const IcpPairDev* d_busy = d_busy_.as<IcpPairDev>();
+    const IcpMoveDev* d_moves = d_moves_.as<IcpMoveDev>();
+    // a list of in-place transforms in one launch; the list goes up from the pinned half of this parity, which the device has long read when the
+    // host writes it again: every round waits for its records in between
+    int  half = 0;
+    auto move = [&](const std::vector<int>& who, const float* (*matrix)(const GicpBatchPair&)) -> int {
+        if (who.empty()) return MRGFE_OK;
+        IcpMoveDev* hm = h_moves_.as<IcpMoveDev>() + size_t(half) * P;
+        uint32_t    widest = 0;
+        for (size_t w = 0; w < who.size(); ++w) {
+            GicpBatchPair& p = pairs[who[w]];
+            hm[w].cur = p.cur.as<float4>();
+            hm[w].n = p.n;
+            hm[w].pad = 0;
+            std::memcpy(hm[w].T12, matrix(p), sizeof(hm[w].T12));
+            widest = std::max(widest, p.n);
+        }
+        MRGFE_HIP_CHECK(hipMemcpyAsync(d_moves_.p, hm, sizeof(IcpMoveDev) * who.size(), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(icp_transform_batch_kernel, dim3((widest + 255) / 256, static_cast<uint32_t>(who.size())), dim3(256), 0, st, d_moves);
+        MRGFE_HIP_CHECK(hipGetLastError());
+        return MRGFE_OK;
+    };
+    // start: the working copies; the guess is applied to those whose guess is not exactly the identity (as the single engine does), in one launch
+    std::vector<int> who;
+    for (int i = 0; i < P; ++i) {
+        GicpBatchPair& p = pairs[i];
+        if (p.icp.degenerate()) continue;
+        MRGFE_HIP_CHECK(hipMemcpyAsync(p.cur.p, p.d_src, size_t(p.n) * 16, hipMemcpyDeviceToDevice, st));
+        bool identity = true;
+        for (int t = 0; t < 16; ++t) identity = identity && p.guess[t] == ((t % 5 == 0) ? 1.0f : 0.0f);
+        if (!identity) who.push_back(i);
+    }
+    MRGFE_TRY(move(who, [](const GicpBatchPair& p) -> const float* { return p.guess; }));
+    MRGFE_HIP_CHECK(hipEventRecord(done_, st));
+    MRGFE_HIP_CHECK(hipEventSynchronize(done_));  // h_grids is a local
+    std::vector<int>           busy;
+    std::vector<const float4*> cur_clouds;
+    std::vector<uint32_t>      cur_sizes;
+    std::vector<NnGrid*>       cur_out;
+    const double zeros[kGicpStride] = {0};
+    const int    round_cap = std::max(prm.max_iterations, 1) + 1;
+    for (int round = 0; round < round_cap; ++round) {
+        half ^= 1;
+        busy.clear();
+        for (int i = 0; i < P; ++i) {
+            IcpController& c = pairs[i].icp;
+            if (c.done()) continue;
+            if (c.degenerate()) c.on_result(zeros);  // an empty source or target: the loop ends on an all-zero record, as in the single engine
+            else busy.push_back(i);
+        }
+        if (busy.empty()) return MRGFE_OK;
+        ++rounds_;
+        const uint32_t B = static_cast<uint32_t>(busy.size());
+        if (reciprocal) {  // the exact-NN grids over the working copies of this round, built together
+            cur_clouds.clear(); cur_sizes.clear(); cur_out.clear();
+            if (cur_views_.size() < B) cur_views_.resize(B);
+            for (uint32_t w = 0; w < B; ++w) {
+                cur_clouds.push_back(pairs[busy[w]].cur.as<float4>());
+                cur_sizes.push_back(pairs[busy[w]].n);
+                cur_out.push_back(&cur_views_[w]);
+            }
+            MRGFE_TRY(cur_set_.build(ctx_, cur_clouds.data(), cur_sizes.data(), static_cast<int>(B), 1.0f, NnGrid::kCrowding1nn, 1, cur_out.data()));
+        }
+        IcpPairDev* hb = h_busy_.as<IcpPairDev>() + size_t(half) * P;
+        uint32_t    widest = 0;
+        for (uint32_t w = 0; w < B; ++w) {
+            const int      i = busy[w];
+            GicpBatchPair& p = pairs[i];
+            IcpPairDev&    d = hb[w];
+            d.cur = p.cur.as<float4>();
+            d.tgt = engines[p.target]->target_points();
+            d.n = p.n;
+            d.part_off = part_off[i];
+            d.target = static_cast<uint32_t>(p.target);
+            d.pair = static_cast<uint32_t>(i);
+            if (reciprocal) d.g_cur = cur_views_[w].dev2();
+            else            std::memset(static_cast<void*>(&d.g_cur), 0, sizeof(d.g_cur));
+            widest = std::max(widest, p.n);
+        }
+        MRGFE_HIP_CHECK(hipMemcpyAsync(d_busy_.p, hb, sizeof(IcpPairDev) * B, hipMemcpyHostToDevice, st));
+        const dim3 grid((widest + kIcpPerBlock - 1) / kIcpPerBlock, B);
+        if (reciprocal) hipLaunchKernelGGL(icp_corr_sums_batch_kernel<true>, grid, dim3(256), 0, st, d_busy, d_grids_.as<NnGrid2Dev>(), max_sq, d_partials_.as<double>());
+        else            hipLaunchKernelGGL(icp_corr_sums_batch_kernel<false>, grid, dim3(256), 0, st, d_busy, d_grids_.as<NnGrid2Dev>(), max_sq, d_partials_.as<double>());
+        hipLaunchKernelGGL(icp_reduce_batch_kernel, dim3(B), dim3(256), 0, st, d_busy, d_partials_.as<double>(), hr);
+        MRGFE_HIP_CHECK(hipGetLastError());
+        MRGFE_HIP_CHECK(hipEventRecord(done_, st));
+        MRGFE_HIP_CHECK(hipEventSynchronize(done_));  // the round's one wait
+        who.clear();
+        for (uint32_t w = 0; w < B; ++w) {
+            IcpController& c = pairs[busy[w]].icp;
+            c.on_result(hr + size_t(busy[w]) * kGicpStride);
+            if (!c.done()) who.push_back(busy[w]);
+        }
+        MRGFE_TRY(move(who, [](const GicpBatchPair& p) -> const float* { return p.icp.step(); }));
+    }
+    set_error("ICP batch did not terminate within %d rounds", round_cap);
     return MRGFE_ERR_STATE;
 }
 

@@ -78,6 +78,12 @@ class GicpEngine {
     void              voxel_grid(double* res, int32_t cmin[3], int32_t dim[3], uint32_t* n_cells) const;
     uint32_t          voxels_occupied() const { return vox_occupied_; }
     NnGrid&           scratch_grid() { return cov_grid_; }
+    // ICP_HIP batches (GicpBatch::align_all_icp): the target's exact-NN grid alone, no covariances.  Built by the engine itself, or — several new
+    // targets of a batch at a time — by an NnGridSet whose view the engine adopts (valid until that set is built again)
+    bool icp_target_ready() const { return tgt_grid_valid_; }
+    bool icp_target_is_view() const { return tgt_grid_view_; }
+    int  prepare_icp_target();
+    void adopt_icp_target(const NnGrid2Dev& g) { tgt_grid_.adopt(g, n_tgt_); tgt_grid_valid_ = true; tgt_grid_view_ = true; }
     const GicpParams& params() const { return prm_; }
 
     const float* final_transformation() const { return final_; }
@@ -101,6 +107,7 @@ class GicpEngine {
     DevBuf d_knn_i_, d_knn_d_;
     bool   tgt_grid_valid_ = false, tgt_cov_valid_ = false, src_cov_valid_ = false;
     bool   src_box_valid_ = false;
+    bool   tgt_grid_view_ = false;  // tgt_grid_ is a view into a batch's NnGridSet
     float  src_box_[6] = {0, 0, 0, 0, 0, 0};
     DevBuf d_tgt_cov_, d_src_cov_, d_corr_, d_mahal_, d_partial_, d_T_;
     DevBuf d_vox_, d_vox_runs_;  // VGICP voxel records; first / last run positions (build scratch)
@@ -164,6 +171,31 @@ class GicpLmController {
     void on_result_small(const double r[32]);  // variant 1
 };
 
+// pcl::IterativeClosestPoint::computeTransformation (TransformationEstimationSVD, DefaultConvergenceCriteria) as a resumable state machine: the
+// decisions of GicpEngine::align_icp, which is this controller driven one record at a time, and of the pairs of GicpBatch::align_all_icp.
+// Every request is the same one — correspondences and moment sums of the working copy as transformed so far — so there is no request record:
+// on_result() takes the 17 sums and, unless the loop ended without an estimate, leaves in step() the row-major float matrix to apply to the copy.
+class IcpController {
+   public:
+    void start(const GicpParams& prm, const float guess_rowmajor[16], uint32_t n_src, uint32_t n_tgt);
+    bool done() const { return done_; }
+    bool degenerate() const { return n_src_ == 0 || n_tgt_ == 0; }  // nothing to search: the caller hands on_result an all-zero record
+    void on_result(const double r[32]);  // [0] correspondences, [1..3] sum src, [4..6] sum dst, [7..15] sum dst src^T, [16] sum of squared distances
+    const float* step() const { return Tm_; }  // of the last on_result(); the identity if that found fewer than 3 correspondences
+    bool converged() const { return converged_; }
+    int  iterations() const { return nr_iterations_; }
+    int  evaluations() const { return evaluations_; }
+    const float* final_transformation() const { return final_; }
+
+   private:
+    GicpParams prm_;
+    uint32_t   n_src_ = 0, n_tgt_ = 0;
+    bool   done_ = true, converged_ = false;
+    int    nr_iterations_ = 0, evaluations_ = 0;
+    double prev_mse_ = 0;
+    float  final_[16], Tm_[16];
+};
+
 // Batched GICP_HIP: the candidates of a batch advance through their LM loops together, one launch per kernel per round
 // (blockIdx.y = busy pair), like the NDT rounds.  Source covariances are computed cloud by cloud beforehand.
 struct GicpBatchPair {
@@ -172,6 +204,8 @@ struct GicpBatchPair {
     uint32_t      n = 0;
     float         guess[16];
     DevBuf        cov, corr, mahal;
+    DevBuf        cur;  // ICP_HIP: the source as transformed so far (n * 16 bytes)
+    IcpController icp;  // ICP_HIP
     // keyframe store (api.cpp): covariances kept with the cloud; *ext_cov_k == k_correspondences means they are valid
     DevBuf*       ext_cov = nullptr;
     int*          ext_cov_k = nullptr;
@@ -183,6 +217,10 @@ class GicpBatch {
     ~GicpBatch();
     // engines[t] holds target t (set_target done); pairs: target index, device source cloud, guess (row-major)
     int align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std::vector<GicpBatchPair>& pairs);
+    // ICP_HIP: the pairs' ICP loops in lock step — per round one correspondence + moment launch and one reduction over the pairs still running, ONE host
+    // wait for their records, the controllers' steps, one transform launch.  No covariances; the records are those of GicpEngine::align_icp, bit for bit.
+    int align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, std::vector<GicpBatchPair>& pairs);
+    int rounds() const { return rounds_; }  // of the last align_all_icp
 
    private:
     mrgfe_ctx* ctx_;
@@ -191,6 +229,12 @@ class GicpBatch {
     std::vector<std::unique_ptr<Lane>> lanes_;
     DevBuf d_pairs_, d_evals_, d_grids_, d_partials_;
     PinBuf h_evals_, h_results_;
+    // ICP_HIP: the busy list and the transforms of a round go up from pinned memory (two halves, used in turn) into d_busy_ / d_moves_
+    PinBuf    h_busy_, h_moves_;
+    DevBuf    d_busy_, d_moves_;
+    NnGridSet tgt_set_, cur_set_;  // exact-NN grids of several new targets; of the busy pairs' working copies (reciprocal correspondences)
+    std::vector<NnGrid> tgt_views_, cur_views_;
+    int       rounds_ = 0;
     Event  done_;
 };
 

@@ -413,7 +413,8 @@ def select_registration_method(params: dict, ctx: Context | None = None) -> HipR
 
 class BatchMatcher:
     """Batched candidate matching: the candidate loop of LoopDetector::matching (src/mrg_slam/loop_detector.cpp:126-145)
-    advanced for all candidates at once on one GPU (mrgfe_batch_*)."""
+    advanced for all candidates at once on one GPU (mrgfe_batch_*).  ``params``: NDT_HIP (the default), PCL_NDT_HIP, GICP_HIP, SMALL_GICP_HIP,
+    VGICP_HIP or ICP_HIP (``default_params(ICP_HIP)``: lock-step ICP rounds, records bit-identical to :class:`IcpHip`)."""
 
     def __init__(self, params: RegParams | None = None, ctx: Context | None = None, **ndt_kwargs):
         self._ctx = ctx or default_context()
@@ -451,7 +452,7 @@ class BatchMatcher:
         return check(lib().mrgfe_batch_add_target_device(self._h, C.c_void_p(dev_ptr), n))
 
     def add_pair(self, target: int, source, guess=None, key: int = 0) -> int:
-        """``key`` != 0 (the candidate's keyframe id): the cloud — and for the GICP methods its covariances — stay in the
+        """``key`` != 0 (the candidate's keyframe id): the cloud — and for the GICP methods (not ICP_HIP) its covariances — stay in the
         batch's HBM keyframe store across ``clear()``; once ``has_cloud(key)`` a later call may pass ``source=None``."""
         g = _colmajor(np.eye(4) if guess is None else guess)
         if key:
@@ -512,7 +513,7 @@ class BatchMatcher:
         return check(lib().mrgfe_batch_add_device(self._h, nt, tp, tn, npair, pt.ctypes.data_as(_ip), sp, sn, g.ctypes.data_as(_fp)))
 
     def rounds(self) -> int:
-        """Rounds (plan -> derivative launches -> reduce / controller step) of the last NDT align()."""
+        """Rounds (plan -> derivative launches -> reduce / controller step) of the last NDT align(); ICP_HIP: its lock-step rounds."""
         return int(lib().mrgfe_batch_rounds(self._h))
 
     def set_guess(self, pair: int, guess) -> None:
