@@ -1884,10 +1884,10 @@ GicpBatch::~GicpBatch()
     if (ctx_) (void)hipSetDevice(ctx_->device);  // the members free themselves on the batch's device
 }
 
-int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std::vector<GicpBatchPair>& pairs)
+int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, const PairBook& book, std::vector<GicpBatchPair>& pairs)
 {
     MRGFE_TRY(ctx_->bind());
-    const int P = static_cast<int>(pairs.size());
+    const int P = book.n_pairs();  // (pairs[i] holds the buffers and controllers of the book's pair i)
     if (P == 0) return MRGFE_OK;
     hipStream_t st = ctx_->stream;
     if (!done_) MRGFE_HIP_CHECK(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
@@ -1927,7 +1927,7 @@ int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std:
         std::vector<int> todo;
         for (int i = 0; i < P; ++i) {
             GicpBatchPair& p = pairs[i];
-            const int k = engines[p.target]->params().k_correspondences;
+            const int k = engines[book.pair(i).target]->params().k_correspondences;
             if (p.ext_cov) {
                 if (*p.ext_cov_k == k) continue;
                 bool dup = false;
@@ -1955,15 +1955,16 @@ int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std:
                 const size_t w0 = c * chunk, w1 = std::min(todo.size(), w0 + chunk);
                 clouds.clear(); sizes.clear(); views.clear();
                 for (size_t w = w0; w < w1; ++w) {
-                    clouds.push_back(pairs[todo[w]].d_src);
-                    sizes.push_back(pairs[todo[w]].n);
+                    clouds.push_back(book.pair(todo[w]).d_src);
+                    sizes.push_back(book.pair(todo[w]).n);
                     views.push_back(&l.views[w - w0]);
                 }
                 int rc = l.set.build(l.ctx.get(), clouds.data(), sizes.data(), static_cast<int>(w1 - w0), 1.0f, NnGrid::kCrowdingKnn, kNnMaxLevels, views.data());
                 for (size_t w = w0; w < w1 && rc == MRGFE_OK; ++w) {
-                    GicpBatchPair& p = pairs[todo[w]];
-                    const int k = engines[p.target]->params().k_correspondences;
-                    rc = gicp_covariances_on_grid(l.ctx.get(), k, p.d_src, p.n, p.ext_cov ? *p.ext_cov : p.cov, l.views[w - w0], l.knn_i, l.knn_d, false);
+                    GicpBatchPair&        p = pairs[todo[w]];
+                    const PairBook::Pair& bp = book.pair(todo[w]);
+                    const int k = engines[bp.target]->params().k_correspondences;
+                    rc = gicp_covariances_on_grid(l.ctx.get(), k, bp.d_src, bp.n, p.ext_cov ? *p.ext_cov : p.cov, l.views[w - w0], l.knn_i, l.knn_d, false);
                     if (rc == MRGFE_OK && p.ext_cov) *p.ext_cov_k = k;
                 }
                 if (rc != MRGFE_OK) { status[li] = rc; message[li] = mrgfe_last_error(); break; }
@@ -1981,20 +1982,21 @@ int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std:
     std::vector<GicpPairDev> h_pairs(P);
     uint32_t part = 0, max_n = 0;
     for (int i = 0; i < P; ++i) {
-        GicpBatchPair& p = pairs[i];
-        GicpEngine*    e = engines[p.target].get();
-        MRGFE_TRY(p.corr.ensure(std::max<size_t>(p.n, 1) * 4));
-        MRGFE_TRY(p.mahal.ensure(std::max<size_t>(p.n, 1) * 72));
+        GicpBatchPair&        p = pairs[i];
+        const PairBook::Pair& bp = book.pair(i);
+        GicpEngine*           e = engines[bp.target].get();
+        MRGFE_TRY(p.corr.ensure(std::max<size_t>(bp.n, 1) * 4));
+        MRGFE_TRY(p.mahal.ensure(std::max<size_t>(bp.n, 1) * 72));
         GicpPairDev d;
-        d.src = p.d_src; d.cov_src = (p.ext_cov ? *p.ext_cov : p.cov).as<double>();
+        d.src = bp.d_src; d.cov_src = (p.ext_cov ? *p.ext_cov : p.cov).as<double>();
         d.tgt = voxel ? nullptr : e->target_points();  // tgt == nullptr tells the linearize / error kernels that cov_tgt holds voxel records
         d.cov_tgt = voxel ? e->voxel_records() : e->target_covariances();
         d.corr = p.corr.as<int32_t>(); d.mahal = p.mahal.as<double>();
-        d.n = p.n; d.part_off = part; d.target = static_cast<uint32_t>(p.target); d.pad = 0;
-        part += (p.n + 255u) / 256u;
-        max_n = std::max(max_n, p.n);
+        d.n = bp.n; d.part_off = part; d.target = static_cast<uint32_t>(bp.target); d.pad = 0;
+        part += (bp.n + 255u) / 256u;
+        max_n = std::max(max_n, bp.n);
         h_pairs[i] = d;
-        p.ctl.start(e->params(), p.guess, p.n);
+        p.ctl.start(e->params(), bp.guess, bp.n);
     }
     MRGFE_TRY(d_pairs_.ensure(sizeof(GicpPairDev) * P));
     MRGFE_TRY(d_grids_.ensure((voxel ? sizeof(VoxGridDev) : sizeof(NnGrid2Dev)) * std::max<size_t>(engines.size(), 1)));
@@ -2008,8 +2010,8 @@ int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std:
     MRGFE_HIP_CHECK(hipStreamSynchronize(st));  // h_pairs / h_grids are locals
     GicpEvalDev* he = h_evals_.as<GicpEvalDev>();
     double*      hr = h_results_.as<double>();
-    const double thr = engines[pairs[0].target]->params().max_corr_dist;
-    const GicpParams& prm0 = engines[pairs[0].target]->params();
+    const double thr = engines[book.pair(0).target]->params().max_corr_dist;
+    const GicpParams& prm0 = engines[book.pair(0).target]->params();
     const int    round_cap = (prm0.max_iterations + 1) * (std::max(prm0.lm_max_iterations, prm0.sg_max_inner_iterations) + 2) + 4;
     std::vector<NnFitnessJob> corr_jobs;
     for (int round = 0; round < round_cap; ++round) {
@@ -2017,17 +2019,17 @@ int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std:
         size_t   lin_queries = 0;
         for (int i = 0; i < P; ++i) {
             GicpLmController& c = pairs[i].ctl;
-            if (c.done() || pairs[i].n == 0) { he[i].type = -1; continue; }
-            he[i].pose = make_pose(c.request().T, engines[pairs[i].target]->params().variant);
+            if (c.done() || book.pair(i).n == 0) { he[i].type = -1; continue; }
+            he[i].pose = make_pose(c.request().T, engines[book.pair(i).target]->params().variant);
             he[i].thr2 = thr * thr;
             he[i].type = c.request().type;
-            if (he[i].type == 0) { he[n_lin++].order[0] = static_cast<uint32_t>(i); lin_queries += pairs[i].n; }
+            if (he[i].type == 0) { he[n_lin++].order[0] = static_cast<uint32_t>(i); lin_queries += book.pair(i).n; }
             else                 he[n_err++].order[1] = static_cast<uint32_t>(i);
         }
         // an empty source still walks its LM loop on all-zero records (like the single engine does)
         bool any_empty = false;
         for (int i = 0; i < P; ++i)
-            if (!pairs[i].ctl.done() && pairs[i].n == 0) any_empty = true;
+            if (!pairs[i].ctl.done() && book.pair(i).n == 0) any_empty = true;
         if (n_lin + n_err == 0 && !any_empty) return MRGFE_OK;
         if (n_lin + n_err) {
             MRGFE_HIP_CHECK(hipMemcpyAsync(d_evals_.p, he, sizeof(GicpEvalDev) * P, hipMemcpyHostToDevice, st));
@@ -2042,9 +2044,9 @@ int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std:
                     for (uint32_t w = 0; w < n_lin; ++w) {
                         const uint32_t i = he[w].order[0];
                         NnFitnessJob job;
-                        job.grid = h_grids[pairs[i].target];
-                        job.src = pairs[i].d_src;
-                        job.n = pairs[i].n;
+                        job.grid = h_grids[book.pair(i).target];
+                        job.src = book.pair(i).d_src;
+                        job.n = book.pair(i).n;
                         job.gicp_order = 1;
                         std::memcpy(job.T12, he[i].pose.Tf, sizeof(job.T12));
                         job.idx_out = pairs[i].corr.as<int32_t>();
@@ -2066,7 +2068,7 @@ int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std:
         for (int i = 0; i < P; ++i) {
             GicpLmController& c = pairs[i].ctl;
             if (c.done()) continue;
-            c.on_result(pairs[i].n ? hr + size_t(i) * kGicpStride : zeros);
+            c.on_result(book.pair(i).n ? hr + size_t(i) * kGicpStride : zeros);
         }
     }
     set_error("GICP batch did not terminate within %d rounds", round_cap);
@@ -2074,15 +2076,15 @@ int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std:
 }
 
 // ---- batched ICP rounds ------------------------------------------------------------------------------------------------------------------
-int GicpBatch::align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, std::vector<GicpBatchPair>& pairs)
+int GicpBatch::align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, const PairBook& book, std::vector<GicpBatchPair>& pairs)
 {
     MRGFE_TRY(ctx_->bind());
     rounds_ = 0;
-    const int P = static_cast<int>(pairs.size());
+    const int P = book.n_pairs();  // (pairs[i] holds the buffers and controllers of the book's pair i)
     if (P == 0) return MRGFE_OK;
     hipStream_t st = ctx_->stream;
     if (!done_) MRGFE_HIP_CHECK(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
-    const GicpParams& prm = engines[pairs[0].target]->params();
+    const GicpParams& prm = engines[book.pair(0).target]->params();
     const bool   reciprocal = prm.use_reciprocal;
     const double max_sq = prm.max_corr_dist * prm.max_corr_dist;
     // target grids: one exact-NN grid per distinct target, kept in its engine.  One new target builds its own; several are built together, and
@@ -2119,12 +2121,13 @@ int GicpBatch::align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, 
     uint32_t part = 0, max_n = 0;
     std::vector<uint32_t> part_off(P);
     for (int i = 0; i < P; ++i) {
-        GicpBatchPair& p = pairs[i];
-        MRGFE_TRY(p.cur.ensure(std::max<size_t>(p.n, 1) * 16));
+        GicpBatchPair&        p = pairs[i];
+        const PairBook::Pair& bp = book.pair(i);
+        MRGFE_TRY(p.cur.ensure(std::max<size_t>(bp.n, 1) * 16));
         part_off[i] = part;
-        part += (p.n + kIcpPerBlock - 1) / kIcpPerBlock;
-        max_n = std::max(max_n, p.n);
-        p.icp.start(prm, p.guess, p.n, static_cast<uint32_t>(engines[p.target]->target_size()));
+        part += (bp.n + kIcpPerBlock - 1) / kIcpPerBlock;
+        max_n = std::max(max_n, bp.n);
+        p.icp.start(prm, bp.guess, bp.n, static_cast<uint32_t>(engines[bp.target]->target_size()));
     }
     MRGFE_TRY(d_grids_.ensure(sizeof(NnGrid2Dev) * h_grids.size()));
     MRGFE_TRY(d_partials_.ensure(sizeof(double) * kGicpStride * std::max<uint32_t>(part, 1)));
@@ -2140,17 +2143,18 @@ int GicpBatch::align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, 
     // a list of in-place transforms in one launch; the list goes up from the pinned half of this parity, which the device has long read when the
     // host writes it again: every round waits for its records in between
     int  half = 0;
-    auto move = [&](const std::vector<int>& who, const float* (*matrix)(const GicpBatchPair&)) -> int {
+    auto move = [&](const std::vector<int>& who, bool by_guess) -> int {  // by the pair's guess, or by its controller's step
         if (who.empty()) return MRGFE_OK;
         IcpMoveDev* hm = h_moves_.as<IcpMoveDev>() + size_t(half) * P;
         uint32_t    widest = 0;
         for (size_t w = 0; w < who.size(); ++w) {
-            GicpBatchPair& p = pairs[who[w]];
+            GicpBatchPair&        p = pairs[who[w]];
+            const PairBook::Pair& bp = book.pair(who[w]);
             hm[w].cur = p.cur.as<float4>();
-            hm[w].n = p.n;
+            hm[w].n = bp.n;
             hm[w].pad = 0;
-            std::memcpy(hm[w].T12, matrix(p), sizeof(hm[w].T12));
-            widest = std::max(widest, p.n);
+            std::memcpy(hm[w].T12, by_guess ? bp.guess : p.icp.step(), sizeof(hm[w].T12));
+            widest = std::max(widest, bp.n);
         }
         MRGFE_HIP_CHECK(hipMemcpyAsync(d_moves_.p, hm, sizeof(IcpMoveDev) * who.size(), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(icp_transform_batch_kernel, dim3((widest + 255) / 256, static_cast<uint32_t>(who.size())), dim3(256), 0, st, d_moves);
@@ -2160,14 +2164,15 @@ int GicpBatch::align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, 
     // start: the working copies; the guess is applied to those whose guess is not exactly the identity (as the single engine does), in one launch
     std::vector<int> who;
     for (int i = 0; i < P; ++i) {
-        GicpBatchPair& p = pairs[i];
+        GicpBatchPair&        p = pairs[i];
+        const PairBook::Pair& bp = book.pair(i);
         if (p.icp.degenerate()) continue;
-        MRGFE_HIP_CHECK(hipMemcpyAsync(p.cur.p, p.d_src, size_t(p.n) * 16, hipMemcpyDeviceToDevice, st));
+        MRGFE_HIP_CHECK(hipMemcpyAsync(p.cur.p, bp.d_src, size_t(bp.n) * 16, hipMemcpyDeviceToDevice, st));
         bool identity = true;
-        for (int t = 0; t < 16; ++t) identity = identity && p.guess[t] == ((t % 5 == 0) ? 1.0f : 0.0f);
+        for (int t = 0; t < 16; ++t) identity = identity && bp.guess[t] == ((t % 5 == 0) ? 1.0f : 0.0f);
         if (!identity) who.push_back(i);
     }
-    MRGFE_TRY(move(who, [](const GicpBatchPair& p) -> const float* { return p.guess; }));
+    MRGFE_TRY(move(who, true));
     MRGFE_HIP_CHECK(hipEventRecord(done_, st));
     MRGFE_HIP_CHECK(hipEventSynchronize(done_));  // h_grids is a local
     std::vector<int>           busy;
@@ -2193,7 +2198,7 @@ int GicpBatch::align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, 
             if (cur_views_.size() < B) cur_views_.resize(B);
             for (uint32_t w = 0; w < B; ++w) {
                 cur_clouds.push_back(pairs[busy[w]].cur.as<float4>());
-                cur_sizes.push_back(pairs[busy[w]].n);
+                cur_sizes.push_back(book.pair(busy[w]).n);
                 cur_out.push_back(&cur_views_[w]);
             }
             MRGFE_TRY(cur_set_.build(ctx_, cur_clouds.data(), cur_sizes.data(), static_cast<int>(B), 1.0f, NnGrid::kCrowding1nn, 1, cur_out.data()));
@@ -2202,17 +2207,18 @@ int GicpBatch::align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, 
         uint32_t    widest = 0;
         for (uint32_t w = 0; w < B; ++w) {
             const int      i = busy[w];
-            GicpBatchPair& p = pairs[i];
-            IcpPairDev&    d = hb[w];
+            GicpBatchPair&        p = pairs[i];
+            const PairBook::Pair& bp = book.pair(i);
+            IcpPairDev&           d = hb[w];
             d.cur = p.cur.as<float4>();
-            d.tgt = engines[p.target]->target_points();
-            d.n = p.n;
+            d.tgt = engines[bp.target]->target_points();
+            d.n = bp.n;
             d.part_off = part_off[i];
-            d.target = static_cast<uint32_t>(p.target);
+            d.target = static_cast<uint32_t>(bp.target);
             d.pair = static_cast<uint32_t>(i);
             if (reciprocal) d.g_cur = cur_views_[w].dev2();
             else            std::memset(static_cast<void*>(&d.g_cur), 0, sizeof(d.g_cur));
-            widest = std::max(widest, p.n);
+            widest = std::max(widest, bp.n);
         }
         MRGFE_HIP_CHECK(hipMemcpyAsync(d_busy_.p, hb, sizeof(IcpPairDev) * B, hipMemcpyHostToDevice, st));
         const dim3 grid((widest + kIcpPerBlock - 1) / kIcpPerBlock, B);
@@ -2228,7 +2234,7 @@ int GicpBatch::align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, 
             c.on_result(hr + size_t(busy[w]) * kGicpStride);
             if (!c.done()) who.push_back(busy[w]);
         }
-        MRGFE_TRY(move(who, [](const GicpBatchPair& p) -> const float* { return p.icp.step(); }));
+        MRGFE_TRY(move(who, false));
     }
     set_error("ICP batch did not terminate within %d rounds", round_cap);
     return MRGFE_ERR_STATE;

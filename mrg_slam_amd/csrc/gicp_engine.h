@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "nn_grid.h"
+#include "pair_book.h"
 
 namespace mrgfe {
 
@@ -198,15 +199,12 @@ class IcpController {
 
 // Batched GICP_HIP: the candidates of a batch advance through their LM loops together, one launch per kernel per round
 // (blockIdx.y = busy pair), like the NDT rounds.  Source covariances are computed cloud by cloud beforehand.
+// (per-pair state only: which clouds pair i aligns, and from which guess, is written in the batch's PairBook)
 struct GicpBatchPair {
-    int           target = -1;
-    const float4* d_src = nullptr;
-    uint32_t      n = 0;
-    float         guess[16];
     DevBuf        cov, corr, mahal;
     DevBuf        cur;  // ICP_HIP: the source as transformed so far (n * 16 bytes)
     IcpController icp;  // ICP_HIP
-    // keyframe store (api.cpp): covariances kept with the cloud; *ext_cov_k == k_correspondences means they are valid
+    // keyframe store (batch.cpp): covariances kept with the cloud; *ext_cov_k == k_correspondences means they are valid
     DevBuf*       ext_cov = nullptr;
     int*          ext_cov_k = nullptr;
     GicpLmController ctl;
@@ -215,11 +213,11 @@ class GicpBatch {
    public:
     explicit GicpBatch(mrgfe_ctx* ctx) : ctx_(ctx) {}
     ~GicpBatch();
-    // engines[t] holds target t (set_target done); pairs: target index, device source cloud, guess (row-major)
-    int align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, std::vector<GicpBatchPair>& pairs);
+    // engines[t] holds target t of the book (set_target done); pairs[i]: the buffers and controllers of the book's pair i (book.n_pairs() of them)
+    int align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, const PairBook& book, std::vector<GicpBatchPair>& pairs);
     // ICP_HIP: the pairs' ICP loops in lock step — per round one correspondence + moment launch and one reduction over the pairs still running, ONE host
     // wait for their records, the controllers' steps, one transform launch.  No covariances; the records are those of GicpEngine::align_icp, bit for bit.
-    int align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, std::vector<GicpBatchPair>& pairs);
+    int align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, const PairBook& book, std::vector<GicpBatchPair>& pairs);
     int rounds() const { return rounds_; }  // of the last align_all_icp
 
    private:

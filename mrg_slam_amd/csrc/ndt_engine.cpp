@@ -48,71 +48,9 @@ NdtEngine::~NdtEngine()
 void NdtEngine::clear()
 {
     targets_.clear();
-    pairs_.clear();
     h_grids_.clear();
     leaf_arrays_.clear();
-    cloud_arena_.reset();
     grid_arena_.reset();
-    pairs_dirty_ = true;
-}
-
-void NdtEngine::clear_pairs()
-{
-    pairs_.clear();
-    pairs_dirty_ = true;
-}
-
-int NdtEngine::add_target_device(const void* d_xyzi, size_t n)
-{
-    if (n > 0 && !d_xyzi) { set_error("add_target: NULL cloud"); return MRGFE_ERR_INVALID; }
-    if (n > 0x7fffffffu) { set_error("add_target: cloud too large"); return MRGFE_ERR_INVALID; }
-    NdtTargetInfo t;
-    t.d_pts = static_cast<const float4*>(d_xyzi);
-    t.n = static_cast<uint32_t>(n);
-    targets_.push_back(t);
-    return static_cast<int>(targets_.size()) - 1;
-}
-
-int NdtEngine::add_target_host(const float* xyzi, size_t n, size_t stride)
-{
-    if (n > 0 && !xyzi) { set_error("add_target: NULL cloud"); return MRGFE_ERR_INVALID; }
-    MRGFE_TRY(ctx_->bind());
-    void* d = nullptr;
-    MRGFE_TRY(cloud_arena_.alloc(n * 16, &d));
-    MRGFE_TRY(upload_cloud(ctx_, xyzi, n, stride, d));
-    return add_target_device(d, n);
-}
-
-int NdtEngine::add_pair_device(int target, const void* d_xyzi, size_t n, const float guess[16])
-{
-    if (target < 0 || target >= n_targets()) { set_error("add_pair: target index %d out of range", target); return MRGFE_ERR_INVALID; }
-    if (n > 0 && !d_xyzi) { set_error("add_pair: NULL cloud"); return MRGFE_ERR_INVALID; }
-    if (n > 0x7fffffffu) { set_error("add_pair: cloud too large"); return MRGFE_ERR_INVALID; }
-    NdtPairInfo p;
-    p.target = target;
-    p.d_src = static_cast<const float4*>(d_xyzi);
-    p.n = static_cast<uint32_t>(n);
-    std::memcpy(p.guess, guess, sizeof(p.guess));
-    pairs_.push_back(p);
-    pairs_dirty_ = true;
-    return static_cast<int>(pairs_.size()) - 1;
-}
-
-int NdtEngine::add_pair_host(int target, const float* xyzi, size_t n, size_t stride, const float guess[16])
-{
-    if (n > 0 && !xyzi) { set_error("add_pair: NULL cloud"); return MRGFE_ERR_INVALID; }
-    MRGFE_TRY(ctx_->bind());
-    void* d = nullptr;
-    MRGFE_TRY(cloud_arena_.alloc(n * 16, &d));
-    MRGFE_TRY(upload_cloud(ctx_, xyzi, n, stride, d));
-    return add_pair_device(target, d, n, guess);
-}
-
-int NdtEngine::set_guess(int pair, const float guess[16])
-{
-    if (pair < 0 || pair >= n_pairs()) { set_error("set_guess: pair index %d out of range", pair); return MRGFE_ERR_INVALID; }
-    std::memcpy(pairs_[pair].guess, guess, sizeof(float) * 16);
-    return MRGFE_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -121,6 +59,7 @@ int NdtEngine::set_guess(int pair, const float guess[16])
 int NdtEngine::build_targets(bool wait)
 {
     MRGFE_TRY(ctx_->bind());
+    targets_.resize(n_targets());
     std::vector<int> todo;
     for (int i = 0; i < n_targets(); ++i) if (!targets_[i].built) todo.push_back(i);
     if (todo.empty()) return MRGFE_OK;
@@ -128,7 +67,7 @@ int NdtEngine::build_targets(bool wait)
     hipStream_t st = ctx_->stream;
 
     std::vector<uint32_t> sizes(P);
-    for (int k = 0; k < P; ++k) sizes[k] = targets_[todo[k]].n;
+    for (int k = 0; k < P; ++k) sizes[k] = book_->target(todo[k]).n;
     SliceTable tab;
     tab.build(sizes.data(), P);
 
@@ -159,7 +98,7 @@ int NdtEngine::build_targets(bool wait)
     const VoxelParams*   d_vp = reinterpret_cast<const VoxelParams*>(dd + o_vp);
     const LeafSlice*     d_ls = reinterpret_cast<const LeafSlice*>(dd + o_ls);
 
-    for (int k = 0; k < P; ++k) { h_sl[k] = tab.h[k]; h_cp[k] = targets_[todo[k]].d_pts; h_nv[k] = 0; }
+    for (int k = 0; k < P; ++k) { h_sl[k] = tab.h[k]; h_cp[k] = book_->target(todo[k]).d_pts; h_nv[k] = 0; }
     std::memset(h_vp, 0, sizeof(VoxelParams) * P);
     std::memset(h_ls, 0, sizeof(LeafSlice) * P);
     MRGFE_HIP_CHECK(hipMemcpyAsync(dd, hd, desc_bytes, hipMemcpyHostToDevice, st));
@@ -356,7 +295,7 @@ int NdtEngine::build_targets(bool wait)
 
 int NdtEngine::read_leaves(int target, int32_t* keys, int32_t* nr_points, double* mean3, double* icov9)
 {
-    if (target < 0 || target >= n_targets() || !targets_[target].built) { set_error("read_leaves: target not built"); return MRGFE_ERR_STATE; }
+    if (target < 0 || target >= n_targets() || !this->target(target).built) { set_error("read_leaves: target not built"); return MRGFE_ERR_STATE; }
     MRGFE_TRY(ctx_->bind());
     const uint32_t V = targets_[target].n_leaves;
     if (V == 0) return MRGFE_OK;
@@ -381,11 +320,12 @@ int NdtEngine::upload_pairs()
     uint32_t part = 0;
     max_nblk_ = 0;
     for (int i = 0; i < P; ++i) {
+        const PairBook::Pair& p = book_->pair(i);
         NdtPairDev d;
-        d.src = pairs_[i].d_src;
-        d.n_src = pairs_[i].n;
-        d.grid = static_cast<uint32_t>(pairs_[i].target);
-        d.nblk = (pairs_[i].n + 255u) / 256u;
+        d.src = p.d_src;
+        d.n_src = p.n;
+        d.grid = static_cast<uint32_t>(p.target);
+        d.nblk = (p.n + 255u) / 256u;
         d.part_off = part;
         part += d.nblk;
         max_nblk_ = std::max(max_nblk_, d.nblk);
@@ -405,7 +345,7 @@ int NdtEngine::upload_pairs()
     MRGFE_TRY(h_results_.ensure(sizeof(double) * (kNdtPartialStride * P1 + 1)));  // (+1: the tag a single registration polls for)
     // (pageable source: staged by the runtime before the call returns — no wait, the rounds are enqueued behind the build and this copy)
     if (P) MRGFE_HIP_CHECK(hipMemcpyAsync(d_pairs_.p, h_pairs_.data(), sizeof(NdtPairDev) * P, hipMemcpyHostToDevice, ctx_->stream));
-    pairs_dirty_ = false;
+    pairs_rev_ = book_->revision();
     return MRGFE_OK;
 }
 
@@ -493,21 +433,21 @@ void NdtEngine::host_plan(std::vector<uint32_t>& plan, uint32_t wg_target, uint3
     NdtPlanHead h{};
     uint32_t tiles[3] = {0, 0, 0};
     for (uint32_t i = 0; i < P; ++i) {
-        const NdtController& c = pairs_[i].ctl;
-        if (!c.done()) tiles[c.request_mode()] += (pairs_[i].n + 255u) / 256u;
+        const NdtController& c = ctls_[i];
+        if (!c.done()) tiles[c.request_mode()] += (book_->pair(i).n + 255u) / 256u;
     }
     for (int m = 0; m < 3; ++m) {
         const uint32_t ppt = std::max(1u, std::min(tiles[m] / wg_target, max_ppt));
         h.ppt[m] = forced_ppt_ > 0 ? static_cast<uint32_t>(forced_ppt_) : ppt;
     }
     for (uint32_t i = 0; i < P; ++i) {
-        const NdtController& c = pairs_[i].ctl;
+        const NdtController& c = ctls_[i];
         if (c.done()) continue;
         const int m = c.request_mode();
         plan[ndt_plan_pair_off(P, m) + h.n_pairs[m]] = i;
         plan[ndt_plan_start_off(P, m) + h.n_pairs[m]] = h.n_items[m];
         h.n_pairs[m] += 1;
-        h.n_items[m] += ((pairs_[i].n + 255u) / 256u + h.ppt[m] - 1) / h.ppt[m];
+        h.n_items[m] += ((book_->pair(i).n + 255u) / 256u + h.ppt[m] - 1) / h.ppt[m];
         h.n_active += 1;
     }
     for (int m = 0; m < 3; ++m) plan[ndt_plan_start_off(P, m) + h.n_pairs[m]] = h.n_items[m];
@@ -543,10 +483,10 @@ int NdtEngine::reference_round()
         return MRGFE_OK;
     };
     for (uint32_t i = 0; i < P; ++i) {
-        const NdtController& c = pairs_[i].ctl;
+        const NdtController& c = ctls_[i];
         if (c.done()) continue;
         const uint32_t mode = static_cast<uint32_t>(c.request_mode());
-        const size_t   n = pairs_[i].n;
+        const size_t   n = book_->pair(i).n;
         const size_t   need = ndt_ref_record_doubles(static_cast<int>(mode), n, static_cast<int>(nnb));  // doubles
         if (!jobs.empty() && (rec_doubles + need) * sizeof(double) > ws_cap) MRGFE_TRY(flush());
         jobs.push_back(NdtRefJob{i, mode, rec_doubles, cnt_bytes});
@@ -674,8 +614,8 @@ void NdtEngine::account(const std::vector<NdtRoundInfo>& info, size_t rounds)
             mode_launches[m] += 1;
         }
     const int probes = prm_.search == MRGFE_DIRECT7 ? 7 : (prm_.search == MRGFE_DIRECT1 ? 1 : 27);
-    for (const auto& p : pairs_) {
-        const NdtCtlState& s = p.ctl.state();
+    for (const NdtController& c : ctls_) {
+        const NdtCtlState& s = c.state();
         for (int m = 0; m < 3; ++m) {
             // SURVEY.md §8(d) byte model: point (16) + probes (8 each) + 48 per valid neighbour voxel; the f64 formulation reads 96 per
             // neighbour (mean 3 x f64 + inverse covariance 9 x f64) and a 16-byte centroid per hit
@@ -695,12 +635,13 @@ int NdtEngine::align_all(NdtSnapshotPort* port)
     struct PhaseDump { ~PhaseDump() { static const bool on = std::getenv("MRGFE_PHASE") != nullptr; if (on) ndt_phase_dump(); } } phase_dump;  // diagnostic builds only
     MRGFE_TRY(ctx_->bind());
     MRGFE_TRY(build_targets(false));
-    if (pairs_dirty_) MRGFE_TRY(upload_pairs());
+    if (pairs_rev_ != book_->revision()) MRGFE_TRY(upload_pairs());
     for (int m = 0; m < 3; ++m) { mode_ms[m] = 0; mode_launches[m] = 0; mode_alg_bytes[m] = 0; mode_points[m] = 0; mode_neighbours[m] = 0; largest_pairs[m] = 0; }
     largest_ms = 0;
     round_info_.clear();
     rounds_ = 0;
     const int P = n_pairs();
+    ctls_.resize(P);
     if (P == 0) return MRGFE_OK;
     NdtEvalDev*  he = h_evals_.as<NdtEvalDev>();
     NdtCtlState* hs = h_states_.as<NdtCtlState>();
@@ -711,15 +652,16 @@ int NdtEngine::align_all(NdtSnapshotPort* port)
     int running = 0;
     const bool ref_order = reference_order() && prm_.formulation == 0;
     for (int i = 0; i < P; ++i) {
-        NdtPairInfo& p = pairs_[i];
-        p.ctl.start(prm_, p.guess, p.n, split_first && !ref_order);
+        const PairBook::Pair& p = book_->pair(i);
+        NdtController&        c = ctls_[i];
+        c.start(prm_, p.guess, p.n, split_first && !ref_order);
         // the reference's order is the reference's solve too: Eigen's two-sided JacobiSVD for every Newton step (the LU fast path and the one-sided SVD give
         // the same step to ~1e-16 — which a run to the iteration limit amplifies like it amplifies summation order)
-        if (ref_order) p.ctl.force_reference_solve();
-        if (targets_[p.target].status != MRGFE_OK && !p.ctl.done()) p.ctl.abort_no_target();
+        if (ref_order) c.force_reference_solve();
+        if (targets_[p.target].status != MRGFE_OK && !c.done()) c.abort_no_target();
         he[i].active = 0;
-        p.ctl.fill_eval(he[i]);
-        running += p.ctl.done() ? 0 : 1;
+        c.fill_eval(he[i]);
+        running += c.done() ? 0 : 1;
     }
     if (!running) return MRGFE_OK;
     // every controller needs at most (max_iterations + 2) * (max line-search trials + 2) evaluations
@@ -743,7 +685,7 @@ int NdtEngine::align_all(NdtSnapshotPort* port)
         // (two ahead, the default until round 6: 256 config[1] pairs 8.98 -> 8.85 ms per step with two steps in flight, 10.13 -> 10.05 one at a time;
         // 32 pairs of 33k points 1.24 -> 1.21 ms; config[3] and its shard of 8 unchanged; same records)
         static const size_t lookahead = static_cast<size_t>(std::max(1, env_int("MRGFE_LOOKAHEAD", 1)));
-        for (int i = 0; i < P; ++i) hs[i] = pairs_[i].ctl.state();
+        for (int i = 0; i < P; ++i) hs[i] = ctls_[i].state();
         MRGFE_HIP_CHECK(hipMemcpyAsync(d_states_.p, hs, sizeof(NdtCtlState) * P, hipMemcpyHostToDevice, st));
         MRGFE_TRY(h_info_.ensure(sizeof(NdtRoundInfo) * (round_cap + lookahead + 2)));
         volatile NdtRoundInfo* hi = h_info_.as<NdtRoundInfo>();
@@ -787,7 +729,7 @@ int NdtEngine::align_all(NdtSnapshotPort* port)
         MRGFE_HIP_CHECK(hipMemcpyAsync(hs, d_states_.p, sizeof(NdtCtlState) * P, hipMemcpyDeviceToHost, st));
         MRGFE_HIP_CHECK(hipStreamSynchronize(st));
         if (!finished) { set_error("NDT alignment did not terminate within %zu rounds", round_cap); return MRGFE_ERR_STATE; }
-        for (int i = 0; i < P; ++i) pairs_[i].ctl.adopt(hs[i]);
+        for (int i = 0; i < P; ++i) ctls_[i].adopt(hs[i]);
         const size_t rounds = seen - 1;  // the last plan seen found nothing left to do
         info.resize(rounds);
         for (size_t r = 0; r < rounds; ++r) info[r] = const_cast<NdtRoundInfo*>(hi)[r];
@@ -813,7 +755,7 @@ int NdtEngine::align_all(NdtSnapshotPort* port)
         bool want[3] = {false, false, false};
         NdtRoundInfo ri{};
         for (int i = 0; i < P; ++i) {
-            const NdtController& c = pairs_[i].ctl;
+            const NdtController& c = ctls_[i];
             if (c.done()) continue;
             want[c.request_mode()] = true;
             ri.n_pairs[c.request_mode()]++;
@@ -847,7 +789,7 @@ int NdtEngine::align_all(NdtSnapshotPort* port)
         // controller steps are independent per pair: spread them over the host worker threads for large batches
         host_parallel_for(P, kHostParallelMinPairs, [&](int b, int e) {
             for (int i = b; i < e; ++i) {
-                NdtController& c = pairs_[i].ctl;
+                NdtController& c = ctls_[i];
                 if (c.done()) continue;
                 c.on_result(hr + size_t(i) * kNdtPartialStride);
                 he[i].active = 0;
@@ -867,11 +809,12 @@ int NdtEngine::evaluate(int pair, const float T[16], const double p[6], int mode
     if (mode < 0 || mode > 2) { set_error("evaluate: mode must be 0, 1 or 2"); return MRGFE_ERR_INVALID; }
     MRGFE_TRY(ctx_->bind());
     MRGFE_TRY(build_targets());
-    if (targets_[pairs_[pair].target].status != MRGFE_OK) { set_error("evaluate: target has no grid"); return MRGFE_ERR_STATE; }
-    if (pairs_dirty_) MRGFE_TRY(upload_pairs());
+    if (targets_[book_->pair(pair).target].status != MRGFE_OK) { set_error("evaluate: target has no grid"); return MRGFE_ERR_STATE; }
+    if (pairs_rev_ != book_->revision()) MRGFE_TRY(upload_pairs());
     const int P = n_pairs();
+    ctls_.resize(P);
     NdtController tmp;
-    tmp.start(prm_, T, pairs_[pair].n);  // gauss constants
+    tmp.start(prm_, T, book_->pair(pair).n);  // gauss constants
     NdtCtlState s = tmp.state();
     std::memcpy(s.final_, T, sizeof(s.final_));
     s.phase = NDT_INIT;
@@ -885,13 +828,13 @@ int NdtEngine::evaluate(int pair, const float T[16], const double p[6], int mode
     bool want[3] = {mode == 0, mode == 1, mode == 2};
     // the host-built plan lists the pairs whose controller has a request pending: lend this pair's controller the request
     std::vector<NdtCtlState> saved(P);
-    for (int i = 0; i < P; ++i) { saved[i] = pairs_[i].ctl.state(); NdtCtlState idle = saved[i]; idle.phase = NDT_DONE; pairs_[i].ctl.adopt(idle); }
-    pairs_[pair].ctl.adopt(s);
+    for (int i = 0; i < P; ++i) { saved[i] = ctls_[i].state(); NdtCtlState idle = saved[i]; idle.phase = NDT_DONE; ctls_[i].adopt(idle); }
+    ctls_[pair].adopt(s);
     const int keep = forced_ppt_;
     forced_ppt_ = 1;
     const int rc = (reference_order() && prm_.formulation == 0) ? reference_round() : enqueue_round(0, false, want, nullptr);
     forced_ppt_ = keep;
-    for (int i = 0; i < P; ++i) pairs_[i].ctl.adopt(saved[i]);
+    for (int i = 0; i < P; ++i) ctls_[i].adopt(saved[i]);
     MRGFE_TRY(rc);
     MRGFE_HIP_CHECK(hipStreamSynchronize(st));
     const double* res = h_results_.as<double>() + size_t(pair) * kNdtPartialStride;
@@ -904,12 +847,12 @@ int NdtEngine::evaluate(int pair, const float T[16], const double p[6], int mode
 int NdtEngine::aligned_cloud(int pair, float* out)
 {
     if (pair < 0 || pair >= n_pairs()) { set_error("aligned_cloud: pair index out of range"); return MRGFE_ERR_INVALID; }
-    const NdtPairInfo& p = pairs_[pair];
+    const PairBook::Pair& p = book_->pair(pair);
     if (p.n == 0) return MRGFE_OK;
     MRGFE_TRY(ctx_->bind());
     MRGFE_TRY(d_T12_.ensure(64));
     MRGFE_TRY(d_aligned_.ensure(size_t(p.n) * 16));
-    MRGFE_HIP_CHECK(hipMemcpyAsync(d_T12_.p, p.ctl.final_transformation(), 48, hipMemcpyHostToDevice, ctx_->stream));
+    MRGFE_HIP_CHECK(hipMemcpyAsync(d_T12_.p, ctls_[pair].final_transformation(), 48, hipMemcpyHostToDevice, ctx_->stream));
     MRGFE_TRY(launch_transform_cloud(ctx_, p.d_src, d_aligned_.as<float4>(), p.n, d_T12_.as<float>()));
     MRGFE_HIP_CHECK(hipMemcpyAsync(out, d_aligned_.p, size_t(p.n) * 16, hipMemcpyDeviceToHost, ctx_->stream));
     MRGFE_HIP_CHECK(hipStreamSynchronize(ctx_->stream));

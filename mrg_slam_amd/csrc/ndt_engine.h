@@ -1,6 +1,7 @@
-// csrc/ndt_engine.h — batched NDT_HIP engine: owns the device-resident clouds and target grids of a batch of
-// (target, source, guess) alignments and advances all of them together, one derivative launch per round.
-// A single pcl::Registration-style object (mrgfe_reg) is a batch with one target and one pair.
+// csrc/ndt_engine.h — batched NDT_HIP engine: owns the target grids and the optimiser states of a batch of (target, source, guess)
+// alignments and advances all of them together, one derivative launch per round.  Which clouds, pairs and guesses those are is written in a
+// PairBook (pair_book.h) that the engine reads and does not own; the clouds' device memory belongs to the book or to the caller.
+// A single pcl::Registration-style object (mrgfe_reg) is a book with one target and one pair.
 #pragma once
 #include <atomic>
 #include <vector>
@@ -10,25 +11,17 @@
 #include "ndt_build.h"
 #include "ndt_controller.h"
 #include "ndt_types.h"
+#include "pair_book.h"
 
 namespace mrgfe {
 
+// the grid of target i of the book
 struct NdtTargetInfo {
-    const float4* d_pts = nullptr;
-    uint32_t      n = 0;
     int           status = MRGFE_ERR_STATE;  // MRGFE_OK once the grid is built
     int32_t       min_b[3] = {0, 0, 0}, max_b[3] = {0, 0, 0}, div_b[3] = {0, 0, 0};
     uint32_t      n_leaves = 0;
     uint32_t      leaf_off = 0;
     bool          built = false;
-};
-
-struct NdtPairInfo {
-    int           target = -1;
-    const float4* d_src = nullptr;
-    uint32_t      n = 0;
-    float         guess[16];  // row-major
-    NdtController ctl;
 };
 
 // who steps the optimiser of the following alignments: -1 automatic (default; MRGFE_HOST_CONTROL overrides), 0 device, 1 host
@@ -55,17 +48,10 @@ struct NdtSnapshotPort {
 
 class NdtEngine {
    public:
-    NdtEngine(mrgfe_ctx* ctx, const NdtParams& prm) : ctx_(ctx), prm_(prm) {}
+    NdtEngine(mrgfe_ctx* ctx, const NdtParams& prm, const PairBook* book) : ctx_(ctx), prm_(prm), book_(book) {}
     ~NdtEngine();
 
-    void clear();                 // forget targets and pairs (device memory is kept for reuse)
-    void clear_pairs();
-    // clouds: host (strided) or device (packed float4). device clouds are referenced, not copied.
-    int add_target_host(const float* xyzi, size_t n, size_t stride);
-    int add_target_device(const void* d_xyzi, size_t n);
-    int add_pair_host(int target, const float* xyzi, size_t n, size_t stride, const float guess_rowmajor[16]);
-    int add_pair_device(int target, const void* d_xyzi, size_t n, const float guess_rowmajor[16]);
-    int set_guess(int pair, const float guess_rowmajor[16]);
+    void clear();                 // forget the grids: call it when the book's targets are cleared (device memory is kept for reuse)
 
     int build_targets(bool wait = true);  // voxelise every target not yet built; `wait`: return with the stream drained
     int align_all(NdtSnapshotPort* port = nullptr);  // run every pair to completion (port: see NdtSnapshotPort; batches under device control only)
@@ -73,10 +59,11 @@ class NdtEngine {
     int evaluate(int pair, const float T_rowmajor[16], const double p[6], int mode, double* score, double grad[6], double hess[36]);
     int aligned_cloud(int pair, float* out_xyzi_host);  // final_transformation * source
 
-    int n_targets() const { return static_cast<int>(targets_.size()); }
-    int n_pairs() const { return static_cast<int>(pairs_.size()); }
-    const NdtTargetInfo& target(int i) const { return targets_[i]; }
-    const NdtPairInfo&   pair(int i) const { return pairs_[i]; }
+    int n_targets() const { return book_->n_targets(); }
+    int n_pairs() const { return book_->n_pairs(); }
+    // grid of target i (a target added since the last build_targets() has none yet); optimiser of pair i as of the last align_all()
+    const NdtTargetInfo& target(int i) const { static const NdtTargetInfo unbuilt; return static_cast<size_t>(i) < targets_.size() ? targets_[i] : unbuilt; }
+    const NdtController& ctl(int i) const { return ctls_[i]; }
     int read_leaves(int target, int32_t* keys, int32_t* nr_points, double* mean3, double* icov9);
 
     // derivative-kernel accounting of the last align_all(), per kernel variant (mode 0 / 1 / 2): device time from HIP
@@ -107,9 +94,9 @@ class NdtEngine {
    private:
     mrgfe_ctx* ctx_;
     NdtParams  prm_;
-    std::vector<NdtTargetInfo> targets_;
-    std::vector<NdtPairInfo>   pairs_;
-    Arena cloud_arena_;  // host-supplied clouds copied to the device
+    const PairBook* book_;
+    std::vector<NdtTargetInfo> targets_;  // sized from the book by build_targets()
+    std::vector<NdtController> ctls_;     // sized from the book by align_all() / evaluate()
     Arena grid_arena_;   // leaves, lookups, ...
     // packed per-leaf arrays of the built targets (grid_arena_)
     std::vector<NdtGridDev> h_grids_;
@@ -117,7 +104,7 @@ class NdtEngine {
     DevBuf d_ticket_;              // ndt_derivatives_single_kernel's workgroup counter: 0 between launches (the last workgroup clears it)
     bool   ticket_dirty_ = false;  // a round was enqueued whose record has not been seen: the counter is cleared before the next one
     PinBuf h_evals_, h_results_;
-    bool   pairs_dirty_ = true;
+    uint64_t pairs_rev_ = 0;  // the book revision the device pair table was made from (0: none yet)
     bool   force_hash_ = false;
     int    forced_ppt_ = 0;  // MRGFE_PPT tuning hook (0: chosen per launch)
     uint32_t max_nblk_ = 0;
