@@ -413,6 +413,43 @@ int    mrgfe_keyframe_callback(mrgfe_map_store* store, uint64_t key, const mrgfe
                                const float* centres_xyz, int n_centres, float radius_sqr, float* kept_xyzi, size_t* n_kept, float* removed_xyzi,
                                size_t* n_removed);
 
+/* ---- the graph database's keyframe and edge loops in one call each (src/mrg_slam/graph_database.cpp) ---- */
+/* Many keyframe messages at once: the point work of GraphDatabase::add_static_keyframes (:181-182), flush_graph_queue (:294-295, another robot's whole
+ * graph at a rendezvous) and load_graph (:449-461), which unpack one sensor_msgs/PointCloud2 per keyframe in a loop (pcl::fromROSMsg); none of the
+ * three removes other robots' points.  Message i becomes keyframe msgs[i].key; layouts (checked as mrgfe_keyframe_callback checks them) may differ
+ * from message to message.  Known keys follow mrgfe_map_store_add, which is the reference's rule (:173-178, :272-274): a key that is already stored,
+ * or comes a second time inside the call, with the same point count is skipped (added[i] = 0); with another count the call fails with
+ * MRGFE_ERR_STATE; key 0, a bad layout, NULL data or a short payload: MRGFE_ERR_INVALID, naming the message.  The new clouds take ONE block of the
+ * store's arena, the payloads go up behind one another through the staging ring, ONE launch gathers all of them (a tile table in device memory names
+ * every 2048-point tile's message) and the stream is waited for ONCE.  After any failure the store has no new entry, mrgfe_map_store_bytes is
+ * unchanged and `added` (n bytes, may be NULL) is all 0; after success the store has grown by exactly 16 * the points added, and every stored cloud
+ * equals, bit for bit, what mrgfe_keyframe_callback with 0 centres stores for the same message. */
+typedef struct mrgfe_keyframe_msg {
+    uint64_t              key;
+    mrgfe_keyframe_params layout;
+    const void*           data;        /* data_bytes >= (height - 1) * row_step + width * point_step */
+    size_t                data_bytes;
+} mrgfe_keyframe_msg;
+size_t mrgfe_keyframe_msg_size(void); /* sizeof(mrgfe_keyframe_msg) as the library was compiled */
+int    mrgfe_map_store_add_keyframes(mrgfe_map_store* store, int n, const mrgfe_keyframe_msg* msgs, uint8_t* added);
+/* Many graph edges at once: InformationMatrixCalculator::calc_information_matrix (information_matrix_calculator.cpp:14-44, max_range = DBL_MAX as
+ * :24 has it) for every edge of GraphDatabase::flush_keyframe_queue (:139-142, up to max_keyframes_per_update odometry edges per tick) or
+ * insert_loops (:579-581).  Edge e: cloud1 = keyframe key1, cloud2 = keyframe key2, relpose column-major (Isometry3d::matrix()); inf receives 36
+ * doubles per edge (row-major 6x6), fitness (may be NULL) the scores.  use_const_inf_matrix touches no GPU and needs no key to exist (nor a store).
+ * Otherwise a key the store does not hold gives MRGFE_ERR_INVALID, names the key and writes nothing; an empty cloud on either side gives the score
+ * DBL_MAX and whatever mrgfe_inf_matrix_from_fitness makes of it.  The distinct key1 clouds without a usable search grid get theirs from ONE grouped
+ * build (three stream waits for the set, not per cloud), all edges are scored by ONE batch of the fitness passes (one wait), and the matrices come
+ * from mrgfe_inf_matrix_from_fitness on the host.  Scores and matrices are those of mrgfe_map_store_information_matrix edge by edge.
+ * Which grids outlive the call: a grid in the 8-entry cache of mrgfe_map_store_fitness is used where it fits (and counts as used) but the call adds
+ * none to it; the grids it builds are kept as ONE set until the next call that has to build — so insert_loops after flush_keyframe_queue in the same
+ * tick finds the new keyframes' grids, and a call all of whose key1 are in the cache or in that set builds nothing.  Results do not depend on it. */
+typedef struct mrgfe_graph_edge {
+    uint64_t key1, key2;
+    double   relpose[16];
+} mrgfe_graph_edge;
+size_t mrgfe_graph_edge_size(void); /* sizeof(mrgfe_graph_edge) as the library was compiled */
+int    mrgfe_map_store_edges(mrgfe_map_store* store, const mrgfe_inf_params* params, int n_edges, const mrgfe_graph_edge* edges, double* inf, double* fitness);
+
 /* replaces PrefilteringComponent::deskewing (apps/prefiltering_component.cpp:231-292): point i is rotated by the inverse of
  * Quaternionf(1, dt/2 * -w) with dt = scan_period * i / n and w the IMU angular velocity */
 int mrgfe_deskew(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride_bytes, const float ang_v_xyz[3], double scan_period, float* out_xyzi);

@@ -8,5 +8,6 @@ from .registration import BatchMatcher, GicpHip, IcpHip, NdtHip, NodeMatcher, Pc
 from .loop_detector import KeyFrame, LoopDetector  # noqa: F401,E402
 from .odometry import ScanMatchingOdometry  # noqa: F401,E402
 from .keyframes import KeyframeCallback, KeyframeUpdater  # noqa: F401,E402
+from .graph_database import GraphDatabaseEdges  # noqa: F401,E402
 from .prefiltering import PrefilteringComponent  # noqa: F401,E402
 from .floor_detection import FloorDetection, FloorDetectionComponent  # noqa: F401,E402

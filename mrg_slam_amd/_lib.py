@@ -60,6 +60,18 @@ class KeyframeParams(C.Structure):
                 ("off_z", C.c_uint32), ("off_intensity", C.c_int32)]
 
 
+class KeyframeMsg(C.Structure):
+    """struct mrgfe_keyframe_msg: one message of ``mrgfe_map_store_add_keyframes`` (key, layout, payload)."""
+
+    _fields_ = [("key", C.c_uint64), ("layout", KeyframeParams), ("data", C.c_void_p), ("data_bytes", C.c_size_t)]
+
+
+class GraphEdge(C.Structure):
+    """struct mrgfe_graph_edge: one edge of ``mrgfe_map_store_edges`` (relpose column-major, Isometry3d::matrix())."""
+
+    _fields_ = [("key1", C.c_uint64), ("key2", C.c_uint64), ("relpose", C.c_double * 16)]
+
+
 class FloorParams(C.Structure):
     """struct mrgfe_floor_params (the floor_detection_component ROS parameters, apps/floor_detection_component.cpp:55-62, config/mrg_slam.yaml:113-122)."""
 
@@ -179,6 +191,10 @@ SIGNATURES = {
     "mrgfe_keyframe_default_params": (None, [C.POINTER(KeyframeParams)]),
     "mrgfe_keyframe_params_size": (C.c_size_t, []),
     "mrgfe_keyframe_callback": (C.c_int, [_vp, C.c_uint64, C.POINTER(KeyframeParams), _vp, C.c_size_t, _fp, C.c_int, C.c_float, _fp, _szp, _fp, _szp]),
+    "mrgfe_keyframe_msg_size": (C.c_size_t, []),
+    "mrgfe_map_store_add_keyframes": (C.c_int, [_vp, C.c_int, C.POINTER(KeyframeMsg), C.POINTER(C.c_uint8)]),
+    "mrgfe_graph_edge_size": (C.c_size_t, []),
+    "mrgfe_map_store_edges": (C.c_int, [_vp, C.POINTER(InfParams), C.c_int, C.POINTER(GraphEdge), _dp, _dp]),
     "mrgfe_prefilter_default_params": (None, [C.POINTER(PrefilterParams)]),
     "mrgfe_prefilter": (C.c_int, [_vp, C.POINTER(PrefilterParams), _fp, C.c_size_t, C.c_size_t, _fp, C.POINTER(C.c_size_t)]),
     "mrgfe_prefilter_device": (C.c_int, [_vp, C.POINTER(PrefilterParams), _fp, C.c_size_t, C.c_size_t, _vp, C.POINTER(C.c_size_t)]),
@@ -349,6 +365,9 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"libmrgfe.so was built with a mrgfe_matching_status of {L.mrgfe_matching_status_size()} bytes, the binding mirrors {C.sizeof(MatchingStatus)}")
         if hasattr(L, "mrgfe_keyframe_params_size") and L.mrgfe_keyframe_params_size() != C.sizeof(KeyframeParams):
             raise RuntimeError(f"libmrgfe.so was built with a mrgfe_keyframe_params of {L.mrgfe_keyframe_params_size()} bytes, the binding mirrors {C.sizeof(KeyframeParams)}")
+        for fn, mirror in (("mrgfe_keyframe_msg_size", KeyframeMsg), ("mrgfe_graph_edge_size", GraphEdge)):
+            if hasattr(L, fn) and getattr(L, fn)() != C.sizeof(mirror):
+                raise RuntimeError(f"libmrgfe.so was built with a {fn[:-5]} of {getattr(L, fn)()} bytes, the binding mirrors {C.sizeof(mirror)}")
         _lib = L
     return _lib
 

@@ -1039,6 +1039,161 @@ int mrgfe_keyframe_callback(mrgfe_map_store* s, uint64_t key, const mrgfe_keyfra
     });
 }
 
+// ---- the graph database's loops in one call each: many keyframe messages into the store, many edges scored (include/mrgfe.h) -----------------------
+static_assert(sizeof(mrgfe_keyframe_msg) == 56, "mrgfe_keyframe_msg: the layout the bindings mirror");
+static_assert(sizeof(mrgfe_graph_edge) == 144, "mrgfe_graph_edge: the layout the bindings mirror");
+size_t mrgfe_keyframe_msg_size(void) { return sizeof(mrgfe_keyframe_msg); }
+size_t mrgfe_graph_edge_size(void) { return sizeof(mrgfe_graph_edge); }
+
+int mrgfe_map_store_add_keyframes(mrgfe_map_store* s, int n, const mrgfe_keyframe_msg* msgs, uint8_t* added)
+{
+    static const char* fn = "mrgfe_map_store_add_keyframes";
+    return abi_guard(fn, [&]() -> int {
+        if (added && n > 0) std::memset(added, 0, size_t(n));
+        if (!s || n < 0 || (n > 0 && !msgs)) { set_error("%s: NULL argument or a negative count", fn); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(s->ctx);
+        MRGFE_TRY(s->ctx->bind());
+        // 1. every message is checked before anything is allocated or sent
+        struct New { int msg; KeyframeLayout lay; size_t n, raw_bytes, raw_at, cloud_at; };
+        std::vector<New> fresh;
+        std::unordered_map<uint64_t, size_t> in_call;  // keys this call adds -> their point count
+        size_t raw_total = 0, block = 0, points = 0;
+        for (int i = 0; i < n; ++i) {
+            const mrgfe_keyframe_msg& m = msgs[i];
+            const unsigned long long  key = static_cast<unsigned long long>(m.key);
+            if (m.key == 0) { set_error("%s: message %d: key 0", fn, i); return MRGFE_ERR_INVALID; }
+            KeyframeLayout l{m.layout.width, m.layout.height, m.layout.point_step, m.layout.row_step, m.layout.off_x, m.layout.off_y, m.layout.off_z, m.layout.off_intensity};
+            MRGFE_TRY(check_pointcloud2_layout(fn, l.width, l.height, l.point_step, &l.row_step, l.off_x, l.off_y, l.off_z, l.off_intensity));
+            const size_t np = size_t(l.width) * l.height;
+            const size_t raw_bytes = np ? size_t(l.height - 1) * l.row_step + size_t(l.width) * l.point_step : 0;
+            if (np && !m.data) { set_error("%s: message %d (keyframe %llu): NULL data", fn, i, key); return MRGFE_ERR_INVALID; }
+            if (m.data_bytes < raw_bytes) { set_error("%s: message %d (keyframe %llu): the payload has %zu bytes, the layout needs %zu", fn, i, key, m.data_bytes, raw_bytes); return MRGFE_ERR_INVALID; }
+            size_t have = 0;
+            bool   known = false;
+            auto it = s->clouds.find(m.key);
+            if (it != s->clouds.end()) { known = true; have = it->second.n; }
+            else { auto jt = in_call.find(m.key); if (jt != in_call.end()) { known = true; have = jt->second; } }
+            if (known) {
+                if (have == np) continue;  // graph_database.cpp:173-178, :272-274: already in the graph or in the queue
+                set_error("%s: message %d: keyframe %llu is stored with %zu points, not %zu", fn, i, key, have, np);
+                return MRGFE_ERR_STATE;
+            }
+            in_call[m.key] = np;
+            fresh.push_back({i, l, np, raw_bytes, raw_total, block});
+            raw_total += (raw_bytes + 255) & ~size_t(255);
+            block += (np * 16 + 255) & ~size_t(255);  // every cloud starts on a 256-byte line, as the clouds of mrgfe_map_store_add do
+            points += np;
+        }
+        s->clouds.reserve(s->clouds.size() + fresh.size());
+        // 2. one block, the payloads behind one another, one launch, one wait
+        char* base = nullptr;
+        if (points) {
+            mrgfe_ctx* ctx = s->ctx;
+            void* p = nullptr;
+            MRGFE_TRY(s->arena.alloc(block, &p));
+            base = static_cast<char*>(p);
+            auto run = [&]() -> int {
+                MRGFE_TRY(ctx->up_raw.ensure(raw_total));  // (grown BEFORE the first copy: stream order keeps the earlier readers of the old buffer safe)
+                std::vector<KeyframeGatherItem> items;
+                for (const New& f : fresh) {
+                    if (!f.n) continue;
+                    char* d_raw = ctx->up_raw.as<char>() + f.raw_at;
+                    MRGFE_TRY(upload_raw_records_to(ctx, msgs[f.msg].data, f.raw_bytes, d_raw));
+                    items.push_back({d_raw, f.lay, reinterpret_cast<float4*>(base + f.cloud_at)});
+                }
+                MRGFE_TRY(keyframe_gather_many_device(ctx, items.data(), items.size()));
+                MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the only wait
+                return MRGFE_OK;
+            };
+            const int rc = run();
+            if (rc != MRGFE_OK) {
+                (void)hipStreamSynchronize(ctx->stream);  // nothing is in flight when the block goes back
+                s->arena.shrink_last(p, block, 0);
+                return rc;
+            }
+        }
+        for (const New& f : fresh) {
+            s->clouds[msgs[f.msg].key] = {f.n ? reinterpret_cast<const float4*>(base + f.cloud_at) : nullptr, static_cast<uint32_t>(f.n)};
+            s->bytes += f.n * 16;
+            if (added) added[f.msg] = 1;
+        }
+        return MRGFE_OK;
+    });
+}
+
+int mrgfe_map_store_edges(mrgfe_map_store* s, const mrgfe_inf_params* p, int n_edges, const mrgfe_graph_edge* edges, double* inf, double* fitness)
+{
+    static const char* fn = "mrgfe_map_store_edges";
+    return abi_guard(fn, [&]() -> int {
+        if (!p || n_edges < 0 || (n_edges > 0 && (!edges || !inf))) { set_error("%s: NULL argument or a negative count", fn); return MRGFE_ERR_INVALID; }
+        const size_t E = static_cast<size_t>(n_edges);
+        std::vector<double> fit(E, 0.0), mats(36 * E);
+        if (!p->use_const_inf_matrix && E) {
+            if (!s) { set_error("%s: NULL store", fn); return MRGFE_ERR_INVALID; }
+            MRGFE_LOCK(s->ctx);
+            MRGFE_TRY(s->ctx->bind());
+            struct Side { const float4* p; uint32_t n; };
+            std::vector<Side> c1(E), c2(E);
+            for (size_t e = 0; e < E; ++e) {
+                auto i1 = s->clouds.find(edges[e].key1), i2 = s->clouds.find(edges[e].key2);
+                if (i1 == s->clouds.end() || i2 == s->clouds.end()) {
+                    set_error("%s: edge %zu: keyframe %llu is not in the store", fn, e, static_cast<unsigned long long>(i1 == s->clouds.end() ? edges[e].key1 : edges[e].key2));
+                    return MRGFE_ERR_INVALID;
+                }
+                c1[e] = {i1->second.p, i1->second.n};
+                c2[e] = {i2->second.p, i2->second.n};
+            }
+            // the grid of every distinct key1 that has points on both sides of one of its edges: the single calls' cache, the last set, or a new set
+            std::unordered_map<uint64_t, const NnGrid*> grid_of;
+            std::vector<uint64_t>      set_keys;  // key1s the cache does not hold, in order of appearance
+            std::vector<const float4*> set_p;
+            std::vector<uint32_t>      set_n;
+            for (size_t e = 0; e < E; ++e) {
+                const uint64_t k = edges[e].key1;
+                if (c1[e].n == 0 || c2[e].n == 0 || grid_of.count(k)) continue;
+                const NnGrid* g = nullptr;
+                for (auto& c : s->grids)
+                    if (c->key == k) { g = &c->grid; c->tick = ++s->tick; }
+                grid_of[k] = g;
+                if (!g) { set_keys.push_back(k); set_p.push_back(c1[e].p); set_n.push_back(c1[e].n); }
+            }
+            bool build = false;
+            for (uint64_t k : set_keys) build = build || std::find(s->edge_keys.begin(), s->edge_keys.end(), k) == s->edge_keys.end();
+            if (build) {
+                s->edge_keys.clear();  // (a failed build leaves no view behind)
+                s->edge_views.clear();
+                s->edge_views.resize(set_keys.size());
+                std::vector<NnGrid*> out(set_keys.size());
+                for (size_t m = 0; m < out.size(); ++m) out[m] = &s->edge_views[m];
+                MRGFE_TRY(s->edge_set.build(s->ctx, set_p.data(), set_n.data(), static_cast<int>(set_keys.size()), 1.0f, NnGrid::kCrowding1nn, 1, out.data()));  // as mrgfe_map_store_fitness builds one
+                s->edge_keys = set_keys;
+            }
+            for (uint64_t k : set_keys) grid_of[k] = &s->edge_views[static_cast<size_t>(std::find(s->edge_keys.begin(), s->edge_keys.end(), k) - s->edge_keys.begin())];
+            std::vector<NnFitnessJob> jobs;
+            std::vector<size_t>       job_edge;
+            for (size_t e = 0; e < E; ++e) {
+                fit[e] = DBL_MAX;  // an empty cloud on either side (NnGrid::fitness: ... or no finite point in cloud1)
+                if (c1[e].n == 0 || c2[e].n == 0) continue;
+                const NnGrid* g = grid_of[edges[e].key1];
+                if (g->dev().n == 0) continue;
+                float T[16];  // relpose.cast<float>(), row-major
+                for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T[r * 4 + c] = static_cast<float>(edges[e].relpose[c * 4 + r]);
+                jobs.push_back(g->make_fitness_job(c2[e].p, c2[e].n, T));
+                job_edge.push_back(e);
+            }
+            if (!jobs.empty()) {
+                std::vector<double> out(jobs.size());
+                MRGFE_TRY(nn_fitness_batch(s->ctx, jobs.data(), jobs.size(), DBL_MAX, out.data()));
+                for (size_t j = 0; j < jobs.size(); ++j) fit[job_edge[j]] = out[j];
+            }
+        }
+        for (size_t e = 0; e < E; ++e) MRGFE_TRY(mrgfe_inf_matrix_from_fitness(p, fit[e], &mats[36 * e]));
+        if (E) std::memcpy(inf, mats.data(), sizeof(double) * 36 * E);
+        if (fitness && E) std::memcpy(fitness, fit.data(), sizeof(double) * E);
+        return MRGFE_OK;
+    });
+}
+
 int mrgfe_remove_points_near(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, const float* centres, int n_centres, float radius_sqr, float* kept, size_t* n_kept,
                              float* removed, size_t* n_removed)
 {

@@ -100,4 +100,8 @@ struct mrgfe_map_store {
     std::vector<std::unique_ptr<CachedGrid>> grids;
     uint64_t tick = 0;
     size_t   max_grids = 8;
+    // mrgfe_map_store_edges: the grids its last grouped build made (views into the set's buffers, valid until the set is built again) and their keys
+    mrgfe::NnGridSet           edge_set;
+    std::vector<mrgfe::NnGrid> edge_views;
+    std::vector<uint64_t>      edge_keys;
 };

@@ -8,6 +8,8 @@ int launch_gather_points(mrgfe_ctx* ctx, const void* d_raw, float4* d_dst, size_
                          int32_t oi);
 // raw record bytes -> the context's raw buffer (*d_raw), one stream-ordered copy through the pinned staging ring
 int upload_raw_records(mrgfe_ctx* ctx, const void* raw, size_t raw_bytes, const void** d_raw);
+// the same copy to a place of the caller's (several messages behind one another in one device buffer: each takes the ring's next slot)
+int upload_raw_records_to(mrgfe_ctx* ctx, const void* raw, size_t raw_bytes, void* d_dst);
 // MRGFE_OK, or MRGFE_ERR_INVALID with the message set; a row_step of 0 becomes width * point_step
 int check_pointcloud2_layout(const char* fn, uint32_t width, uint32_t height, uint32_t point_step, uint32_t* row_step, uint32_t off_x, uint32_t off_y, uint32_t off_z,
                              int32_t off_intensity);

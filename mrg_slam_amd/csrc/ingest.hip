@@ -32,8 +32,8 @@ int launch_gather_points(mrgfe_ctx* ctx, const void* d_raw, float4* d_dst, size_
     return MRGFE_OK;
 }
 
-// raw host bytes -> the context's raw record buffer: one contiguous copy through the staging ring, stream-ordered (`raw` is free on return)
-int upload_raw_records(mrgfe_ctx* ctx, const void* raw, size_t raw_bytes, const void** d_raw)
+// raw host bytes -> d_dst: one contiguous copy through the staging ring, stream-ordered (`raw` is free on return)
+int upload_raw_records_to(mrgfe_ctx* ctx, const void* raw, size_t raw_bytes, void* d_dst)
 {
     const int slot = ctx->up_next;
     ctx->up_next ^= 1;
@@ -42,11 +42,18 @@ int upload_raw_records(mrgfe_ctx* ctx, const void* raw, size_t raw_bytes, const 
     PinBuf& pb = ctx->up_pin[slot];
     MRGFE_TRY(pb.ensure(raw_bytes));
     std::memcpy(pb.p, raw, raw_bytes);
-    // the raw device buffer is reused by the next upload of records: stream order (copy k+1 after the kernel that reads copy k) keeps that safe
-    MRGFE_TRY(ctx->up_raw.ensure(raw_bytes));
-    MRGFE_HIP_CHECK(hipMemcpyAsync(ctx->up_raw.p, pb.p, raw_bytes, hipMemcpyHostToDevice, ctx->stream));
+    MRGFE_HIP_CHECK(hipMemcpyAsync(d_dst, pb.p, raw_bytes, hipMemcpyHostToDevice, ctx->stream));
     MRGFE_HIP_CHECK(hipEventRecord(ctx->up_ev[slot], ctx->stream));
     ctx->up_busy[slot] = true;
+    return MRGFE_OK;
+}
+
+// raw host bytes -> the context's raw record buffer
+int upload_raw_records(mrgfe_ctx* ctx, const void* raw, size_t raw_bytes, const void** d_raw)
+{
+    // the raw device buffer is reused by the next upload of records: stream order (copy k+1 after the kernel that reads copy k) keeps that safe
+    MRGFE_TRY(ctx->up_raw.ensure(raw_bytes));
+    MRGFE_TRY(upload_raw_records_to(ctx, raw, raw_bytes, ctx->up_raw.p));
     *d_raw = ctx->up_raw.p;
     return MRGFE_OK;
 }

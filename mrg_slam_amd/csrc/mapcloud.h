@@ -22,6 +22,10 @@ int remove_points_near_device(mrgfe_ctx* ctx, const float4* d_in, size_t n, cons
 struct KeyframeLayout { uint32_t width, height, point_step, row_step, off_x, off_y, off_z; int32_t off_intensity; };
 // no other robot: the records are gathered straight into d_cloud (width * height packed points); one launch, no wait
 int keyframe_gather_device(mrgfe_ctx* ctx, const void* d_raw, const KeyframeLayout& lay, float4* d_cloud);
+// the same gather for MANY messages in ONE launch (mrgfe_map_store_add_keyframes): a tile table in device memory (scratch[0], staged through the descriptor
+// ring) names every 2048-point tile's message — raw base, layout, first point, destination — so keyframes of any size and layout share the launch; no wait
+struct KeyframeGatherItem { const void* d_raw; KeyframeLayout lay; float4* d_cloud; };
+int keyframe_gather_many_device(mrgfe_ctx* ctx, const KeyframeGatherItem* items, size_t count);
 // with centres (1 <= n_centres <= 64): two launches — records -> packed cloud + keep flags + tile counts, then the stable two-way partition into
 // d_kept / d_removed (room for width * height points each; d_removed may be nullptr) — and ONE wait for the two totals
 int keyframe_split_device(mrgfe_ctx* ctx, const void* d_raw, const KeyframeLayout& lay, const float* centres_xyz, int n_centres, float radius_sqr, float4* d_kept,

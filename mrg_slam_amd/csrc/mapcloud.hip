@@ -406,6 +406,55 @@ int keyframe_gather_device(mrgfe_ctx* ctx, const void* d_raw, const KeyframeLayo
     return MRGFE_OK;
 }
 
+// The gather of keyframe_head_kernel<false> for many messages at once (GraphDatabase::add_static_keyframes / flush_graph_queue / load_graph hand over
+// whole lists of PointCloud2 clouds: src/mrg_slam/graph_database.cpp:181-182, 294-295, 449-461).  One workgroup per 2048-point tile as there; what the
+// head kernel takes as kernel arguments comes from the tile's record instead — a workgroup-uniform 64-byte read (scalar loads), then the same per-point
+// body.  A 33k-point keyframe alone is 17 workgroups on 256 compute units; ten of them in one launch are 170.
+struct KeyframeTile {
+    const uint8_t* raw;    // the message's records
+    float4*        out;    // the message's cloud
+    uint32_t       first;  // the tile's first point within the message
+    uint32_t       n;      // points of the message
+    uint32_t       width, row_step, point_step, ox, oy, oz;
+    int32_t        oi;
+    uint32_t       pad[3];
+};
+static_assert(sizeof(KeyframeTile) == 64, "KeyframeTile: one 64-byte record per tile");
+__global__ __launch_bounds__(256) void keyframe_gather_many_kernel(const KeyframeTile* __restrict__ tiles)
+{
+    const KeyframeTile t = tiles[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < kTile / 256; ++k) {
+        const uint32_t i = t.first + k * 256 + threadIdx.x;
+        if (i < t.n) t.out[i] = load_point_record(t.raw, i, t.width, t.row_step, t.point_step, t.ox, t.oy, t.oz, t.oi);
+    }
+}
+
+int keyframe_gather_many_device(mrgfe_ctx* ctx, const KeyframeGatherItem* items, size_t count)
+{
+    std::vector<KeyframeTile> tiles;
+    for (size_t m = 0; m < count; ++m) {
+        const KeyframeHeadArgs a = keyframe_head_args(items[m].d_raw, items[m].lay, items[m].d_cloud);
+        KeyframeTile t;
+        std::memset(&t, 0, sizeof(t));
+        t.raw = a.raw; t.out = a.out; t.n = a.n;
+        t.width = a.width; t.row_step = a.row_step; t.point_step = a.point_step;
+        t.ox = a.ox; t.oy = a.oy; t.oz = a.oz; t.oi = a.oi;
+        for (uint64_t first = 0; first < a.n; first += kTile) {  // (an empty message has no tile)
+            t.first = static_cast<uint32_t>(first);
+            tiles.push_back(t);
+        }
+    }
+    if (tiles.empty()) return MRGFE_OK;
+    if (tiles.size() > 0x7fffffffu) { set_error("keyframe gather: %zu tiles in one launch", tiles.size()); return MRGFE_ERR_INVALID; }
+    DevBuf& dtab = ctx->scratch[0];
+    MRGFE_TRY(dtab.ensure(tiles.size() * sizeof(KeyframeTile)));
+    MRGFE_TRY(ctx->stage_h2d(dtab.p, tiles.data(), tiles.size() * sizeof(KeyframeTile), ctx->stream));
+    hipLaunchKernelGGL(keyframe_gather_many_kernel, dim3(static_cast<uint32_t>(tiles.size())), dim3(256), 0, ctx->stream, dtab.as<KeyframeTile>());
+    MRGFE_HIP_CHECK(hipGetLastError());
+    return MRGFE_OK;
+}
+
 int keyframe_split_device(mrgfe_ctx* ctx, const void* d_raw, const KeyframeLayout& lay, const float* centres, int K, float radius_sqr, float4* d_kept, size_t* n_kept,
                           float4* d_removed, size_t* n_removed)
 {

@@ -156,6 +156,7 @@ class InformationMatrixCalculator:
                 raise KeyError(k)
             setattr(self._p, k, int(bool(v)) if k == "use_const_inf_matrix" else float(v))
         self.last_fitness_score = None
+        self.last_fitness_scores = None
 
     calc_fitness_score = staticmethod(calc_fitness_score)
 
@@ -185,6 +186,16 @@ class InformationMatrixCalculator:
         dp = C.POINTER(C.c_double)
         check(lib().mrgfe_map_store_information_matrix(store._h, C.byref(self._p), int(key1), int(key2), T.ctypes.data_as(dp), inf.ctypes.data_as(dp), C.byref(fit)))
         self.last_fitness_score = fit.value
+        return inf
+
+
+    def calc_information_matrices_keyed(self, store, edges) -> np.ndarray:
+        """The same for a list of edges ``(key1, key2, relpose)`` in ONE call (``mrgfe_map_store_edges``): returns ``(n, 6, 6)``; the scores are in
+        ``last_fitness_scores`` (and the last of them in ``last_fitness_score``)."""
+        inf, fit = store.information_matrices(self._p, edges)
+        self.last_fitness_scores = fit
+        if len(fit):
+            self.last_fitness_score = float(fit[-1])
         return inf
 
 

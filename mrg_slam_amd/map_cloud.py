@@ -13,7 +13,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import Context, KeyframeParams, MrgfeError, check, default_context, lib
+from ._lib import Context, GraphEdge, KeyframeMsg, KeyframeParams, MrgfeError, check, default_context, lib
 from .filters import _cloud
 from .io import pointcloud2_from_xyzi
 
@@ -89,6 +89,42 @@ class MapCloudStore:
         if want_removed and removed is None:
             removed = np.empty((0, 4), dtype=np.float32)  # (no other robot: nothing was removed)
         return (kept[: nk.value] if kept is not None else None), (removed[: nr.value] if removed is not None else None)
+
+    def add_keyframes(self, items) -> np.ndarray:
+        """``mrgfe_map_store_add_keyframes``: the point work of GraphDatabase::add_static_keyframes / flush_graph_queue / load_graph
+        (src/mrg_slam/graph_database.cpp:181-182, 294-295, 449-461) for a whole list of keyframe messages — one arena block, the payloads up behind
+        one another, ONE launch, ONE wait.  ``items``: ``(key, payload_or_msg)`` pairs, each as :meth:`keyframe_callback` takes it; layouts may
+        differ.  Returns the added flags (uint8 [n]): 0 for a key that was already stored, or came earlier in the list, with the same point count."""
+        items = list(items)
+        n = len(items)
+        msgs = (KeyframeMsg * max(n, 1))()
+        keep = []  # the payload buffers stay alive until the call has returned
+        for i, (key, payload_or_msg) in enumerate(items):
+            msg = payload_or_msg if isinstance(payload_or_msg, dict) else pointcloud2_from_xyzi(payload_or_msg)
+            buf = np.frombuffer(msg["data"], dtype=np.uint8)
+            keep.append(buf)
+            msgs[i].key = int(key)
+            msgs[i].layout = keyframe_params(msg)
+            msgs[i].data = buf.ctypes.data if buf.nbytes else None
+            msgs[i].data_bytes = buf.nbytes
+        added = np.zeros(n, dtype=np.uint8)
+        check(lib().mrgfe_map_store_add_keyframes(self._h, n, msgs, added.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return added
+
+    def information_matrices(self, params, edges):
+        """``mrgfe_map_store_edges``: InformationMatrixCalculator::calc_information_matrix for every edge ``(key1, key2, relpose)`` of a list (the
+        loops of GraphDatabase::flush_keyframe_queue :139-142 and insert_loops :579-581) — one grouped grid build for the key1 clouds that have
+        none, one batch of the fitness passes.  ``params``: a ``_lib.InfParams``.  Returns ``(inf [n, 6, 6], fitness [n])``."""
+        edges = list(edges)
+        n = len(edges)
+        rec = (GraphEdge * max(n, 1))()
+        for i, (key1, key2, relpose) in enumerate(edges):
+            rec[i].key1, rec[i].key2 = int(key1), int(key2)
+            rec[i].relpose[:] = np.asarray(relpose, dtype=np.float64).T.reshape(16).tolist()  # column-major
+        inf, fit = np.zeros((n, 6, 6)), np.zeros(n)
+        dp = C.POINTER(C.c_double)
+        check(lib().mrgfe_map_store_edges(self._h, C.byref(params), n, rec, inf.ctypes.data_as(dp), fit.ctypes.data_as(dp)))
+        return inf, fit
 
     def has(self, key: int):
         n = C.c_size_t(0)
