@@ -575,7 +575,7 @@ int  mrgfe_batch_fitness_stats(const mrgfe_batch* b, double out[11]);
  * being the least fitness in the group (> score_cap), and the result is identical to the full path's everywhere else.
  * fitness_max_range: as mrgfe_batch_align, >= 0 (else MRGFE_ERR_INVALID; so is a group id outside [-1, n_groups)).  With a finite range a pair
  * is pruned only when its counted point set is already certain.  One extra host wait per call.  No early fitness pass in this mode.
- * mrgfe_batch_align_async and mrgfe_node_* have no selection mode. */
+ * The asynchronous form is mrgfe_batch_align_best_async, the node's mrgfe_node_align_best (below). */
 enum mrgfe_fit_state { MRGFE_FIT_EXACT = 0, MRGFE_FIT_PRUNED = 1, MRGFE_FIT_ABOVE_CAP = 2, MRGFE_FIT_SKIPPED = 3 };
 int  mrgfe_batch_align_best(mrgfe_batch* b, double fitness_max_range, double score_cap, const int32_t* group /* n_pairs */, int n_groups,
                             mrgfe_pair_result* results /* n_pairs */, int32_t* fit_state /* n_pairs, nullable */, int32_t* best /* n_groups */,
@@ -583,6 +583,14 @@ int  mrgfe_batch_align_best(mrgfe_batch* b, double fitness_max_range, double sco
 /* the last mrgfe_batch_align_best: out[0..3] = pairs EXACT / PRUNED / ABOVE_CAP / SKIPPED, out[4] / out[5] = queries left to the sweep / the
  * pyramid walk after the selection, out[6] = host ms of the bound stage (block, seed, bound sums, selection), out[7] = of the contender stage */
 int  mrgfe_batch_select_stats(const mrgfe_batch* b, double out[8]);
+/* mrgfe_batch_align_best on the batch's worker thread, as mrgfe_batch_align_async runs mrgfe_batch_align: returns once the worker holds the batch's
+ * context, mrgfe_batch_wait returns the align's status.  The arguments are checked in the calling thread, before anything is posted: the codes and texts
+ * of mrgfe_batch_align_best, returned by this call.  `group` is copied here; results, fit_state (nullable), best and best_score must stay valid until
+ * mrgfe_batch_wait has returned, which leaves in them what the synchronous call would, bit for bit.  One align in flight per batch: a second _async of
+ * either kind before _wait is MRGFE_ERR_STATE and leaves the running align and its outputs alone. */
+int  mrgfe_batch_align_best_async(mrgfe_batch* b, double fitness_max_range, double score_cap, const int32_t* group /* n_pairs */, int n_groups,
+                                  mrgfe_pair_result* results /* n_pairs */, int32_t* fit_state /* n_pairs, nullable */, int32_t* best /* n_groups */,
+                                  double* best_score /* n_groups */);
 
 /* ---- the same batch over the GPUs of one node ---------------------------------------------------------------------------
  * LoopDetector::matching runs in ONE host process per robot (src/mrg_slam/loop_detector.cpp:104,126-145 under mrg_slam_component's main
@@ -612,7 +620,27 @@ int    mrgfe_node_add_pair(mrgfe_node* node, int target_index, const float* src_
 int    mrgfe_node_add_pair_keyed(mrgfe_node* node, int target_index, uint64_t cloud_key, const float* src_xyzi, size_t n, size_t stride_bytes, const float guess[16]);
 int    mrgfe_node_num_pairs(const mrgfe_node* node);
 int    mrgfe_node_align(mrgfe_node* node, double fitness_max_range, mrgfe_pair_result* results /* n_pairs, pair_id = index in the list */);
-/* block of member `member` in the last mrgfe_node_align; how its records were gathered (0 host memory, 1 RCCL all-gather) */
+/* mrgfe_batch_align_best over the node: the records (pose fields; fitness exact, a certified bound or DBL_MAX), fit_state, best[g] — an index into the
+ * node's pair list —, best_score[g] and the intervals are those of mrgfe_batch_align_best on ONE batch holding the whole list, bit for bit, for any
+ * member count; score_cap behaves as there; pair_id is the index in the list; the blocks are those of mrgfe_node_align.  A group is the candidates of one
+ * new keyframe and regularly straddles a block boundary, where a member holding only its wrong candidates could prune none of them; so the selection
+ * — a pure function of per-pair values — is taken ONCE for the whole list, between two stages that every member runs on its own block:
+ *   1. every member aligns its block and computes the interval of each of its pairs (block pass, seed, bound sums: one host wait per member);
+ *   2. the calling thread prunes over the whole list;
+ *   3. every member runs the exact passes for the contenders of its block (a second host wait); the records are gathered as in mrgfe_node_align.
+ * Arguments are checked before any member runs: NULL node / results / group (with pairs) / best or best_score (with n_groups > 0), fitness_max_range
+ * not >= 0, a NaN score_cap, a group id outside [-1, n_groups): MRGFE_ERR_INVALID.  A member that fails in either stage makes the call return its code
+ * with the member named in mrgfe_last_error(), as mrgfe_node_align does; the members whose first stage had succeeded give their stage up first (their
+ * streams are waited for), so no kernel of the call is in flight and no caller buffer is being read when the call returns.  The node stays usable.
+ * With no pairs: MRGFE_OK, best[g] = -1 and best_score[g] = DBL_MAX for every g, nothing else written. */
+int    mrgfe_node_align_best(mrgfe_node* node, double fitness_max_range, double score_cap, const int32_t* group /* n_pairs */, int n_groups,
+                             mrgfe_pair_result* results /* n_pairs */, int32_t* fit_state /* n_pairs, nullable */, int32_t* best /* n_groups */,
+                             double* best_score /* n_groups */);
+/* the last mrgfe_node_align_best, in the layout of mrgfe_batch_select_stats: out[0..5] the members' counts added up, out[6] / out[7] the largest
+ * member's host ms of the bound stage (which ends when the second stage reaches that member: the wait for the slowest member and the selection are
+ * in it) and of the contender stage */
+int    mrgfe_node_select_stats(const mrgfe_node* node, double out[8]);
+/* block of member `member` in the last mrgfe_node_align / mrgfe_node_align_best; how its records were gathered (0 host memory, 1 RCCL all-gather) */
 int    mrgfe_node_shard(const mrgfe_node* node, int member, int* first_pair, int* n_pairs);
 int    mrgfe_node_last_gather(const mrgfe_node* node);
 int    mrgfe_node_forget(mrgfe_node* node, uint64_t cloud_key); /* drops a key from every member's stores (0: all) */

@@ -119,6 +119,9 @@ int  mrgfe_dbg_icp_ctl_final(const mrgfe_dbg_icp_ctl* h, float T[16], int* conve
  * pair's counted point set was not certain at the selection, so no interval; DBL_MAX / DBL_MAX: no job — not converged or an empty cloud).
  * MRGFE_ERR_STATE when the last align was not an align_best. */
 int mrgfe_dbg_batch_fit_bounds(const mrgfe_batch* b, double* lower, double* upper);
+/* the same for the node's pair list after mrgfe_node_align_best (n_pairs entries each, in list order): the intervals of ONE batch holding the whole
+ * list, bit for bit.  MRGFE_ERR_STATE when the last align of the node was not an align_best (or failed). */
+int mrgfe_dbg_node_fit_bounds(const mrgfe_node* node, double* lower, double* upper);
 /* the product's host selection on given intervals, no GPU needed: state[i] = enum mrgfe_fit_state of every pair (group[i] -1 or in [0, n_groups),
  * else MRGFE_ERR_INVALID).  A candidate without an upper bound passes upper = +inf. */
 int mrgfe_dbg_select_prune(int n_pairs, const double* lower, const double* upper, const int32_t* converged, const int32_t* group, int n_groups, double score_cap,

@@ -253,6 +253,7 @@ SIGNATURES = {
     "mrgfe_batch_fitness_stats": (C.c_int, [_vp, _dp]),
     "mrgfe_batch_align_best": (C.c_int, [_vp, C.c_double, C.c_double, _ip, C.c_int, C.POINTER(PairResult), _ip, _ip, _dp]),
     "mrgfe_batch_select_stats": (C.c_int, [_vp, _dp]),
+    "mrgfe_batch_align_best_async": (C.c_int, [_vp, C.c_double, C.c_double, _ip, C.c_int, C.POINTER(PairResult), _ip, _ip, _dp]),
     "mrgfe_batch_kernel_stats": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_int64), _dp]),
     "mrgfe_reg_kernel_stats": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_int64), _dp]),
     "mrgfe_batch_pair_counts": (C.c_int, [_vp, C.c_int, _dp, _dp]),
@@ -267,6 +268,8 @@ SIGNATURES = {
     "mrgfe_node_add_pair_keyed": (C.c_int, [_vp, C.c_int, C.c_uint64, _fp, C.c_size_t, C.c_size_t, _fp]),
     "mrgfe_node_num_pairs": (C.c_int, [_vp]),
     "mrgfe_node_align": (C.c_int, [_vp, C.c_double, C.POINTER(PairResult)]),
+    "mrgfe_node_align_best": (C.c_int, [_vp, C.c_double, C.c_double, _ip, C.c_int, C.POINTER(PairResult), _ip, _ip, _dp]),
+    "mrgfe_node_select_stats": (C.c_int, [_vp, _dp]),
     "mrgfe_node_shard": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mrgfe_node_last_gather": (C.c_int, [_vp]),
     "mrgfe_node_forget": (C.c_int, [_vp, C.c_uint64]),
@@ -308,6 +311,7 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_icp_ctl_result": (C.c_int, [_vp, _dp, C.POINTER(C.c_int), _fp]),
     "mrgfe_dbg_icp_ctl_final": (C.c_int, [_vp, _fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mrgfe_dbg_batch_fit_bounds": (C.c_int, [_vp, _dp, _dp]),
+    "mrgfe_dbg_node_fit_bounds": (C.c_int, [_vp, _dp, _dp]),
     "mrgfe_dbg_select_prune": (C.c_int, [C.c_int, _dp, _dp, _ip, _ip, C.c_int, C.c_double, _ip]),
 }
 # ... and its fault injectors and their allocation count, which exist only in the -DMRGFE_TESTING build (libmrgfe_testing.so: tests/faultinject/ runs under MRGFE_LIB=that file)

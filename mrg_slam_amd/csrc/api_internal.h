@@ -87,6 +87,20 @@ inline bool keeps_covariances(const mrgfe_reg_params& p) { return !is_ndt(p.meth
 
 }  // namespace mrgfe
 
+// mrgfe_batch_align_best in two stages (batch.cpp), for a caller that takes the selection between them over more pairs than this batch holds (a node:
+// node.cpp).  Arguments are not checked here (max_range >= 0; group: n_pairs entries of -1 or a group id).
+//   batch_align_bounds: the align, the records, the fitness grids and jobs, and the bound stage of the selection.  results[i]: the record with
+//     fitness DBL_MAX; lo[i] / hi[i]: the pair's certified interval (0 / +inf: none; DBL_MAX / DBL_MAX: no job — an empty cloud, or grouped and not
+//     converged).  On success the selection stays PENDING in the batch: until batch_align_finish or batch_align_abandon nothing else may run on the
+//     batch's context (FitSelectRun, nn_grid.h).  On failure nothing is pending and the caller's clouds have been given back.
+//   batch_align_finish: state[i] per pair (enum mrgfe_fit_state, as fit_select_prune decides) -> the contender passes; fills results[i].fitness
+//     (exact, the lower bound, or DBL_MAX), mrgfe_batch_select_stats and mrgfe_batch_timing.  MRGFE_ERR_STATE when nothing is pending.
+//   batch_align_abandon: waits for the batch's stream and side stream and drops the pending selection: no kernel of the call is in flight and no
+//     caller buffer is read any more when it returns.
+int batch_align_bounds(mrgfe_batch* b, double max_range, const int32_t* group, mrgfe_pair_result* results, double* lo, double* hi);
+int batch_align_finish(mrgfe_batch* b, const int32_t* state, mrgfe_pair_result* results);
+int batch_align_abandon(mrgfe_batch* b);
+
 // map store: keyframe clouds resident in HBM (include/mrgfe.h); its entry points are in api.cpp, a batch takes targets and pairs out of it
 struct mrgfe_map_store {
     mrgfe_ctx* ctx = nullptr;

@@ -51,6 +51,14 @@ struct mrgfe_batch {
     FitStats   fit_total;             // getFitnessScore passes of the last align(), all waves added up
     FitSelectStats select_stats;      // the last mrgfe_batch_align_best
     std::vector<double> fit_lo, fit_hi;  // per pair: the fitness interval of the last mrgfe_batch_align_best (mrgfe_dbg_batch_fit_bounds)
+    // batch_align_bounds .. batch_align_finish: the selection between its two stages.  While `run` is pending nothing else may use the batch's context
+    // (FitSelectRun, nn_grid.h): both stages of mrgfe_batch_align_best run under one hold of the context lock, and a node member's batch is reached
+    // through its node alone.
+    struct Select {
+        FitSelectRun     run;
+        std::vector<int> job_pair;  // the pair of every fitness job of the run
+        std::chrono::steady_clock::time_point t_start;  // mrgfe_batch_timing: the align that ends with the second stage
+    } select;
     std::unique_ptr<NdtSnapshotPort> port;  // early fitness passes (mrgfe_batch_align)
     Event      uploads_done;  // recorded on ctx->stream before helper streams read the batch's clouds (upload_cloud is stream-ordered only)
     uint64_t epoch = 1, tick = 0;
@@ -70,6 +78,13 @@ struct mrgfe_batch {
         bool   quit = false;
         double fitness_max_range = -1.0;
         mrgfe_pair_result* results = nullptr;
+        // mrgfe_batch_align_best_async: the selection arguments (`group` copied at the call), else best = false
+        bool   best = false;
+        double score_cap = DBL_MAX;
+        std::vector<int32_t> group;
+        int    n_groups = 0;
+        int32_t *fit_state = nullptr, *best_out = nullptr;
+        double*  best_score = nullptr;
         int    status = MRGFE_OK;
         std::string error;
     };
@@ -133,7 +148,10 @@ static void batch_async_main(mrgfe_batch* b)
             }
             a.cv.notify_all();
             // (an exception becomes an error code for the waiter, never std::terminate)
-            st = abi_guard("mrgfe_batch_align_async", [&] { return mrgfe_batch_align(b, a.fitness_max_range, a.results); });
+            st = abi_guard("mrgfe_batch_align_async", [&] {
+                if (!a.best) return mrgfe_batch_align(b, a.fitness_max_range, a.results);
+                return mrgfe_batch_align_best(b, a.fitness_max_range, a.score_cap, a.group.data(), a.n_groups, a.results, a.fit_state, a.best_out, a.best_score);
+            });
             if (st != MRGFE_OK) err = mrgfe_last_error();
         }
         {
@@ -146,25 +164,71 @@ static void batch_async_main(mrgfe_batch* b)
     }
 }
 
+// Hand an align to the batch's worker (started on first use): `fill` writes the arguments into the idle Async record.  Returns once the worker holds the
+// context lock, so later calls on this batch queue up behind the align.
+extern "C++" template <class Fill>
+static int batch_post_async(mrgfe_batch* b, const char* fn, Fill fill)
+{
+    if (!b->async) {
+        b->async.reset(new (std::nothrow) mrgfe_batch::Async());
+        if (!b->async) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+        const int st = abi_guard(fn, [&] { b->async->th = std::thread(batch_async_main, b); return MRGFE_OK; });
+        if (st != MRGFE_OK) { b->async.reset(); return st; }
+    }
+    mrgfe_batch::Async& a = *b->async;
+    std::unique_lock<std::mutex> lk(a.mu);
+    if (a.state != 0) { set_error("%s: an align of this batch is %s: call mrgfe_batch_wait first", fn, a.state == 3 ? "finished and not yet waited for" : "in flight"); return MRGFE_ERR_STATE; }
+    fill(a);
+    a.state = 1;
+    a.cv.notify_all();
+    a.cv.wait(lk, [&] { return a.state >= 2; });  // the worker holds the context lock now: later calls on this batch queue up behind the align
+    return MRGFE_OK;
+}
+
 int mrgfe_batch_align_async(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results)
 {
     return abi_guard("mrgfe_batch_align_async", [&]() -> int {
         if (!b || !results) { set_error("mrgfe_batch_align_async: NULL argument"); return MRGFE_ERR_INVALID; }
-        if (!b->async) {
-            b->async.reset(new (std::nothrow) mrgfe_batch::Async());
-            if (!b->async) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-            const int st = abi_guard("mrgfe_batch_align_async", [&] { b->async->th = std::thread(batch_async_main, b); return MRGFE_OK; });
-            if (st != MRGFE_OK) { b->async.reset(); return st; }
+        return batch_post_async(b, "mrgfe_batch_align_async", [&](mrgfe_batch::Async& a) {
+            a.best = false;
+            a.fitness_max_range = fitness_max_range;
+            a.results = results;
+        });
+    });
+}
+
+static int check_best_args(const mrgfe_batch* b, double fitness_max_range, double score_cap, const int32_t* group, int n_groups, const mrgfe_pair_result* results,
+                           const int32_t* best, const double* best_score);
+
+int mrgfe_batch_align_best_async(mrgfe_batch* b, double fitness_max_range, double score_cap, const int32_t* group, int n_groups, mrgfe_pair_result* results, int32_t* fit_state,
+                                 int32_t* best, double* best_score)
+{
+    return abi_guard("mrgfe_batch_align_best_async", [&]() -> int {
+        if (!b) { set_error("mrgfe_batch_align_best: NULL argument"); return MRGFE_ERR_INVALID; }
+        // A running align holds the context lock the argument check needs (the pair list must not move under it): refuse here rather than wait for it.
+        // (Only this thread can start an align between this look and the post below: a batch has one caller at a time.)
+        if (b->async) {
+            mrgfe_batch::Async& a = *b->async;
+            std::lock_guard<std::mutex> lk(a.mu);
+            if (a.state != 0) { set_error("mrgfe_batch_align_best_async: an align of this batch is %s: call mrgfe_batch_wait first", a.state == 3 ? "finished and not yet waited for" : "in flight"); return MRGFE_ERR_STATE; }
         }
-        mrgfe_batch::Async& a = *b->async;
-        std::unique_lock<std::mutex> lk(a.mu);
-        if (a.state != 0) { set_error("mrgfe_batch_align_async: an align of this batch is %s: call mrgfe_batch_wait first", a.state == 3 ? "finished and not yet waited for" : "in flight"); return MRGFE_ERR_STATE; }
-        a.fitness_max_range = fitness_max_range;
-        a.results = results;
-        a.state = 1;
-        a.cv.notify_all();
-        a.cv.wait(lk, [&] { return a.state >= 2; });  // the worker holds the context lock now: later calls on this batch queue up behind the align
-        return MRGFE_OK;
+        int P;
+        {
+            MRGFE_LOCK(b->ctx);
+            MRGFE_TRY(check_best_args(b, fitness_max_range, score_cap, group, n_groups, results, best, best_score));
+            P = b->book.n_pairs();
+        }
+        return batch_post_async(b, "mrgfe_batch_align_best_async", [&](mrgfe_batch::Async& a) {
+            a.best = true;
+            a.fitness_max_range = fitness_max_range;
+            a.score_cap = score_cap;
+            a.group.assign(group, group + (group ? P : 0));
+            a.n_groups = n_groups;
+            a.results = results;
+            a.fit_state = fit_state;
+            a.best_out = best;
+            a.best_score = best_score;
+        });
     });
 }
 
@@ -431,41 +495,54 @@ int mrgfe_batch_build_targets(mrgfe_batch* b)
 }
 int mrgfe_batch_num_pairs(const mrgfe_batch* b) { return b ? b->book.n_pairs() : 0; }
 
-// the selection arguments of mrgfe_batch_align_best
-struct BatchSelect {
-    double         score_cap;
-    const int32_t* group;
-    int            n_groups;
-    int32_t*       state;  // n_pairs
-};
-static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results, const BatchSelect* sel = nullptr);
+// `sel_group` (mrgfe_batch_align_best's group per pair, or null): the fitness passes stop after the bound stage and leave b->select pending
+static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results, const int32_t* sel_group = nullptr);
 
-static int batch_align_timed(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results, const BatchSelect* sel);
+static int batch_align_timed(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results);
 
 int mrgfe_batch_align(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results)
 {
     return abi_guard("mrgfe_batch_align", [&]() -> int {
         if (!b || !results) { set_error("mrgfe_batch_align: NULL argument"); return MRGFE_ERR_INVALID; }
-        return batch_align_timed(b, fitness_max_range, results, nullptr);
+        return batch_align_timed(b, fitness_max_range, results);
     });
+}
+
+// the argument checks of mrgfe_batch_align_best (and of its _async form, in the calling thread); the context lock is held
+static int check_best_args(const mrgfe_batch* b, double fitness_max_range, double score_cap, const int32_t* group, int n_groups, const mrgfe_pair_result* results,
+                           const int32_t* best, const double* best_score)
+{
+    if (!b || !results || n_groups < 0 || (n_groups > 0 && (!best || !best_score))) { set_error("mrgfe_batch_align_best: NULL argument"); return MRGFE_ERR_INVALID; }
+    const int P = b->book.n_pairs();
+    if (P > 0 && !group) { set_error("mrgfe_batch_align_best: NULL group"); return MRGFE_ERR_INVALID; }
+    if (!(fitness_max_range >= 0) || std::isnan(score_cap)) { set_error("mrgfe_batch_align_best: fitness_max_range must be >= 0 and score_cap a number"); return MRGFE_ERR_INVALID; }
+    for (int i = 0; i < P; ++i)
+        if (group[i] < -1 || group[i] >= n_groups) { set_error("mrgfe_batch_align_best: group[%d] = %d is not -1 or in [0, %d)", i, group[i], n_groups); return MRGFE_ERR_INVALID; }
+    return MRGFE_OK;
 }
 
 int mrgfe_batch_align_best(mrgfe_batch* b, double fitness_max_range, double score_cap, const int32_t* group, int n_groups, mrgfe_pair_result* results, int32_t* fit_state,
                            int32_t* best, double* best_score)
 {
     return abi_guard("mrgfe_batch_align_best", [&]() -> int {
-        if (!b || !results || n_groups < 0 || (n_groups > 0 && (!best || !best_score))) { set_error("mrgfe_batch_align_best: NULL argument"); return MRGFE_ERR_INVALID; }
-        MRGFE_LOCK(b->ctx);
-        const int P = b->book.n_pairs();
-        if (P > 0 && !group) { set_error("mrgfe_batch_align_best: NULL group"); return MRGFE_ERR_INVALID; }
-        if (!(fitness_max_range >= 0) || std::isnan(score_cap)) { set_error("mrgfe_batch_align_best: fitness_max_range must be >= 0 and score_cap a number"); return MRGFE_ERR_INVALID; }
-        for (int i = 0; i < P; ++i)
-            if (group[i] < -1 || group[i] >= n_groups) { set_error("mrgfe_batch_align_best: group[%d] = %d is not -1 or in [0, %d)", i, group[i], n_groups); return MRGFE_ERR_INVALID; }
-        std::vector<int32_t> state(static_cast<size_t>(std::max(P, 1)), kFitSkipped);
-        BatchSelect sel{score_cap, group, n_groups, state.data()};
-        MRGFE_TRY(batch_align_timed(b, fitness_max_range, results, &sel));
-        std::vector<double>  fit(static_cast<size_t>(std::max(P, 1)));
-        std::vector<int32_t> conv(static_cast<size_t>(std::max(P, 1)));
+        if (!b) { set_error("mrgfe_batch_align_best: NULL argument"); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(b->ctx);  // held over both stages: nothing else reaches the context while the selection is pending
+        MRGFE_TRY(check_best_args(b, fitness_max_range, score_cap, group, n_groups, results, best, best_score));
+        const int    P = b->book.n_pairs();
+        const size_t N = static_cast<size_t>(std::max(P, 1));
+        std::vector<double> lo(N), hi(N);
+        MRGFE_TRY(batch_align_bounds(b, fitness_max_range, group, results, lo.data(), hi.data()));
+        // the selection over the pairs that have a fitness job; every other pair (an empty cloud; grouped and not converged) is SKIPPED
+        const std::vector<int>& job_pair = b->select.job_pair;
+        const size_t J = job_pair.size();
+        std::vector<int32_t> jgroup(J), jconv(J), jstate(J), state(N, kFitSkipped);
+        std::vector<double>  jlo(J), jhi(J);
+        for (size_t j = 0; j < J; ++j) { const int i = job_pair[j]; jgroup[j] = group[i]; jconv[j] = results[i].converged; jlo[j] = lo[i]; jhi[j] = hi[i]; }
+        fit_select_prune(static_cast<int>(J), jlo.data(), jhi.data(), jconv.data(), jgroup.data(), n_groups, score_cap, jstate.data());
+        for (size_t j = 0; j < J; ++j) state[job_pair[j]] = jstate[j];
+        MRGFE_TRY(batch_align_finish(b, state.data(), results));
+        std::vector<double>  fit(N);
+        std::vector<int32_t> conv(N);
         for (int i = 0; i < P; ++i) { fit[i] = results[i].fitness; conv[i] = results[i].converged; }
         fit_select_groups(P, fit.data(), conv.data(), group, n_groups, score_cap, best, best_score);
         if (fit_state) std::memcpy(fit_state, state.data(), sizeof(int32_t) * static_cast<size_t>(P));
@@ -493,22 +570,15 @@ int mrgfe_dbg_batch_fit_bounds(const mrgfe_batch* b, double* lower, double* uppe
     return MRGFE_OK;
 }
 
-static int batch_align_timed(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results, const BatchSelect* sel)
+// mrgfe_batch_timing, and the caller's clouds, at the end of an align that started at `t_start` and ended with status `st`
+static int batch_align_ended(mrgfe_batch* b, std::chrono::steady_clock::time_point t_start, int st)
 {
-    MRGFE_LOCK(b->ctx);
-    const auto t_start = b->t_queue_set ? b->t_queue : std::chrono::steady_clock::now();
-    int st;
-    {
-        TraceRange tr(sel ? "mrgfe_batch_align_best" : "mrgfe_batch_align");
-        st = batch_align_impl(b, fitness_max_range, results, sel);
-    }
     if (st == MRGFE_OK) {
         b->last_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count();
         b->last_pairs = b->book.n_pairs();
         b->total_us += b->last_us;
         b->total_pairs += b->last_pairs;
     }
-    b->t_queue_set = false;
     // zero-copy uploads (mrgfe_ctx_set_zero_copy_uploads): the caller's page-locked clouds are its own again when this call returns — also when it fails
     // with their DMA still queued.  The error text of the failure is kept.
     if (st != MRGFE_OK && b->ctx->dma_from_caller) {
@@ -520,6 +590,88 @@ static int batch_align_timed(mrgfe_batch* b, double fitness_max_range, mrgfe_pai
     }
     return st;
 }
+
+static int batch_align_timed(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results)
+{
+    MRGFE_LOCK(b->ctx);
+    const auto t_start = b->t_queue_set ? b->t_queue : std::chrono::steady_clock::now();
+    int st;
+    {
+        TraceRange tr("mrgfe_batch_align");
+        st = batch_align_impl(b, fitness_max_range, results);
+    }
+    b->t_queue_set = false;
+    return batch_align_ended(b, t_start, st);
+}
+
+}  // extern "C"
+
+// ---- mrgfe_batch_align_best in two stages (api_internal.h): the callers are mrgfe_batch_align_best, which decides between them over this batch's
+// pairs, and a node member (node.cpp), whose node decides over the pair lists of all its members
+int batch_align_bounds(mrgfe_batch* b, double max_range, const int32_t* group, mrgfe_pair_result* results, double* lo, double* hi)
+{
+    MRGFE_LOCK(b->ctx);
+    static const int32_t no_group = -1;
+    if (!group) group = &no_group;  // (an empty pair list: nothing reads it, but "not null" is what asks for the selection)
+    b->select.run.drop();
+    b->select.t_start =b->t_queue_set ? b->t_queue : std::chrono::steady_clock::now();
+    b->t_queue_set = false;
+    int st;
+    {
+        TraceRange tr("mrgfe_batch_align_best: align and bounds");
+        st = batch_align_impl(b, max_range, results, group);
+    }
+    if (st != MRGFE_OK) {
+        b->select.run.drop();
+        return batch_align_ended(b, b->select.t_start, st);
+    }
+    std::copy(b->fit_lo.begin(), b->fit_lo.end(), lo);
+    std::copy(b->fit_hi.begin(), b->fit_hi.end(), hi);
+    return MRGFE_OK;
+}
+
+int batch_align_finish(mrgfe_batch* b, const int32_t* state, mrgfe_pair_result* results)
+{
+    MRGFE_LOCK(b->ctx);
+    if (!b->select.run.pending()) { set_error("batch_align_finish: no selection is pending on this batch"); return MRGFE_ERR_STATE; }
+    TraceRange tr("mrgfe_batch_align_best: contenders");
+    const std::vector<int>& job_pair = b->select.job_pair;
+    const size_t J = job_pair.size();
+    std::vector<int32_t> jstate(J);
+    std::vector<double>  fit(J);
+    for (size_t j = 0; j < J; ++j) jstate[j] = state[job_pair[j]];
+    int st = b->ctx->bind();
+    if (st == MRGFE_OK) st = b->select.run.finish(jstate.data(), fit.data(), &b->select_stats);
+    b->select.run.drop();
+    if (st == MRGFE_OK) {
+        for (size_t j = 0; j < J; ++j) results[job_pair[j]].fitness = fit[j];
+        // the counts are per PAIR; a SKIPPED pair has fitness DBL_MAX (what the full path gives a pair with an empty cloud; so has every pair without a job)
+        FitSelectStats& ss = b->select_stats;
+        ss.exact = ss.pruned = ss.above_cap = ss.skipped = 0;
+        for (int i = 0; i < b->book.n_pairs(); ++i) {
+            switch (state[i]) {
+                case kFitExact: ++ss.exact; break;
+                case kFitPruned: ++ss.pruned; break;
+                case kFitAboveCap: ++ss.above_cap; break;
+                default: ++ss.skipped; results[i].fitness = DBL_MAX;
+            }
+        }
+    }
+    return batch_align_ended(b, b->select.t_start, st);
+}
+
+int batch_align_abandon(mrgfe_batch* b)
+{
+    MRGFE_LOCK(b->ctx);
+    b->select.run.drop();
+    MRGFE_TRY(b->ctx->bind());
+    MRGFE_HIP_CHECK(hipStreamSynchronize(b->ctx->stream));
+    if (b->ctx->side) MRGFE_HIP_CHECK(hipStreamSynchronize(b->ctx->side));
+    b->ctx->dma_from_caller = false;  // whatever was queued has run
+    return MRGFE_OK;
+}
+
+extern "C" {
 
 // GICP_HIP: the candidates of a target share its covariances and correspondence grid, and all LM loops advance together (GicpBatch: one
 // launch per kernel and round for the pairs still running); ICP_HIP: lock-step ICP rounds, no covariances.  The records follow in batch_records.
@@ -769,39 +921,28 @@ static void batch_records(mrgfe_batch* b, const std::vector<char>& early_done, m
     }
 }
 
-// nn_fitness_select on the jobs (bounded selection: every job's interval, exact scores only for the candidates that can still win); the pairs
-// without a job are SKIPPED: fitness DBL_MAX (what the full path gives a pair with an empty cloud)
-static int select_fitness(mrgfe_batch* b, double max_range, mrgfe_pair_result* results, const BatchSelect& sel, const std::vector<NnFitnessJob>& jobs, const std::vector<int>& job_pair)
+// The bound stage of the selection on the jobs (FitSelectRun::bounds: every job's interval); the run stays pending in b->select for batch_align_finish.
+// The pairs without a job keep the interval DBL_MAX / DBL_MAX.
+static int select_bounds(mrgfe_batch* b, double max_range, const mrgfe_pair_result* results, const int32_t* group, const std::vector<NnFitnessJob>& jobs, std::vector<int>& job_pair)
 {
     const size_t J = jobs.size();
-    std::vector<int32_t> jgroup(J), jconv(J), jstate(J);
-    std::vector<double>  fit(J), lo(J), hi(J);
-    for (size_t j = 0; j < J; ++j) { jgroup[j] = sel.group[job_pair[j]]; jconv[j] = results[job_pair[j]].converged; }
-    MRGFE_TRY(nn_fitness_select(b->ctx, jobs.data(), J, max_range, jgroup.data(), sel.n_groups, jconv.data(), sel.score_cap, fit.data(), jstate.data(), lo.data(), hi.data(),
-                                &b->select_stats));
+    std::vector<int32_t> jgroup(J), jconv(J);
+    std::vector<double>  lo(J), hi(J);
+    for (size_t j = 0; j < J; ++j) { jgroup[j] = group[job_pair[j]]; jconv[j] = results[job_pair[j]].converged; }
+    b->select_stats = FitSelectStats();
+    MRGFE_TRY(b->select.run.bounds(b->ctx, jobs.data(), J, max_range, jgroup.data(), jconv.data(), lo.data(), hi.data()));
     for (size_t j = 0; j < J; ++j) {
-        const int i = job_pair[j];
-        results[i].fitness = fit[j];
-        sel.state[i] = jstate[j];
-        b->fit_lo[i] = lo[j];
-        b->fit_hi[i] = hi[j];
+        b->fit_lo[job_pair[j]] = lo[j];
+        b->fit_hi[job_pair[j]] = hi[j];
     }
-    FitSelectStats& ss = b->select_stats;
-    ss.exact = ss.pruned = ss.above_cap = ss.skipped = 0;
-    for (int i = 0; i < b->book.n_pairs(); ++i) {
-        switch (sel.state[i]) {
-            case kFitExact: ++ss.exact; break;
-            case kFitPruned: ++ss.pruned; break;
-            case kFitAboveCap: ++ss.above_cap; break;
-            default: ++ss.skipped; results[i].fitness = DBL_MAX;
-        }
-    }
+    b->select.job_pair.swap(job_pair);
     return MRGFE_OK;
 }
 
 // getFitnessScore of every pair the early pass did not score, in one launch: one exact-NN grid per distinct target (built here unless a builder
-// thread made it, `built`); with `sel` the bounded selection, where grouped pairs that did not converge are SKIPPED (never the best, no grid)
-static int batch_fitness(mrgfe_batch* b, double max_range, mrgfe_pair_result* results, const BatchSelect* sel, std::vector<char>& built, const std::vector<char>& early_skip)
+// thread made it, `built`); with `sel_group` the bound stage of the bounded selection, where grouped pairs that did not converge are SKIPPED (never
+// the best, no grid)
+static int batch_fitness(mrgfe_batch* b, double max_range, mrgfe_pair_result* results, const int32_t* sel_group, std::vector<char>& built, const std::vector<char>& early_skip)
 {
     TraceRange tr("mrgfe fitness passes");
     const PairBook& e = b->book;
@@ -809,8 +950,7 @@ static int batch_fitness(mrgfe_batch* b, double max_range, mrgfe_pair_result* re
     std::vector<NnGrid>& grids = b->fit_grids;
     if (grids.size() < static_cast<size_t>(e.n_targets())) grids.resize(e.n_targets());
     if (built.size() < static_cast<size_t>(e.n_targets())) built.resize(e.n_targets(), 0);
-    if (sel) {
-        std::fill(sel->state, sel->state + P, kFitSkipped);
+    if (sel_group) {
         b->fit_lo.assign(P, DBL_MAX);
         b->fit_hi.assign(P, DBL_MAX);
     }
@@ -820,12 +960,12 @@ static int batch_fitness(mrgfe_batch* b, double max_range, mrgfe_pair_result* re
         const PairBook::Pair& p = e.pair(i);
         const PairBook::Target& t = e.target(p.target);
         if (t.n == 0 || p.n == 0 || (static_cast<size_t>(i) < early_skip.size() && early_skip[i])) continue;
-        if (sel && sel->group[i] >= 0 && !results[i].converged) continue;
+        if (sel_group && sel_group[i] >= 0 && !results[i].converged) continue;
         if (!built[p.target]) { built[p.target] = 1; MRGFE_TRY(grids[p.target].build(b->ctx, t.d_pts, t.n, 1.0f, NnGrid::kCrowding1nn, 1)); }
         jobs.push_back(grids[p.target].make_fitness_job(p.d_src, p.n, &b->final_rm[size_t(i) * 16]));
         job_pair.push_back(i);
     }
-    if (sel) return select_fitness(b, max_range, results, *sel, jobs, job_pair);
+    if (sel_group) return select_bounds(b, max_range, results, sel_group, jobs, job_pair);
     if (jobs.empty()) return MRGFE_OK;
     std::vector<double> fit(jobs.size());
     MRGFE_TRY(nn_fitness_batch(b->ctx, jobs.data(), jobs.size(), max_range, fit.data()));
@@ -834,18 +974,18 @@ static int batch_fitness(mrgfe_batch* b, double max_range, mrgfe_pair_result* re
     return MRGFE_OK;
 }
 
-static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results, const BatchSelect* sel)
+static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair_result* results, const int32_t* sel_group)
 {
     MRGFE_LOCK(b->ctx);
     std::vector<char> fit_built;   // targets whose fitness grid is built in this call
     std::vector<char> early_skip;  // pairs whose fitness score was computed beside the alignment rounds
-    if (!sel) { b->fit_lo.clear(); b->fit_hi.clear(); }  // mrgfe_dbg_batch_fit_bounds: intervals of an align_best only
+    if (!sel_group) { b->fit_lo.clear(); b->fit_hi.clear(); }  // mrgfe_dbg_batch_fit_bounds: intervals of an align_best only
     if (!b->ndt) {
         MRGFE_TRY(gicp_align_batch(b));
         batch_records(b, early_skip, results);
     } else {
         FitOverlap ov{b, results, fitness_max_range};
-        MRGFE_TRY(ov.start(sel != nullptr));
+        MRGFE_TRY(ov.start(sel_group != nullptr));
         int align_status;
         {
             TraceRange tr("mrgfe rounds (set_target + align_all)");
@@ -858,7 +998,7 @@ static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair
         fit_built.swap(ov.built);
         early_skip.swap(ov.early_done);
     }
-    return fitness_max_range >= 0 ? batch_fitness(b, fitness_max_range, results, sel, fit_built, early_skip) : MRGFE_OK;
+    return fitness_max_range >= 0 ? batch_fitness(b, fitness_max_range, results, sel_group, fit_built, early_skip) : MRGFE_OK;
 }
 
 int mrgfe_batch_fitness_stats(const mrgfe_batch* b, double out[11])

@@ -157,18 +157,43 @@ int nn_status_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, doub
 // nearest to T * src[i] (ties: the lowest index) if its squared distance is < max_sq, else -1.  Enqueued on ctx->stream, no host wait.
 int nn_nearest_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_sq);
 
-// What the last nn_fitness_select did: jobs per state, queries left to the sweep / the pyramid walk after the selection, host milliseconds of
+// What the last nn_fitness_select / FitSelectRun did: jobs per state, queries left to the sweep / the pyramid walk after the selection, host milliseconds of
 // the bound stage (block, seed, bound sums, the selection) and of the contender stage (sweep, walk, sums).
 struct FitSelectStats {
     uint64_t exact = 0, pruned = 0, above_cap = 0, skipped = 0, to_sweep = 0, to_far = 0;
     double   ms_bound = 0, ms_contend = 0;
 };
-// getFitnessScore of every job, exact only where the best-candidate rule still needs it (mrgfe_batch_align_best).  Block pass and seed write a
-// per-query interval lo <= d <= hi (hi: the attained distance in the query's slot); the bound sums give every job [Σlo, Σhi] / count over the
-// same slices and reduction tree as the exact sum (bit-valid, no epsilon) when the counted point sets agree, else no bound; one host wait;
-// fit_select_prune decides per job (group[j] / converged[j], see fit_select.h); the queues of the jobs that need no exact score are emptied and
-// the sweep, the walk and the sum run for the rest.  out_fit[j]: the exact score (EXACT), the lower bound (PRUNED / ABOVE_CAP), DBL_MAX (SKIPPED);
-// out_lo / out_hi: the interval (0 / +inf: none certified).  Two host waits per call.
+// getFitnessScore of every job, exact only where the best-candidate rule still needs it (mrgfe_batch_align_best), in two stages with the selection
+// between them left to the caller — who may hold the jobs of ONE batch (nn_fitness_select, batch_align_bounds / batch_align_finish) or be a node
+// that decides over the pair lists of all its members at once.
+//   bounds(): block pass and seed write a per-query interval lo <= d <= hi (hi: the attained distance in the query's slot); the bound sums give
+//     every job [Σlo, Σhi] / count over the same slices and reduction tree as the exact sum (bit-valid, no epsilon) when the counted point sets
+//     agree, else no bound (0 / +inf); one host wait.  Jobs that need nothing (group[j] >= 0 and not converged[j]) run with no queries: DBL_MAX / DBL_MAX.
+//     A job's interval does not depend on the other jobs of the launch (per-query values; sums over fixed slices).
+//   finish(): state[j] per job as fit_select_prune gives it (fit_select.h); the queues of the jobs that are not EXACT are emptied and the sweep, the
+//     walk and the 2-column sum run for the rest; one more host wait (none when no job is left).  out_fit[j]: the exact score (EXACT), the lower
+//     bound (PRUNED / ABOVE_CAP), DBL_MAX (SKIPPED).  stats: the jobs per state, the queries left to the sweep / the walk, and the host
+//     milliseconds from the start of bounds() to the start of finish() (ms_bound) and of finish() (ms_contend).
+// BETWEEN the two calls the run lives in the context's scratch buffers 9, 12, 13 and 14 (queues, per-query distances, lo) and on its streams:
+// NOTHING else may run on that context in between.  The two callers hold to that: a batch runs both stages inside one ABI call under the
+// context's lock, and a node member's context is reachable only through the node, whose api_mu is held from the first stage to the last.
+// A run that is not finished is simply dropped (drop(), the destructor, the next bounds()): it owns no device memory.
+class FitSelectRun {
+   public:
+    FitSelectRun();
+    ~FitSelectRun();
+    FitSelectRun(const FitSelectRun&) = delete;
+    FitSelectRun& operator=(const FitSelectRun&) = delete;
+    int  bounds(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_range, const int32_t* group, const int32_t* converged, double* out_lo, double* out_hi);
+    int  finish(const int32_t* state, double* out_fit, FitSelectStats* stats = nullptr);
+    bool pending() const;
+    void drop();
+
+   private:
+    struct Impl;
+    Impl* impl_ = nullptr;
+};
+// bounds -> fit_select_prune over the jobs -> finish: out_state[j] the decision, out_lo / out_hi the interval.  Two host waits per call.
 int nn_fitness_select(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_range, const int32_t* group, int n_groups, const int32_t* converged, double score_cap,
                       double* out_fit, int32_t* out_state, double* out_lo, double* out_hi, FitSelectStats* stats = nullptr);
 

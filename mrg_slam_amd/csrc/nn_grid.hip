@@ -2189,69 +2189,115 @@ int nn_status_batch(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, doub
     return MRGFE_OK;
 }
 
-int nn_fitness_select(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_range, const int32_t* group, int n_groups, const int32_t* converged, double score_cap,
-                      double* out_fit, int32_t* out_state, double* out_lo, double* out_hi, FitSelectStats* stats)
-{
+// One bounded selection between its two stages (nn_grid.h): the launch plan, whose device pointers lie in the context's scratch 9 / 12 / 13 / 14, the
+// queue lengths the bound stage read back, and the lower bounds that become the fitness of the jobs that are not scored exactly.
+struct FitSelectRun::Impl {
     using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    FitSelectStats ss;
-    for (size_t j = 0; j < count; ++j) { out_fit[j] = DBL_MAX; out_lo[j] = DBL_MAX; out_hi[j] = DBL_MAX; out_state[j] = kFitExact; }
-    if (stats) *stats = ss;
-    if (count == 0) return MRGFE_OK;
+    FitPlan<false>        fp;
+    std::vector<uint32_t> n;     // per job: its queries in this run (0: grouped and not converged)
+    std::vector<uint32_t> cnts;  // the queue lengths after the bound passes
+    std::vector<double>   lo;
+    clk::time_point       t0;
+    Impl(mrgfe_ctx* ctx, size_t count, double max_range) : fp(ctx, count, max_range, fit_sweep_mode() != 0), n(count, 0u), cnts(2 * (count + 1), 0u), lo(count, DBL_MAX), t0(clk::now()) {}
+};
+
+FitSelectRun::FitSelectRun() = default;
+FitSelectRun::~FitSelectRun() { drop(); }
+bool FitSelectRun::pending() const { return impl_ != nullptr; }
+void FitSelectRun::drop()
+{
+    delete impl_;
+    impl_ = nullptr;
+}
+
+int FitSelectRun::bounds(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_range, const int32_t* group, const int32_t* converged, double* out_lo, double* out_hi)
+{
+    drop();
+    for (size_t j = 0; j < count; ++j) { out_lo[j] = DBL_MAX; out_hi[j] = DBL_MAX; }
+    std::unique_ptr<Impl> run(new Impl(ctx, count, max_range));
+    if (count == 0) { impl_ = run.release(); return MRGFE_OK; }
     // jobs that need nothing (grouped and not converged) are run with no queries: every pass skips them
     std::vector<NnFitnessJob> hjobs(jobs, jobs + count);
-    for (size_t j = 0; j < count; ++j)
+    for (size_t j = 0; j < count; ++j) {
         if (group[j] >= 0 && !converged[j]) hjobs[j].n = 0;
-    FitPlan<false> fp(ctx, count, max_range, fit_sweep_mode() != 0);
-    const bool     sweep = fp.sweep;
+        run->n[j] = hjobs[j].n;
+    }
+    FitPlan<false>& fp = run->fp;
     MRGFE_TRY(fp.plan("nn_fitness_select", hjobs.data()));
     MRGFE_TRY(fp.load(hjobs.data(), 4, false));  // sqd: hi, then the exact distance; the exact sums use the first 2 of the 4 columns
-    // 1. bounds: block pass and seed, both writing lo beside sqd; the one extra host wait: the selection needs every job's interval
-    std::vector<double>   res(4 * count, 0.0);
-    std::vector<uint32_t> cnts(2 * (count + 1), 0u);
+    // block pass and seed, both writing lo beside sqd; the one extra host wait: the selection needs every job's interval
+    std::vector<double> res(4 * count, 0.0);
     if (fp.max_n > 0) {
         MRGFE_TRY(fp.near<true>(fp.d_lo));
-        MRGFE_TRY(fp.sums(4, res.data(), cnts.data()));
+        MRGFE_TRY(fp.sums(4, res.data(), run->cnts.data()));
     }
-    // 2. the per-job intervals and the selection
     for (size_t j = 0; j < count; ++j) {
         const double* r = &res[4 * j];
-        if (r[1] != r[3]) { out_lo[j] = 0.0; out_hi[j] = INFINITY; continue; }  // the counted point set is not certain yet: no bound
-        out_lo[j] = r[1] > 0 ? r[0] / r[1] : DBL_MAX;
-        out_hi[j] = r[3] > 0 ? r[2] / r[3] : DBL_MAX;
+        if (r[1] != r[3]) { out_lo[j] = 0.0; out_hi[j] = INFINITY; }  // the counted point set is not certain yet: no bound
+        else {
+            out_lo[j] = r[1] > 0 ? r[0] / r[1] : DBL_MAX;
+            out_hi[j] = r[3] > 0 ? r[2] / r[3] : DBL_MAX;
+        }
+        run->lo[j] = out_lo[j];
     }
-    fit_select_prune(static_cast<int>(count), out_lo, out_hi, converged, group, n_groups, score_cap, out_state);
+    impl_ = run.release();
+    return MRGFE_OK;
+}
+
+int FitSelectRun::finish(const int32_t* state, double* out_fit, FitSelectStats* stats)
+{
+    if (!impl_) { set_error("FitSelectRun::finish without bounds"); return MRGFE_ERR_STATE; }
+    std::unique_ptr<Impl> run(impl_);  // finished or failed: the run is over either way
+    impl_ = nullptr;
+    FitPlan<false>& fp = run->fp;
+    const size_t    count = fp.count;
+    const bool      sweep = fp.sweep;
+    FitSelectStats  ss;
     std::vector<uint32_t> drop(count, 0u);
     bool any_exact = false;
     for (size_t j = 0; j < count; ++j) {
-        switch (out_state[j]) {
-            case kFitPruned: out_fit[j] = out_lo[j]; ++ss.pruned; drop[j] = 1; break;
-            case kFitAboveCap: out_fit[j] = out_lo[j]; ++ss.above_cap; drop[j] = 1; break;
+        out_fit[j] = DBL_MAX;
+        switch (state[j]) {
+            case kFitPruned: out_fit[j] = run->lo[j]; ++ss.pruned; drop[j] = 1; break;
+            case kFitAboveCap: out_fit[j] = run->lo[j]; ++ss.above_cap; drop[j] = 1; break;
             case kFitSkipped: ++ss.skipped; drop[j] = 1; break;
             default:
                 ++ss.exact;
-                if (hjobs[j].n > 0) {
+                if (run->n[j] > 0) {
                     any_exact = true;
-                    ss.to_far += sweep ? cnts[count + 1 + j] : cnts[j];
-                    ss.to_sweep += sweep ? cnts[j] - cnts[count + 1 + j] : 0;
+                    ss.to_far += sweep ? run->cnts[count + 1 + j] : run->cnts[j];
+                    ss.to_sweep += sweep ? run->cnts[j] - run->cnts[count + 1 + j] : 0;
                 }
         }
     }
-    const auto t1 = clk::now();
-    // 3. contenders: the passes and the sum of nn_fitness_batch on the queues the selection left; the fork to the side stream comes after the
+    const auto t1 = Impl::clk::now();
+    // contenders: the passes and the sum of nn_fitness_batch on the queues the selection left; the fork to the side stream comes after the
     // drop kernel, so the walk sees the emptied queues
     if (any_exact) {
+        std::vector<double> res(2 * count, 0.0);
         MRGFE_HIP_CHECK(hipMemcpyAsync(fp.d_drop, drop.data(), sizeof(uint32_t) * count, hipMemcpyHostToDevice, fp.st));
         hipLaunchKernelGGL(nn_fit_drop_kernel, dim3(static_cast<uint32_t>((count + 255) / 256)), dim3(256), 0, fp.st, fp.d_drop, static_cast<uint32_t>(count), fp.cnt(0), fp.cnt(1));
         MRGFE_TRY(fp.far());
         MRGFE_TRY(fp.sums(2, res.data(), nullptr));
         for (size_t j = 0; j < count; ++j)
-            if (out_state[j] == kFitExact && hjobs[j].n > 0 && res[2 * j + 1] > 0) out_fit[j] = res[2 * j] / res[2 * j + 1];
+            if (state[j] == kFitExact && run->n[j] > 0 && res[2 * j + 1] > 0) out_fit[j] = res[2 * j] / res[2 * j + 1];
     }
-    ss.ms_bound = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    ss.ms_contend = std::chrono::duration<double, std::milli>(clk::now() - t1).count();
+    ss.ms_bound = std::chrono::duration<double, std::milli>(t1 - run->t0).count();
+    ss.ms_contend = std::chrono::duration<double, std::milli>(Impl::clk::now() - t1).count();
     if (stats) *stats = ss;
     return MRGFE_OK;
+}
+
+int nn_fitness_select(mrgfe_ctx* ctx, const NnFitnessJob* jobs, size_t count, double max_range, const int32_t* group, int n_groups, const int32_t* converged, double score_cap,
+                      double* out_fit, int32_t* out_state, double* out_lo, double* out_hi, FitSelectStats* stats)
+{
+    for (size_t j = 0; j < count; ++j) { out_fit[j] = DBL_MAX; out_state[j] = kFitExact; }
+    if (stats) *stats = FitSelectStats();
+    FitSelectRun run;
+    MRGFE_TRY(run.bounds(ctx, jobs, count, max_range, group, converged, out_lo, out_hi));
+    if (count == 0) return MRGFE_OK;
+    fit_select_prune(static_cast<int>(count), out_lo, out_hi, converged, group, n_groups, score_cap, out_state);
+    return run.finish(out_state, out_fit, stats);
 }
 
 int NnGrid::fitness(mrgfe_ctx* ctx, const float4* d_src, size_t n_src, const float T[16], double max_range, double* out)

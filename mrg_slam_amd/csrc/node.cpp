@@ -19,6 +19,7 @@
 
 #include <atomic>
 #include <cfloat>
+#include <cmath>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -29,7 +30,8 @@
 #include <unordered_map>
 #include <vector>
 
-#include "common.h"
+#include "api_internal.h"
+#include "fit_select.h"
 
 using namespace mrgfe;
 
@@ -87,7 +89,8 @@ struct ResidentCloud {
     uint64_t last_use = 0;  // serial of the member's align call that named it last
 };
 
-enum Job { JOB_NONE = 0, JOB_ALIGN = 1, JOB_QUIT = 2 };
+// JOB_BOUNDS / JOB_FINISH: the two stages of mrgfe_node_align_best; JOB_ABANDON: give up a first stage that succeeded, because another member's failed
+enum Job { JOB_NONE = 0, JOB_ALIGN = 1, JOB_QUIT = 2, JOB_BOUNDS = 3, JOB_FINISH = 4, JOB_ABANDON = 5 };
 struct BatchDestroy { void operator()(mrgfe_batch* b) const { mrgfe_batch_destroy(b); } };
 
 }  // namespace
@@ -111,6 +114,7 @@ struct mrgfe_node {
         size_t       target_cap = size_t(16) << 30;             // bytes of keyed targets kept resident (MRGFE_KEYFRAME_STORE_MB, the batch store's cap), LRU beyond it
         DevBuf       d_send, d_recv;                            // RCCL gather
         int          fail_next = 0;                             // test hook
+        bool         staged = false;                            // mrgfe_node_align_best: this member's first stage succeeded and its selection is pending
         std::unique_ptr<mrgfe_batch, BatchDestroy> batch;
     };
     mrgfe_reg_params         params;
@@ -121,6 +125,13 @@ struct mrgfe_node {
     std::vector<nccl_comm_t> comms;     // one per member when the RCCL gather is in use
     bool                     rccl_tried = false;
     int                      last_gather = 0;  // 0 host, 1 RCCL
+    // mrgfe_node_align_best, per pair of the whole list: the caller's groups, what the members' first stages report (each member writes its own block),
+    // and the states the calling thread decides between the stages
+    const int32_t*           sel_group = nullptr;
+    std::vector<double>      sel_lo, sel_hi;
+    std::vector<int32_t>     sel_conv, sel_state;
+    bool                     last_best = false;  // the last align was a successful align_best: sel_lo / sel_hi are its intervals
+    double                   select_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     std::mutex               api_mu;    // one align at a time
 };
 
@@ -135,8 +146,8 @@ int member_fail(Member& m, int status)
     return status;
 }
 
-// the member's block: targets in order of first use, pairs in list order; then the batch's own align
-int member_align(mrgfe_node* node, Member& m)
+// the member's block into its batch: targets in order of first use, pairs in list order (nothing for an empty block)
+int member_fill(mrgfe_node* node, Member& m)
 {
     m.status = MRGFE_OK;
     m.error.clear();
@@ -197,7 +208,41 @@ int member_align(mrgfe_node* node, Member& m)
                              : mrgfe_batch_add_pair(m.batch.get(), it->second, p.xyzi, p.n, p.stride, p.guess);
         if (pi < 0) return member_fail(m, pi);
     }
+    return MRGFE_OK;
+}
+
+// mrgfe_node_align: the block, then the batch's own align
+int member_align(mrgfe_node* node, Member& m)
+{
+    int st = member_fill(node, m);
+    if (st != MRGFE_OK || m.count == 0) return st;
     st = mrgfe_batch_align(m.batch.get(), node->fitness_max_range, m.local.data());
+    if (st != MRGFE_OK) return member_fail(m, st);
+    for (int k = 0; k < m.count; ++k) m.local[static_cast<size_t>(k)].pair_id = m.first + k;  // the GLOBAL pair index
+    return MRGFE_OK;
+}
+
+// mrgfe_node_align_best, first stage: the block, the align and the interval of every pair of the block, written with `converged` into the node's arrays
+// at the block's place.  The selection stays pending in the member's batch (batch_align_bounds): nobody else can reach its context, the node's api_mu is held.
+int member_bounds(mrgfe_node* node, Member& m)
+{
+    m.staged = false;
+    int st = member_fill(node, m);
+    if (st != MRGFE_OK || m.count == 0) return st;
+    const size_t f = static_cast<size_t>(m.first);
+    st = batch_align_bounds(m.batch.get(), node->fitness_max_range, node->sel_group + f, m.local.data(), node->sel_lo.data() + f, node->sel_hi.data() + f);
+    if (st != MRGFE_OK) return member_fail(m, st);
+    for (int k = 0; k < m.count; ++k) node->sel_conv[f + static_cast<size_t>(k)] = m.local[static_cast<size_t>(k)].converged;
+    m.staged = true;
+    return MRGFE_OK;
+}
+
+// second stage: the exact passes for the contenders of the block, by the states the node decided over the whole list
+int member_finish(mrgfe_node* node, Member& m)
+{
+    if (m.count == 0) return MRGFE_OK;
+    m.staged = false;  // batch_align_finish leaves nothing pending, whether it succeeds or fails
+    const int st = batch_align_finish(m.batch.get(), node->sel_state.data() + m.first, m.local.data());
     if (st != MRGFE_OK) return member_fail(m, st);
     for (int k = 0; k < m.count; ++k) m.local[static_cast<size_t>(k)].pair_id = m.first + k;  // the GLOBAL pair index
     return MRGFE_OK;
@@ -213,8 +258,15 @@ void member_main(mrgfe_node* node, Member* m)
             job = m->job;
         }
         if (job == JOB_QUIT) return;
-        const int st = abi_guard("mrgfe_node_align member", [&] { return member_align(node, *m); });
-        if (st != MRGFE_OK && m->status == MRGFE_OK) member_fail(*m, st);  // an exception: member_align did not get to record it
+        if (job == JOB_ABANDON) {
+            // (its own failure changes nothing the caller could act on: the error reported is the one of the member that made the call fail)
+            (void)abi_guard("mrgfe_node_align_best member", [&] { return batch_align_abandon(m->batch.get()); });
+            m->staged = false;
+        }
+        const int st = job == JOB_ABANDON ? MRGFE_OK : abi_guard("mrgfe_node_align member", [&] {
+            return job == JOB_BOUNDS ? member_bounds(node, *m) : job == JOB_FINISH ? member_finish(node, *m) : member_align(node, *m);
+        });
+        if (st != MRGFE_OK && m->status == MRGFE_OK) member_fail(*m, st);  // an exception: the member did not get to record it
         if (st != MRGFE_OK) {
             // the member's clouds go up by DMA out of the caller's page-locked buffers (zero-copy uploads are always on for members) and a failing
             // block may have queued copies it never waited for: mrgfe_node_align hands the buffers back only after they have drained
@@ -332,6 +384,51 @@ int rccl_gather(mrgfe_node* node, int per, mrgfe_pair_result* results, int n_pai
         ++seen;
     }
     if (seen != n_pairs) { set_error("gathered %d records for %d pairs", seen, n_pairs); return MRGFE_ERR_STATE; }
+    return MRGFE_OK;
+}
+
+// contiguous blocks, sizes differing by at most one, the first n mod G blocks the longer ones
+void cut_blocks(mrgfe_node* node)
+{
+    const int n = static_cast<int>(node->pairs.size()), G = static_cast<int>(node->members.size());
+    const int base = n / G, extra = n % G;
+    for (int g = 0; g < G; ++g) {
+        Member* m = node->members[static_cast<size_t>(g)].get();
+        m->first = g * base + std::min(g, extra);
+        m->count = base + (g < extra ? 1 : 0);
+    }
+}
+
+// one job for every member, all waited for from the calling thread (a member that fails has finished too); the first member that failed names the error
+int run_members(mrgfe_node* node, Job job, const char* fn, const char* what)
+{
+    {
+        TraceRange tr(what);
+        for (auto& m : node->members) post(m.get(), job);
+        for (auto& m : node->members) wait_done(m.get());
+    }
+    for (auto& m : node->members)
+        if (m->status != MRGFE_OK) {
+            set_error("%s: member %d (device %d): %s", fn, m->index, m->device, m->error.c_str());
+            return m->status;
+        }
+    return MRGFE_OK;
+}
+
+// the members' records into the caller's array in pair order: RCCL between distinct devices, host memory otherwise (want_rccl)
+int gather_records(mrgfe_node* node, mrgfe_pair_result* results, int n)
+{
+    const int G = static_cast<int>(node->members.size());
+    node->last_gather = 0;
+    if (want_rccl(node) && rccl_setup(node) == MRGFE_OK) {
+        const int per = (n + G - 1) / G;
+        TraceRange tr("mrgfe_node_align record gather (RCCL)");
+        const int st = rccl_gather(node, per, results, n);
+        if (st == MRGFE_OK) { node->last_gather = 1; return MRGFE_OK; }
+        if (const char* e = std::getenv("MRGFE_NODE_GATHER")) if (std::strcmp(e, "rccl") == 0) return st;  // asked for: do not hide the failure
+    }
+    for (auto& m : node->members)
+        if (m->count) std::memcpy(results + m->first, m->local.data(), sizeof(mrgfe_pair_result) * static_cast<size_t>(m->count));
     return MRGFE_OK;
 }
 
@@ -453,39 +550,103 @@ int mrgfe_node_align(mrgfe_node* node, double fitness_max_range, mrgfe_pair_resu
     return abi_guard("mrgfe_node_align", [&]() -> int {
         if (!node) { set_error("mrgfe_node_align: NULL node"); return MRGFE_ERR_INVALID; }
         std::lock_guard<std::mutex> lk(node->api_mu);
-        const int n = static_cast<int>(node->pairs.size()), G = static_cast<int>(node->members.size());
+        const int n = static_cast<int>(node->pairs.size());
         if (n && !results) { set_error("mrgfe_node_align: NULL results"); return MRGFE_ERR_INVALID; }
         node->fitness_max_range = fitness_max_range;
-        // contiguous blocks, sizes differing by at most one, the first n mod G blocks the longer ones
-        const int base = n / G, extra = n % G;
-        for (int g = 0; g < G; ++g) {
-            Member* m = node->members[static_cast<size_t>(g)].get();
-            m->first = g * base + std::min(g, extra);
-            m->count = base + (g < extra ? 1 : 0);
-        }
-        {
-            TraceRange tr("mrgfe_node_align members");
-            for (auto& m : node->members) post(m.get(), JOB_ALIGN);
-            for (auto& m : node->members) wait_done(m.get());
-        }
-        for (auto& m : node->members)
-            if (m->status != MRGFE_OK) {  // the first member that failed names the error; the others have finished their blocks and are idle again
-                set_error("mrgfe_node_align: member %d (device %d): %s", m->index, m->device, m->error.c_str());
-                return m->status;
-            }
+        node->last_best = false;
+        cut_blocks(node);
+        // (after a failure the other members have finished their blocks and are idle again)
+        MRGFE_TRY(run_members(node, JOB_ALIGN, "mrgfe_node_align", "mrgfe_node_align members"));
         if (n == 0) return MRGFE_OK;
-        node->last_gather = 0;
-        if (want_rccl(node) && rccl_setup(node) == MRGFE_OK) {
-            const int per = (n + G - 1) / G;
-            TraceRange tr("mrgfe_node_align record gather (RCCL)");
-            const int st = rccl_gather(node, per, results, n);
-            if (st == MRGFE_OK) { node->last_gather = 1; return MRGFE_OK; }
-            if (const char* e = std::getenv("MRGFE_NODE_GATHER")) if (std::strcmp(e, "rccl") == 0) return st;  // asked for: do not hide the failure
+        return gather_records(node, results, n);
+    });
+}
+
+int mrgfe_node_align_best(mrgfe_node* node, double fitness_max_range, double score_cap, const int32_t* group, int n_groups, mrgfe_pair_result* results, int32_t* fit_state,
+                          int32_t* best, double* best_score)
+{
+    static const char* fn = "mrgfe_node_align_best";
+    return abi_guard(fn, [&]() -> int {
+        if (!node || n_groups < 0 || (n_groups > 0 && (!best || !best_score))) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        std::lock_guard<std::mutex> lk(node->api_mu);
+        const int    n = static_cast<int>(node->pairs.size());
+        const size_t N = static_cast<size_t>(n);
+        if (n && (!results || !group)) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        if (!(fitness_max_range >= 0) || std::isnan(score_cap)) { set_error("%s: fitness_max_range must be >= 0 and score_cap a number", fn); return MRGFE_ERR_INVALID; }
+        for (int i = 0; i < n; ++i)
+            if (group[i] < -1 || group[i] >= n_groups) { set_error("%s: group[%d] = %d is not -1 or in [0, %d)", fn, i, group[i], n_groups); return MRGFE_ERR_INVALID; }
+        node->fitness_max_range = fitness_max_range;
+        node->last_best = false;
+        node->sel_group = group;
+        node->sel_lo.assign(N, DBL_MAX);
+        node->sel_hi.assign(N, DBL_MAX);
+        node->sel_conv.assign(N, 0);
+        node->sel_state.assign(N, kFitSkipped);
+        std::fill(node->select_stats, node->select_stats + 8, 0.0);
+        cut_blocks(node);
+        if (n == 0) {  // one batch without pairs: every group is empty
+            for (int g = 0; g < n_groups; ++g) { best[g] = -1; best_score[g] = DBL_MAX; }
+            node->last_best = true;
+            return MRGFE_OK;
         }
-        for (auto& m : node->members)
-            if (m->count) std::memcpy(results + m->first, m->local.data(), sizeof(mrgfe_pair_result) * static_cast<size_t>(m->count));
+        // 1. every member: its block, the align, the intervals
+        int st = run_members(node, JOB_BOUNDS, fn, "mrgfe_node_align_best members: align and bounds");
+        if (st != MRGFE_OK) {
+            // the members whose stage succeeded hold a pending selection and may still have work of this call queued: they give it up and wait for their
+            // streams, so the caller's buffers are its own again.  (Posted from this thread like every job: a member that never got here cannot hold up another.)
+            const std::string msg = mrgfe_last_error();
+            for (auto& m : node->members) if (m->staged) post(m.get(), JOB_ABANDON);
+            for (auto& m : node->members) wait_done(m.get());
+            node->sel_group = nullptr;
+            set_error("%s", msg.c_str());
+            return st;
+        }
+        // 2. the selection over the WHOLE list.  A pair without a fitness job is SKIPPED as in one batch: an empty cloud (a grouped pair that did not
+        // converge is SKIPPED by the rule itself); its interval DBL_MAX / DBL_MAX prunes nothing (no lower bound is above DBL_MAX)
+        fit_select_prune(n, node->sel_lo.data(), node->sel_hi.data(), node->sel_conv.data(), group, n_groups, score_cap, node->sel_state.data());
+        for (int i = 0; i < n; ++i) {
+            const PairDecl& p = node->pairs[static_cast<size_t>(i)];
+            if (p.n == 0 || node->targets[static_cast<size_t>(p.target)].n == 0) node->sel_state[static_cast<size_t>(i)] = kFitSkipped;
+        }
+        // 3. every member: the exact passes of its contenders.  A member that fails here has dropped its selection; the others have finished theirs.
+        st = run_members(node, JOB_FINISH, fn, "mrgfe_node_align_best members: contenders");
+        node->sel_group = nullptr;
+        if (st != MRGFE_OK) return st;
+        MRGFE_TRY(gather_records(node, results, n));
+        // the rule on the gathered records; the states were decided here
+        std::vector<double>  fit(N);
+        std::vector<int32_t> conv(N);
+        for (int i = 0; i < n; ++i) { fit[static_cast<size_t>(i)] = results[i].fitness; conv[static_cast<size_t>(i)] = results[i].converged; }
+        fit_select_groups(n, fit.data(), conv.data(), group, n_groups, score_cap, best, best_score);
+        if (fit_state) std::memcpy(fit_state, node->sel_state.data(), sizeof(int32_t) * N);
+        for (auto& m : node->members) {
+            if (!m->count) continue;
+            double v[8];
+            MRGFE_TRY(mrgfe_batch_select_stats(m->batch.get(), v));
+            for (int k = 0; k < 6; ++k) node->select_stats[k] += v[k];
+            for (int k = 6; k < 8; ++k) node->select_stats[k] = std::max(node->select_stats[k], v[k]);
+        }
+        node->last_best = true;
         return MRGFE_OK;
     });
+}
+
+int mrgfe_node_select_stats(const mrgfe_node* node, double out[8])
+{
+    if (!node || !out) { set_error("mrgfe_node_select_stats: NULL argument"); return MRGFE_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(const_cast<mrgfe_node*>(node)->api_mu);
+    std::memcpy(out, node->select_stats, sizeof(node->select_stats));
+    return MRGFE_OK;
+}
+
+int mrgfe_dbg_node_fit_bounds(const mrgfe_node* node, double* lower, double* upper)
+{
+    if (!node || !lower || !upper) { set_error("mrgfe_dbg_node_fit_bounds: NULL argument"); return MRGFE_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(const_cast<mrgfe_node*>(node)->api_mu);
+    if (!node->last_best || node->sel_lo.size() != node->pairs.size()) { set_error("mrgfe_dbg_node_fit_bounds: no mrgfe_node_align_best on this pair list"); return MRGFE_ERR_STATE; }
+    std::copy(node->sel_lo.begin(), node->sel_lo.end(), lower);
+    std::copy(node->sel_hi.begin(), node->sel_hi.end(), upper);
+    return MRGFE_OK;
 }
 
 int mrgfe_node_shard(const mrgfe_node* node, int member, int* first_pair, int* n_pairs)

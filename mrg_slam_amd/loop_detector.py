@@ -37,7 +37,7 @@ DEFAULTS = {  # config/mrg_slam.yaml:169-179
     "fitness_score_max_range": float("inf"),
     "fitness_score_thresh": 1.25,
     # "bounded": batch 1 of detect_batched scores exactly only the candidates that can still be the best of their (new keyframe, SLAM instance)
-    # group (BatchMatcher.align_best, capped at fitness_score_thresh); the Loop list is the same as with "full"
+    # group (BatchMatcher.align_best or NodeMatcher.align_best, capped at fitness_score_thresh); the Loop list is the same as with "full"
     "fitness_selection": "full",
     "use_planar_registration_guess": False,
     "enable_loop_closure_consistency_check": True,

@@ -535,19 +535,9 @@ class BatchMatcher:
         fitness_score_thresh gate (:156-160).  Returns (records, state, best, best_score): ``state[i]`` one of FIT_EXACT / FIT_PRUNED /
         FIT_ABOVE_CAP / FIT_SKIPPED, ``best[g]`` a pair index, -1 (no converged candidate) or -2 (the group's best exceeds the cap)."""
         n = lib().mrgfe_batch_num_pairs(self._h)
-        grp = np.ascontiguousarray(np.asarray(group, dtype=np.int32).reshape(-1))
-        if grp.size != n:
-            raise ValueError(f"group has {grp.size} entries for {n} pairs")
-        n_groups = int(grp.max()) + 1 if n else 0
-        n_groups = max(n_groups, 0)
-        res = (PairResult * max(n, 1))()
-        state = np.empty(max(n, 1), dtype=np.int32)
-        best = np.empty(max(n_groups, 1), dtype=np.int32)
-        best_score = np.empty(max(n_groups, 1), dtype=np.float64)
-        cap = np.finfo(np.float64).max if score_cap is None else float(score_cap)
-        check(lib().mrgfe_batch_align_best(self._h, float(max_range), cap, grp.ctypes.data_as(_ip) if n else None, n_groups, res, state.ctypes.data_as(_ip),
-                                            best.ctypes.data_as(_ip), best_score.ctypes.data_as(_dp)))
-        return results_to_numpy(res, n), state[:n].copy(), best[:n_groups].copy(), best_score[:n_groups].copy()
+        out = _BestBuffers(n, group, score_cap)
+        check(lib().mrgfe_batch_align_best(self._h, float(max_range), *out.args()))
+        return out.result()
 
     def select_stats(self) -> dict:
         """What the last :meth:`align_best` did (``mrgfe_batch_select_stats``)."""
@@ -571,12 +561,24 @@ class BatchMatcher:
         check(lib().mrgfe_batch_align_async(self._h, fitness_max_range, buf))  # (a refused call must not replace the buffer a running align writes into)
         self._async = (buf, n)
 
+    def align_best_async(self, max_range: float, group, score_cap: float | None = None):
+        """``mrgfe_batch_align_best_async``: :meth:`align_best` on the batch's worker thread; :meth:`wait` then returns the same 4-tuple.  Bad arguments
+        are refused here, by this call; so is a second ``_async`` of either kind before :meth:`wait` (the running align keeps its buffers)."""
+        n = lib().mrgfe_batch_num_pairs(self._h)
+        out = _BestBuffers(n, group, score_cap)
+        check(lib().mrgfe_batch_align_best_async(self._h, float(max_range), *out.args()))
+        self._async = out
+
     def wait(self):
-        res, n = self._async
+        """The result of the align in flight: the records after :meth:`align_async`, (records, state, best, best_score) after :meth:`align_best_async`."""
+        pending = self._async
         try:
             check(lib().mrgfe_batch_wait(self._h))
         finally:
             self._async = None
+        if isinstance(pending, _BestBuffers):
+            return pending.result()
+        res, n = pending
         return results_to_numpy(res, n)
 
     def pair_counts(self, mode: int = -1):
@@ -666,6 +668,32 @@ class NodeMatcher:
             self._keep = []
         return results_to_numpy(res, n)
 
+    def align_best(self, max_range: float, group, score_cap: float | None = None):
+        """``mrgfe_node_align_best``: :meth:`BatchMatcher.align_best` over the node — (records, state, best, best_score) of ONE batch holding the whole
+        pair list, bit for bit, for any member count; ``best[g]`` indexes the node's pair list.  The selection is taken once over the whole list between
+        the members' two stages, so a group that straddles a block boundary is pruned as in one batch."""
+        n = lib().mrgfe_node_num_pairs(self._h)
+        out = _BestBuffers(n, group, score_cap)
+        try:
+            check(lib().mrgfe_node_align_best(self._h, float(max_range), *out.args()))
+        finally:
+            self._keep = []
+        return out.result()
+
+    def select_stats(self) -> dict:
+        """What the last :meth:`align_best` did (``mrgfe_node_select_stats``): the members' counts added up, the largest member's stage times."""
+        v = (C.c_double * 8)()
+        check(lib().mrgfe_node_select_stats(self._h, v))
+        keys = ("exact", "pruned", "above_cap", "skipped", "to_sweep", "to_far", "ms_bound", "ms_contend")
+        return dict(zip(keys, [float(x) for x in v]))
+
+    def fit_bounds(self):
+        """(lower, upper) per pair of the last :meth:`align_best` (``mrgfe_dbg_node_fit_bounds``); raises when the last align was not one."""
+        n = lib().mrgfe_node_num_pairs(self._h)
+        lo, hi = np.empty(max(n, 1)), np.empty(max(n, 1))
+        check(lib().mrgfe_dbg_node_fit_bounds(self._h, lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp)))
+        return lo[:n].copy(), hi[:n].copy()
+
     def has_cloud(self, key: int):
         """The BatchMatcher call surface (LoopDetector's matcher): a node cannot say which member will need a key before the pair list is complete, so the
         caller always hands the cloud over — the member that gets the pair uploads it only when the key is not resident there with the same point count."""
@@ -699,6 +727,30 @@ class NodeMatcher:
         best, score = np.empty(max(ng, 1), dtype=np.int32), np.empty(max(ng, 1))
         check(lib().mrgfe_node_select_best(C.cast(rec.ctypes.data, C.POINTER(PairResult)), ng, gf.ctypes.data_as(_ip), best.ctypes.data_as(_ip), score.ctypes.data_as(_dp)))
         return [(int(best[g]) if best[g] >= 0 else None, float(score[g])) for g in range(ng)]
+
+
+class _BestBuffers:
+    """The argument and output arrays of one ``*_align_best`` call (batch, its asynchronous form, node): kept alive until the result is read."""
+
+    def __init__(self, n: int, group, score_cap):
+        grp = np.ascontiguousarray(np.asarray(group, dtype=np.int32).reshape(-1))
+        if grp.size != n:
+            raise ValueError(f"group has {grp.size} entries for {n} pairs")
+        self.n, self.grp = n, grp
+        self.n_groups = max(int(grp.max()) + 1 if n else 0, 0)
+        self.res = (PairResult * max(n, 1))()
+        self.state = np.empty(max(n, 1), dtype=np.int32)
+        self.best = np.empty(max(self.n_groups, 1), dtype=np.int32)
+        self.best_score = np.empty(max(self.n_groups, 1), dtype=np.float64)
+        self.cap = np.finfo(np.float64).max if score_cap is None else float(score_cap)
+
+    def args(self):
+        """score_cap, group, n_groups, results, fit_state, best, best_score"""
+        return (self.cap, self.grp.ctypes.data_as(_ip) if self.n else None, self.n_groups, self.res, self.state.ctypes.data_as(_ip),
+                self.best.ctypes.data_as(_ip), self.best_score.ctypes.data_as(_dp))
+
+    def result(self):
+        return results_to_numpy(self.res, self.n), self.state[: self.n].copy(), self.best[: self.n_groups].copy(), self.best_score[: self.n_groups].copy()
 
 
 RESULT_DTYPE = np.dtype([("T", np.float32, (16,)), ("H", np.float64, (36,)), ("fitness", np.float64), ("trans_probability", np.float64),
