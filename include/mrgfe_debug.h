@@ -54,6 +54,20 @@ int mrgfe_dbg_set_fused_launch(int mode);
  * 1e-4 bar unconditionally, several times slower (a 130k-step chain per evaluation whatever the batch size; host-stepped rounds); 0 = the tree (default; the
  * environment variable MRGFE_NDT_REFERENCE_ORDER sets the initial value).  Any other value only asks.  Returns the setting in effect. */
 int mrgfe_dbg_set_ndt_reference_order(int mode);
+/* ---- the NDT work items and the round plan (tests/test_gpu_ndt_items.py) ------------------------------------------------------------------
+ * A derivative launch cuts a pair's source into ITEMS of ppt consecutive 256-point tiles, one partial record each, and a pair's records are added in a fixed
+ * order; a round picks ppt per kernel variant as clamp(tiles of the variant's busy pairs / wg_target, 1, max_ppt) with wg_target = CUs * MRGFE_WG_PER_CU and
+ * max_ppt = MRGFE_MAX_PPT (8).  So a pair's f64 sums are a function of its own points and of the round's ppt, and of nothing else.
+ * mrgfe_ndt_evaluate with items of `ppt` tiles (1..64, the range MRGFE_PPT accepts), for NDT_HIP and PCL_NDT_HIP: */
+int mrgfe_dbg_ndt_evaluate_ppt(mrgfe_reg* reg, const float T[16], const double p[6], int mode, int ppt, double* score, double grad[6], double hess[36]);
+/* wg_target and max_ppt of that rule during the following rounds of this process, for the device's plan kernel and the host's plan alike; 0 restores a
+ * default.  With wg_target = 2 a batch of a few thousand points runs through ppt 8, 7, ..., 1 as its pairs finish, as a full-size batch does. */
+int mrgfe_dbg_set_ndt_round_shape(int wg_target, int max_ppt);
+/* the rounds of the last align of a registration, a batch or a node member: busy pairs and work items per kernel variant, n_pairs / n_items [round][3] (either
+ * may be NULL), the first `cap` rounds.  Returns the number of rounds (>= 0) or an error code. */
+int mrgfe_dbg_reg_ndt_rounds(const mrgfe_reg* reg, int cap, uint32_t* n_pairs, uint32_t* n_items);
+int mrgfe_dbg_batch_ndt_rounds(const mrgfe_batch* b, int cap, uint32_t* n_pairs, uint32_t* n_items);
+int mrgfe_dbg_node_ndt_rounds(const mrgfe_node* node, int member, int cap, uint32_t* n_pairs, uint32_t* n_items);
 /* How getFitnessScore's far pass runs during the following calls of this process: 1 = seed + sweep (nn_fit_sweep_kernel: a near occupied
  * cell found through the occupancy words gives a radius, the occupied cells inside it are enumerated top-down with bit masks; default,
  * MRGFE_FIT_SWEEP sets the initial value), 0 = round 2's pyramid walk for every queued query.  Any other value only asks.  Returns the
@@ -102,6 +116,8 @@ void mrgfe_dbg_ctl_destroy(mrgfe_dbg_ctl* h);
 int  mrgfe_dbg_ctl_request(const mrgfe_dbg_ctl* h, int* mode, float T[16], double p[6]);
 int  mrgfe_dbg_ctl_result(mrgfe_dbg_ctl* h, double score, const double grad[6], const double hess[36], double neighbours);
 int  mrgfe_dbg_ctl_final(const mrgfe_dbg_ctl* h, float T[16], int* converged, int* iterations, int* evaluations);
+/* the f64 fields a mrgfe_pair_result takes from the optimiser: H (6 x 6 row-major) and trans_probability as they stand */
+int  mrgfe_dbg_ctl_record(const mrgfe_dbg_ctl* h, double hessian[36], double* trans_probability);
 /* The ICP_HIP loop (csrc/gicp_engine.h IcpController: pcl::IterativeClosestPoint::computeTransformation with TransformationEstimationSVD and
  * DefaultConvergenceCriteria) stepped by hand, no GPU involved — the one controller behind single registrations and batches.  Every step wants the
  * same thing: the correspondences of the source AS TRANSFORMED SO FAR (by `guess`, then by every Tm returned) and their 17 sums: [0] their number,

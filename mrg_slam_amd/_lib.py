@@ -291,6 +291,11 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_set_host_control": (C.c_int, [C.c_int]),
     "mrgfe_dbg_set_fused_launch": (C.c_int, [C.c_int]),
     "mrgfe_dbg_set_ndt_reference_order": (C.c_int, [C.c_int]),
+    "mrgfe_dbg_ndt_evaluate_ppt": (C.c_int, [_vp, _fp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "mrgfe_dbg_set_ndt_round_shape": (C.c_int, [C.c_int, C.c_int]),
+    "mrgfe_dbg_reg_ndt_rounds": (C.c_int, [_vp, C.c_int, _u32p, _u32p]),
+    "mrgfe_dbg_batch_ndt_rounds": (C.c_int, [_vp, C.c_int, _u32p, _u32p]),
+    "mrgfe_dbg_node_ndt_rounds": (C.c_int, [_vp, C.c_int, C.c_int, _u32p, _u32p]),
     "mrgfe_dbg_set_fit_sweep": (C.c_int, [C.c_int]),
     "mrgfe_dbg_set_prefilter_device_driven": (C.c_int, [C.c_int]),
     "mrgfe_dbg_floor_ransac": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(C.c_int), _fp, _ip, _szp, _ip, _ip]),
@@ -306,6 +311,7 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_ctl_request": (C.c_int, [_vp, C.POINTER(C.c_int), _fp, _dp]),
     "mrgfe_dbg_ctl_result": (C.c_int, [_vp, C.c_double, _dp, _dp, C.c_double]),
     "mrgfe_dbg_ctl_final": (C.c_int, [_vp, _fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mrgfe_dbg_ctl_record": (C.c_int, [_vp, _dp, _dp]),
     "mrgfe_dbg_icp_ctl_create": (C.c_int, [C.POINTER(RegParams), _fp, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
     "mrgfe_dbg_icp_ctl_destroy": (None, [_vp]),
     "mrgfe_dbg_icp_ctl_result": (C.c_int, [_vp, _dp, C.POINTER(C.c_int), _fp]),

@@ -413,7 +413,7 @@ int    mrgfe_reg_hessian(const mrgfe_reg* reg, double out[36])
 }
 
 // ---- NDT internals --------------------------------------------------------------------------------------------
-int mrgfe_ndt_evaluate(mrgfe_reg* reg, const float T[16], const double p[6], int mode, double* score, double grad[6], double hess[36])
+static int ndt_evaluate_ppt(mrgfe_reg* reg, const float T[16], const double p[6], int mode, int ppt, double* score, double grad[6], double hess[36])
 {
     if (!reg || !reg->ndt || !T || !p || !score || !grad || !hess) { set_error("mrgfe_ndt_evaluate: needs an NDT registration and non-NULL arguments"); return MRGFE_ERR_INVALID; }
     if (!reg->has_target || !reg->has_source) { set_error("evaluate: target / source not set"); return MRGFE_ERR_STATE; }
@@ -426,7 +426,21 @@ int mrgfe_ndt_evaluate(mrgfe_reg* reg, const float T[16], const double p[6], int
     for (int i = 0; i < 16; ++i) ident[i] = (i % 5 == 0) ? 1.0f : 0.0f;
     int pi = reg->book.add_pair_device(0, reg->d_src, reg->n_src, ident);
     if (pi < 0) return pi;
-    return e.evaluate(0, Tr, p, mode, score, grad, hess);
+    return e.evaluate(0, Tr, p, mode, score, grad, hess, ppt);
+}
+int mrgfe_ndt_evaluate(mrgfe_reg* reg, const float T[16], const double p[6], int mode, double* score, double grad[6], double hess[36])
+{
+    return ndt_evaluate_ppt(reg, T, p, mode, 1, score, grad, hess);
+}
+int mrgfe_dbg_ndt_evaluate_ppt(mrgfe_reg* reg, const float T[16], const double p[6], int mode, int ppt, double* score, double grad[6], double hess[36])
+{
+    return ndt_evaluate_ppt(reg, T, p, mode, ppt, score, grad, hess);
+}
+int mrgfe_dbg_reg_ndt_rounds(const mrgfe_reg* reg, int cap, uint32_t* n_pairs, uint32_t* n_items)
+{
+    if (!reg || !reg->ndt || cap < 0) { set_error("mrgfe_dbg_reg_ndt_rounds: needs an NDT registration"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(reg->ctx);
+    return reg->ndt->round_info(cap, n_pairs, n_items);
 }
 
 int mrgfe_knn(mrgfe_ctx* ctx, const float* cloud, size_t n, const float* query, size_t nq, size_t stride, int k, int32_t* idx, float* sqd)
@@ -1381,6 +1395,12 @@ int mrgfe_dbg_set_host_control(int mode)
 }
 int mrgfe_dbg_set_fused_launch(int mode) { return ndt_set_fused_launch(mode); }
 int mrgfe_dbg_set_ndt_reference_order(int mode) { return ndt_set_reference_order(mode); }
+int mrgfe_dbg_set_ndt_round_shape(int wg_target, int max_ppt)
+{
+    if (wg_target < 0 || max_ppt < 0 || max_ppt > 64) { set_error("mrgfe_dbg_set_ndt_round_shape: wg_target >= 0, max_ppt 0..64"); return MRGFE_ERR_INVALID; }
+    ndt_set_round_shape(static_cast<uint32_t>(wg_target), static_cast<uint32_t>(max_ppt));
+    return MRGFE_OK;
+}
 int mrgfe_dbg_set_fit_sweep(int mode) { return nn_set_fit_sweep(mode); }
 int mrgfe_dbg_set_fit_stats(int mode) { return nn_set_fit_stats(mode); }
 void mrgfe_dbg_sincosf(const float* x, size_t n, float* sin_out, float* cos_out)
@@ -1487,6 +1507,13 @@ int mrgfe_dbg_ctl_final(const mrgfe_dbg_ctl* h, float T[16], int* converged, int
     if (converged) *converged = h->c.converged() ? 1 : 0;
     if (iterations) *iterations = h->c.iterations();
     if (evaluations) *evaluations = h->c.evaluations();
+    return MRGFE_OK;
+}
+int mrgfe_dbg_ctl_record(const mrgfe_dbg_ctl* h, double hessian[36], double* trans_probability)
+{
+    if (!h || !hessian || !trans_probability) { set_error("mrgfe_dbg_ctl_record: NULL argument"); return MRGFE_ERR_INVALID; }
+    std::memcpy(hessian, h->c.hessian(), sizeof(double) * 36);
+    *trans_probability = h->c.trans_probability();
     return MRGFE_OK;
 }
 

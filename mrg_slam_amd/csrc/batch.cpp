@@ -570,6 +570,13 @@ int mrgfe_dbg_batch_fit_bounds(const mrgfe_batch* b, double* lower, double* uppe
     return MRGFE_OK;
 }
 
+int mrgfe_dbg_batch_ndt_rounds(const mrgfe_batch* b, int cap, uint32_t* n_pairs, uint32_t* n_items)
+{
+    if (!b || !b->ndt || cap < 0) { set_error("mrgfe_dbg_batch_ndt_rounds: needs an NDT batch"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(b->ctx);
+    return b->ndt->round_info(cap, n_pairs, n_items);
+}
+
 // mrgfe_batch_timing, and the caller's clouds, at the end of an align that started at `t_start` and ended with status `st`
 static int batch_align_ended(mrgfe_batch* b, std::chrono::steady_clock::time_point t_start, int st)
 {

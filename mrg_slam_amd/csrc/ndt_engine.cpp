@@ -405,6 +405,14 @@ static int host_control_mode()
 void ndt_set_host_control(int mode) { g_host_control.store(mode < -1 || mode > 1 ? -1 : mode, std::memory_order_relaxed); }
 static int env_int(const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; }
 
+// test hook (ndt_set_round_shape): 0 = the default
+static std::atomic<uint32_t> g_wg_target{0}, g_max_ppt{0};
+void ndt_set_round_shape(uint32_t wg_target, uint32_t max_ppt)
+{
+    g_wg_target.store(wg_target, std::memory_order_relaxed);
+    g_max_ppt.store(max_ppt, std::memory_order_relaxed);
+}
+
 // grid of a derivative launch: a few workgroups per resident slot; they walk the plan's items (item += gridDim.x)
 uint32_t NdtEngine::derivative_grid(int mode) const
 {
@@ -503,15 +511,19 @@ int NdtEngine::enqueue_round(uint32_t round, bool device_control, const bool wan
     hipStream_t st = ctx_->stream;
     const uint32_t P = static_cast<uint32_t>(n_pairs());
     static const uint32_t per_cu = static_cast<uint32_t>(std::max(1, env_int("MRGFE_WG_PER_CU", 4)));
-    static const uint32_t max_ppt = static_cast<uint32_t>(std::max(1, env_int("MRGFE_MAX_PPT", 8)));
+    static const uint32_t env_max_ppt = static_cast<uint32_t>(std::max(1, env_int("MRGFE_MAX_PPT", 8)));
+    // (both plans below take the same two numbers: the device's own, or the test hook's)
+    const uint32_t wg_override = g_wg_target.load(std::memory_order_relaxed), ppt_override = g_max_ppt.load(std::memory_order_relaxed);
+    const uint32_t wg_target = wg_override ? wg_override : static_cast<uint32_t>(ctx_->cu_count) * per_cu;
+    const uint32_t max_ppt = ppt_override ? ppt_override : env_max_ppt;
     if (device_control) {
-        MRGFE_TRY(ndt_launch_plan(ctx_, d_pairs_.as<NdtPairDev>(), d_evals_.as<NdtEvalDev>(), P, d_plan(), static_cast<uint32_t>(ctx_->cu_count) * per_cu, max_ppt,
+        MRGFE_TRY(ndt_launch_plan(ctx_, d_pairs_.as<NdtPairDev>(), d_evals_.as<NdtEvalDev>(), P, d_plan(), wg_target, max_ppt,
                                   static_cast<uint32_t>(forced_ppt_), round, h_info));
     } else {
         // host-stepped: the requests (filled by the caller in h_evals_) and the plan go up in ONE copy out of the pinned buffer, no plan launch
         // (round 3 sent them as two copies: a copy command per round less on the single registration's critical path)
         const size_t words = ndt_plan_words(P);
-        host_plan(plan_scratch_, static_cast<uint32_t>(ctx_->cu_count) * per_cu, max_ppt);
+        host_plan(plan_scratch_, wg_target, max_ppt);
         std::memcpy(h_evals_.as<char>() + evals_bytes_, plan_scratch_.data(), words * 4);
         MRGFE_HIP_CHECK(hipMemcpyAsync(d_evals_.p, h_evals_.p, evals_bytes_ + words * 4, hipMemcpyHostToDevice, st));
     }
@@ -785,6 +797,8 @@ int NdtEngine::align_all(NdtSnapshotPort* port)
             MRGFE_TRY(enqueue_round(static_cast<uint32_t>(round), false, want, nullptr));
             MRGFE_HIP_CHECK(hipStreamSynchronize(st));
         }
+        if (!ref_order)  // the items the host's plan cut the round into (the device-stepped path hears them from the plan kernel)
+            for (int m = 0; m < 3; ++m) info.back().n_items[m] = reinterpret_cast<const NdtPlanHead*>(plan_scratch_.data())->n_items[m];
         const auto t1 = std::chrono::steady_clock::now();
         // controller steps are independent per pair: spread them over the host worker threads for large batches
         host_parallel_for(P, kHostParallelMinPairs, [&](int b, int e) {
@@ -803,10 +817,11 @@ int NdtEngine::align_all(NdtSnapshotPort* port)
     return MRGFE_ERR_STATE;
 }
 
-int NdtEngine::evaluate(int pair, const float T[16], const double p[6], int mode, double* score, double grad[6], double hess[36])
+int NdtEngine::evaluate(int pair, const float T[16], const double p[6], int mode, double* score, double grad[6], double hess[36], int ppt)
 {
     if (pair < 0 || pair >= n_pairs()) { set_error("evaluate: pair index out of range"); return MRGFE_ERR_INVALID; }
     if (mode < 0 || mode > 2) { set_error("evaluate: mode must be 0, 1 or 2"); return MRGFE_ERR_INVALID; }
+    if (ppt < 1 || ppt > 64) { set_error("evaluate: tiles per item must be 1..64"); return MRGFE_ERR_INVALID; }  // (the range MRGFE_PPT accepts)
     MRGFE_TRY(ctx_->bind());
     MRGFE_TRY(build_targets());
     if (targets_[book_->pair(pair).target].status != MRGFE_OK) { set_error("evaluate: target has no grid"); return MRGFE_ERR_STATE; }
@@ -831,7 +846,7 @@ int NdtEngine::evaluate(int pair, const float T[16], const double p[6], int mode
     for (int i = 0; i < P; ++i) { saved[i] = ctls_[i].state(); NdtCtlState idle = saved[i]; idle.phase = NDT_DONE; ctls_[i].adopt(idle); }
     ctls_[pair].adopt(s);
     const int keep = forced_ppt_;
-    forced_ppt_ = 1;
+    forced_ppt_ = ppt;
     const int rc = (reference_order() && prm_.formulation == 0) ? reference_round() : enqueue_round(0, false, want, nullptr);
     forced_ppt_ = keep;
     for (int i = 0; i < P; ++i) ctls_[i].adopt(saved[i]);

@@ -3,6 +3,7 @@
 // PairBook (pair_book.h) that the engine reads and does not own; the clouds' device memory belongs to the book or to the caller.
 // A single pcl::Registration-style object (mrgfe_reg) is a book with one target and one pair.
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <vector>
 
@@ -32,6 +33,10 @@ int ndt_set_fused_launch(int mode);
 // NDT_OMP sums of the following alignments: 1 = the reference's own order (per-point sums, then point-order chains: ndt_ref_*_kernel; host-stepped, several
 // times slower), 0 = the tree (default; MRGFE_NDT_REFERENCE_ORDER sets the initial value); any other value only asks.  Returns the setting in effect.
 int ndt_set_reference_order(int mode);
+// test hook: the round plan's work-group target (default: CUs * MRGFE_WG_PER_CU) and its tiles-per-item cap (default MRGFE_MAX_PPT) for the following rounds of
+// this process, for the device's plan kernel and the host's plan alike; 0 restores a default.  A target of 2 lets a batch of a few thousand points walk
+// through every tiles-per-item value a full-size batch sees.
+void ndt_set_round_shape(uint32_t wg_target, uint32_t max_ppt);
 
 // A second host thread may ask a running device-controlled align_all() for snapshots (which pairs have finished, their final
 // transformations): it raises `want`; the aligning thread enqueues ndt_snapshot_kernel between two rounds and counts `issued` up; the
@@ -55,8 +60,8 @@ class NdtEngine {
 
     int build_targets(bool wait = true);  // voxelise every target not yet built; `wait`: return with the stream drained
     int align_all(NdtSnapshotPort* port = nullptr);  // run every pair to completion (port: see NdtSnapshotPort; batches under device control only)
-    // one derivative evaluation of pair `pair` (tests): mode 0/1/2
-    int evaluate(int pair, const float T_rowmajor[16], const double p[6], int mode, double* score, double grad[6], double hess[36]);
+    // one derivative evaluation of pair `pair` (tests): mode 0/1/2, items of `ppt` tiles
+    int evaluate(int pair, const float T_rowmajor[16], const double p[6], int mode, double* score, double grad[6], double hess[36], int ppt = 1);
     int aligned_cloud(int pair, float* out_xyzi_host);  // final_transformation * source
 
     int n_targets() const { return book_->n_targets(); }
@@ -90,6 +95,16 @@ class NdtEngine {
     void set_force_hash(bool f) { force_hash_ = f; }  // tests: exercise the hashed lookup on small grids
     mrgfe_ctx* ctx() const { return ctx_; }
     int rounds() const { return rounds_; }  // rounds of the last align_all()
+    // busy pairs and work items per kind of each of them, [round][3] each, the first `cap` rounds (tests: mrgfe_dbg_*_ndt_rounds); returns rounds()
+    int round_info(int cap, uint32_t* n_pairs, uint32_t* n_items) const
+    {
+        for (size_t r = 0; r < round_info_.size() && r < static_cast<size_t>(std::max(cap, 0)); ++r)
+            for (int m = 0; m < 3; ++m) {
+                if (n_pairs) n_pairs[r * 3 + m] = round_info_[r].n_pairs[m];
+                if (n_items) n_items[r * 3 + m] = round_info_[r].n_items[m];
+            }
+        return static_cast<int>(round_info_.size());
+    }
 
    private:
     mrgfe_ctx* ctx_;
@@ -125,7 +140,7 @@ class NdtEngine {
     int    rounds_ = 0;
     int      key_bits_hint_ = 0;   // key width of this engine's last single-target build + 1 (0: none yet): lets the next one sort before the host has seen its box
     uint64_t result_tag_ = 0;  // host-stepped single registration: the value its next reduction stores behind the record
-    std::vector<NdtRoundInfo> round_info_;  // busy pairs per kind of every round of the last align_all
+    std::vector<NdtRoundInfo> round_info_;  // busy pairs and items per kind of every round of the last align_all
     int upload_pairs();
     int ensure_events(size_t rounds);
     uint32_t derivative_grid(int mode) const;

@@ -649,6 +649,13 @@ int mrgfe_dbg_node_fit_bounds(const mrgfe_node* node, double* lower, double* upp
     return MRGFE_OK;
 }
 
+int mrgfe_dbg_node_ndt_rounds(const mrgfe_node* node, int member, int cap, uint32_t* n_pairs, uint32_t* n_items)
+{
+    if (!node || member < 0 || member >= static_cast<int>(node->members.size())) { set_error("mrgfe_dbg_node_ndt_rounds: bad argument"); return MRGFE_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(const_cast<mrgfe_node*>(node)->api_mu);
+    return mrgfe_dbg_batch_ndt_rounds(node->members[static_cast<size_t>(member)]->batch.get(), cap, n_pairs, n_items);
+}
+
 int mrgfe_node_shard(const mrgfe_node* node, int member, int* first_pair, int* n_pairs)
 {
     if (!node || member < 0 || member >= static_cast<int>(node->members.size())) { set_error("mrgfe_node_shard: bad argument"); return MRGFE_ERR_INVALID; }

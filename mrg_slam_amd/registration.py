@@ -59,6 +59,15 @@ def status_poses(final_transformation, msf_delta=None):
     return rel, (None if d is None else err)
 
 
+def _ndt_rounds(call):
+    """the two [rounds, 3] arrays of a ``mrgfe_dbg_*_ndt_rounds`` getter: asked once for the count, once for the rows"""
+    n = check(call(0, None, None))
+    pairs, items = np.zeros((max(n, 1), 3), dtype=np.uint32), np.zeros((max(n, 1), 3), dtype=np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    check(call(n, pairs.ctypes.data_as(u32p), items.ctypes.data_as(u32p)))
+    return pairs[:n], items[:n]
+
+
 def default_params(method: int) -> RegParams:
     p = RegParams()
     lib().mrgfe_reg_default_params(method, C.byref(p))
@@ -207,11 +216,20 @@ class NdtHip(HipRegistration):
     def mean_neighbours(self) -> float:
         return lib().mrgfe_ndt_mean_neighbours(self._h)
 
-    def evaluate(self, T, p, mode=0):
+    def evaluate(self, T, p, mode=0, ppt=None):
+        """One derivative evaluation (score, grad[6], hess[6,6]); ``ppt`` (tests): work items of that many 256-point tiles (``mrgfe_dbg_ndt_evaluate_ppt``)."""
         p = np.ascontiguousarray(p, dtype=np.float64)
         s, g, H = C.c_double(0), np.zeros(6), np.zeros((6, 6))
-        check(lib().mrgfe_ndt_evaluate(self._h, _colmajor(T).ctypes.data_as(_fp), p.ctypes.data_as(_dp), mode, C.byref(s), g.ctypes.data_as(_dp), H.ctypes.data_as(_dp)))
+        out = (C.byref(s), g.ctypes.data_as(_dp), H.ctypes.data_as(_dp))
+        if ppt is None:
+            check(lib().mrgfe_ndt_evaluate(self._h, _colmajor(T).ctypes.data_as(_fp), p.ctypes.data_as(_dp), mode, *out))
+        else:
+            check(lib().mrgfe_dbg_ndt_evaluate_ppt(self._h, _colmajor(T).ctypes.data_as(_fp), p.ctypes.data_as(_dp), mode, int(ppt), *out))
         return s.value, g, H
+
+    def ndt_rounds(self):
+        """(n_pairs, n_items), [rounds, 3] each: busy pairs and work items per kernel variant of every round of the last align (``mrgfe_dbg_reg_ndt_rounds``)."""
+        return _ndt_rounds(lambda cap, a, b: lib().mrgfe_dbg_reg_ndt_rounds(self._h, cap, a, b))
 
     def leaves(self):
         n = lib().mrgfe_ndt_num_leaves(self._h)
@@ -516,6 +534,10 @@ class BatchMatcher:
         """Rounds (plan -> derivative launches -> reduce / controller step) of the last NDT align(); ICP_HIP: its lock-step rounds."""
         return int(lib().mrgfe_batch_rounds(self._h))
 
+    def ndt_rounds(self):
+        """(n_pairs, n_items), [rounds, 3] each, of the last NDT align (``mrgfe_dbg_batch_ndt_rounds``)."""
+        return _ndt_rounds(lambda cap, a, b: lib().mrgfe_dbg_batch_ndt_rounds(self._h, cap, a, b))
+
     def set_guess(self, pair: int, guess) -> None:
         check(lib().mrgfe_batch_set_guess(self._h, pair, _colmajor(guess).ctypes.data_as(_fp)))
 
@@ -703,6 +725,10 @@ class NodeMatcher:
         a, b = C.c_int(0), C.c_int(0)
         check(lib().mrgfe_node_shard(self._h, member, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def ndt_rounds(self, member: int):
+        """(n_pairs, n_items), [rounds, 3] each, of that member's last NDT align (``mrgfe_dbg_node_ndt_rounds``)."""
+        return _ndt_rounds(lambda cap, a, b: lib().mrgfe_dbg_node_ndt_rounds(self._h, member, cap, a, b))
 
     def last_gather(self) -> str:
         return "rccl" if lib().mrgfe_node_last_gather(self._h) == 1 else "host"

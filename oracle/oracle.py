@@ -334,6 +334,10 @@ class Ndt:
         lib().orc_ndt_set_thread_sums(self._h, int(thread_sums))
         self._n_src = 0
 
+    def set_gpu_order_ppt(self, ppt):
+        """the tiles per item of the following evaluations (a batch round picks it per kernel variant: tests/ndt_items_cases.py)"""
+        lib().orc_ndt_set_gpu_order(self._h, int(ppt))
+
     def __del__(self):
         try:
             if getattr(self, "_h", None):

@@ -100,7 +100,7 @@ def test_agrees_with_pclomp_float_formulation_at_float_level():
     np.testing.assert_allclose(Ha, H2, rtol=0, atol=1e-12 * np.abs(Ha).max())
 
 
-@pytest.mark.parametrize("ppt", [1, 3])
+@pytest.mark.parametrize("ppt", [1, 3, 8])
 def test_gpu_order_mode_only_reassociates(ppt):
     """the per-point factorisation the HIP kernel uses (exact algebra) in the kernel's summation tree: the same sums to f64 rounding"""
     tgt, src, rel = _pair(n=4000, m=1500, seed=3)
