@@ -458,6 +458,76 @@ int mrgfe_deskew(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride_byte
  * T column-major 4x4 float; non-finite points pass through unchanged, intensity is copied */
 int mrgfe_transform_cloud(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride_bytes, const float T[16], float* out_xyzi);
 
+/* ---- the odometry frame in one call (ScanMatchingOdometryComponent::cloud_callback -> matching(), apps/scan_matching_odometry_component.cpp:138-150, 195-350) ----
+ * A mrgfe_odom is the state of matching() — keyframe pose and stamp, prev_trans_, the rejection counter — over ONE mrgfe_reg it borrows (the registration
+ * and its context outlive it; nothing else sets that registration's clouds while the handle is in use).  One mrgfe_odom_frame stands for pcl::fromROSMsg
+ * (:144-145), downsample (:166-187), setInputTarget on a first frame (:197-205), else setInputSource, align(prev_trans * msf_delta) (:266), the status of
+ * :268 when asked, the decisions of :270-339 (non-convergence, transform thresholding, the keyframe switch) and transformPointCloud(*cloud, odom) (:341-343).
+ * The imu / robot-odometry prediction (:213-263) is TF and message handling and stays with the caller: its result is msf_delta.
+ * Arithmetic of the state machine (csrc/odom_ctl.h): float 4x4 products row times column with every product and sum rounded to float; the thresholding
+ * delta uses the rigid inverse (R^T, -R^T t) as mrgfe_status_poses forms it; norms in float, promoted; angles acosf of the clamped Quaternionf w. */
+typedef struct mrgfe_odom mrgfe_odom;
+typedef struct mrgfe_odom_params {                 /* :98-132, config/mrg_slam.yaml:77-95                                                       */
+    int32_t downsample_method;                     /* 0 NONE (yaml default), 1 VOXELGRID, 2 APPROX_VOXELGRID                            :166-187 */
+    float   downsample_resolution;                 /* 0.1                                                                                        */
+    int32_t downsample_min_points_per_voxel;       /* 1 (VOXELGRID only)                                                                         */
+    int32_t reserved0;
+    double  keyframe_delta_translation, keyframe_delta_angle, keyframe_delta_time;   /* 1.0 m, 0.5236 rad, 10000 s                      :326-331 */
+    int32_t enable_transform_thresholding, max_consecutive_rejections;               /* 0, 5                                            :278-315 */
+    double  max_acceptable_translation, max_acceptable_angle;                        /* 1.0 m, 1.0 rad                                           */
+    double  status_max_correspondence_dist;        /* 0.5                                                                                   :413 */
+} mrgfe_odom_params;                               /* 72 bytes */
+void   mrgfe_odom_default_params(mrgfe_odom_params* out);
+size_t mrgfe_odom_params_size(void);               /* sizeof(mrgfe_odom_params) as the library was compiled */
+/* MRGFE_ERR_INVALID: a NULL argument, an unknown downsample method, a resolution that is not > 0 with a downsample, max_consecutive_rejections < 1 with
+ * thresholding on.  The handle is destroyed BEFORE its registration. */
+int    mrgfe_odom_create(mrgfe_reg* reg, const mrgfe_odom_params* params, mrgfe_odom** out);
+void   mrgfe_odom_destroy(mrgfe_odom* odom);
+int    mrgfe_odom_reset(mrgfe_odom* odom);         /* forgets the keyframe: the next frame is a first frame (:197-205).  The registration is not touched. */
+
+enum mrgfe_odom_outcome {
+    MRGFE_ODOM_FIRST_FRAME = 0,    /* :197-205: the cloud became the keyframe, odom = identity, nothing was aligned          */
+    MRGFE_ODOM_ACCEPTED = 1,       /* :317-349                                                                               */
+    MRGFE_ODOM_NOT_CONVERGED = 2,  /* :270-273: odom = keyframe_pose * prev_trans, nothing else changes                      */
+    MRGFE_ODOM_REJECTED = 3,       /* :306-307: a large transform below the rejection limit                                  */
+    MRGFE_ODOM_REJECTED_RESET = 4  /* :291-304: the rejection that reaches the limit: the frame becomes the keyframe         */
+};
+typedef struct mrgfe_odom_result {
+    int32_t  outcome;              /* enum mrgfe_odom_outcome                                                                */
+    int32_t  new_keyframe;         /* this frame's cloud became the keyframe (:203, :294-295, :332-333)                      */
+    int32_t  consecutive_rejections, converged, iterations;
+    uint32_t n_source;             /* points after the downsample                                                            */
+    float    odom[16];             /* what matching() returns, column-major                                                  */
+    float    keyframe_pose[16];    /* keyframe_pose_ as :323 reads it (before a switch made by this frame)                   */
+    float    trans[16];            /* getFinalTransformation(); the identity on FIRST_FRAME                                  */
+    int32_t  has_status, reserved; /* `status` is filled: want_status and the frame was aligned (:268)                       */
+    mrgfe_matching_status status;
+} mrgfe_odom_result;               /* 368 bytes */
+size_t mrgfe_odom_result_size(void); /* sizeof(mrgfe_odom_result) as the library was compiled */
+
+/* One frame from the message as it arrives (layout and payload as for mrgfe_keyframe_callback; an empty message is MRGFE_ERR_INVALID).
+ *   First frame: the (downsampled) cloud becomes the registration's target; afterwards the registration is exactly where mrgfe_reg_set_target of that
+ *     cloud leaves it (a target, the source untouched).
+ *   Later frames: the cloud becomes the source, align(prev_trans * msf_delta) runs, the status is taken when want_status (before every decision, and
+ *     against the keyframe the frame was aligned to), the decisions follow; when the frame becomes the keyframe the hand-over is that of
+ *     mrgfe_reg_source_becomes_target (GICP family: nothing is recomputed; NDT builds its grid).  Non-convergence is an outcome, not an error.
+ *   msf_delta: column-major 4x4 or NULL (the identity, :211).  aligned_xyzi (may be NULL): room for width * height packed points; on ACCEPTED it receives
+ *     the WHOLE input cloud, before the downsample, moved by `odom` with the bits of mrgfe_transform_cloud(cloud, odom); other outcomes leave it untouched.
+ *   The wire records go up once; one kernel gathers them straight into the buffer the registration takes over (the one mrgfe_reg_set_source uploads into)
+ *     and finds the exact box of the finite points on the way, which the GICP family's source grid is built in (no bounding-box pass of its own).  The
+ *     registration owns every cloud it keeps: `data` is free when the call returns, and a keyframe never aliases caller memory.
+ *   A failing call (a bad layout, a short payload, a NULL argument: MRGFE_ERR_INVALID; a cloud with nothing left after the downsample: MRGFE_ERR_EMPTY; an
+ *     alignment or target build that returns an error code: that code) leaves the handle's state and the registration's source and target as they were:
+ *     the next good frame gives what it would have given without the failed call.  The context lock is held once for the whole call. */
+int mrgfe_odom_frame(mrgfe_odom* odom, const mrgfe_keyframe_params* layout, const void* data, size_t data_bytes, double stamp_seconds, const float* msf_delta,
+                     int want_status, float* aligned_xyzi, mrgfe_odom_result* out);
+/* the same for a packed cloud already in HBM on the registration's device (n > 0 points of 16 bytes; the output of mrgfe_scan_callback_device): it is copied
+ * device to device into the registration's buffer, so the caller may overwrite d_xyzi as soon as the call returns.  When d_xyzi / n are what the last
+ * device-driven prefilter chain on the SAME context left (the rule of mrgfe_reg_set_source_from_prefilter) the source grid is built in the chain's box;
+ * otherwise the registration's own bounding-box pass runs. */
+int mrgfe_odom_frame_device(mrgfe_odom* odom, const void* d_xyzi, size_t n, double stamp_seconds, const float* msf_delta, int want_status, float* aligned_xyzi,
+                            mrgfe_odom_result* out);
+
 /* ---- batched candidate matching (LoopDetector::matching candidate loop, src/mrg_slam/loop_detector.cpp:126-145) ---- */
 typedef struct mrgfe_pair_result {
     float   T[16];      /* final transformation, column-major                */

@@ -143,6 +143,30 @@ int mrgfe_dbg_node_fit_bounds(const mrgfe_node* node, double* lower, double* upp
 int mrgfe_dbg_select_prune(int n_pairs, const double* lower, const double* upper, const int32_t* converged, const int32_t* group, int n_groups, double score_cap,
                            int32_t* state);
 
+/* ---- the odometry frame's state machine and head kernel (mrgfe_odom_frame; tests/test_odom_controller_cpu.py, tests/test_gpu_odometry_frame.py) ---- */
+/* The controller behind mrgfe_odom_frame (csrc/odom_ctl.h: the state and decisions of ScanMatchingOdometryComponent::matching) stepped by hand, no GPU
+ * involved; only the keyframe / thresholding fields of the params are read.  _begin: the frame's stamp and prediction (column-major or NULL) -> *aligns
+ * (0 on a first frame) and the guess of :266; it changes nothing _state shows.  _end: hasConverged() and getFinalTransformation() of that frame (final
+ * may be NULL on a first frame only) -> outcome, new_keyframe, consecutive_rejections, converged, odom, keyframe_pose and trans of `out`, the other fields
+ * zero; MRGFE_ERR_STATE without a _begin before it.  A frame that fails between the two is simply not ended. */
+typedef struct mrgfe_dbg_odom_ctl mrgfe_dbg_odom_ctl;
+typedef struct mrgfe_dbg_odom_state {
+    int32_t has_keyframe, consecutive_rejections, has_prev_time, reserved;
+    double  keyframe_stamp, prev_time;           /* keyframe_stamp_, prev_time_ (seconds) */
+    float   keyframe_pose[16], prev_trans[16];   /* column-major */
+} mrgfe_dbg_odom_state;                          /* 160 bytes */
+int  mrgfe_dbg_odom_ctl_create(const mrgfe_odom_params* params, mrgfe_dbg_odom_ctl** out);
+void mrgfe_dbg_odom_ctl_destroy(mrgfe_dbg_odom_ctl* h);
+int  mrgfe_dbg_odom_ctl_begin(mrgfe_dbg_odom_ctl* h, double stamp_seconds, const float* msf_delta, int* aligns, float guess[16]);
+int  mrgfe_dbg_odom_ctl_end(mrgfe_dbg_odom_ctl* h, int converged, const float* final_transformation, mrgfe_odom_result* out);
+int  mrgfe_dbg_odom_ctl_state(const mrgfe_dbg_odom_ctl* h, mrgfe_dbg_odom_state* out);
+/* the state of a mrgfe_odom's own controller, same record */
+int  mrgfe_dbg_odom_state_of(const mrgfe_odom* odom, mrgfe_dbg_odom_state* out);
+/* What the last successful frame of `odom` handed to the registration: the cloud (out_xyzi: room for *n points, may be NULL to ask for *n alone) and, for a
+ * message frame, the box the head kernel found over the message's finite points (box: min xyz, max xyz; +inf / -inf without a finite point) with their
+ * count; *n_finite is 0xffffffff when that frame ran no head kernel (the device form). */
+int  mrgfe_dbg_odom_source(mrgfe_odom* odom, float* out_xyzi, size_t* n, float box[6], uint32_t* n_finite);
+
 #ifdef MRGFE_TESTING
 /* hardening hook: the k-th device / pinned allocation of this process from now on (0 = the next one) fails as if the device were out of memory, every
  * later one works again; k < 0 switches the injector off (MRGFE_FAIL_ALLOC_AFTER sets the initial value).  Returns the number of allocations made

@@ -6,7 +6,7 @@ from .filters import ApproximateVoxelGrid, InformationMatrixCalculator, RadiusOu
 from .map_cloud import KeyFrameSnapshot, MapCloudGenerator, MapCloudStore, deskew, remove_points_near, transform_cloud  # noqa: F401
 from .registration import BatchMatcher, GicpHip, IcpHip, NdtHip, NodeMatcher, PclGicpHip, PclNdtHip, SmallGicpHip, VgicpHip, select_registration_method  # noqa: F401
 from .loop_detector import KeyFrame, LoopDetector  # noqa: F401,E402
-from .odometry import ScanMatchingOdometry  # noqa: F401,E402
+from .odometry import HipOdometry, ScanMatchingOdometry  # noqa: F401,E402
 from .keyframes import KeyframeCallback, KeyframeUpdater  # noqa: F401,E402
 from .graph_database import GraphDatabaseEdges  # noqa: F401,E402
 from .prefiltering import PrefilteringComponent  # noqa: F401,E402

@@ -94,6 +94,32 @@ class MatchingStatus(C.Structure):
                 ("relative_pose", C.c_double * 7), ("prediction_error", C.c_double * 7), ("has_prediction", C.c_int32), ("reserved", C.c_int32)]
 
 
+class OdomParams(C.Structure):
+    """struct mrgfe_odom_params (the scan_matching_odometry_component ROS parameters, config/mrg_slam.yaml:77-95)."""
+
+    _fields_ = [("downsample_method", C.c_int32), ("downsample_resolution", C.c_float), ("downsample_min_points_per_voxel", C.c_int32), ("reserved0", C.c_int32),
+                ("keyframe_delta_translation", C.c_double), ("keyframe_delta_angle", C.c_double), ("keyframe_delta_time", C.c_double),
+                ("enable_transform_thresholding", C.c_int32), ("max_consecutive_rejections", C.c_int32), ("max_acceptable_translation", C.c_double),
+                ("max_acceptable_angle", C.c_double), ("status_max_correspondence_dist", C.c_double)]
+
+
+class OdomResult(C.Structure):
+    """struct mrgfe_odom_result: what one ``mrgfe_odom_frame`` decided and returns (matrices column-major)."""
+
+    _fields_ = [("outcome", C.c_int32), ("new_keyframe", C.c_int32), ("consecutive_rejections", C.c_int32), ("converged", C.c_int32), ("iterations", C.c_int32),
+                ("n_source", C.c_uint32), ("odom", C.c_float * 16), ("keyframe_pose", C.c_float * 16), ("trans", C.c_float * 16), ("has_status", C.c_int32),
+                ("reserved", C.c_int32), ("status", MatchingStatus)]
+
+
+class OdomState(C.Structure):
+    """struct mrgfe_dbg_odom_state (include/mrgfe_debug.h): everything ``matching()`` keeps between frames."""
+
+    _fields_ = [("has_keyframe", C.c_int32), ("consecutive_rejections", C.c_int32), ("has_prev_time", C.c_int32), ("reserved", C.c_int32), ("keyframe_stamp", C.c_double),
+                ("prev_time", C.c_double), ("keyframe_pose", C.c_float * 16), ("prev_trans", C.c_float * 16)]
+
+
+ODOM_FIRST_FRAME, ODOM_ACCEPTED, ODOM_NOT_CONVERGED, ODOM_REJECTED, ODOM_REJECTED_RESET = 0, 1, 2, 3, 4  # enum mrgfe_odom_outcome
+ODOM_OUTCOMES = ("first_frame", "accepted", "not_converged", "rejected", "rejected_reset")
 FLOOR_REASONS = ("found", "empty_input", "none_after_clip", "too_few_filtered", "no_model", "too_few_inliers", "not_vertical")
 
 
@@ -230,6 +256,14 @@ SIGNATURES = {
     "mrgfe_remove_points_near": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, _fp, C.c_int, C.c_float, _fp, _szp, _fp, _szp]),
     "mrgfe_deskew": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, _fp, C.c_double, _fp]),
     "mrgfe_transform_cloud": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, _fp, _fp]),
+    "mrgfe_odom_default_params": (None, [C.POINTER(OdomParams)]),
+    "mrgfe_odom_params_size": (C.c_size_t, []),
+    "mrgfe_odom_result_size": (C.c_size_t, []),
+    "mrgfe_odom_create": (C.c_int, [_vp, C.POINTER(OdomParams), C.POINTER(_vp)]),
+    "mrgfe_odom_destroy": (None, [_vp]),
+    "mrgfe_odom_reset": (C.c_int, [_vp]),
+    "mrgfe_odom_frame": (C.c_int, [_vp, C.POINTER(KeyframeParams), _vp, C.c_size_t, C.c_double, _fp, C.c_int, _fp, C.POINTER(OdomResult)]),
+    "mrgfe_odom_frame_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_double, _fp, C.c_int, _fp, C.POINTER(OdomResult)]),
     "mrgfe_batch_create": (C.c_int, [_vp, C.POINTER(RegParams), C.POINTER(_vp)]),
     "mrgfe_batch_destroy": (None, [_vp]),
     "mrgfe_batch_clear": (C.c_int, [_vp]),
@@ -319,6 +353,13 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_batch_fit_bounds": (C.c_int, [_vp, _dp, _dp]),
     "mrgfe_dbg_node_fit_bounds": (C.c_int, [_vp, _dp, _dp]),
     "mrgfe_dbg_select_prune": (C.c_int, [C.c_int, _dp, _dp, _ip, _ip, C.c_int, C.c_double, _ip]),
+    "mrgfe_dbg_odom_ctl_create": (C.c_int, [C.POINTER(OdomParams), C.POINTER(_vp)]),
+    "mrgfe_dbg_odom_ctl_destroy": (None, [_vp]),
+    "mrgfe_dbg_odom_ctl_begin": (C.c_int, [_vp, C.c_double, _fp, C.POINTER(C.c_int), _fp]),
+    "mrgfe_dbg_odom_ctl_end": (C.c_int, [_vp, C.c_int, _fp, C.POINTER(OdomResult)]),
+    "mrgfe_dbg_odom_ctl_state": (C.c_int, [_vp, C.POINTER(OdomState)]),
+    "mrgfe_dbg_odom_state_of": (C.c_int, [_vp, C.POINTER(OdomState)]),
+    "mrgfe_dbg_odom_source": (C.c_int, [_vp, _fp, _szp, _fp, _u32p]),
 }
 # ... and its fault injectors and their allocation count, which exist only in the -DMRGFE_TESTING build (libmrgfe_testing.so: tests/faultinject/ runs under MRGFE_LIB=that file)
 TESTING_SIGNATURES = {
@@ -375,7 +416,8 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"libmrgfe.so was built with a mrgfe_matching_status of {L.mrgfe_matching_status_size()} bytes, the binding mirrors {C.sizeof(MatchingStatus)}")
         if hasattr(L, "mrgfe_keyframe_params_size") and L.mrgfe_keyframe_params_size() != C.sizeof(KeyframeParams):
             raise RuntimeError(f"libmrgfe.so was built with a mrgfe_keyframe_params of {L.mrgfe_keyframe_params_size()} bytes, the binding mirrors {C.sizeof(KeyframeParams)}")
-        for fn, mirror in (("mrgfe_keyframe_msg_size", KeyframeMsg), ("mrgfe_graph_edge_size", GraphEdge)):
+        for fn, mirror in (("mrgfe_keyframe_msg_size", KeyframeMsg), ("mrgfe_graph_edge_size", GraphEdge), ("mrgfe_odom_params_size", OdomParams),
+                           ("mrgfe_odom_result_size", OdomResult)):
             if hasattr(L, fn) and getattr(L, fn)() != C.sizeof(mirror):
                 raise RuntimeError(f"libmrgfe.so was built with a {fn[:-5]} of {getattr(L, fn)()} bytes, the binding mirrors {C.sizeof(mirror)}")
         _lib = L

@@ -30,28 +30,7 @@
 
 using namespace mrgfe;
 
-struct mrgfe_reg {
-    explicit mrgfe_reg(mrgfe_ctx* c) : ctx(c), book(c) {}
-    mrgfe_ctx*       ctx;
-    mrgfe_reg_params params;
-    PairBook         book;                // NDT: the target and the one pair (declared before the engine that reads it, so destroyed after it)
-    std::unique_ptr<NdtEngine>  ndt;
-    std::unique_ptr<GicpEngine> gicp;
-    DevBuf           tgt, src;            // owned copies of host-supplied clouds
-    const void*      d_tgt = nullptr;     // current clouds (owned buffer or caller's device memory)
-    const void*      d_src = nullptr;
-    size_t           n_tgt = 0, n_src = 0;
-    bool             has_target = false, has_source = false, aligned_once = false;
-    int              target_status = MRGFE_ERR_STATE;
-    NnGrid           nn;                  // exact 1-NN structure over the target (getFitnessScore / nearestKSearch)
-    bool             nn_valid = false;
-    float            final_rm[16];        // row-major
-    bool             converged = false;
-    int              iterations = 0, evaluations = 0;
-    double           trans_probability = 0;
-    double           hessian[36];
-    double           mean_neighbours = 0;
-};
+// (struct mrgfe_reg: api_internal.h — the odometry frame of odometry.cpp works on it too)
 
 extern "C" {
 

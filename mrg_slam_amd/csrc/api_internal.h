@@ -87,6 +87,30 @@ inline bool keeps_covariances(const mrgfe_reg_params& p) { return !is_ndt(p.meth
 
 }  // namespace mrgfe
 
+// one registration (api.cpp; the one-call odometry frame of odometry.cpp hands it its clouds): the engine, the clouds it owns or borrows, the last result
+struct mrgfe_reg {
+    explicit mrgfe_reg(mrgfe_ctx* c) : ctx(c), book(c) {}
+    mrgfe_ctx*       ctx;
+    mrgfe_reg_params params;
+    mrgfe::PairBook  book;                // NDT: the target and the one pair (declared before the engine that reads it, so destroyed after it)
+    std::unique_ptr<mrgfe::NdtEngine>  ndt;
+    std::unique_ptr<mrgfe::GicpEngine> gicp;
+    mrgfe::DevBuf    tgt, src;            // owned copies of host-supplied clouds
+    const void*      d_tgt = nullptr;     // current clouds (owned buffer or caller's device memory)
+    const void*      d_src = nullptr;
+    size_t           n_tgt = 0, n_src = 0;
+    bool             has_target = false, has_source = false, aligned_once = false;
+    int              target_status = MRGFE_ERR_STATE;
+    mrgfe::NnGrid    nn;                  // exact 1-NN structure over the target (getFitnessScore / nearestKSearch)
+    bool             nn_valid = false;
+    float            final_rm[16];        // row-major
+    bool             converged = false;
+    int              iterations = 0, evaluations = 0;
+    double           trans_probability = 0;
+    double           hessian[36];
+    double           mean_neighbours = 0;
+};
+
 // mrgfe_batch_align_best in two stages (batch.cpp), for a caller that takes the selection between them over more pairs than this batch holds (a node:
 // node.cpp).  Arguments are not checked here (max_range >= 0; group: n_pairs entries of -1 or a group id).
 //   batch_align_bounds: the align, the records, the fitness grids and jobs, and the bound stage of the selection.  results[i]: the record with

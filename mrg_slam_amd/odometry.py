@@ -132,3 +132,169 @@ class ScanMatchingOdometry:
         self.prev_time = stamp
         self.prev_trans = np.eye(4, dtype=np.float32)
         self.keyframes += 1
+
+
+# ---- the same frame as ONE library call (include/mrgfe.h mrgfe_odom_frame): the state machine above lives in csrc/odom_ctl.h ----------------------
+OUTCOMES = ("first_frame", "accepted", "not_converged", "rejected", "rejected_reset")  # enum mrgfe_odom_outcome
+_DOWNSAMPLE = {"NONE": 0, "VOXELGRID": 1, "APPROX_VOXELGRID": 2}
+
+
+class OdomFrame:
+    """One ``mrgfe_odom_result``: matrices as row-major 4 x 4 float arrays, ``status`` a ``registration.MatchingStatus`` or None, ``aligned`` the whole
+    input cloud moved by ``odom`` (N x 4) when it was asked for and the frame was accepted, else None; ``raw`` is the ctypes record itself."""
+
+    def __init__(self, raw, aligned):
+        from .registration import MatchingStatus
+
+        self.raw = raw
+        self.outcome = OUTCOMES[raw.outcome]
+        self.new_keyframe = bool(raw.new_keyframe)
+        self.consecutive_rejections = int(raw.consecutive_rejections)
+        self.converged = bool(raw.converged)
+        self.iterations = int(raw.iterations)
+        self.n_source = int(raw.n_source)
+        self.odom = np.array(raw.odom, dtype=np.float32).reshape(4, 4).T.copy()
+        self.keyframe_pose = np.array(raw.keyframe_pose, dtype=np.float32).reshape(4, 4).T.copy()
+        self.trans = np.array(raw.trans, dtype=np.float32).reshape(4, 4).T.copy()
+        s = raw.status
+        self.status = None
+        if raw.has_status:
+            self.status = MatchingStatus(bool(s.has_converged), int(s.n_points), int(s.num_inliers), np.float32(s.inlier_fraction), float(s.matching_error),
+                                         np.array(s.relative_pose, dtype=np.float64), np.array(s.prediction_error, dtype=np.float64) if s.has_prediction else None)
+        self.aligned = aligned
+
+
+class HipOdometry:
+    """``ScanMatchingOdometryComponent::cloud_callback`` -> ``matching()`` in one call per frame over a HIP registration (``mrgfe_odom_*``): the message's
+    bytes go up once, the cloud becomes the keyframe (first frame) or the source, is aligned from ``prev_trans * msf_delta``, and the decisions of
+    :270-339 are made by the library's controller.  ``params``: the keys of ``DEFAULTS`` plus ``downsample_method`` ("NONE" / "VOXELGRID" /
+    "APPROX_VOXELGRID"), ``downsample_resolution``, ``downsample_min_points_per_voxel`` and ``status_max_correspondence_dist``.  The registration must
+    outlive this object (it is kept referenced here)."""
+
+    def __init__(self, registration, params: dict | None = None):
+        import ctypes as C
+
+        from . import _lib
+
+        self.reg = registration
+        p = _lib.OdomParams()
+        _lib.lib().mrgfe_odom_default_params(C.byref(p))
+        for k, v in (params or {}).items():
+            if k == "downsample_method":
+                v = _DOWNSAMPLE[v] if isinstance(v, str) else int(v)
+            if not hasattr(p, k):
+                raise KeyError(k)
+            setattr(p, k, v)
+        self.params = p
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().mrgfe_odom_create(registration._h, C.byref(p), C.byref(self._h)))
+
+    def close(self):
+        from . import _lib
+
+        if getattr(self, "_h", None):
+            # the handle borrows the registration and its context: when the collector has finalised one of them first (members of a reference cycle are
+            # finalised in no particular order) the library call would touch freed memory, so the handle is dropped unfreed instead
+            reg = getattr(self, "reg", None)
+            if reg is not None and getattr(reg, "_h", None) and getattr(getattr(reg, "_ctx", None), "_h", None):
+                _lib.lib().mrgfe_odom_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _handle(self):
+        from . import _lib
+
+        if not getattr(self, "_h", None):
+            raise _lib.MrgfeError(_lib.ERR_INVALID, "the odometry handle has been destroyed")
+        return self._h
+
+    def reset(self):
+        """Forgets the keyframe: the next frame is a first frame."""
+        from . import _lib
+
+        _lib.check(_lib.lib().mrgfe_odom_reset(self._handle()))
+
+    def state(self):
+        """The controller's state (``_lib.OdomState``: keyframe pose and stamp, prev_trans, the rejection counter)."""
+        import ctypes as C
+
+        from . import _lib
+
+        s = _lib.OdomState()
+        _lib.check(_lib.lib().mrgfe_dbg_odom_state_of(self._handle(), C.byref(s)))
+        return s
+
+    @staticmethod
+    def _delta(msf_delta):
+        import ctypes as C
+
+        if msf_delta is None:
+            return None, None
+        d = np.ascontiguousarray(np.asarray(msf_delta, dtype=np.float32).T)
+        return d, d.ctypes.data_as(C.POINTER(C.c_float))
+
+    def frame(self, msg_or_cloud, stamp: float, msf_delta=None, want_status: bool = False, want_aligned: bool = False) -> OdomFrame:
+        """One frame from a PointCloud2 dict (``data``, ``width``, ``height``, ``point_step``, ``row_step``, ``fields``: name -> offset) or from an
+        N x 4 float32 cloud (sent as the packed 16-byte message)."""
+        import ctypes as C
+
+        from . import _lib
+
+        h = self._handle()
+        lay = _lib.KeyframeParams()
+        if isinstance(msg_or_cloud, dict):
+            m = msg_or_cloud
+            f = m["fields"]
+            data = m["data"]
+            lay.width, lay.height, lay.point_step, lay.row_step = int(m["width"]), int(m["height"]), int(m["point_step"]), int(m.get("row_step", 0))
+            lay.off_x, lay.off_y, lay.off_z, lay.off_intensity = int(f["x"]), int(f["y"]), int(f["z"]), int(f.get("intensity", -1))
+        else:
+            c = np.ascontiguousarray(msg_or_cloud, dtype=np.float32)
+            if c.ndim != 2 or c.shape[1] != 4:
+                raise ValueError("clouds are N x 4 float32 arrays (x, y, z, intensity)")
+            data = c.tobytes()
+            _lib.lib().mrgfe_keyframe_default_params(C.byref(lay))
+            lay.width = len(c)
+        n = lay.width * lay.height
+        aligned = np.empty((n, 4), dtype=np.float32) if want_aligned else None
+        keep, dptr = self._delta(msf_delta)
+        out = _lib.OdomResult()
+        buf = (C.c_char * len(data)).from_buffer_copy(data) if len(data) else None
+        _lib.check(_lib.lib().mrgfe_odom_frame(h, C.byref(lay), C.cast(buf, C.c_void_p) if buf is not None else None, len(data), float(stamp), dptr, int(bool(want_status)),
+                                                 None if aligned is None else aligned.ctypes.data_as(C.POINTER(C.c_float)), C.byref(out)))
+        return OdomFrame(out, aligned if (aligned is not None and out.outcome == _lib.ODOM_ACCEPTED) else None)
+
+    def frame_device(self, dev_ptr: int, n: int, stamp: float, msf_delta=None, want_status: bool = False, want_aligned: bool = False) -> OdomFrame:
+        """One frame from a packed cloud of ``n`` points already in HBM at ``dev_ptr`` (the output of ``scan_callback_to_device`` / ``prefilter_to_device``
+        on the registration's context); the buffer may be overwritten as soon as this returns."""
+        import ctypes as C
+
+        from . import _lib
+
+        h = self._handle()
+        aligned = np.empty((int(n), 4), dtype=np.float32) if want_aligned else None
+        keep, dptr = self._delta(msf_delta)
+        out = _lib.OdomResult()
+        _lib.check(_lib.lib().mrgfe_odom_frame_device(h, C.c_void_p(dev_ptr), int(n), float(stamp), dptr, int(bool(want_status)),
+                                                        None if aligned is None else aligned.ctypes.data_as(C.POINTER(C.c_float)), C.byref(out)))
+        return OdomFrame(out, aligned if (aligned is not None and out.outcome == _lib.ODOM_ACCEPTED) else None)
+
+    def source(self):
+        """(cloud N x 4, box of 6 floats, finite count or None) of the last frame: ``mrgfe_dbg_odom_source``."""
+        import ctypes as C
+
+        from . import _lib
+
+        n = C.c_size_t(0)
+        box = np.zeros(6, dtype=np.float32)
+        nf = C.c_uint32(0)
+        fp = C.POINTER(C.c_float)
+        _lib.check(_lib.lib().mrgfe_dbg_odom_source(self._handle(), None, C.byref(n), box.ctypes.data_as(fp), C.byref(nf)))
+        cloud = np.empty((n.value, 4), dtype=np.float32)
+        _lib.check(_lib.lib().mrgfe_dbg_odom_source(self._handle(), cloud.ctypes.data_as(fp), C.byref(n), box.ctypes.data_as(fp), C.byref(nf)))
+        return cloud, box, (None if nf.value == 0xFFFFFFFF else int(nf.value))
