@@ -553,6 +553,15 @@ typedef struct mrgfe_batch mrgfe_batch;
 int  mrgfe_batch_create(mrgfe_ctx* ctx, const mrgfe_reg_params* params, mrgfe_batch** out);
 void mrgfe_batch_destroy(mrgfe_batch* b);
 int  mrgfe_batch_clear(mrgfe_batch* b);
+/* Forgets the PAIRS and keeps the targets with everything built for them — NDT voxel grids, GICP target covariances and grids or voxel maps, ICP target
+ * grids, getFitnessScore grids — and the device copies of the host clouds the batch uploaded.  The keyframe store, the epoch and mrgfe_batch_timing
+ * behave as after mrgfe_batch_clear (stored keyframes stay, none is referenced by a pair; the next align's time starts here), except that the targets
+ * stay referenced.  Pairs added afterwards may name the old target indices (an index out of range is refused as always), and the next
+ * mrgfe_batch_align / _align_best / _async returns the records a fresh batch holding the same targets and those pairs returns, bit for bit, for every
+ * batch method: a pair's sums depend on its own clouds and guess and on the pair list (the round plan's tiles per item), never on a target.  A target no pair names enters no launch and no NDT round plan.  This is what a
+ * second matching stage against the same target is in the reference: registration_->setInputTarget(new_keyframe->cloud) happens ONCE per new keyframe
+ * (loop_detector.cpp:104) before the candidate loop (:126-145) and the consistency alignments (:222-231, :265-274) alike. */
+int  mrgfe_batch_clear_pairs(mrgfe_batch* b);
 /* returns the target index (>= 0) or an error (< 0) */
 int  mrgfe_batch_add_target(mrgfe_batch* b, const float* xyzi, size_t n, size_t stride_bytes);
 int  mrgfe_batch_add_target_device(mrgfe_batch* b, const void* d_xyzi, size_t n);
@@ -661,6 +670,85 @@ int  mrgfe_batch_select_stats(const mrgfe_batch* b, double out[8]);
 int  mrgfe_batch_align_best_async(mrgfe_batch* b, double fitness_max_range, double score_cap, const int32_t* group /* n_pairs */, int n_groups,
                                   mrgfe_pair_result* results /* n_pairs */, int32_t* fit_state /* n_pairs, nullable */, int32_t* best /* n_groups */,
                                   double* best_score /* n_groups */);
+
+/* ---- LoopDetector::detect in one call over the map store (src/mrg_slam/loop_detector.cpp:15-303) -----------------------------------------
+ * A mrgfe_loop is the state of a LoopDetector — the LoopManager (include/mrg_slam/loop_detector.hpp:39-115) and the counters of :22-34 — over ONE batch
+ * and ONE map store it borrows (both outlive it and sit on one device; nothing else queues on that batch while a detect call runs).  One
+ * mrgfe_loop_detect stands for the loop of :17-36 over the new keyframes: find_candidates (:41-95), matching (:97-180) with its candidate loop
+ * (:126-145), the fitness gate (:156-160), the consistency check (:162-166, :190-303) and LoopManager::add_loop (:176), in the batched form of
+ * mrg_slam_amd/loop_detector.py::detect_batched:
+ *   1. the candidate supersets: :41-76 WITHOUT the LoopManager gates of :77-90 (the gates only remove candidates, and all of a SLAM instance or none);
+ *   2. stage 1: ONE batch over all (new keyframe, candidate) pairs, one target per new keyframe that has pairs — mrgfe_batch_align, or with
+ *      fitness_selection 1 mrgfe_batch_align_best grouped by (new keyframe, slam_id) and capped at fitness_score_thresh;
+ *   3. the best match (:137-144: the last of equal scores wins, non-converged candidates never) of every subset of gated instances;
+ *   4. mrgfe_batch_clear_pairs: the targets stay built;
+ *   5. stage 2: the previous and next keyframe of those best matches against the same targets (:222-231, :265-274), no fitness;
+ *   6. the replay, keyframe after keyframe, of :21-31 with the gates of :77-90, :137-144, :156-166 and :190-303 on the records — `prev` is tried before
+ *      `next`, first and static keyframes are consistent without an alignment, a loop found for new keyframe k prunes the candidates of k + 1;
+ *   7. add_loop for every loop.
+ * Same loops as the sequential loop.  Clouds are named by map-store key alone (mrgfe_batch_add_target_from_store / _add_pair_from_store).  OUT OF SCOPE:
+ * host clouds; mrgfe_node_* (it has no store form); the PCL_GICP_* methods (batches refuse them, and that stays).
+ * Arithmetic (csrc/loop_ctl.h): normalize_estimate and the guess in double, cast to float (:124,129-133,183-188; Isometry3d::inverse() is the rigid
+ * inverse); the consistency deltas (:242-245, :285-291) with Matrix4f products, the general float inverse and Quaternionf::angularDistance. */
+typedef struct mrgfe_loop mrgfe_loop;
+typedef struct mrgfe_loop_params {                  /* config/mrg_slam.yaml:169-179                                                           */
+    double  candidate_max_xy_distance;              /* 15.0                                                                          :60-65 */
+    double  accum_distance_thresh_same_robot;       /* 15.0                                                                    :68-73,81-84 */
+    double  accum_distance_thresh_other_robot;      /* 5.0                                                                           :85-89 */
+    double  fitness_score_max_range;                /* +inf                                                                            :136 */
+    double  fitness_score_thresh;                   /* 1.25                                                                        :156-160 */
+    double  loop_closure_consistency_max_delta_trans;  /* 0.3 m                                                               :246,292 */
+    double  loop_closure_consistency_max_delta_angle;  /* 0.0523599 rad                                                       :246,292 */
+    int32_t fitness_selection;                      /* 0 full (mrgfe_batch_align), 1 bounded (mrgfe_batch_align_best): same loops             */
+    int32_t use_planar_registration_guess;          /* 0                                                                           :131-133 */
+    int32_t enable_loop_closure_consistency_check;  /* 1                                                                           :162,196 */
+    int32_t reserved;
+} mrgfe_loop_params;                                /* 72 bytes */
+void   mrgfe_loop_default_params(mrgfe_loop_params* out);
+size_t mrgfe_loop_params_size(void);                /* sizeof(mrgfe_loop_params) as the library was compiled */
+typedef struct mrgfe_loop_keyframe {                /* the slice of KeyFrame the detector reads (include/mrg_slam/keyframe.hpp)                 */
+    uint64_t key;                                   /* the map-store key of the cloud, non-zero                                                */
+    uint64_t slam_id;                               /* any stable id of slam_uuid                                                              */
+    double   estimate[16];                          /* node->estimate().matrix(), column-major                                                 */
+    double   accum_distance;
+    int32_t  first_keyframe, static_keyframe;
+    uint64_t prev_key, next_key;                    /* prev_edge->to_keyframe / next_edge->from_keyframe (:213,256); 0: no such edge           */
+    double   prev_relpose[16], next_relpose[16];    /* prev_edge->relative_pose() / next_edge->relative_pose() (:226,269), column-major        */
+} mrgfe_loop_keyframe;                              /* 432 bytes */
+size_t mrgfe_loop_keyframe_size(void);              /* sizeof(mrgfe_loop_keyframe) as the library was compiled */
+typedef struct mrgfe_loop_result {                  /* a Loop (loop_detector.hpp:23-37)                                                        */
+    uint64_t key1, key2;                            /* the new keyframe, the best matched candidate                                            */
+    float    relative_pose[16];                     /* key1 -> key2: getFinalTransformation() of that pair, column-major, copied from its record */
+    double   score;                                 /* its fitness score                                                                       */
+} mrgfe_loop_result;                                /* 88 bytes */
+size_t mrgfe_loop_result_size(void);                /* sizeof(mrgfe_loop_result) as the library was compiled */
+/* MRGFE_ERR_INVALID: a NULL argument (batch and store may be NULL only once mrgfe_dbg_loop_set_aligner has replaced them, include/mrgfe_debug.h: a
+ * detector created with both NULL refuses to detect until then), fitness_selection not 0 or 1.  The handle is destroyed BEFORE its batch and store. */
+int    mrgfe_loop_create(mrgfe_batch* batch, mrgfe_map_store* store, const mrgfe_loop_params* params, mrgfe_loop** out);
+void   mrgfe_loop_destroy(mrgfe_loop* det);
+int    mrgfe_loop_reset(mrgfe_loop* det);           /* forgets the loops (the LoopManager) and the counters; the batch and the store are not touched */
+/* keyframes: the keyframes of the graph in the reference's order (candidate order decides ties); new_keyframes: those that test for a loop (:17);
+ * edge_keys: 2 keys per edge, the unordered pairs of KeyFrame::edge_exists (:55).  loops_out: room for `capacity` records, *n_loops the loops found.
+ * MRGFE_ERR_INVALID, before anything is queued: a key 0; a prev_key / next_key of `keyframes` that appears in neither list; a key the store lacks
+ * (named in mrgfe_last_error(); checked are the new keyframes that have candidates, their candidates, and the neighbours the consistency check can
+ * reach); capacity too small (*n_loops = the loops found; then, after the alignments).  Any failing call — also a failing align — leaves the
+ * LoopManager, the counters, mrgfe_loop_stats and mrgfe_loop_timing as they were.  With n_new == 0, no keyframes or no candidates the call returns
+ * MRGFE_OK with 0 loops and touches no GPU. */
+int    mrgfe_loop_detect(mrgfe_loop* det, int n_keyframes, const mrgfe_loop_keyframe* keyframes, int n_new, const mrgfe_loop_keyframe* new_keyframes, int n_edges,
+                         const uint64_t* edge_keys /* 2 per edge */, mrgfe_loop_result* loops_out, int capacity, int* n_loops);
+/* the last successful call (all 0 but out[3] when it had no candidates): out[0] superset pairs (stage 1), out[1] sequential pairs (the candidates the reference's loop would
+ * have aligned), out[2] consistency pairs (stage 2), out[3] new keyframes, out[4] target_builds: the targets the two stages queued for building — the new
+ * keyframes that had candidates, since stage 2 runs on the targets stage 1 built */
+int    mrgfe_loop_stats(const mrgfe_loop* det, int64_t out[5]);
+/* The reference's only performance counters (:22-34, written out as average_time_per_candidate_us by apps/mrg_slam_component.cpp:1032-1037), since
+ * create / reset: loop_candidates_sizes and loop_detection_times (microseconds) per new keyframe that had candidates after the gates; a call's time is
+ * shared out by candidate count.  candidates / micros: room for `capacity` entries each (may be NULL with capacity 0); *n the entries there are. */
+int    mrgfe_loop_timing(const mrgfe_loop* det, int capacity, int32_t* candidates, int64_t* micros, int* n);
+/* The arithmetic of :183-188 and of :124,129-133 alone, on the host, no context (as mrgfe_status_poses): normalize_estimate — linear() =
+ * Quaterniond(linear()).normalized().toRotationMatrix() — and the guess (new_estimate.inverse() * normalize_estimate(candidate)).cast<float>(), its z
+ * translation zeroed when planar (:131-133).  Matrices column-major; `in` and `out` may be the same array. */
+int    mrgfe_loop_normalize_estimate(const double in[16], double out[16]);
+int    mrgfe_loop_guess(const double new_estimate_normalized[16], const double candidate_estimate[16], int planar, float guess[16]);
 
 /* ---- the same batch over the GPUs of one node ---------------------------------------------------------------------------
  * LoopDetector::matching runs in ONE host process per robot (src/mrg_slam/loop_detector.cpp:104,126-145 under mrg_slam_component's main

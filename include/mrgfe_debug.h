@@ -167,6 +167,22 @@ int  mrgfe_dbg_odom_state_of(const mrgfe_odom* odom, mrgfe_dbg_odom_state* out);
  * count; *n_finite is 0xffffffff when that frame ran no head kernel (the device form). */
 int  mrgfe_dbg_odom_source(mrgfe_odom* odom, float* out_xyzi, size_t* n, float box[6], uint32_t* n_finite);
 
+/* ---- the one-call loop detector without a GPU, and its stage reuse (mrgfe_loop_detect; tests/test_loop_ctl_cpu.py, profiles/loop_detect_profile.py) ---- */
+/* Replaces BOTH stages' GPU batches of `det` by a callback (fn NULL: the batches again).  A stage hands it its targets (target_keys: the new
+ * keyframes' store keys), its pairs (pair_target indexes target_keys; source_keys; guesses: 16 column-major floats per pair) and want_fitness (stage 1:
+ * 1, stage 2: 0); the callback fills results[i].T, .converged and, when want_fitness, .fitness of every pair (the records arrive zeroed, fitness
+ * DBL_MAX) and returns MRGFE_OK or an error code, which mrgfe_loop_detect returns.  With an aligner set the batch and the store are never touched, and a
+ * detector may have been created with both NULL.  Runs without a GPU, like mrgfe_dbg_select_prune. */
+typedef int (*mrgfe_dbg_loop_aligner)(void* user, int stage, int n_targets, const uint64_t* target_keys, int n_pairs, const int32_t* pair_target,
+                                      const uint64_t* source_keys, const float* guesses, int want_fitness, mrgfe_pair_result* results);
+int  mrgfe_dbg_loop_set_aligner(mrgfe_loop* det, mrgfe_dbg_loop_aligner fn, void* user);
+/* on = 0: stage 2 clears the batch and queues its targets again (the composed route's mrgfe_batch_clear between the two batches), so they are built a
+ * second time; 1 (the default): mrgfe_batch_clear_pairs.  Same loops either way.  Returns the previous setting. */
+int  mrgfe_dbg_loop_set_stage_reuse(mrgfe_loop* det, int on);
+/* the LoopManager of `det`: 4 words per entry — the new keyframe's slam_id, the candidate's slam_id, key1, key2 — ordered by the two ids; out: room for
+ * `capacity` entries (may be NULL with capacity 0), *n the entries there are */
+int  mrgfe_dbg_loop_manager(const mrgfe_loop* det, int capacity, uint64_t* out, int* n);
+
 #ifdef MRGFE_TESTING
 /* hardening hook: the k-th device / pinned allocation of this process from now on (0 = the next one) fails as if the device were out of memory, every
  * later one works again; k < 0 switches the injector off (MRGFE_FAIL_ALLOC_AFTER sets the initial value).  Returns the number of allocations made

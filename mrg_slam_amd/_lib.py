@@ -118,6 +118,28 @@ class OdomState(C.Structure):
                 ("prev_time", C.c_double), ("keyframe_pose", C.c_float * 16), ("prev_trans", C.c_float * 16)]
 
 
+class LoopParams(C.Structure):
+    """struct mrgfe_loop_params (the loop detector's ROS parameters, config/mrg_slam.yaml:169-179)."""
+
+    _fields_ = [("candidate_max_xy_distance", C.c_double), ("accum_distance_thresh_same_robot", C.c_double), ("accum_distance_thresh_other_robot", C.c_double),
+                ("fitness_score_max_range", C.c_double), ("fitness_score_thresh", C.c_double), ("loop_closure_consistency_max_delta_trans", C.c_double),
+                ("loop_closure_consistency_max_delta_angle", C.c_double), ("fitness_selection", C.c_int32), ("use_planar_registration_guess", C.c_int32),
+                ("enable_loop_closure_consistency_check", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LoopKeyframe(C.Structure):
+    """struct mrgfe_loop_keyframe: the slice of KeyFrame ``mrgfe_loop_detect`` reads (matrices column-major)."""
+
+    _fields_ = [("key", C.c_uint64), ("slam_id", C.c_uint64), ("estimate", C.c_double * 16), ("accum_distance", C.c_double), ("first_keyframe", C.c_int32),
+                ("static_keyframe", C.c_int32), ("prev_key", C.c_uint64), ("next_key", C.c_uint64), ("prev_relpose", C.c_double * 16), ("next_relpose", C.c_double * 16)]
+
+
+class LoopResult(C.Structure):
+    """struct mrgfe_loop_result: one Loop of ``mrgfe_loop_detect`` (relative_pose column-major)."""
+
+    _fields_ = [("key1", C.c_uint64), ("key2", C.c_uint64), ("relative_pose", C.c_float * 16), ("score", C.c_double)]
+
+
 ODOM_FIRST_FRAME, ODOM_ACCEPTED, ODOM_NOT_CONVERGED, ODOM_REJECTED, ODOM_REJECTED_RESET = 0, 1, 2, 3, 4  # enum mrgfe_odom_outcome
 ODOM_OUTCOMES = ("first_frame", "accepted", "not_converged", "rejected", "rejected_reset")
 FLOOR_REASONS = ("found", "empty_input", "none_after_clip", "too_few_filtered", "no_model", "too_few_inliers", "not_vertical")
@@ -267,6 +289,7 @@ SIGNATURES = {
     "mrgfe_batch_create": (C.c_int, [_vp, C.POINTER(RegParams), C.POINTER(_vp)]),
     "mrgfe_batch_destroy": (None, [_vp]),
     "mrgfe_batch_clear": (C.c_int, [_vp]),
+    "mrgfe_batch_clear_pairs": (C.c_int, [_vp]),
     "mrgfe_batch_add_target": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t]),
     "mrgfe_batch_add_target_device": (C.c_int, [_vp, _vp, C.c_size_t]),
     "mrgfe_batch_add_pair": (C.c_int, [_vp, C.c_int, _fp, C.c_size_t, C.c_size_t, _fp]),
@@ -312,7 +335,22 @@ SIGNATURES = {
     "mrgfe_batch_rounds": (C.c_int, [_vp]),
     "mrgfe_batch_timing": (C.c_int, [_vp, _dp]),
     "mrgfe_batch_timing_reset": (C.c_int, [_vp]),
+    "mrgfe_loop_default_params": (None, [C.POINTER(LoopParams)]),
+    "mrgfe_loop_params_size": (C.c_size_t, []),
+    "mrgfe_loop_keyframe_size": (C.c_size_t, []),
+    "mrgfe_loop_result_size": (C.c_size_t, []),
+    "mrgfe_loop_create": (C.c_int, [_vp, _vp, C.POINTER(LoopParams), C.POINTER(_vp)]),
+    "mrgfe_loop_destroy": (None, [_vp]),
+    "mrgfe_loop_reset": (C.c_int, [_vp]),
+    "mrgfe_loop_detect": (C.c_int, [_vp, C.c_int, C.POINTER(LoopKeyframe), C.c_int, C.POINTER(LoopKeyframe), C.c_int, C.POINTER(C.c_uint64), C.POINTER(LoopResult), C.c_int,
+                                    C.POINTER(C.c_int)]),
+    "mrgfe_loop_stats": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "mrgfe_loop_timing": (C.c_int, [_vp, C.c_int, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "mrgfe_loop_normalize_estimate": (C.c_int, [_dp, _dp]),
+    "mrgfe_loop_guess": (C.c_int, [_dp, _dp, C.c_int, _fp]),
 }
+# mrgfe_dbg_loop_aligner (include/mrgfe_debug.h): the callback that stands in for both stages' GPU batches
+LOOP_ALIGNER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int, _ip, C.POINTER(C.c_uint64), _fp, C.c_int, C.POINTER(PairResult))
 
 # include/mrgfe_debug.h: diagnostic entry points (exported by the shipped library) ...
 DEBUG_SIGNATURES = {
@@ -360,6 +398,9 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_odom_ctl_state": (C.c_int, [_vp, C.POINTER(OdomState)]),
     "mrgfe_dbg_odom_state_of": (C.c_int, [_vp, C.POINTER(OdomState)]),
     "mrgfe_dbg_odom_source": (C.c_int, [_vp, _fp, _szp, _fp, _u32p]),
+    "mrgfe_dbg_loop_set_aligner": (C.c_int, [_vp, _vp, _vp]),  # (the callback goes in as ctypes.cast(LOOP_ALIGNER(fn), c_void_p); NULL: the GPU batches again)
+    "mrgfe_dbg_loop_set_stage_reuse": (C.c_int, [_vp, C.c_int]),
+    "mrgfe_dbg_loop_manager": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
 }
 # ... and its fault injectors and their allocation count, which exist only in the -DMRGFE_TESTING build (libmrgfe_testing.so: tests/faultinject/ runs under MRGFE_LIB=that file)
 TESTING_SIGNATURES = {
@@ -417,7 +458,8 @@ def lib() -> C.CDLL:
         if hasattr(L, "mrgfe_keyframe_params_size") and L.mrgfe_keyframe_params_size() != C.sizeof(KeyframeParams):
             raise RuntimeError(f"libmrgfe.so was built with a mrgfe_keyframe_params of {L.mrgfe_keyframe_params_size()} bytes, the binding mirrors {C.sizeof(KeyframeParams)}")
         for fn, mirror in (("mrgfe_keyframe_msg_size", KeyframeMsg), ("mrgfe_graph_edge_size", GraphEdge), ("mrgfe_odom_params_size", OdomParams),
-                           ("mrgfe_odom_result_size", OdomResult)):
+                           ("mrgfe_odom_result_size", OdomResult), ("mrgfe_loop_params_size", LoopParams), ("mrgfe_loop_keyframe_size", LoopKeyframe),
+                           ("mrgfe_loop_result_size", LoopResult)):
             if hasattr(L, fn) and getattr(L, fn)() != C.sizeof(mirror):
                 raise RuntimeError(f"libmrgfe.so was built with a {fn[:-5]} of {getattr(L, fn)()} bytes, the binding mirrors {C.sizeof(mirror)}")
         _lib = L

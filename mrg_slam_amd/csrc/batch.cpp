@@ -1,7 +1,8 @@
 // csrc/batch.cpp — mrgfe_batch: the candidate batch behind loop closure, the node (mrgfe_node_*), the loop detector and the keyframe store.  A PairBook
 // says which pairs there are; the method's engine runs their rounds (NdtEngine for the NDTs, GicpBatch over one GicpEngine per target for the LM GICPs and
 // ICP_HIP); the fitness passes — overlapped with the rounds for NDT (FitOverlap) — fill in getFitnessScore; one writer makes the records.  Also here: the
-// batch's keyframe store and its asynchronous worker.  Entry points follow the rules of api.cpp: codes and a thread-local message, no exception crosses.
+// batch's keyframe store, its asynchronous worker, and mrgfe_batch_clear_pairs (the pairs go, the targets and what was built for them stay).  Entry
+// points follow the rules of api.cpp: codes and a thread-local message, no exception crosses.
 #include <atomic>
 #include <cfloat>
 #include <condition_variable>
@@ -37,6 +38,10 @@ struct mrgfe_batch {
     std::vector<GicpBatchPair> gicp_pairs;  // per-pair device buffers, kept between align calls
     std::vector<NnGrid> fit_grids;  // getFitnessScore grids, one per target; device buffers kept between align calls
     std::vector<std::unique_ptr<NnGridSet>> fit_sets;  // ... which are views into these when the grids were built a chunk of targets at a time
+    // mrgfe_batch_clear_pairs keeps the targets: their fitness grids stay good (fit_valid, per target), and so do the sets the valid grids are views
+    // into (the first fit_sets_used of fit_sets: a later build takes the sets behind them).  mrgfe_batch_clear forgets both.
+    std::vector<char>   fit_valid;
+    size_t              fit_sets_used = 0;
     // keyframe store (mrgfe_batch_add_pair_keyed): packed clouds and GICP covariances by caller-chosen key, resident across clears
     struct Keyframe {
         DevBuf   cloud, cov;
@@ -269,9 +274,23 @@ int mrgfe_batch_clear(mrgfe_batch* b)
     b->book.clear();
     if (b->ndt) b->ndt->clear();
     b->gicp.clear();  // their cached target state belongs to the clouds just forgotten
+    b->fit_valid.clear();
+    b->fit_sets_used = 0;
     b->pair_key.clear();
     ++b->epoch;  // stored keyframes stay; none is referenced by the (now empty) batch
     b->t_queue = std::chrono::steady_clock::now();  // mrgfe_batch_timing: the next align's time starts where its queueing starts
+    b->t_queue_set = true;
+    return MRGFE_OK;
+}
+int mrgfe_batch_clear_pairs(mrgfe_batch* b)
+{
+    if (!b) { set_error("NULL batch"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(b->ctx);
+    // the targets, the engines' state for them (NdtEngine's grids, one GicpEngine per target, the fitness grids) and the book's uploads stay
+    b->book.clear_pairs();
+    b->pair_key.clear();
+    ++b->epoch;
+    b->t_queue = std::chrono::steady_clock::now();
     b->t_queue_set = true;
     return MRGFE_OK;
 }
@@ -731,6 +750,7 @@ struct FitOverlap {
     std::vector<char>  built;       // per target: its fitness grid is built in this call
     std::vector<char>  early_done;  // per pair: scored by the early pass
     std::vector<int>   todo;        // the targets the builders make, in chunks
+    size_t             set_base = 0, sets_taken = 0;  // ... into b->fit_sets[set_base .. set_base + sets_taken)
     std::unique_ptr<std::atomic<char>[]> grid_ready;  // per target: its fitness grid is complete (set by the builder that made it)
     std::vector<std::thread> threads;
     std::mutex         mu;
@@ -774,7 +794,12 @@ struct FitOverlap {
             built.resize(T, 0);
             if (b->fit_grids.size() < static_cast<size_t>(T)) b->fit_grids.resize(T);
             grid_ready.reset(new std::atomic<char>[std::max(1, T)]);
-            for (int t = 0; t < T; ++t) grid_ready[t].store(0, std::memory_order_relaxed);
+            // (a target whose grid an earlier align of these targets built — mrgfe_batch_clear_pairs — is ready as it stands)
+            for (int t = 0; t < T; ++t) {
+                const char valid = static_cast<size_t>(t) < b->fit_valid.size() ? b->fit_valid[t] : 0;
+                built[t] = valid;
+                grid_ready[t].store(valid, std::memory_order_relaxed);
+            }
             for (int i = 0; i < P; ++i) {
                 const PairBook::Pair& p = e.pair(i);
                 if (e.target(p.target).n == 0 || p.n == 0 || built[p.target]) continue;
@@ -791,7 +816,9 @@ struct FitOverlap {
             const size_t n_chunks = (todo.size() + chunk - 1) / chunk;
             if (n_builders == 0) n_builders = n_chunks > 8 ? 2 : 1;
             n_builders = std::min(n_builders, n_chunks);
-            while (b->fit_sets.size() < n_chunks) b->fit_sets.emplace_back(new NnGridSet());
+            set_base = b->fit_sets_used;
+            sets_taken = n_chunks;
+            while (b->fit_sets.size() < set_base + n_chunks) b->fit_sets.emplace_back(new NnGridSet());
             while (b->fit_ctxs.size() < n_builders) {
                 mrgfe_ctx* fc = nullptr;
                 if (ctx_create_like(b->ctx, &fc) != MRGFE_OK) return MRGFE_ERR_HIP;  // (same compute-unit mask as the batch's own context)
@@ -830,7 +857,7 @@ struct FitOverlap {
                             sizes.push_back(static_cast<uint32_t>(T.n));
                             views.push_back(&b->fit_grids[todo[k]]);
                         }
-                        const int st = b->fit_sets[c]->build(fc, clouds.data(), sizes.data(), static_cast<int>(k1 - k0), 1.0f, NnGrid::kCrowding1nn, 1, views.data());  // returns with the grids complete (synchronised)
+                        const int st = b->fit_sets[set_base + c]->build(fc, clouds.data(), sizes.data(), static_cast<int>(k1 - k0), 1.0f, NnGrid::kCrowding1nn, 1, views.data());  // returns with the grids complete (synchronised)
                         if (st != MRGFE_OK) { fail(st, mrgfe_last_error()); return; }
                         for (size_t k = k0; k < k1; ++k) grid_ready[todo[k]].store(1, std::memory_order_release);
                     }
@@ -957,6 +984,8 @@ static int batch_fitness(mrgfe_batch* b, double max_range, mrgfe_pair_result* re
     std::vector<NnGrid>& grids = b->fit_grids;
     if (grids.size() < static_cast<size_t>(e.n_targets())) grids.resize(e.n_targets());
     if (built.size() < static_cast<size_t>(e.n_targets())) built.resize(e.n_targets(), 0);
+    if (b->fit_valid.size() < static_cast<size_t>(e.n_targets())) b->fit_valid.resize(e.n_targets(), 0);
+    for (int t = 0; t < e.n_targets(); ++t) built[t] = built[t] || b->fit_valid[t];
     if (sel_group) {
         b->fit_lo.assign(P, DBL_MAX);
         b->fit_hi.assign(P, DBL_MAX);
@@ -969,6 +998,7 @@ static int batch_fitness(mrgfe_batch* b, double max_range, mrgfe_pair_result* re
         if (t.n == 0 || p.n == 0 || (static_cast<size_t>(i) < early_skip.size() && early_skip[i])) continue;
         if (sel_group && sel_group[i] >= 0 && !results[i].converged) continue;
         if (!built[p.target]) { built[p.target] = 1; MRGFE_TRY(grids[p.target].build(b->ctx, t.d_pts, t.n, 1.0f, NnGrid::kCrowding1nn, 1)); }
+        b->fit_valid[p.target] = 1;
         jobs.push_back(grids[p.target].make_fitness_job(p.d_src, p.n, &b->final_rm[size_t(i) * 16]));
         job_pair.push_back(i);
     }
@@ -1002,6 +1032,10 @@ static int batch_align_impl(mrgfe_batch* b, double fitness_max_range, mrgfe_pair
         MRGFE_TRY(align_status);
         if (ov.status != MRGFE_OK) { set_error("%s", ov.error.c_str()); return ov.status; }
         batch_records(b, ov.early_done, results);
+        // the builders' grids are complete: they outlive the pairs (mrgfe_batch_clear_pairs), in sets no later build writes into
+        if (b->fit_valid.size() < static_cast<size_t>(b->book.n_targets())) b->fit_valid.resize(b->book.n_targets(), 0);
+        for (int t : ov.todo) b->fit_valid[t] = 1;
+        if (ov.sets_taken) b->fit_sets_used = ov.set_base + ov.sets_taken;
         fit_built.swap(ov.built);
         early_skip.swap(ov.early_done);
     }

@@ -18,6 +18,10 @@ ignored are a superset of what the sequential loop will ever align: ONE batch al
 second batch supplies the consistency alignments of every best match any gate state can produce, and the gates, the best-score rule, the
 thresholds and ``add_loop`` are replayed keyframe after keyframe on the host from the records.  Same Loop list as ``detect``.
 
+``HipLoopDetector`` is ``detect_batched`` as ONE call of the C ABI (``mrgfe_loop_detect``, include/mrgfe.h) over a ``BatchMatcher`` and a ``MapCloudStore``: the
+supersets, both batches — the second after ``mrgfe_batch_clear_pairs``, on the targets the first built — and the replay run inside ``libmrgfe.so``
+(csrc/loop_ctl.h), which also holds the LoopManager and the counters.  ``LoopDetector`` stays the mirror the tests hold it against.
+
 Poses are ``numpy`` 4 x 4 matrices: keyframe estimates in double (``Eigen::Isometry3d``), registration results in float
 (``Eigen::Matrix4f``), products and inverses in the type the reference forms them in."""
 from __future__ import annotations
@@ -458,4 +462,228 @@ class LoopDetector:
         return self._within(M)
 
 
-__all__ = ["DEFAULTS", "Edge", "KeyFrame", "Loop", "LoopManager", "LoopDetector", "normalize_estimate", "angular_distance_to_identity", "loop_closure"]
+# struct mrgfe_loop_keyframe, field for field (``_lib.LoopKeyframe`` is its ctypes mirror)
+_KEYFRAME_DTYPE = np.dtype([("key", "<u8"), ("slam_id", "<u8"), ("estimate", "<f8", (16,)), ("accum_distance", "<f8"), ("first_keyframe", "<i4"), ("static_keyframe", "<i4"),
+                            ("prev_key", "<u8"), ("next_key", "<u8"), ("prev_relpose", "<f8", (16,)), ("next_relpose", "<f8", (16,))])
+assert _KEYFRAME_DTYPE.itemsize == 432
+
+
+class HipLoopDetector:
+    """``mrgfe_loop_*``: ``LoopDetector.detect_batched`` as ONE call of the C ABI over a :class:`BatchMatcher` and a :class:`MapCloudStore` — the supersets,
+    both batches (the second on the targets the first built), the replay of the gates and ``add_loop`` all happen inside ``libmrgfe.so``, and the
+    LoopManager and the reference's counters live in the handle.  Every keyframe's cloud is named by its ``store_key()`` and must be in ``store``.
+
+    ``aligner=`` (``mrgfe_dbg_loop_set_aligner``, no GPU; ``matcher`` and ``store`` may then be None): a callable
+    ``aligner(stage, target_keys, pair_target, source_keys, guesses, want_fitness)`` — guesses ``[n, 4, 4]`` float32 — that returns one
+    ``(T 4 x 4, converged, fitness)`` per pair."""
+
+    def __init__(self, params: dict | None = None, matcher=None, store=None, aligner=None):
+        import ctypes as C
+
+        from . import _lib
+
+        if aligner is None and (matcher is None or store is None):
+            raise ValueError("HipLoopDetector needs a BatchMatcher and a MapCloudStore (or an aligner=)")
+        self.p = dict(DEFAULTS)
+        self.p.update(params or {})
+        if self.p["fitness_selection"] not in ("full", "bounded"):
+            raise ValueError(f"fitness_selection must be 'full' or 'bounded', not {self.p['fitness_selection']!r}")
+        self.matcher, self.store = matcher, store
+        cp = _lib.LoopParams()
+        _lib.lib().mrgfe_loop_default_params(C.byref(cp))
+        for name in ("candidate_max_xy_distance", "accum_distance_thresh_same_robot", "accum_distance_thresh_other_robot", "fitness_score_max_range", "fitness_score_thresh"):
+            setattr(cp, name, float(self.p[name]))
+        cp.loop_closure_consistency_max_delta_trans = float(self.p["loop_closure_consistency_max_delta_trans"])
+        cp.loop_closure_consistency_max_delta_angle = float(self.p["loop_closure_consistency_max_delta_angle"])
+        cp.fitness_selection = 1 if self.p["fitness_selection"] == "bounded" else 0
+        cp.use_planar_registration_guess = int(bool(self.p["use_planar_registration_guess"]))
+        cp.enable_loop_closure_consistency_check = int(bool(self.p["enable_loop_closure_consistency_check"]))
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().mrgfe_loop_create(matcher._h if matcher is not None else None, store._h if store is not None else None, C.byref(cp), C.byref(self._h)))
+        self._slam_ids: dict = {}
+        self._cb = None
+        self.last_batched: dict | None = None
+        self.last_target_builds = 0
+        if aligner is not None:
+            self._set_aligner(aligner)
+
+    def _set_aligner(self, aligner):
+        import ctypes as C
+
+        from . import _lib
+
+        def cb(user, stage, n_targets, target_keys, n_pairs, pair_target, source_keys, guesses, want_fitness, results):
+            try:
+                tk = [int(target_keys[i]) for i in range(n_targets)]
+                pt = [int(pair_target[i]) for i in range(n_pairs)]
+                sk = [int(source_keys[i]) for i in range(n_pairs)]
+                g = np.ctypeslib.as_array(guesses, shape=(max(n_pairs, 1) * 16,))[: n_pairs * 16].reshape(n_pairs, 4, 4).transpose(0, 2, 1).copy()
+                out = aligner(stage, tk, pt, sk, g, bool(want_fitness))
+                for i, (T, converged, fitness) in enumerate(out):
+                    results[i].T[:] = [float(x) for x in np.asarray(T, dtype=np.float32).T.reshape(-1)]
+                    results[i].converged = int(bool(converged))
+                    if want_fitness:
+                        results[i].fitness = float(fitness)
+                return _lib.MRGFE_OK
+            except Exception:  # noqa: BLE001  (no exception crosses the C frames: the call fails with this code)
+                return _lib.ERR_INVALID
+
+        self._cb = _lib.LOOP_ALIGNER(cb)  # kept alive as long as the handle uses it
+        _lib.check(_lib.lib().mrgfe_dbg_loop_set_aligner(self._h, C.cast(self._cb, C.c_void_p), None))
+
+    def close(self):
+        from . import _lib
+
+        if getattr(self, "_h", None):
+            _lib.lib().mrgfe_loop_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def reset(self):
+        """``mrgfe_loop_reset``: forget the loops and the counters."""
+        from . import _lib
+
+        _lib.check(_lib.lib().mrgfe_loop_reset(self._h))
+        self.last_batched = None
+
+    def set_stage_reuse(self, on: bool) -> bool:
+        """``mrgfe_dbg_loop_set_stage_reuse``: off = stage 2 clears the batch and builds its targets again (the composed route).  Returns the old setting."""
+        from . import _lib
+
+        return bool(_lib.check(_lib.lib().mrgfe_dbg_loop_set_stage_reuse(self._h, int(bool(on)))))
+
+    def slam_id(self, uuid) -> int:
+        """the stable 64-bit id a ``slam_uuid`` is given in the records"""
+        v = self._slam_ids.get(uuid)
+        if v is None:
+            v = self._slam_ids[uuid] = int.from_bytes(hashlib.blake2b(str(uuid).encode(), digest_size=8).digest(), "little")
+        return v
+
+    def _records(self, kfs):
+        """the keyframes as an array of ``mrgfe_loop_keyframe`` (filled field by field over all keyframes at once: a graph has hundreds)"""
+        from . import _lib
+
+        n = len(kfs)
+        a = np.zeros(max(n, 1), dtype=_KEYFRAME_DTYPE)
+        if n:
+            colmajor = lambda mats: np.stack(mats).astype(np.float64).transpose(0, 2, 1).reshape(len(mats), 16)  # noqa: E731
+            a["key"][:n] = np.array([kf.store_key() for kf in kfs], dtype=np.uint64)
+            a["slam_id"][:n] = np.array([self.slam_id(kf.slam_uuid) for kf in kfs], dtype=np.uint64)
+            a["estimate"][:n] = colmajor([kf.estimate for kf in kfs])
+            a["accum_distance"][:n] = [kf.accum_distance for kf in kfs]
+            a["first_keyframe"][:n] = [bool(kf.first_keyframe) for kf in kfs]
+            a["static_keyframe"][:n] = [bool(kf.static_keyframe) for kf in kfs]
+            prev = [i for i, kf in enumerate(kfs) if kf.prev_edge is not None]
+            if prev:
+                a["prev_key"][prev] = np.array([kfs[i].prev_edge.to_keyframe.store_key() for i in prev], dtype=np.uint64)
+                a["prev_relpose"][prev] = colmajor([kfs[i].prev_edge.relative_pose for i in prev])
+            nxt = [i for i, kf in enumerate(kfs) if kf.next_edge is not None]
+            if nxt:
+                a["next_key"][nxt] = np.array([kfs[i].next_edge.from_keyframe.store_key() for i in nxt], dtype=np.uint64)
+                a["next_relpose"][nxt] = colmajor([kfs[i].next_edge.relative_pose for i in nxt])
+        return (_lib.LoopKeyframe * max(n, 1)).from_buffer(a)  # (a view: the numpy array lives as long as it)
+
+    def detect(self, keyframes, new_keyframes):
+        """The Loop list of ``LoopDetector.detect(keyframes, new_keyframes)`` (each with its ``score``), from one ``mrgfe_loop_detect``."""
+        import ctypes as C
+
+        from . import _lib
+
+        keyframes, new_keyframes = list(keyframes), list(new_keyframes)
+        by_key = {}
+        for kf in new_keyframes + keyframes:
+            by_key[kf.store_key()] = kf
+        edges = [(n.store_key(), c.store_key()) for n in new_keyframes if n.connected for c in keyframes if c.id in n.connected]  # KeyFrame::edge_exists
+        ek = (C.c_uint64 * max(2 * len(edges), 1))(*[k for e in edges for k in e])
+        out = (_lib.LoopResult * max(len(new_keyframes), 1))()
+        n = C.c_int(0)
+        _lib.check(_lib.lib().mrgfe_loop_detect(self._h, len(keyframes), self._records(keyframes), len(new_keyframes), self._records(new_keyframes), len(edges), ek, out,
+                                                 len(new_keyframes), C.byref(n)))
+        loops = []
+        for r in out[: n.value]:
+            lp = Loop(by_key[r.key1], by_key[r.key2], np.array(r.relative_pose[:], dtype=np.float32).reshape(4, 4).T.copy())
+            lp.score = float(r.score)
+            loops.append(lp)
+        st = self.stats()
+        if st["superset_pairs"]:  # (a call without candidates leaves last_batched alone, as detect_batched does)
+            self.last_batched = {k: st[k] for k in ("superset_pairs", "sequential_pairs", "consistency_pairs", "new_keyframes")}
+        self.last_target_builds = st["target_builds"]
+        return loops
+
+    def stats(self) -> dict:
+        """``mrgfe_loop_stats``: the pair counts of the last successful call (0 when it had no candidates) and the targets it built."""
+        import ctypes as C
+
+        from . import _lib
+
+        v = (C.c_int64 * 5)()
+        _lib.check(_lib.lib().mrgfe_loop_stats(self._h, v))
+        return dict(zip(("superset_pairs", "sequential_pairs", "consistency_pairs", "new_keyframes", "target_builds"), [int(x) for x in v]))
+
+    def _timing(self):
+        import ctypes as C
+
+        from . import _lib
+
+        n = C.c_int(0)
+        _lib.check(_lib.lib().mrgfe_loop_timing(self._h, 0, None, None, C.byref(n)))
+        cand, us = (C.c_int32 * max(n.value, 1))(), (C.c_int64 * max(n.value, 1))()
+        _lib.check(_lib.lib().mrgfe_loop_timing(self._h, n.value, cand, us, C.byref(n)))
+        return [int(x) for x in cand[: n.value]], [int(x) for x in us[: n.value]]
+
+    @property
+    def loop_candidates_sizes(self) -> list:
+        return self._timing()[0]
+
+    @property
+    def loop_detection_times(self) -> list:
+        return self._timing()[1]
+
+    def average_time_per_candidate_us(self) -> float | None:
+        cand, us = self._timing()
+        return float(sum(us)) / sum(cand) if sum(cand) else None
+
+    def loop_manager_entries(self) -> list:
+        """``mrgfe_dbg_loop_manager``: (new keyframe's slam id, candidate's slam id, key1, key2) per LoopManager entry."""
+        import ctypes as C
+
+        from . import _lib
+
+        n = C.c_int(0)
+        _lib.check(_lib.lib().mrgfe_dbg_loop_manager(self._h, 0, None, C.byref(n)))
+        buf = (C.c_uint64 * max(4 * n.value, 1))()
+        _lib.check(_lib.lib().mrgfe_dbg_loop_manager(self._h, n.value, buf, C.byref(n)))
+        return [tuple(int(x) for x in buf[4 * i: 4 * i + 4]) for i in range(n.value)]
+
+
+def lib_normalize_estimate(estimate) -> np.ndarray:
+    """``mrgfe_loop_normalize_estimate``: the library's restatement of :func:`normalize_estimate`."""
+    import ctypes as C
+
+    from . import _lib
+
+    a = np.ascontiguousarray(np.asarray(estimate, dtype=np.float64).T)
+    out = np.empty((4, 4), dtype=np.float64)
+    _lib.check(_lib.lib().mrgfe_loop_normalize_estimate(a.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out.T.copy()
+
+
+def lib_guess(new_estimate_normalized, candidate_estimate, planar: bool = False) -> np.ndarray:
+    """``mrgfe_loop_guess``: the library's restatement of ``LoopDetector._guess`` (4 x 4 float32)."""
+    import ctypes as C
+
+    from . import _lib
+
+    a = np.ascontiguousarray(np.asarray(new_estimate_normalized, dtype=np.float64).T)
+    b = np.ascontiguousarray(np.asarray(candidate_estimate, dtype=np.float64).T)
+    out = np.empty((4, 4), dtype=np.float32)
+    _lib.check(_lib.lib().mrgfe_loop_guess(a.ctypes.data_as(C.POINTER(C.c_double)), b.ctypes.data_as(C.POINTER(C.c_double)), int(bool(planar)), out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out.T.copy()
+
+
+__all__ = ["DEFAULTS", "Edge", "KeyFrame", "Loop", "LoopManager", "LoopDetector", "HipLoopDetector", "lib_normalize_estimate", "lib_guess", "normalize_estimate", "angular_distance_to_identity", "loop_closure"]

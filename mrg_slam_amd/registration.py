@@ -456,6 +456,10 @@ class BatchMatcher:
     def clear(self):
         check(lib().mrgfe_batch_clear(self._h))
 
+    def clear_pairs(self):
+        """``mrgfe_batch_clear_pairs``: forget the pairs, keep the targets and everything built for them (a second stage against the same targets)."""
+        check(lib().mrgfe_batch_clear_pairs(self._h))
+
     def add_target(self, cloud) -> int:
         c = _cloud(cloud)
         return check(lib().mrgfe_batch_add_target(self._h, c.ctypes.data_as(_fp), len(c), 16))
