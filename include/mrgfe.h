@@ -129,6 +129,16 @@ int  mrgfe_unpin_host_buffer(mrgfe_ctx* ctx, void* p);
  * Pageable buffers, and everything while the switch is off, keep the default contract: free or reuse the memory as soon as the add / set call returns.
  * (mrgfe_node_* declares its clouds by pointer and uploads them inside mrgfe_node_align: its members always run with the switch on.) */
 int  mrgfe_ctx_set_zero_copy_uploads(mrgfe_ctx* ctx, int on);
+/* Byte-aligned PointCloud2 layouts (off by default).  Every call that reads the bytes of a sensor_msgs/PointCloud2 — mrgfe_ingest_pointcloud2,
+ * mrgfe_scan_callback[_device], mrgfe_keyframe_callback, mrgfe_map_store_add_keyframes, mrgfe_odom_frame — by default demands FLOAT32 fields at offsets
+ * that are multiples of 4 and a point_step and row_step that are multiples of 4 (MRGFE_ERR_INVALID otherwise).  pcl::fromROSMsg demands none of this:
+ * the Velodyne driver's XYZIRT records are 22 bytes (x@0 y@4 z@8 intensity@12 FLOAT32, ring@16 UINT16, time@18 FLOAT32), others publish 26-byte
+ * records with a FLOAT64 stamp at byte 18.  on = 1: calls that run on this context (a store's or a registration's context is the one it was made on)
+ * take any point_step >= 1, any row_step >= width * point_step and any field offset with off + 4 <= point_step; fields may overlap.  The size and
+ * count limits, the data_bytes checks and off_intensity < 0 stay as they are.  Such records are read by second instantiations of the same kernels
+ * (each field put together from at most two aligned 4-byte words, its bits as they are, NaN payloads and denormals included); a layout that satisfies
+ * the default rules launches exactly the kernels it launches with the switch off.  Contexts made like this one (mrgfe_ctx_create_like) inherit it. */
+int  mrgfe_ctx_set_byte_layouts(mrgfe_ctx* ctx, int on);
 /* HIP stream of the context as an opaque pointer (hipStream_t), for callers that order their own work after it */
 void* mrgfe_ctx_stream(mrgfe_ctx* ctx);
 /* Measurement hook ("1-NN fitness on hash grid: N (16 + 27*8 + m*16)"): what the last getFitnessScore pass on this context
@@ -146,7 +156,9 @@ int mrgfe_ctx_knn_stats(mrgfe_ctx* ctx, double out[5]);
 
 /* ---- cloud ingest --------------------------------------------------------------------------------- */
 /* replaces pcl::fromROSMsg(*cloud_msg, *cloud) (apps/prefiltering_component.cpp:119-120, scan_matching_odometry_component.cpp:144-145):
- * the byte payload of a sensor_msgs/PointCloud2 (little-endian FLOAT32 fields at the given byte offsets; row_step 0 means
+ * the byte payload of a sensor_msgs/PointCloud2 (little-endian FLOAT32 fields at the given byte offsets — multiples of 4 inside a point_step and
+ * row_step that are multiples of 4, or any with mrgfe_ctx_set_byte_layouts; mrgfe_pointcloud2_layout below finds them in the message's field list,
+ * matching as pcl::fromROSMsg does, NOT by name alone; row_step 0 means
  * width * point_step; off_intensity < 0: no such field, intensity 0 like PointXYZI's default) becomes a packed x,y,z,intensity
  * cloud in host memory (out_xyzi, width*height*16 bytes, may be NULL) and / or device memory (d_out_xyzi, may be NULL) — the
  * latter feeds mrgfe_reg_set_*_device / mrgfe_batch_add_*_device / mrgfe_prefilter_device without the cloud leaving HBM.
@@ -155,6 +167,25 @@ int mrgfe_ctx_knn_stats(mrgfe_ctx* ctx, double out[5]);
  * length argument (a sensor_msgs/PointCloud2 guarantees it; the Python wrapper checks it). */
 int mrgfe_ingest_pointcloud2(mrgfe_ctx* ctx, const uint8_t* data, uint32_t width, uint32_t height, uint32_t point_step, uint32_t row_step, uint32_t off_x, uint32_t off_y,
                              uint32_t off_z, int32_t off_intensity, float* out_xyzi, void* d_out_xyzi);
+/* The layout arguments of the calls that read a PointCloud2 from the message's own description.  mrgfe_pointcloud2_field is sensor_msgs/PointField;
+ * the result is a mrgfe_keyframe_params (declared here; the FIRST EIGHT members of mrgfe_scan_params are this struct, in this order, so a caller may
+ * copy it over the head of one; mrgfe_ingest_pointcloud2 takes the same eight values as arguments).  Runs on the host and needs no context.
+ * The matching rule is pcl::fromROSMsg's (pcl::createMapping / FieldMatches): the first field with the name, datatype FLOAT32 (7) and count 1.
+ * x, y or z without a match: MRGFE_ERR_INVALID, naming the field (PCL would leave it unset).  intensity without a match — no such field, or one that
+ * is UINT8 / UINT16 / has count 2 —: off_intensity = -1, the intensity PCL leaves at 0; matching by name alone would read such a field as float bits.
+ * is_bigendian != 0: MRGFE_ERR_INVALID.  width, height, point_step and row_step are copied as they are: whether the fields fit point_step and the rows
+ * fit row_step is checked, as before, by the entry point the layout is handed to, which refuses under its own name.
+ * *needs_byte_layouts (may be NULL) = 1 when the layout is outside the default rules, i.e. needs mrgfe_ctx_set_byte_layouts(ctx, 1). */
+typedef struct mrgfe_pointcloud2_field {
+    const char* name;
+    uint32_t    offset;
+    uint8_t     datatype;  /* sensor_msgs/PointField: INT8 1, UINT8 2, INT16 3, UINT16 4, INT32 5, UINT32 6, FLOAT32 7, FLOAT64 8 */
+    uint32_t    count;
+} mrgfe_pointcloud2_field;
+struct mrgfe_keyframe_params;
+size_t mrgfe_pointcloud2_field_size(void); /* sizeof(mrgfe_pointcloud2_field) as the library was compiled */
+int    mrgfe_pointcloud2_layout(const mrgfe_pointcloud2_field* fields, int n_fields, uint32_t width, uint32_t height, uint32_t point_step, uint32_t row_step,
+                                int is_bigendian, struct mrgfe_keyframe_params* out, int* needs_byte_layouts);
 
 /* ---- registration: the pcl::Registration call surface the reference uses (SURVEY.md §8b "Seam") ---------------- */
 /* defaults of select_registration_method's parameters (registrations.cpp:34-43 comments) for `method` */
@@ -281,7 +312,8 @@ int  mrgfe_prefilter_device(mrgfe_ctx* ctx, const mrgfe_prefilter_params* params
  * -> mrgfe_prefilter[_device] for the same inputs.  The reference's quirks are kept: deskewing counts i and n = width * height over the UNFILTERED
  * cloud (:286), non-finite points included; the transform leaves non-finite points as they are; the distance filter is what drops them. */
 typedef struct mrgfe_scan_params {
-    /* the message's layout, as for mrgfe_ingest_pointcloud2 (little-endian FLOAT32 fields; offsets multiples of 4 inside point_step) */
+    /* the message's layout, as for mrgfe_ingest_pointcloud2 (little-endian FLOAT32 fields; offsets and steps multiples of 4 unless the context has
+     * mrgfe_ctx_set_byte_layouts on).  These first eight members are a mrgfe_keyframe_params: what mrgfe_pointcloud2_layout fills in. */
     uint32_t width, height, point_step, row_step;   /* row_step 0: width * point_step                                      */
     uint32_t off_x, off_y, off_z;
     int32_t  off_intensity;                         /* < 0: no such field, intensity 0                                     */
@@ -396,7 +428,8 @@ int mrgfe_remove_points_near(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t
  * The layout of the message, as for mrgfe_ingest_pointcloud2 / mrgfe_scan_params: */
 typedef struct mrgfe_keyframe_params {
     uint32_t width, height, point_step, row_step;   /* row_step 0: width * point_step                                      */
-    uint32_t off_x, off_y, off_z;                   /* little-endian FLOAT32 fields; offsets multiples of 4 inside point_step */
+    uint32_t off_x, off_y, off_z;                   /* little-endian FLOAT32 fields inside point_step; offsets and steps multiples of 4 unless
+                                                     * the store's context has mrgfe_ctx_set_byte_layouts on                 */
     int32_t  off_intensity;                         /* < 0: no such field, intensity 0                                     */
 } mrgfe_keyframe_params;
 /* height 1, the packed 16-byte layout (offsets 0/4/8/12); `width` is left 0 for the caller */

@@ -60,6 +60,12 @@ class KeyframeParams(C.Structure):
                 ("off_z", C.c_uint32), ("off_intensity", C.c_int32)]
 
 
+class PointField(C.Structure):
+    """struct mrgfe_pointcloud2_field: one sensor_msgs/PointField of a message, as ``mrgfe_pointcloud2_layout`` reads it."""
+
+    _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint8), ("count", C.c_uint32)]
+
+
 class KeyframeMsg(C.Structure):
     """struct mrgfe_keyframe_msg: one message of ``mrgfe_map_store_add_keyframes`` (key, layout, payload)."""
 
@@ -203,6 +209,7 @@ SIGNATURES = {
     "mrgfe_pin_host_buffer": (C.c_int, [_vp, _vp, C.c_size_t]),
     "mrgfe_unpin_host_buffer": (C.c_int, [_vp, _vp]),
     "mrgfe_ctx_set_zero_copy_uploads": (C.c_int, [_vp, C.c_int]),
+    "mrgfe_ctx_set_byte_layouts": (C.c_int, [_vp, C.c_int]),
     "mrgfe_ctx_stream": (_vp, [_vp]),
     "mrgfe_ctx_fitness_stats": (C.c_int, [_vp, _dp]),
     "mrgfe_ctx_knn_stats": (C.c_int, [_vp, _dp]),
@@ -238,6 +245,8 @@ SIGNATURES = {
                                            C.POINTER(C.c_size_t)]),
     "mrgfe_keyframe_default_params": (None, [C.POINTER(KeyframeParams)]),
     "mrgfe_keyframe_params_size": (C.c_size_t, []),
+    "mrgfe_pointcloud2_field_size": (C.c_size_t, []),
+    "mrgfe_pointcloud2_layout": (C.c_int, [C.POINTER(PointField), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(KeyframeParams), C.POINTER(C.c_int)]),
     "mrgfe_keyframe_callback": (C.c_int, [_vp, C.c_uint64, C.POINTER(KeyframeParams), _vp, C.c_size_t, _fp, C.c_int, C.c_float, _fp, _szp, _fp, _szp]),
     "mrgfe_keyframe_msg_size": (C.c_size_t, []),
     "mrgfe_map_store_add_keyframes": (C.c_int, [_vp, C.c_int, C.POINTER(KeyframeMsg), C.POINTER(C.c_uint8)]),
@@ -457,7 +466,7 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"libmrgfe.so was built with a mrgfe_matching_status of {L.mrgfe_matching_status_size()} bytes, the binding mirrors {C.sizeof(MatchingStatus)}")
         if hasattr(L, "mrgfe_keyframe_params_size") and L.mrgfe_keyframe_params_size() != C.sizeof(KeyframeParams):
             raise RuntimeError(f"libmrgfe.so was built with a mrgfe_keyframe_params of {L.mrgfe_keyframe_params_size()} bytes, the binding mirrors {C.sizeof(KeyframeParams)}")
-        for fn, mirror in (("mrgfe_keyframe_msg_size", KeyframeMsg), ("mrgfe_graph_edge_size", GraphEdge), ("mrgfe_odom_params_size", OdomParams),
+        for fn, mirror in (("mrgfe_pointcloud2_field_size", PointField), ("mrgfe_keyframe_msg_size", KeyframeMsg), ("mrgfe_graph_edge_size", GraphEdge), ("mrgfe_odom_params_size", OdomParams),
                            ("mrgfe_odom_result_size", OdomResult), ("mrgfe_loop_params_size", LoopParams), ("mrgfe_loop_keyframe_size", LoopKeyframe),
                            ("mrgfe_loop_result_size", LoopResult)):
             if hasattr(L, fn) and getattr(L, fn)() != C.sizeof(mirror):
@@ -497,6 +506,11 @@ class Context:
         """``mrgfe_ctx_set_zero_copy_uploads``: clouds in page-locked host memory go up by DMA from the caller's buffer — which must then stay
         unchanged until the consuming call (align / wait / synchronize) has returned."""
         check(lib().mrgfe_ctx_set_zero_copy_uploads(self._h, int(bool(on))))
+
+    def set_byte_layouts(self, on: bool = True):
+        """``mrgfe_ctx_set_byte_layouts``: the calls that read PointCloud2 bytes on this context (and on the stores and registrations made on it) take
+        layouts whose field offsets or steps are not multiples of 4 — Velodyne's 22-byte records — as ``pcl::fromROSMsg`` does."""
+        check(lib().mrgfe_ctx_set_byte_layouts(self._h, int(bool(on))))
 
     def fitness_stats(self) -> dict:
         """What the last getFitnessScore pass on this context did (``mrgfe_ctx_fitness_stats``)."""

@@ -689,7 +689,7 @@ static int scan_callback_impl(const char* fn, mrgfe_ctx* ctx, const mrgfe_scan_p
         h.data = data;
         h.width = p->width; h.height = p->height; h.point_step = p->point_step; h.row_step = p->row_step;
         h.off_x = p->off_x; h.off_y = p->off_y; h.off_z = p->off_z; h.off_intensity = p->off_intensity;
-        MRGFE_TRY(check_pointcloud2_layout(fn, h.width, h.height, h.point_step, &h.row_step, h.off_x, h.off_y, h.off_z, h.off_intensity));
+        MRGFE_TRY(check_pointcloud2_layout(ctx, fn, h.width, h.height, h.point_step, &h.row_step, h.off_x, h.off_y, h.off_z, h.off_intensity));
         h.deskew = p->deskew != 0;
         for (int k = 0; k < 3; ++k) h.ang_v[k] = p->ang_v[k];
         h.scan_period = p->scan_period;
@@ -985,7 +985,7 @@ int mrgfe_keyframe_callback(mrgfe_map_store* s, uint64_t key, const mrgfe_keyfra
         if (key == 0) { set_error("%s: key 0", fn); return MRGFE_ERR_INVALID; }
         if (n_centres < 0 || n_centres > kMaxCentres || (n_centres > 0 && !centres)) { set_error("%s: %d centres (0 to %d, and their positions)", fn, n_centres, kMaxCentres); return MRGFE_ERR_INVALID; }
         KeyframeLayout l{lay->width, lay->height, lay->point_step, lay->row_step, lay->off_x, lay->off_y, lay->off_z, lay->off_intensity};
-        MRGFE_TRY(check_pointcloud2_layout(fn, l.width, l.height, l.point_step, &l.row_step, l.off_x, l.off_y, l.off_z, l.off_intensity));
+        MRGFE_TRY(check_pointcloud2_layout(s->ctx, fn, l.width, l.height, l.point_step, &l.row_step, l.off_x, l.off_y, l.off_z, l.off_intensity));
         const size_t n = size_t(l.width) * l.height;
         const size_t raw_bytes = n ? size_t(l.height - 1) * l.row_step + size_t(l.width) * l.point_step : 0;
         if (n && !data) { set_error("%s: NULL data", fn); return MRGFE_ERR_INVALID; }
@@ -1056,7 +1056,7 @@ int mrgfe_map_store_add_keyframes(mrgfe_map_store* s, int n, const mrgfe_keyfram
             const unsigned long long  key = static_cast<unsigned long long>(m.key);
             if (m.key == 0) { set_error("%s: message %d: key 0", fn, i); return MRGFE_ERR_INVALID; }
             KeyframeLayout l{m.layout.width, m.layout.height, m.layout.point_step, m.layout.row_step, m.layout.off_x, m.layout.off_y, m.layout.off_z, m.layout.off_intensity};
-            MRGFE_TRY(check_pointcloud2_layout(fn, l.width, l.height, l.point_step, &l.row_step, l.off_x, l.off_y, l.off_z, l.off_intensity));
+            MRGFE_TRY(check_pointcloud2_layout(s->ctx, fn, l.width, l.height, l.point_step, &l.row_step, l.off_x, l.off_y, l.off_z, l.off_intensity));
             const size_t np = size_t(l.width) * l.height;
             const size_t raw_bytes = np ? size_t(l.height - 1) * l.row_step + size_t(l.width) * l.point_step : 0;
             if (np && !m.data) { set_error("%s: message %d (keyframe %llu): NULL data", fn, i, key); return MRGFE_ERR_INVALID; }

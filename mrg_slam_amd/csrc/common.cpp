@@ -482,6 +482,7 @@ static int ctx_create(int device_id, int high_priority, int reserve_cus, const m
         c->cu_mask = like->cu_mask;
         c->cu_count = like->cu_count;
         c->zero_copy_uploads = like->zero_copy_uploads;
+        c->byte_layouts.store(like->byte_layouts.load());
     } else if (reserve_cus == MRGFE_RESERVE_AUTO && c->cu_count < 8) {
         // nothing sensible to split off: a plain context
     } else if (reserve_cus > 0 || reserve_cus == MRGFE_RESERVE_AUTO) {
@@ -532,6 +533,14 @@ int mrgfe_ctx_set_zero_copy_uploads(mrgfe_ctx* ctx, int on)
     if (!ctx) { mrgfe::set_error("mrgfe_ctx_set_zero_copy_uploads: NULL context"); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(ctx);  // (an asynchronous align of a batch on this context holds the lock: the switch takes effect behind it)
     ctx->zero_copy_uploads = on != 0;
+    return MRGFE_OK;
+}
+
+int mrgfe_ctx_set_byte_layouts(mrgfe_ctx* ctx, int on)
+{
+    if (!ctx) { mrgfe::set_error("mrgfe_ctx_set_byte_layouts: NULL context"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(ctx);  // (behind whatever call holds the context: the next layout check sees the new value)
+    ctx->byte_layouts.store(on != 0);
     return MRGFE_OK;
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -236,6 +237,7 @@ struct mrgfe_ctx {
     int          up_next = 0;
     bool         dma_from_caller = false;     // a zero-copy upload was queued since the last wait for the stream (drain_caller_dma on error paths)
     bool         zero_copy_uploads = false;   // mrgfe_ctx_set_zero_copy_uploads: clouds in page-locked host memory go up by DMA from the caller's buffer
+    std::atomic<bool> byte_layouts{false};    // mrgfe_ctx_set_byte_layouts: PointCloud2 layouts need not be multiples of 4 (read by check_pointcloud2_layout, before the call takes the lock)
     mrgfe::Event ev_fit[4];                     // around the passes of nn_fitness_batch
     int          priority = 0;                  // > 0: streams at the device's highest priority, < 0: at its lowest (throughput work beside latency-critical rounds)
     std::vector<uint32_t> cu_mask;              // non-empty: every stream of this context is confined to these compute units (mrgfe_ctx_create_reserving)

@@ -526,7 +526,8 @@ struct ScanHeadArgs {
     PfState*       st;
     const float4  *cp0, *cp1;
 };
-template <bool kDeskew, bool kTransform, bool kFlags>
+// kBytes: the layout is not a strict one (ingest.h layout_is_strict) and the record's fields are put together from aligned words.
+template <bool kDeskew, bool kTransform, bool kFlags, bool kBytes = false>
 __global__ __launch_bounds__(256) void scan_head_kernel(const ScanHeadArgs a)
 {
     if (kFlags && blockIdx.x == 0 && threadIdx.x == 0) pf_state_init(a.st, a.cp0, a.cp1, a.n);
@@ -536,7 +537,7 @@ __global__ __launch_bounds__(256) void scan_head_kernel(const ScanHeadArgs a)
     for (int k = 0; k < kTile / 256; ++k) {
         const uint32_t i = base + k * 256 + threadIdx.x;
         if (i < a.n) {
-            float4 p = load_point_record(a.raw, i, a.width, a.row_step, a.point_step, a.ox, a.oy, a.oz, a.oi);
+            float4 p = load_point_record_as<kBytes>(a.raw, i, a.width, a.row_step, a.point_step, a.ox, a.oy, a.oz, a.oi);
             if (kDeskew) p = deskew_point(p, i, a.n, a.av[0], a.av[1], a.av[2], a.scan_period);
             if (kTransform) p = transform_finite_point(a.T, p);
             a.out[i] = p;
@@ -579,7 +580,11 @@ static int launch_scan_head(mrgfe_ctx* ctx, const ScanHead& h, const void* d_raw
     static const Kernel variants[8] = {scan_head_kernel<false, false, false>, scan_head_kernel<false, false, true>, scan_head_kernel<false, true, false>,
                                        scan_head_kernel<false, true, true>,   scan_head_kernel<true, false, false>, scan_head_kernel<true, false, true>,
                                        scan_head_kernel<true, true, false>,   scan_head_kernel<true, true, true>};
-    const Kernel kern = variants[(h.deskew ? 4 : 0) | (h.transform ? 2 : 0) | (fl ? 1 : 0)];
+    static const Kernel byte_variants[8] = {scan_head_kernel<false, false, false, true>, scan_head_kernel<false, false, true, true>, scan_head_kernel<false, true, false, true>,
+                                            scan_head_kernel<false, true, true, true>,   scan_head_kernel<true, false, false, true>, scan_head_kernel<true, false, true, true>,
+                                            scan_head_kernel<true, true, false, true>,   scan_head_kernel<true, true, true, true>};
+    const bool   strict = layout_is_strict(h.point_step, h.row_step, h.off_x, h.off_y, h.off_z, h.off_intensity);
+    const Kernel kern = (strict ? variants : byte_variants)[(h.deskew ? 4 : 0) | (h.transform ? 2 : 0) | (fl ? 1 : 0)];
     hipLaunchKernelGGL(kern, dim3((a.n + kTile - 1) / kTile), dim3(256), 0, ctx->stream, a);
     MRGFE_HIP_CHECK(hipGetLastError());
     return MRGFE_OK;

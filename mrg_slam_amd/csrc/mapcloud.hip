@@ -17,6 +17,7 @@
 #include "dev_float.h"
 #include "dev_utils.h"
 #include "filters.h"
+#include "ingest.h"
 #include "scan_point.h"
 
 namespace mrgfe {
@@ -303,7 +304,8 @@ struct KeyframeHeadArgs {
     int            K;
     float          radius_sqr;
 };
-template <bool kCentres>
+// kBytes: the layout is not a strict one (ingest.h layout_is_strict) and the record's fields are put together from aligned words.
+template <bool kCentres, bool kBytes>
 __global__ __launch_bounds__(256) void keyframe_head_kernel(const KeyframeHeadArgs a, const Centres c)
 {
     const uint32_t base = blockIdx.x * kTile;
@@ -312,7 +314,7 @@ __global__ __launch_bounds__(256) void keyframe_head_kernel(const KeyframeHeadAr
     for (int k = 0; k < kTile / 256; ++k) {
         const uint32_t i = base + k * 256 + threadIdx.x;
         if (i < a.n) {
-            const float4 p = load_point_record(a.raw, i, a.width, a.row_step, a.point_step, a.ox, a.oy, a.oz, a.oi);
+            const float4 p = load_point_record_as<kBytes>(a.raw, i, a.width, a.row_step, a.point_step, a.ox, a.oy, a.oz, a.oi);
             a.out[i] = p;
             if (kCentres) {
                 const uint32_t f = near_a_centre(p, c, a.K, a.radius_sqr) ^ 1u;
@@ -396,12 +398,14 @@ static KeyframeHeadArgs keyframe_head_args(const void* d_raw, const KeyframeLayo
     a.ox = lay.off_x; a.oy = lay.off_y; a.oz = lay.off_z; a.oi = lay.off_intensity;
     return a;
 }
+static bool head_is_strict(const KeyframeHeadArgs& a) { return layout_is_strict(a.point_step, a.row_step, a.ox, a.oy, a.oz, a.oi); }
 
 int keyframe_gather_device(mrgfe_ctx* ctx, const void* d_raw, const KeyframeLayout& lay, float4* d_cloud)
 {
     const KeyframeHeadArgs a = keyframe_head_args(d_raw, lay, d_cloud);
     if (a.n == 0) return MRGFE_OK;
-    hipLaunchKernelGGL(keyframe_head_kernel<false>, dim3((a.n + kTile - 1) / kTile), dim3(256), 0, ctx->stream, a, Centres{});
+    const auto kern = head_is_strict(a) ? keyframe_head_kernel<false, false> : keyframe_head_kernel<false, true>;
+    hipLaunchKernelGGL(kern, dim3((a.n + kTile - 1) / kTile), dim3(256), 0, ctx->stream, a, Centres{});
     MRGFE_HIP_CHECK(hipGetLastError());
     return MRGFE_OK;
 }
@@ -417,12 +421,23 @@ struct KeyframeTile {
     uint32_t       n;      // points of the message
     uint32_t       width, row_step, point_step, ox, oy, oz;
     int32_t        oi;
-    uint32_t       pad[3];
+    uint32_t       bytes;  // 1: not a strict layout, the tile reads its records by aligned words (messages of one call may differ)
+    uint32_t       pad[2];
 };
 static_assert(sizeof(KeyframeTile) == 64, "KeyframeTile: one 64-byte record per tile");
+// kAnyBytes: some tile of the launch has its `bytes` flag set (a workgroup-uniform branch); a call of strict messages only launches the kernel without it.
+template <bool kAnyBytes>
 __global__ __launch_bounds__(256) void keyframe_gather_many_kernel(const KeyframeTile* __restrict__ tiles)
 {
     const KeyframeTile t = tiles[blockIdx.x];
+    if (kAnyBytes && t.bytes) {
+#pragma unroll
+        for (int k = 0; k < kTile / 256; ++k) {
+            const uint32_t i = t.first + k * 256 + threadIdx.x;
+            if (i < t.n) t.out[i] = load_point_record_bytes(t.raw, i, t.width, t.row_step, t.point_step, t.ox, t.oy, t.oz, t.oi);
+        }
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < kTile / 256; ++k) {
         const uint32_t i = t.first + k * 256 + threadIdx.x;
@@ -433,6 +448,7 @@ __global__ __launch_bounds__(256) void keyframe_gather_many_kernel(const Keyfram
 int keyframe_gather_many_device(mrgfe_ctx* ctx, const KeyframeGatherItem* items, size_t count)
 {
     std::vector<KeyframeTile> tiles;
+    bool any_bytes = false;
     for (size_t m = 0; m < count; ++m) {
         const KeyframeHeadArgs a = keyframe_head_args(items[m].d_raw, items[m].lay, items[m].d_cloud);
         KeyframeTile t;
@@ -440,6 +456,8 @@ int keyframe_gather_many_device(mrgfe_ctx* ctx, const KeyframeGatherItem* items,
         t.raw = a.raw; t.out = a.out; t.n = a.n;
         t.width = a.width; t.row_step = a.row_step; t.point_step = a.point_step;
         t.ox = a.ox; t.oy = a.oy; t.oz = a.oz; t.oi = a.oi;
+        t.bytes = head_is_strict(a) ? 0u : 1u;
+        any_bytes = any_bytes || (t.bytes && a.n);
         for (uint64_t first = 0; first < a.n; first += kTile) {  // (an empty message has no tile)
             t.first = static_cast<uint32_t>(first);
             tiles.push_back(t);
@@ -450,7 +468,7 @@ int keyframe_gather_many_device(mrgfe_ctx* ctx, const KeyframeGatherItem* items,
     DevBuf& dtab = ctx->scratch[0];
     MRGFE_TRY(dtab.ensure(tiles.size() * sizeof(KeyframeTile)));
     MRGFE_TRY(ctx->stage_h2d(dtab.p, tiles.data(), tiles.size() * sizeof(KeyframeTile), ctx->stream));
-    hipLaunchKernelGGL(keyframe_gather_many_kernel, dim3(static_cast<uint32_t>(tiles.size())), dim3(256), 0, ctx->stream, dtab.as<KeyframeTile>());
+    hipLaunchKernelGGL(any_bytes ? keyframe_gather_many_kernel<true> : keyframe_gather_many_kernel<false>, dim3(static_cast<uint32_t>(tiles.size())), dim3(256), 0, ctx->stream, dtab.as<KeyframeTile>());
     MRGFE_HIP_CHECK(hipGetLastError());
     return MRGFE_OK;
 }
@@ -478,7 +496,8 @@ int keyframe_split_device(mrgfe_ctx* ctx, const void* d_raw, const KeyframeLayou
     Centres c{};
     for (int k = 0; k < K; ++k) for (int x = 0; x < 3; ++x) c.xyz[k][x] = centres[3 * k + x];
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(keyframe_head_kernel<true>, dim3(nblk), dim3(256), 0, st, a, c);
+    const auto kern = head_is_strict(a) ? keyframe_head_kernel<true, false> : keyframe_head_kernel<true, true>;
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), 0, st, a, c);
     MRGFE_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(keyframe_partition_kernel, dim3(nblk), dim3(256), 0, st, a.out, a.flags, a.blk, a.n, d_kept, d_removed, d_tot);
     MRGFE_HIP_CHECK(hipGetLastError());

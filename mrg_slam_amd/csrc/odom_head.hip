@@ -8,6 +8,7 @@
 // finite points, whatever the tiling — the one the separate pass (cellsort.hip bounding_boxes) gives.
 #include "bbox_device.h"
 #include "common.h"
+#include "ingest.h"
 #include "odom_head.h"
 #include "scan_point.h"
 
@@ -21,6 +22,8 @@ struct OdomHeadArgs {
     int32_t        oi;
 };
 
+// kBytes: the layout is not a strict one (ingest.h layout_is_strict) and the record's fields are put together from aligned words
+template <bool kBytes>
 __global__ __launch_bounds__(256) void odom_head_kernel(const OdomHeadArgs a)
 {
     const uint32_t base = blockIdx.x * kTile;
@@ -30,7 +33,7 @@ __global__ __launch_bounds__(256) void odom_head_kernel(const OdomHeadArgs a)
     for (int k = 0; k < kTile / 256; ++k) {
         const uint32_t i = base + k * 256 + threadIdx.x;
         if (i < a.n) {
-            const float4 p = load_point_record(a.raw, i, a.width, a.row_step, a.point_step, a.ox, a.oy, a.oz, a.oi);
+            const float4 p = load_point_record_as<kBytes>(a.raw, i, a.width, a.row_step, a.point_step, a.ox, a.oy, a.oz, a.oi);
             a.out[i] = p;
             acc.add(p);
         }
@@ -55,7 +58,8 @@ int launch_odom_head(mrgfe_ctx* ctx, const void* d_raw, const mrgfe_keyframe_par
     a.width = lay.width; a.row_step = lay.row_step; a.point_step = lay.point_step;
     a.ox = lay.off_x; a.oy = lay.off_y; a.oz = lay.off_z; a.oi = lay.off_intensity;
     const uint32_t nblk = odom_head_tiles(a.n);
-    if (nblk > 0) hipLaunchKernelGGL(odom_head_kernel, dim3(nblk), dim3(256), 0, ctx->stream, a);
+    const auto     kern = layout_is_strict(lay.point_step, lay.row_step, lay.off_x, lay.off_y, lay.off_z, lay.off_intensity) ? odom_head_kernel<false> : odom_head_kernel<true>;
+    if (nblk > 0) hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), 0, ctx->stream, a);
     hipLaunchKernelGGL(odom_box_merge_kernel, dim3(1), dim3(256), 0, ctx->stream, d_partial, nblk, d_box);  // (no tile: the empty box, n_finite 0)
     MRGFE_HIP_CHECK(hipGetLastError());
     return MRGFE_OK;

@@ -327,7 +327,7 @@ int mrgfe_odom_frame(mrgfe_odom* o, const mrgfe_keyframe_params* lay, const void
         if (!o || !lay || !data || !out) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
         FrameInput in;
         in.lay = *lay;
-        MRGFE_TRY(check_pointcloud2_layout(fn, in.lay.width, in.lay.height, in.lay.point_step, &in.lay.row_step, in.lay.off_x, in.lay.off_y, in.lay.off_z, in.lay.off_intensity));
+        MRGFE_TRY(check_pointcloud2_layout(o->ctx, fn, in.lay.width, in.lay.height, in.lay.point_step, &in.lay.row_step, in.lay.off_x, in.lay.off_y, in.lay.off_z, in.lay.off_intensity));
         in.n = size_t(in.lay.width) * in.lay.height;
         if (in.n == 0) { set_error("%s: an empty message", fn); return MRGFE_ERR_INVALID; }
         in.raw_bytes = size_t(in.lay.height - 1) * in.lay.row_step + size_t(in.lay.width) * in.lay.point_step;

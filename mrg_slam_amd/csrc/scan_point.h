@@ -25,6 +25,41 @@ __device__ __forceinline__ float4 load_point_record(const uint8_t* __restrict__ 
     return o;
 }
 
+// The same for a layout whose field offsets or steps are NOT multiples of 4 (mrgfe_ctx_set_byte_layouts: Velodyne's 22-byte XYZIRT records, 26-byte
+// records with a FLOAT64 stamp; pcl::fromROSMsg copies a field wherever it sits).  `raw` is 4-byte aligned — every raw device buffer of the library
+// starts on a 256-byte line — so the FLOAT32 at byte address a is in the aligned word a >> 2 and, when a & 3 is not 0, the word behind it: the two are
+// shifted together.  At most two aligned words per field and never a word that holds none of the field's bytes, so nothing is read past
+// round_up(payload bytes, 4), which every raw buffer has room for.  The result is the field's bits as they are: NaN payloads and denormals survive.
+__device__ __forceinline__ float load_f32_at_byte(const uint32_t* __restrict__ words, size_t a)
+{
+    const size_t   w = a >> 2;
+    const uint32_t s = 8u * (static_cast<uint32_t>(a) & 3u);
+    uint32_t       v = words[w];
+    if (s) v = (v >> s) | (words[w + 1] << (32u - s));
+    return __uint_as_float(v);
+}
+__device__ __forceinline__ float4 load_point_record_bytes(const uint8_t* __restrict__ raw, uint32_t i, uint32_t width, uint32_t row_step, uint32_t point_step, uint32_t ox,
+                                                          uint32_t oy, uint32_t oz, int32_t oi)
+{
+    const uint32_t  row = i / width, col = i - row * width;
+    const size_t    at = size_t(row) * row_step + size_t(col) * point_step;
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(raw);
+    float4 o;
+    o.x = load_f32_at_byte(words, at + ox);
+    o.y = load_f32_at_byte(words, at + oy);
+    o.z = load_f32_at_byte(words, at + oz);
+    o.w = oi >= 0 ? load_f32_at_byte(words, at + static_cast<uint32_t>(oi)) : 0.0f;
+    return o;
+}
+// the reader of a kernel's instantiation: kBytes is chosen on the host (ingest.h layout_is_strict), a strict layout always reads as it did
+template <bool kBytes>
+__device__ __forceinline__ float4 load_point_record_as(const uint8_t* __restrict__ raw, uint32_t i, uint32_t width, uint32_t row_step, uint32_t point_step, uint32_t ox, uint32_t oy,
+                                                       uint32_t oz, int32_t oi)
+{
+    if (kBytes) return load_point_record_bytes(raw, i, width, row_step, point_step, ox, oy, oz, oi);
+    return load_point_record(raw, i, width, row_step, point_step, ox, oy, oz, oi);
+}
+
 // PrefilteringComponent::deskewing (:272-290) for point i of a cloud of n points (n counts the non-finite points too): the point is rotated by the
 // inverse of Quaternionf(1, dt/2 * w) with dt = scan_period * i / n; `av*` is the angular velocity ALREADY negated (:275).
 __device__ __forceinline__ float4 deskew_point(float4 p, uint32_t i, uint32_t n, float avx, float avy, float avz, double scan_period)

@@ -254,15 +254,16 @@ def prefilter_to_device(cloud, dev_ptr: int, capacity: int, params: dict | None 
     return m.value
 
 
-def _scan_params(width, height, point_step, fields, row_step, ang_v, scan_period, T, params) -> "_lib.ScanParams":
+def _scan_params(width, height, point_step, fields, row_step, ang_v, scan_period, T, params, ctx=None) -> "_lib.ScanParams":
+    from .io import layout_from_fields
+
     p = dict(_PREFILTER_DEFAULTS)
     p.update(params or {})
     q = _lib.ScanParams()
     lib().mrgfe_scan_default_params(C.byref(q))
-    q.width, q.height, q.point_step, q.row_step = int(width), int(height), int(point_step), int(row_step)
-    q.off_x, q.off_y, q.off_z = int(fields["x"]), int(fields["y"]), int(fields["z"])
-    oi = fields.get("intensity")
-    q.off_intensity = -1 if oi is None else int(oi)
+    lay, _ = layout_from_fields(fields, width, height, point_step, row_step, ctx=ctx)  # (a field list that needs it switches the context to byte layouts)
+    C.memmove(C.byref(q), C.byref(lay), C.sizeof(lay))  # the first eight members of mrgfe_scan_params are a mrgfe_keyframe_params
+    q.row_step = int(row_step)
     if ang_v is not None:
         q.deskew = 1
         q.ang_v[:] = [float(v) for v in np.asarray(ang_v, dtype=np.float32).reshape(3)]
@@ -274,24 +275,25 @@ def _scan_params(width, height, point_step, fields, row_step, ang_v, scan_period
     return q
 
 
-def scan_callback(data, width: int, height: int, point_step: int, fields: dict[str, int], row_step: int = 0, ang_v=None, scan_period: float = 0.1, T=None,
+def scan_callback(data, width: int, height: int, point_step: int, fields, row_step: int = 0, ang_v=None, scan_period: float = 0.1, T=None,
                   params: dict | None = None, ctx: Context | None = None) -> np.ndarray:
     """PrefilteringComponent::cloud_callback (:116-156) on the payload of a sensor_msgs/PointCloud2, in one call (``mrgfe_scan_callback``):
     pcl::fromROSMsg -> deskewing with the angular velocity ``ang_v`` (None: the IMU queue was empty, no deskewing) -> the transform ``T`` into
     base_link_frame (4 x 4; None: no transform) -> distance_filter -> downsample -> outlier_removal.  The payload goes up once; only the
-    filtered cloud comes back.  Same result as ``ingest_pointcloud2`` -> ``deskew`` -> ``transform_cloud`` -> ``prefilter``."""
+    filtered cloud comes back.  Same result as ``ingest_pointcloud2`` -> ``deskew`` -> ``transform_cloud`` -> ``prefilter``.  ``fields``: a
+    ``{name: offset}`` dict or the message's field list, as ``io.layout_from_fields`` takes them."""
     from .io import pointcloud2_payload
 
     ctx = ctx or default_context()
     buf = pointcloud2_payload(data, width, height, point_step, row_step)
-    q = _scan_params(width, height, point_step, fields, row_step, ang_v, scan_period, T, params)
+    q = _scan_params(width, height, point_step, fields, row_step, ang_v, scan_period, T, params, ctx)
     n = int(width) * int(height)
     out, m = np.empty((max(n, 1), 4), dtype=np.float32), C.c_size_t(0)
     check(lib().mrgfe_scan_callback(ctx._h, C.byref(q), buf.ctypes.data_as(C.POINTER(C.c_uint8)), out.ctypes.data_as(_fp), C.byref(m)))
     return out[: m.value].copy()
 
 
-def scan_callback_to_device(data, width: int, height: int, point_step: int, fields: dict[str, int], dev_ptr: int, capacity: int, row_step: int = 0, ang_v=None,
+def scan_callback_to_device(data, width: int, height: int, point_step: int, fields, dev_ptr: int, capacity: int, row_step: int = 0, ang_v=None,
                             scan_period: float = 0.1, T=None, params: dict | None = None, ctx: Context | None = None) -> int:
     """:func:`scan_callback` with the filtered scan left in device memory at ``dev_ptr`` (packed float4, room for ``capacity`` >= width * height
     points), ready for setInputSourceFromPrefilter / add_pair_device (``mrgfe_scan_callback_device``).  Returns the point count."""
@@ -301,7 +303,7 @@ def scan_callback_to_device(data, width: int, height: int, point_step: int, fiel
         raise ValueError("device buffer too small")
     ctx = ctx or default_context()
     buf = pointcloud2_payload(data, width, height, point_step, row_step)
-    q, m = _scan_params(width, height, point_step, fields, row_step, ang_v, scan_period, T, params), C.c_size_t(0)
+    q, m = _scan_params(width, height, point_step, fields, row_step, ang_v, scan_period, T, params, ctx), C.c_size_t(0)
     check(lib().mrgfe_scan_callback_device(ctx._h, C.byref(q), buf.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_void_p(dev_ptr), C.byref(m)))
     return m.value
 

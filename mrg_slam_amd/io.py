@@ -199,10 +199,42 @@ def pointcloud2_payload(data, width: int, height: int, point_step: int, row_step
     return buf
 
 
-def ingest_pointcloud2(data, width: int, height: int, point_step: int, fields: dict[str, int], row_step: int = 0, ctx=None, dev_ptr: int = 0) -> np.ndarray | None:
+FLOAT32 = 7  # sensor_msgs/PointField.FLOAT32
+
+
+def layout_from_fields(fields, width: int, height: int = 1, point_step: int = 16, row_step: int = 0, is_bigendian: bool = False, ctx=None):
+    """The layout arguments of the calls that read PointCloud2 bytes, from the message's field list (``mrgfe_pointcloud2_layout``): a
+    ``_lib.KeyframeParams`` and whether the layout needs ``Context.set_byte_layouts`` (offsets or steps that are not multiples of 4).
+    ``fields``: a ``{name: offset}`` dict (every field taken as FLOAT32, count 1) or a list of ``(name, offset, datatype, count)`` as
+    sensor_msgs/PointField has them (objects with those attributes do too).  The matching rule is ``pcl::fromROSMsg``'s: the first field with the
+    name, datatype FLOAT32 and count 1 — so a UINT8 ``intensity`` gives ``off_intensity = -1`` (intensity 0), an ``x`` that is FLOAT64 an error.
+    With ``ctx`` and a field LIST, the context is switched to byte layouts when the layout needs it (and is never switched back here): the list is
+    the message's own description.  A ``{name: offset}`` dict is the caller's claim and switches nothing: such a layout is refused by the call it is
+    handed to, as it always was, unless the caller has switched the context on (``Context.set_byte_layouts``)."""
+    import ctypes as C
+
+    from . import _lib
+
+    if isinstance(fields, dict):
+        items = [(k, v, FLOAT32, 1) for k, v in fields.items() if v is not None and int(v) >= 0]  # (``"intensity": None`` or -1: no such field)
+    else:
+        items = [(f.name, f.offset, f.datatype, f.count) if hasattr(f, "offset") else tuple(f) for f in fields]
+    arr = (_lib.PointField * max(len(items), 1))()
+    for a, (name, off, dt, cnt) in zip(arr, items):
+        a.name, a.offset, a.datatype, a.count = (name.encode() if isinstance(name, str) else bytes(name)), int(off), int(dt), int(cnt)
+    lay, needs = _lib.KeyframeParams(), C.c_int(0)
+    _lib.check(_lib.lib().mrgfe_pointcloud2_layout(arr, len(items), int(width), int(height), int(point_step), int(row_step or 0), int(bool(is_bigendian)), C.byref(lay),
+                                                   C.byref(needs)))
+    if needs.value and ctx is not None and not isinstance(fields, dict):
+        ctx.set_byte_layouts(True)
+    return lay, bool(needs.value)
+
+
+def ingest_pointcloud2(data, width: int, height: int, point_step: int, fields, row_step: int = 0, ctx=None, dev_ptr: int = 0) -> np.ndarray | None:
     """pcl::fromROSMsg on the GPU: the PointCloud2 payload goes to the device as it is and x, y, z, intensity are gathered
     there (``mrgfe_ingest_pointcloud2``).  Returns the packed N x 4 float32 cloud, or — with ``dev_ptr`` (room for N packed
-    points in device memory) — leaves it there and returns None.  Same result as :func:`xyzi_from_pointcloud2`."""
+    points in device memory) — leaves it there and returns None.  Same result as :func:`xyzi_from_pointcloud2`.  ``fields``: as
+    :func:`layout_from_fields` takes them (a field list whose layout needs it switches the context to byte layouts)."""
     import ctypes as C
 
     from ._lib import check, default_context, lib
@@ -211,9 +243,9 @@ def ingest_pointcloud2(data, width: int, height: int, point_step: int, fields: d
     n = int(width) * int(height)
     buf = pointcloud2_payload(data, width, height, point_step, row_step)
     out = None if dev_ptr else np.empty((n, 4), dtype=np.float32)
-    oi = fields.get("intensity")
-    check(lib().mrgfe_ingest_pointcloud2(ctx._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), int(width), int(height), int(point_step), int(row_step), int(fields["x"]), int(fields["y"]),
-                                         int(fields["z"]), -1 if oi is None else int(oi),
+    lay, _ = layout_from_fields(fields, width, height, point_step, row_step, ctx=ctx)
+    check(lib().mrgfe_ingest_pointcloud2(ctx._h, buf.ctypes.data_as(C.POINTER(C.c_uint8)), lay.width, lay.height, lay.point_step, lay.row_step, lay.off_x, lay.off_y, lay.off_z,
+                                         lay.off_intensity,
                                          out.ctypes.data_as(C.POINTER(C.c_float)) if out is not None else None, C.c_void_p(dev_ptr) if dev_ptr else None))
     return out
 

@@ -30,14 +30,15 @@ class KeyFrameSnapshot:
     first_keyframe: bool = False
 
 
-def keyframe_params(msg: dict) -> KeyframeParams:
-    """struct mrgfe_keyframe_params of a PointCloud2 given as a dict (``width``, ``height``, ``point_step``, ``fields``, optionally ``row_step``)."""
-    p = KeyframeParams()
-    lib().mrgfe_keyframe_default_params(C.byref(p))
-    f = msg["fields"]
-    p.width, p.height, p.point_step, p.row_step = int(msg["width"]), int(msg.get("height", 1)), int(msg["point_step"]), int(msg.get("row_step", 0) or 0)
-    p.off_x, p.off_y, p.off_z = int(f["x"]), int(f["y"]), int(f["z"])
-    p.off_intensity = int(f["intensity"]) if f.get("intensity") is not None else -1
+def keyframe_params(msg: dict, ctx: Context | None = None) -> KeyframeParams:
+    """struct mrgfe_keyframe_params of a PointCloud2 given as a dict (``width``, ``height``, ``point_step``, ``fields``, optionally ``row_step``,
+    ``is_bigendian``).  ``fields``: a ``{name: offset}`` dict or the message's field list, as ``io.layout_from_fields`` takes them; with ``ctx`` a
+    field list whose layout needs it switches that context to byte layouts."""
+    from .io import layout_from_fields
+
+    row_step = int(msg.get("row_step", 0) or 0)
+    p, _ = layout_from_fields(msg["fields"], msg["width"], msg.get("height", 1), msg["point_step"], row_step, msg.get("is_bigendian", False), ctx=ctx)
+    p.row_step = row_step  # (0 stays 0: the call fills it in)
     return p
 
 
@@ -75,7 +76,7 @@ class MapCloudStore:
         ``centres_sensor`` (K x 3, sensor frame, K <= 64; robot_radius_sqr is float(radius * radius), :406-407) is split off, and the kept cloud
         becomes keyframe ``key`` of this store.  Returns ``(kept, removed)``; an output that is not wanted is None and is not downloaded."""
         msg = payload_or_msg if isinstance(payload_or_msg, dict) else pointcloud2_from_xyzi(payload_or_msg)
-        p = keyframe_params(msg)
+        p = keyframe_params(msg, self._ctx)
         n = int(p.width) * int(p.height)
         buf = np.frombuffer(msg["data"], dtype=np.uint8) if n else np.zeros(0, dtype=np.uint8)
         ctr = np.ascontiguousarray(np.asarray(centres_sensor if centres_sensor is not None else np.zeros((0, 3)), dtype=np.float32).reshape(-1, 3))
@@ -104,7 +105,7 @@ class MapCloudStore:
             buf = np.frombuffer(msg["data"], dtype=np.uint8)
             keep.append(buf)
             msgs[i].key = int(key)
-            msgs[i].layout = keyframe_params(msg)
+            msgs[i].layout = keyframe_params(msg, self._ctx)
             msgs[i].data = buf.ctypes.data if buf.nbytes else None
             msgs[i].data_bytes = buf.nbytes
         added = np.zeros(n, dtype=np.uint8)

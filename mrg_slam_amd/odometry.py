@@ -239,7 +239,8 @@ class HipOdometry:
         return d, d.ctypes.data_as(C.POINTER(C.c_float))
 
     def frame(self, msg_or_cloud, stamp: float, msf_delta=None, want_status: bool = False, want_aligned: bool = False) -> OdomFrame:
-        """One frame from a PointCloud2 dict (``data``, ``width``, ``height``, ``point_step``, ``row_step``, ``fields``: name -> offset) or from an
+        """One frame from a PointCloud2 dict (``data``, ``width``, ``height``, ``point_step``, ``row_step``, ``fields``: name -> offset, or the
+        message's field list as ``io.layout_from_fields`` takes it) or from an
         N x 4 float32 cloud (sent as the packed 16-byte message)."""
         import ctypes as C
 
@@ -249,10 +250,12 @@ class HipOdometry:
         lay = _lib.KeyframeParams()
         if isinstance(msg_or_cloud, dict):
             m = msg_or_cloud
-            f = m["fields"]
+            from .io import layout_from_fields
+
             data = m["data"]
-            lay.width, lay.height, lay.point_step, lay.row_step = int(m["width"]), int(m["height"]), int(m["point_step"]), int(m.get("row_step", 0))
-            lay.off_x, lay.off_y, lay.off_z, lay.off_intensity = int(f["x"]), int(f["y"]), int(f["z"]), int(f.get("intensity", -1))
+            row_step = int(m.get("row_step", 0) or 0)  # (a field list whose layout needs it switches the registration's context to byte layouts)
+            lay, _ = layout_from_fields(m["fields"], m["width"], m["height"], m["point_step"], row_step, m.get("is_bigendian", False), ctx=getattr(self.reg, "_ctx", None))
+            lay.row_step = row_step
         else:
             c = np.ascontiguousarray(msg_or_cloud, dtype=np.float32)
             if c.ndim != 2 or c.shape[1] != 4:

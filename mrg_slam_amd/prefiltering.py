@@ -158,10 +158,11 @@ class PrefilteringComponent:
             src = self.ops.transform(src, T)
         return self.ops.filters(src, self.p)
 
-    def pointcloud2_callback(self, data, width: int, height: int, point_step: int, fields: dict, row_step: int = 0, stamp: float = 0.0, frame_id: str = "",
+    def pointcloud2_callback(self, data, width: int, height: int, point_step: int, fields, row_step: int = 0, stamp: float = 0.0, frame_id: str = "",
                              dev_ptr: int = 0):
         """``cloud_callback`` from the wire message (the payload and layout of a sensor_msgs/PointCloud2): pcl::fromROSMsg happens in the same
-        GPU call as the rest.  Returns the filtered cloud, or — with ``dev_ptr`` (device memory for width * height packed points) — leaves it
+        GPU call as the rest.  ``fields``: a ``{name: offset}`` dict or the message's field list ``(name, offset, datatype, count)``, as
+        ``io.layout_from_fields`` takes them (the list switches the context to byte layouts when the records need it: Velodyne's 22-byte points).  Returns the filtered cloud, or — with ``dev_ptr`` (device memory for width * height packed points) — leaves it
         there and returns its point count; None where the reference returns early.  Needs point operations with ``scan_pointcloud2`` (HipOps)."""
         if int(width) * int(height) == 0:
             return None
