@@ -627,7 +627,8 @@ int  mrgfe_batch_forget(mrgfe_batch* b, uint64_t cloud_key);
  * covariances are cached there as for mrgfe_batch_add_pair_keyed (mrgfe_batch_store_bytes counts the covariances only; mrgfe_batch_has_cloud does not
  * report such an entry), and mrgfe_batch_forget / mrgfe_batch_clear treat it like a keyed pair.  Records are those of the same batch fed from host
  * memory, bit for bit.  Return the target / pair index (>= 0) or an error (< 0): MRGFE_ERR_INVALID for a key the store does not hold or a store on
- * another device.  mrgfe_node_* has no such form: its members sit on other devices than the store. */
+ * another device.  The node's form is mrgfe_node_add_target_from_store / _add_pair_from_store (below): a member on the store's device goes through these two
+ * calls, a member on another device reads a replica it keeps of the keyframe. */
 int  mrgfe_batch_add_target_from_store(mrgfe_batch* b, mrgfe_map_store* store, uint64_t key);
 int  mrgfe_batch_add_pair_from_store(mrgfe_batch* b, int target_index, mrgfe_map_store* store, uint64_t key, const float guess[16]);
 int  mrgfe_batch_set_guess(mrgfe_batch* b, int pair_index, const float guess[16]);
@@ -720,7 +721,8 @@ int  mrgfe_batch_align_best_async(mrgfe_batch* b, double fitness_max_range, doub
  *      `next`, first and static keyframes are consistent without an alignment, a loop found for new keyframe k prunes the candidates of k + 1;
  *   7. add_loop for every loop.
  * Same loops as the sequential loop.  Clouds are named by map-store key alone (mrgfe_batch_add_target_from_store / _add_pair_from_store).  OUT OF SCOPE:
- * host clouds; mrgfe_node_* (it has no store form); the PCL_GICP_* methods (batches refuse them, and that stays).
+ * host clouds; the PCL_GICP_* methods (batches and nodes refuse them, and that stays).  mrgfe_loop_create_node (below, after mrgfe_node_*) runs the same
+ * detector over the GPUs of a node: the two stages on a mrgfe_node fed by key from the store, everything else — handle, controller, validation — as here.
  * Arithmetic (csrc/loop_ctl.h): normalize_estimate and the guess in double, cast to float (:124,129-133,183-188; Isometry3d::inverse() is the rigid
  * inverse); the consistency deltas (:242-245, :285-291) with Matrix4f products, the general float inverse and Quaternionf::angularDistance. */
 typedef struct mrgfe_loop mrgfe_loop;
@@ -809,6 +811,32 @@ int    mrgfe_node_add_target_keyed(mrgfe_node* node, uint64_t cloud_key, const f
 /* one candidate: setInputSource(candidate->cloud) + align(guess), loop_detector.cpp:127-134: returns the pair index (>= 0) or an error (< 0) */
 int    mrgfe_node_add_pair(mrgfe_node* node, int target_index, const float* src_xyzi, size_t n, size_t stride_bytes, const float guess[16]);
 int    mrgfe_node_add_pair_keyed(mrgfe_node* node, int target_index, uint64_t cloud_key, const float* src_xyzi, size_t n, size_t stride_bytes, const float guess[16]);
+/* A target / a pair whose cloud is keyframe `key` of a map store (mrgfe_keyframe_callback, mrgfe_map_store_add) on ANY device: nothing comes from host
+ * memory.  The key is looked up when the call is made, under the store's lock alone, and the store's stream is waited for there (mrgfe_map_store_add
+ * uploads asynchronously); MRGFE_ERR_INVALID for a NULL argument, a target index out of range, or a key the store lacks (named in mrgfe_last_error();
+ * nothing is queued).  Like mrgfe_batch_add_*_from_store, the STORE MUST OUTLIVE the node's use of it: destroy the node, or mrgfe_node_clear and
+ * mrgfe_node_forget(0) it, first.
+ *   A member on the store's device reads the store's memory in place, through mrgfe_batch_add_target_from_store / _add_pair_from_store (for the GICP
+ * methods, not ICP_HIP, the k-NN covariances of a source are cached in the member's batch under `key`).
+ *   A member on another device keeps a REPLICA of the keyframe on its own device, copied store device -> member device on the member's stream
+ * (hipMemcpyPeerAsync; peer access need not be enabled, the runtime stages the copy when it is not).  Replicas are kept by key across calls next to the
+ * member's keyed targets, under the same byte cap (MRGFE_KEYFRAME_STORE_MB) and least-recently-named rule; one the current call names, or one under a target
+ * the member still holds built (mrgfe_node_clear_pairs), is never dropped.  A replicated source enters the member's batch so that its covariances are
+ * cached under `key` exactly as above.  mrgfe_node_store_bytes counts replicas (16 bytes per point), mrgfe_node_forget drops them, mrgfe_node_clear
+ * drops nothing resident.
+ * Store-fed and host-fed targets and pairs may be mixed in one list; the records of mrgfe_node_align / mrgfe_node_align_best are those of ONE mrgfe_batch
+ * holding the same list from the same store, bit for bit, for every member count and batch method. */
+int    mrgfe_node_add_target_from_store(mrgfe_node* node, mrgfe_map_store* store, uint64_t key);
+int    mrgfe_node_add_pair_from_store(mrgfe_node* node, int target_index, mrgfe_map_store* store, uint64_t key, const float guess[16]);
+/* The pairs go, the declared targets keep their indices (mrgfe_batch_clear_pairs over the node).  A member keeps the targets its previous align built —
+ * it clears the pairs of its batch alone — as long as the node's target list has not been cleared, and builds only the targets its new block needs and
+ * lacks.  Blocks move with the length of the list, so reuse is an optimisation, never a condition: the records are those of a fresh node given the same
+ * targets and the new pairs, bit for bit.  Host-fed targets without a key stay declared too: THEIR BUFFERS MUST STAY VALID until the last align that names
+ * them (a member that lacks one uploads it then), not only until the first. */
+int    mrgfe_node_clear_pairs(mrgfe_node* node);
+/* the last mrgfe_node_align / _align_best, the members' counts added up: out[0] clouds read in place in the store, out[1] clouds copied to a replica in this
+ * call, out[2] bytes copied, out[3] targets a member found already built (mrgfe_node_clear_pairs) */
+int    mrgfe_node_store_stats(const mrgfe_node* node, int64_t out[4]);
 int    mrgfe_node_num_pairs(const mrgfe_node* node);
 int    mrgfe_node_align(mrgfe_node* node, double fitness_max_range, mrgfe_pair_result* results /* n_pairs, pair_id = index in the list */);
 /* mrgfe_batch_align_best over the node: the records (pose fields; fitness exact, a certified bound or DBL_MAX), fit_state, best[g] — an index into the
@@ -836,6 +864,15 @@ int    mrgfe_node_shard(const mrgfe_node* node, int member, int* first_pair, int
 int    mrgfe_node_last_gather(const mrgfe_node* node);
 int    mrgfe_node_forget(mrgfe_node* node, uint64_t cloud_key); /* drops a key from every member's stores (0: all) */
 size_t mrgfe_node_store_bytes(const mrgfe_node* node);
+/* LoopDetector::detect in one call (mrgfe_loop_*, above) over a NODE: the same handle, mrgfe_loop_detect / _reset / _stats / _timing, controller and
+ * validation before anything is queued as a detector of mrgfe_loop_create; only the two stages run elsewhere.  Stage 1: mrgfe_node_clear, the targets
+ * and pairs by key from `store` (mrgfe_node_add_*_from_store), mrgfe_node_align — with fitness_selection 1 mrgfe_node_align_best, same groups and cap as
+ * on a batch.  Stage 2: mrgfe_node_clear_pairs, the consistency pairs on the same target indices, mrgfe_node_align without fitness.  Same loops,
+ * relative poses and scores as the detector over one batch, bit for bit, for any member count.  mrgfe_loop_stats out[4] counts the targets the stages
+ * declared.  A failing call — also a failing member, named in mrgfe_last_error() — leaves the LoopManager, the counters, the stats and the timing as they
+ * were, and the node usable.  MRGFE_ERR_INVALID: a NULL argument, fitness_selection not 0 or 1.  The store may sit on any device; nothing else queues on
+ * the node while a detect call runs.  The handle is destroyed BEFORE its node and its store. */
+int    mrgfe_loop_create_node(mrgfe_node* node, mrgfe_map_store* store, const mrgfe_loop_params* params, mrgfe_loop** out);
 /* the reference's sequential rule on gathered records (loop_detector.cpp:126-145: "if( !hasConverged() || score > best_score ) continue;"): group g
  * = records group_first[g] .. group_first[g + 1] - 1 (the candidates of one new keyframe, in candidate order); best[g] = position within the
  * group or -1, best_score[g] = its fitness or DBL_MAX.  Among equal scores the LAST candidate wins, as there. */

@@ -182,6 +182,10 @@ int  mrgfe_dbg_loop_set_stage_reuse(mrgfe_loop* det, int on);
 /* the LoopManager of `det`: 4 words per entry — the new keyframe's slam_id, the candidate's slam_id, key1, key2 — ordered by the two ids; out: room for
  * `capacity` entries (may be NULL with capacity 0), *n the entries there are */
 int  mrgfe_dbg_loop_manager(const mrgfe_loop* det, int capacity, uint64_t* out, int* n);
+/* how a node's members reach a map-store keyframe (mrgfe_node_add_*_from_store): 0 (the default) in place on the store's device, a replica elsewhere;
+ * 1: always a replica, also on the store's device — there the copy is a plain device-to-device copy and everything after it is the replica route, which
+ * a one-card machine exercises this way.  Same records either way. */
+int  mrgfe_dbg_node_set_store_copy(mrgfe_node* node, int mode);
 
 #ifdef MRGFE_TESTING
 /* hardening hook: the k-th device / pinned allocation of this process from now on (0 = the next one) fails as if the device were out of memory, every

@@ -333,6 +333,10 @@ SIGNATURES = {
     "mrgfe_node_add_pair": (C.c_int, [_vp, C.c_int, _fp, C.c_size_t, C.c_size_t, _fp]),
     "mrgfe_node_add_pair_keyed": (C.c_int, [_vp, C.c_int, C.c_uint64, _fp, C.c_size_t, C.c_size_t, _fp]),
     "mrgfe_node_num_pairs": (C.c_int, [_vp]),
+    "mrgfe_node_add_target_from_store": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "mrgfe_node_add_pair_from_store": (C.c_int, [_vp, C.c_int, _vp, C.c_uint64, _fp]),
+    "mrgfe_node_clear_pairs": (C.c_int, [_vp]),
+    "mrgfe_node_store_stats": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mrgfe_node_align": (C.c_int, [_vp, C.c_double, C.POINTER(PairResult)]),
     "mrgfe_node_align_best": (C.c_int, [_vp, C.c_double, C.c_double, _ip, C.c_int, C.POINTER(PairResult), _ip, _ip, _dp]),
     "mrgfe_node_select_stats": (C.c_int, [_vp, _dp]),
@@ -349,6 +353,7 @@ SIGNATURES = {
     "mrgfe_loop_keyframe_size": (C.c_size_t, []),
     "mrgfe_loop_result_size": (C.c_size_t, []),
     "mrgfe_loop_create": (C.c_int, [_vp, _vp, C.POINTER(LoopParams), C.POINTER(_vp)]),
+    "mrgfe_loop_create_node": (C.c_int, [_vp, _vp, C.POINTER(LoopParams), C.POINTER(_vp)]),
     "mrgfe_loop_destroy": (None, [_vp]),
     "mrgfe_loop_reset": (C.c_int, [_vp]),
     "mrgfe_loop_detect": (C.c_int, [_vp, C.c_int, C.POINTER(LoopKeyframe), C.c_int, C.POINTER(LoopKeyframe), C.c_int, C.POINTER(C.c_uint64), C.POINTER(LoopResult), C.c_int,
@@ -409,6 +414,7 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_odom_source": (C.c_int, [_vp, _fp, _szp, _fp, _u32p]),
     "mrgfe_dbg_loop_set_aligner": (C.c_int, [_vp, _vp, _vp]),  # (the callback goes in as ctypes.cast(LOOP_ALIGNER(fn), c_void_p); NULL: the GPU batches again)
     "mrgfe_dbg_loop_set_stage_reuse": (C.c_int, [_vp, C.c_int]),
+    "mrgfe_dbg_node_set_store_copy": (C.c_int, [_vp, C.c_int]),
     "mrgfe_dbg_loop_manager": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
 }
 # ... and its fault injectors and their allocation count, which exist only in the -DMRGFE_TESTING build (libmrgfe_testing.so: tests/faultinject/ runs under MRGFE_LIB=that file)

@@ -124,6 +124,10 @@ struct mrgfe_reg {
 int batch_align_bounds(mrgfe_batch* b, double max_range, const int32_t* group, mrgfe_pair_result* results, double* lo, double* hi);
 int batch_align_finish(mrgfe_batch* b, const int32_t* state, mrgfe_pair_result* results);
 int batch_align_abandon(mrgfe_batch* b);
+// A pair whose source is keyframe `key` held as a packed device cloud on the batch's device that is NOT the map store's memory (a node member's replica,
+// node.cpp): entered exactly as mrgfe_batch_add_pair_from_store enters a store keyframe — for the GICP family the covariances are cached under `key`,
+// ICP_HIP and the NDTs cache nothing.  The cloud must stay valid as caller device memory does.  Returns the pair index or an error (< 0).
+int batch_add_pair_device_keyed(mrgfe_batch* b, int target, uint64_t key, const void* d_xyzi, size_t n, const float guess[16]);
 
 // map store: keyframe clouds resident in HBM (include/mrgfe.h); its entry points are in api.cpp, a batch takes targets and pairs out of it
 struct mrgfe_map_store {

@@ -456,6 +456,40 @@ int mrgfe_batch_add_target_from_store(mrgfe_batch* b, mrgfe_map_store* s, uint64
         return b->book.add_target_device(p, n);
     });
 }
+// A pair whose source is the packed device cloud `p` of keyframe `key`: for the methods that keep covariances they are cached in the batch's store under the
+// key, next to no cloud (its owner has it: a map store, or a node member's replica of one).  The batch's lock is held.
+static int add_pair_device_keyed(mrgfe_batch* b, const char* fn, int target, uint64_t key, const void* p, size_t n, const float guess[16])
+{
+    MRGFE_TRY(b->ctx->bind());
+    if (target < 0 || target >= b->book.n_targets()) { set_error("%s: target index %d out of range", fn, target); return MRGFE_ERR_INVALID; }
+    mrgfe_batch::Keyframe* kf = nullptr;
+    if (keeps_covariances(b->params)) {  // the covariances of the keyframe are cached under its key, next to no cloud (the store has it)
+        auto it = b->store.find(key);
+        if (it != b->store.end() && it->second->n != n) {
+            if (it->second->last_epoch == b->epoch) { set_error("%s: key %llu is already used in this batch with %u points", fn, static_cast<unsigned long long>(key), it->second->n); return MRGFE_ERR_INVALID; }
+            b->store.erase(it);
+            it = b->store.end();
+        }
+        if (it == b->store.end()) {
+            store_make_room(b, n * 48);
+            std::unique_ptr<mrgfe_batch::Keyframe> fresh(new (std::nothrow) mrgfe_batch::Keyframe());
+            if (!fresh) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+            fresh->n = static_cast<uint32_t>(n);
+            it = b->store.emplace(key, std::move(fresh)).first;
+        }
+        kf = it->second.get();
+    }
+    float g[16];
+    col2row(guess, g);
+    const int pair = b->book.add_pair_device(target, p, n, g);
+    if (pair >= 0 && kf) {
+        kf->last_epoch = b->epoch;
+        kf->last_tick = ++b->tick;
+        if (b->pair_key.size() <= static_cast<size_t>(pair)) b->pair_key.resize(pair + 1, 0);
+        b->pair_key[pair] = key;
+    }
+    return pair;
+}
 int mrgfe_batch_add_pair_from_store(mrgfe_batch* b, int target, mrgfe_map_store* s, uint64_t key, const float guess[16])
 {
     static const char* fn = "mrgfe_batch_add_pair_from_store";
@@ -465,35 +499,7 @@ int mrgfe_batch_add_pair_from_store(mrgfe_batch* b, int target, mrgfe_map_store*
         size_t n = 0;
         MRGFE_TRY(store_lookup(fn, b, s, key, &p, &n));
         MRGFE_LOCK(b->ctx);
-        MRGFE_TRY(b->ctx->bind());
-        if (target < 0 || target >= b->book.n_targets()) { set_error("%s: target index %d out of range", fn, target); return MRGFE_ERR_INVALID; }
-        mrgfe_batch::Keyframe* kf = nullptr;
-        if (keeps_covariances(b->params)) {  // the covariances of the keyframe are cached under its key, next to no cloud (the store has it)
-            auto it = b->store.find(key);
-            if (it != b->store.end() && it->second->n != n) {
-                if (it->second->last_epoch == b->epoch) { set_error("%s: key %llu is already used in this batch with %u points", fn, static_cast<unsigned long long>(key), it->second->n); return MRGFE_ERR_INVALID; }
-                b->store.erase(it);
-                it = b->store.end();
-            }
-            if (it == b->store.end()) {
-                store_make_room(b, n * 48);
-                std::unique_ptr<mrgfe_batch::Keyframe> fresh(new (std::nothrow) mrgfe_batch::Keyframe());
-                if (!fresh) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-                fresh->n = static_cast<uint32_t>(n);
-                it = b->store.emplace(key, std::move(fresh)).first;
-            }
-            kf = it->second.get();
-        }
-        float g[16];
-        col2row(guess, g);
-        const int pair = b->book.add_pair_device(target, p, n, g);
-        if (pair >= 0 && kf) {
-            kf->last_epoch = b->epoch;
-            kf->last_tick = ++b->tick;
-            if (b->pair_key.size() <= static_cast<size_t>(pair)) b->pair_key.resize(pair + 1, 0);
-            b->pair_key[pair] = key;
-        }
-        return pair;
+        return add_pair_device_keyed(b, fn, target, key, p, n, guess);
     });
 }
 int mrgfe_batch_set_guess(mrgfe_batch* b, int pair, const float guess[16])
@@ -684,6 +690,18 @@ int batch_align_finish(mrgfe_batch* b, const int32_t* state, mrgfe_pair_result* 
         }
     }
     return batch_align_ended(b, b->select.t_start, st);
+}
+
+// (api_internal.h) a node member's replica of a store keyframe as a source: mrgfe_batch_add_pair_from_store without the lookup
+int batch_add_pair_device_keyed(mrgfe_batch* b, int target, uint64_t key, const void* d_xyzi, size_t n, const float guess[16])
+{
+    static const char* fn = "batch_add_pair_device_keyed";
+    return abi_guard(fn, [&]() -> int {
+        MRGFE_TRY(check_count(n, fn));
+        if (!b || !guess || key == 0) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(b->ctx);
+        return add_pair_device_keyed(b, fn, target, key, d_xyzi, n, guess);
+    });
 }
 
 int batch_align_abandon(mrgfe_batch* b)

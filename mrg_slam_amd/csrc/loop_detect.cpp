@@ -1,7 +1,7 @@
 // csrc/loop_detect.cpp — mrgfe_loop: LoopDetector::detect (src/mrg_slam/loop_detector.cpp:15-303) in one call over a batch and a map store.  The
 // decisions are the controller's (loop_ctl.h, no HIP); this file checks the arguments, runs the two stages — on the borrowed batch through its public
-// calls (stage 2 after mrgfe_batch_clear_pairs, on the targets stage 1 built), or through the aligner of mrgfe_dbg_loop_set_aligner — and hands the
-// records to the replay.  Entry points follow the rules of api.cpp: codes and a thread-local message, no exception crosses.
+// calls (stage 2 after mrgfe_batch_clear_pairs, on the targets stage 1 built), on a borrowed node through the same calls of mrgfe_node_*
+// (mrgfe_loop_create_node), or through the aligner of mrgfe_dbg_loop_set_aligner — and hands the records to the replay.  Entry points follow the rules of api.cpp: codes and a thread-local message, no exception crosses.
 #include <cfloat>
 #include <chrono>
 #include <cstring>
@@ -20,6 +20,7 @@ static_assert(sizeof(LoopCtlKeyframe) == sizeof(mrgfe_loop_keyframe) && sizeof(L
 struct mrgfe_loop {
     std::mutex       mu;  // one detect at a time (the detector has no context of its own)
     mrgfe_batch*     batch = nullptr;
+    mrgfe_node*      node = nullptr;   // mrgfe_loop_create_node: the stages run on it instead of the batch
     mrgfe_map_store* store = nullptr;
     mrgfe_loop_params params;
     LoopCtl          ctl;
@@ -78,6 +79,7 @@ struct Stage {
         for (mrgfe_pair_result& r : *results) r.fitness = DBL_MAX;
         if (d->aligner) return run_aligner(stage, pairs, want_fitness, results);
         const bool reuse = stage == 2 && d->stage_reuse;
+        if (d->node) return run_node(reuse, pairs, want_fitness, n_groups, results);
         if (reuse) {
             MRGFE_TRY(mrgfe_batch_clear_pairs(d->batch));
         } else {
@@ -104,6 +106,35 @@ struct Stage {
         for (int i = 0; i < P; ++i) group[i] = pairs[i].group;
         return mrgfe_batch_align_best(d->batch, d->params.fitness_score_max_range, d->params.fitness_score_thresh, group.data(), n_groups, results->data(), nullptr, best.data(),
                                       best_score.data());
+    }
+
+    // the same stage over the GPUs of a node: the same list, groups and cap, through the node's forms of the same calls
+    int run_node(bool reuse, const std::vector<LoopCtlPair>& pairs, bool want_fitness, int n_groups, std::vector<mrgfe_pair_result>* results)
+    {
+        const int P = static_cast<int>(pairs.size());
+        if (reuse) {
+            MRGFE_TRY(mrgfe_node_clear_pairs(d->node));
+        } else {
+            MRGFE_TRY(mrgfe_node_clear(d->node));
+            std::fill(tid.begin(), tid.end(), -1);
+        }
+        for (const LoopCtlPair& pr : pairs) {
+            if (tid[pr.k] < 0) {
+                const int t = mrgfe_node_add_target_from_store(d->node, d->store, news[pr.k].key);
+                if (t < 0) return t;
+                tid[pr.k] = t;
+                ++targets_queued;
+            }
+            const int pi = mrgfe_node_add_pair_from_store(d->node, tid[pr.k], d->store, pr.source_key, pr.guess);
+            if (pi < 0) return pi;
+        }
+        if (!want_fitness) return mrgfe_node_align(d->node, -1.0, results->data());
+        if (d->params.fitness_selection == 0) return mrgfe_node_align(d->node, d->params.fitness_score_max_range, results->data());
+        std::vector<int32_t> group(static_cast<size_t>(std::max(P, 1))), best(static_cast<size_t>(std::max(n_groups, 1)));
+        std::vector<double>  best_score(best.size());
+        for (int i = 0; i < P; ++i) group[i] = pairs[i].group;
+        return mrgfe_node_align_best(d->node, d->params.fitness_score_max_range, d->params.fitness_score_thresh, group.data(), n_groups, results->data(), nullptr, best.data(),
+                                     best_score.data());
     }
 
     int run_aligner(int stage, const std::vector<LoopCtlPair>& pairs, bool want_fitness, std::vector<mrgfe_pair_result>* results)
@@ -168,6 +199,23 @@ int mrgfe_loop_create(mrgfe_batch* batch, mrgfe_map_store* store, const mrgfe_lo
         return MRGFE_OK;
     });
 }
+int mrgfe_loop_create_node(mrgfe_node* node, mrgfe_map_store* store, const mrgfe_loop_params* params, mrgfe_loop** out)
+{
+    return abi_guard("mrgfe_loop_create_node", [&]() -> int {
+        if (!out) { set_error("mrgfe_loop_create_node: NULL argument"); return MRGFE_ERR_INVALID; }
+        *out = nullptr;
+        if (!params || !node || !store) { set_error("mrgfe_loop_create_node: NULL argument"); return MRGFE_ERR_INVALID; }
+        if (params->fitness_selection != 0 && params->fitness_selection != 1) { set_error("mrgfe_loop_create_node: fitness_selection must be 0 (full) or 1 (bounded), not %d", params->fitness_selection); return MRGFE_ERR_INVALID; }
+        mrgfe_loop* d = new (std::nothrow) mrgfe_loop();
+        if (!d) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+        d->node = node;
+        d->store = store;
+        d->params = *params;
+        ctl_params(*params, &d->ctl.p);
+        *out = d;
+        return MRGFE_OK;
+    });
+}
 void mrgfe_loop_destroy(mrgfe_loop* det) { delete det; }
 int mrgfe_loop_reset(mrgfe_loop* det)
 {
@@ -205,7 +253,7 @@ int mrgfe_loop_detect(mrgfe_loop* det, int n_keyframes, const mrgfe_loop_keyfram
             return MRGFE_OK;
         }
         if (!det->aligner) {
-            if (!det->batch || !det->store) { set_error("%s: the detector has neither a batch and a store nor an aligner", fn); return MRGFE_ERR_STATE; }
+            if ((!det->batch && !det->node) || !det->store) { set_error("%s: the detector has neither a batch and a store nor an aligner", fn); return MRGFE_ERR_STATE; }
             // every key the two stages can name, before anything is queued
             auto in_store = [&](uint64_t key) -> int {
                 if (mrgfe_map_store_has(det->store, key, nullptr)) return MRGFE_OK;

@@ -71,10 +71,17 @@ Rccl& rccl()
     return r;
 }
 
+// a cloud named by map-store key (mrgfe_node_add_*_from_store): where it lies, as the lookup at the add call found it (the store is append-only)
+struct StoreRef {
+    mrgfe_map_store* store = nullptr;  // null: a host-fed cloud
+    const float4*    d = nullptr;
+    int              device = -1;
+};
 struct TargetDecl {
     uint64_t     key;
     const float* xyzi;
     size_t       n, stride;
+    StoreRef     from = {};
 };
 struct PairDecl {
     int          target;
@@ -82,11 +89,13 @@ struct PairDecl {
     const float* xyzi;
     size_t       n, stride;
     float        guess[16];
+    StoreRef     from = {};
 };
 struct ResidentCloud {
     DevBuf   buf;
     size_t   n = 0;
     uint64_t last_use = 0;  // serial of the member's align call that named it last
+    bool     in_batch = false;  // a target of the member's batch reads it: it stays until the batch is cleared (mrgfe_node_clear_pairs keeps targets built)
 };
 
 // JOB_BOUNDS / JOB_FINISH: the two stages of mrgfe_node_align_best; JOB_ABANDON: give up a first stage that succeeded, because another member's failed
@@ -110,8 +119,13 @@ struct mrgfe_node {
         int          first = 0, count = 0;  // this member's block of the pair list
         std::vector<mrgfe_pair_result> local;
         std::unordered_map<uint64_t, std::unique_ptr<ResidentCloud>> targets;  // keyed target clouds resident on this member's device
+        std::unordered_map<uint64_t, std::unique_ptr<ResidentCloud>> replicas; // map-store keyframes copied to this member's device, as targets and as sources
         uint64_t     align_serial = 0;
-        size_t       target_cap = size_t(16) << 30;             // bytes of keyed targets kept resident (MRGFE_KEYFRAME_STORE_MB, the batch store's cap), LRU beyond it
+        size_t       target_cap = size_t(16) << 30;             // bytes of keyed targets and replicas kept resident (MRGFE_KEYFRAME_STORE_MB, the batch store's cap), LRU beyond it
+        // mrgfe_node_clear_pairs: the targets the member's batch holds, node target index -> index in the batch, good while batch_gen is the node's target_gen
+        std::unordered_map<int, int> built;
+        uint64_t     batch_gen = 0;                             // 0: the batch's targets are not to be reused (never filled, a failed call, mrgfe_node_forget)
+        int64_t      store_stat[4] = {0, 0, 0, 0};              // mrgfe_node_store_stats, this member's part of the last align
         DevBuf       d_send, d_recv;                            // RCCL gather
         int          fail_next = 0;                             // test hook
         bool         staged = false;                            // mrgfe_node_align_best: this member's first stage succeeded and its selection is pending
@@ -121,6 +135,9 @@ struct mrgfe_node {
     std::vector<std::unique_ptr<Member>> members;
     std::vector<TargetDecl>  targets;
     std::vector<PairDecl>    pairs;
+    uint64_t                 target_gen = 1;     // counts mrgfe_node_clear: the target indices mean the same clouds while it stands
+    bool                     keep_targets = false;  // mrgfe_node_clear_pairs since the last mrgfe_node_clear: members keep what they built for these targets
+    int                      store_copy = 0;     // mrgfe_dbg_node_set_store_copy
     double                   fitness_max_range = -1.0;
     std::vector<nccl_comm_t> comms;     // one per member when the RCCL gather is in use
     bool                     rccl_tried = false;
@@ -143,15 +160,70 @@ int member_fail(Member& m, int status)
 {
     m.status = status;
     m.error = mrgfe_last_error();
+    m.batch_gen = 0;  // whatever the batch holds now, the next call starts it afresh
     return status;
 }
 
-// the member's block into its batch: targets in order of first use, pairs in list order (nothing for an empty block)
+// room for `need` more bytes of resident clouds under the member's cap: least recently named keyed targets and replicas go first, never one this call has
+// named, never one a target of the member's batch still reads.  The store is bounded (in the LoopDetector flow every keyframe is a target once, so
+// an unbounded store grows by a cloud per keyframe for the life of the process).  The member's context is locked and bound.
+void member_make_room(Member& m, size_t need)
+{
+    size_t held = 0;
+    for (auto& kv : m.targets) held += kv.second->buf.cap;
+    for (auto& kv : m.replicas) held += kv.second->buf.cap;
+    while (held + need > m.target_cap) {
+        std::unordered_map<uint64_t, std::unique_ptr<ResidentCloud>>* from = nullptr;
+        uint64_t victim = 0, oldest = 0;
+        for (auto* map : {&m.targets, &m.replicas})
+            for (auto& kv : *map) {
+                const ResidentCloud& c = *kv.second;
+                if (c.last_use >= m.align_serial || !c.buf.p || c.in_batch || (from && c.last_use >= oldest)) continue;
+                from = map; victim = kv.first; oldest = c.last_use;
+            }
+        if (!from) break;  // everything left is named by this call or built upon: the block's own working set may exceed the cap
+        auto it = from->find(victim);
+        held -= it->second->buf.cap;
+        from->erase(it);
+    }
+}
+
+// keyframe `key` of a map store on this member's device: the replica kept under the key, copied store device -> member device on the member's stream when it
+// is not there (the runtime stages the copy where peer access is not enabled)
+int member_replica(Member& m, uint64_t key, size_t n, const StoreRef& from, ResidentCloud** out)
+{
+    std::unique_ptr<ResidentCloud>& rc = m.replicas[key];
+    if (!rc) rc.reset(new (std::nothrow) ResidentCloud());
+    if (!rc) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+    rc->last_use = m.align_serial;
+    *out = rc.get();
+    if (rc->n == n && rc->buf.p) return MRGFE_OK;
+    if (rc->in_batch) { set_error("member %d: keyframe %llu is held with %zu points under a built target and named with %zu", m.index, static_cast<unsigned long long>(key), rc->n, n); return MRGFE_ERR_INVALID; }
+    const size_t bytes = std::max<size_t>(n, 1) * 16;
+    MRGFE_LOCK(m.ctx);
+    MRGFE_TRY(m.ctx->bind());
+    rc->n = 0;
+    rc->buf.release();
+    member_make_room(m, bytes);
+    MRGFE_TRY(rc->buf.ensure_exact(bytes));  // (filled once: mrgfe_node_store_bytes counts 16 bytes per point)
+    if (n) {
+        if (from.device == m.device) MRGFE_HIP_CHECK(hipMemcpyAsync(rc->buf.p, from.d, n * 16, hipMemcpyDeviceToDevice, m.ctx->stream));
+        else                         MRGFE_HIP_CHECK(hipMemcpyPeerAsync(rc->buf.p, m.device, from.d, from.device, n * 16, m.ctx->stream));
+    }
+    rc->n = n;
+    m.store_stat[1] += 1;
+    m.store_stat[2] += static_cast<int64_t>(n * 16);
+    return MRGFE_OK;
+}
+
+// the member's block into its batch: targets in order of first use, pairs in list order (nothing for an empty block).  After mrgfe_node_clear_pairs the
+// batch keeps the targets it holds (mrgfe_batch_clear_pairs) and only those the block needs and lacks are added.
 int member_fill(mrgfe_node* node, Member& m)
 {
     m.status = MRGFE_OK;
     m.error.clear();
     m.local.assign(static_cast<size_t>(m.count), mrgfe_pair_result{});
+    std::fill(m.store_stat, m.store_stat + 4, int64_t(0));
 #ifdef MRGFE_TESTING
     if (m.fail_next) {
         m.fail_next = 0;
@@ -161,8 +233,15 @@ int member_fill(mrgfe_node* node, Member& m)
 #endif
     if (m.count == 0) return MRGFE_OK;
     ++m.align_serial;
-    int st = mrgfe_batch_clear(m.batch.get());
+    const bool reuse = node->keep_targets && m.batch_gen == node->target_gen;
+    m.batch_gen = 0;  // until the block is in
+    int st = reuse ? mrgfe_batch_clear_pairs(m.batch.get()) : mrgfe_batch_clear(m.batch.get());
     if (st != MRGFE_OK) return member_fail(m, st);
+    if (!reuse) {
+        m.built.clear();
+        for (auto& kv : m.targets) kv.second->in_batch = false;
+        for (auto& kv : m.replicas) kv.second->in_batch = false;
+    }
     std::unordered_map<int, int> local_target;
     for (int i = m.first; i < m.first + m.count; ++i) {
         const PairDecl& p = node->pairs[static_cast<size_t>(i)];
@@ -170,7 +249,21 @@ int member_fill(mrgfe_node* node, Member& m)
         if (it == local_target.end()) {
             const TargetDecl& t = node->targets[static_cast<size_t>(p.target)];
             int ti;
-            if (t.key) {
+            auto bt = m.built.find(p.target);
+            if (bt != m.built.end()) {
+                ti = bt->second;  // built by an earlier align on this target list
+                ++m.store_stat[3];
+            } else if (t.from.store) {
+                if (t.from.device == m.device && node->store_copy == 0) {
+                    ti = mrgfe_batch_add_target_from_store(m.batch.get(), t.from.store, t.key);
+                    ++m.store_stat[0];
+                } else {
+                    ResidentCloud* rc = nullptr;
+                    if ((st = member_replica(m, t.key, t.n, t.from, &rc)) != MRGFE_OK) return member_fail(m, st);
+                    rc->in_batch = true;
+                    ti = mrgfe_batch_add_target_device(m.batch.get(), rc->buf.p, rc->n);
+                }
+            } else if (t.key) {
                 // a keyed target stays resident on this member's device: uploaded once, found again by the next batches that name it
                 std::unique_ptr<ResidentCloud>& rc = m.targets[t.key];
                 if (!rc) rc.reset(new (std::nothrow) ResidentCloud());
@@ -178,36 +271,51 @@ int member_fill(mrgfe_node* node, Member& m)
                 rc->last_use = m.align_serial;
                 if (rc->n != t.n || !rc->buf.p) {
                     if (!t.xyzi && t.n) { set_error("member %d: target key %llu is not resident and no cloud was given", m.index, static_cast<unsigned long long>(t.key)); return member_fail(m, MRGFE_ERR_INVALID); }
+                    if (rc->in_batch) { set_error("member %d: target key %llu is held with %zu points under a built target and named with %zu", m.index, static_cast<unsigned long long>(t.key), rc->n, t.n); return member_fail(m, MRGFE_ERR_INVALID); }
                     MRGFE_LOCK(m.ctx);
                     if ((st = m.ctx->bind()) != MRGFE_OK) return member_fail(m, st);
-                    // the store is bounded (in the LoopDetector flow every keyframe is a target once, so an unbounded store grows by a cloud per
-                    // keyframe for the life of the process): least recently named keys go first, never one this call has named
-                    size_t held = 0;
-                    for (auto& kv : m.targets) held += kv.second->buf.cap;
-                    const size_t need = std::max<size_t>(t.n, 1) * 16;
-                    while (held + need > m.target_cap) {
-                        auto victim = m.targets.end();
-                        for (auto jt = m.targets.begin(); jt != m.targets.end(); ++jt)
-                            if (jt->second->last_use < m.align_serial && jt->second->buf.p && (victim == m.targets.end() || jt->second->last_use < victim->second->last_use)) victim = jt;
-                        if (victim == m.targets.end()) break;  // everything left is named by this call: the block's own working set may exceed the cap
-                        held -= victim->second->buf.cap;
-                        m.targets.erase(victim);
-                    }
+                    member_make_room(m, std::max<size_t>(t.n, 1) * 16);
                     if ((st = rc->buf.ensure(std::max<size_t>(t.n, 1) * 16)) != MRGFE_OK) return member_fail(m, st);
                     if ((st = upload_cloud(m.ctx.get(), t.xyzi, t.n, t.stride, rc->buf.p)) != MRGFE_OK) return member_fail(m, st);
                     rc->n = t.n;
                 }
+                rc->in_batch = true;
                 ti = mrgfe_batch_add_target_device(m.batch.get(), rc->buf.p, rc->n);
             } else {
                 ti = mrgfe_batch_add_target(m.batch.get(), t.xyzi, t.n, t.stride);
             }
             if (ti < 0) return member_fail(m, ti);
+            m.built[p.target] = ti;
             it = local_target.emplace(p.target, ti).first;
         }
-        const int pi = p.key ? mrgfe_batch_add_pair_keyed(m.batch.get(), it->second, p.key, p.xyzi, p.n, p.stride, p.guess)
-                             : mrgfe_batch_add_pair(m.batch.get(), it->second, p.xyzi, p.n, p.stride, p.guess);
+        int pi;
+        if (p.from.store) {
+            if (p.from.device == m.device && node->store_copy == 0) {
+                pi = mrgfe_batch_add_pair_from_store(m.batch.get(), it->second, p.from.store, p.key, p.guess);
+                ++m.store_stat[0];
+            } else {
+                // (the covariances of the GICP family are cached in the batch under the key, as the route above caches them)
+                ResidentCloud* rc = nullptr;
+                if ((st = member_replica(m, p.key, p.n, p.from, &rc)) != MRGFE_OK) return member_fail(m, st);
+                pi = batch_add_pair_device_keyed(m.batch.get(), it->second, p.key, rc->buf.p, rc->n, p.guess);
+            }
+        } else {
+            pi = p.key ? mrgfe_batch_add_pair_keyed(m.batch.get(), it->second, p.key, p.xyzi, p.n, p.stride, p.guess)
+                       : mrgfe_batch_add_pair(m.batch.get(), it->second, p.xyzi, p.n, p.stride, p.guess);
+        }
         if (pi < 0) return member_fail(m, pi);
     }
+    if (m.store_stat[1]) {  // the replicas are complete before anything reads them, and a copy that failed fails this member here
+        MRGFE_LOCK(m.ctx);
+        if ((st = m.ctx->bind()) != MRGFE_OK) return member_fail(m, st);
+        const hipError_t e = hipStreamSynchronize(m.ctx->stream);
+        if (e != hipSuccess) {
+            set_error("member %d: copying keyframes from the map store: %s", m.index, hipGetErrorString(e));
+            for (auto& kv : m.replicas) if (kv.second->last_use == m.align_serial) kv.second->n = 0;  // (not known to be complete; member_fail has the batch cleared before they are named again)
+            return member_fail(m, MRGFE_ERR_HIP);
+        }
+    }
+    m.batch_gen = node->target_gen;
     return MRGFE_OK;
 }
 
@@ -506,6 +614,19 @@ int mrgfe_node_clear(mrgfe_node* node)
         std::lock_guard<std::mutex> lk(node->api_mu);
         node->targets.clear();
         node->pairs.clear();
+        ++node->target_gen;
+        node->keep_targets = false;
+        return MRGFE_OK;
+    });
+}
+
+int mrgfe_node_clear_pairs(mrgfe_node* node)
+{
+    return abi_guard("mrgfe_node_clear_pairs", [&]() -> int {
+        if (!node) { set_error("mrgfe_node_clear_pairs: NULL node"); return MRGFE_ERR_INVALID; }
+        std::lock_guard<std::mutex> lk(node->api_mu);
+        node->pairs.clear();
+        node->keep_targets = true;  // (a member whose batch was filled for another target list, or failed, starts afresh all the same: Member::batch_gen)
         return MRGFE_OK;
     });
 }
@@ -543,6 +664,70 @@ int mrgfe_node_add_pair_keyed(mrgfe_node* node, int target_index, uint64_t cloud
 int mrgfe_node_add_pair(mrgfe_node* node, int target_index, const float* src_xyzi, size_t n, size_t stride_bytes, const float guess[16])
 {
     return mrgfe_node_add_pair_keyed(node, target_index, 0, src_xyzi, n, stride_bytes, guess);
+}
+
+// Keyframe `key` of a map store on any device: looked up, and the store's stream waited for (mrgfe_map_store_add uploads asynchronously), under the store's
+// lock ALONE, as store_lookup of batch.cpp does it — it is released before the node's lock is taken.
+static int node_store_lookup(const char* fn, mrgfe_map_store* s, uint64_t key, StoreRef* ref, size_t* n)
+{
+    MRGFE_LOCK(s->ctx);
+    MRGFE_TRY(s->ctx->bind());
+    auto it = s->clouds.find(key);
+    if (it == s->clouds.end()) { set_error("%s: keyframe %llu is not in the store", fn, static_cast<unsigned long long>(key)); return MRGFE_ERR_INVALID; }
+    MRGFE_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
+    ref->store = s;
+    ref->d = it->second.p;
+    ref->device = s->ctx->device;
+    *n = it->second.n;
+    return MRGFE_OK;
+}
+
+int mrgfe_node_add_target_from_store(mrgfe_node* node, mrgfe_map_store* store, uint64_t key)
+{
+    static const char* fn = "mrgfe_node_add_target_from_store";
+    return abi_guard(fn, [&]() -> int {
+        if (!node || !store) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        StoreRef ref;
+        size_t n = 0;
+        MRGFE_TRY(node_store_lookup(fn, store, key, &ref, &n));
+        std::lock_guard<std::mutex> lk(node->api_mu);
+        node->targets.push_back(TargetDecl{key, nullptr, n, 16, ref});
+        return static_cast<int>(node->targets.size()) - 1;
+    });
+}
+
+int mrgfe_node_add_pair_from_store(mrgfe_node* node, int target_index, mrgfe_map_store* store, uint64_t key, const float guess[16])
+{
+    static const char* fn = "mrgfe_node_add_pair_from_store";
+    return abi_guard(fn, [&]() -> int {
+        if (!node || !store || !guess) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        PairDecl p;
+        p.target = target_index; p.key = key; p.xyzi = nullptr; p.stride = 16;
+        std::memcpy(p.guess, guess, sizeof(p.guess));
+        MRGFE_TRY(node_store_lookup(fn, store, key, &p.from, &p.n));
+        std::lock_guard<std::mutex> lk(node->api_mu);
+        if (target_index < 0 || target_index >= static_cast<int>(node->targets.size())) { set_error("%s: target index %d out of range", fn, target_index); return MRGFE_ERR_INVALID; }
+        node->pairs.push_back(p);
+        return static_cast<int>(node->pairs.size()) - 1;
+    });
+}
+
+int mrgfe_node_store_stats(const mrgfe_node* node, int64_t out[4])
+{
+    if (!node || !out) { set_error("mrgfe_node_store_stats: NULL argument"); return MRGFE_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(const_cast<mrgfe_node*>(node)->api_mu);
+    std::fill(out, out + 4, int64_t(0));
+    for (auto& m : node->members)
+        for (int k = 0; k < 4; ++k) out[k] += m->store_stat[k];
+    return MRGFE_OK;
+}
+
+int mrgfe_dbg_node_set_store_copy(mrgfe_node* node, int mode)
+{
+    if (!node || (mode != 0 && mode != 1)) { set_error("mrgfe_dbg_node_set_store_copy: NULL node or a mode that is not 0 or 1"); return MRGFE_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(node->api_mu);
+    node->store_copy = mode;
+    return MRGFE_OK;
 }
 
 int mrgfe_node_align(mrgfe_node* node, double fitness_max_range, mrgfe_pair_result* results)
@@ -675,10 +860,15 @@ int mrgfe_node_forget(mrgfe_node* node, uint64_t cloud_key)
             {
                 MRGFE_LOCK(m->ctx);
                 (void)m->ctx->bind();
-                for (auto it = m->targets.begin(); it != m->targets.end();) {
-                    if (cloud_key == 0 || it->first == cloud_key) it = m->targets.erase(it);
-                    else ++it;
-                }
+                for (auto* map : {&m->targets, &m->replicas})
+                    for (auto it = map->begin(); it != map->end();) {
+                        if (cloud_key == 0 || it->first == cloud_key) it = map->erase(it);
+                        else ++it;
+                    }
+                for (auto* map : {&m->targets, &m->replicas})
+                    for (auto& kv : *map) kv.second->in_batch = false;  // (the batch is cleared below)
+                m->built.clear();
+                m->batch_gen = 0;
             }
             MRGFE_TRY(mrgfe_batch_clear(m->batch.get()));  // the member's last block still references its clouds; the node's own list is re-declared per call anyway
             MRGFE_TRY(mrgfe_batch_forget(m->batch.get(), cloud_key));
@@ -694,6 +884,7 @@ size_t mrgfe_node_store_bytes(const mrgfe_node* node)
     for (auto& m : node->members) {
         total += mrgfe_batch_store_bytes(m->batch.get());
         for (auto& kv : m->targets) total += kv.second->buf.cap;
+        for (auto& kv : m->replicas) total += kv.second->buf.cap;
     }
     return total;
 }

@@ -469,7 +469,8 @@ assert _KEYFRAME_DTYPE.itemsize == 432
 
 
 class HipLoopDetector:
-    """``mrgfe_loop_*``: ``LoopDetector.detect_batched`` as ONE call of the C ABI over a :class:`BatchMatcher` and a :class:`MapCloudStore` — the supersets,
+    """``mrgfe_loop_*``: ``LoopDetector.detect_batched`` as ONE call of the C ABI over a :class:`BatchMatcher` — or a :class:`NodeMatcher`, whose members
+    share out the pairs of both stages over the GPUs of the machine, same loops bit for bit — and a :class:`MapCloudStore` — the supersets,
     both batches (the second on the targets the first built), the replay of the gates and ``add_loop`` all happen inside ``libmrgfe.so``, and the
     LoopManager and the reference's counters live in the handle.  Every keyframe's cloud is named by its ``store_key()`` and must be in ``store``.
 
@@ -499,7 +500,12 @@ class HipLoopDetector:
         cp.use_planar_registration_guess = int(bool(self.p["use_planar_registration_guess"]))
         cp.enable_loop_closure_consistency_check = int(bool(self.p["enable_loop_closure_consistency_check"]))
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().mrgfe_loop_create(matcher._h if matcher is not None else None, store._h if store is not None else None, C.byref(cp), C.byref(self._h)))
+        from .registration import NodeMatcher
+
+        if isinstance(matcher, NodeMatcher):  # the stages run over the node's GPUs, fed by key from the store (mrgfe_loop_create_node)
+            _lib.check(_lib.lib().mrgfe_loop_create_node(matcher._h, store._h if store is not None else None, C.byref(cp), C.byref(self._h)))
+        else:
+            _lib.check(_lib.lib().mrgfe_loop_create(matcher._h if matcher is not None else None, store._h if store is not None else None, C.byref(cp), C.byref(self._h)))
         self._slam_ids: dict = {}
         self._cb = None
         self.last_batched: dict | None = None

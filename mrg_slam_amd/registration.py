@@ -650,6 +650,7 @@ class NodeMatcher:
         self._h = C.c_void_p()
         check(lib().mrgfe_node_create(len(devices), dev, C.byref(params), C.byref(self._h)))
         self._keep = []  # the add calls only REFERENCE the clouds: keep them alive until align() returns
+        self._keep_targets = []  # ... and the targets until clear(): after clear_pairs() a later align may still upload them
 
     def __del__(self):
         try:
@@ -668,13 +669,41 @@ class NodeMatcher:
     def clear(self):
         check(lib().mrgfe_node_clear(self._h))
         self._keep = []
+        self._keep_targets = []
+
+    def clear_pairs(self):
+        """``mrgfe_node_clear_pairs``: forget the pairs, keep the declared targets and their indices; every member keeps the targets its last align built
+        (a second stage against the same targets).  Records are those of a fresh node given the same targets and the new pairs."""
+        check(lib().mrgfe_node_clear_pairs(self._h))
+        self._keep = []
+
+    def add_target_from_store(self, store, key: int) -> int:
+        """The target is keyframe ``key`` of a :class:`MapCloudStore` on any device (``mrgfe_node_add_target_from_store``): a member on the store's
+        device reads it in place, a member elsewhere keeps a replica.  The store must outlive the node's use of it."""
+        return check(lib().mrgfe_node_add_target_from_store(self._h, store._h, int(key)))
+
+    def add_pair_from_store(self, target: int, store, key: int, guess=None) -> int:
+        """A candidate that is keyframe ``key`` of a :class:`MapCloudStore` (``mrgfe_node_add_pair_from_store``)."""
+        g = _colmajor(np.eye(4) if guess is None else guess)
+        return check(lib().mrgfe_node_add_pair_from_store(self._h, target, store._h, int(key), g.ctypes.data_as(_fp)))
+
+    def store_stats(self):
+        """``mrgfe_node_store_stats`` of the last align, the members' counts added up: (clouds read in place, clouds copied to a replica, bytes copied,
+        targets found already built)."""
+        v = (C.c_int64 * 4)()
+        check(lib().mrgfe_node_store_stats(self._h, v))
+        return tuple(int(x) for x in v)
+
+    def set_store_copy(self, mode: int) -> None:
+        """``mrgfe_dbg_node_set_store_copy``: 0 in place on the store's device and a replica elsewhere, 1 always a replica."""
+        check(lib().mrgfe_dbg_node_set_store_copy(self._h, int(mode)))
 
     def add_target(self, cloud, key: int = 0, n_points: int | None = None) -> int:
         """``cloud=None``: a keyed target that is resident on the member that will need it (same key and point count as before)."""
         if cloud is None:
             return check(lib().mrgfe_node_add_target_keyed(self._h, key, None, int(n_points or 0), 16))
         c = _cloud(cloud)
-        self._keep.append(c)
+        self._keep_targets.append(c)
         return check(lib().mrgfe_node_add_target_keyed(self._h, key, c.ctypes.data_as(_fp), len(c), 16))
 
     def add_pair(self, target: int, source, guess=None, key: int = 0, n_points: int | None = None) -> int:
