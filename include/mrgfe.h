@@ -483,6 +483,67 @@ typedef struct mrgfe_graph_edge {
 size_t mrgfe_graph_edge_size(void); /* sizeof(mrgfe_graph_edge) as the library was compiled */
 int    mrgfe_map_store_edges(mrgfe_map_store* store, const mrgfe_inf_params* params, int n_edges, const mrgfe_graph_edge* edges, double* inf, double* fitness);
 
+/* ---- the ground fill of the first keyframe (GraphDatabase::flush_keyframe_queue, src/mrg_slam/graph_database.cpp:114-129; src/pcl/fill_ground_plane.cpp) ---- */
+/* With enable_fill_first_cloud the reference replaces the first keyframe's cloud by cloud_filled: the cloud plus a disc of synthetic ground points
+ * (intensity 0) under the robot, appended behind the cloud's own points, rings outermost and angles inner (fill_cloud, fill_ground_plane.cpp:49-65).
+ * The plane of the disc:
+ *   simple == 0  fill_ground_plane_ransac (:21-35): RandomSampleConsensus<SampleConsensusModelPlane> over the WHOLE cloud, distance threshold 0.01,
+ *                computeModel() only — the coefficients of the winning sample, nothing refined; the RANSAC of mrgfe_floor_detect with that threshold.
+ *                normal = (double)c[0..2], offset = (double)c[3].  `estimate` is ignored.
+ *   simple != 0  fill_ground_plane_simple (:37-47): normal = the third column of the rotation of keyframe->node->estimate(), offset 0.  `estimate`:
+ *                that pose, column-major 4x4 double; NULL is MRGFE_ERR_INVALID.
+ * The disc, all in double: angle_inc = map_resolution / radius; rings `for (r = map_resolution; r <= radius; r += map_resolution)` and angles
+ * `for (angle = 0; angle < 2 * M_PI; angle += angle_inc)`, both ACCUMULATED as written (resolution 0.1 with radius 0.3 gives 2 rings: 0.1 + 0.1 + 0.1 >
+ * 0.3); per ring sample = p - (normal . p + offset) * normal with p = (r, 0, 0) (Eigen::Hyperplane::projection: the normal is not normalised); per point
+ * AngleAxis<double>(angle, normal).toRotationMatrix() * sample — the axis as it is given, the rotation about the axis THROUGH THE ORIGIN, as the reference
+ * has it — cast to float.  The host walks the two loops and takes sin and cos of every angle from the C library, as the reference's host does; the device
+ * does the rest in IEEE double operations in a fixed order (three-term sums left to right), so no device sin / cos enters the result.
+ * config/mrg_slam_ouster.yaml:158-160 ships the fill ON (radius 7.5, RANSAC): at the declared map_cloud_resolution 0.05 that is 150 rings x 943 angles =
+ * 141450 points. */
+typedef struct mrgfe_ground_fill_params {
+    double  radius;          /* 5.0   "fill_first_cloud_radius"  apps/mrg_slam_component.cpp:271, config/mrg_slam.yaml:159  */
+    double  map_resolution;  /* 0.05  "map_cloud_resolution"     apps/mrg_slam_component.cpp:245 (the YAMLs set 0.1, :235) */
+    int32_t simple;          /* 0     "fill_first_cloud_simple"  apps/mrg_slam_component.cpp:272, config/mrg_slam.yaml:160  */
+    int32_t pad;
+} mrgfe_ground_fill_params;  /* 24 bytes */
+typedef struct mrgfe_ground_fill_result {
+    int32_t  has_model;          /* a plane was found: always 1 with simple != 0; 0 when RANSAC found none — then nothing was filled                  */
+    int32_t  ransac_iterations;  /* RandomSampleConsensus::iterations_ at the end of computeModel (0 with simple != 0)                              */
+    float    coeffs[4];          /* RANSAC: the model coefficients; simple: the normal rounded to float and 0 (the fill itself uses the doubles)     */
+    uint32_t n_before;           /* points of the source cloud                                                                                      */
+    uint32_t n_rings, n_angles;  /* the two loop counts                                                                                             */
+    uint32_t n_added;            /* n_rings * n_angles, or 0 without a model                                                                        */
+} mrgfe_ground_fill_result;      /* 40 bytes */
+void   mrgfe_ground_fill_default_params(mrgfe_ground_fill_params* out); /* 5.0, 0.05, 0: apps/mrg_slam_component.cpp:245,271-272 */
+size_t mrgfe_ground_fill_params_size(void); /* sizeof(mrgfe_ground_fill_params) as the library was compiled */
+size_t mrgfe_ground_fill_result_size(void); /* sizeof(mrgfe_ground_fill_result) as the library was compiled */
+/* The two loop counts alone, on the host, no context.  MRGFE_ERR_INVALID: a NULL argument; a radius or map_resolution that is not finite and > 0 (the
+ * reference's loops would not terminate); more than 2^31 - 1 points.  radius < map_resolution is a valid fill of 0 rings. */
+int    mrgfe_ground_fill_counts(const mrgfe_ground_fill_params* params, uint32_t* n_rings, uint32_t* n_angles);
+/* The fill of a host cloud (`stride_bytes` as for mrgfe_map_store_add): out_xyzi (required, room for `capacity` packed 16-byte points) receives the n
+ * points of the cloud, packed, and the disc behind them.
+ * Outcomes, for this call and the next:
+ *   MRGFE_OK with has_model = 0, n_added = 0: RANSAC found no model (fewer than 3 points, no non-collinear sample).  Nothing is written to out_xyzi and
+ *     the store gets NO dst_key entry.  (The reference would index an empty coefficient vector here: ransac.getModelCoefficients(c) leaves c empty and
+ *     :31 reads c[0..3].)
+ *   MRGFE_OK with n_rings = 0 (radius < map_resolution): a valid fill of 0 points; the output is a copy of the cloud.
+ *   MRGFE_ERR_INVALID: a NULL argument (`estimate` may be NULL with simple == 0; the store call's out_xyzi may be NULL); radius or map_resolution not
+ *     finite and > 0; n + n_rings * n_angles > 2^31 - 1; key 0; a src_key the store lacks; capacity < n + n_rings * n_angles (the message names the count;
+ *     checked before any work, so also where RANSAC would have found no model).
+ *   MRGFE_ERR_STATE: dst_key is already stored, or equals src_key.
+ * One host wait with simple != 0; with RANSAC those of its waves (one per wave of hypotheses) plus one. */
+int    mrgfe_fill_ground_plane(mrgfe_ctx* ctx, const mrgfe_ground_fill_params* params, const double estimate[16], const float* xyzi, size_t n, size_t stride_bytes,
+                               float* out_xyzi, size_t capacity, mrgfe_ground_fill_result* result);
+/* The same for keyframe src_key of a map store, which is where mrgfe_keyframe_callback left the first keyframe's cloud.  The filled cloud is stored as a
+ * NEW keyframe dst_key — the integrator names the first keyframe by dst_key from then on (`keyframe->cloud = cloud_filled`, :125) — and src_key stays as
+ * it was: the store stays append-only, no device pointer handed out earlier (batch targets, node replicas, cached edge grids) changes or dangles, and
+ * nothing needs invalidating.  The source points reach the new cloud by a device-to-device copy on the store's stream, the disc by one launch behind
+ * them.  out_xyzi (may be NULL; else room for `capacity` points) receives the filled cloud.  mrgfe_map_store_bytes grows by exactly
+ * 16 * (n_before + n_added).  The call returns after the store's stream has been waited for: the new cloud is complete and immutable.  After any failure,
+ * and without a model, the store has no new entry and its byte count is unchanged (the arena block is handed back). */
+int    mrgfe_map_store_fill_ground(mrgfe_map_store* store, uint64_t src_key, uint64_t dst_key, const mrgfe_ground_fill_params* params, const double estimate[16],
+                                   float* out_xyzi, size_t capacity, mrgfe_ground_fill_result* result);
+
 /* replaces PrefilteringComponent::deskewing (apps/prefiltering_component.cpp:231-292): point i is rotated by the inverse of
  * Quaternionf(1, dt/2 * -w) with dt = scan_period * i / n and w the IMU angular velocity */
 int mrgfe_deskew(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride_bytes, const float ang_v_xyz[3], double scan_period, float* out_xyzi);

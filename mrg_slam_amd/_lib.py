@@ -78,6 +78,19 @@ class GraphEdge(C.Structure):
     _fields_ = [("key1", C.c_uint64), ("key2", C.c_uint64), ("relpose", C.c_double * 16)]
 
 
+class GroundFillParams(C.Structure):
+    """struct mrgfe_ground_fill_params: fill_first_cloud_radius, map_cloud_resolution, fill_first_cloud_simple (apps/mrg_slam_component.cpp:245,271-272)."""
+
+    _fields_ = [("radius", C.c_double), ("map_resolution", C.c_double), ("simple", C.c_int32), ("pad", C.c_int32)]
+
+
+class GroundFillResult(C.Structure):
+    """struct mrgfe_ground_fill_result: the plane the disc was laid on and the counts of the fill."""
+
+    _fields_ = [("has_model", C.c_int32), ("ransac_iterations", C.c_int32), ("coeffs", C.c_float * 4), ("n_before", C.c_uint32), ("n_rings", C.c_uint32),
+                ("n_angles", C.c_uint32), ("n_added", C.c_uint32)]
+
+
 class FloorParams(C.Structure):
     """struct mrgfe_floor_params (the floor_detection_component ROS parameters, apps/floor_detection_component.cpp:55-62, config/mrg_slam.yaml:113-122)."""
 
@@ -252,6 +265,12 @@ SIGNATURES = {
     "mrgfe_map_store_add_keyframes": (C.c_int, [_vp, C.c_int, C.POINTER(KeyframeMsg), C.POINTER(C.c_uint8)]),
     "mrgfe_graph_edge_size": (C.c_size_t, []),
     "mrgfe_map_store_edges": (C.c_int, [_vp, C.POINTER(InfParams), C.c_int, C.POINTER(GraphEdge), _dp, _dp]),
+    "mrgfe_ground_fill_default_params": (None, [C.POINTER(GroundFillParams)]),
+    "mrgfe_ground_fill_params_size": (C.c_size_t, []),
+    "mrgfe_ground_fill_result_size": (C.c_size_t, []),
+    "mrgfe_ground_fill_counts": (C.c_int, [C.POINTER(GroundFillParams), _u32p, _u32p]),
+    "mrgfe_fill_ground_plane": (C.c_int, [_vp, C.POINTER(GroundFillParams), _dp, _fp, C.c_size_t, C.c_size_t, _fp, C.c_size_t, C.POINTER(GroundFillResult)]),
+    "mrgfe_map_store_fill_ground": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.POINTER(GroundFillParams), _dp, _fp, C.c_size_t, C.POINTER(GroundFillResult)]),
     "mrgfe_prefilter_default_params": (None, [C.POINTER(PrefilterParams)]),
     "mrgfe_prefilter": (C.c_int, [_vp, C.POINTER(PrefilterParams), _fp, C.c_size_t, C.c_size_t, _fp, C.POINTER(C.c_size_t)]),
     "mrgfe_prefilter_device": (C.c_int, [_vp, C.POINTER(PrefilterParams), _fp, C.c_size_t, C.c_size_t, _vp, C.POINTER(C.c_size_t)]),
@@ -474,7 +493,7 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"libmrgfe.so was built with a mrgfe_keyframe_params of {L.mrgfe_keyframe_params_size()} bytes, the binding mirrors {C.sizeof(KeyframeParams)}")
         for fn, mirror in (("mrgfe_pointcloud2_field_size", PointField), ("mrgfe_keyframe_msg_size", KeyframeMsg), ("mrgfe_graph_edge_size", GraphEdge), ("mrgfe_odom_params_size", OdomParams),
                            ("mrgfe_odom_result_size", OdomResult), ("mrgfe_loop_params_size", LoopParams), ("mrgfe_loop_keyframe_size", LoopKeyframe),
-                           ("mrgfe_loop_result_size", LoopResult)):
+                           ("mrgfe_loop_result_size", LoopResult), ("mrgfe_ground_fill_params_size", GroundFillParams), ("mrgfe_ground_fill_result_size", GroundFillResult)):
             if hasattr(L, fn) and getattr(L, fn)() != C.sizeof(mirror):
                 raise RuntimeError(f"libmrgfe.so was built with a {fn[:-5]} of {getattr(L, fn)()} bytes, the binding mirrors {C.sizeof(mirror)}")
         _lib = L

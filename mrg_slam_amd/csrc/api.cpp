@@ -18,6 +18,7 @@
 #include "glibc_exp.h"
 #include "filters.h"
 #include "floor.h"
+#include "ground_fill.h"
 #include "mapcloud.h"
 #include "gicp_engine.h"
 #include "ingest.h"
@@ -1581,6 +1582,129 @@ int mrgfe_floor_detect_device(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const
         MRGFE_LOCK(ctx);
         MRGFE_TRY(ctx->bind());
         return floor_detect(ctx, p, static_cast<const float4*>(d_xyzi), n, res, out_filtered, out_inliers);
+    });
+}
+
+// ---- the ground fill of the first keyframe (ground_fill.hip; GraphDatabase::flush_keyframe_queue :114-129) ---------------------------------------
+static_assert(sizeof(mrgfe_ground_fill_params) == 24, "mrgfe_ground_fill_params: the layout the bindings mirror");
+static_assert(sizeof(mrgfe_ground_fill_result) == 40, "mrgfe_ground_fill_result: the layout the bindings mirror");
+size_t mrgfe_ground_fill_params_size(void) { return sizeof(mrgfe_ground_fill_params); }
+size_t mrgfe_ground_fill_result_size(void) { return sizeof(mrgfe_ground_fill_result); }
+void mrgfe_ground_fill_default_params(mrgfe_ground_fill_params* p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->radius = 5.0;            // apps/mrg_slam_component.cpp:271
+    p->map_resolution = 0.05;   // :245
+    p->simple = 0;              // :272
+}
+int mrgfe_ground_fill_counts(const mrgfe_ground_fill_params* p, uint32_t* n_rings, uint32_t* n_angles)
+{
+    static const char* fn = "mrgfe_ground_fill_counts";
+    if (!p || !n_rings || !n_angles) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+    MRGFE_TRY(ground_fill_check(p, fn));
+    return ground_fill_counts(p, 0, n_rings, n_angles, fn);
+}
+// What both entry points check before they touch a context: the parameters, the estimate of the simple variant, the counts behind `n` points.
+static int ground_fill_begin(const char* fn, const mrgfe_ground_fill_params* p, const double* estimate, mrgfe_ground_fill_result* res)
+{
+    if (!p || !res) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+    std::memset(res, 0, sizeof(*res));
+    MRGFE_TRY(ground_fill_check(p, fn));
+    if (p->simple && !estimate) { set_error("%s: the simple variant needs the keyframe's estimate", fn); return MRGFE_ERR_INVALID; }
+    return MRGFE_OK;
+}
+// The plane (fill_ground_plane.cpp:21-47) of the n points at d_cloud and, when there is one, the disc queued behind them (room for n + rings * angles
+// points).  res->n_before / n_rings / n_angles are set by the caller; has_model, coeffs, ransac_iterations and n_added here.
+static int ground_fill_plane_and_disc(mrgfe_ctx* ctx, const mrgfe_ground_fill_params* p, const double* estimate, float4* d_cloud, uint32_t n, mrgfe_ground_fill_result* res)
+{
+    double normal[3], offset = 0.0;
+    if (p->simple) {  // base_link_pose.rotation() * (0, 0, 1): the third column; Hyperplane(normal, 0)
+        for (int j = 0; j < 3; ++j) normal[j] = estimate[8 + j];
+        res->has_model = 1;
+        for (int j = 0; j < 3; ++j) res->coeffs[j] = static_cast<float>(normal[j]);
+    } else {
+        FloorRansacOut r;
+        MRGFE_TRY(floor_ransac_device(ctx, d_cloud, n, 0.01, nullptr, &r));  // setDistanceThreshold(.01), computeModel() (:26-27)
+        res->ransac_iterations = r.iterations;
+        res->has_model = r.has_model;
+        if (!r.has_model) return MRGFE_OK;
+        for (int j = 0; j < 4; ++j) res->coeffs[j] = r.coeffs[j];
+        for (int j = 0; j < 3; ++j) normal[j] = static_cast<double>(r.coeffs[j]);  // :31
+        offset = static_cast<double>(r.coeffs[3]);                                 // :32
+    }
+    MRGFE_TRY(ground_fill_device(ctx, p, normal, offset, res->n_rings, res->n_angles, d_cloud + n));
+    res->n_added = res->n_rings * res->n_angles;
+    return MRGFE_OK;
+}
+int mrgfe_fill_ground_plane(mrgfe_ctx* ctx, const mrgfe_ground_fill_params* p, const double estimate[16], const float* xyzi, size_t n, size_t stride, float* out,
+                            size_t capacity, mrgfe_ground_fill_result* res)
+{
+    static const char* fn = "mrgfe_fill_ground_plane";
+    return abi_guard(fn, [&]() -> int {
+        MRGFE_TRY(ground_fill_begin(fn, p, estimate, res));
+        MRGFE_TRY(check_count(n, fn));
+        if (!ctx || !out || (n && !xyzi)) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        MRGFE_TRY(ground_fill_counts(p, n, &res->n_rings, &res->n_angles, fn));
+        res->n_before = static_cast<uint32_t>(n);
+        const size_t total = n + size_t(res->n_rings) * res->n_angles;
+        if (capacity < total) { set_error("%s: the filled cloud has %zu points, out_xyzi has room for %zu", fn, total, capacity); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(ctx);
+        MRGFE_TRY(ctx->bind());
+        DevBuf& dc = ctx->gf_cloud;
+        MRGFE_TRY(dc.ensure(std::max<size_t>(total, 1) * 16));
+        if (n) MRGFE_TRY(upload_cloud(ctx, xyzi, n, stride, dc.p));
+        MRGFE_TRY(ground_fill_plane_and_disc(ctx, p, estimate, dc.as<float4>(), res->n_before, res));
+        if (!res->has_model) return MRGFE_OK;  // (RANSAC's last wave was waited for: the stream is idle)
+        const size_t filled = n + res->n_added;
+        if (filled) MRGFE_HIP_CHECK(hipMemcpyAsync(out, dc.p, filled * 16, hipMemcpyDeviceToHost, ctx->stream));
+        MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the one wait of the fill
+        return MRGFE_OK;
+    });
+}
+int mrgfe_map_store_fill_ground(mrgfe_map_store* s, uint64_t src_key, uint64_t dst_key, const mrgfe_ground_fill_params* p, const double estimate[16], float* out,
+                                size_t capacity, mrgfe_ground_fill_result* res)
+{
+    static const char* fn = "mrgfe_map_store_fill_ground";
+    return abi_guard(fn, [&]() -> int {
+        MRGFE_TRY(ground_fill_begin(fn, p, estimate, res));
+        if (!s) { set_error("%s: NULL store", fn); return MRGFE_ERR_INVALID; }
+        if (src_key == 0 || dst_key == 0) { set_error("%s: key 0", fn); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(s->ctx);
+        MRGFE_TRY(s->ctx->bind());
+        mrgfe_ctx* ctx = s->ctx;
+        auto it = s->clouds.find(src_key);
+        if (it == s->clouds.end()) { set_error("%s: keyframe %llu is not in the store", fn, static_cast<unsigned long long>(src_key)); return MRGFE_ERR_INVALID; }
+        const mrgfe_map_store::Entry src = it->second;
+        MRGFE_TRY(ground_fill_counts(p, src.n, &res->n_rings, &res->n_angles, fn));
+        res->n_before = src.n;
+        const size_t total = size_t(src.n) + size_t(res->n_rings) * res->n_angles;
+        if (out && capacity < total) { set_error("%s: the filled cloud has %zu points, out_xyzi has room for %zu", fn, total, capacity); return MRGFE_ERR_INVALID; }
+        if (dst_key == src_key || s->clouds.count(dst_key)) {
+            set_error("%s: keyframe %llu is already stored (the store is append-only: the filled cloud needs a key of its own)", fn, static_cast<unsigned long long>(dst_key));
+            return MRGFE_ERR_STATE;
+        }
+        s->clouds.reserve(s->clouds.size() + 1);
+        void* blk = nullptr;
+        if (total) MRGFE_TRY(s->arena.alloc(total * 16, &blk));
+        auto run = [&]() -> int {
+            // the source points: device to device on the store's stream, behind whatever upload of src_key is still on its way
+            if (src.n) MRGFE_HIP_CHECK(hipMemcpyAsync(blk, src.p, size_t(src.n) * 16, hipMemcpyDeviceToDevice, ctx->stream));
+            MRGFE_TRY(ground_fill_plane_and_disc(ctx, p, estimate, static_cast<float4*>(blk), src.n, res));  // (RANSAC reads the copy: the same bytes)
+            if (!res->has_model) return MRGFE_OK;
+            if (out && total) MRGFE_HIP_CHECK(hipMemcpyAsync(out, blk, total * 16, hipMemcpyDeviceToHost, ctx->stream));
+            MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the one wait of the fill: the new cloud is complete
+            return MRGFE_OK;
+        };
+        const int rc = run();
+        if (rc != MRGFE_OK || !res->has_model) {
+            (void)hipStreamSynchronize(ctx->stream);  // nothing is in flight when the block goes back
+            if (total) s->arena.shrink_last(blk, total * 16, 0);
+            return rc;
+        }
+        s->clouds[dst_key] = {static_cast<const float4*>(blk), static_cast<uint32_t>(total)};
+        s->bytes += total * 16;
+        return MRGFE_OK;
     });
 }
 int mrgfe_dbg_floor_ransac(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, double threshold, int* has_model, float coeffs[4], int32_t* inliers,

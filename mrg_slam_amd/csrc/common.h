@@ -268,6 +268,7 @@ struct mrgfe_ctx {
     mrgfe::PinBuf fl_pin;                       // ... and the hypothesis records and counts the host reads after each RANSAC wave
     mrgfe::Event fl_ev[5];                      // stage boundaries of the last floor detection (mrgfe_dbg_floor_stats)
     double       fl_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    mrgfe::DevBuf gf_tab, gf_cloud;             // ground fill (ground_fill.hip): the ring and angle tables; the filled cloud of the host-cloud entry point
     std::unique_ptr<mrgfe::NnGrid> tmp_grid;    // reusable exact-NN grid of the stateless filter / fitness calls (nn_grid.hip)
     std::recursive_mutex mu;                    // serialises API calls that share this context's stream / workspaces
     int          bind();                        // hipSetDevice(device)

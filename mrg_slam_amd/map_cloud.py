@@ -4,7 +4,9 @@ libmrgfe.so:
 * :class:`MapCloudGenerator` — mrg_slam::MapCloudGenerator (/root/reference/src/mrg_slam/map_cloud_generator.cpp:14-86,
   called from apps/mrg_slam_component.cpp:727,781,1097) with its pcl::ApproximateMeanVoxelGrid pass;
 * :func:`remove_points_near` — the other-robot point removal of apps/mrg_slam_component.cpp:396-429;
-* :func:`deskew` — PrefilteringComponent::deskewing (apps/prefiltering_component.cpp:231-292).
+* :func:`deskew` — PrefilteringComponent::deskewing (apps/prefiltering_component.cpp:231-292);
+* :func:`fill_ground_plane` and :meth:`MapCloudStore.fill_ground` — the ground fill of the first keyframe
+  (src/mrg_slam/graph_database.cpp:114-129, src/pcl/fill_ground_plane.cpp).
 """
 from __future__ import annotations
 
@@ -13,7 +15,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import Context, GraphEdge, KeyframeMsg, KeyframeParams, MrgfeError, check, default_context, lib
+from ._lib import Context, GraphEdge, GroundFillParams, GroundFillResult, KeyframeMsg, KeyframeParams, MrgfeError, check, default_context, lib
 from .filters import _cloud
 from .io import pointcloud2_from_xyzi
 
@@ -40,6 +42,43 @@ def keyframe_params(msg: dict, ctx: Context | None = None) -> KeyframeParams:
     p, _ = layout_from_fields(msg["fields"], msg["width"], msg.get("height", 1), msg["point_step"], row_step, msg.get("is_bigendian", False), ctx=ctx)
     p.row_step = row_step  # (0 stays 0: the call fills it in)
     return p
+
+
+def _ground_fill_args(radius: float, map_resolution: float, simple: bool, estimate):
+    """The parameter record, the column-major estimate (or None) and the two loop counts (``mrgfe_ground_fill_counts``: refuses what the library refuses)."""
+    p = GroundFillParams(float(radius), float(map_resolution), int(bool(simple)), 0)
+    est = None if estimate is None else np.ascontiguousarray(np.asarray(estimate, dtype=np.float64).reshape(4, 4).T)
+    rings, angles = ground_fill_counts(radius, map_resolution)
+    return p, est, rings * angles
+
+
+def _ground_fill_info(r: GroundFillResult) -> dict:
+    return {"has_model": bool(r.has_model), "ransac_iterations": int(r.ransac_iterations), "coeffs": np.array(r.coeffs[:], dtype=np.float32), "n_before": int(r.n_before),
+            "n_rings": int(r.n_rings), "n_angles": int(r.n_angles), "n_added": int(r.n_added)}
+
+
+def ground_fill_counts(radius: float, map_resolution: float):
+    """``mrgfe_ground_fill_counts``: (rings, angles) of the disc, the accumulated loops of fill_cloud (src/pcl/fill_ground_plane.cpp:53-56); host only."""
+    p = GroundFillParams(float(radius), float(map_resolution), 0, 0)
+    rings, angles = C.c_uint32(0), C.c_uint32(0)
+    check(lib().mrgfe_ground_fill_counts(C.byref(p), C.byref(rings), C.byref(angles)))
+    return rings.value, angles.value
+
+
+def fill_ground_plane(cloud, radius: float = 5.0, map_resolution: float = 0.05, simple: bool = False, estimate=None, ctx: Context | None = None, stride_bytes: int = 16):
+    """``mrgfe_fill_ground_plane``: mrg_slam_pcl::fill_ground_plane_ransac / _simple (src/pcl/fill_ground_plane.cpp:21-47) on a host cloud.  ``estimate``:
+    the 4 x 4 pose of the simple variant.  ``stride_bytes``: 16 for an [n, 4] cloud, or a ``_lib.layout`` descriptor for an array whose rows are such records
+    (``io.pcl_xyzi_records``).  Returns ``(filled, info)``; ``filled`` is None when RANSAC found no model (``info["has_model"]`` False)."""
+    ctx = ctx or default_context()
+    c = _cloud(cloud) if stride_bytes == 16 else np.ascontiguousarray(cloud)  # (records of any dtype: their bytes are what is read)
+    p, est, added = _ground_fill_args(radius, map_resolution, simple, estimate)
+    cap = len(c) + added
+    out = np.empty((max(cap, 1), 4), dtype=np.float32)
+    r = GroundFillResult()
+    check(lib().mrgfe_fill_ground_plane(ctx._h, C.byref(p), est.ctypes.data_as(C.POINTER(C.c_double)) if est is not None else None, C.cast(c.ctypes.data, _fp), len(c),
+                                        int(stride_bytes), out.ctypes.data_as(_fp), cap, C.byref(r)))
+    info = _ground_fill_info(r)
+    return (out[: r.n_before + r.n_added] if r.has_model else None), info
 
 
 class MapCloudStore:
@@ -90,6 +129,21 @@ class MapCloudStore:
         if want_removed and removed is None:
             removed = np.empty((0, 4), dtype=np.float32)  # (no other robot: nothing was removed)
         return (kept[: nk.value] if kept is not None else None), (removed[: nr.value] if removed is not None else None)
+
+    def fill_ground(self, src_key: int, dst_key: int, radius: float = 5.0, map_resolution: float = 0.05, simple: bool = False, estimate=None, want_cloud: bool = True):
+        """``mrgfe_map_store_fill_ground``: the ground fill of the first keyframe (src/mrg_slam/graph_database.cpp:114-129) for the stored keyframe
+        ``src_key``.  The filled cloud becomes the NEW keyframe ``dst_key`` — name the first keyframe by it from then on —; ``src_key`` stays as it was.
+        ``estimate``: the 4 x 4 ``keyframe->node->estimate()`` of the simple variant.  Returns ``(filled, info)``: ``filled`` is the filled cloud
+        (``keyframe->cloud = cloud_filled``) or None when it was not wanted or RANSAC found no model — then ``info["has_model"]`` is False and there is
+        no ``dst_key``."""
+        p, est, added = _ground_fill_args(radius, map_resolution, simple, estimate)
+        cap = (self.has(int(src_key)) or 0) + added
+        out = np.empty((max(cap, 1), 4), dtype=np.float32) if want_cloud else None
+        r = GroundFillResult()
+        check(lib().mrgfe_map_store_fill_ground(self._h, int(src_key), int(dst_key), C.byref(p), est.ctypes.data_as(C.POINTER(C.c_double)) if est is not None else None,
+                                                out.ctypes.data_as(_fp) if out is not None else None, cap, C.byref(r)))
+        info = _ground_fill_info(r)
+        return (out[: r.n_before + r.n_added] if out is not None and r.has_model else None), info
 
     def add_keyframes(self, items) -> np.ndarray:
         """``mrgfe_map_store_add_keyframes``: the point work of GraphDatabase::add_static_keyframes / flush_graph_queue / load_graph
