@@ -445,6 +445,19 @@ size_t mrgfe_keyframe_params_size(void); /* sizeof(mrgfe_keyframe_params) as the
 int    mrgfe_keyframe_callback(mrgfe_map_store* store, uint64_t key, const mrgfe_keyframe_params* layout, const void* data, size_t data_bytes,
                                const float* centres_xyz, int n_centres, float radius_sqr, float* kept_xyzi, size_t* n_kept, float* removed_xyzi,
                                size_t* n_removed);
+/* The same callback for a filtered scan that is already in HBM — all four components in one component_container_mt (launch/mrg_slam.launch.py:214-319):
+ * the cloud that becomes a keyframe (apps/mrg_slam_component.cpp:372 would unpack it from the message) is the packed float4 cloud
+ * mrgfe_scan_callback_device / mrgfe_prefilter_device left in the caller's buffer.  d_xyzi: n packed 16-byte points in the memory of the store's
+ * device, COMPLETE when the call is made — the `_device` producers of this header return only after their wait, so a buffer one of them filled is;
+ * work the caller queued on a stream of its own must have been waited for.  A packed device cloud is a PointCloud2 payload with point_step 16 that
+ * already sits where the head kernel reads it: this is mrgfe_keyframe_callback without its upload — the same two kernels, the same arena block, the
+ * same waits (with 0 centres one gather into the store and one wait) — and stored cloud, kept, removed, both counts, mrgfe_map_store_bytes and the
+ * refusals equal mrgfe_keyframe_callback on the bytes of the same cloud in the packed layout.  The caller's buffer is only read and is free on return.
+ * MRGFE_ERR_INVALID: key 0, more than 64 centres, n > 2^31 - 1, a NULL d_xyzi with n > 0, and a d_xyzi that hipPointerGetAttributes does not show to
+ * be memory of the store's device (host memory, another GPU's: it is not read); MRGFE_ERR_STATE: `key` is already stored.  After any failure the store
+ * has no new entry and its byte count is unchanged. */
+int    mrgfe_keyframe_callback_device(mrgfe_map_store* store, uint64_t key, const void* d_xyzi, size_t n, const float* centres_xyz, int n_centres,
+                                      float radius_sqr, float* kept_xyzi, size_t* n_kept, float* removed_xyzi, size_t* n_removed);
 
 /* ---- the graph database's keyframe and edge loops in one call each (src/mrg_slam/graph_database.cpp) ---- */
 /* Many keyframe messages at once: the point work of GraphDatabase::add_static_keyframes (:181-182), flush_graph_queue (:294-295, another robot's whole
@@ -993,6 +1006,18 @@ int  mrgfe_floor_detect(mrgfe_ctx* ctx, const mrgfe_floor_params* params, const 
  * the component subscribes to — without a round trip through the host */
 int  mrgfe_floor_detect_device(mrgfe_ctx* ctx, const mrgfe_floor_params* params, const void* d_xyzi, size_t n, mrgfe_floor_result* result,
                                float* out_filtered, float* out_inliers);
+/* FloorDetectionComponent::cloud_callback (apps/floor_detection_component.cpp:69-93) in one call on the bytes of the sensor_msgs/PointCloud2 it
+ * receives (prefiltering/filtered_points, in a floor-detection process of its own): pcl::fromROSMsg (:72), the empty-cloud return (:74-77) and
+ * detect() (:80).  `layout`: what mrgfe_pointcloud2_layout fills, checked under this entry point's name by the rules of mrgfe_keyframe_callback (a
+ * row_step that does not hold a row, offsets or steps that are not multiples of 4 unless the context has mrgfe_ctx_set_byte_layouts on:
+ * MRGFE_ERR_INVALID); `data`: data_bytes >= (height - 1) * row_step + width * point_step bytes (less, or NULL with points: MRGFE_ERR_INVALID).
+ * width * height == 0: MRGFE_OK with reason MRGFE_FLOOR_EMPTY_INPUT, nothing is sent or launched.  The payload goes up ONCE as it is and the first
+ * kernel reads the records, applies the tilt and flags the height band: no packed copy of the cloud is written and read back in front of it.
+ * out_filtered / out_inliers: as for mrgfe_floor_detect, room for width * height packed points each, either may be NULL.  result and both clouds equal,
+ * bit for bit, mrgfe_ingest_pointcloud2 followed by mrgfe_floor_detect_device for the same message and parameters, with the same number of host
+ * waits; a failing call leaves nothing behind. */
+int  mrgfe_floor_callback(mrgfe_ctx* ctx, const mrgfe_floor_params* params, const mrgfe_keyframe_params* layout, const void* data, size_t data_bytes,
+                          mrgfe_floor_result* result, float* out_filtered, float* out_inliers);
 
 /* Diagnostic entry points (alternative paths of the same arithmetic, primitives, the optimiser stepped by hand) are declared in mrgfe_debug.h; the two
  * fault injectors there exist only in a library built with -DMRGFE_TESTING (mrg_slam_amd/libmrgfe_testing.so): the shipped libmrgfe.so has neither. */

@@ -261,6 +261,7 @@ SIGNATURES = {
     "mrgfe_pointcloud2_field_size": (C.c_size_t, []),
     "mrgfe_pointcloud2_layout": (C.c_int, [C.POINTER(PointField), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(KeyframeParams), C.POINTER(C.c_int)]),
     "mrgfe_keyframe_callback": (C.c_int, [_vp, C.c_uint64, C.POINTER(KeyframeParams), _vp, C.c_size_t, _fp, C.c_int, C.c_float, _fp, _szp, _fp, _szp]),
+    "mrgfe_keyframe_callback_device": (C.c_int, [_vp, C.c_uint64, _vp, C.c_size_t, _fp, C.c_int, C.c_float, _fp, _szp, _fp, _szp]),
     "mrgfe_keyframe_msg_size": (C.c_size_t, []),
     "mrgfe_map_store_add_keyframes": (C.c_int, [_vp, C.c_int, C.POINTER(KeyframeMsg), C.POINTER(C.c_uint8)]),
     "mrgfe_graph_edge_size": (C.c_size_t, []),
@@ -281,6 +282,7 @@ SIGNATURES = {
     "mrgfe_floor_default_params": (None, [C.POINTER(FloorParams)]),
     "mrgfe_floor_detect": (C.c_int, [_vp, C.POINTER(FloorParams), _fp, C.c_size_t, C.c_size_t, C.POINTER(FloorResult), _fp, _fp]),
     "mrgfe_floor_detect_device": (C.c_int, [_vp, C.POINTER(FloorParams), _vp, C.c_size_t, C.POINTER(FloorResult), _fp, _fp]),
+    "mrgfe_floor_callback": (C.c_int, [_vp, C.POINTER(FloorParams), C.POINTER(KeyframeParams), _vp, C.c_size_t, C.POINTER(FloorResult), _fp, _fp]),
     "mrgfe_knn": (C.c_int, [_vp, _fp, C.c_size_t, _fp, C.c_size_t, C.c_size_t, C.c_int, _ip, _fp]),
     "mrgfe_pclgicp_evaluate": (C.c_int, [_vp, _fp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     "mrgfe_gicp_linearize": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _ip]),

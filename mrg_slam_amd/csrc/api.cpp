@@ -975,6 +975,57 @@ void mrgfe_keyframe_default_params(mrgfe_keyframe_params* p)
     p->point_step = 16;  // the replay scripts' layout: python_scripts/kitti_singlerobot_processor.py:164-185
     p->off_x = 0; p->off_y = 4; p->off_z = 8; p->off_intensity = 12;
 }
+// The callback behind its argument checks, for both forms (the caller holds the context's lock and has bound its device; `l` has passed
+// check_pointcloud2_layout): `d_records` NULL: `raw_bytes` of `data` go up through the raw staging path first; else the records are read where they are.
+static int keyframe_callback_locked(const char* fn, mrgfe_map_store* s, uint64_t key, const KeyframeLayout& l, const void* data, size_t raw_bytes, const void* d_records,
+                                    const float* centres, int n_centres, float radius_sqr, float* kept, size_t* n_kept, float* removed, size_t* n_removed)
+{
+    const size_t n = size_t(l.width) * l.height;
+    if (s->clouds.count(key)) { set_error("%s: keyframe %llu is already stored", fn, static_cast<unsigned long long>(key)); return MRGFE_ERR_STATE; }
+    size_t nk = 0, nr = 0;
+    void*  p = nullptr;
+    if (n) {
+        mrgfe_ctx* ctx = s->ctx;
+        MRGFE_TRY(s->arena.alloc(n * 16, &p));  // room for every point; what the removal does not keep is handed back below
+        DevBuf& drem = ctx->scratch[2];
+        auto run = [&]() -> int {
+            const void* d_raw = d_records;
+            if (!d_raw) MRGFE_TRY(upload_raw_records(ctx, data, raw_bytes, &d_raw));
+            if (n_centres == 0) {
+                MRGFE_TRY(keyframe_gather_device(ctx, d_raw, l, static_cast<float4*>(p)));
+                nk = n;
+            } else {
+                if (removed) MRGFE_TRY(drem.ensure(n * 16));
+                MRGFE_TRY(keyframe_split_device(ctx, d_raw, l, centres, n_centres, radius_sqr, static_cast<float4*>(p), &nk, removed ? drem.as<float4>() : nullptr, &nr));  // (the first wait)
+                if (!((kept && nk) || (removed && nr))) return MRGFE_OK;  // nothing to bring down: the stream is idle
+            }
+            if (kept && nk) MRGFE_HIP_CHECK(hipMemcpyAsync(kept, p, nk * 16, hipMemcpyDeviceToHost, ctx->stream));
+            if (removed && nr) MRGFE_HIP_CHECK(hipMemcpyAsync(removed, drem.p, nr * 16, hipMemcpyDeviceToHost, ctx->stream));
+            MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // without centres the only wait, else the second
+            return MRGFE_OK;
+        };
+        const int rc = run();
+        if (rc != MRGFE_OK) {
+            (void)hipStreamSynchronize(ctx->stream);  // nothing is in flight when the room goes back
+            s->arena.shrink_last(p, n * 16, 0);
+            return rc;
+        }
+        s->arena.shrink_last(p, n * 16, nk * 16);
+        if (nk == 0) p = nullptr;
+    }
+    s->clouds[key] = {static_cast<const float4*>(p), static_cast<uint32_t>(nk)};
+    s->bytes += nk * 16;
+    *n_kept = nk;
+    if (n_removed) *n_removed = nr;
+    return MRGFE_OK;
+}
+// what both forms refuse before they look at the cloud
+static int keyframe_callback_check(const char* fn, uint64_t key, const float* centres, int n_centres)
+{
+    if (key == 0) { set_error("%s: key 0", fn); return MRGFE_ERR_INVALID; }
+    if (n_centres < 0 || n_centres > kMaxCentres || (n_centres > 0 && !centres)) { set_error("%s: %d centres (0 to %d, and their positions)", fn, n_centres, kMaxCentres); return MRGFE_ERR_INVALID; }
+    return MRGFE_OK;
+}
 int mrgfe_keyframe_callback(mrgfe_map_store* s, uint64_t key, const mrgfe_keyframe_params* lay, const void* data, size_t data_bytes, const float* centres, int n_centres,
                             float radius_sqr, float* kept, size_t* n_kept, float* removed, size_t* n_removed)
 {
@@ -983,8 +1034,7 @@ int mrgfe_keyframe_callback(mrgfe_map_store* s, uint64_t key, const mrgfe_keyfra
         if (!s || !lay || !n_kept) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
         *n_kept = 0;
         if (n_removed) *n_removed = 0;
-        if (key == 0) { set_error("%s: key 0", fn); return MRGFE_ERR_INVALID; }
-        if (n_centres < 0 || n_centres > kMaxCentres || (n_centres > 0 && !centres)) { set_error("%s: %d centres (0 to %d, and their positions)", fn, n_centres, kMaxCentres); return MRGFE_ERR_INVALID; }
+        MRGFE_TRY(keyframe_callback_check(fn, key, centres, n_centres));
         KeyframeLayout l{lay->width, lay->height, lay->point_step, lay->row_step, lay->off_x, lay->off_y, lay->off_z, lay->off_intensity};
         MRGFE_TRY(check_pointcloud2_layout(s->ctx, fn, l.width, l.height, l.point_step, &l.row_step, l.off_x, l.off_y, l.off_z, l.off_intensity));
         const size_t n = size_t(l.width) * l.height;
@@ -993,43 +1043,44 @@ int mrgfe_keyframe_callback(mrgfe_map_store* s, uint64_t key, const mrgfe_keyfra
         if (data_bytes < raw_bytes) { set_error("%s: the payload has %zu bytes, the layout needs %zu", fn, data_bytes, raw_bytes); return MRGFE_ERR_INVALID; }
         MRGFE_LOCK(s->ctx);
         MRGFE_TRY(s->ctx->bind());
-        if (s->clouds.count(key)) { set_error("%s: keyframe %llu is already stored", fn, static_cast<unsigned long long>(key)); return MRGFE_ERR_STATE; }
-        size_t nk = 0, nr = 0;
-        void*  p = nullptr;
-        if (n) {
-            mrgfe_ctx* ctx = s->ctx;
-            MRGFE_TRY(s->arena.alloc(n * 16, &p));  // room for every point; what the removal does not keep is handed back below
-            DevBuf& drem = ctx->scratch[2];
-            auto run = [&]() -> int {
-                const void* d_raw = nullptr;
-                MRGFE_TRY(upload_raw_records(ctx, data, raw_bytes, &d_raw));
-                if (n_centres == 0) {
-                    MRGFE_TRY(keyframe_gather_device(ctx, d_raw, l, static_cast<float4*>(p)));
-                    nk = n;
-                } else {
-                    if (removed) MRGFE_TRY(drem.ensure(n * 16));
-                    MRGFE_TRY(keyframe_split_device(ctx, d_raw, l, centres, n_centres, radius_sqr, static_cast<float4*>(p), &nk, removed ? drem.as<float4>() : nullptr, &nr));  // (the first wait)
-                    if (!((kept && nk) || (removed && nr))) return MRGFE_OK;  // nothing to bring down: the stream is idle
-                }
-                if (kept && nk) MRGFE_HIP_CHECK(hipMemcpyAsync(kept, p, nk * 16, hipMemcpyDeviceToHost, ctx->stream));
-                if (removed && nr) MRGFE_HIP_CHECK(hipMemcpyAsync(removed, drem.p, nr * 16, hipMemcpyDeviceToHost, ctx->stream));
-                MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // without centres the only wait, else the second
-                return MRGFE_OK;
-            };
-            const int rc = run();
-            if (rc != MRGFE_OK) {
-                (void)hipStreamSynchronize(ctx->stream);  // nothing is in flight when the room goes back
-                s->arena.shrink_last(p, n * 16, 0);
-                return rc;
-            }
-            s->arena.shrink_last(p, n * 16, nk * 16);
-            if (nk == 0) p = nullptr;
+        return keyframe_callback_locked(fn, s, key, l, data, raw_bytes, nullptr, centres, n_centres, radius_sqr, kept, n_kept, removed, n_removed);
+    });
+}
+// MRGFE_OK when the n packed points at `d` are device memory of the context's GPU (both ends of the cloud are asked about: hipPointerGetAttributes);
+// anything else — host memory, managed memory, another GPU's, a pointer the runtime does not know — is refused unread
+static int check_device_cloud(const mrgfe_ctx* ctx, const char* fn, const void* d, size_t n)
+{
+    const char* ends[2] = {static_cast<const char*>(d), static_cast<const char*>(d) + n * 16 - 1};
+    for (const char* e : ends) {
+        hipPointerAttribute_t a;
+        if (hipPointerGetAttributes(&a, e) != hipSuccess || a.type != hipMemoryTypeDevice || a.device != ctx->device) {
+            (void)hipGetLastError();  // (a pointer the runtime does not know is an error to the query, not a failure of the device)
+            set_error("%s: the cloud is not in the memory of device %d", fn, ctx->device);
+            return MRGFE_ERR_INVALID;
         }
-        s->clouds[key] = {static_cast<const float4*>(p), static_cast<uint32_t>(nk)};
-        s->bytes += nk * 16;
-        *n_kept = nk;
-        if (n_removed) *n_removed = nr;
-        return MRGFE_OK;
+    }
+    return MRGFE_OK;
+}
+int mrgfe_keyframe_callback_device(mrgfe_map_store* s, uint64_t key, const void* d_xyzi, size_t n, const float* centres, int n_centres, float radius_sqr, float* kept,
+                                   size_t* n_kept, float* removed, size_t* n_removed)
+{
+    static const char* fn = "mrgfe_keyframe_callback_device";
+    return abi_guard(fn, [&]() -> int {
+        if (!n_kept) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        *n_kept = 0;
+        if (n_removed) *n_removed = 0;
+        // (what can be refused without the store is refused first)
+        MRGFE_TRY(keyframe_callback_check(fn, key, centres, n_centres));
+        MRGFE_TRY(check_count(n, fn));
+        if (n && !d_xyzi) { set_error("%s: NULL cloud", fn); return MRGFE_ERR_INVALID; }
+        if (!s) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        // a packed device cloud is a PointCloud2 payload with point_step 16 that already sits where the head kernel reads it (one row: its row_step, which
+        // past 2^28 points no longer fits the field, is never multiplied)
+        const KeyframeLayout l{static_cast<uint32_t>(n), 1, 16, static_cast<uint32_t>(n * 16), 0, 4, 8, 12};
+        MRGFE_LOCK(s->ctx);
+        MRGFE_TRY(s->ctx->bind());
+        if (n) MRGFE_TRY(check_device_cloud(s->ctx, fn, d_xyzi, n));
+        return keyframe_callback_locked(fn, s, key, l, nullptr, 0, n ? d_xyzi : nullptr, centres, n_centres, radius_sqr, kept, n_kept, removed, n_removed);
     });
 }
 
@@ -1582,6 +1633,26 @@ int mrgfe_floor_detect_device(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const
         MRGFE_LOCK(ctx);
         MRGFE_TRY(ctx->bind());
         return floor_detect(ctx, p, static_cast<const float4*>(d_xyzi), n, res, out_filtered, out_inliers);
+    });
+}
+int mrgfe_floor_callback(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const mrgfe_keyframe_params* lay, const void* data, size_t data_bytes, mrgfe_floor_result* res,
+                         float* out_filtered, float* out_inliers)
+{
+    static const char* fn = "mrgfe_floor_callback";
+    return abi_guard(fn, [&]() -> int {
+        if (!p || !lay || !res) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        MRGFE_TRY(floor_check(p, fn));
+        // (the message is judged before the context is asked for: without one, by the strict rules)
+        KeyframeLayout l{lay->width, lay->height, lay->point_step, lay->row_step, lay->off_x, lay->off_y, lay->off_z, lay->off_intensity};
+        MRGFE_TRY(check_pointcloud2_layout(ctx, fn, l.width, l.height, l.point_step, &l.row_step, l.off_x, l.off_y, l.off_z, l.off_intensity));
+        const size_t n = size_t(l.width) * l.height;
+        const size_t raw_bytes = n ? size_t(l.height - 1) * l.row_step + size_t(l.width) * l.point_step : 0;
+        if (n && !data) { set_error("%s: NULL data", fn); return MRGFE_ERR_INVALID; }
+        if (data_bytes < raw_bytes) { set_error("%s: the payload has %zu bytes, the layout needs %zu", fn, data_bytes, raw_bytes); return MRGFE_ERR_INVALID; }
+        if (!ctx) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(ctx);
+        MRGFE_TRY(ctx->bind());
+        return floor_callback(ctx, p, l, data, raw_bytes, res, out_filtered, out_inliers);  // (an empty message: EMPTY_INPUT before any upload or launch, :74-77)
     });
 }
 

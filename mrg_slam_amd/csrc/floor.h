@@ -2,11 +2,17 @@
 // GPU — tilt + height band, k = 10 normal filter, RANSAC plane fit — and its two stage entry points for the tests.
 #pragma once
 #include "common.h"
+#include "mapcloud.h"
 
 namespace mrgfe {
 
 // the whole of detect() on a packed float4 device cloud (the input may be the caller's: it is only read)
 int floor_detect(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const float4* d_in, size_t n, mrgfe_floor_result* res, float* out_filtered, float* out_inliers);
+// the same on the bytes of a sensor_msgs/PointCloud2 (FloorDetectionComponent::cloud_callback :69-93): `raw_bytes` of `data` go up once through the raw
+// staging path and the first kernel reads the records (`lay` was checked by check_pointcloud2_layout, row_step filled in); behind it the same stages,
+// waits and results as floor_detect on the cloud mrgfe_ingest_pointcloud2 makes of the message
+int floor_callback(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const KeyframeLayout& lay, const void* data, size_t raw_bytes, mrgfe_floor_result* res, float* out_filtered,
+                   float* out_inliers);
 
 // RandomSampleConsensus<SampleConsensusModelPlane> on a device cloud: coefficients of the winning sample, inlier flags (device, n words; may be null),
 // iterations, skipped samples; *has_model = 0 when RANSAC found none (coeffs untouched then)

@@ -1,6 +1,7 @@
 // csrc/floor.hip — FloorDetectionComponent::detect (the reference's apps/floor_detection_component.cpp:100-183) on the GPU.
 //
 //   tilt + height band (:103-113, plane_clip :192-208)  floor_band_kernel -> compact_by_flags (order kept, as ExtractIndices)
+//   ... on the message's bytes (cloud_callback :72)      floor_head_kernel<kBytes>: pcl::fromROSMsg, the tilt and the band flag in one pass over the records
 //   normal_filtering (:216-243)                          NnGrid k = 10 -> floor_normals_kernel (PCL's float covariance, eigen33) -> compact_by_flags
 //   transform back (:124)                                floor_transform_kernel
 //   RandomSampleConsensus (:139-145)                     floor_sample_kernel (one wave: MT19937 + the index swaps) -> floor_count_kernel
@@ -37,7 +38,9 @@
 
 #include "dev_float.h"
 #include "filters.h"
+#include "ingest.h"
 #include "nn_grid.h"
+#include "scan_point.h"
 
 namespace mrgfe {
 
@@ -65,20 +68,46 @@ static_assert(sizeof(FloorHyp) == 32, "FloorHyp layout");
 
 struct Rot12 { float m[12]; };  // row-major 3 x 4
 
+// tilt + height band for one point (:109-112): ONE body for the band kernel and the head kernel, so the route over the message's bytes cannot round or
+// flag differently from the route over a packed cloud
+__device__ __forceinline__ void floor_band_point(const Rot12& T, float4 p, float lo, float hi, float4* __restrict__ out, uint32_t* __restrict__ flag)
+{
+#pragma clang fp contract(off)
+    float x, y, z;
+    transform_point(T.m, p.x, p.y, p.z, x, y, z);  // pcl::transformPointCloud(*cloud, *filtered, tilt_matrix) (:109)
+    *out = make_float4(x, y, z, p.w);
+    // PlaneClipper3D::clipPoint3D with plane (0, 0, 1, d): (0 x + 0 y + 1 z) >= -d.  Kept by the first clip (d = h + r, :111) and not removed by the
+    // second (d = h - r, setNegative(true), :112)
+    const float h = dot3f(0.0f, x, 0.0f, y, 1.0f, z);
+    *flag = (h >= lo && !(h >= hi)) ? 1u : 0u;
+}
+
 __global__ __launch_bounds__(256) void floor_band_kernel(const float4* __restrict__ in, uint32_t n, Rot12 T, float lo, float hi, float4* __restrict__ out,
                                                          uint32_t* __restrict__ flags)
 {
 #pragma clang fp contract(off)
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const float4 p = in[i];
-    float x, y, z;
-    transform_point(T.m, p.x, p.y, p.z, x, y, z);  // pcl::transformPointCloud(*cloud, *filtered, tilt_matrix) (:109)
-    out[i] = make_float4(x, y, z, p.w);
-    // PlaneClipper3D::clipPoint3D with plane (0, 0, 1, d): (0 x + 0 y + 1 z) >= -d.  Kept by the first clip (d = h + r, :111) and not removed by the
-    // second (d = h - r, setNegative(true), :112)
-    const float h = dot3f(0.0f, x, 0.0f, y, 1.0f, z);
-    flags[i] = (h >= lo && !(h >= hi)) ? 1u : 0u;
+    floor_band_point(T, in[i], lo, hi, out + i, flags + i);
+}
+
+// The head of FloorDetectionComponent::cloud_callback on the message's bytes (:72 pcl::fromROSMsg, then :109-112): point i is read out of its strided
+// record (scan_point.h load_point_record_as, the body every reader of PointCloud2 bytes uses), tilted and flagged as floor_band_kernel does.  One point
+// per thread; reads 16 B of fields (within point_step bytes of record), writes 16 + 4 B.  No LDS, no atomics.
+// kBytes: the layout is not a strict one (ingest.h layout_is_strict) and the record's fields are put together from aligned words.
+struct FloorHeadArgs {
+    const uint8_t* raw;
+    uint32_t       n, width, row_step, point_step, ox, oy, oz;
+    int32_t        oi;
+};
+template <bool kBytes>
+__global__ __launch_bounds__(256) void floor_head_kernel(const FloorHeadArgs a, Rot12 T, float lo, float hi, float4* __restrict__ out, uint32_t* __restrict__ flags)
+{
+#pragma clang fp contract(off)
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= a.n) return;
+    const float4 p = load_point_record_as<kBytes>(a.raw, i, a.width, a.row_step, a.point_step, a.ox, a.oy, a.oz, a.oi);
+    floor_band_point(T, p, lo, hi, out + i, flags + i);
 }
 
 __global__ __launch_bounds__(256) void floor_transform_kernel(const float4* __restrict__ in, uint32_t n, Rot12 T, float4* __restrict__ out)
@@ -507,7 +536,12 @@ int floor_ransac_device(mrgfe_ctx* ctx, const float4* d_pts, uint32_t n, double 
     return MRGFE_OK;
 }
 
-int floor_detect(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const float4* d_in, size_t n_in, mrgfe_floor_result* res, float* out_filtered, float* out_inliers)
+// detect() behind its first stage.  `head(T, lo, hi, d_tilt, d_flags)` queues on the context's stream whatever leaves the n_in tilted points and their
+// height-band flags in those two buffers (floor_detect: floor_band_kernel over a packed cloud; floor_callback: the upload and floor_head_kernel over the
+// message's records); everything from the band's compaction on — normal filter, inverse tilt, RANSAC, verticality, inlier extraction, the event timings,
+// fl_stats — is this one body for both routes.
+template <class Head>
+static int floor_detect_behind(mrgfe_ctx* ctx, const mrgfe_floor_params* p, size_t n_in, Head&& head, mrgfe_floor_result* res, float* out_filtered, float* out_inliers)
 {
     std::memset(res, 0, sizeof(*res));
     for (double& s : ctx->fl_stats) s = 0;
@@ -529,8 +563,7 @@ int floor_detect(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const float4* d_in
     MRGFE_TRY(dflags.ensure(size_t(n) * 4));
     MRGFE_TRY(dband.ensure(size_t(n) * 16));
     MRGFE_TRY(dfilt.ensure(size_t(n) * 16));
-    hipLaunchKernelGGL(floor_band_kernel, blocks(n), dim3(256), 0, st, d_in, n, T, lo, hi, dtilt.as<float4>(), dflags.as<uint32_t>());
-    MRGFE_HIP_CHECK(hipGetLastError());
+    MRGFE_TRY(head(T, lo, hi, dtilt.as<float4>(), dflags.as<uint32_t>()));
     uint32_t n_clip = 0;
     MRGFE_TRY(compact_by_flags(ctx, dtilt.as<float4>(), n, dflags.as<uint32_t>(), dband.as<float4>(), &n_clip));
     ctx->fl_stats[4] += 1;
@@ -607,6 +640,37 @@ int floor_detect(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const float4* d_in
         ctx->fl_stats[s] = ms;
     }
     return MRGFE_OK;
+}
+
+int floor_detect(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const float4* d_in, size_t n_in, mrgfe_floor_result* res, float* out_filtered, float* out_inliers)
+{
+    const uint32_t n = static_cast<uint32_t>(n_in);
+    auto head = [&](const Rot12& T, float lo, float hi, float4* d_tilt, uint32_t* d_flags) -> int {
+        hipLaunchKernelGGL(floor_band_kernel, blocks(n), dim3(256), 0, ctx->stream, d_in, n, T, lo, hi, d_tilt, d_flags);
+        MRGFE_HIP_CHECK(hipGetLastError());
+        return MRGFE_OK;
+    };
+    return floor_detect_behind(ctx, p, n_in, head, res, out_filtered, out_inliers);
+}
+
+int floor_callback(mrgfe_ctx* ctx, const mrgfe_floor_params* p, const KeyframeLayout& lay, const void* data, size_t raw_bytes, mrgfe_floor_result* res, float* out_filtered,
+                   float* out_inliers)
+{
+    FloorHeadArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.n = lay.width * lay.height;
+    a.width = lay.width; a.row_step = lay.row_step; a.point_step = lay.point_step;
+    a.ox = lay.off_x; a.oy = lay.off_y; a.oz = lay.off_z; a.oi = lay.off_intensity;
+    auto head = [&](const Rot12& T, float lo, float hi, float4* d_tilt, uint32_t* d_flags) -> int {
+        const void* d_raw = nullptr;
+        MRGFE_TRY(upload_raw_records(ctx, data, raw_bytes, &d_raw));  // stream-ordered, no wait: `data` is free on return
+        a.raw = static_cast<const uint8_t*>(d_raw);
+        const auto kern = layout_is_strict(a.point_step, a.row_step, a.ox, a.oy, a.oz, a.oi) ? floor_head_kernel<false> : floor_head_kernel<true>;
+        hipLaunchKernelGGL(kern, blocks(a.n), dim3(256), 0, ctx->stream, a, T, lo, hi, d_tilt, d_flags);
+        MRGFE_HIP_CHECK(hipGetLastError());
+        return MRGFE_OK;
+    };
+    return floor_detect_behind(ctx, p, a.n, head, res, out_filtered, out_inliers);
 }
 
 }  // namespace mrgfe

@@ -1,5 +1,6 @@
 """Floor detection on the GPU: ``FloorDetectionComponent::detect`` (the reference's apps/floor_detection_component.cpp:100-183) — tilt compensation,
-the height band, the k = 10 normal filter and the RANSAC plane fit — through ``mrgfe_floor_detect`` (csrc/floor.hip), and a host mirror of the
+the height band, the k = 10 normal filter and the RANSAC plane fit — through ``mrgfe_floor_detect`` (csrc/floor.hip), on a host cloud, on a packed
+cloud in device memory or, in one call, on the bytes of the sensor_msgs/PointCloud2 (``mrgfe_floor_callback``), and a host mirror of the
 component's ``cloud_callback`` (:69-95).
 
 Parameter names and defaults are the component's (:55-62) and config/mrg_slam.yaml:113-122.  The reference declares ``enable_normal_filtering``
@@ -97,6 +98,25 @@ class FloorDetection:
         self.last = _record(r, filt, inl)
         return self.last.coeffs
 
+    def detect_pointcloud2(self, data, width: int, height: int, point_step: int, fields, row_step: int = 0, want_clouds: bool = True):
+        """``cloud_callback`` (:69-93) on the bytes of the sensor_msgs/PointCloud2 in one call (``mrgfe_floor_callback``): the payload goes up once and
+        the first kernel reads the records.  ``fields``: as ``io.layout_from_fields`` takes them (a field list whose layout needs it switches the
+        context to byte layouts).  Same plane, record and clouds as ``io.ingest_pointcloud2`` followed by :meth:`detect_device`; an empty message
+        gives None with ``last.reason == "empty_input"``."""
+        from .io import layout_from_fields, pointcloud2_payload
+
+        ctx = self.ctx or default_context()
+        buf = pointcloud2_payload(data, width, height, point_step, row_step)
+        lay, _ = layout_from_fields(fields, width, height, point_step, row_step, ctx=ctx)
+        n = int(width) * int(height)
+        q, r = _params(self.p), _lib.FloorResult()
+        filt = np.empty((max(n, 1), 4), dtype=np.float32) if want_clouds else None
+        inl = np.empty((max(n, 1), 4), dtype=np.float32) if want_clouds else None
+        check(lib().mrgfe_floor_callback(ctx._h, C.byref(q), C.byref(lay), buf.ctypes.data_as(C.c_void_p) if buf.nbytes else None, buf.nbytes, C.byref(r),
+                                         None if filt is None else filt.ctypes.data_as(_fp), None if inl is None else inl.ctypes.data_as(_fp)))
+        self.last = _record(r, filt, inl)
+        return self.last.coeffs
+
     def stage_times(self) -> dict:
         """HIP-event milliseconds of the stages of the last detection on the context, its host waits and RANSAC waves (``mrgfe_dbg_floor_stats``)."""
         ctx = self.ctx or default_context()
@@ -137,6 +157,11 @@ class HipOps:
         fd = FloorDetection(ctx=self.ctx, **p)
         return fd.detect(cloud, want_clouds=False)
 
+    def detect_pointcloud2(self, msg: dict, p: dict):
+        """The message's bytes in one call (``mrgfe_floor_callback``)."""
+        fd = FloorDetection(ctx=self.ctx, **p)
+        return fd.detect_pointcloud2(msg["data"], msg["width"], msg.get("height", 1), msg["point_step"], msg["fields"], int(msg.get("row_step", 0) or 0), want_clouds=False)
+
 
 class FloorDetectionComponent:
     """Host mirror of ``FloorDetectionComponent::cloud_callback`` (:69-95).  ``ops.detect(cloud, params)`` supplies ``detect()``: by default the HIP
@@ -152,4 +177,12 @@ class FloorDetectionComponent:
         if len(c) == 0:
             return None
         floor = self.ops.detect(c, self.p)
+        return [] if floor is None else [float(v) for v in np.asarray(floor, dtype=np.float32)]
+
+    def pointcloud2_callback(self, msg: dict):
+        """The same callback on the sensor_msgs/PointCloud2 itself — a dict with ``data``, ``width``, ``height``, ``point_step``, ``fields`` and
+        optionally ``row_step``: ``ops.detect_pointcloud2(msg, params)`` gets its bytes in one call (``pcl::fromROSMsg``, :72, runs on the device)."""
+        if int(msg["width"]) * int(msg.get("height", 1)) == 0:  # :74-77
+            return None
+        floor = self.ops.detect_pointcloud2(msg, self.p)
         return [] if floor is None else [float(v) for v in np.asarray(floor, dtype=np.float32)]

@@ -97,13 +97,17 @@ def robot_radius_sqr(radius: float) -> float:
 
 
 class HipOps:
-    """The point operations on the GPU in one call (``mrgfe_keyframe_callback``): the kept cloud becomes keyframe ``key`` of ``store``."""
+    """The point operations on the GPU in one call (``mrgfe_keyframe_callback``, or ``mrgfe_keyframe_callback_device`` for a cloud that is already in
+    HBM): the kept cloud becomes keyframe ``key`` of ``store``."""
 
     def __init__(self, store):
         self.store = store
 
     def keyframe(self, key, msg, centres_sensor, radius, want_removed):
         return self.store.keyframe_callback(key, msg, centres_sensor, radius, want_kept=len(centres_sensor) > 0, want_removed=want_removed)
+
+    def keyframe_device(self, key, dev_ptr, n, centres_sensor, radius, want_removed):
+        return self.store.keyframe_callback_device(key, dev_ptr, n, centres_sensor, radius, want_kept=len(centres_sensor) > 0, want_removed=want_removed)
 
 
 @dataclasses.dataclass
@@ -131,8 +135,8 @@ class KeyframeCallback:
         self.others_odom_poses: dict = {}  # robot name -> position x, y, z in the map frame (others_odom_poses_), :386-393
         self.next_key = 1
 
-    def cloud_callback(self, odom, msg, key: int | None = None, removed_points_wanted: bool = False):
-        """:358-447.  Returns a :class:`KeyframeResult`, or None when the pose starts no keyframe."""
+    def _keyframe(self, odom, key, removed_points_wanted, point_work):
+        """:358-447 around the point work: ``point_work(key, centres, radius, want_removed)`` returns ``(kept, removed)``."""
         odom = np.array(odom, dtype=np.float64)
         update_required = self.updater.update(odom)  # :367
         accum_d = self.updater.get_accum_distance()
@@ -149,12 +153,21 @@ class KeyframeCallback:
         centres = others_positions_sensor(odom, map2odom, others) if others else np.zeros((0, 3), dtype=np.float32)  # :396-404
         if key is None:
             key, self.next_key = self.next_key, self.next_key + 1
-        kept, removed = self.ops.keyframe(key, msg, centres, self.p["robot_remove_points_radius"], bool(removed_points_wanted))
+        kept, removed = point_work(key, centres, self.p["robot_remove_points_radius"], bool(removed_points_wanted))
         if not len(centres):
             kept = None
             if removed_points_wanted and removed is None:
                 removed = np.empty((0, 4), dtype=np.float32)  # removed_cloud stays empty, :395
         return KeyframeResult(key, accum_d, odom, kept, removed if removed_points_wanted else None, centres)
+
+    def cloud_callback(self, odom, msg, key: int | None = None, removed_points_wanted: bool = False):
+        """:358-447.  Returns a :class:`KeyframeResult`, or None when the pose starts no keyframe."""
+        return self._keyframe(odom, key, removed_points_wanted, lambda k, centres, radius, want_removed: self.ops.keyframe(k, msg, centres, radius, want_removed))
+
+    def cloud_callback_device(self, odom, dev_ptr: int, n: int, key: int | None = None, removed_points_wanted: bool = False):
+        """The same callback — the same :class:`KeyframeUpdater` decision, the same centres — for a filtered scan that is already in HBM (all
+        components in one container): ``n`` packed float4 points at ``dev_ptr`` on the store's device (``ops.keyframe_device``)."""
+        return self._keyframe(odom, key, removed_points_wanted, lambda k, centres, radius, want_removed: self.ops.keyframe_device(k, dev_ptr, n, centres, radius, want_removed))
 
 
 __all__ = ["DEFAULTS", "KeyframeUpdater", "KeyframeCallback", "KeyframeResult", "HipOps", "angle_axis_angle", "isometry_inverse", "others_positions_sensor", "robot_radius_sqr"]

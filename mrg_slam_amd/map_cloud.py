@@ -130,6 +130,23 @@ class MapCloudStore:
             removed = np.empty((0, 4), dtype=np.float32)  # (no other robot: nothing was removed)
         return (kept[: nk.value] if kept is not None else None), (removed[: nr.value] if removed is not None else None)
 
+    def keyframe_callback_device(self, key: int, dev_ptr: int, n: int, centres_sensor=None, radius: float = 0.0, want_kept: bool = True, want_removed: bool = False):
+        """``mrgfe_keyframe_callback_device``: :meth:`keyframe_callback` for a filtered scan that is already in HBM (all components in one container) —
+        ``n`` packed float4 points at ``dev_ptr`` on the store's device, complete when the call is made (``scan_callback_to_device`` and the other
+        ``*_device`` producers return only after their wait).  No upload: the same kernels read the buffer where it is; it is only read and is free
+        on return.  Returns ``(kept, removed)`` as :meth:`keyframe_callback` does."""
+        n = int(n)
+        ctr = np.ascontiguousarray(np.asarray(centres_sensor if centres_sensor is not None else np.zeros((0, 3)), dtype=np.float32).reshape(-1, 3))
+        kept = np.empty((n, 4), dtype=np.float32) if want_kept else None
+        removed = np.empty((n, 4), dtype=np.float32) if want_removed and len(ctr) else None
+        nk, nr = C.c_size_t(0), C.c_size_t(0)
+        check(lib().mrgfe_keyframe_callback_device(self._h, int(key), C.c_void_p(int(dev_ptr)) if dev_ptr else None, n, ctr.ctypes.data_as(_fp) if len(ctr) else None, len(ctr),
+                                                   float(np.float32(float(radius) * float(radius))), kept.ctypes.data_as(_fp) if kept is not None else None, C.byref(nk),
+                                                   removed.ctypes.data_as(_fp) if removed is not None else None, C.byref(nr)))
+        if want_removed and removed is None:
+            removed = np.empty((0, 4), dtype=np.float32)  # (no other robot: nothing was removed)
+        return (kept[: nk.value] if kept is not None else None), (removed[: nr.value] if removed is not None else None)
+
     def fill_ground(self, src_key: int, dst_key: int, radius: float = 5.0, map_resolution: float = 0.05, simple: bool = False, estimate=None, want_cloud: bool = True):
         """``mrgfe_map_store_fill_ground``: the ground fill of the first keyframe (src/mrg_slam/graph_database.cpp:114-129) for the stored keyframe
         ``src_key``.  The filled cloud becomes the NEW keyframe ``dst_key`` — name the first keyframe by it from then on —; ``src_key`` stays as it was.
