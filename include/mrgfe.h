@@ -139,6 +139,12 @@ int  mrgfe_ctx_set_zero_copy_uploads(mrgfe_ctx* ctx, int on);
  * (each field put together from at most two aligned 4-byte words, its bits as they are, NaN payloads and denormals included); a layout that satisfies
  * the default rules launches exactly the kernels it launches with the switch off.  Contexts made like this one (mrgfe_ctx_create_like) inherit it. */
 int  mrgfe_ctx_set_byte_layouts(mrgfe_ctx* ctx, int on);
+/* Batches of the BFGS methods (off by default).  on = 1: mrgfe_batch_create on this context accepts MRGFE_PCL_GICP_HIP and MRGFE_PCL_GICP_OMP_HIP
+ * (registration_method "GICP" / "GICP_OMP"): the candidates' BFGS loops advance in lock step, one round per functor evaluation of the pairs still running,
+ * and every record is that of a single registration of the same pair, bit for bit (see mrgfe_batch_create).  Off: mrgfe_batch_create refuses the two
+ * methods as it always did ("offered for single registrations only").  Contexts made like this one (mrgfe_ctx_create_like) inherit the switch.
+ * mrgfe_node_create makes its own contexts and keeps refusing the two methods: nodes of BFGS batches are not offered. */
+int  mrgfe_ctx_set_bfgs_batches(mrgfe_ctx* ctx, int on);
 /* HIP stream of the context as an opaque pointer (hipStream_t), for callers that order their own work after it */
 void* mrgfe_ctx_stream(mrgfe_ctx* ctx);
 /* Measurement hook ("1-NN fitness on hash grid: N (16 + 27*8 + m*16)"): what the last getFitnessScore pass on this context
@@ -656,7 +662,12 @@ typedef struct mrgfe_batch mrgfe_batch;
  * its exact-NN grid, and the ICP loops of all pairs advance in lock step — per round one correspondence + moment launch and one
  * reduction over the pairs still running, one host wait for their 17-sum records, one transform launch; no covariances are computed
  * and H of the records is all zero.  The records are those of a single ICP_HIP registration of the same pair, bit for bit.
- * PCL_GICP_HIP and PCL_GICP_OMP_HIP are offered for single registrations only. */
+ * PCL_GICP_HIP and PCL_GICP_OMP_HIP are offered for single registrations only, unless the context has mrgfe_ctx_set_bfgs_batches on.  Then: the
+ * candidates of a target share its covariances (PCL's form) and correspondence grid, the source covariances are computed as for GICP_HIP (or taken
+ * from the keyframe store), and the pairs' BFGS loops advance in lock step — per round the correspondence searches of the pairs that begin an outer
+ * iteration, one cost / gradient launch and one sum launch (ONE workgroup per pair: the sums are chains in the reference's order) over the pairs still
+ * running, one host wait for their 14-sum records.  H of the records is all zero, trans_probability 0, evaluations = functor evaluations + outer
+ * iterations; the records are those of a single registration of the same pair, bit for bit.  mrgfe_batch_rounds counts the rounds. */
 int  mrgfe_batch_create(mrgfe_ctx* ctx, const mrgfe_reg_params* params, mrgfe_batch** out);
 void mrgfe_batch_destroy(mrgfe_batch* b);
 int  mrgfe_batch_clear(mrgfe_batch* b);
@@ -952,7 +963,9 @@ int    mrgfe_loop_create_node(mrgfe_node* node, mrgfe_map_store* store, const mr
  * group or -1, best_score[g] = its fitness or DBL_MAX.  Among equal scores the LAST candidate wins, as there. */
 int    mrgfe_node_select_best(const mrgfe_pair_result* results, int n_groups, const int32_t* group_first, int32_t* best, double* best_score);
 /* rounds (plan -> derivative launches -> reduce / controller step) of the last mrgfe_batch_align of an NDT_HIP batch; of an ICP_HIP batch its
- * lock-step rounds (correspondences + sums -> reduce -> controller steps -> transform), which is the largest evaluation count of its pairs */
+ * lock-step rounds (correspondences + sums -> reduce -> controller steps -> transform), which is the largest evaluation count of its pairs; of a
+ * PCL_GICP_HIP / PCL_GICP_OMP_HIP batch its rounds (searches -> cost / gradient terms -> sums -> controller steps), which is the largest number of
+ * functor evaluations of its pairs (at most the largest `evaluations` of the records) */
 int mrgfe_batch_rounds(const mrgfe_batch* b);
 /* The reference's own performance counters (loop_detector.cpp:22-34: per new keyframe with candidates the wall microseconds of find_candidates + matching
  * and the candidate count; apps/mrg_slam_component.cpp:1032-1037 writes their ratio as average_time_per_candidate_us) for this batch object:

@@ -223,6 +223,7 @@ SIGNATURES = {
     "mrgfe_unpin_host_buffer": (C.c_int, [_vp, _vp]),
     "mrgfe_ctx_set_zero_copy_uploads": (C.c_int, [_vp, C.c_int]),
     "mrgfe_ctx_set_byte_layouts": (C.c_int, [_vp, C.c_int]),
+    "mrgfe_ctx_set_bfgs_batches": (C.c_int, [_vp, C.c_int]),
     "mrgfe_ctx_stream": (_vp, [_vp]),
     "mrgfe_ctx_fitness_stats": (C.c_int, [_vp, _dp]),
     "mrgfe_ctx_knn_stats": (C.c_int, [_vp, _dp]),
@@ -538,6 +539,11 @@ class Context:
         """``mrgfe_ctx_set_byte_layouts``: the calls that read PointCloud2 bytes on this context (and on the stores and registrations made on it) take
         layouts whose field offsets or steps are not multiples of 4 — Velodyne's 22-byte records — as ``pcl::fromROSMsg`` does."""
         check(lib().mrgfe_ctx_set_byte_layouts(self._h, int(bool(on))))
+
+    def set_bfgs_batches(self, on: bool = True):
+        """``mrgfe_ctx_set_bfgs_batches``: ``BatchMatcher`` on this context takes PCL_GICP_HIP and PCL_GICP_OMP_HIP (the candidates' BFGS loops in lock
+        step, records bit-identical to :class:`PclGicpHip`).  Off, the default, such a batch is refused as it always was."""
+        check(lib().mrgfe_ctx_set_bfgs_batches(self._h, int(bool(on))))
 
     def fitness_stats(self) -> dict:
         """What the last getFitnessScore pass on this context did (``mrgfe_ctx_fitness_stats``)."""

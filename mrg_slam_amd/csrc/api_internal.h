@@ -25,6 +25,7 @@ inline int check_count(size_t n, const char* fn)
 }
 
 inline bool is_ndt(int method) { return method == MRGFE_NDT_HIP || method == MRGFE_PCL_NDT_HIP; }
+inline bool is_pcl_gicp(int method) { return method == MRGFE_PCL_GICP_HIP || method == MRGFE_PCL_GICP_OMP_HIP; }
 
 inline NdtParams ndt_params_from(const mrgfe_reg_params& p)
 {
@@ -82,7 +83,8 @@ inline int check_params(const mrgfe_reg_params* p)
     return MRGFE_OK;
 }
 
-// GICP_HIP, SMALL_GICP_HIP and VGICP_HIP keep the k-NN covariances of a stored keyframe (48 bytes per point) with it; NDT and ICP_HIP need the cloud alone
+// GICP_HIP, SMALL_GICP_HIP, VGICP_HIP and the two PCL GICPs (PCL's form of them) keep the k-NN covariances of a stored keyframe (48 bytes per point) with
+// it; NDT and ICP_HIP need the cloud alone
 inline bool keeps_covariances(const mrgfe_reg_params& p) { return !is_ndt(p.method) && p.method != MRGFE_ICP_HIP; }
 
 }  // namespace mrgfe

@@ -121,7 +121,7 @@ int mrgfe_batch_create(mrgfe_ctx* ctx, const mrgfe_reg_params* params, mrgfe_bat
         if (!ctx || !out) { set_error("mrgfe_batch_create: NULL argument"); return MRGFE_ERR_INVALID; }
         *out = nullptr;
         MRGFE_TRY(check_params(params));
-        if (params->method == MRGFE_PCL_GICP_HIP || params->method == MRGFE_PCL_GICP_OMP_HIP) {
+        if (is_pcl_gicp(params->method) && !ctx->bfgs_batches.load(std::memory_order_relaxed)) {  // (mrgfe_ctx_set_bfgs_batches opens the door)
             set_error("mrgfe_batch_create: PCL_GICP_HIP and PCL_GICP_OMP_HIP are offered for single registrations only");
             return MRGFE_ERR_INVALID;
         }
@@ -718,7 +718,8 @@ int batch_align_abandon(mrgfe_batch* b)
 extern "C" {
 
 // GICP_HIP: the candidates of a target share its covariances and correspondence grid, and all LM loops advance together (GicpBatch: one
-// launch per kernel and round for the pairs still running); ICP_HIP: lock-step ICP rounds, no covariances.  The records follow in batch_records.
+// launch per kernel and round for the pairs still running); ICP_HIP: lock-step ICP rounds, no covariances; PCL_GICP_HIP / PCL_GICP_OMP_HIP: PCL's
+// covariances, the BFGS loops of the pairs in lock step, a round per functor evaluation.  The records follow in batch_records.
 static int gicp_align_batch(mrgfe_batch* b)
 {
     const PairBook& book = b->book;
@@ -744,6 +745,7 @@ static int gicp_align_batch(mrgfe_batch* b)
         }
     }
     if (b->params.method == MRGFE_ICP_HIP) return b->gicp_batch->align_all_icp(b->gicp, book, b->gicp_pairs);
+    if (is_pcl_gicp(b->params.method)) return b->gicp_batch->align_all_pcl(b->gicp, book, b->gicp_pairs);
     return b->gicp_batch->align_all(b->gicp, book, b->gicp_pairs);
 }
 
@@ -965,6 +967,10 @@ static void batch_records(mrgfe_batch* b, const std::vector<char>& early_done, m
             const IcpController& c = b->gicp_pairs[i].icp;
             std::memcpy(F, c.final_transformation(), sizeof(float) * 16);
             write_record(results[i], i, F, nullptr, 0.0, c.converged(), c.iterations(), c.evaluations(), scored);
+        } else if (is_pcl_gicp(b->params.method)) {  // the BFGS keeps no Hessian
+            const PclGicpController& c = b->gicp_pairs[i].pcl;
+            std::memcpy(F, c.final_transformation(), sizeof(float) * 16);
+            write_record(results[i], i, F, nullptr, 0.0, c.converged(), c.iterations(), c.evaluations(), scored);
         } else {
             const GicpLmController& c = b->gicp_pairs[i].ctl;
             c.final_transformation(F);
@@ -1121,7 +1127,7 @@ int mrgfe_batch_pair_counts(const mrgfe_batch* b, int mode, double* points, doub
 int mrgfe_batch_rounds(const mrgfe_batch* b)
 {
     if (!b) return 0;
-    if (b->params.method == MRGFE_ICP_HIP) return b->gicp_batch ? b->gicp_batch->rounds() : 0;
+    if (b->params.method == MRGFE_ICP_HIP || is_pcl_gicp(b->params.method)) return b->gicp_batch ? b->gicp_batch->rounds() : 0;
     return b->ndt ? b->ndt->rounds() : 0;
 }
 

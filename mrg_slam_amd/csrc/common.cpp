@@ -483,6 +483,7 @@ static int ctx_create(int device_id, int high_priority, int reserve_cus, const m
         c->cu_count = like->cu_count;
         c->zero_copy_uploads = like->zero_copy_uploads;
         c->byte_layouts.store(like->byte_layouts.load());
+        c->bfgs_batches.store(like->bfgs_batches.load());
     } else if (reserve_cus == MRGFE_RESERVE_AUTO && c->cu_count < 8) {
         // nothing sensible to split off: a plain context
     } else if (reserve_cus > 0 || reserve_cus == MRGFE_RESERVE_AUTO) {
@@ -541,6 +542,14 @@ int mrgfe_ctx_set_byte_layouts(mrgfe_ctx* ctx, int on)
     if (!ctx) { mrgfe::set_error("mrgfe_ctx_set_byte_layouts: NULL context"); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(ctx);  // (behind whatever call holds the context: the next layout check sees the new value)
     ctx->byte_layouts.store(on != 0);
+    return MRGFE_OK;
+}
+
+int mrgfe_ctx_set_bfgs_batches(mrgfe_ctx* ctx, int on)
+{
+    if (!ctx) { mrgfe::set_error("mrgfe_ctx_set_bfgs_batches: NULL context"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(ctx);  // (behind whatever call holds the context: the next mrgfe_batch_create sees the new value)
+    ctx->bfgs_batches.store(on != 0);
     return MRGFE_OK;
 }
 

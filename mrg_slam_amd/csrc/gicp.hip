@@ -11,7 +11,6 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
-#include <functional>
 #include <atomic>
 #include <string>
 #include <thread>
@@ -20,14 +19,12 @@
 #include "dev_float.h"
 #include "dev_linalg.h"
 #include "dev_utils.h"
-#include "bfgs.h"
 #include "gicp_engine.h"
 #include "nn_device.h"
 #include "ndt_derivatives.h"  // launch_transform_cloud
+#include "pclgicp_ctl.h"      // kGicpStride (partial record: err, b[6], H upper[21], n_corr, pad); the host side of PCL_GICP_HIP
 
 namespace mrgfe {
-
-constexpr int kGicpStride = 32;  // partial record: err, b[6], H upper[21], n_corr, pad
 
 __device__ __forceinline__ int gidx(int i, int j) { return i * 6 - (i * (i - 1)) / 2 + (j - i); }
 
@@ -323,11 +320,12 @@ struct PclGicpIter {
     double R[9];
     double thr2;
 };
-__global__ __launch_bounds__(256) void pclgicp_corr_kernel(NnGrid2Dev g, const float4* __restrict__ src, uint32_t n, PclGicpIter it, const double* __restrict__ cov_src,
-                                                            const double* __restrict__ cov_tgt, int32_t* __restrict__ corr, double* __restrict__ mahal)
+// (the body of block `blk`: the single registration's kernel and the batch's call it, so there is one text of the arithmetic)
+__device__ __forceinline__ void pclgicp_corr_block(const NnGrid2Dev& g, const float4* __restrict__ src, uint32_t n, const PclGicpIter& it, const double* __restrict__ cov_src,
+                                                   const double* __restrict__ cov_tgt, int32_t* __restrict__ corr, double* __restrict__ mahal, uint32_t blk)
 {
 #pragma clang fp contract(off)
-    const uint32_t i = blockIdx.x * (256u / kGicpGroup) + threadIdx.x / kGicpGroup;
+    const uint32_t i = blk * (256u / kGicpGroup) + threadIdx.x / kGicpGroup;
     if (i >= n) return;
     const float4 a = src[i];
     float q[3];
@@ -358,20 +356,27 @@ __global__ __launch_bounds__(256) void pclgicp_corr_kernel(NnGrid2Dev g, const f
     double* o = mahal + size_t(i) * 9;
     for (int t = 0; t < 9; ++t) o[t] = M[t];
 }
+__global__ __launch_bounds__(256) void pclgicp_corr_kernel(NnGrid2Dev g, const float4* __restrict__ src, uint32_t n, PclGicpIter it, const double* __restrict__ cov_src,
+                                                            const double* __restrict__ cov_tgt, int32_t* __restrict__ corr, double* __restrict__ mahal)
+{
+    pclgicp_corr_block(g, src, n, it, cov_src, cov_tgt, corr, mahal, blockIdx.x);
+}
 
 // OptimizationFunctorWithIndices::fdf over the correspondences: d = T(x) p_src - p_tgt (float), Md = M d, f += d^T Md, g_t += Md,
 // dCost_dR_T += p_base_src Md^T (base_transformation_ is the identity in computeTransformation: p_base_src = p_src)
 // kTerms: the 13 terms + the correspondence flag of every point go to `terms` ([14][n_pad], a column per sum) instead of into the block tree — the
 // serial reference adds them one after the other in point order, and pclgicp_seqsum_kernel does exactly that
+// (the body of block `blk`, for the single registration's kernel and the batch's; `partials` is the first block-partial record of the cloud)
 template <bool kTerms>
-__global__ __launch_bounds__(256) void pclgicp_fdf_kernel(const float4* __restrict__ src, uint32_t n, const float4* __restrict__ tgt, const int32_t* __restrict__ corr,
-                                                           const double* __restrict__ mahal, PclGicpIter it, double* __restrict__ partials, double* __restrict__ terms, uint32_t n_pad)
+__device__ __forceinline__ void pclgicp_fdf_block(const float4* __restrict__ src, uint32_t n, const float4* __restrict__ tgt, const int32_t* __restrict__ corr,
+                                                  const double* __restrict__ mahal, const PclGicpIter& it, double* __restrict__ partials, double* __restrict__ terms, uint32_t n_pad,
+                                                  uint32_t blk)
 {
 #pragma clang fp contract(off)
     double vals[29];
 #pragma unroll
     for (int k = 0; k < 29; ++k) vals[k] = 0.0;
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t i = blk * 256u + threadIdx.x;
     if (i < n) {
         const int32_t j = corr[i];
         if (j >= 0) {
@@ -406,7 +411,13 @@ __global__ __launch_bounds__(256) void pclgicp_fdf_kernel(const float4* __restri
         }
         return;
     }
-    gicp_block_reduce(vals, partials + size_t(blockIdx.x) * kGicpStride, 13);
+    gicp_block_reduce(vals, partials + size_t(blk) * kGicpStride, 13);
+}
+template <bool kTerms>
+__global__ __launch_bounds__(256) void pclgicp_fdf_kernel(const float4* __restrict__ src, uint32_t n, const float4* __restrict__ tgt, const int32_t* __restrict__ corr,
+                                                           const double* __restrict__ mahal, PclGicpIter it, double* __restrict__ partials, double* __restrict__ terms, uint32_t n_pad)
+{
+    pclgicp_fdf_block<kTerms>(src, n, tgt, corr, mahal, it, partials, terms, n_pad, blockIdx.x);
 }
 
 // The reference's order of additions for serial pcl::GICP (registration_method "GICP"): OptimizationFunctorWithIndices adds the terms of the
@@ -415,7 +426,8 @@ __global__ __launch_bounds__(256) void pclgicp_fdf_kernel(const float4* __restri
 // source points.  Lane c (c < 14; the fourteenth chain counts the correspondences) walks its column: 32 terms in flight, then 32 dependent adds.
 // Not parallel and meant not to be: ~4 ns per point and evaluation, which is what bit-identity with a deterministic reference costs
 // (the tree of pclgicp_fdf_kernel<false> leaves the bar on one random scene in fourteen).
-__global__ __launch_bounds__(256) void pclgicp_seqsum_kernel(const double* __restrict__ terms, uint32_t n, uint32_t n_pad, double* __restrict__ out)
+// (one workgroup's work, for the single registration's kernel and the batch's; every barrier is reached by the whole workgroup: the tile count depends on n alone)
+__device__ __forceinline__ void pclgicp_seqsum_group(const double* __restrict__ terms, uint32_t n, uint32_t n_pad, double* __restrict__ out)
 {
     // The chains are bound by the latency of a dependent f64 addition (~8 cycles) only if the terms are THERE: a lane streaming its column from
     // global memory waited a round trip per 32 terms (2.1 ms per 130k-point evaluation).  So the whole workgroup streams the next tile of 256 points
@@ -455,6 +467,10 @@ __global__ __launch_bounds__(256) void pclgicp_seqsum_kernel(const double* __res
     if (tid < 14) out[tid < 13 ? tid : 28] = acc;
     else if (tid < kGicpStride + 1 && tid - 1 != 28 && tid - 1 >= 13) out[tid - 1] = 0.0;
 }
+__global__ __launch_bounds__(256) void pclgicp_seqsum_kernel(const double* __restrict__ terms, uint32_t n, uint32_t n_pad, double* __restrict__ out)
+{
+    pclgicp_seqsum_group(terms, n, n_pad, out);
+}
 
 // pclomp::GICP (registration_method "GICP_OMP") accumulates into f_array / g_array / R_array[omp_get_thread_num()] inside `#pragma omp parallel for`
 // and adds the per-thread partials afterwards: T chains over the static chunks of the CORRESPONDENCE list (libgomp: thread t takes the
@@ -463,7 +479,7 @@ __global__ __launch_bounds__(256) void pclgicp_seqsum_kernel(const double* __res
 // pclgicp_chunk_bounds_kernel: the chunk boundaries in SOURCE-POINT space (a point without a correspondence adds +0.0 wherever it falls): bounds[t] =
 // index of the point that holds correspondence number start_t, bounds[T] = n.  Once per outer iteration: the correspondences stay while the BFGS runs.
 constexpr int kChunkMaxThreads = 16;
-__global__ __launch_bounds__(256) void pclgicp_chunk_bounds_kernel(const int32_t* __restrict__ corr, uint32_t n, int T, uint32_t* __restrict__ bounds)
+__device__ __forceinline__ void pclgicp_chunk_bounds_group(const int32_t* __restrict__ corr, uint32_t n, int T, uint32_t* __restrict__ bounds)
 {
     __shared__ uint32_t lds[8];
     __shared__ uint32_t s_start[kChunkMaxThreads + 1];
@@ -486,11 +502,15 @@ __global__ __launch_bounds__(256) void pclgicp_chunk_bounds_kernel(const int32_t
         ++rank;
     }
 }
+__global__ __launch_bounds__(256) void pclgicp_chunk_bounds_kernel(const int32_t* __restrict__ corr, uint32_t n, int T, uint32_t* __restrict__ bounds)
+{
+    pclgicp_chunk_bounds_group(corr, n, T, bounds);
+}
 // The chains.  Thread (column c, chunk t) adds its chunk's terms of column c in point order; the workgroup streams tiles of kChunkTile / T points per
 // chunk and all 14 columns into LDS (coalesced along the points) while the chains add the previous tile.  n / T dependent additions per evaluation
 // instead of n: 130k points, T = 8: ~55 us (the single chain of serial pcl::GICP: ~430 us; the tree, which matches no reference: ~10 us).
 constexpr int kChunkTile = 512;  // points per column and tile, over all chunks
-__global__ __launch_bounds__(256) void pclgicp_chunksum_kernel(const double* __restrict__ terms, uint32_t n, uint32_t n_pad, const uint32_t* __restrict__ bounds, int T, double* __restrict__ out)
+__device__ __forceinline__ void pclgicp_chunksum_group(const double* __restrict__ terms, uint32_t n, uint32_t n_pad, const uint32_t* __restrict__ bounds, int T, double* __restrict__ out)
 {
     __shared__ double   buf[2][14][kChunkTile];  // [column][chunk * L + j]
     __shared__ uint32_t s_b[kChunkMaxThreads + 1];
@@ -539,6 +559,10 @@ __global__ __launch_bounds__(256) void pclgicp_chunksum_kernel(const double* __r
         for (int k = 0; k < T; ++k) s += s_part[tid][k];  // f = std::accumulate(f_array.begin(), f_array.end(), 0.0): thread order
         out[tid < 13 ? tid : 28] = s;
     } else if (tid < kGicpStride + 1 && tid - 1 != 28 && tid - 1 >= 13) out[tid - 1] = 0.0;
+}
+__global__ __launch_bounds__(256) void pclgicp_chunksum_kernel(const double* __restrict__ terms, uint32_t n, uint32_t n_pad, const uint32_t* __restrict__ bounds, int T, double* __restrict__ out)
+{
+    pclgicp_chunksum_group(terms, n, n_pad, bounds, T, out);
 }
 
 // linearize over the correspondences of gicp_corr_kernel
@@ -860,6 +884,70 @@ __global__ __launch_bounds__(256) void icp_transform_batch_kernel(const IcpMoveD
     float  x, y, z;
     transform_point(s_T, p.x, p.y, p.z, x, y, z);  // pcl::transformPointCloud
     cur[i] = make_float4(x, y, z, p.w);
+}
+
+// ---- batched PCL GICP: blockIdx.y (or .x, one workgroup per pair) = the y-th busy pair of the round -----------------------------
+// The kernels call the per-block bodies of the single registration's kernels above: one text of the arithmetic for both.
+struct PclPairDev {  // per busy pair and round
+    const float4* cur;      // the pair's working copy: its source moved by the guess
+    const float4* tgt;
+    const double* cov_src;
+    const double* cov_tgt;
+    int32_t*      corr;
+    double*       mahal;
+    double*       terms;    // [14][n_pad]: the terms modes
+    uint32_t*     bounds;   // PCL_GICP_OMP_HIP: kChunkMaxThreads + 1 chunk boundaries
+    uint32_t      n, n_pad;
+    uint32_t      part_off;     // first block-partial record of this pair (tree mode)
+    uint32_t      target;       // index into the grid array
+    uint32_t      pair;         // index of the pair in the batch: its record is results[pair]
+    int32_t       sum_threads;  // > 1: pclomp's chunked sums over that many threads
+    uint32_t      search_order; // entry k: the k-th busy entry whose request has `search` this round
+    uint32_t      pad;
+    PclGicpIter   search;       // at transformation_ (rounds with a search)
+    PclGicpIter   eval;         // at x
+};
+
+__global__ __launch_bounds__(256) void pclgicp_corr_batch_kernel(const PclPairDev* __restrict__ busy, const NnGrid2Dev* __restrict__ grids)
+{
+    __shared__ NnGrid2Dev s_grid;
+    const PclPairDev* pr = busy + busy[blockIdx.y].search_order;
+    const uint32_t    n = pr->n;
+    if (blockIdx.x * (256u / kGicpGroup) >= n) return;  // uniform: past this pair's own blocks
+    icp_stage_grid(&s_grid, grids + pr->target);
+    __syncthreads();
+    pclgicp_corr_block(s_grid, pr->cur, n, pr->search, pr->cov_src, pr->cov_tgt, pr->corr, pr->mahal, blockIdx.x);
+}
+// behind the search, one workgroup per searching pair: the chunk boundaries of pclomp's per-thread sums over the new correspondences
+__global__ __launch_bounds__(256) void pclgicp_chunk_bounds_batch_kernel(const PclPairDev* __restrict__ busy)
+{
+    const PclPairDev* pr = busy + busy[blockIdx.x].search_order;
+    pclgicp_chunk_bounds_group(pr->corr, pr->n, pr->sum_threads, pr->bounds);
+}
+template <bool kTerms>
+__global__ __launch_bounds__(256) void pclgicp_fdf_batch_kernel(const PclPairDev* __restrict__ busy, double* __restrict__ partials)
+{
+    const PclPairDev* pr = busy + blockIdx.y;
+    const uint32_t    n = pr->n;
+    if (blockIdx.x * 256u >= n) return;  // uniform
+    pclgicp_fdf_block<kTerms>(pr->cur, n, pr->tgt, pr->corr, pr->mahal, pr->eval, partials + size_t(pr->part_off) * kGicpStride, pr->terms, pr->n_pad, blockIdx.x);
+}
+// ONE workgroup per busy pair: the chains of serial pcl::GICP / of pclomp's threads, or the fixed-order tree over the pair's block partials; the record
+// goes to (pinned host) results[pair][32]
+__global__ __launch_bounds__(256) void pclgicp_seqsum_batch_kernel(const PclPairDev* __restrict__ busy, double* __restrict__ results)
+{
+    const PclPairDev* pr = busy + blockIdx.x;
+    pclgicp_seqsum_group(pr->terms, pr->n, pr->n_pad, results + size_t(pr->pair) * kGicpStride);
+}
+__global__ __launch_bounds__(256) void pclgicp_chunksum_batch_kernel(const PclPairDev* __restrict__ busy, double* __restrict__ results)
+{
+    const PclPairDev* pr = busy + blockIdx.x;
+    pclgicp_chunksum_group(pr->terms, pr->n, pr->n_pad, pr->bounds, pr->sum_threads, results + size_t(pr->pair) * kGicpStride);
+}
+__global__ __launch_bounds__(256) void pclgicp_tree_batch_kernel(const PclPairDev* __restrict__ busy, const double* __restrict__ partials, double* __restrict__ results)
+{
+    const PclPairDev* pr = busy + blockIdx.x;
+    gicp_reduce_record(partials + size_t(pr->part_off) * kGicpStride, (pr->n + 255u) / 256u, results + size_t(pr->pair) * kGicpStride);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1468,79 +1556,8 @@ int GicpEngine::align_icp(const float guess[16])
 
 // pcl::GeneralizedIterativeClosestPoint::computeTransformation + estimateRigidTransformationBFGS (gicp_engine.h, variant 4).  Per outer
 // iteration one correspondence + Mahalanobis kernel; per functor evaluation of the inner BFGS one 14-sum kernel and a small record to the host.
-namespace {
-struct PclGicpFunctor {
-    GicpEngine* eng;
-    std::function<int(const double x[6], double* f, double g[6])> eval;  // 0 on success
-    int  status = MRGFE_OK, evaluations = 0;
-    double operator()(const double x[6]) { double f = 0, g[6]; run(x, &f, g); return f; }
-    void   df(const double x[6], double g[6]) { double f = 0; run(x, &f, g); }
-    void   fdf(const double x[6], double& f, double g[6]) { run(x, &f, g); }
-    void   run(const double x[6], double* f, double g[6])
-    {
-        ++evaluations;
-        const int rc = eval(x, f, g);
-        if (rc != MRGFE_OK && status == MRGFE_OK) status = rc;
-    }
-};
-// GeneralizedIterativeClosestPoint::applyState: t.topLeftCorner<3,3>() = Rz(x5) Ry(x4) Rx(x3) t.topLeftCorner<3,3>(); t.col(3) += (x0, x1, x2, 0); all float,
-// the rotations as Eigen::AngleAxisf::toRotationMatrix() builds them
-void angle_axis_unit_f(float angle, int axis, float R[9])
-{
-    float ax[3] = {0, 0, 0};
-    ax[axis] = 1.0f;
-    const float sn = std::sin(angle), c = std::cos(angle);
-    const float sin_axis[3] = {sn * ax[0], sn * ax[1], sn * ax[2]};
-    const float cos1_axis[3] = {(1.0f - c) * ax[0], (1.0f - c) * ax[1], (1.0f - c) * ax[2]};
-    float tmp;
-    tmp = cos1_axis[0] * ax[1]; R[1] = tmp - sin_axis[2]; R[3] = tmp + sin_axis[2];
-    tmp = cos1_axis[0] * ax[2]; R[2] = tmp + sin_axis[1]; R[6] = tmp - sin_axis[1];
-    tmp = cos1_axis[1] * ax[2]; R[5] = tmp - sin_axis[0]; R[7] = tmp + sin_axis[0];
-    R[0] = cos1_axis[0] * ax[0] + c; R[4] = cos1_axis[1] * ax[1] + c; R[8] = cos1_axis[2] * ax[2] + c;
-}
-void mul3f(const float a[9], const float b[9], float out[9])
-{
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) {
-            const float p0 = a[r * 3 + 0] * b[0 * 3 + c], p1 = a[r * 3 + 1] * b[1 * 3 + c], p2 = a[r * 3 + 2] * b[2 * 3 + c];
-            const float s = p0 + p1;
-            out[r * 3 + c] = s + p2;
-        }
-}
-void pclgicp_apply_state(float t[16], const double x[6])
-{
-    float Rx[9], Ry[9], Rz[9], Rzy[9], R[9], old[9], nw[9];
-    angle_axis_unit_f(static_cast<float>(x[5]), 2, Rz);
-    angle_axis_unit_f(static_cast<float>(x[4]), 1, Ry);
-    angle_axis_unit_f(static_cast<float>(x[3]), 0, Rx);
-    mul3f(Rz, Ry, Rzy);
-    mul3f(Rzy, Rx, R);
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) old[r * 3 + c] = t[r * 4 + c];
-    mul3f(R, old, nw);
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) t[r * 4 + c] = nw[r * 3 + c];
-    for (int r = 0; r < 3; ++r) t[r * 4 + 3] += static_cast<float>(x[r]);
-}
-// computeRDerivative: g[3..5] = tr(dR/dphi dCost_dR_T), ... for R = Rz(psi) Ry(theta) Rx(phi)
-void pclgicp_r_derivative(const double x[6], const double dC[9], double g[6])
-{
-    const double phi = x[3], theta = x[4], psi = x[5];
-    const double cphi = std::cos(phi), sphi = std::sin(phi), ctheta = std::cos(theta), stheta = std::sin(theta), cpsi = std::cos(psi), spsi = std::sin(psi);
-    const double dPhi[9] = {0, sphi * spsi + cphi * cpsi * stheta, cphi * spsi - cpsi * sphi * stheta, 0, -cpsi * sphi + cphi * spsi * stheta, -cphi * cpsi - sphi * spsi * stheta,
-                            0, cphi * ctheta, -ctheta * sphi};
-    const double dTheta[9] = {-cpsi * stheta, cpsi * ctheta * sphi, cphi * cpsi * ctheta, -spsi * stheta, ctheta * sphi * spsi, cphi * ctheta * spsi, -ctheta, -sphi * stheta, -cphi * stheta};
-    const double dPsi[9] = {-ctheta * spsi, -cphi * cpsi - sphi * spsi * stheta, cpsi * sphi - cphi * spsi * stheta, cpsi * ctheta, -cphi * spsi + cpsi * sphi * stheta,
-                            sphi * spsi + cphi * cpsi * stheta, 0, 0, 0};
-    auto inner = [&](const double A[9]) {  // matricesInnerProd(A, dCost_dR_T) = sum_ij A(j, i) dC(i, j)
-        double r = 0;
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) r += A[j * 3 + i] * dC[i * 3 + j];
-        return r;
-    };
-    g[3] = inner(dPhi);
-    g[4] = inner(dTheta);
-    g[5] = inner(dPsi);
-}
-}  // namespace
-
+// The host side — applyState, computeRDerivative, the loop over BFGS<F>, and the same loop as the batch's resumable controller — is csrc/pclgicp_ctl.h.
+//
 // serial pcl::GICP adds its cost terms in point order: 1 (default) so does PCL_GICP_HIP (pclgicp_seqsum_kernel), 0 the tree sums of round 3
 // (MRGFE_PCLGICP_TREE_SUMS=1; mrgfe_dbg_set_pclgicp_reference_order).  PCL_GICP_OMP_HIP always sums in a tree: pclomp's own per-thread sums have no fixed order.
 static std::atomic<int> g_pclgicp_ref_order{-1};
@@ -1556,51 +1573,88 @@ int gicp_set_pcl_reference_order(int mode)
     return pclgicp_reference_order_mode();
 }
 
-int GicpEngine::pcl_evaluate(const float T_rowmajor[16], const float guess_rowmajor[16], const float4* d_pts, bool search, const double x[6], double* f, double g[6], int* n_corr)
+// how the 13 sums of an evaluation are formed: 0 one chain in point order (serial pcl::GICP), 1 pclomp's chunked chains, 2 the block tree
+static int pclgicp_sum_mode(const GicpParams& prm)
 {
-    hipStream_t    st = ctx_->stream;
-    const uint32_t n = static_cast<uint32_t>(n_src_), nblk = (n + 255) / 256;
-    *f = 0;
-    for (int k = 0; k < 6; ++k) g[k] = 0;
-    if (n_corr) *n_corr = 0;
-    if (n == 0 || n_tgt_ == 0) return MRGFE_OK;
+    if (prm.pcl_reference_order_sums && pclgicp_reference_order_mode()) return 0;
+    if (prm.pcl_omp_sum_threads > 1 && pclgicp_reference_order_mode()) return 1;
+    return 2;
+}
+// the search of an outer iteration at transformation_ = T: the float matrix the queries are moved by, R = rotation of T * guess (double), the squared gate
+static PclGicpIter pclgicp_search_iter(const float T_rowmajor[16], const float guess_rowmajor[16], double max_corr_dist)
+{
     PclGicpIter it;
-    if (search) {  // the outer iteration's correspondences and Mahalanobis matrices at transformation_ = T
-        for (int k = 0; k < 12; ++k) it.Tf[k] = T_rowmajor[k];
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                double s = 0;
-                for (int k = 0; k < 4; ++k) s += static_cast<double>(T_rowmajor[i * 4 + k]) * static_cast<double>(guess_rowmajor[k * 4 + j]);
-                it.R[i * 3 + j] = s;
-            }
-        it.thr2 = prm_.max_corr_dist * prm_.max_corr_dist;
-        constexpr uint32_t per_blk = 256u / kGicpGroup;
-        hipLaunchKernelGGL(pclgicp_corr_kernel, dim3((n + per_blk - 1) / per_blk), dim3(256), 0, st, tgt_grid_.dev2(), d_pts, n, it, d_src_cov_.as<double>(), d_tgt_cov_.as<double>(),
-                           d_corr_.as<int32_t>(), d_mahal_.as<double>());
-        MRGFE_HIP_CHECK(hipGetLastError());
-        if (prm_.pcl_omp_sum_threads > 1) {  // the chunk boundaries of pclomp's per-thread sums belong to these correspondences
-            MRGFE_TRY(d_chunk_bounds_.ensure(sizeof(uint32_t) * (kChunkMaxThreads + 1)));
-            hipLaunchKernelGGL(pclgicp_chunk_bounds_kernel, dim3(1), dim3(256), 0, st, d_corr_.as<int32_t>(), n, prm_.pcl_omp_sum_threads, d_chunk_bounds_.as<uint32_t>());
-            MRGFE_HIP_CHECK(hipGetLastError());
+    for (int k = 0; k < 12; ++k) it.Tf[k] = T_rowmajor[k];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double s = 0;
+            for (int k = 0; k < 4; ++k) s += static_cast<double>(T_rowmajor[i * 4 + k]) * static_cast<double>(guess_rowmajor[k * 4 + j]);
+            it.R[i * 3 + j] = s;
         }
-        if (!x) return MRGFE_OK;
-    }
+    it.thr2 = max_corr_dist * max_corr_dist;
+    return it;
+}
+// the functor at x: applyState on base_transformation_ = Identity
+static PclGicpIter pclgicp_eval_iter(const double x[6])
+{
+    PclGicpIter it;
     float Tx[16];
-    for (int i = 0; i < 16; ++i) Tx[i] = (i % 5 == 0) ? 1.0f : 0.0f;  // base_transformation_ = Identity
+    pclgicp_identity(Tx);
     pclgicp_apply_state(Tx, x);
     for (int k = 0; k < 12; ++k) it.Tf[k] = Tx[k];
     for (int k = 0; k < 9; ++k) it.R[k] = 0;
     it.thr2 = 0;
+    return it;
+}
+static PclGicpCtlParams pclgicp_ctl_params(const GicpParams& prm)
+{
+    PclGicpCtlParams c;
+    c.max_iterations = prm.max_iterations;
+    c.max_inner_iterations = prm.max_inner_iterations;
+    c.trans_eps = prm.trans_eps;
+    c.rot_eps = prm.rot_eps;
+    c.whole_gradient_norm = prm.pcl_whole_gradient_norm;
+    return c;
+}
+
+// the outer iteration's correspondences and Mahalanobis matrices at transformation_ = T (and, for pclomp's sums, the chunk boundaries that belong to them)
+int GicpEngine::pcl_search(const float T_rowmajor[16], const float guess_rowmajor[16], const float4* d_pts)
+{
+    hipStream_t    st = ctx_->stream;
+    const uint32_t n = static_cast<uint32_t>(n_src_);
+    if (n == 0 || n_tgt_ == 0) return MRGFE_OK;
+    const PclGicpIter it = pclgicp_search_iter(T_rowmajor, guess_rowmajor, prm_.max_corr_dist);
+    constexpr uint32_t per_blk = 256u / kGicpGroup;
+    hipLaunchKernelGGL(pclgicp_corr_kernel, dim3((n + per_blk - 1) / per_blk), dim3(256), 0, st, tgt_grid_.dev2(), d_pts, n, it, d_src_cov_.as<double>(), d_tgt_cov_.as<double>(),
+                       d_corr_.as<int32_t>(), d_mahal_.as<double>());
+    MRGFE_HIP_CHECK(hipGetLastError());
+    if (prm_.pcl_omp_sum_threads > 1) {  // the chunk boundaries of pclomp's per-thread sums belong to these correspondences
+        MRGFE_TRY(d_chunk_bounds_.ensure(sizeof(uint32_t) * (kChunkMaxThreads + 1)));
+        hipLaunchKernelGGL(pclgicp_chunk_bounds_kernel, dim3(1), dim3(256), 0, st, d_corr_.as<int32_t>(), n, prm_.pcl_omp_sum_threads, d_chunk_bounds_.as<uint32_t>());
+        MRGFE_HIP_CHECK(hipGetLastError());
+    }
+    return MRGFE_OK;
+}
+
+// the raw record of the functor of estimateRigidTransformationBFGS at x over the stored correspondences: r[0] cost sum, r[1..3], r[4..12], r[28] correspondences
+int GicpEngine::pcl_record(const float4* d_pts, const double x[6], double r[32])
+{
+    hipStream_t    st = ctx_->stream;
+    const uint32_t n = static_cast<uint32_t>(n_src_), nblk = (n + 255) / 256;
+    for (int k = 0; k < kGicpStride; ++k) r[k] = 0;
+    if (n == 0 || n_tgt_ == 0) return MRGFE_OK;
+    const PclGicpIter it = pclgicp_eval_iter(x);
     double* d_part = d_partial_.as<double>();
     double* d_res = d_part + size_t(nblk) * kGicpStride;
     MRGFE_HIP_CHECK(hipEventRecord(ctx_->ev0, st));
-    if (prm_.pcl_reference_order_sums && pclgicp_reference_order_mode()) {
+    const int mode = pclgicp_sum_mode(prm_);
+    if (mode == 0) {
         const uint32_t n_pad = (n + 1u) & ~1u;
         MRGFE_TRY(d_terms_.ensure(sizeof(double) * 14 * size_t(n_pad)));
         hipLaunchKernelGGL(pclgicp_fdf_kernel<true>, dim3(nblk), dim3(256), 0, st, d_pts, n, d_tgt_, d_corr_.as<int32_t>(), d_mahal_.as<double>(), it, d_part, d_terms_.as<double>(), n_pad);
         hipLaunchKernelGGL(pclgicp_seqsum_kernel, dim3(1), dim3(256), 0, st, d_terms_.as<double>(), n, n_pad, d_res);
         MRGFE_HIP_CHECK(hipEventRecord(ctx_->ev1, st));
-    } else if (prm_.pcl_omp_sum_threads > 1 && pclgicp_reference_order_mode()) {
+    } else if (mode == 1) {
         // pclomp::GICP for T = pcl_omp_sum_threads OpenMP threads: T chains over the static chunks of the correspondence list, partials in thread order
         const uint32_t n_pad = (n + 1u) & ~1u;
         const int      T = prm_.pcl_omp_sum_threads;
@@ -1616,22 +1670,28 @@ int GicpEngine::pcl_evaluate(const float T_rowmajor[16], const float guess_rowma
         hipLaunchKernelGGL(gicp_reduce_kernel, dim3(1), dim3(256), 0, st, d_part, nblk, d_res);
     }
     MRGFE_HIP_CHECK(hipGetLastError());
-    double r[kGicpStride];
-    MRGFE_HIP_CHECK(hipMemcpyAsync(r, d_res, sizeof(r), hipMemcpyDeviceToHost, st));
+    MRGFE_HIP_CHECK(hipMemcpyAsync(r, d_res, sizeof(double) * kGicpStride, hipMemcpyDeviceToHost, st));
     MRGFE_HIP_CHECK(hipStreamSynchronize(st));
     float ms = 0;
     MRGFE_HIP_CHECK(hipEventElapsedTime(&ms, ctx_->ev0, ctx_->ev1));
     kernel_ms += ms;
     kernel_launches += 1;
     kernel_alg_bytes += double(n) * (16 + 4) + r[28] * (16 + 72);
-    const double m = r[28];
-    if (n_corr) *n_corr = static_cast<int>(m);
-    if (m <= 0) return MRGFE_OK;
-    *f = r[0] / m;
-    for (int k = 0; k < 3; ++k) g[k] = r[1 + k] * (2.0 / m);
-    double dC[9];
-    for (int k = 0; k < 9; ++k) dC[k] = r[4 + k] * (2.0 / m);
-    pclgicp_r_derivative(x, dC, g);
+    return MRGFE_OK;
+}
+
+int GicpEngine::pcl_evaluate(const float T_rowmajor[16], const float guess_rowmajor[16], const float4* d_pts, bool search, const double x[6], double* f, double g[6], int* n_corr)
+{
+    *f = 0;
+    for (int k = 0; k < 6; ++k) g[k] = 0;
+    if (n_corr) *n_corr = 0;
+    if (search) MRGFE_TRY(pcl_search(T_rowmajor, guess_rowmajor, d_pts));
+    if (!x) return MRGFE_OK;
+    double r[kGicpStride];
+    MRGFE_TRY(pcl_record(d_pts, x, r));
+    int m = 0;
+    pclgicp_normalise(r, x, f, g, &m);
+    if (n_corr) *n_corr = m;
     return MRGFE_OK;
 }
 
@@ -1644,8 +1704,7 @@ int GicpEngine::align_pcl_gicp(const float guess[16])
     converged_ = false;
     nr_iterations_ = 0;
     for (int t = 0; t < 36; ++t) final_hessian_[t] = 0.0;
-    float transformation[16], previous[16];
-    for (int i = 0; i < 16; ++i) transformation[i] = previous[i] = final_[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+    pclgicp_identity(final_);
     const uint32_t n = static_cast<uint32_t>(n_src_);
     // pcl::Registration::align copies the source into `output`; computeTransformation moves it by the guess (pcl::transformPointCloud)
     MRGFE_TRY(d_cur_.ensure(std::max<size_t>(n_src_, 1) * 16));
@@ -1658,63 +1717,21 @@ int GicpEngine::align_pcl_gicp(const float guess[16])
         MRGFE_HIP_CHECK(hipGetLastError());
         MRGFE_HIP_CHECK(hipStreamSynchronize(st));
     }
-    while (!converged_ && n > 0) {
-        double f0 = 0, g0[6];
-        int    m = 0;
-        MRGFE_TRY(pcl_evaluate(transformation, guess, d_out, true, nullptr, &f0, g0, nullptr));  // the search loop of this iteration
-        std::memcpy(previous, transformation, sizeof(previous));
-        // ---- estimateRigidTransformationBFGS
-        // x[3] = std::atan2(T(2,1), T(2,2)) and x[5] = std::atan2(T(1,0), T(0,0)) on floats, x[4] = asin(-T(2,0)) through the C function (double)
-        double x[6] = {transformation[3], transformation[7], transformation[11], static_cast<double>(std::atan2(transformation[9], transformation[10])),
-                       std::asin(static_cast<double>(-transformation[8])), static_cast<double>(std::atan2(transformation[4], transformation[0]))};
-        PclGicpFunctor fn;
-        fn.eng = this;
-        fn.eval = [&](const double xx[6], double* f, double g[6]) { return pcl_evaluate(nullptr, nullptr, d_out, false, xx, f, g, &m); };
-        // NotEnoughPointsException when fewer than four correspondences: known after the first evaluation (the count comes back with every record)
-        BFGS<PclGicpFunctor> bfgs(fn);
-        int inner = 0;
-        BFGSSpace::Status result = bfgs.minimizeInit(x);
-        MRGFE_TRY(fn.status);
-        if (m < 4) break;
-        result = BFGSSpace::Running;
-        do {
-            ++inner;
-            result = bfgs.minimizeOneStep(x);
-            MRGFE_TRY(fn.status);
-            if (result) break;
-            // testGradient -> OptimizationFunctorWithIndices::checkGradient (PCL >= 1.11: translation and rotation parts apart; pclomp: the whole norm)
-            const double* gr = bfgs.gradient;
-            const double gt = std::sqrt(gr[0] * gr[0] + gr[1] * gr[1] + gr[2] * gr[2]), grn = std::sqrt(gr[3] * gr[3] + gr[4] * gr[4] + gr[5] * gr[5]);
-            const bool ok = prm_.pcl_whole_gradient_norm ? std::sqrt(gt * gt + grn * grn) < 1e-2 : (gt < 1e-2 && grn < 1e-2);
-            result = ok ? BFGSSpace::Success : BFGSSpace::Running;
-        } while (result == BFGSSpace::Running && inner < prm_.max_inner_iterations);
-        n_error_ += fn.evaluations;
-        n_linearize_ += 1;
-        if (result == BFGSSpace::NoProgress || result == BFGSSpace::Success || inner == prm_.max_inner_iterations) {
-            for (int i = 0; i < 16; ++i) transformation[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-            pclgicp_apply_state(transformation, x);
-        } else {
-            break;  // SolverDidntConvergeException
-        }
-        double delta = 0;
-        for (int k = 0; k < 4; ++k)
-            for (int l = 0; l < 4; ++l) {
-                const double ratio = (k < 3 && l < 3) ? 1.0 / prm_.rot_eps : 1.0 / prm_.trans_eps;
-                const double c_delta = ratio * std::fabs(static_cast<double>(previous[k * 4 + l] - transformation[k * 4 + l]));
-                if (c_delta > delta) delta = c_delta;
-            }
-        ++nr_iterations_;
-        if (nr_iterations_ >= prm_.max_iterations || delta < 1) {
-            converged_ = true;
-            std::memcpy(previous, transformation, sizeof(previous));
-        }
-    }
-    for (int r = 0; r < 4; ++r)  // final_transformation_ = previous_transformation_ * guess (float)
-        for (int c = 0; c < 4; ++c) {
-            float s = 0;
-            for (int k = 0; k < 4; ++k) s += previous[r * 4 + k] * guess[k * 4 + c];
-            final_[r * 4 + c] = s;
-        }
+    // the host loop (pclgicp_ctl.h: BFGS<F> over the GPU sums), every functor evaluation one launch pair and one host wait
+    struct Evaluator {
+        GicpEngine*   eng;
+        const float*  guess;
+        const float4* d_out;
+        int search(const float T[16]) { return eng->pcl_search(T, guess, d_out); }
+        int evaluate(const double x[6], double r[kGicpStride]) { return eng->pcl_record(d_out, x, r); }
+    } ev{this, guess, d_out};
+    PclGicpOutcome out;
+    MRGFE_TRY(pclgicp_align_host(pclgicp_ctl_params(prm_), guess, n, ev, out));
+    n_error_ = out.n_functor;
+    n_linearize_ = out.n_search;
+    converged_ = out.converged;
+    nr_iterations_ = out.iterations;
+    std::memcpy(final_, out.final_rm, sizeof(final_));
     return MRGFE_OK;
 }
 
@@ -1884,32 +1901,13 @@ GicpBatch::~GicpBatch()
     if (ctx_) (void)hipSetDevice(ctx_->device);  // the members free themselves on the batch's device
 }
 
-int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, const PairBook& book, std::vector<GicpBatchPair>& pairs)
+// Source covariances: one cloud is a chain of small launches and a few host round trips (bounding box, cell-size
+// passes, sorts, k-NN, covariance) that leaves most of the chip idle, so `lanes` host threads work through the clouds
+// side by side, each on its own stream and workspace.  pcl_moments: PCL's form (pclgicp_cov_kernel) for PCL_GICP_HIP.
+int GicpBatch::source_covariances(std::vector<std::unique_ptr<GicpEngine>>& engines, const PairBook& book, std::vector<GicpBatchPair>& pairs, bool pcl_moments)
 {
-    MRGFE_TRY(ctx_->bind());
-    const int P = book.n_pairs();  // (pairs[i] holds the buffers and controllers of the book's pair i)
-    if (P == 0) return MRGFE_OK;
-    hipStream_t st = ctx_->stream;
-    if (!done_) MRGFE_HIP_CHECK(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
-    // targets: covariances + correspondence grid once each; sources: covariances cloud by cloud
-    std::vector<NnGrid2Dev> h_grids(engines.size());
-    std::vector<VoxGridDev> h_vgrids(engines.size());
-    bool voxel = false;  // VGICP: the targets are voxel maps, the correspondence search is a table lookup
-    for (size_t t = 0; t < engines.size(); ++t) {
-        if (!engines[t]) continue;
-        MRGFE_TRY(engines[t]->prepare_target());
-        h_grids[t] = engines[t]->target_grid();
-        voxel = engines[t]->params().variant == 2;
-        if (voxel) {
-            VoxGridDev& g = h_vgrids[t];
-            engines[t]->voxel_grid(&g.res, g.cmin, g.dim, &g.n_cells);
-            g.vox = engines[t]->voxel_records();
-        }
-    }
-    // Source covariances: one cloud is a chain of small launches and a few host round trips (bounding box, cell-size
-    // passes, sorts, k-NN, covariance) that leaves most of the chip idle, so `lanes` host threads work through the clouds
-    // side by side, each on its own stream and workspace.
-    MRGFE_HIP_CHECK(hipStreamSynchronize(st));  // the clouds were uploaded on this stream
+    const int P = book.n_pairs();
+    MRGFE_HIP_CHECK(hipStreamSynchronize(ctx_->stream));  // the clouds were uploaded on this stream
     {
         int want = 4;
         if (const char* e = std::getenv("MRGFE_GICP_LANES")) want = std::atoi(e);
@@ -1964,7 +1962,7 @@ int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, cons
                     GicpBatchPair&        p = pairs[todo[w]];
                     const PairBook::Pair& bp = book.pair(todo[w]);
                     const int k = engines[bp.target]->params().k_correspondences;
-                    rc = gicp_covariances_on_grid(l.ctx.get(), k, bp.d_src, bp.n, p.ext_cov ? *p.ext_cov : p.cov, l.views[w - w0], l.knn_i, l.knn_d, false);
+                    rc = gicp_covariances_on_grid(l.ctx.get(), k, bp.d_src, bp.n, p.ext_cov ? *p.ext_cov : p.cov, l.views[w - w0], l.knn_i, l.knn_d, pcl_moments);
                     if (rc == MRGFE_OK && p.ext_cov) *p.ext_cov_k = k;
                 }
                 if (rc != MRGFE_OK) { status[li] = rc; message[li] = mrgfe_last_error(); break; }
@@ -1979,6 +1977,32 @@ int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, cons
         for (int li = 0; li < n_lanes; ++li)
             if (status[li] != MRGFE_OK) { set_error("GICP batch: source covariances failed: %s", message[li].c_str()); return status[li]; }
     }
+    return MRGFE_OK;
+}
+
+int GicpBatch::align_all(std::vector<std::unique_ptr<GicpEngine>>& engines, const PairBook& book, std::vector<GicpBatchPair>& pairs)
+{
+    MRGFE_TRY(ctx_->bind());
+    const int P = book.n_pairs();  // (pairs[i] holds the buffers and controllers of the book's pair i)
+    if (P == 0) return MRGFE_OK;
+    hipStream_t st = ctx_->stream;
+    if (!done_) MRGFE_HIP_CHECK(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
+    // targets: covariances + correspondence grid once each; sources: covariances cloud by cloud
+    std::vector<NnGrid2Dev> h_grids(engines.size());
+    std::vector<VoxGridDev> h_vgrids(engines.size());
+    bool voxel = false;  // VGICP: the targets are voxel maps, the correspondence search is a table lookup
+    for (size_t t = 0; t < engines.size(); ++t) {
+        if (!engines[t]) continue;
+        MRGFE_TRY(engines[t]->prepare_target());
+        h_grids[t] = engines[t]->target_grid();
+        voxel = engines[t]->params().variant == 2;
+        if (voxel) {
+            VoxGridDev& g = h_vgrids[t];
+            engines[t]->voxel_grid(&g.res, g.cmin, g.dim, &g.n_cells);
+            g.vox = engines[t]->voxel_records();
+        }
+    }
+    MRGFE_TRY(source_covariances(engines, book, pairs, false));
     std::vector<GicpPairDev> h_pairs(P);
     uint32_t part = 0, max_n = 0;
     for (int i = 0; i < P; ++i) {
@@ -2237,6 +2261,162 @@ int GicpBatch::align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, 
         MRGFE_TRY(move(who, false));
     }
     set_error("ICP batch did not terminate within %d rounds", round_cap);
+    return MRGFE_ERR_STATE;
+}
+
+// ---- batched PCL GICP rounds -------------------------------------------------------------------------------------------------------------
+int GicpBatch::align_all_pcl(std::vector<std::unique_ptr<GicpEngine>>& engines, const PairBook& book, std::vector<GicpBatchPair>& pairs)
+{
+    MRGFE_TRY(ctx_->bind());
+    rounds_ = 0;
+    const int P = book.n_pairs();  // (pairs[i] holds the buffers and controllers of the book's pair i)
+    if (P == 0) return MRGFE_OK;
+    hipStream_t st = ctx_->stream;
+    if (!done_) MRGFE_HIP_CHECK(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
+    const GicpParams&      prm = engines[book.pair(0).target]->params();
+    const PclGicpCtlParams cprm = pclgicp_ctl_params(prm);
+    const int              mode = pclgicp_sum_mode(prm);  // one mode per align: every pair of a batch has the batch's parameters
+    // targets: PCL's covariances and the correspondence grid once each, kept in the engines (across mrgfe_batch_clear_pairs too)
+    std::vector<NnGrid2Dev> h_grids(std::max<size_t>(engines.size(), 1));
+    std::memset(static_cast<void*>(h_grids.data()), 0, sizeof(NnGrid2Dev) * h_grids.size());
+    for (size_t t = 0; t < engines.size(); ++t) {
+        if (!engines[t]) continue;
+        MRGFE_TRY(engines[t]->prepare_target());
+        h_grids[t] = engines[t]->target_grid();
+    }
+    // sources: PCL's covariances of the ORIGINAL clouds (computeCovariances runs before the guess is applied), on the lanes of align_all or out of the keyframe store
+    MRGFE_TRY(source_covariances(engines, book, pairs, true));
+    // per pair: the working copy, correspondences, Mahalanobis matrices, terms (grow-only), the slice of the block partials, the controller
+    uint32_t part = 0;
+    std::vector<uint32_t> part_off(P);
+    for (int i = 0; i < P; ++i) {
+        GicpBatchPair&        p = pairs[i];
+        const PairBook::Pair& bp = book.pair(i);
+        const size_t          ns = std::max<size_t>(bp.n, 1), n_pad = (size_t(bp.n) + 1u) & ~size_t(1);
+        MRGFE_TRY(p.cur.ensure(ns * 16));
+        MRGFE_TRY(p.corr.ensure(ns * 4));
+        MRGFE_TRY(p.mahal.ensure(ns * 72));
+        if (mode != 2) MRGFE_TRY(p.terms.ensure(sizeof(double) * 14 * std::max<size_t>(n_pad, 2)));
+        if (mode == 1) MRGFE_TRY(p.bounds.ensure(sizeof(uint32_t) * (kChunkMaxThreads + 1)));
+        part_off[i] = part;
+        if (mode == 2) part += (bp.n + 255u) / 256u;
+        p.pcl.start(cprm, bp.guess, bp.n, static_cast<uint32_t>(engines[bp.target]->target_size()));
+    }
+    MRGFE_TRY(d_grids_.ensure(sizeof(NnGrid2Dev) * h_grids.size()));
+    MRGFE_TRY(d_partials_.ensure(sizeof(double) * kGicpStride * std::max<uint32_t>(part, 1)));
+    MRGFE_TRY(d_busy_.ensure(sizeof(PclPairDev) * P));
+    MRGFE_TRY(d_moves_.ensure(sizeof(IcpMoveDev) * P));
+    MRGFE_TRY(h_busy_.ensure(sizeof(PclPairDev) * P * 2));
+    MRGFE_TRY(h_moves_.ensure(sizeof(IcpMoveDev) * P));
+    MRGFE_TRY(h_results_.ensure(sizeof(double) * kGicpStride * P));
+    MRGFE_HIP_CHECK(hipMemcpyAsync(d_grids_.p, h_grids.data(), sizeof(NnGrid2Dev) * h_grids.size(), hipMemcpyHostToDevice, st));
+    // the working copies = the sources moved by the guess (pcl::transformPointCloud, the identity included, as the single registration does): one launch
+    {
+        IcpMoveDev* hm = h_moves_.as<IcpMoveDev>();
+        uint32_t    M = 0, widest = 0;
+        for (int i = 0; i < P; ++i) {
+            GicpBatchPair&        p = pairs[i];
+            const PairBook::Pair& bp = book.pair(i);
+            if (p.pcl.done() || p.pcl.degenerate()) continue;
+            MRGFE_HIP_CHECK(hipMemcpyAsync(p.cur.p, bp.d_src, size_t(bp.n) * 16, hipMemcpyDeviceToDevice, st));
+            hm[M].cur = p.cur.as<float4>();
+            hm[M].n = bp.n;
+            hm[M].pad = 0;
+            std::memcpy(hm[M].T12, bp.guess, sizeof(hm[M].T12));
+            widest = std::max(widest, bp.n);
+            ++M;
+        }
+        if (M) {
+            MRGFE_HIP_CHECK(hipMemcpyAsync(d_moves_.p, hm, sizeof(IcpMoveDev) * M, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(icp_transform_batch_kernel, dim3((widest + 255) / 256, M), dim3(256), 0, st, d_moves_.as<IcpMoveDev>());
+            MRGFE_HIP_CHECK(hipGetLastError());
+        }
+    }
+    MRGFE_HIP_CHECK(hipEventRecord(done_, st));
+    MRGFE_HIP_CHECK(hipEventSynchronize(done_));  // h_grids is a local
+    double*           hr = h_results_.as<double>();
+    const PclPairDev* d_busy = d_busy_.as<PclPairDev>();
+    std::vector<int>  busy;
+    const double      zeros[kGicpStride] = {0};
+    // every request is one round; a line search asks at most bracket_iters + section_iters times, an outer iteration adds minimizeInit and updatePosition
+    const int64_t cap64 = int64_t(std::max(prm.max_iterations, 1)) * (int64_t(std::max(prm.max_inner_iterations, 1)) * PclGicpController::line_search_iterations() + 2);
+    const int     round_cap = static_cast<int>(std::min<int64_t>(cap64, 0x7fffffff));
+    int           half = 0;
+    for (int round = 0; round < round_cap; ++round) {
+        half ^= 1;
+        busy.clear();
+        for (int i = 0; i < P; ++i) {
+            PclGicpController& c = pairs[i].pcl;
+            if (c.done()) continue;
+            if (c.degenerate()) c.on_result(zeros);  // an empty target: nothing to search, the loop ends on an all-zero record, as in the single engine
+            else busy.push_back(i);
+        }
+        if (busy.empty()) {
+            bool all_done = true;
+            for (int i = 0; i < P; ++i) all_done = all_done && pairs[i].pcl.done();
+            if (all_done) return MRGFE_OK;
+            continue;
+        }
+        ++rounds_;
+        const uint32_t B = static_cast<uint32_t>(busy.size());
+        // the pair table of this round goes up from the pinned half of this parity (the device has long read it when the host writes it again: every round waits)
+        PclPairDev* hb = h_busy_.as<PclPairDev>() + size_t(half) * P;
+        uint32_t    widest = 0, widest_search = 0, n_search = 0;
+        for (uint32_t w = 0; w < B; ++w) {
+            const int             i = busy[w];
+            GicpBatchPair&        p = pairs[i];
+            const PairBook::Pair& bp = book.pair(i);
+            const PclGicpRequest& rq = p.pcl.request();
+            GicpEngine*           e = engines[bp.target].get();
+            PclPairDev&           d = hb[w];
+            d.cur = p.cur.as<float4>();
+            d.tgt = e->target_points();
+            d.cov_src = (p.ext_cov ? *p.ext_cov : p.cov).as<double>();
+            d.cov_tgt = e->target_covariances();
+            d.corr = p.corr.as<int32_t>();
+            d.mahal = p.mahal.as<double>();
+            d.terms = mode != 2 ? p.terms.as<double>() : nullptr;
+            d.bounds = mode == 1 ? p.bounds.as<uint32_t>() : nullptr;
+            d.n = bp.n;
+            d.n_pad = mode != 2 ? ((bp.n + 1u) & ~1u) : 0u;
+            d.part_off = part_off[i];
+            d.target = static_cast<uint32_t>(bp.target);
+            d.pair = static_cast<uint32_t>(i);
+            d.sum_threads = prm.pcl_omp_sum_threads;
+            d.pad = 0;
+            if (rq.search) {
+                d.search = pclgicp_search_iter(rq.T, bp.guess, prm.max_corr_dist);
+                hb[n_search++].search_order = w;
+                widest_search = std::max(widest_search, bp.n);
+            } else {
+                std::memset(static_cast<void*>(&d.search), 0, sizeof(d.search));
+            }
+            d.eval = pclgicp_eval_iter(rq.x);
+            widest = std::max(widest, bp.n);
+        }
+        for (uint32_t w = n_search; w < B; ++w) hb[w].search_order = 0;
+        MRGFE_HIP_CHECK(hipMemcpyAsync(d_busy_.p, hb, sizeof(PclPairDev) * B, hipMemcpyHostToDevice, st));
+        if (n_search) {  // a search never costs a round of its own: the x of minimizeInit came with the request
+            constexpr uint32_t per_blk = 256u / kGicpGroup;
+            hipLaunchKernelGGL(pclgicp_corr_batch_kernel, dim3((widest_search + per_blk - 1) / per_blk, n_search), dim3(256), 0, st, d_busy, d_grids_.as<NnGrid2Dev>());
+            // (the chunk boundaries of pclomp's sums belong to these correspondences; the tree mode reads none, and its pairs have no `bounds`)
+            if (mode == 1) hipLaunchKernelGGL(pclgicp_chunk_bounds_batch_kernel, dim3(n_search), dim3(256), 0, st, d_busy);
+        }
+        const dim3 grid((widest + 255) / 256, B);
+        if (mode == 2) {
+            hipLaunchKernelGGL(pclgicp_fdf_batch_kernel<false>, grid, dim3(256), 0, st, d_busy, d_partials_.as<double>());
+            hipLaunchKernelGGL(pclgicp_tree_batch_kernel, dim3(B), dim3(256), 0, st, d_busy, d_partials_.as<double>(), hr);
+        } else {
+            hipLaunchKernelGGL(pclgicp_fdf_batch_kernel<true>, grid, dim3(256), 0, st, d_busy, d_partials_.as<double>());
+            if (mode == 0) hipLaunchKernelGGL(pclgicp_seqsum_batch_kernel, dim3(B), dim3(256), 0, st, d_busy, hr);
+            else           hipLaunchKernelGGL(pclgicp_chunksum_batch_kernel, dim3(B), dim3(256), 0, st, d_busy, hr);
+        }
+        MRGFE_HIP_CHECK(hipGetLastError());
+        MRGFE_HIP_CHECK(hipEventRecord(done_, st));
+        MRGFE_HIP_CHECK(hipEventSynchronize(done_));  // the round's one wait
+        for (uint32_t w = 0; w < B; ++w) pairs[busy[w]].pcl.on_result(hr + size_t(busy[w]) * kGicpStride);
+    }
+    set_error("PCL GICP batch did not terminate within %d rounds", round_cap);
     return MRGFE_ERR_STATE;
 }
 

@@ -8,6 +8,7 @@
 
 #include "nn_grid.h"
 #include "pair_book.h"
+#include "pclgicp_ctl.h"
 
 namespace mrgfe {
 
@@ -123,6 +124,9 @@ class GicpEngine {
     // PCL_GICP_HIP: (search) the correspondences + Mahalanobis matrices at transformation_ = T with `guess`, and / or (x != NULL) the functor of
     // estimateRigidTransformationBFGS at x over the stored correspondences of the points d_pts: f, g[6], number of correspondences
     int pcl_evaluate(const float T_rowmajor[16], const float guess_rowmajor[16], const float4* d_pts, bool search, const double x[6], double* f, double g[6], int* n_corr);
+    // ... its two halves, which the host loop of pclgicp_ctl.h drives: the search, and the raw 14-sum record at x (r[0] cost sum, r[1..3], r[4..12], r[28] correspondences)
+    int pcl_search(const float T_rowmajor[16], const float guess_rowmajor[16], const float4* d_pts);
+    int pcl_record(const float4* d_pts, const double x[6], double r[32]);
     const float4* source_points() const { return d_src_; }
    private:
     DevBuf   d_chunk_bounds_;  // PCL_GICP_OMP_HIP: the chunk boundaries (source-point indices) of pclomp's per-thread sums for the current correspondences
@@ -204,6 +208,9 @@ struct GicpBatchPair {
     DevBuf        cov, corr, mahal;
     DevBuf        cur;  // ICP_HIP: the source as transformed so far (n * 16 bytes)
     IcpController icp;  // ICP_HIP
+    // PCL_GICP_HIP / PCL_GICP_OMP_HIP: the working copy is `cur`; the per-point terms of an evaluation (112 bytes per point, terms modes), pclomp's chunk boundaries
+    DevBuf            terms, bounds;
+    PclGicpController pcl;
     // keyframe store (batch.cpp): covariances kept with the cloud; *ext_cov_k == k_correspondences means they are valid
     DevBuf*       ext_cov = nullptr;
     int*          ext_cov_k = nullptr;
@@ -218,7 +225,12 @@ class GicpBatch {
     // ICP_HIP: the pairs' ICP loops in lock step — per round one correspondence + moment launch and one reduction over the pairs still running, ONE host
     // wait for their records, the controllers' steps, one transform launch.  No covariances; the records are those of GicpEngine::align_icp, bit for bit.
     int align_all_icp(std::vector<std::unique_ptr<GicpEngine>>& engines, const PairBook& book, std::vector<GicpBatchPair>& pairs);
-    int rounds() const { return rounds_; }  // of the last align_all_icp
+    // PCL_GICP_HIP / PCL_GICP_OMP_HIP: the pairs' BFGS loops in lock step — every round the requests of the controllers still running (PclGicpController:
+    // where BFGS<F> would call its functor next), the searches of the pairs that begin an outer iteration, one cost / gradient launch and one sum launch
+    // (ONE workgroup per pair: the chains are sequential per pair and independent between pairs), ONE host wait.  The records are those of
+    // GicpEngine::align_pcl_gicp, bit for bit: the kernels call the same per-block bodies, the controllers make the same decisions.
+    int align_all_pcl(std::vector<std::unique_ptr<GicpEngine>>& engines, const PairBook& book, std::vector<GicpBatchPair>& pairs);
+    int rounds() const { return rounds_; }  // of the last align_all_icp / align_all_pcl
 
    private:
     mrgfe_ctx* ctx_;
@@ -229,6 +241,7 @@ class GicpBatch {
     PinBuf h_evals_, h_results_;
     // ICP_HIP: the busy list and the transforms of a round go up from pinned memory (two halves, used in turn) into d_busy_ / d_moves_
     PinBuf    h_busy_, h_moves_;
+    int source_covariances(std::vector<std::unique_ptr<GicpEngine>>& engines, const PairBook& book, std::vector<GicpBatchPair>& pairs, bool pcl_moments);
     DevBuf    d_busy_, d_moves_;
     NnGridSet tgt_set_, cur_set_;  // exact-NN grids of several new targets; of the busy pairs' working copies (reciprocal correspondences)
     std::vector<NnGrid> tgt_views_, cur_views_;

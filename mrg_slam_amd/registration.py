@@ -432,7 +432,9 @@ def select_registration_method(params: dict, ctx: Context | None = None) -> HipR
 class BatchMatcher:
     """Batched candidate matching: the candidate loop of LoopDetector::matching (src/mrg_slam/loop_detector.cpp:126-145)
     advanced for all candidates at once on one GPU (mrgfe_batch_*).  ``params``: NDT_HIP (the default), PCL_NDT_HIP, GICP_HIP, SMALL_GICP_HIP,
-    VGICP_HIP or ICP_HIP (``default_params(ICP_HIP)``: lock-step ICP rounds, records bit-identical to :class:`IcpHip`)."""
+    VGICP_HIP or ICP_HIP (``default_params(ICP_HIP)``: lock-step ICP rounds, records bit-identical to :class:`IcpHip`); PCL_GICP_HIP and
+    PCL_GICP_OMP_HIP on a context with ``Context.set_bfgs_batches()`` on (the BFGS loops of the pairs in lock step, one round per functor evaluation,
+    records bit-identical to :class:`PclGicpHip`; any other context refuses them)."""
 
     def __init__(self, params: RegParams | None = None, ctx: Context | None = None, **ndt_kwargs):
         self._ctx = ctx or default_context()
@@ -535,7 +537,8 @@ class BatchMatcher:
         return check(lib().mrgfe_batch_add_device(self._h, nt, tp, tn, npair, pt.ctypes.data_as(_ip), sp, sn, g.ctypes.data_as(_fp)))
 
     def rounds(self) -> int:
-        """Rounds (plan -> derivative launches -> reduce / controller step) of the last NDT align(); ICP_HIP: its lock-step rounds."""
+        """Rounds (plan -> derivative launches -> reduce / controller step) of the last NDT align(); ICP_HIP: its lock-step rounds; PCL_GICP_HIP /
+        PCL_GICP_OMP_HIP: its rounds, one per functor evaluation of the pairs still running."""
         return int(lib().mrgfe_batch_rounds(self._h))
 
     def ndt_rounds(self):
