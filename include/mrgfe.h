@@ -414,6 +414,56 @@ size_t mrgfe_map_store_bytes(const mrgfe_map_store* store);
 int    mrgfe_map_store_generate(mrgfe_map_store* store, int n_keyframes, const uint64_t* keys, const double* poses, const uint8_t* first_keyframe, float resolution,
                                 int min_points_per_voxel, float distance_far_thresh, int skip_first_cloud, float* out_xyzi, size_t capacity, size_t* out_n);
 
+/* ---- the map as the message or file its three callers make of it, and stored keyframes read back ---- */
+/* update_map_cloud_msg (apps/mrg_slam_component.cpp:712-740), publish_map_service (:764-796) and save_map_service (:1078-1144) run
+ * MapCloudGenerator::generate and then pcl::toROSMsg, or the two `+=` offset passes (:1104-1116) and pcl::io::savePCDFileBinary, over every map point.
+ * mrgfe_map_store_publish is mrgfe_map_store_generate for the same keys, poses, flags and parameters — the same points in the same order (ascending
+ * (z, y, x) cell) with the same bits, the same MRGFE_ERR_EMPTY rules — followed, ON THE DEVICE and in the kernel that writes the final points (the
+ * scatter of the last compaction, or the copy of the unfiltered union), by
+ *   the offsets: n_offsets separate f32 additions per coordinate, in the order given, after the voxel filter as :1106-1115 apply them;
+ *   the record:  point_step 32: x, y, z, 1.0f, intensity, 0, 0, 0 — the pcl::PointXYZI of the reference in memory, which toROSMsg copies as it is;
+ *                point_step 16: x, y, z, intensity — the body of the binary PCD.
+ * Only the records come down.  The message's other members are the caller's: width = n_points, height 1, row_step = data_bytes, is_dense false,
+ * little endian, fields x@0 y@4 z@8 intensity@off_intensity, all FLOAT32. */
+typedef struct mrgfe_map_publish_params {   /* config/mrg_slam.yaml:235-237; SaveMap / PublishMap requests            */
+    float   resolution;                     /* 0.1; <= 0: the unfiltered union (map_cloud_generator.cpp:66-70)       */
+    int32_t min_points_per_voxel;           /* 1                                                                     */
+    float   distance_far_thresh;            /* 10000.0; <= 0: no cut (:27)                                           */
+    int32_t skip_first_cloud;               /* 0                                                                     */
+    int32_t point_step;                     /* 32: pcl::toROSMsg records; 16: packed x, y, z, intensity (PCD body)   */
+    int32_t n_offsets;                      /* 0..2: zero_utm, then zero_enu (mrg_slam_component.cpp:1104-1116)      */
+    float   offsets[6];                     /* each already cast to float, x y z                                     */
+} mrgfe_map_publish_params;                 /* 48 bytes */
+typedef struct mrgfe_map_publish_result {
+    uint64_t n_points, n_unfiltered, data_bytes;   /* width; points before the voxel filter; n_points * point_step   */
+    int32_t  point_step, off_intensity;            /* 32 / 16; 16 / 12                                               */
+} mrgfe_map_publish_result;                 /* 32 bytes */
+void   mrgfe_map_publish_default_params(mrgfe_map_publish_params* out); /* 0.1, 1, 10000, 0, point_step 32, no offsets */
+size_t mrgfe_map_publish_params_size(void); /* sizeof(mrgfe_map_publish_params) as the library was compiled */
+size_t mrgfe_map_publish_result_size(void); /* sizeof(mrgfe_map_publish_result) as the library was compiled */
+/* data: room for capacity_bytes.  MRGFE_ERR_INVALID: a NULL argument; point_step other than 16 or 32; n_offsets outside 0..2; a key the store lacks
+ * (before any launch; a first keyframe that skip_first_cloud leaves out is not looked up, as in mrgfe_map_store_generate); capacity_bytes too small —
+ * then out->n_points and out->data_bytes say what is needed and `data` is untouched.  MRGFE_ERR_EMPTY: as mrgfe_map_store_generate.
+ * The working buffers and the records live in a grow-only workspace of the store (freed with it) and in the context's scratch buffers: a call whose
+ * sizes do not exceed an earlier call's allocates and frees no device memory.  The store's keyframes are only read. */
+int    mrgfe_map_store_publish(mrgfe_map_store* store, int n_keyframes, const uint64_t* keys, const double* poses, const uint8_t* first_keyframe,
+                               const mrgfe_map_publish_params* params, void* data, size_t capacity_bytes, mrgfe_map_publish_result* out);
+/* The same, with the records left in the store's workspace: *d_data (NULL for 0 points) is device memory of the store's GPU, complete when the call
+ * returns (the hand-over rule of the other `_device` producers) and valid until the next publish, read or destroy on this store. */
+int    mrgfe_map_store_publish_device(mrgfe_map_store* store, int n_keyframes, const uint64_t* keys, const double* poses, const uint8_t* first_keyframe,
+                                      const mrgfe_map_publish_params* params, const void** d_data, mrgfe_map_publish_result* out);
+/* The stored clouds of `keys` as records, back to back in list order — what KeyFrame::save (src/mrg_slam/keyframe.cpp:109, the PCD body: point_step 16)
+ * and the cloud_msg of publish_graph_service (keyframe.cpp:200, apps/mrg_slam_component.cpp:434: point_step 32) are made of, so the host need not keep
+ * a second copy of every keyframe.  offsets_bytes (n_keys + 1 entries): where keyframe i begins, and the total.  A key may repeat; a keyframe of 0
+ * points is an empty range.  point_step 16: copies out of the store, no kernel; point_step 32: ONE launch over a tile table for the whole list.  Either
+ * way ONE host wait.  MRGFE_ERR_INVALID: a NULL argument, another point_step, a key the store lacks (nothing is written, offsets_bytes included), more
+ * than 2^31 - 1 points, capacity_bytes too small (offsets_bytes is filled, `data` untouched). */
+int    mrgfe_map_store_read(mrgfe_map_store* store, int n_keys, const uint64_t* keys, int point_step, void* data, size_t capacity_bytes, uint64_t* offsets_bytes);
+/* What the last publish / read on the store did: out[0] kernel launches of its record stage (publish: the record kernel and, where points are dropped,
+ * the three of the scan in front of it — the generator's passes before them are not counted; read: all of the call's), out[1] host waits of the whole
+ * call, out[2] bytes brought down, out[3] device bytes the workspace and the context's scratch buffers grew by. */
+int    mrgfe_map_store_egress_stats(const mrgfe_map_store* store, int64_t out[4]);
+
 /* The same two calls for keyframes that already sit in a map store: a graph edge names its two keyframes, so
  * neither cloud is uploaded again, and the exact-NN grid of key1's cloud is kept for the next edges of that keyframe (the
  * reference builds a fresh kd-tree over cloud1 for every edge: information_matrix_calculator.cpp:51-52). */

@@ -78,6 +78,19 @@ class GraphEdge(C.Structure):
     _fields_ = [("key1", C.c_uint64), ("key2", C.c_uint64), ("relpose", C.c_double * 16)]
 
 
+class MapPublishParams(C.Structure):
+    """struct mrgfe_map_publish_params: the generator's parameters (config/mrg_slam.yaml:235-237), the record layout and the save offsets."""
+
+    _fields_ = [("resolution", C.c_float), ("min_points_per_voxel", C.c_int32), ("distance_far_thresh", C.c_float), ("skip_first_cloud", C.c_int32),
+                ("point_step", C.c_int32), ("n_offsets", C.c_int32), ("offsets", C.c_float * 6)]
+
+
+class MapPublishResult(C.Structure):
+    """struct mrgfe_map_publish_result: the counts and the record layout of one ``mrgfe_map_store_publish``."""
+
+    _fields_ = [("n_points", C.c_uint64), ("n_unfiltered", C.c_uint64), ("data_bytes", C.c_uint64), ("point_step", C.c_int32), ("off_intensity", C.c_int32)]
+
+
 class GroundFillParams(C.Structure):
     """struct mrgfe_ground_fill_params: fill_first_cloud_radius, map_cloud_resolution, fill_first_cloud_simple (apps/mrg_slam_component.cpp:245,271-272)."""
 
@@ -257,6 +270,14 @@ SIGNATURES = {
     "mrgfe_map_store_bytes": (C.c_size_t, [_vp]),
     "mrgfe_map_store_generate": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64), _dp, C.POINTER(C.c_uint8), C.c_float, C.c_int, C.c_float, C.c_int, _fp, C.c_size_t,
                                            C.POINTER(C.c_size_t)]),
+    "mrgfe_map_publish_default_params": (None, [C.POINTER(MapPublishParams)]),
+    "mrgfe_map_publish_params_size": (C.c_size_t, []),
+    "mrgfe_map_publish_result_size": (C.c_size_t, []),
+    "mrgfe_map_store_publish": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64), _dp, C.POINTER(C.c_uint8), C.POINTER(MapPublishParams), _vp, C.c_size_t, C.POINTER(MapPublishResult)]),
+    "mrgfe_map_store_publish_device": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64), _dp, C.POINTER(C.c_uint8), C.POINTER(MapPublishParams), C.POINTER(_vp),
+                                                 C.POINTER(MapPublishResult)]),
+    "mrgfe_map_store_read": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64), C.c_int, _vp, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "mrgfe_map_store_egress_stats": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mrgfe_keyframe_default_params": (None, [C.POINTER(KeyframeParams)]),
     "mrgfe_keyframe_params_size": (C.c_size_t, []),
     "mrgfe_pointcloud2_field_size": (C.c_size_t, []),
@@ -496,7 +517,8 @@ def lib() -> C.CDLL:
             raise RuntimeError(f"libmrgfe.so was built with a mrgfe_keyframe_params of {L.mrgfe_keyframe_params_size()} bytes, the binding mirrors {C.sizeof(KeyframeParams)}")
         for fn, mirror in (("mrgfe_pointcloud2_field_size", PointField), ("mrgfe_keyframe_msg_size", KeyframeMsg), ("mrgfe_graph_edge_size", GraphEdge), ("mrgfe_odom_params_size", OdomParams),
                            ("mrgfe_odom_result_size", OdomResult), ("mrgfe_loop_params_size", LoopParams), ("mrgfe_loop_keyframe_size", LoopKeyframe),
-                           ("mrgfe_loop_result_size", LoopResult), ("mrgfe_ground_fill_params_size", GroundFillParams), ("mrgfe_ground_fill_result_size", GroundFillResult)):
+                           ("mrgfe_loop_result_size", LoopResult), ("mrgfe_ground_fill_params_size", GroundFillParams), ("mrgfe_ground_fill_result_size", GroundFillResult),
+                           ("mrgfe_map_publish_params_size", MapPublishParams), ("mrgfe_map_publish_result_size", MapPublishResult)):
             if hasattr(L, fn) and getattr(L, fn)() != C.sizeof(mirror):
                 raise RuntimeError(f"libmrgfe.so was built with a {fn[:-5]} of {getattr(L, fn)()} bytes, the binding mirrors {C.sizeof(mirror)}")
         _lib = L

@@ -928,6 +928,154 @@ int mrgfe_map_store_generate(mrgfe_map_store* s, int K, const uint64_t* keys, co
     });
 }
 
+// ---- egress: the map as wire records, stored keyframes read back (include/mrgfe.h) -----------------------------------------------------
+static_assert(sizeof(mrgfe_map_publish_params) == 48, "mrgfe_map_publish_params: the layout the bindings mirror");
+static_assert(sizeof(mrgfe_map_publish_result) == 32, "mrgfe_map_publish_result: the layout the bindings mirror");
+size_t mrgfe_map_publish_params_size(void) { return sizeof(mrgfe_map_publish_params); }
+size_t mrgfe_map_publish_result_size(void) { return sizeof(mrgfe_map_publish_result); }
+void mrgfe_map_publish_default_params(mrgfe_map_publish_params* p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->resolution = 0.1f;              // config/mrg_slam.yaml:235
+    p->min_points_per_voxel = 1;       // :236
+    p->distance_far_thresh = 10000.0f; // :237
+    p->point_step = 32;
+}
+// One publish / read past its argument checks: the store's statistics start over, and what the workspace grew by is known when the call ends
+struct EgressCall {
+    mrgfe_map_store* s;
+    size_t           before;
+    explicit EgressCall(mrgfe_map_store* st) : s(st), before(st->egress.footprint(st->ctx)) { s->egress_stats = EgressStats(); }
+    ~EgressCall() { s->egress_stats.grown = static_cast<int64_t>(s->egress.footprint(s->ctx) - before); }
+};
+// both forms behind their NULL checks; to_host: the records come down into `data` (capacity_bytes), else they stay in the workspace and *d_data receives their address
+static int map_publish_locked(const char* fn, mrgfe_map_store* s, int K, const uint64_t* keys, const double* poses, const uint8_t* first_keyframe, const mrgfe_map_publish_params* p,
+                              bool to_host, void* data, size_t capacity_bytes, const void** d_data, mrgfe_map_publish_result* out)
+{
+    std::memset(out, 0, sizeof(*out));
+    if (p->point_step != 16 && p->point_step != 32) { set_error("%s: point_step %d (32: pcl::PointXYZI records, 16: packed points)", fn, p->point_step); return MRGFE_ERR_INVALID; }
+    if (p->n_offsets < 0 || p->n_offsets > 2) { set_error("%s: %d offsets (0 to 2)", fn, p->n_offsets); return MRGFE_ERR_INVALID; }
+    out->point_step = p->point_step;
+    out->off_intensity = p->point_step == 32 ? 16 : 12;
+    if (K <= 0) { set_error("keyframes are empty, cannot generate map cloud"); return MRGFE_ERR_EMPTY; }  // map_cloud_generator.cpp:19-22
+    MRGFE_LOCK(s->ctx);
+    MRGFE_TRY(s->ctx->bind());
+    std::vector<uint32_t>      off(1, 0u);
+    std::vector<float>         pose_f;
+    std::vector<const float4*> ptrs;
+    uint64_t total = 0;
+    for (int k = 0; k < K; ++k) {  // (as mrgfe_map_store_generate walks them: every key is looked up before anything is launched)
+        if (first_keyframe && first_keyframe[k] && p->skip_first_cloud) continue;  // :32-34
+        auto it = s->clouds.find(keys[k]);
+        if (it == s->clouds.end()) { set_error("%s: keyframe %llu is not in the store", fn, static_cast<unsigned long long>(keys[k])); return MRGFE_ERR_INVALID; }
+        total += it->second.n;
+        if (total > 0x7fffffffu) { set_error("%s: more than 2^31 points", fn); return MRGFE_ERR_INVALID; }
+        ptrs.push_back(it->second.p);
+        off.push_back(static_cast<uint32_t>(total));
+        for (int t = 0; t < 16; ++t) pose_f.push_back(static_cast<float>(poses[16 * k + t]));
+    }
+    EgressCall  call(s);
+    EgressStats& st = s->egress_stats;
+    MRGFE_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));  // clouds added just before are still on their way up
+    st.waits += 1;
+    EgressFormat f{p->point_step, p->n_offsets, {0, 0, 0, 0, 0, 0}};
+    for (int t = 0; t < 3 * p->n_offsets; ++t) f.offsets[t] = p->offsets[t];
+    size_t m = 0, unfiltered = 0;
+    bool   complete = true;
+    if (total) MRGFE_TRY(map_publish_device(s->ctx, s->egress, off.data(), pose_f.data(), static_cast<int>(ptrs.size()), ptrs.data(), p->resolution, p->min_points_per_voxel,
+                                            p->distance_far_thresh, f, &m, &unfiltered, &complete, &st));
+    // :57-60: the cloud BEFORE the voxel filter decides
+    if (unfiltered == 0 && K > 1) { set_error("cloud is empty after processing keyframes"); return MRGFE_ERR_EMPTY; }
+    out->n_points = m;
+    out->n_unfiltered = unfiltered;
+    out->data_bytes = uint64_t(m) * p->point_step;
+    if (!to_host) {
+        if (m && !complete) {  // the hand-over rule of the `_device` producers: the records are complete when the call returns, for readers on any stream
+            MRGFE_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
+            st.waits += 1;
+        }
+        *d_data = m ? s->egress.rec.p : nullptr;
+        return MRGFE_OK;
+    }
+    if (out->data_bytes > capacity_bytes) { set_error("%s: the records need %llu bytes, capacity is %zu", fn, static_cast<unsigned long long>(out->data_bytes), capacity_bytes); return MRGFE_ERR_INVALID; }
+    if (m) {
+        if (!data) { set_error("%s: NULL data", fn); return MRGFE_ERR_INVALID; }
+        MRGFE_HIP_CHECK(hipMemcpyAsync(data, s->egress.rec.p, out->data_bytes, hipMemcpyDeviceToHost, s->ctx->stream));
+        MRGFE_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
+        st.waits += 1;
+        st.bytes_down = static_cast<int64_t>(out->data_bytes);
+    }
+    return MRGFE_OK;
+}
+int mrgfe_map_store_publish(mrgfe_map_store* s, int K, const uint64_t* keys, const double* poses, const uint8_t* first_keyframe, const mrgfe_map_publish_params* p, void* data,
+                            size_t capacity_bytes, mrgfe_map_publish_result* out)
+{
+    static const char* fn = "mrgfe_map_store_publish";
+    return abi_guard(fn, [&]() -> int {
+        if (!s || !p || !out || (K > 0 && (!keys || !poses))) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        return map_publish_locked(fn, s, K, keys, poses, first_keyframe, p, true, data, capacity_bytes, nullptr, out);
+    });
+}
+int mrgfe_map_store_publish_device(mrgfe_map_store* s, int K, const uint64_t* keys, const double* poses, const uint8_t* first_keyframe, const mrgfe_map_publish_params* p,
+                                   const void** d_data, mrgfe_map_publish_result* out)
+{
+    static const char* fn = "mrgfe_map_store_publish_device";
+    return abi_guard(fn, [&]() -> int {
+        if (!s || !p || !out || !d_data || (K > 0 && (!keys || !poses))) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        *d_data = nullptr;
+        return map_publish_locked(fn, s, K, keys, poses, first_keyframe, p, false, nullptr, 0, d_data, out);
+    });
+}
+int mrgfe_map_store_read(mrgfe_map_store* s, int n_keys, const uint64_t* keys, int point_step, void* data, size_t capacity_bytes, uint64_t* offsets_bytes)
+{
+    static const char* fn = "mrgfe_map_store_read";
+    return abi_guard(fn, [&]() -> int {
+        if (!s || n_keys < 0 || !offsets_bytes || (n_keys > 0 && !keys)) { set_error("%s: NULL argument or a negative count", fn); return MRGFE_ERR_INVALID; }
+        if (point_step != 16 && point_step != 32) { set_error("%s: point_step %d (32: pcl::PointXYZI records, 16: packed points)", fn, point_step); return MRGFE_ERR_INVALID; }
+        MRGFE_LOCK(s->ctx);
+        MRGFE_TRY(s->ctx->bind());
+        std::vector<KeyframeRecordItem> items;
+        uint64_t points = 0;
+        for (int i = 0; i < n_keys; ++i) {  // every key is looked up before anything is written
+            auto it = s->clouds.find(keys[i]);
+            if (it == s->clouds.end()) { set_error("%s: keyframe %llu is not in the store", fn, static_cast<unsigned long long>(keys[i])); return MRGFE_ERR_INVALID; }
+            items.push_back({it->second.p, it->second.n, points});
+            points += it->second.n;
+        }
+        if (points > kMaxPoints) { set_error("%s: more than 2^31 - 1 points", fn); return MRGFE_ERR_INVALID; }
+        for (int i = 0; i < n_keys; ++i) offsets_bytes[i] = items[i].first_record * uint64_t(point_step);
+        offsets_bytes[n_keys] = points * uint64_t(point_step);
+        const uint64_t bytes = offsets_bytes[n_keys];
+        if (bytes > capacity_bytes) { set_error("%s: the records need %llu bytes, capacity is %zu", fn, static_cast<unsigned long long>(bytes), capacity_bytes); return MRGFE_ERR_INVALID; }
+        EgressCall  call(s);
+        EgressStats& st = s->egress_stats;
+        if (!points) return MRGFE_OK;
+        if (!data) { set_error("%s: NULL data", fn); return MRGFE_ERR_INVALID; }
+        mrgfe_ctx* ctx = s->ctx;
+        if (point_step == 16) {  // the stored clouds are the records: copies out of the arena, behind whatever is still filling it on the stream
+            for (const KeyframeRecordItem& it : items)
+                if (it.n) MRGFE_HIP_CHECK(hipMemcpyAsync(static_cast<char*>(data) + it.first_record * 16, it.d_cloud, size_t(it.n) * 16, hipMemcpyDeviceToHost, ctx->stream));
+        } else {
+            MRGFE_TRY(s->egress.rec.ensure(bytes));
+            MRGFE_TRY(keyframe_records_many_device(ctx, items.data(), items.size(), s->egress.rec.p));
+            st.launches += 1;
+            MRGFE_HIP_CHECK(hipMemcpyAsync(data, s->egress.rec.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the only wait
+        st.waits += 1;
+        st.bytes_down = static_cast<int64_t>(bytes);
+        return MRGFE_OK;
+    });
+}
+int mrgfe_map_store_egress_stats(const mrgfe_map_store* s, int64_t out[4])
+{
+    if (!s || !out) { set_error("mrgfe_map_store_egress_stats: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(s->ctx);
+    out[0] = s->egress_stats.launches; out[1] = s->egress_stats.waits; out[2] = s->egress_stats.bytes_down; out[3] = s->egress_stats.grown;
+    return MRGFE_OK;
+}
+
 int mrgfe_map_store_fitness(mrgfe_map_store* s, uint64_t key1, uint64_t key2, const double relpose[16], double max_range, double* out)
 {
     return abi_guard("mrgfe_map_store_fitness", [&]() -> int {

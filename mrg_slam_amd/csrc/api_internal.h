@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "gicp_engine.h"
+#include "mapcloud.h"
 #include "ndt_engine.h"
 #include "nn_grid.h"
 
@@ -148,4 +149,7 @@ struct mrgfe_map_store {
     mrgfe::NnGridSet           edge_set;
     std::vector<mrgfe::NnGrid> edge_views;
     std::vector<uint64_t>      edge_keys;
+    // mrgfe_map_store_publish / _read: the working buffers and the records of the last call (grow-only; freed with the store, under its context bound)
+    mrgfe::MapEgressWorkspace egress;
+    mrgfe::EgressStats        egress_stats;  // of the last publish / read
 };

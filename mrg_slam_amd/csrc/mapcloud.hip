@@ -253,6 +253,274 @@ int map_cloud_device(mrgfe_ctx* ctx, const float4* d_cat, const uint32_t* kf_off
     return rc;
 }
 
+// ---- egress: the map as wire records (mrgfe_map_store_publish) -----------------------------------------------------------------
+// update_map_cloud_msg / publish_map_service / save_map_service (apps/mrg_slam_component.cpp:712-740, 764-796, 1078-1144) run the generator and
+// then pcl::toROSMsg or the two `+=` offset passes and savePCDFileBinary over every map point.  Here the kernel that writes the FINAL points
+// writes them as the records the caller sends or saves: the scatter of the last compaction (the voxel count threshold, or the far cut of the
+// unfiltered map), or the copy of the unfiltered map without a far cut.  Per kept point: up to two f32 offset additions per coordinate, one after
+// the other (:1106-1115 add zero_utm, then zero_enu, to the filtered cloud), then
+//   point_step 32: x, y, z, 1.0f | intensity, 0, 0, 0   the pcl::PointXYZI in memory, which is what toROSMsg copies (two 16-byte stores)
+//   point_step 16: x, y, z, intensity                   the body of a binary PCD (one 16-byte store)
+// Without offsets no arithmetic touches the point: its bits, a NaN's payload included, are those of the generator.
+struct EgressOffsets { int32_t n; float v[2][3]; };
+template <int kStep>
+__device__ __forceinline__ void store_record(float4* __restrict__ out, size_t at, float4 p, const EgressOffsets& o)
+{
+#pragma clang fp contract(off)
+    for (int k = 0; k < o.n; ++k) {
+        p.x = p.x + o.v[k][0];
+        p.y = p.y + o.v[k][1];
+        p.z = p.z + o.v[k][2];
+    }
+    if (kStep == 16) out[at] = p;
+    else {
+        out[2 * at] = make_float4(p.x, p.y, p.z, 1.0f);
+        out[2 * at + 1] = make_float4(p.w, 0.0f, 0.0f, 0.0f);
+    }
+}
+// flags / pos: the keep flags and their exclusive scan; both nullptr: every point is kept where it stands
+template <int kStep>
+__global__ __launch_bounds__(256) void egress_records_kernel(const float4* __restrict__ in, const uint32_t* __restrict__ flags, const uint32_t* __restrict__ pos, uint32_t n,
+                                                              EgressOffsets o, float4* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    if (flags && !flags[i]) return;
+    store_record<kStep>(out, flags ? pos[i] : i, in[i], o);  // pos[i] <= i < n: inside the n records of `out`
+}
+
+static EgressOffsets egress_offsets(const EgressFormat& f)
+{
+    EgressOffsets o{};
+    o.n = f.n_offsets;
+    for (int k = 0; k < f.n_offsets; ++k) for (int a = 0; a < 3; ++a) o.v[k][a] = f.offsets[3 * k + a];
+    return o;
+}
+// compact_by_flags with the record kernel as its scatter: *total records in d_rec (room for n).  d_flags nullptr: all n points, no scan and no wait —
+// *waited says whether the stream was waited for BEHIND the record kernel (the records are complete) or the kernel is only queued.
+static int egress_records(mrgfe_ctx* ctx, const float4* d_in, uint32_t n, const uint32_t* d_flags, const EgressFormat& f, void* d_rec, uint32_t* total, bool* waited, EgressStats* stats)
+{
+    *total = 0;
+    *waited = false;
+    if (n == 0) return MRGFE_OK;
+    hipStream_t st = ctx->stream;
+    const auto kern = f.point_step == 16 ? egress_records_kernel<16> : egress_records_kernel<32>;
+    const dim3 grid((n + 255) / 256);
+    if (!d_flags) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, d_in, nullptr, nullptr, n, egress_offsets(f), static_cast<float4*>(d_rec));
+        MRGFE_HIP_CHECK(hipGetLastError());
+        stats->launches += 1;
+        *total = n;
+        return MRGFE_OK;
+    }
+    SliceTable tab;
+    tab.build(&n, 1);
+    DevBuf &ds = ctx->scratch[0], &dpos = ctx->scratch[4], &dblk = ctx->scratch[8];  // (the slots of compact_by_flags)
+    MRGFE_TRY(ds.ensure(sizeof(Slice)));
+    MRGFE_TRY(dpos.ensure(size_t(n) * 4));
+    MRGFE_TRY(dblk.ensure(sizeof(uint32_t) * (tab.total_blks + 8)));
+    MRGFE_HIP_CHECK(hipMemcpyAsync(ds.p, tab.h.data(), sizeof(Slice), hipMemcpyHostToDevice, st));
+    uint32_t* d_tot = dblk.as<uint32_t>() + tab.total_blks;
+    MRGFE_TRY(exclusive_scan(ctx, d_flags, dpos.as<uint32_t>(), ds.as<Slice>(), tab, dblk.as<uint32_t>(), d_tot));
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, d_in, d_flags, dpos.as<uint32_t>(), n, egress_offsets(f), static_cast<float4*>(d_rec));
+    MRGFE_HIP_CHECK(hipGetLastError());
+    stats->launches += 4;  // the three of the scan, the record kernel
+    MRGFE_HIP_CHECK(hipMemcpyAsync(total, d_tot, 4, hipMemcpyDeviceToHost, st));
+    MRGFE_HIP_CHECK(hipStreamSynchronize(st));
+    stats->waits += 1;
+    *waited = true;
+    return MRGFE_OK;
+}
+
+// mean_voxelgrid_device up to its centroids and keep flags (ctx->scratch[10] / [11], *n_cells of each; 0: no finite point).  The passes, their order
+// and their buffers are that function's, which stays as it is — the generator is what the egress tests hold this against — so a change there is a
+// change here; only its last step, compact_by_flags into a packed cloud, is not taken: the caller's record kernel is that step.
+static int mean_voxel_cells(mrgfe_ctx* ctx, const float4* d_in, size_t n, float leaf, int min_pts, uint32_t* n_cells, EgressStats* stats)
+{
+    *n_cells = 0;
+    hipStream_t st = ctx->stream;
+    uint32_t    nn = static_cast<uint32_t>(n);
+    SliceTable  tab;
+    tab.build(&nn, 1);
+    struct Desc { Slice sl; const float4* cp; };
+    PinBuf& hp = ctx->pin[1];
+    MRGFE_TRY(hp.ensure(sizeof(Desc) + sizeof(BBox) + 16));
+    Desc* hd = hp.as<Desc>();
+    hd->sl = tab.h[0];
+    hd->cp = d_in;
+    DevBuf& dd = ctx->scratch[0];
+    MRGFE_TRY(dd.ensure(sizeof(Desc)));
+    Desc* d_desc = dd.as<Desc>();
+    MRGFE_HIP_CHECK(hipMemcpyAsync(d_desc, hd, sizeof(Desc), hipMemcpyHostToDevice, st));
+    DevBuf& dbb = ctx->scratch[1];
+    MRGFE_TRY(dbb.ensure(sizeof(BBox) * (tab.total_blks + 1)));
+    BBox* d_part = dbb.as<BBox>();
+    BBox* d_bbo = d_part + tab.total_blks;
+    MRGFE_TRY(bounding_boxes(ctx, &d_desc->cp, &d_desc->sl, tab, d_part, d_bbo));
+    BBox* h_bb = reinterpret_cast<BBox*>(hp.as<char>() + sizeof(Desc));
+    MRGFE_HIP_CHECK(hipMemcpyAsync(h_bb, d_bbo, sizeof(BBox), hipMemcpyDeviceToHost, st));
+    MRGFE_HIP_CHECK(hipStreamSynchronize(st));
+    stats->waits += 1;
+    const uint32_t n_valid = h_bb->n_finite;
+    if (n_valid == 0) return MRGFE_OK;
+    CellKeyParams kp;
+    kp.inv_leaf = 1.0f / leaf;
+    uint32_t bits[3];
+    for (int a = 0; a < 3; ++a) {
+        const double lo = std::floor(static_cast<double>(h_bb->mn[a] * kp.inv_leaf)), hi = std::floor(static_cast<double>(h_bb->mx[a] * kp.inv_leaf));
+        if (!(lo > -2147483000.0 && hi < 2147483000.0)) { set_error("map cloud: cell index beyond int32 (the reference's int cast overflows there too)"); return MRGFE_ERR_OVERFLOW; }
+        kp.min_c[a] = static_cast<int32_t>(lo);
+        const uint64_t span = static_cast<uint64_t>(hi - lo);
+        bits[a] = 1;
+        while ((uint64_t(1) << bits[a]) <= span) ++bits[a];
+    }
+    kp.shift_y = bits[0];
+    kp.shift_z = bits[0] + bits[1];
+    kp.total_bits = bits[0] + bits[1] + bits[2];
+    if (kp.total_bits > 62) { set_error("map cloud: %u key bits needed (extent / resolution)", kp.total_bits); return MRGFE_ERR_OVERFLOW; }
+    DevBuf &dk = ctx->scratch[2], &dv = ctx->scratch[3], &dkt = ctx->scratch[4], &dvt = ctx->scratch[5], &dh = ctx->scratch[6], &dfl = ctx->scratch[7], &dblk = ctx->scratch[8],
+           &dkh = ctx->scratch[12], &dlo = ctx->scratch[13];
+    MRGFE_TRY(dk.ensure(n * 4)); MRGFE_TRY(dv.ensure(n * 4)); MRGFE_TRY(dkt.ensure(n * 4)); MRGFE_TRY(dvt.ensure(n * 4)); MRGFE_TRY(dkh.ensure(n * 4)); MRGFE_TRY(dlo.ensure(n * 4));
+    MRGFE_TRY(dh.ensure(sizeof(uint32_t) * 256 * (tab.total_blks + 1)));
+    MRGFE_TRY(dfl.ensure(n * 4));
+    MRGFE_TRY(dblk.ensure(sizeof(uint32_t) * (tab.total_blks + 8)));
+    const dim3 grid((nn + 255) / 256);
+    hipLaunchKernelGGL(mapvox_keys_kernel, grid, dim3(256), 0, st, d_in, nn, kp, dlo.as<uint32_t>(), dkh.as<uint32_t>(), dv.as<uint32_t>());
+    MRGFE_HIP_CHECK(hipGetLastError());
+    MRGFE_HIP_CHECK(hipMemcpyAsync(dk.p, dlo.p, n * 4, hipMemcpyDeviceToDevice, st));
+    const int key_bits = static_cast<int>(kp.total_bits) + 1;
+    uint32_t *sk, *sv;
+    MRGFE_TRY(radix_sort_pairs(ctx, dk.as<uint32_t>(), dv.as<uint32_t>(), dkt.as<uint32_t>(), dvt.as<uint32_t>(), &d_desc->sl, tab, std::min(key_bits, 32), dh.as<uint32_t>(), &sk, &sv));
+    if (key_bits > 32) {
+        uint32_t* k2 = (sk == dk.as<uint32_t>()) ? dk.as<uint32_t>() : dkt.as<uint32_t>();
+        uint32_t* k2t = (sk == dk.as<uint32_t>()) ? dkt.as<uint32_t>() : dk.as<uint32_t>();
+        uint32_t* v2t = (sv == dv.as<uint32_t>()) ? dvt.as<uint32_t>() : dv.as<uint32_t>();
+        hipLaunchKernelGGL(gather_u32_kernel, grid, dim3(256), 0, st, dkh.as<uint32_t>(), sv, nn, k2);
+        MRGFE_HIP_CHECK(hipGetLastError());
+        MRGFE_TRY(radix_sort_pairs(ctx, k2, sv, k2t, v2t, &d_desc->sl, tab, key_bits - 32, dh.as<uint32_t>(), &sk, &sv));
+    }
+    hipLaunchKernelGGL(heads64_kernel, grid, dim3(256), 0, st, dlo.as<uint32_t>(), dkh.as<uint32_t>(), sv, nn, n_valid, dfl.as<uint32_t>());
+    MRGFE_HIP_CHECK(hipGetLastError());
+    uint32_t* d_ord = (sk == dk.as<uint32_t>()) ? dkt.as<uint32_t>() : dk.as<uint32_t>();
+    uint32_t* d_tot = dblk.as<uint32_t>() + tab.total_blks;
+    MRGFE_TRY(exclusive_scan(ctx, dfl.as<uint32_t>(), d_ord, &d_desc->sl, tab, dblk.as<uint32_t>(), d_tot));
+    uint32_t* h_tot = reinterpret_cast<uint32_t*>(hp.as<char>() + sizeof(Desc) + sizeof(BBox));
+    MRGFE_HIP_CHECK(hipMemcpyAsync(h_tot, d_tot, 4, hipMemcpyDeviceToHost, st));
+    MRGFE_HIP_CHECK(hipStreamSynchronize(st));
+    stats->waits += 1;
+    const uint32_t V = *h_tot;
+    if (V == 0) return MRGFE_OK;
+    DevBuf &dseg = ctx->scratch[9], &dcent = ctx->scratch[10], &dkeep = ctx->scratch[11];
+    MRGFE_TRY(dseg.ensure(sizeof(uint32_t) * (size_t(V) + 4)));
+    MRGFE_TRY(dcent.ensure(sizeof(float4) * size_t(V)));
+    MRGFE_TRY(dkeep.ensure(sizeof(uint32_t) * size_t(V)));
+    hipLaunchKernelGGL(seg_from_heads_kernel, grid, dim3(256), 0, st, dfl.as<uint32_t>(), d_ord, nn, n_valid, V, dseg.as<uint32_t>());
+    MRGFE_HIP_CHECK(hipGetLastError());
+    MRGFE_TRY(launch_voxel_centroids(ctx, d_in, sv, dseg.as<uint32_t>(), V, min_pts, dcent.as<float4>(), dkeep.as<uint32_t>()));
+    *n_cells = V;
+    return MRGFE_OK;
+}
+
+size_t MapEgressWorkspace::footprint(const mrgfe_ctx* ctx) const
+{
+    size_t b = tab.cap + trans.cap + flags.cap + comp.cap + rec.cap + ctx->sort_chunks.cap;
+    for (const DevBuf& d : ctx->scratch) b += d.cap;
+    return b;
+}
+
+int map_publish_device(mrgfe_ctx* ctx, MapEgressWorkspace& ws, const uint32_t* kf_off, const float* poses_f, int K, const float4* const* kf_ptrs, float resolution, int min_pts,
+                       float far_thresh, const EgressFormat& f, size_t* out_n, size_t* n_unfiltered, bool* records_complete, EgressStats* stats)
+{
+    *out_n = 0;
+    *n_unfiltered = 0;
+    *records_complete = true;  // (no record kernel queued yet)
+    const uint32_t n = kf_off[K];
+    if (n == 0) return MRGFE_OK;
+    hipStream_t st = ctx->stream;
+    // the tables of map_cloud_device in one staged copy: offsets, poses, cloud pointers
+    const size_t pose_at = sizeof(uint32_t) * (K + 1), ptr_at = (pose_at + sizeof(float) * 16 * K + 15) & ~size_t(15), tab_bytes = ptr_at + sizeof(void*) * K;
+    std::vector<char> h_tab(tab_bytes, 0);
+    std::memcpy(h_tab.data(), kf_off, pose_at);
+    std::memcpy(h_tab.data() + pose_at, poses_f, sizeof(float) * 16 * K);
+    std::memcpy(h_tab.data() + ptr_at, kf_ptrs, sizeof(void*) * K);
+    MRGFE_TRY(ws.tab.ensure(tab_bytes));
+    MRGFE_TRY(ws.trans.ensure(size_t(n) * 16));
+    MRGFE_TRY(ws.flags.ensure(size_t(n) * 4));
+    MRGFE_TRY(ctx->stage_h2d(ws.tab.p, h_tab.data(), tab_bytes, st));
+    const bool use_far = far_thresh > 0;  // map_cloud_generator.cpp:27-28
+    hipLaunchKernelGGL(map_transform_kernel, dim3((n + 255) / 256), dim3(256), 0, st, static_cast<const float4*>(nullptr), reinterpret_cast<const float4* const*>(ws.tab.as<char>() + ptr_at), n,
+                       ws.tab.as<uint32_t>(), reinterpret_cast<const float*>(ws.tab.as<char>() + pose_at), K, use_far ? 1 : 0, far_thresh * far_thresh, ws.trans.as<float4>(), ws.flags.as<uint32_t>());
+    MRGFE_HIP_CHECK(hipGetLastError());
+    uint32_t m = 0;
+    if (resolution <= 0.0f) {  // :66-70: the unfiltered cloud — the far cut is the last compaction, or there is none
+        MRGFE_TRY(ws.rec.ensure(size_t(n) * f.point_step));
+        MRGFE_TRY(egress_records(ctx, ws.trans.as<float4>(), n, use_far ? ws.flags.as<uint32_t>() : nullptr, f, ws.rec.p, &m, records_complete, stats));
+        *n_unfiltered = m;
+        *out_n = m;
+        return MRGFE_OK;
+    }
+    const float4* d_cloud = ws.trans.as<float4>();
+    uint32_t      total = n;
+    if (use_far) {
+        MRGFE_TRY(ws.comp.ensure(size_t(n) * 16));
+        MRGFE_TRY(compact_by_flags(ctx, ws.trans.as<float4>(), n, ws.flags.as<uint32_t>(), ws.comp.as<float4>(), &total));
+        stats->waits += 1;
+        d_cloud = ws.comp.as<float4>();
+    }
+    *n_unfiltered = total;
+    if (total == 0) return MRGFE_OK;
+    uint32_t V = 0;
+    MRGFE_TRY(mean_voxel_cells(ctx, d_cloud, total, resolution, min_pts, &V, stats));
+    if (V == 0) return MRGFE_OK;
+    MRGFE_TRY(ws.rec.ensure(size_t(V) * f.point_step));
+    MRGFE_TRY(egress_records(ctx, ctx->scratch[10].as<float4>(), V, ctx->scratch[11].as<uint32_t>(), f, ws.rec.p, &m, records_complete, stats));
+    *out_n = m;
+    return MRGFE_OK;
+}
+
+// ---- egress: stored keyframes as 32-byte records (mrgfe_map_store_read) ----------------------------------------------------------------
+// KeyFrame::save / the cloud_msg of publish_graph_service (src/mrg_slam/keyframe.cpp:109, 200) for a list of keyframes: ONE launch over a tile table,
+// as keyframe_gather_many_kernel is driven — a workgroup-uniform 32-byte read names the tile's cloud, its first point and the record that point becomes.
+struct RecordTile {
+    const float4* src;    // the keyframe's cloud
+    uint64_t      out;    // the record of the keyframe's point 0 in the output
+    uint32_t      first;  // the tile's first point within the keyframe
+    uint32_t      n;      // points of the keyframe
+    uint32_t      pad[2];
+};
+static_assert(sizeof(RecordTile) == 32, "RecordTile: one 32-byte record per tile");
+__global__ __launch_bounds__(256) void keyframe_records_many_kernel(const RecordTile* __restrict__ tiles, float4* __restrict__ out)
+{
+    const RecordTile t = tiles[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < kTile / 256; ++k) {
+        const uint32_t i = t.first + k * 256 + threadIdx.x;
+        if (i < t.n) store_record<32>(out, t.out + i, t.src[i], EgressOffsets{});
+    }
+}
+
+int keyframe_records_many_device(mrgfe_ctx* ctx, const KeyframeRecordItem* items, size_t count, void* d_records)
+{
+    std::vector<RecordTile> tiles;
+    for (size_t m = 0; m < count; ++m) {
+        RecordTile t;
+        std::memset(&t, 0, sizeof(t));
+        t.src = items[m].d_cloud; t.out = items[m].first_record; t.n = items[m].n;
+        for (uint64_t first = 0; first < t.n; first += kTile) {  // (an empty keyframe has no tile)
+            t.first = static_cast<uint32_t>(first);
+            tiles.push_back(t);
+        }
+    }
+    if (tiles.empty()) return MRGFE_OK;
+    if (tiles.size() > 0x7fffffffu) { set_error("keyframe records: %zu tiles in one launch", tiles.size()); return MRGFE_ERR_INVALID; }
+    DevBuf& dtab = ctx->scratch[0];
+    MRGFE_TRY(dtab.ensure(tiles.size() * sizeof(RecordTile)));
+    MRGFE_TRY(ctx->stage_h2d(dtab.p, tiles.data(), tiles.size() * sizeof(RecordTile), ctx->stream));
+    hipLaunchKernelGGL(keyframe_records_many_kernel, dim3(static_cast<uint32_t>(tiles.size())), dim3(256), 0, ctx->stream, dtab.as<RecordTile>(), static_cast<float4*>(d_records));
+    MRGFE_HIP_CHECK(hipGetLastError());
+    return MRGFE_OK;
+}
+
 // ---- other-robot point removal -----------------------------------------------------------------------------------
 // (the sphere test itself: scan_point.h near_a_centre, shared with the keyframe head kernel below)
 __global__ __launch_bounds__(256) void near_flags_kernel(const float4* __restrict__ in, uint32_t n, Centres c, int K, float radius_sqr, uint32_t* __restrict__ keep,

@@ -62,15 +62,19 @@ def write_kitti_bin(path: str, cloud) -> None:
 
 
 # ---- PCD -----------------------------------------------------------------------------------------------------------
+def pcd_binary_header(n: int) -> bytes:
+    """The v0.7 header PCDWriter::generateHeader produces for an unorganised pcl::PointCloud<pcl::PointXYZI> of ``n`` points with the default viewpoint;
+    the body behind it is the four fields of every point packed to 16 bytes."""
+    return ("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\n"
+            f"WIDTH {n}\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS {n}\nDATA binary\n").encode("ascii")
+
+
 def write_pcd_binary(path: str, cloud) -> None:
     """What pcl::io::savePCDFileBinary emits for a pcl::PointCloud<pcl::PointXYZI> (unorganised, default viewpoint): the
     v0.7 header PCDWriter::generateHeader produces and the four fields of every point packed to 16 bytes."""
     c = np.ascontiguousarray(cloud, dtype=_F32).reshape(-1, 4)
-    n = len(c)
-    header = ("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\n"
-              f"WIDTH {n}\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS {n}\nDATA binary\n")
     with open(path, "wb") as f:
-        f.write(header.encode("ascii"))
+        f.write(pcd_binary_header(len(c)))
         f.write(c.tobytes())
 
 

@@ -5,19 +5,24 @@ libmrgfe.so:
   called from apps/mrg_slam_component.cpp:727,781,1097) with its pcl::ApproximateMeanVoxelGrid pass;
 * :func:`remove_points_near` — the other-robot point removal of apps/mrg_slam_component.cpp:396-429;
 * :func:`deskew` — PrefilteringComponent::deskewing (apps/prefiltering_component.cpp:231-292);
+* :meth:`MapCloudStore.publish` / :meth:`MapCloudStore.read` and :class:`MapPublisher` — the map as the message or file its three callers make of
+  it (update_map_cloud_msg, publish_map_service, save_map_service: apps/mrg_slam_component.cpp:712-740, 764-796, 1078-1144) and stored keyframes
+  read back as records (KeyFrame::save, the cloud_msg of publish_graph_service: src/mrg_slam/keyframe.cpp:109, 200);
 * :func:`fill_ground_plane` and :meth:`MapCloudStore.fill_ground` — the ground fill of the first keyframe
   (src/mrg_slam/graph_database.cpp:114-129, src/pcl/fill_ground_plane.cpp).
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import Context, GraphEdge, GroundFillParams, GroundFillResult, KeyframeMsg, KeyframeParams, MrgfeError, check, default_context, lib
+from ._lib import (Context, GraphEdge, GroundFillParams, GroundFillResult, KeyframeMsg, KeyframeParams, MapPublishParams, MapPublishResult, MrgfeError, check, default_context,
+                   lib)
 from .filters import _cloud
-from .io import pointcloud2_from_xyzi
+from .io import pcd_binary_header, pointcloud2_from_xyzi
 
 _fp = C.POINTER(C.c_float)
 ERR_EMPTY = -4  # MRGFE_ERR_EMPTY (include/mrgfe.h)
@@ -94,6 +99,20 @@ class MapCloudStore:
         if getattr(self, "_out", None) is not None and getattr(self, "_out_pinned", False):
             lib().mrgfe_unpin_host_buffer(self._ctx._h, self._out.ctypes.data_as(C.c_void_p))
         self._out, self._out_pinned = None, False
+
+    def _download_buffer(self, rows: int) -> np.ndarray:
+        """The buffer the store keeps between calls for what comes down, with room for ``rows`` 16-byte rows: grown with a quarter of headroom, touched
+        once and page-locked where the runtime allows it (the download is then direct DMA)."""
+        if getattr(self, "_out", None) is None or len(self._out) < rows:
+            self._release_out()
+            self._out = np.empty((rows + rows // 4, 4), dtype=np.float32)
+            self._out[:] = 0  # (touch the pages once, here)
+            try:  # page-locked: the download is direct DMA
+                check(lib().mrgfe_pin_host_buffer(self._ctx._h, self._out.ctypes.data_as(C.c_void_p), self._out.nbytes))
+                self._out_pinned = True
+            except MrgfeError:
+                self._out_pinned = False
+        return self._out
 
     def __del__(self):
         try:
@@ -222,16 +241,7 @@ class MapCloudStore:
         P = np.ascontiguousarray(np.stack([np.asarray(p, dtype=np.float64).T.reshape(16) for p in poses])) if K else np.zeros((0, 16))
         first = np.ascontiguousarray(np.asarray(first_keyframe if first_keyframe is not None else np.zeros(K), dtype=np.uint8))
         cap = max(sum(self.has(int(k)) or 0 for k in keys), 1)
-        if getattr(self, "_out", None) is None or len(self._out) < cap:
-            self._release_out()
-            self._out = np.empty((cap + cap // 4, 4), dtype=np.float32)
-            self._out[:] = 0  # (touch the pages once, here)
-            try:  # page-locked: the download is direct DMA
-                check(lib().mrgfe_pin_host_buffer(self._ctx._h, self._out.ctypes.data_as(C.c_void_p), self._out.nbytes))
-                self._out_pinned = True
-            except MrgfeError:
-                self._out_pinned = False
-        out = self._out
+        out = self._download_buffer(cap)
         m = C.c_size_t(0)
         try:
             check(lib().mrgfe_map_store_generate(self._h, K, ks.ctypes.data_as(C.POINTER(C.c_uint64)), P.ctypes.data_as(C.POINTER(C.c_double)),
@@ -242,6 +252,182 @@ class MapCloudStore:
                 return None
             raise
         return out[: m.value].copy() if copy else out[: m.value]
+
+    def _publish_args(self, keys, poses, first_keyframe, resolution, min_points_per_voxel, distance_far_thresh, skip_first_cloud, point_step, offsets):
+        K = len(keys)
+        ks = np.ascontiguousarray(np.asarray(keys, dtype=np.uint64))
+        P = np.ascontiguousarray(np.stack([np.asarray(p, dtype=np.float64).T.reshape(16) for p in poses])) if K else np.zeros((0, 16))
+        first = np.ascontiguousarray(np.asarray(first_keyframe if first_keyframe is not None else np.zeros(K), dtype=np.uint8))
+        offs = [np.asarray(o, dtype=np.float64).reshape(3).astype(np.float32) for o in offsets]  # (*zero_utm).cast<float>()
+        p = MapPublishParams(float(resolution), int(min_points_per_voxel), float(distance_far_thresh), int(bool(skip_first_cloud)), int(point_step), len(offs))
+        for i, o in enumerate(offs[:2]):  # (a third offset: n_offsets = 3, which the library refuses)
+            p.offsets[3 * i:3 * i + 3] = [float(v) for v in o]
+        return K, ks, P, first, p
+
+    def publish(self, keys, poses, first_keyframe=None, resolution: float = 0.1, min_points_per_voxel: int = 1, distance_far_thresh: float = 10000.0,
+                skip_first_cloud: bool = False, point_step: int = 32, offsets=(), copy: bool = True):
+        """``mrgfe_map_store_publish``: the map of :meth:`generate` — same points, order and bits — as the records its callers send or save, written on the
+        device: ``point_step`` 32 gives the ``pcl::toROSMsg`` records (x, y, z, 1.0f, intensity, three zero words), 16 the packed points of a binary PCD's
+        body; ``offsets``: up to two (x, y, z) added in f32 one after the other behind the voxel filter (zero_utm, then zero_enu:
+        apps/mrg_slam_component.cpp:1104-1116).  Returns the message as a dict — ``data`` (uint8), ``width``, ``height``, ``point_step``, ``row_step``,
+        ``fields``, ``is_dense``, ``is_bigendian``, and ``n_unfiltered`` (the points before the voxel filter) — which ``io.xyzi_from_pointcloud2``,
+        ``io.layout_from_fields`` and :meth:`keyframe_callback` take back, or None where the reference returns nullptr.  The download lands in the
+        buffer :meth:`generate` uses; ``copy=False`` returns a view of it that the next call overwrites."""
+        K, ks, P, first, p = self._publish_args(keys, poses, first_keyframe, resolution, min_points_per_voxel, distance_far_thresh, skip_first_cloud, point_step, offsets)
+        cap = max(sum(self.has(int(k)) or 0 for k in keys), 1)
+        out = self._download_buffer(cap * (2 if int(point_step) == 32 else 1)).reshape(-1).view(np.uint8)
+        r = MapPublishResult()
+        try:
+            check(lib().mrgfe_map_store_publish(self._h, K, ks.ctypes.data_as(C.POINTER(C.c_uint64)), P.ctypes.data_as(C.POINTER(C.c_double)),
+                                                first.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(p), out.ctypes.data_as(C.c_void_p), cap * int(point_step), C.byref(r)))
+        except MrgfeError as e:
+            if e.status == ERR_EMPTY:
+                return None
+            raise
+        data = out[: r.data_bytes]
+        return _map_message(data.copy() if copy else data, r)
+
+    def publish_device(self, keys, poses, first_keyframe=None, resolution: float = 0.1, min_points_per_voxel: int = 1, distance_far_thresh: float = 10000.0,
+                       skip_first_cloud: bool = False, point_step: int = 32, offsets=()):
+        """``mrgfe_map_store_publish_device``: :meth:`publish` with the records left in the store's workspace.  Returns the message dict with ``data`` None and
+        ``dev_ptr`` (0 for an empty map): device memory that is complete on return and valid until the next publish, read or the end of this store."""
+        K, ks, P, first, p = self._publish_args(keys, poses, first_keyframe, resolution, min_points_per_voxel, distance_far_thresh, skip_first_cloud, point_step, offsets)
+        r, d = MapPublishResult(), C.c_void_p()
+        try:
+            check(lib().mrgfe_map_store_publish_device(self._h, K, ks.ctypes.data_as(C.POINTER(C.c_uint64)), P.ctypes.data_as(C.POINTER(C.c_double)),
+                                                       first.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(p), C.byref(d), C.byref(r)))
+        except MrgfeError as e:
+            if e.status == ERR_EMPTY:
+                return None
+            raise
+        msg = _map_message(None, r)
+        msg["dev_ptr"] = int(d.value or 0)
+        return msg
+
+    def read(self, keys, point_step: int = 32):
+        """``mrgfe_map_store_read``: the stored clouds of ``keys`` (a key may repeat) as records — ``uint8 [n_i, point_step]`` arrays, views of one buffer —
+        with ``point_step`` 32 (``io.pcl_xyzi_records``: the cloud_msg of publish_graph_service) or 16 (the packed points: a binary PCD's body).  One
+        launch at most and one wait for the whole list."""
+        keys = [int(k) for k in keys]
+        step = int(point_step)
+        ks = np.ascontiguousarray(np.asarray(keys, dtype=np.uint64))
+        cap = sum(self.has(k) or 0 for k in keys) * (step if step in (16, 32) else 0)
+        data = np.empty(max(cap, 1), dtype=np.uint8)
+        offs = np.zeros(len(keys) + 1, dtype=np.uint64)
+        check(lib().mrgfe_map_store_read(self._h, len(keys), ks.ctypes.data_as(C.POINTER(C.c_uint64)), step, data.ctypes.data_as(C.c_void_p), cap,
+                                         offs.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return [data[int(offs[i]):int(offs[i + 1])].reshape(-1, step) for i in range(len(keys))]
+
+    def egress_stats(self) -> dict:
+        """``mrgfe_map_store_egress_stats``: what the last :meth:`publish` / :meth:`read` did — kernel launches of its record stage, host waits of the whole
+        call, bytes brought down, device bytes its workspace grew by."""
+        v = (C.c_int64 * 4)()
+        check(lib().mrgfe_map_store_egress_stats(self._h, v))
+        return dict(zip(("launches", "host_waits", "bytes_down", "workspace_grown"), [int(x) for x in v]))
+
+
+def _map_message(data, r) -> dict:
+    """The sensor_msgs/PointCloud2 members of a published map: what pcl::toROSMsg fills for an unorganised pcl::PointXYZI cloud (four FLOAT32 fields; the
+    padding words of the record are no fields), or the packed layout of ``io.pointcloud2_from_xyzi``."""
+    return {"height": 1, "width": int(r.n_points), "is_dense": False, "is_bigendian": False, "point_step": int(r.point_step), "row_step": int(r.data_bytes),
+            "fields": {"x": 0, "y": 4, "z": 8, "intensity": int(r.off_intensity)}, "data": data, "n_unfiltered": int(r.n_unfiltered)}
+
+
+@dataclass
+class MapRequest:
+    """The members of mrg_slam_msgs/srv/PublishMap and SaveMap the two services read; the defaults are the "not set" values of
+    apps/mrg_slam_component.cpp:774-779 / 1087-1092."""
+
+    resolution: float = 0.0  # 0: map_cloud_resolution
+    min_points_per_voxel: int = -1  # < 0: map_cloud_min_points_per_voxel
+    distance_far_thresh: float = 0.0  # 0: map_cloud_distance_far_thresh
+    skip_first_cloud: bool = False
+    frame_id: str = ""  # empty: map_frame_id
+    utm: bool = False  # SaveMap: add zero_utm to the points
+
+
+class MapPublisher:
+    """Host mirror of the three callers of MapCloudGenerator::generate in MrgSlamComponent over a map store (anything with :meth:`MapCloudStore.publish`'s
+    signature: the logic runs on the CPU against a stand-in):
+
+    * :meth:`update` — update_map_cloud_msg (apps/mrg_slam_component.cpp:712-740) behind ``map_cloud_msg_update_required_``;
+    * :meth:`publish_map` — publish_map_service (:764-796);
+    * :meth:`save_map` — save_map_service (:1078-1144): the PCD and the ``.utm`` file.
+
+    ``set_snapshot`` is what the optimisation timer does at :880-890: the new ``(key, pose, first_keyframe)`` list and the flag."""
+
+    def __init__(self, store, map_cloud_resolution: float = 0.05, map_cloud_min_points_per_voxel: int = 2, map_cloud_distance_far_thresh: float = 10000.0,
+                 map_frame_id: str = "map", zero_utm=None, zero_enu=None):
+        self.store = store
+        self.resolution, self.min_points_per_voxel, self.distance_far_thresh = float(map_cloud_resolution), int(map_cloud_min_points_per_voxel), float(map_cloud_distance_far_thresh)
+        self.map_frame_id = map_frame_id
+        self.zero_utm, self.zero_enu = zero_utm, zero_enu  # GpsProcessor::zero_utm() / zero_enu(): (x, y, z) doubles or None
+        self.snapshot: list = []
+        self.update_required = False
+        self.map_cloud_msg = None
+        self.updated = False  # what the last update_map_cloud_msg returned
+
+    def set_snapshot(self, snapshot) -> None:
+        self.snapshot = [(int(k), np.asarray(T, dtype=np.float64), bool(f)) for k, T, f in snapshot]
+        self.update_required = True
+
+    def _request(self, req):
+        """(resolution, min_points_per_voxel, distance_far_thresh, frame_id) of a request: the config values where it sets none (:774-779)."""
+        resolution = self.resolution if req.resolution == 0 else req.resolution
+        min_points = self.min_points_per_voxel if req.min_points_per_voxel < 0 else req.min_points_per_voxel
+        far = self.distance_far_thresh if req.distance_far_thresh == 0 else req.distance_far_thresh
+        return float(np.float32(resolution)), int(min_points), float(np.float32(far)), (req.frame_id or self.map_frame_id)
+
+    def _publish(self, snapshot, **kw):
+        return self.store.publish([k for k, _, _ in snapshot], [T for _, T, _ in snapshot], [f for _, _, f in snapshot], **kw)
+
+    def update(self):
+        """update_map_cloud_msg: regenerates ``map_cloud_msg`` when the snapshot has changed since the last call, and returns it — the cached message
+        otherwise, and after a generation that gave no cloud; ``updated`` is the reference's return value."""
+        self.updated = False
+        if not self.update_required:
+            return self.map_cloud_msg
+        snapshot, self.update_required = self.snapshot, False
+        msg = self._publish(snapshot, resolution=self.resolution, min_points_per_voxel=self.min_points_per_voxel, distance_far_thresh=self.distance_far_thresh,
+                            skip_first_cloud=False, point_step=32)
+        if msg is None:
+            return self.map_cloud_msg
+        msg["frame_id"] = self.map_frame_id
+        self.map_cloud_msg, self.updated = msg, True
+        return msg
+
+    def publish_map(self, req=None):
+        """publish_map_service: the message to publish, or None (``res->success = false``)."""
+        req = req or MapRequest()
+        resolution, min_points, far, frame_id = self._request(req)
+        msg = self._publish(self.snapshot, resolution=resolution, min_points_per_voxel=min_points, distance_far_thresh=far, skip_first_cloud=bool(req.skip_first_cloud),
+                            point_step=32)
+        if msg is not None:
+            msg["frame_id"] = frame_id
+        return msg
+
+    def save_map(self, req, path: str) -> bool:
+        """save_map_service: the map with zero_utm (only when ``req.utm``) and zero_enu (whenever set) added, as a binary PCD at ``path`` — the header of
+        ``io.write_pcd_binary`` and the 16-byte records as they came down — and ``path + ".utm"`` whenever zero_utm is set (:1121-1124).  The directory
+        is made first (the reference makes it after the ``.utm`` file).  Returns ``res->success``."""
+        resolution, min_points, far, _ = self._request(req)
+        offsets = []
+        if self.zero_utm is not None and req.utm:
+            offsets.append(self.zero_utm)
+        if self.zero_enu is not None:
+            offsets.append(self.zero_enu)
+        msg = self._publish(self.snapshot, resolution=resolution, min_points_per_voxel=min_points, distance_far_thresh=far, skip_first_cloud=bool(req.skip_first_cloud),
+                            point_step=16, offsets=offsets, copy=False)
+        if msg is None:
+            return False
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        if self.zero_utm is not None:
+            with open(path + ".utm", "w") as f:
+                f.write("%.6f %.6f %.6f\n" % tuple(float(v) for v in self.zero_utm))
+        with open(path, "wb") as f:
+            f.write(pcd_binary_header(msg["width"]))
+            f.write(memoryview(msg["data"]))
+        return True
 
 
 class MapCloudGenerator:
