@@ -97,6 +97,11 @@ void mrgfe_dbg_sincosf(const float* x, size_t n, float* sin_out, float* cos_out)
  * correctly rounded — the device library's differs in the last bit on one argument in ten): on the host (on_device = 0, ctx may be NULL) or on the device.
  * tests/test_glibc_exp.py holds the host build against the C library and regenerates the table; tests/test_gpu_primitives.py holds the device against the host. */
 int mrgfe_dbg_exp(mrgfe_ctx* ctx, const double* x, size_t n, int on_device, double* out);
+/* The exp of the float path of the default NDT kernels (csrc/dev_exp.h exp_float_arg: the device library's exp(double) restated with scalar
+ * coefficients) against that library call, on the device, for the `count` <= 2^32 float bit patterns first_bits, first_bits + 1, ... (wrapping):
+ * *mismatches = patterns x for which the bits of exp_float_arg((double)x) differ from exp((double)x) (two NaNs are equal), *first_bad = the first such
+ * pattern in sweep order (0 if none); classes (may be NULL): how many exp_float_arg results were zero, subnormal, infinite, NaN. */
+int mrgfe_dbg_exp_float_args(mrgfe_ctx* ctx, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_bad, uint64_t classes[4]);
 int mrgfe_dbg_ctl_math(mrgfe_ctx* ctx, const double* cases48, int n, int on_device, float* M16, double* tables69, double* x6);
 /* ---- floor detection stages (tests/test_gpu_floor.py; csrc/floor.hip) ------------------------------------------------------------------- */
 /* RandomSampleConsensus<SampleConsensusModelPlane> alone on a cloud (floor_detection_component.cpp:139-145): *has_model, the coefficients of the

@@ -1608,6 +1608,27 @@ int mrgfe_dbg_exp(mrgfe_ctx* ctx, const double* x, size_t n, int on_device, doub
     return st;
 }
 
+int mrgfe_dbg_exp_float_args(mrgfe_ctx* ctx, uint32_t first_bits, uint64_t count, uint64_t* mismatches, uint32_t* first_bad, uint64_t classes[4])
+{
+    if (!ctx || !mismatches || !first_bad || count > (1ull << 32)) { set_error("mrgfe_dbg_exp_float_args: NULL argument or more than 2^32 patterns"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(ctx);
+    MRGFE_TRY(ctx->bind());
+    unsigned long long h[6] = {0, ~0ull, 0, 0, 0, 0};
+    DevBuf dout;  // (freed at the return)
+    MRGFE_TRY(dout.ensure(sizeof(h)));
+    int st = MRGFE_OK;
+    if (hipMemcpyAsync(dout.p, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) st = MRGFE_ERR_HIP;
+    if (st == MRGFE_OK) st = exp_float_args_device(ctx, first_bits, count, dout.as<unsigned long long>());
+    if (st == MRGFE_OK && hipMemcpyAsync(h, dout.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) st = MRGFE_ERR_HIP;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && st == MRGFE_OK) st = MRGFE_ERR_HIP;
+    if (st == MRGFE_ERR_HIP) set_error("mrgfe_dbg_exp_float_args: a HIP call failed");
+    if (st != MRGFE_OK) return st;
+    *mismatches = h[0];
+    *first_bad = h[0] ? first_bits + static_cast<uint32_t>(h[1]) : 0u;
+    if (classes) for (int c = 0; c < 4; ++c) classes[c] = h[2 + c];
+    return MRGFE_OK;
+}
+
 int mrgfe_dbg_ctl_math(mrgfe_ctx* ctx, const double* cases48, int n, int on_device, float* M16, double* tables69, double* x6)
 {
     if (!cases48 || !M16 || !tables69 || !x6 || n < 0) { set_error("mrgfe_dbg_ctl_math: bad argument"); return MRGFE_ERR_INVALID; }

@@ -37,6 +37,9 @@ int ndt_ctl_math_device(mrgfe_ctx* ctx, const double* d_in, int n, float* d_M, d
 int wave_fold_check_device(mrgfe_ctx* ctx, int n_vals, const double* d_in, int cases, double* d_fold, double* d_plain);
 int ndt_ctl_svd_wave_device(mrgfe_ctx* ctx, const double* d_in, int n, double* d_x);  // the wavefront form of the solve, one case per workgroup
 int glibc_exp_device(mrgfe_ctx* ctx, const double* d_x, size_t n, double* d_out);  // diagnostic: glibc_exp (glibc_exp.h) on n doubles
+// diagnostic: exp_float_arg (dev_exp.h) against exp on `count` <= 2^32 float bit patterns from `first_bits`; d_out6 (preset to 0, ~0, 0, 0, 0, 0): mismatches, smallest
+// offending offset, results that are zero / subnormal / infinite / NaN
+int exp_float_args_device(mrgfe_ctx* ctx, uint32_t first_bits, unsigned long long count, unsigned long long* d_out6);
 // diagnostic builds (-DNDT_PHASE_CLOCK): prints the phase clocks of the derivative kernel to stderr; a no-op otherwise
 void ndt_phase_dump();
 // dst = T * src (row-major 3x4 float T in device memory)

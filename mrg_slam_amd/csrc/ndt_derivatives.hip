@@ -20,6 +20,7 @@
 // dependent point -> lookup -> record loads, which is what the byte-model roofline in bench.py is held against.
 #include <cstdio>
 
+#include "dev_exp.h"
 #include "dev_float.h"
 #include "dev_utils.h"
 #include "glibc_exp.h"
@@ -48,9 +49,11 @@ __device__ unsigned long long g_rphase[10];  // ndt_reduce_kernel<true>: sums | 
 constexpr int kTilePts = 256;  // points per tile == threads per workgroup
 
 // exp of the per-pair weight.  The f64 passes (computeHessian, PCL NDT) and everything in reference-order mode call glibc's exp restated (glibc_exp.h): the
-// double the reference's host computes.  The float path of the DEFAULT kernels keeps the device library's: its result differs from glibc's in the last bit of
-// the double on one argument in ten, which survives the cast to float once in ~2^29 pairs (far below the default tree order's own noise), and glibc_exp costs
-// the dominant kernel 5 % (0.585 -> 0.615 ms per launch of a 256-pair step, profiles/ab_libs.sh).  GLIBC = true: the reference-order record kernel.
+// double the reference's host computes.  The float path of the DEFAULT kernels keeps the device library's VALUE: its result differs from glibc's in the last
+// bit of the double on one argument in ten, which survives the cast to float once in ~2^29 pairs (far below the default tree order's own noise), and glibc_exp
+// costs the dominant kernel 5 % (0.585 -> 0.615 ms per launch of a 256-pair step, profiles/ab_libs.sh).  It no longer calls the library: exp_float_arg
+// (dev_exp.h) is the same routine with its Horner steps as three-operand fma on scalar coefficients — bit-identical on every converted float
+// (tests/test_gpu_exp_float_args.py sweeps all 2^32), eight register moves and 16 resident VGPRs less per pair.  GLIBC = true: the reference-order record kernel.
 
 struct Accum {
     double score;
@@ -85,7 +88,7 @@ __device__ __forceinline__ void pair_float_c(Accum& acc, const double (&mean)[3]
     const float qCq = fdot3f(q[0], qC[0], q[1], qC[1], q[2], qC[2]);
     const float arg0 = -gauss_d2f * qCq;
     const float arg = arg0 * 0.5f;
-    float e = static_cast<float>(GLIBC ? glibc_exp(static_cast<double>(arg)) : exp(static_cast<double>(arg)));
+    float e = static_cast<float>(GLIBC ? glibc_exp(static_cast<double>(arg)) : exp_float_arg(static_cast<double>(arg)));
     const float score_inc = static_cast<float>(-gauss_d1 * static_cast<double>(e));
     e = gauss_d2f * e;
     if (e > 1.0f || e < 0.0f || e != e) return;
@@ -152,7 +155,8 @@ __device__ __forceinline__ void pair_float(Accum& acc, const NdtLeafRec& rec, co
 
 // MODE 0: score+gradient+Hessian, 1: score+gradient, 2: Hessian only (double).  NNB: probed voxels (7, 1 or 27).
 // Register budget: the full variant (43 f64 accumulators) is latency-bound at 2 waves/SIMD; capping it at 168 VGPRs
-// (3 waves/SIMD, ~44 B/lane of spill) is 12 % faster on MI355X, 128 VGPRs (4 waves) spills too much (measured).
+// (3 waves/SIMD) is 12 % faster on MI355X, 128 VGPRs (4 waves) spills too much (measured).  At 168 the fused DIRECT7 kernel spilled 15 VGPRs
+// (64 B/lane of scratch) while the exp coefficients lived in vector registers; with them in scalar registers (dev_exp.h) it spills none.
 #ifndef NDT_MODE0_WAVES
 #define NDT_MODE0_WAVES 3
 #endif
@@ -369,10 +373,14 @@ __device__ __forceinline__ void ndt_derivatives_item(NdtDerivShared<NNB>& sh, co
                 for (int n = 0; n < NNB; ++n) ids[n] = -1;
             } else if (MODE == 1) {
                 // ---- score + gradient (line-search trials), one lane per POINT ---------------------------------------------------
-                // ~110 instructions per pair: less than the queue machinery around them costs (staging through LDS, the offsets, three
-                // barriers per tile — this variant spent two thirds of a tile there), so the lane walks its own voxels in probe order
-                // although a third of the lanes idle in every step (0 - 7 occupied neighbours, 4.4 on average).  Same per-pair float
-                // terms; the f64 sums run per point instead of per queue slot (the oracle's GPU-order mode follows).
+                // 111 VALU instructions per pair (119 before dev_exp.h): less than the queue machinery around them costs (staging through
+                // LDS, the offsets, three barriers per tile — this variant spent two thirds of a tile there), so the lane walks its own
+                // voxels in probe order although a third of the lanes idle in every step (0 - 7 occupied neighbours, 4.4 on average; a
+                // wavefront skips a probe none of its lanes has).  Same per-pair float terms; the f64 sums run per point instead of per
+                // queue slot (the oracle's GPU-order mode follows).
+                // (each lane's occupied voxels packed into its own LDS column and the loop run to the wavefront's largest count — 5.5 ->
+                // 4.9 steps per wavefront on the bench scans, same sums — was measured for this kind and the f64 Hessian kind: a rolled
+                // loop of 112 instructions and one LDS read, kernel 0.7 x the code size, but ~1 % SLOWER per launch.  Not kept.)
                 nb_mine += cnt;
                 if (cnt) {
                     float xj[8];
@@ -1564,6 +1572,47 @@ int glibc_exp_device(mrgfe_ctx* ctx, const double* d_x, size_t n, double* d_out)
 {
     if (n == 0) return MRGFE_OK;
     hipLaunchKernelGGL(glibc_exp_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, ctx->stream, d_x, n, d_out);
+    MRGFE_HIP_CHECK(hipGetLastError());
+    return MRGFE_OK;
+}
+
+// ---- diagnostic: exp_float_arg (dev_exp.h) against the device library's exp on a range of float bit patterns (tests/test_gpu_exp_float_args.py sweeps all 2^32)
+// out[0] patterns whose two doubles differ in some bit (two NaNs compare equal), out[1] the smallest offset of one (~0 if none),
+// out[2..5] exp_float_arg results that are zero / subnormal / infinite / NaN.  64 patterns per thread, so a workgroup adds to `out` six times at the most.
+constexpr uint32_t kExpSweepPerThread = 64;
+__global__ __launch_bounds__(256) void exp_float_args_kernel(uint32_t first_bits, unsigned long long count, unsigned long long* __restrict__ out)
+{
+    __shared__ unsigned long long s_out[6];
+    if (threadIdx.x < 6) s_out[threadIdx.x] = threadIdx.x == 1 ? ~0ull : 0ull;
+    __syncthreads();
+    unsigned long long bad = 0, first = ~0ull, cls[4] = {0, 0, 0, 0};
+    const unsigned long long base = static_cast<unsigned long long>(blockIdx.x) * (256ull * kExpSweepPerThread) + threadIdx.x;
+    for (uint32_t k = 0; k < kExpSweepPerThread; ++k) {
+        const unsigned long long off = base + 256ull * k;  // (consecutive lanes, consecutive patterns)
+        if (off >= count) break;
+        const double x = static_cast<double>(__uint_as_float(first_bits + static_cast<uint32_t>(off)));
+        const double mine = exp_float_arg(x), theirs = exp(x);
+        const unsigned long long mb = static_cast<unsigned long long>(__double_as_longlong(mine)), tb = static_cast<unsigned long long>(__double_as_longlong(theirs));
+        if (mb != tb && !(mine != mine && theirs != theirs)) { ++bad; first = off < first ? off : first; }
+        const unsigned long long mag = mb & 0x7fffffffffffffffull;
+        cls[0] += mag == 0;
+        cls[1] += mag != 0 && mag < 0x0010000000000000ull;
+        cls[2] += mag == 0x7ff0000000000000ull;
+        cls[3] += mag > 0x7ff0000000000000ull;
+    }
+    if (bad) { atomicAdd(&s_out[0], bad); atomicMin(&s_out[1], first); }
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        if (cls[c]) atomicAdd(&s_out[2 + c], cls[c]);
+    __syncthreads();
+    if (threadIdx.x < 6 && threadIdx.x != 1 && s_out[threadIdx.x]) atomicAdd(&out[threadIdx.x], s_out[threadIdx.x]);
+    if (threadIdx.x == 1 && s_out[1] != ~0ull) atomicMin(&out[1], s_out[1]);
+}
+int exp_float_args_device(mrgfe_ctx* ctx, uint32_t first_bits, unsigned long long count, unsigned long long* d_out6)
+{
+    if (count == 0) return MRGFE_OK;
+    const unsigned long long per_block = 256ull * kExpSweepPerThread;
+    hipLaunchKernelGGL(exp_float_args_kernel, dim3(static_cast<unsigned>((count + per_block - 1) / per_block)), dim3(256), 0, ctx->stream, first_bits, count, d_out6);
     MRGFE_HIP_CHECK(hipGetLastError());
     return MRGFE_OK;
 }
