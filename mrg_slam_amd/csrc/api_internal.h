@@ -131,6 +131,8 @@ int batch_align_abandon(mrgfe_batch* b);
 // node.cpp): entered exactly as mrgfe_batch_add_pair_from_store enters a store keyframe — for the GICP family the covariances are cached under `key`,
 // ICP_HIP and the NDTs cache nothing.  The cloud must stay valid as caller device memory does.  Returns the pair index or an error (< 0).
 int batch_add_pair_device_keyed(mrgfe_batch* b, int target, uint64_t key, const void* d_xyzi, size_t n, const float guess[16]);
+// Keyframe `key` of a map store, on whatever device it is: its packed cloud, complete (the store's stream has been waited for).  Takes the store's lock alone.
+int map_store_lookup(const char* fn, struct mrgfe_map_store* s, uint64_t key, const float4** p, size_t* n);
 
 // map store: keyframe clouds resident in HBM (include/mrgfe.h); its entry points are in api.cpp, a batch takes targets and pairs out of it
 struct mrgfe_map_store {

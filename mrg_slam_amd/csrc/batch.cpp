@@ -18,6 +18,7 @@
 #include "api_internal.h"
 #include "fit_select.h"
 #include "ndt_derivatives.h"
+#include "resident_cache.h"
 
 using namespace mrgfe;
 
@@ -42,16 +43,16 @@ struct mrgfe_batch {
     // into (the first fit_sets_used of fit_sets: a later build takes the sets behind them).  mrgfe_batch_clear forgets both.
     std::vector<char>   fit_valid;
     size_t              fit_sets_used = 0;
-    // keyframe store (mrgfe_batch_add_pair_keyed): packed clouds and GICP covariances by caller-chosen key, resident across clears
+    // keyframe store (mrgfe_batch_add_pair_keyed): packed clouds and GICP covariances by caller-chosen key, resident across clears.  An era of the
+    // cache is one batch: what was named since the last clear / clear_pairs is in use.
     struct Keyframe {
-        DevBuf   cloud, cov;
+        DevBuf   cloud, cov;  // (no cloud: an entry of mrgfe_batch_add_pair_from_store, whose cloud a map store or a node member's replica owns)
         uint32_t n = 0;
-        int      cov_k = 0;       // k_correspondences the covariances were computed with; 0: none yet
-        uint64_t last_epoch = 0;  // batch epoch (number of clears) of the last use
-        uint64_t last_tick = 0;
+        int      cov_k = 0;   // k_correspondences the covariances were computed with; 0: none yet
         size_t   bytes() const { return cloud.cap + cov.cap; }
     };
-    std::unordered_map<uint64_t, std::unique_ptr<Keyframe>> store;
+    using Store = ResidentCache<uint64_t, Keyframe>;
+    Store store;
     std::vector<uint64_t> pair_key;  // per pair; 0: not from the store
     FitStats   fit_total;             // getFitnessScore passes of the last align(), all waves added up
     FitSelectStats select_stats;      // the last mrgfe_batch_align_best
@@ -66,8 +67,6 @@ struct mrgfe_batch {
     } select;
     std::unique_ptr<NdtSnapshotPort> port;  // early fitness passes (mrgfe_batch_align)
     Event      uploads_done;  // recorded on ctx->stream before helper streams read the batch's clouds (upload_cloud is stream-ordered only)
-    uint64_t epoch = 1, tick = 0;
-    size_t   store_cap = size_t(16384) << 20;
     // mrgfe_batch_timing: the reference's per-candidate time (loop_detector.cpp:22-34): from the clear that starts queueing a batch to its records
     std::chrono::steady_clock::time_point t_queue;
     bool     t_queue_set = false;
@@ -96,20 +95,42 @@ struct mrgfe_batch {
     std::unique_ptr<Async> async;
 };
 
-// drop least recently used keyframes that the current batch does not reference until `need` more bytes fit
-static void store_make_room(mrgfe_batch* b, size_t need)
+// The store's entry for keyframe `key` with `n` points, for a pair that `fn` is adding: the resident one, or a fresh one after room was made for it — with `own_cloud`
+// its packed cloud, uploaded from `xyzi`; without, for the covariances alone.  An entry that does not fit (another size, or no cloud where one is to be owned) is
+// replaced, unless this batch already uses it.  The context is locked and bound.
+static int store_entry(mrgfe_batch* b, const char* fn, uint64_t key, size_t n, bool own_cloud, const float* xyzi, size_t stride, mrgfe_batch::Store::Entry** out)
 {
-    size_t total = 0;
-    for (auto& kv : b->store) total += kv.second->bytes();
-    while (total + need > b->store_cap) {
-        uint64_t victim = 0, best = ~uint64_t(0);
-        for (auto& kv : b->store)
-            if (kv.second->last_epoch < b->epoch && kv.second->last_tick < best) { best = kv.second->last_tick; victim = kv.first; }
-        if (!victim) return;  // everything left is in use: the store grows past its cap for this batch
-        auto it = b->store.find(victim);
-        total -= it->second->bytes();
-        b->store.erase(it);
+    mrgfe_batch::Store::Entry* e = b->store.find(key);
+    if (e && e->data.n == n && (e->data.cloud.p || !own_cloud)) { *out = e; return MRGFE_OK; }
+    if (own_cloud && n && !xyzi) { set_error("%s: key %llu is not in the store (or has another size) and no cloud was given", fn, static_cast<unsigned long long>(key)); return MRGFE_ERR_INVALID; }
+    if (e && b->store.in_use(*e)) { set_error("%s: key %llu is already used in this batch with %u points", fn, static_cast<unsigned long long>(key), e->data.n); return MRGFE_ERR_INVALID; }
+    b->store.erase(key);  // (the entry that does not fit, if there is one)
+    b->store.make_room((own_cloud ? n * 16 : 0) + (keeps_covariances(b->params) ? n * 48 : 0));
+    if (!(e = b->store.find_or_insert(key))) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+    e->data.n = static_cast<uint32_t>(n);
+    if (own_cloud) {
+        // (ICP_HIP keeps the cloud alone and the entry never grows: mrgfe_batch_store_bytes counts 16 bytes per point, no allocation headroom)
+        DevBuf& c = e->data.cloud;
+        int st = b->params.method == MRGFE_ICP_HIP ? c.ensure_exact(std::max<size_t>(n, 1) * 16) : c.ensure(std::max<size_t>(n, 1) * 16);
+        if (st == MRGFE_OK && n) st = upload_cloud(b->ctx, xyzi, n, stride, c.p);
+        if (st != MRGFE_OK) { b->store.erase(key); return st; }
     }
+    *out = e;
+    return MRGFE_OK;
+}
+
+// pair (target, the packed device cloud `p`) of keyframe `key`; its store entry `e` (null: nothing is kept for it) is named by the batch
+static int add_stored_pair(mrgfe_batch* b, int target, uint64_t key, mrgfe_batch::Store::Entry* e, const void* p, size_t n, const float guess[16])
+{
+    if (e) b->store.touch(*e);
+    float g[16];
+    col2row(guess, g);
+    const int pair = b->book.add_pair_device(target, p, n, g);
+    if (pair >= 0 && e) {
+        if (b->pair_key.size() <= static_cast<size_t>(pair)) b->pair_key.resize(pair + 1, 0);
+        b->pair_key[pair] = key;
+    }
+    return pair;
 }
 
 extern "C" {
@@ -129,7 +150,7 @@ int mrgfe_batch_create(mrgfe_ctx* ctx, const mrgfe_reg_params* params, mrgfe_bat
         if (!b) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
         b->params = *params;
         if (is_ndt(params->method)) b->ndt = std::make_unique<NdtEngine>(ctx, ndt_params_from(*params), &b->book);
-        if (const char* e = std::getenv("MRGFE_KEYFRAME_STORE_MB")) b->store_cap = static_cast<size_t>(std::max(0.0, std::atof(e))) << 20;
+        b->store.set_cap(mrgfe_batch::Store::cap_from_env(size_t(16384) << 20));
         *out = b.release();
         return MRGFE_OK;
     });
@@ -277,7 +298,7 @@ int mrgfe_batch_clear(mrgfe_batch* b)
     b->fit_valid.clear();
     b->fit_sets_used = 0;
     b->pair_key.clear();
-    ++b->epoch;  // stored keyframes stay; none is referenced by the (now empty) batch
+    b->store.next_era();  // stored keyframes stay; none is referenced by the (now empty) batch
     b->t_queue = std::chrono::steady_clock::now();  // mrgfe_batch_timing: the next align's time starts where its queueing starts
     b->t_queue_set = true;
     return MRGFE_OK;
@@ -289,7 +310,7 @@ int mrgfe_batch_clear_pairs(mrgfe_batch* b)
     // the targets, the engines' state for them (NdtEngine's grids, one GicpEngine per target, the fitness grids) and the book's uploads stay
     b->book.clear_pairs();
     b->pair_key.clear();
-    ++b->epoch;
+    b->store.next_era();
     b->t_queue = std::chrono::steady_clock::now();
     b->t_queue_set = true;
     return MRGFE_OK;
@@ -368,73 +389,42 @@ int mrgfe_batch_add_pair_keyed(mrgfe_batch* b, int target, uint64_t key, const f
         MRGFE_LOCK(b->ctx);
         MRGFE_TRY(b->ctx->bind());
         if (n > 0x7fffffffu) { set_error("cloud too large"); return MRGFE_ERR_INVALID; }
-        mrgfe_batch::Keyframe* kf = nullptr;
-        auto it = b->store.find(key);
-        if (it != b->store.end() && it->second->n == n && it->second->cloud.p) {  // (an entry of mrgfe_batch_add_pair_from_store holds covariances and no cloud)
-            kf = it->second.get();
-        } else {
-            if (n && !xyzi) { set_error("mrgfe_batch_add_pair_keyed: key %llu is not in the store (or has another size) and no cloud was given", static_cast<unsigned long long>(key)); return MRGFE_ERR_INVALID; }
-            if (it != b->store.end()) {  // same key, different cloud: replace — unless this batch already uses the old one
-                if (it->second->last_epoch == b->epoch) { set_error("mrgfe_batch_add_pair_keyed: key %llu is already used in this batch with %u points", static_cast<unsigned long long>(key), it->second->n); return MRGFE_ERR_INVALID; }
-                b->store.erase(it);
-            }
-            store_make_room(b, n * 16 + (keeps_covariances(b->params) ? n * 48 : 0));
-            std::unique_ptr<mrgfe_batch::Keyframe> fresh(new (std::nothrow) mrgfe_batch::Keyframe());
-            if (!fresh) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-            // (ICP_HIP keeps the cloud alone and the entry never grows: mrgfe_batch_store_bytes counts 16 bytes per point, no allocation headroom)
-            if (b->params.method == MRGFE_ICP_HIP) MRGFE_TRY(fresh->cloud.ensure_exact(std::max<size_t>(n, 1) * 16));
-            else                                   MRGFE_TRY(fresh->cloud.ensure(std::max<size_t>(n, 1) * 16));
-            if (n) MRGFE_TRY(upload_cloud(b->ctx, xyzi, n, stride, fresh->cloud.p));
-            fresh->n = static_cast<uint32_t>(n);
-            kf = fresh.get();
-            b->store[key] = std::move(fresh);
-        }
-        kf->last_epoch = b->epoch;
-        kf->last_tick = ++b->tick;
-        float g[16];
-        col2row(guess, g);
-        const int pair = b->book.add_pair_device(target, kf->cloud.p, n, g);
-        if (pair >= 0) {
-            if (b->pair_key.size() <= static_cast<size_t>(pair)) b->pair_key.resize(pair + 1, 0);
-            b->pair_key[pair] = key;
-        }
-        return pair;
+        mrgfe_batch::Store::Entry* e = nullptr;
+        MRGFE_TRY(store_entry(b, "mrgfe_batch_add_pair_keyed", key, n, true, xyzi, stride, &e));
+        return add_stored_pair(b, target, key, e, e->data.cloud.p, n, guess);
     });
 }
 int mrgfe_batch_has_cloud(const mrgfe_batch* b, uint64_t key, size_t* n)
 {
     if (!b || key == 0) return 0;
     MRGFE_LOCK(b->ctx);
-    auto it = b->store.find(key);
-    if (it == b->store.end() || !it->second->cloud.p) return 0;  // (no cloud: an entry of mrgfe_batch_add_pair_from_store)
-    if (n) *n = it->second->n;
+    const mrgfe_batch::Store::Entry* e = b->store.find(key);
+    if (!e || !e->data.cloud.p) return 0;  // (no cloud: an entry of mrgfe_batch_add_pair_from_store)
+    if (n) *n = e->data.n;
     return 1;
 }
 size_t mrgfe_batch_store_bytes(const mrgfe_batch* b)
 {
     if (!b) return 0;
     MRGFE_LOCK(b->ctx);
-    size_t total = 0;
-    for (auto& kv : b->store) total += kv.second->bytes();
-    return total;
+    return b->store.bytes();
 }
 int mrgfe_batch_forget(mrgfe_batch* b, uint64_t key)
 {
     if (!b) { set_error("NULL batch"); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(b->ctx);
     MRGFE_TRY(b->ctx->bind());
-    for (auto it = b->store.begin(); it != b->store.end();) {
-        if (key != 0 && it->first != key) { ++it; continue; }
-        if (it->second->last_epoch == b->epoch && !b->pair_key.empty()) { set_error("mrgfe_batch_forget: key %llu is used by the current batch (clear it first)", static_cast<unsigned long long>(it->first)); return MRGFE_ERR_STATE; }
-        it = b->store.erase(it);
-    }
+    if (!b->pair_key.empty())  // (no keyed pair: the batch reads nothing of the store)
+        for (auto& kv : b->store)
+            if ((key == 0 || kv.first == key) && b->store.in_use(kv.second)) { set_error("mrgfe_batch_forget: key %llu is used by the current batch (clear it first)", static_cast<unsigned long long>(kv.first)); return MRGFE_ERR_STATE; }
+    if (key == 0) b->store.clear();
+    else          b->store.erase(key);
     return MRGFE_OK;
 }
-// Keyframe `key` of a map store for a batch on the same device: looked up, and the store's stream waited for (mrgfe_map_store_add uploads asynchronously), under
-// the store's lock ALONE — it is released before the caller takes the batch's lock, so no thread ever holds both context locks.
-static int store_lookup(const char* fn, const mrgfe_batch* b, mrgfe_map_store* s, uint64_t key, const float4** p, size_t* n)
+// (api_internal.h) Keyframe `key` of a map store: looked up, and the store's stream waited for (mrgfe_map_store_add uploads asynchronously), under the store's
+// lock ALONE — it is released before the caller takes the batch's or the node's lock, so no thread ever holds two of them.
+extern "C++" int map_store_lookup(const char* fn, mrgfe_map_store* s, uint64_t key, const float4** p, size_t* n)
 {
-    if (s->ctx->device != b->ctx->device) { set_error("%s: the store is on device %d, the batch on device %d", fn, s->ctx->device, b->ctx->device); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(s->ctx);
     MRGFE_TRY(s->ctx->bind());
     auto it = s->clouds.find(key);
@@ -443,6 +433,12 @@ static int store_lookup(const char* fn, const mrgfe_batch* b, mrgfe_map_store* s
     *p = it->second.p;
     *n = it->second.n;
     return MRGFE_OK;
+}
+// ... for a batch, which reads the store's memory in place: on the same device
+static int store_lookup(const char* fn, const mrgfe_batch* b, mrgfe_map_store* s, uint64_t key, const float4** p, size_t* n)
+{
+    if (s->ctx->device != b->ctx->device) { set_error("%s: the store is on device %d, the batch on device %d", fn, s->ctx->device, b->ctx->device); return MRGFE_ERR_INVALID; }
+    return map_store_lookup(fn, s, key, p, n);
 }
 int mrgfe_batch_add_target_from_store(mrgfe_batch* b, mrgfe_map_store* s, uint64_t key)
 {
@@ -462,33 +458,9 @@ static int add_pair_device_keyed(mrgfe_batch* b, const char* fn, int target, uin
 {
     MRGFE_TRY(b->ctx->bind());
     if (target < 0 || target >= b->book.n_targets()) { set_error("%s: target index %d out of range", fn, target); return MRGFE_ERR_INVALID; }
-    mrgfe_batch::Keyframe* kf = nullptr;
-    if (keeps_covariances(b->params)) {  // the covariances of the keyframe are cached under its key, next to no cloud (the store has it)
-        auto it = b->store.find(key);
-        if (it != b->store.end() && it->second->n != n) {
-            if (it->second->last_epoch == b->epoch) { set_error("%s: key %llu is already used in this batch with %u points", fn, static_cast<unsigned long long>(key), it->second->n); return MRGFE_ERR_INVALID; }
-            b->store.erase(it);
-            it = b->store.end();
-        }
-        if (it == b->store.end()) {
-            store_make_room(b, n * 48);
-            std::unique_ptr<mrgfe_batch::Keyframe> fresh(new (std::nothrow) mrgfe_batch::Keyframe());
-            if (!fresh) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-            fresh->n = static_cast<uint32_t>(n);
-            it = b->store.emplace(key, std::move(fresh)).first;
-        }
-        kf = it->second.get();
-    }
-    float g[16];
-    col2row(guess, g);
-    const int pair = b->book.add_pair_device(target, p, n, g);
-    if (pair >= 0 && kf) {
-        kf->last_epoch = b->epoch;
-        kf->last_tick = ++b->tick;
-        if (b->pair_key.size() <= static_cast<size_t>(pair)) b->pair_key.resize(pair + 1, 0);
-        b->pair_key[pair] = key;
-    }
-    return pair;
+    mrgfe_batch::Store::Entry* e = nullptr;
+    if (keeps_covariances(b->params)) MRGFE_TRY(store_entry(b, fn, key, n, false, nullptr, 0, &e));
+    return add_stored_pair(b, target, key, e, p, n, guess);
 }
 int mrgfe_batch_add_pair_from_store(mrgfe_batch* b, int target, mrgfe_map_store* s, uint64_t key, const float guess[16])
 {
@@ -739,9 +711,9 @@ static int gicp_align_batch(mrgfe_batch* b)
         bp.ext_cov = nullptr;
         bp.ext_cov_k = nullptr;
         if (static_cast<size_t>(i) < b->pair_key.size() && b->pair_key[i]) {
-            mrgfe_batch::Keyframe* kf = b->store.at(b->pair_key[i]).get();
-            bp.ext_cov = &kf->cov;
-            bp.ext_cov_k = &kf->cov_k;
+            mrgfe_batch::Keyframe& kf = b->store.find(b->pair_key[i])->data;  // (in use since the pair was added: it is there, and stays where it is)
+            bp.ext_cov = &kf.cov;
+            bp.ext_cov_k = &kf.cov_k;
         }
     }
     if (b->params.method == MRGFE_ICP_HIP) return b->gicp_batch->align_all_icp(b->gicp, book, b->gicp_pairs);

@@ -32,6 +32,7 @@
 
 #include "api_internal.h"
 #include "fit_select.h"
+#include "resident_cache.h"
 
 using namespace mrgfe;
 
@@ -91,12 +92,13 @@ struct PairDecl {
     float        guess[16];
     StoreRef     from = {};
 };
-struct ResidentCloud {
-    DevBuf   buf;
-    size_t   n = 0;
-    uint64_t last_use = 0;  // serial of the member's align call that named it last
-    bool     in_batch = false;  // a target of the member's batch reads it: it stays until the batch is cleared (mrgfe_node_clear_pairs keeps targets built)
-};
+// A member's resident clouds, one cache and one budget for both kinds: the caller's keyed targets and the replicas of map-store keyframes (as targets and as
+// sources) — the same 64-bit key may name one of each.  An era is one member_fill; `held`: a target of the member's batch reads the cloud, which stays
+// until the batch is cleared (mrgfe_node_clear_pairs keeps targets built).  n == 0 over a buffer: not known to be complete, filled again when next named.
+enum CloudKind : uint8_t { kKeyedTarget = 0, kReplica = 1 };
+using CloudKey = std::pair<CloudKind, uint64_t>;
+struct ResidentCloud { DevBuf buf; size_t n = 0; size_t bytes() const { return buf.cap; } };
+using Clouds = ResidentCache<CloudKey, ResidentCloud>;
 
 // JOB_BOUNDS / JOB_FINISH: the two stages of mrgfe_node_align_best; JOB_ABANDON: give up a first stage that succeeded, because another member's failed
 enum Job { JOB_NONE = 0, JOB_ALIGN = 1, JOB_QUIT = 2, JOB_BOUNDS = 3, JOB_FINISH = 4, JOB_ABANDON = 5 };
@@ -118,10 +120,7 @@ struct mrgfe_node {
         std::string  error;
         int          first = 0, count = 0;  // this member's block of the pair list
         std::vector<mrgfe_pair_result> local;
-        std::unordered_map<uint64_t, std::unique_ptr<ResidentCloud>> targets;  // keyed target clouds resident on this member's device
-        std::unordered_map<uint64_t, std::unique_ptr<ResidentCloud>> replicas; // map-store keyframes copied to this member's device, as targets and as sources
-        uint64_t     align_serial = 0;
-        size_t       target_cap = size_t(16) << 30;             // bytes of keyed targets and replicas kept resident (MRGFE_KEYFRAME_STORE_MB, the batch store's cap), LRU beyond it
+        Clouds       clouds;                                    // bounded (MRGFE_KEYFRAME_STORE_MB, a budget beside the batch store's): in the LoopDetector flow every keyframe is a target once
         // mrgfe_node_clear_pairs: the targets the member's batch holds, node target index -> index in the batch, good while batch_gen is the node's target_gen
         std::unordered_map<int, int> built;
         uint64_t     batch_gen = 0;                             // 0: the batch's targets are not to be reused (never filled, a failed call, mrgfe_node_forget)
@@ -164,56 +163,45 @@ int member_fail(Member& m, int status)
     return status;
 }
 
-// room for `need` more bytes of resident clouds under the member's cap: least recently named keyed targets and replicas go first, never one this call has
-// named, never one a target of the member's batch still reads.  The store is bounded (in the LoopDetector flow every keyframe is a target once, so
-// an unbounded store grows by a cloud per keyframe for the life of the process).  The member's context is locked and bound.
-void member_make_room(Member& m, size_t need)
+// The member's resident cloud under `key` with `n` points: found, or filled by `fill(dst)` — a host upload, a same-device copy or a peer copy on the member's
+// stream — after room was made under the member's cap.  A keyed target grows in place; a replica is filled once, so it is allocated exactly
+// (mrgfe_node_store_bytes counts 16 bytes per point) and counted in store_stat.  `have_source`: there is something to fill it from.
+template <class Fill>
+int member_cloud(Member& m, CloudKey key, size_t n, bool have_source, Fill fill, Clouds::Entry** out)
 {
-    size_t held = 0;
-    for (auto& kv : m.targets) held += kv.second->buf.cap;
-    for (auto& kv : m.replicas) held += kv.second->buf.cap;
-    while (held + need > m.target_cap) {
-        std::unordered_map<uint64_t, std::unique_ptr<ResidentCloud>>* from = nullptr;
-        uint64_t victim = 0, oldest = 0;
-        for (auto* map : {&m.targets, &m.replicas})
-            for (auto& kv : *map) {
-                const ResidentCloud& c = *kv.second;
-                if (c.last_use >= m.align_serial || !c.buf.p || c.in_batch || (from && c.last_use >= oldest)) continue;
-                from = map; victim = kv.first; oldest = c.last_use;
-            }
-        if (!from) break;  // everything left is named by this call or built upon: the block's own working set may exceed the cap
-        auto it = from->find(victim);
-        held -= it->second->buf.cap;
-        from->erase(it);
-    }
+    const bool  replica = key.first == kReplica;
+    const char* what = replica ? "keyframe" : "target key";
+    const unsigned long long k = key.second;
+    Clouds::Entry* e = m.clouds.find_or_insert(key);
+    if (!e) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
+    m.clouds.touch(*e);
+    *out = e;
+    ResidentCloud& c = e->data;
+    if (c.n == n && c.buf.p) return MRGFE_OK;
+    if (!have_source) { set_error("member %d: %s %llu is not resident and no cloud was given", m.index, what, k); return MRGFE_ERR_INVALID; }
+    if (e->held) { set_error("member %d: %s %llu is held with %zu points under a built target and named with %zu", m.index, what, k, c.n, n); return MRGFE_ERR_INVALID; }
+    const size_t bytes = std::max<size_t>(n, 1) * 16;
+    MRGFE_LOCK(m.ctx);
+    MRGFE_TRY(m.ctx->bind());
+    c.n = 0;
+    if (replica) c.buf.release();
+    m.clouds.make_room(bytes);
+    MRGFE_TRY(replica ? c.buf.ensure_exact(bytes) : c.buf.ensure(bytes));
+    MRGFE_TRY(fill(c.buf.p));
+    c.n = n;
+    if (replica) { m.store_stat[1] += 1; m.store_stat[2] += static_cast<int64_t>(n * 16); }
+    return MRGFE_OK;
 }
 
 // keyframe `key` of a map store on this member's device: the replica kept under the key, copied store device -> member device on the member's stream when it
 // is not there (the runtime stages the copy where peer access is not enabled)
-int member_replica(Member& m, uint64_t key, size_t n, const StoreRef& from, ResidentCloud** out)
+int member_replica(Member& m, uint64_t key, size_t n, const StoreRef& from, Clouds::Entry** out)
 {
-    std::unique_ptr<ResidentCloud>& rc = m.replicas[key];
-    if (!rc) rc.reset(new (std::nothrow) ResidentCloud());
-    if (!rc) { set_error("out of host memory"); return MRGFE_ERR_INVALID; }
-    rc->last_use = m.align_serial;
-    *out = rc.get();
-    if (rc->n == n && rc->buf.p) return MRGFE_OK;
-    if (rc->in_batch) { set_error("member %d: keyframe %llu is held with %zu points under a built target and named with %zu", m.index, static_cast<unsigned long long>(key), rc->n, n); return MRGFE_ERR_INVALID; }
-    const size_t bytes = std::max<size_t>(n, 1) * 16;
-    MRGFE_LOCK(m.ctx);
-    MRGFE_TRY(m.ctx->bind());
-    rc->n = 0;
-    rc->buf.release();
-    member_make_room(m, bytes);
-    MRGFE_TRY(rc->buf.ensure_exact(bytes));  // (filled once: mrgfe_node_store_bytes counts 16 bytes per point)
-    if (n) {
-        if (from.device == m.device) MRGFE_HIP_CHECK(hipMemcpyAsync(rc->buf.p, from.d, n * 16, hipMemcpyDeviceToDevice, m.ctx->stream));
-        else                         MRGFE_HIP_CHECK(hipMemcpyPeerAsync(rc->buf.p, m.device, from.d, from.device, n * 16, m.ctx->stream));
-    }
-    rc->n = n;
-    m.store_stat[1] += 1;
-    m.store_stat[2] += static_cast<int64_t>(n * 16);
-    return MRGFE_OK;
+    return member_cloud(m, CloudKey{kReplica, key}, n, true, [&](void* dst) -> int {
+        if (n && from.device == m.device) MRGFE_HIP_CHECK(hipMemcpyAsync(dst, from.d, n * 16, hipMemcpyDeviceToDevice, m.ctx->stream));
+        else if (n)                       MRGFE_HIP_CHECK(hipMemcpyPeerAsync(dst, m.device, from.d, from.device, n * 16, m.ctx->stream));
+        return MRGFE_OK;
+    }, out);
 }
 
 // the member's block into its batch: targets in order of first use, pairs in list order (nothing for an empty block).  After mrgfe_node_clear_pairs the
@@ -232,15 +220,14 @@ int member_fill(mrgfe_node* node, Member& m)
     }
 #endif
     if (m.count == 0) return MRGFE_OK;
-    ++m.align_serial;
+    m.clouds.next_era();
     const bool reuse = node->keep_targets && m.batch_gen == node->target_gen;
     m.batch_gen = 0;  // until the block is in
     int st = reuse ? mrgfe_batch_clear_pairs(m.batch.get()) : mrgfe_batch_clear(m.batch.get());
     if (st != MRGFE_OK) return member_fail(m, st);
     if (!reuse) {
         m.built.clear();
-        for (auto& kv : m.targets) kv.second->in_batch = false;
-        for (auto& kv : m.replicas) kv.second->in_batch = false;
+        m.clouds.clear_held();
     }
     std::unordered_map<int, int> local_target;
     for (int i = m.first; i < m.first + m.count; ++i) {
@@ -253,34 +240,17 @@ int member_fill(mrgfe_node* node, Member& m)
             if (bt != m.built.end()) {
                 ti = bt->second;  // built by an earlier align on this target list
                 ++m.store_stat[3];
-            } else if (t.from.store) {
-                if (t.from.device == m.device && node->store_copy == 0) {
-                    ti = mrgfe_batch_add_target_from_store(m.batch.get(), t.from.store, t.key);
-                    ++m.store_stat[0];
-                } else {
-                    ResidentCloud* rc = nullptr;
-                    if ((st = member_replica(m, t.key, t.n, t.from, &rc)) != MRGFE_OK) return member_fail(m, st);
-                    rc->in_batch = true;
-                    ti = mrgfe_batch_add_target_device(m.batch.get(), rc->buf.p, rc->n);
-                }
-            } else if (t.key) {
-                // a keyed target stays resident on this member's device: uploaded once, found again by the next batches that name it
-                std::unique_ptr<ResidentCloud>& rc = m.targets[t.key];
-                if (!rc) rc.reset(new (std::nothrow) ResidentCloud());
-                if (!rc) { set_error("out of host memory"); return member_fail(m, MRGFE_ERR_INVALID); }
-                rc->last_use = m.align_serial;
-                if (rc->n != t.n || !rc->buf.p) {
-                    if (!t.xyzi && t.n) { set_error("member %d: target key %llu is not resident and no cloud was given", m.index, static_cast<unsigned long long>(t.key)); return member_fail(m, MRGFE_ERR_INVALID); }
-                    if (rc->in_batch) { set_error("member %d: target key %llu is held with %zu points under a built target and named with %zu", m.index, static_cast<unsigned long long>(t.key), rc->n, t.n); return member_fail(m, MRGFE_ERR_INVALID); }
-                    MRGFE_LOCK(m.ctx);
-                    if ((st = m.ctx->bind()) != MRGFE_OK) return member_fail(m, st);
-                    member_make_room(m, std::max<size_t>(t.n, 1) * 16);
-                    if ((st = rc->buf.ensure(std::max<size_t>(t.n, 1) * 16)) != MRGFE_OK) return member_fail(m, st);
-                    if ((st = upload_cloud(m.ctx.get(), t.xyzi, t.n, t.stride, rc->buf.p)) != MRGFE_OK) return member_fail(m, st);
-                    rc->n = t.n;
-                }
-                rc->in_batch = true;
-                ti = mrgfe_batch_add_target_device(m.batch.get(), rc->buf.p, rc->n);
+            } else if (t.from.store && t.from.device == m.device && node->store_copy == 0) {
+                ti = mrgfe_batch_add_target_from_store(m.batch.get(), t.from.store, t.key);
+                ++m.store_stat[0];
+            } else if (t.from.store || t.key) {
+                // a replica of a store keyframe, or a keyed target: resident on this member's device, filled once, found again by the next batches that name it
+                Clouds::Entry* rc = nullptr;
+                st = t.from.store ? member_replica(m, t.key, t.n, t.from, &rc)
+                                  : member_cloud(m, CloudKey{kKeyedTarget, t.key}, t.n, t.xyzi || !t.n, [&](void* dst) { return upload_cloud(m.ctx.get(), t.xyzi, t.n, t.stride, dst); }, &rc);
+                if (st != MRGFE_OK) return member_fail(m, st);
+                rc->held = true;
+                ti = mrgfe_batch_add_target_device(m.batch.get(), rc->data.buf.p, rc->data.n);
             } else {
                 ti = mrgfe_batch_add_target(m.batch.get(), t.xyzi, t.n, t.stride);
             }
@@ -295,9 +265,9 @@ int member_fill(mrgfe_node* node, Member& m)
                 ++m.store_stat[0];
             } else {
                 // (the covariances of the GICP family are cached in the batch under the key, as the route above caches them)
-                ResidentCloud* rc = nullptr;
+                Clouds::Entry* rc = nullptr;
                 if ((st = member_replica(m, p.key, p.n, p.from, &rc)) != MRGFE_OK) return member_fail(m, st);
-                pi = batch_add_pair_device_keyed(m.batch.get(), it->second, p.key, rc->buf.p, rc->n, p.guess);
+                pi = batch_add_pair_device_keyed(m.batch.get(), it->second, p.key, rc->data.buf.p, rc->data.n, p.guess);
             }
         } else {
             pi = p.key ? mrgfe_batch_add_pair_keyed(m.batch.get(), it->second, p.key, p.xyzi, p.n, p.stride, p.guess)
@@ -311,7 +281,7 @@ int member_fill(mrgfe_node* node, Member& m)
         const hipError_t e = hipStreamSynchronize(m.ctx->stream);
         if (e != hipSuccess) {
             set_error("member %d: copying keyframes from the map store: %s", m.index, hipGetErrorString(e));
-            for (auto& kv : m.replicas) if (kv.second->last_use == m.align_serial) kv.second->n = 0;  // (not known to be complete; member_fail has the batch cleared before they are named again)
+            for (auto& kv : m.clouds) if (kv.first.first == kReplica && m.clouds.named(kv.second)) kv.second.data.n = 0;  // (not known to be complete; member_fail has the batch cleared before they are named again)
             return member_fail(m, MRGFE_ERR_HIP);
         }
     }
@@ -561,7 +531,7 @@ int mrgfe_node_create(int n_members, const int* device_ids, const mrgfe_reg_para
             Member* m = node->members.back().get();
             m->index = i;
             m->device = device_ids[i];
-            if (const char* e = std::getenv("MRGFE_KEYFRAME_STORE_MB")) m->target_cap = static_cast<size_t>(std::max(0.0, std::atof(e))) << 20;
+            m->clouds.set_cap(Clouds::cap_from_env(size_t(16) << 30));
             mrgfe_ctx*   ctx = nullptr;
             mrgfe_batch* batch = nullptr;
             st = mrgfe_ctx_create(m->device, &ctx);
@@ -666,30 +636,14 @@ int mrgfe_node_add_pair(mrgfe_node* node, int target_index, const float* src_xyz
     return mrgfe_node_add_pair_keyed(node, target_index, 0, src_xyzi, n, stride_bytes, guess);
 }
 
-// Keyframe `key` of a map store on any device: looked up, and the store's stream waited for (mrgfe_map_store_add uploads asynchronously), under the store's
-// lock ALONE, as store_lookup of batch.cpp does it — it is released before the node's lock is taken.
-static int node_store_lookup(const char* fn, mrgfe_map_store* s, uint64_t key, StoreRef* ref, size_t* n)
-{
-    MRGFE_LOCK(s->ctx);
-    MRGFE_TRY(s->ctx->bind());
-    auto it = s->clouds.find(key);
-    if (it == s->clouds.end()) { set_error("%s: keyframe %llu is not in the store", fn, static_cast<unsigned long long>(key)); return MRGFE_ERR_INVALID; }
-    MRGFE_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
-    ref->store = s;
-    ref->d = it->second.p;
-    ref->device = s->ctx->device;
-    *n = it->second.n;
-    return MRGFE_OK;
-}
-
 int mrgfe_node_add_target_from_store(mrgfe_node* node, mrgfe_map_store* store, uint64_t key)
 {
     static const char* fn = "mrgfe_node_add_target_from_store";
     return abi_guard(fn, [&]() -> int {
         if (!node || !store) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
-        StoreRef ref;
+        StoreRef ref{store, nullptr, store->ctx->device};  // (the lookup takes the store's lock alone: it is released before the node's is taken)
         size_t n = 0;
-        MRGFE_TRY(node_store_lookup(fn, store, key, &ref, &n));
+        MRGFE_TRY(map_store_lookup(fn, store, key, &ref.d, &n));
         std::lock_guard<std::mutex> lk(node->api_mu);
         node->targets.push_back(TargetDecl{key, nullptr, n, 16, ref});
         return static_cast<int>(node->targets.size()) - 1;
@@ -704,7 +658,8 @@ int mrgfe_node_add_pair_from_store(mrgfe_node* node, int target_index, mrgfe_map
         PairDecl p;
         p.target = target_index; p.key = key; p.xyzi = nullptr; p.stride = 16;
         std::memcpy(p.guess, guess, sizeof(p.guess));
-        MRGFE_TRY(node_store_lookup(fn, store, key, &p.from, &p.n));
+        p.from.store = store; p.from.device = store->ctx->device;
+        MRGFE_TRY(map_store_lookup(fn, store, key, &p.from.d, &p.n));
         std::lock_guard<std::mutex> lk(node->api_mu);
         if (target_index < 0 || target_index >= static_cast<int>(node->targets.size())) { set_error("%s: target index %d out of range", fn, target_index); return MRGFE_ERR_INVALID; }
         node->pairs.push_back(p);
@@ -860,13 +815,9 @@ int mrgfe_node_forget(mrgfe_node* node, uint64_t cloud_key)
             {
                 MRGFE_LOCK(m->ctx);
                 (void)m->ctx->bind();
-                for (auto* map : {&m->targets, &m->replicas})
-                    for (auto it = map->begin(); it != map->end();) {
-                        if (cloud_key == 0 || it->first == cloud_key) it = map->erase(it);
-                        else ++it;
-                    }
-                for (auto* map : {&m->targets, &m->replicas})
-                    for (auto& kv : *map) kv.second->in_batch = false;  // (the batch is cleared below)
+                if (cloud_key == 0) m->clouds.clear();
+                for (CloudKind kind : {kKeyedTarget, kReplica}) m->clouds.erase(CloudKey{kind, cloud_key});
+                m->clouds.clear_held();  // (the batch is cleared below)
                 m->built.clear();
                 m->batch_gen = 0;
             }
@@ -882,9 +833,7 @@ size_t mrgfe_node_store_bytes(const mrgfe_node* node)
     if (!node) return 0;
     size_t total = 0;
     for (auto& m : node->members) {
-        total += mrgfe_batch_store_bytes(m->batch.get());
-        for (auto& kv : m->targets) total += kv.second->buf.cap;
-        for (auto& kv : m->replicas) total += kv.second->buf.cap;
+        total += mrgfe_batch_store_bytes(m->batch.get()) + m->clouds.bytes();
     }
     return total;
 }

@@ -29,6 +29,13 @@ def test_optimiser_and_bfgs_are_clean_under_asan_ubsan(tmp_path):
     assert "0 failed checks" in out
 
 
+def test_resident_cache_keeps_its_rules_under_asan_ubsan(tmp_path):
+    """csrc/resident_cache.h (the keyed store of the batch and of a node member) beside a naive model over random operations: what is in use stays,
+    the least recently used goes first and only as far as the cap requires, entries never move"""
+    out = _build_and_run(tmp_path, "resident_cache_san", ["-I" + os.path.join(ROOT, "mrg_slam_amd", "csrc"), os.path.join(ROOT, "tests", "sanitize", "resident_cache_san.cpp")])
+    assert "0 failed checks" in out
+
+
 def test_oracle_is_clean_under_asan_ubsan(tmp_path):
     """every restated algorithm of oracle/ once on a small cloud (plus empty inputs), sources linked straight into the sanitized program"""
     src = [os.path.join(ROOT, "oracle", f) for f in ("ndt.cpp", "pcl_ndt.cpp", "filters.cpp", "mapcloud.cpp", "gicp.cpp", "pcl_gicp.cpp")]
