@@ -159,6 +159,15 @@ int mrgfe_ctx_fitness_stats(mrgfe_ctx* ctx, double out[11]);
  * launch, out[1] = queries, out[2] = k, out[3] = candidate points measured (0 unless the diagnostic counters are on,
  * mrgfe_dbg_set_fit_stats), out[4] = k-NN launches on this context so far.  Waits for that launch to finish. */
 int mrgfe_ctx_knn_stats(mrgfe_ctx* ctx, double out[5]);
+/* Which route served the last prefilter chain call on this context (mrgfe_prefilter[_device], mrgfe_scan_callback[_device]):
+ * out[0] = route — 0 the host-driven passes (every stage hands its point count to the host), 1 the device-driven chain (one wait; [distance filter] ->
+ * VOXELGRID -> RADIUS or STATISTICAL with statistical_mean_k in 1..63), 2 the device-driven chain attempted and handed back to the host-driven passes
+ * (same output); out[1] = the device-driven chain's anomaly word (routes 1 and 2): 1 no finite point survived the distance filter, 2 PCL's "leaf size too
+ * small" pass-through, 4 no voxel, 8 a sum of the statistical filter's threshold could have depended on the order of addition, 16 the host's re-check of
+ * that threshold differs from the device's, 256 the outlier filter's search grid needs more cells than its table; out[2..6] = its stage counts (points
+ * after the distance filter, finite among them, voxels, points after the voxel grid, points after the outlier filter; routes 1 and 2); out[7] = points
+ * out; out[8] = chain calls on this context so far; out[9] = calls served device-driven so far. */
+int mrgfe_ctx_prefilter_stats(mrgfe_ctx* ctx, double out[10]);
 
 /* ---- cloud ingest --------------------------------------------------------------------------------- */
 /* replaces pcl::fromROSMsg(*cloud_msg, *cloud) (apps/prefiltering_component.cpp:119-120, scan_matching_odometry_component.cpp:144-145):
@@ -312,8 +321,9 @@ int  mrgfe_prefilter_device(mrgfe_ctx* ctx, const mrgfe_prefilter_params* params
 /* ---- the scan callback in one call (PrefilteringComponent::cloud_callback, apps/prefiltering_component.cpp:116-156) --- */
 /* pcl::fromROSMsg (:119-120) -> deskewing (:125, :231-295) -> pcl_ros::transformPointCloud into base_link_frame (:141-146) -> distance_filter ->
  * downsample -> outlier_removal (:149-151) on the byte payload of a sensor_msgs/PointCloud2.  The payload goes up ONCE as it is; one kernel reads
- * the records, deskews, transforms, stores the packed cloud and (on the usual chain) is the distance filter's first pass; nothing comes down but
- * the chain's status words and, for the host form, the filtered cloud; the usual chain (VOXELGRID + RADIUS) waits for the device once.
+ * the records, deskews, transforms, stores the packed cloud and (on the usual chains) is the distance filter's first pass; nothing comes down but
+ * the chain's status words and, for the host form, the filtered cloud; the usual chains (VOXELGRID + RADIUS, and VOXELGRID + STATISTICAL — the
+ * reference's code default — with statistical_mean_k in 1..63) wait for the device once (mrgfe_ctx_prefilter_stats says which route served a call).
  * The output equals, bit for bit and in order, mrgfe_ingest_pointcloud2 -> mrgfe_deskew (if `deskew`) -> mrgfe_transform_cloud (if `transform`)
  * -> mrgfe_prefilter[_device] for the same inputs.  The reference's quirks are kept: deskewing counts i and n = width * height over the UNFILTERED
  * cloud (:286), non-finite points included; the transform leaves non-finite points as they are; the distance filter is what drops them. */

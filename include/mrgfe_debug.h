@@ -73,10 +73,17 @@ int mrgfe_dbg_node_ndt_rounds(const mrgfe_node* node, int member, int cap, uint3
  * MRGFE_FIT_SWEEP sets the initial value), 0 = round 2's pyramid walk for every queued query.  Any other value only asks.  Returns the
  * setting in effect.  Both give the exact nearest distances (tests/test_gpu_fitness_passes.py). */
 int mrgfe_dbg_set_fit_sweep(int mode);
-/* mrgfe_prefilter / mrgfe_prefilter_device with VoxelGrid + RadiusOutlierRemoval: 1 (default) the stages' point counts stay on the device and the
- * call waits once at its end, 0 every stage reports its count to the host (round 3; also what an unusual scan falls back to); other values
- * query.  Same outputs either way. */
+/* mrgfe_prefilter / mrgfe_prefilter_device with VoxelGrid + RadiusOutlierRemoval or VoxelGrid + StatisticalOutlierRemoval (mean_k in 1..63): 1 (default)
+ * the stages' point counts stay on the device and the call waits once at its end, 0 every stage reports its count to the host (round 3; also what an
+ * unusual scan falls back to); other values query.  Same outputs either way (mrgfe_ctx_prefilter_stats reports the route a call took). */
 int mrgfe_dbg_set_prefilter_device_driven(int mode);
+/* StatisticalOutlierRemoval's threshold from the mean distances dist[n] and the flags valid[n] (1: all mean_k neighbours were found): out[0] = sum of
+ * dist, out[1] = sum of float(dist * dist), out[2] = sum of valid, out[3] = mean + stddev_mul * sqrt(variance) as the reference computes it, out[4] = 1
+ * iff both sums are certified to have the same bits in every order of addition (csrc/sor_threshold.h: the sum is below 2^(q + 52) for 2^q the lowest
+ * set bit of its non-zero terms), out[5] = that q for the terms of out[0] (2147483647: no non-zero term; -2147483647: a negative or non-finite term).
+ * on_device = 0: the reference's sequential f64 loop on the host (ctx may be NULL); 1: the tree reduction and finish kernels of the device-driven
+ * prefilter chain on the uploaded arrays.  One source compiled twice; where out[4] is 1 the two agree bit for bit. */
+int mrgfe_dbg_sor_threshold(mrgfe_ctx* ctx, const float* dist, const uint32_t* valid, size_t n, double stddev_mul, int on_device, double out[6]);
 /* PCL_GICP_HIP (serial pcl::GeneralizedIterativeClosestPoint, registrations.cpp:93-103): 1 (default) the thirteen sums of every cost / gradient
  * evaluation are added in the reference's order, point after point (bit-identical BFGS trajectories; ~4 ns per point and evaluation), 0 in a tree
  * (round 3: faster, and outside the 1e-4 bar on one random scene in fourteen); other values query.  PCL_GICP_OMP_HIP: 1 = pclomp's per-thread chunk

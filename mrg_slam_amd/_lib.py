@@ -19,6 +19,8 @@ MRGFE_OK, ERR_INVALID, ERR_HIP, ERR_OVERFLOW, ERR_EMPTY, ERR_STATE = 0, -1, -2, 
 NDT_HIP, GICP_HIP, SMALL_GICP_HIP, VGICP_HIP, ICP_HIP, PCL_GICP_HIP, PCL_GICP_OMP_HIP, PCL_NDT_HIP = 0, 1, 2, 3, 4, 5, 6, 7
 FIT_EXACT, FIT_PRUNED, FIT_ABOVE_CAP, FIT_SKIPPED = 0, 1, 2, 3  # enum mrgfe_fit_state (mrgfe_batch_align_best)
 SEARCH = {"KDTREE": 0, "DIRECT26": 1, "DIRECT7": 2, "DIRECT1": 3}
+# bits of the device-driven prefilter chain's anomaly word (mrgfe_ctx_prefilter_stats out[1])
+PF_ANOMALY_EMPTY, PF_ANOMALY_OVERFLOW, PF_ANOMALY_NO_VOXEL, PF_ANOMALY_CERTIFICATE, PF_ANOMALY_RECHECK, PF_ANOMALY_CELLS = 1, 2, 4, 8, 16, 256
 
 
 def layout(stride: int, xyz_offset: int = 0, intensity_offset: int = 12) -> int:
@@ -240,6 +242,7 @@ SIGNATURES = {
     "mrgfe_ctx_stream": (_vp, [_vp]),
     "mrgfe_ctx_fitness_stats": (C.c_int, [_vp, _dp]),
     "mrgfe_ctx_knn_stats": (C.c_int, [_vp, _dp]),
+    "mrgfe_ctx_prefilter_stats": (C.c_int, [_vp, _dp]),
     "mrgfe_ingest_pointcloud2": (C.c_int, [_vp, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, _fp, _vp]),
     "mrgfe_reg_default_params": (None, [C.c_int, C.POINTER(RegParams)]),
     "mrgfe_reg_create": (C.c_int, [_vp, C.POINTER(RegParams), C.POINTER(_vp)]),
@@ -427,6 +430,7 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_node_ndt_rounds": (C.c_int, [_vp, C.c_int, C.c_int, _u32p, _u32p]),
     "mrgfe_dbg_set_fit_sweep": (C.c_int, [C.c_int]),
     "mrgfe_dbg_set_prefilter_device_driven": (C.c_int, [C.c_int]),
+    "mrgfe_dbg_sor_threshold": (C.c_int, [_vp, _fp, _u32p, C.c_size_t, C.c_double, C.c_int, _dp]),
     "mrgfe_dbg_floor_ransac": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(C.c_int), _fp, _ip, _szp, _ip, _ip]),
     "mrgfe_dbg_floor_normals": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, C.c_double, _fp, C.POINTER(C.c_uint8)]),
     "mrgfe_dbg_floor_stats": (C.c_int, [_vp, _dp]),
@@ -580,6 +584,13 @@ class Context:
         v = (C.c_double * 5)()
         check(lib().mrgfe_ctx_knn_stats(self._h, v))
         return dict(zip(("ms", "queries", "k", "candidates", "launches"), [float(x) for x in v]))
+
+    def prefilter_stats(self) -> dict:
+        """Which route served the last prefilter chain call on this context (``mrgfe_ctx_prefilter_stats``): ``route`` 0 host-driven, 1 device-driven,
+        2 device-driven attempted and handed back; ``anomaly`` the device-driven chain's word (``PF_ANOMALY_*``); ``counts`` its five stage counts."""
+        v = (C.c_double * 10)()
+        check(lib().mrgfe_ctx_prefilter_stats(self._h, v))
+        return {"route": int(v[0]), "anomaly": int(v[1]), "counts": [int(x) for x in v[2:7]], "points_out": int(v[7]), "calls": int(v[8]), "served": int(v[9])}
 
     def close(self):
         if getattr(self, "_h", None):

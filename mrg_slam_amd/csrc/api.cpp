@@ -1468,6 +1468,15 @@ int mrgfe_dbg_select_prune(int n_pairs, const double* lower, const double* upper
     return MRGFE_OK;
 }
 int mrgfe_dbg_set_prefilter_device_driven(int mode) { return prefilter_set_device_driven(mode); }
+
+int mrgfe_dbg_sor_threshold(mrgfe_ctx* ctx, const float* dist, const uint32_t* valid, size_t n, double stddev_mul, int on_device, double out[6])
+{
+    if (!out || (n && (!dist || !valid)) || (on_device && !ctx)) { set_error("mrgfe_dbg_sor_threshold: NULL argument"); return MRGFE_ERR_INVALID; }
+    if (!on_device) return sor_threshold_debug(nullptr, dist, valid, n, stddev_mul, 0, out);
+    MRGFE_LOCK(ctx);
+    MRGFE_TRY(ctx->bind());
+    return sor_threshold_debug(ctx, dist, valid, n, stddev_mul, 1, out);
+}
 int mrgfe_dbg_set_pclgicp_reference_order(int mode) { return gicp_set_pcl_reference_order(mode); }
 
 // ---- diagnostics ----------------------------------------------------------------------------------------------

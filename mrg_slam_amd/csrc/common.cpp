@@ -592,6 +592,20 @@ int mrgfe_ctx_knn_stats(mrgfe_ctx* ctx, double out[5])
     return MRGFE_OK;
 }
 
+int mrgfe_ctx_prefilter_stats(mrgfe_ctx* ctx, double out[10])
+{
+    if (!ctx || !out) { mrgfe::set_error("mrgfe_ctx_prefilter_stats: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(ctx);
+    const mrgfe::PrefilterStats& p = ctx->pf_stats;
+    out[0] = double(p.route);
+    out[1] = double(p.anomaly);
+    for (int k = 0; k < 5; ++k) out[2 + k] = double(p.counts[k]);
+    out[7] = double(p.out_n);
+    out[8] = double(p.calls);
+    out[9] = double(p.served);
+    return MRGFE_OK;
+}
+
 int mrgfe_ctx_fitness_stats(mrgfe_ctx* ctx, double out[11])
 {
     if (!ctx || !out) { mrgfe::set_error("mrgfe_ctx_fitness_stats: NULL argument"); return MRGFE_ERR_INVALID; }

@@ -217,6 +217,13 @@ struct KnnStats {
     int        k = 0;
     bool       counted = false;
 };
+// the last prefilter chain call on a context and the calls so far (mrgfe_ctx_prefilter_stats)
+struct PrefilterStats {
+    int      route = 0;          // 0 host-driven, 1 device-driven, 2 device-driven attempted and handed back
+    uint32_t anomaly = 0;        // the device-driven chain's anomaly word (routes 1 and 2)
+    uint32_t counts[5] = {0, 0, 0, 0, 0};  // its five stage counts
+    uint64_t out_n = 0, calls = 0, served = 0;
+};
 }  // namespace mrgfe
 
 struct mrgfe_ctx {
@@ -264,6 +271,7 @@ struct mrgfe_ctx {
     size_t       pf_out_n = 0;
     float        pf_out_box[6] = {0, 0, 0, 0, 0, 0};  // min xyz, max xyz
     bool         pf_out_valid = false;
+    mrgfe::PrefilterStats pf_stats;
     int          cu_count = 256;
     mrgfe::DevBuf fl_buf[11];                   // floor detection (floor.hip): clouds, flags, k-NN lists, RANSAC state / hypotheses / counts
     mrgfe::PinBuf fl_pin;                       // ... and the hypothesis records and counts the host reads after each RANSAC wave

@@ -32,8 +32,11 @@ struct PrefilterChain {
     int    mean_k = 30;
     double stddev_mul = 1.2;
 };
-// 1: the usual chain (voxel grid + radius filter) keeps its point counts on the device and waits once (default); 0: host-driven stages; < 0: query
+// 1: the usual chains (voxel grid + radius filter, voxel grid + statistical filter with mean_k in 1..63) keep their point counts on the device and wait
+// once (default); 0: host-driven stages; < 0: query
 int prefilter_set_device_driven(int mode);
+// mrgfe_dbg_sor_threshold (include/mrgfe_debug.h): the statistical filter's sums, threshold and certificate, host loop or the chain's kernels
+int sor_threshold_debug(mrgfe_ctx* ctx, const float* dist, const uint32_t* valid, size_t n, double stddev_mul, int on_device, double out[6]);
 // the three passes back to back on the device (one upload, one download)
 int filter_chain(mrgfe_ctx* ctx, const PrefilterChain& chain, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool out_on_device = false);
 

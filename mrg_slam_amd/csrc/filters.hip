@@ -19,6 +19,7 @@
 #include "ndt_build.h"
 #include "nn_grid.h"
 #include "scan_point.h"
+#include "sor_threshold.h"
 
 namespace mrgfe {
 
@@ -400,17 +401,7 @@ int filter_statistical_outlier_device(mrgfe_ctx* ctx, const float4* d_in, size_t
         set_error("statistical outlier: device to host copy failed");
         return MRGFE_ERR_HIP;
     }
-    double sum = 0, sq_sum = 0;
-    size_t valid = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const float d2 = h_dist[i] * h_dist[i];
-        sum += h_dist[i];
-        sq_sum += d2;
-        valid += h_valid[i];
-    }
-    const double mean = sum / static_cast<double>(valid);
-    const double variance = (sq_sum - sum * sum / static_cast<double>(valid)) / (static_cast<double>(valid) - 1);
-    const double thr = mean + stddev_mul * std::sqrt(variance);
+    const double thr = sor::sequential<false>(h_dist.data(), h_valid.data(), n, stddev_mul).thr;  // (sor_threshold.h: the loop and the mean / variance / threshold tail)
     DevBuf& dfl = ctx->scratch[7];
     MRGFE_TRY(dfl.ensure(n * 4));
     hipLaunchKernelGGL(sor_flags_kernel, dim3((nn + 255) / 256), dim3(256), 0, st, d_dist, nn, thr, dfl.as<uint32_t>());
@@ -447,6 +438,9 @@ static int host_wrap(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride,
 // points came out.  Anything unusual (no finite point, PCL's "leaf size too small" pass-through, a grid beyond its table) sets a bit in that
 // word and the call is repeated through the host-driven chain below: same kernels for the arithmetic, so the outputs are the same bits
 // either way (tests/test_gpu_filters.py holds the two against each other and the oracle).
+// The same chain serves distance filter -> VoxelGrid -> StatisticalOutlierRemoval, the reference's code default: behind the voxel grid's compaction
+// the k-NN mean distances on a grid that sizes itself (nn_knn_mean_device_driven) and PCL's threshold from certified tree sums (sor_threshold.h)
+// take the radius filter's place (tests/test_gpu_prefilter_statistical.py).
 struct PfState {
     const float4* cp[2];  // cloud read by the voxel grid / by the radius filter
     Slice       sl_in;    // points after the distance filter
@@ -455,12 +449,19 @@ struct PfState {
     uint32_t    nv, pad0;
     VoxelParams vp;
     LeafSlice   ls;
-    uint32_t    counts[6];  // after the distance filter, finite among them, voxels, after the voxel grid, after the radius filter
+    uint32_t    counts[6];  // after the distance filter, finite among them, voxels, after the voxel grid, after the outlier filter (radius or statistical)
     uint32_t    anomaly;
     uint32_t    pad1;
     uint32_t    bb_n[2];    // partial bounding boxes (one per tile of the producer's INPUT) of the cloud the voxel grid / the radius filter reads
+    sor::Result sor;        // StatisticalOutlierRemoval: the sums, the threshold and their certificate (sor_finish_kernel)
 };
 constexpr uint32_t kPfAnomalyEmpty = 1u, kPfAnomalyOverflow = 2u, kPfAnomalyNoVoxel = 4u;
+constexpr uint32_t kPfAnomalyCertificate = 8u;  // a tree sum of the statistical filter is not certified to be the sequential one (sor_threshold.h)
+constexpr uint32_t kPfAnomalyRecheck = 16u;     // set by the HOST behind the wait: its own build of the threshold's tail gives other bits than the device's
+// the pinned status record the host reads behind its one wait: words 0..4 the stage counts, 5 the anomaly word, 6 the completion mark; the box of the
+// voxel centroids at word 8 (28 bytes); the statistical filter's result at byte 64
+constexpr size_t kPfStatusSorOffset = 64, kPfStatusBytes = kPfStatusSorOffset + sizeof(sor::Result);
+static_assert(32 + sizeof(BBox) <= kPfStatusSorOffset, "the box ends before the statistical filter's record");
 
 __device__ __forceinline__ Slice pf_slice(uint32_t n)
 {
@@ -594,7 +595,7 @@ static int launch_scan_head(mrgfe_ctx* ctx, const ScanHead& h, const void* d_raw
 // exclusive scan (three launches), the compaction, the count and the bounding-box pass were six launches.
 //   kWhich 0: the distance filter (n known to the host)      -> sl_in,  counts[0], boxes for the voxel grid
 //   kWhich 1: the voxel grid's centroids (n = sl_vox.n)       -> sl_rad, counts[3], boxes for the radius filter's grid
-//   kWhich 2: the radius filter (n = sl_rad.n)               -> counts[4] and the host's status words
+//   kWhich 2: the outlier filter, radius or statistical (n = sl_rad.n) -> counts[4] and the host's status words
 template <int kWhich>
 __global__ __launch_bounds__(256) void pf_compact_kernel(const float4* __restrict__ in, const uint32_t* __restrict__ flags, const uint32_t* __restrict__ blk, uint32_t n_host,
                                                           float4* __restrict__ out, PfState* st, uint32_t* __restrict__ h_status, BBox* __restrict__ partial)
@@ -749,6 +750,147 @@ __global__ __launch_bounds__(256) void voxel_centroid_dd_kernel(const float4* __
     centroids[s] = make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
     keep[s] = (e - b) >= static_cast<uint32_t>(min_pts) ? 1u : 0u;
 }
+// ---- StatisticalOutlierRemoval's threshold without a host round trip (sor_threshold.h) --------------------------------------------------------------
+// The reference's two f64 sums are sequential over the points; a dependent chain of n additions on one lane would cost as much as the rest of the chain.
+// They are added in a tree instead — per thread, per wavefront, per tile of 2048 points, over the tiles — together with the minimum lowest-bit exponent
+// of the terms of either sum; sor::certified then says whether the order could have mattered.  When it could (it does not on scans: q is -24 .. -34 and
+// the sums stay below 2^17 where 2^(q + 52) is 2^18 at the least), the finish sets kPfAnomalyCertificate and the host-driven passes add in the
+// reference's order.
+struct SorPartial {
+    double   sum, sq_sum;
+    uint32_t valid;
+    int32_t  q_sum, q_sq;
+    uint32_t pad;
+};
+__device__ __forceinline__ SorPartial sor_partial_zero()
+{
+    SorPartial a;
+    a.sum = 0.0; a.sq_sum = 0.0; a.valid = 0u; a.q_sum = sor::kNoTerm; a.q_sq = sor::kNoTerm; a.pad = 0u;
+    return a;
+}
+__device__ __forceinline__ void sor_partial_add(SorPartial& a, double sum, double sq_sum, uint32_t valid, int32_t q_sum, int32_t q_sq)
+{
+    a.sum += sum; a.sq_sum += sq_sum; a.valid += valid;
+    a.q_sum = sor::min_exponent(a.q_sum, q_sum);
+    a.q_sq = sor::min_exponent(a.q_sq, q_sq);
+}
+// the 256 threads' partials in a fixed tree (lane i + lane i + off for off = 32 .. 1, then the four wavefronts); the result is valid in thread 0
+__device__ __forceinline__ SorPartial sor_block_merge(SorPartial a, SorPartial* lds)
+{
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1)
+        sor_partial_add(a, __shfl_down(a.sum, off, kWave), __shfl_down(a.sq_sum, off, kWave), __shfl_down(a.valid, off, kWave), __shfl_down(a.q_sum, off, kWave),
+                        __shfl_down(a.q_sq, off, kWave));
+    if (lane_id() == 0) lds[wave_id()] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        SorPartial lo = lds[0], hi = lds[2];
+        sor_partial_add(lo, lds[1].sum, lds[1].sq_sum, lds[1].valid, lds[1].q_sum, lds[1].q_sq);
+        sor_partial_add(hi, lds[3].sum, lds[3].sq_sum, lds[3].valid, lds[3].q_sum, lds[3].q_sq);
+        sor_partial_add(lo, hi.sum, hi.sq_sum, hi.valid, hi.q_sum, hi.q_sq);
+        a = lo;
+    }
+    return a;
+}
+// one workgroup per tile of 2048 of the first *n_ptr distances; part[tile] = the tile's sums
+__global__ __launch_bounds__(256) void sor_reduce_tiles_kernel(const float* __restrict__ dist, const uint32_t* __restrict__ valid, const uint32_t* __restrict__ n_ptr,
+                                                                SorPartial* __restrict__ part)
+{
+    const uint32_t n = *n_ptr, base = blockIdx.x * kTile;
+    if (base >= n) return;  // uniform
+    __shared__ SorPartial lds[4];
+    SorPartial a = sor_partial_zero();
+#pragma unroll
+    for (int k = 0; k < kTile / 256; ++k) {
+        const uint32_t i = base + k * 256 + threadIdx.x;
+        if (i < n) {
+            const float d = dist[i], d2 = sor::square_term(d);
+            sor_partial_add(a, static_cast<double>(d), static_cast<double>(d2), valid[i], sor::low_bit_exponent(d), sor::low_bit_exponent(d2));
+        }
+    }
+    a = sor_block_merge(a, lds);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+// one workgroup: the tiles' sums in a tree, then ONE thread certifies them and evaluates the threshold — into *out (device memory: sor_flags_dd_kernel
+// reads the threshold there), into the host's pinned record, and a failed certificate into the chain's anomaly word
+__global__ __launch_bounds__(256) void sor_finish_kernel(const SorPartial* __restrict__ part, const uint32_t* __restrict__ n_ptr, double stddev_mul, sor::Result* __restrict__ out,
+                                                          sor::Result* __restrict__ h_out, uint32_t* __restrict__ anomaly)
+{
+    const uint32_t n = *n_ptr, nblk = (n + kTile - 1) / kTile;
+    __shared__ SorPartial lds[4];
+    SorPartial a = sor_partial_zero();
+    for (uint32_t b = threadIdx.x; b < nblk; b += 256) {
+        const SorPartial t = part[b];
+        sor_partial_add(a, t.sum, t.sq_sum, t.valid, t.q_sum, t.q_sq);
+    }
+    uint64_t valid = a.valid;  // (the tiles' counts fit 32 bits, their total need not in the diagnostic's arrays)
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) valid += __shfl_down(valid, off, kWave);
+    __shared__ uint64_t s_valid[4];
+    if (lane_id() == 0) s_valid[wave_id()] = valid;
+    a = sor_block_merge(a, lds);  // (synchronises)
+    if (threadIdx.x) return;
+    sor::Result r;
+    r.sum = a.sum;
+    r.sq_sum = a.sq_sum;
+    r.valid = (s_valid[0] + s_valid[1]) + (s_valid[2] + s_valid[3]);
+    r.q_sum = a.q_sum;
+    r.q_sq = a.q_sq;
+    r.thr = sor::threshold(r.sum, r.sq_sum, r.valid, stddev_mul);
+    r.certified = (sor::certified(r.sum, r.q_sum) && sor::certified(r.sq_sum, r.q_sq)) ? 1u : 0u;
+    r.pad = 0u;
+    *out = r;
+    if (h_out) *h_out = r;  // (pinned host memory: read behind the caller's stream wait)
+    if (anomaly && !r.certified) *anomaly |= kPfAnomalyCertificate;
+}
+// sor_flags_kernel with the count and the threshold read from device memory
+__global__ __launch_bounds__(256) void sor_flags_dd_kernel(const float* __restrict__ dist, const uint32_t* __restrict__ n_ptr, const double* __restrict__ thr, uint32_t* __restrict__ flags)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < *n_ptr) flags[i] = (static_cast<double>(dist[i]) > *thr) ? 0u : 1u;
+}
+// enqueue the reduction and the finish over the first *d_n of d_dist / d_valid (n_cap >= *d_n sizes the launch); d_part: n_cap / 2048 + 1 partials
+static int sor_threshold_launch(mrgfe_ctx* ctx, const float* d_dist, const uint32_t* d_valid, const uint32_t* d_n, uint32_t n_cap, double stddev_mul, SorPartial* d_part,
+                                sor::Result* d_out, sor::Result* h_out, uint32_t* d_anomaly)
+{
+    const uint32_t tiles = (n_cap + kTile - 1) / kTile;
+    if (tiles) hipLaunchKernelGGL(sor_reduce_tiles_kernel, dim3(tiles), dim3(256), 0, ctx->stream, d_dist, d_valid, d_n, d_part);
+    hipLaunchKernelGGL(sor_finish_kernel, dim3(1), dim3(256), 0, ctx->stream, d_part, d_n, stddev_mul, d_out, h_out, d_anomaly);
+    MRGFE_HIP_CHECK(hipGetLastError());
+    return MRGFE_OK;
+}
+
+// mrgfe_dbg_sor_threshold: out = sum, sq_sum, valid, thr, certified, q of the `sum` terms — from the reference's sequential loop on the host, or from the
+// chain's own reduction and finish kernels over the uploaded arrays
+int sor_threshold_debug(mrgfe_ctx* ctx, const float* dist, const uint32_t* valid, size_t n, double stddev_mul, int on_device, double out[6])
+{
+    sor::Result r;
+    if (!on_device) {
+        r = sor::sequential(dist, valid, n, stddev_mul);
+    } else {
+        if (n > 0x7fffffffu) { set_error("mrgfe_dbg_sor_threshold: too many values"); return MRGFE_ERR_INVALID; }
+        const uint32_t nn = static_cast<uint32_t>(n);
+        DevBuf dres, dpart, din;  // (per-call buffers of a diagnostic, freed at the return)
+        MRGFE_TRY(din.ensure(std::max<size_t>(n, 1) * 8));
+        MRGFE_TRY(dpart.ensure(sizeof(SorPartial) * (size_t(nn) / kTile + 2)));
+        MRGFE_TRY(dres.ensure(sizeof(sor::Result) + 8));
+        float*    d_dist = din.as<float>();
+        uint32_t* d_valid = reinterpret_cast<uint32_t*>(d_dist + std::max<size_t>(n, 1));
+        uint32_t* d_n = reinterpret_cast<uint32_t*>(dres.as<char>() + sizeof(sor::Result));
+        if (n) {
+            MRGFE_HIP_CHECK(hipMemcpyAsync(d_dist, dist, n * 4, hipMemcpyHostToDevice, ctx->stream));
+            MRGFE_HIP_CHECK(hipMemcpyAsync(d_valid, valid, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        }
+        MRGFE_HIP_CHECK(hipMemcpyAsync(d_n, &nn, 4, hipMemcpyHostToDevice, ctx->stream));
+        MRGFE_TRY(sor_threshold_launch(ctx, d_dist, d_valid, d_n, nn, stddev_mul, dpart.as<SorPartial>(), dres.as<sor::Result>(), nullptr, nullptr));
+        MRGFE_HIP_CHECK(hipMemcpyAsync(&r, dres.p, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
+        MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    out[0] = r.sum; out[1] = r.sq_sum; out[2] = static_cast<double>(r.valid); out[3] = r.thr; out[4] = static_cast<double>(r.certified);
+    out[5] = static_cast<double>(r.q_sum);
+    return MRGFE_OK;
+}
+
 // 1 (default): the usual chain keeps its counts on the device; 0: always the host-driven chain of round 3 (MRGFE_PREFILTER_HOST_DRIVEN=1, tests)
 static std::atomic<int> g_pf_device_driven{-1};
 static int prefilter_device_driven_mode()
@@ -772,8 +914,24 @@ static NnDeviceDrivenGrid& pf_grid(mrgfe_ctx* ctx)
 // the chains the device-driven form serves (the others, and its anomalies, go through the host-driven passes)
 static bool device_driven_applies(const PrefilterChain& ch, uint32_t n)
 {
-    return prefilter_device_driven_mode() && !ch.approx_voxelgrid && ch.voxelgrid && ch.outlier == 1 && n != 0 && ch.leaf > 0;
+    const bool outlier_served = ch.outlier == 1 || (ch.outlier == 2 && ch.mean_k >= 1 && ch.mean_k <= 63);  // (mean_k + 1 entries must fit a wavefront's list)
+    return prefilter_device_driven_mode() && !ch.approx_voxelgrid && ch.voxelgrid && outlier_served && n != 0 && ch.leaf > 0;
 }
+
+// The cell edge of the statistical filter's k-NN grid.  Search results do not depend on it, only the time does, and the host cannot run NnGrid::build's
+// adaptive halving (which counts the points per cell) without a wait — so the edge comes from what the host knows: the voxel grid that made the cloud
+// leaves at most one centroid per leaf^3, a scan's surfaces therefore at most (edge / leaf)^2 per cell.  EIGHT leaves, measured (MI355X, leaf 0.1, k = 20
+// and 30; profiles/prefilter_statistical_summary.md): the search is ONE level, so what sets its time is the sparse far rings of a scan, whose queries
+// walk ring after ring of small cells — at 4 leaves the k-NN launch of a 26k-point VLP-16 scan took 0.14 - 0.17 ms, at 8 leaves 0.05 - 0.06 ms, while the
+// denser 130k-point VLP-64 scan is flat from 4 to 10 leaves (0.07 - 0.10 ms) and loses from 16 on (0.12 - 0.15 ms: hundreds of candidates per cell).
+// Never below 0.2 m: a leaf of a few centimetres must not cost a table of 10^8 cells.  A cloud whose box needs more than kSorCellsCap cells at this edge
+// sets kNnAnomalyCells and is handed back; 8^3 leaves per cell and 2^24 cells put that beyond PCL's own limit of 2^31 leaves for every leaf >= 0.025 m.
+// A second, coarser level for the far rings was not tried.
+constexpr uint32_t kSorCellsCap = (1u << 24) - 1u;  // 24 key bits: three radix passes, as for the radius filter's 2^22 cells
+#ifndef MRGFE_SOR_CELL_LEAVES
+#define MRGFE_SOR_CELL_LEAVES 8.0f
+#endif
+static float sor_cell_edge(const PrefilterChain& ch) { return std::max(MRGFE_SOR_CELL_LEAVES * ch.leaf, 0.2f); }
 
 // A chain the device-driven form serves (device_driven_applies).  The packed input is in d_in already, or — `head` and its uploaded records `d_raw` —
 // the scan head kernel writes it there as the chain's first launch.  Returns MRGFE_OK with *used = true when it produced the output, *used = false
@@ -786,10 +944,16 @@ static int filter_chain_device_driven(mrgfe_ctx* ctx, const PrefilterChain& ch, 
     SliceTable  tab;
     tab.build(&n, 1);
     MRGFE_TRY(ctx->pf_state.ensure(sizeof(PfState)));
-    MRGFE_TRY(ctx->pf_status.ensure(64));
+    MRGFE_TRY(ctx->pf_status.ensure(kPfStatusBytes));
     PfState*  d_st = ctx->pf_state.as<PfState>();
     uint32_t* h_status = ctx->pf_status.as<uint32_t>();
     h_status[6] = 0;
+    const bool statistical = ch.outlier == 2;
+    DevBuf &dsor = ctx->scratch[12], &dsorp = ctx->scratch[14];  // the statistical filter's mean distances and flags of validity, its tiles' sums
+    if (statistical) {
+        MRGFE_TRY(dsor.ensure(size_t(n) * 8));
+        MRGFE_TRY(dsorp.ensure(sizeof(SorPartial) * (size_t(tab.total_blks) + 1)));
+    }
     DevBuf &dbb = ctx->scratch[1], &dk = ctx->scratch[2], &dv = ctx->scratch[3], &dkt = ctx->scratch[4], &dvt = ctx->scratch[5], &dh = ctx->scratch[6], &dfl = ctx->scratch[7],
            &dblk = ctx->scratch[8], &dseg = ctx->scratch[9], &dcent = ctx->scratch[10], &dkeep = ctx->scratch[11];
     MRGFE_TRY(dbb.ensure(sizeof(BBox) * (tab.total_blks + 2)));
@@ -831,19 +995,40 @@ static int filter_chain_device_driven(mrgfe_ctx* ctx, const PrefilterChain& ch, 
     MRGFE_TRY(tile_sums(ctx, dkeep.as<uint32_t>(), &d_st->sl_vox, tab, d_blk));
     // (the voxel grid's output goes to d_final for now: the radius filter reads it there and compacts into the work buffer ...)
     hipLaunchKernelGGL(pf_compact_kernel<1>, gtiles, b256, 0, st, dcent.as<float4>(), dkeep.as<uint32_t>(), d_blk, 0u, d_final, d_st, h_status, d_part);
-    // ---- RadiusOutlierRemoval: a grid that sizes itself (from the boxes of the centroids kept), neighbour counts, compaction
+    // ---- the outlier filter: a grid that sizes itself (from the boxes of the centroids kept), flags, compaction
     NnDeviceDrivenGrid& grid = pf_grid(ctx);
-    const float cell = static_cast<float>(ch.radius);
     BBox* h_box = reinterpret_cast<BBox*>(h_status + 8);  // the box of the voxel centroids: it encloses what the outlier filter keeps of them
-    MRGFE_TRY(nn_build_device_driven(ctx, &d_st->cp[1], &d_st->sl_rad, n, d_part, &d_st->bb_n[1], cell, 1u << 22, grid, &d_st->anomaly, h_box));
-    // inlier iff #{q: (double)sqdist <= radius*radius} >= min_neighbors + 1 (the point itself counts)
-    MRGFE_TRY(nn_radius_flags_device_driven(ctx, grid, d_final, &d_st->sl_rad, n, ch.radius * ch.radius, ch.radius_min_neighbors + 1, cell, dfl.as<uint32_t>()));
+    sor::Result* h_sor = reinterpret_cast<sor::Result*>(ctx->pf_status.as<char>() + kPfStatusSorOffset);
+    if (!statistical) {
+        // RadiusOutlierRemoval: inlier iff #{q: (double)sqdist <= radius*radius} >= min_neighbors + 1 (the point itself counts)
+        const float cell = static_cast<float>(ch.radius);
+        MRGFE_TRY(nn_build_device_driven(ctx, &d_st->cp[1], &d_st->sl_rad, n, d_part, &d_st->bb_n[1], cell, 1u << 22, grid, &d_st->anomaly, h_box));
+        MRGFE_TRY(nn_radius_flags_device_driven(ctx, grid, d_final, &d_st->sl_rad, n, ch.radius * ch.radius, ch.radius_min_neighbors + 1, cell, dfl.as<uint32_t>()));
+    } else {
+        // StatisticalOutlierRemoval: mean distance to the mean_k nearest (the exact wave-per-query search, its lists consumed in registers), the threshold
+        // from the certified tree sums, inlier iff (double)mean distance <= threshold
+        float*    d_dist = dsor.as<float>();
+        uint32_t* d_valid = reinterpret_cast<uint32_t*>(d_dist + n);
+        MRGFE_TRY(nn_build_device_driven(ctx, &d_st->cp[1], &d_st->sl_rad, n, d_part, &d_st->bb_n[1], sor_cell_edge(ch), kSorCellsCap, grid, &d_st->anomaly, h_box));
+        MRGFE_TRY(nn_knn_mean_device_driven(ctx, grid, d_final, &d_st->sl_rad, n, ch.mean_k + 1, d_dist, d_valid));
+        MRGFE_TRY(sor_threshold_launch(ctx, d_dist, d_valid, &d_st->sl_rad.n, n, ch.stddev_mul, dsorp.as<SorPartial>(), &d_st->sor, h_sor, &d_st->anomaly));
+        hipLaunchKernelGGL(sor_flags_dd_kernel, g256, b256, 0, st, d_dist, &d_st->sl_rad.n, &d_st->sor.thr, dfl.as<uint32_t>());
+    }
     MRGFE_TRY(tile_sums(ctx, dfl.as<uint32_t>(), &d_st->sl_rad, tab, d_blk));
     hipLaunchKernelGGL(pf_compact_kernel<2>, gtiles, b256, 0, st, d_final, dfl.as<uint32_t>(), d_blk, 0u, d_work, d_st, h_status, d_part);
     MRGFE_HIP_CHECK(hipGetLastError());
     MRGFE_HIP_CHECK(hipStreamSynchronize(st));  // the chain's one wait
     if (h_status[6] != 0x600df00du) { set_error("prefilter: the device-driven chain did not report"); return MRGFE_ERR_HIP; }
-    if (h_status[5] != 0) return MRGFE_OK;  // something unusual: the host-driven chain decides what the reference does with it
+    PrefilterStats& ps = ctx->pf_stats;
+    ps.anomaly = h_status[5];
+    for (int k = 0; k < 5; ++k) ps.counts[k] = h_status[k];
+    if (statistical) {
+        ctx->knn_stats.queries = h_status[3];  // (the live count of the k-NN launch)
+        // the host's own build of the threshold's tail on the reported sums: the result must not depend on how the device library rounds an f64 divide or
+        // square root (it costs nothing here)
+        if (!sor::same_bits(sor::threshold(h_sor->sum, h_sor->sq_sum, h_sor->valid, ch.stddev_mul), h_sor->thr)) ps.anomaly |= kPfAnomalyRecheck;
+    }
+    if (ps.anomaly != 0) return MRGFE_OK;  // something unusual: the host-driven chain decides what the reference does with it
     *out_n = h_status[4];
     *used = true;
     if (h_box->n_finite > 0 && *out_n > 0) {  // (remembered for mrgfe_reg_set_source_from_prefilter; filter_chain says whether d_work is the caller's buffer)
@@ -867,6 +1052,12 @@ static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const Cha
 {
     *out_n = 0;
     ctx->pf_out_valid = false;
+    PrefilterStats& ps = ctx->pf_stats;  // (mrgfe_ctx_prefilter_stats: which route serves this call)
+    ps.route = 0;
+    ps.anomaly = 0;
+    for (uint32_t& c : ps.counts) c = 0;
+    ps.out_n = 0;
+    ps.calls += 1;
     if (n == 0) return MRGFE_OK;
     if (n > 0x7fffffffu) { set_error("prefilter: cloud too large"); return MRGFE_ERR_INVALID; }
     DevBuf &a = ctx->pf_buf[0], &b = ctx->pf_buf[1];  // ping-pong, kept between calls (grow-only: a hipMalloc / hipFree pair per scan is a device-wide wait)
@@ -887,10 +1078,11 @@ static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const Cha
         if (!out_on_device) { rc = c.ensure(n * 16); final_buf = c.as<float4>(); }
         if (rc == MRGFE_OK) rc = filter_chain_device_driven(ctx, ch, in.head, d_raw, a.as<float4>(), static_cast<uint32_t>(n), work, final_buf, &m, &used);
         if (rc != MRGFE_OK) return rc;
+        ps.route = used ? 1 : 2;
         if (used) {
             if (!out_on_device) ctx->pf_out_valid = false;  // (the cloud went to the host: nothing of the caller's stays on the device)
             if (!out_on_device) rc = download(ctx, work, m, static_cast<float*>(out));
-            if (rc == MRGFE_OK) *out_n = m;
+            if (rc == MRGFE_OK) { *out_n = m; ps.out_n = m; ps.served += 1; }
             return rc;
         }
     }
@@ -915,7 +1107,7 @@ static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const Cha
             rc = MRGFE_ERR_HIP;
         }
     }
-    if (rc == MRGFE_OK) *out_n = m;
+    if (rc == MRGFE_OK) { *out_n = m; ps.out_n = m; }
     return rc;
 }
 

@@ -130,7 +130,8 @@ class NnGridSet {
 // single-thread kernel derives the geometry exactly as NnGrid::build_level does on the host and writes the build descriptor the *_many
 // kernels read; launches are sized for `n_cap` points.  The cell table is written entry by entry from the sorted keys (nn_fill_body), so
 // its capacity `cells_cap` only has to be allocated, never cleared; a cloud that needs more cells sets bit kNnAnomalyCells in *d_anomaly
-// (the caller then falls back to the host-driven build).  No pyramid: the grid serves ring walks (radius counts) only.
+// (the caller then falls back to the host-driven build).  No pyramid: the grid serves ring walks only — radius counts, and the one-level k-NN walk of
+// nn_knn_mean_device_driven, which reads no occupancy words.
 constexpr uint32_t kNnAnomalyCells = 1u << 8;
 struct NnDeviceDrivenGrid {
     DevBuf cells, sorted, desc;  // cell table (cells_cap + 8 words), cell-major points (n_cap), the NnBuildDev record
@@ -141,6 +142,10 @@ int nn_build_device_driven(mrgfe_ctx* ctx, const float4* const* d_cloud_ptr, con
 // flags[i] = 1 iff #{j : sqdist(q_i, p_j) <= r2} >= need for the first d_slice->n points of d_q (the grid's own cloud): nn_radius_flags_kernel with
 // the grid and the count read from device memory
 int nn_radius_flags_device_driven(mrgfe_ctx* ctx, const NnDeviceDrivenGrid& g, const float4* d_q, const Slice* d_slice, uint32_t n_cap, double r2, int need, float cell, uint32_t* d_flags);
+// StatisticalOutlierRemoval's search on such a grid (its own cloud, the first d_slice->n points of d_q): for every query the exact k1 = mean_k + 1 nearest
+// (the query itself first), consumed in registers — d_dist[i] = the mean distance to the mean_k others as sor_mean_dist_kernel computes it from a
+// row of NnGrid::knn_device, d_valid[i] = 1 iff all k1 were found.  One wavefront per query, launched for n_cap; 2 <= k1 <= 64; no host wait.
+int nn_knn_mean_device_driven(mrgfe_ctx* ctx, const NnDeviceDrivenGrid& g, const float4* d_q, const Slice* d_slice, uint32_t n_cap, int k1, float* d_dist, uint32_t* d_valid);
 
 // the context's reusable grid (created on first use; buffers grow only; freed with the context)
 NnGrid& ctx_tmp_grid(mrgfe_ctx* ctx);

@@ -2436,8 +2436,10 @@ __device__ __forceinline__ void knn_sort_merge(float& td, int32_t& ti, float d, 
     for (int stride = 32; stride > 0; stride >>= 1) knn_cmpx(td, ti, stride, true);
 }
 
-// one query per wavefront: the k nearest of p, written to row i of idx / sqd; returns the candidates measured
-__device__ __forceinline__ uint32_t nn_knn_query(const NnGrid2Dev& g, const float4 p, uint32_t i, int k, int32_t* __restrict__ idx, float* __restrict__ sqd)
+// one query per wavefront: the k nearest of p; `done(td, ti, cnt)` consumes the list where it lies — entry j in lane j (td squared distance, ti index), the
+// first cnt (uniform) of them found, ascending by (distance, index); returns the candidates measured
+template <class Epilogue>
+__device__ __forceinline__ uint32_t nn_knn_walk(const NnGrid2Dev& g, const float4 p, int k, Epilogue&& done)
 {
     const int    lane = lane_id();
     float        td = INFINITY;     // list entry of this lane
@@ -2625,11 +2627,19 @@ __device__ __forceinline__ uint32_t nn_knn_query(const NnGrid2Dev& g, const floa
             }
         }
     }
-    if (lane < k) {
-        idx[size_t(i) * k + lane] = lane < cnt ? ti : -1;
-        sqd[size_t(i) * k + lane] = lane < cnt ? td : -1.0f;
-    }
+    done(td, ti, cnt);
     return n_cand;
+}
+// ... written to row i of idx / sqd
+__device__ __forceinline__ uint32_t nn_knn_query(const NnGrid2Dev& g, const float4 p, uint32_t i, int k, int32_t* __restrict__ idx, float* __restrict__ sqd)
+{
+    return nn_knn_walk(g, p, k, [&](float td, int32_t ti, int cnt) {
+        const int lane = lane_id();
+        if (lane < k) {
+            idx[size_t(i) * k + lane] = lane < cnt ? ti : -1;
+            sqd[size_t(i) * k + lane] = lane < cnt ? td : -1.0f;
+        }
+    });
 }
 
 #ifndef MRGFE_KNN_WAVES
@@ -2670,6 +2680,74 @@ int NnGrid::knn_device(mrgfe_ctx* ctx, const float4* d_q, size_t n, int k, int32
     ks.queries = n;
     ks.k = k;
     ks.counted = d_cand != nullptr;
+    ks.launches += 1;
+    return MRGFE_OK;
+}
+
+// StatisticalOutlierRemoval's mean neighbour distances on a grid the device sized (nn_build_device_driven), for the prefilter chain that keeps its counts
+// on the device: the same walk, one wavefront per query, with the grid record and the live count read from device memory (the launch covers n_cap
+// queries).  The walk runs on one level and reads origin / cell / slack / dim / n / cell_start / sorted only, so the pyramid-less grid serves it.  No
+// [n][k1] rows: the sorted list stays in the lanes and dist[i] / valid[i] are what sor_mean_dist_kernel (filters.hip) makes of a row — valid iff all k1
+// entries were found, dist = float(sum_{j = 1 .. k1 - 1} double(sqrtf(sqd_j)) / double(k1 - 1)) added in ascending j (the reference's order: at most 63
+// dependent additions beside ~1000 VALU instructions of search; entry 0 is the query itself).
+// The grid record is staged in LDS by the workgroup and read from there as wave-uniform (scalar) values, its pointers named global again: the walk then
+// holds it in scalar registers exactly as nn_knn_kernel holds its by-value argument.
+__attribute__((amdgpu_waves_per_eu(MRGFE_KNN_WAVES)))
+__global__ __launch_bounds__(256) void nn_knn_mean_dd_kernel(const NnBuildDev* __restrict__ d, const float4* __restrict__ q, const Slice* __restrict__ slice, int k1,
+                                                              float* __restrict__ dist, uint32_t* __restrict__ valid)
+{
+    const uint32_t n = slice->n;
+    if (blockIdx.x * 4u >= n) return;  // uniform
+    __shared__ NnGridDev s_g;
+    static_assert(sizeof(NnGridDev) % 4 == 0 && sizeof(NnGridDev) / 4 <= 256, "one word per thread");
+    if (threadIdx.x < sizeof(NnGridDev) / 4) reinterpret_cast<uint32_t*>(&s_g)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&d->lv)[threadIdx.x];
+    __syncthreads();
+    const uint32_t i = (blockIdx.x * 256u + threadIdx.x) >> 6;
+    if (i >= n) return;  // uniform per wave
+    NnGrid2Dev g;
+    {
+        uint32_t w[sizeof(NnGridDev) / 4];
+#pragma unroll
+        for (uint32_t k = 0; k < sizeof(NnGridDev) / 4; ++k) w[k] = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(reinterpret_cast<const uint32_t*>(&s_g)[k])));
+        memcpy(&g.level[0], w, sizeof(NnGridDev));
+        // (the two arrays' addresses as integers -> pointers into global memory: the walk's loads are global_load, not flat_load)
+        constexpr size_t cs = offsetof(NnGridDev, cell_start) / 4, so = offsetof(NnGridDev, sorted) / 4;
+        g.level[0].cell_start = (const uint32_t*)(const MRGFE_GLOBAL uint32_t*)(static_cast<uintptr_t>(w[cs]) | static_cast<uintptr_t>(w[cs + 1]) << 32);
+        g.level[0].sorted = (const float4*)(const MRGFE_GLOBAL float4*)(static_cast<uintptr_t>(w[so]) | static_cast<uintptr_t>(w[so + 1]) << 32);
+        g.level[0].occ = g.level[0].occ1 = g.level[0].occ2 = nullptr;
+        g.level[1] = g.level[2] = g.level[0];
+        g.n_levels = 1;
+        g.pad = 0;
+    }
+    nn_knn_walk(g, q[i], k1, [&](float td, int32_t, int cnt) {
+        const float s = sqrtf(td);  // (lanes >= cnt hold +inf: read only when all k1 entries were found)
+        float    dm = 0.0f;
+        uint32_t ok = 0;
+        if (cnt == k1) {  // uniform
+            double sum = 0.0;
+            for (int j = 1; j < k1; ++j) sum += static_cast<double>(wave_read(s, j));
+            dm = static_cast<float>(sum / static_cast<double>(k1 - 1));
+            ok = 1;
+        }
+        if (lane_id() == 0) { dist[i] = dm; valid[i] = ok; }
+    });
+}
+
+int nn_knn_mean_device_driven(mrgfe_ctx* ctx, const NnDeviceDrivenGrid& g, const float4* d_q, const Slice* d_slice, uint32_t n_cap, int k1, float* d_dist, uint32_t* d_valid)
+{
+    if (k1 < 2 || k1 > 64) { set_error("nn_knn_mean_device_driven: k + 1 must be in [2, 64]"); return MRGFE_ERR_INVALID; }
+    if (n_cap == 0) return MRGFE_OK;
+    if (n_cap > (0xffffffffu >> 6)) { set_error("nn_knn_mean_device_driven: too many queries"); return MRGFE_ERR_INVALID; }
+    KnnStats& ks = ctx->knn_stats;  // (mrgfe_ctx_knn_stats: HIP events around the launch, as NnGrid::knn_device records them)
+    for (auto& e : ks.ev)
+        if (!e) MRGFE_HIP_CHECK(hipEventCreate(&e));
+    MRGFE_HIP_CHECK(hipEventRecord(ks.ev[0], ctx->stream));
+    hipLaunchKernelGGL(nn_knn_mean_dd_kernel, dim3((n_cap + 3) / 4), dim3(256), 0, ctx->stream, g.desc.as<NnBuildDev>(), d_q, d_slice, k1, d_dist, d_valid);
+    MRGFE_HIP_CHECK(hipGetLastError());
+    MRGFE_HIP_CHECK(hipEventRecord(ks.ev[1], ctx->stream));
+    ks.queries = n_cap;  // (the launch's size: the live count is on the device; the chain puts it here behind its wait)
+    ks.k = k1;
+    ks.counted = false;
     ks.launches += 1;
     return MRGFE_OK;
 }
