@@ -161,12 +161,15 @@ int mrgfe_ctx_fitness_stats(mrgfe_ctx* ctx, double out[11]);
 int mrgfe_ctx_knn_stats(mrgfe_ctx* ctx, double out[5]);
 /* Which route served the last prefilter chain call on this context (mrgfe_prefilter[_device], mrgfe_scan_callback[_device]):
  * out[0] = route — 0 the host-driven passes (every stage hands its point count to the host), 1 the device-driven chain (one wait; [distance filter] ->
- * VOXELGRID -> RADIUS or STATISTICAL with statistical_mean_k in 1..63), 2 the device-driven chain attempted and handed back to the host-driven passes
- * (same output); out[1] = the device-driven chain's anomaly word (routes 1 and 2): 1 no finite point survived the distance filter, 2 PCL's "leaf size too
- * small" pass-through, 4 no voxel, 8 a sum of the statistical filter's threshold could have depended on the order of addition, 16 the host's re-check of
- * that threshold differs from the device's, 256 the outlier filter's search grid needs more cells than its table; out[2..6] = its stage counts (points
- * after the distance filter, finite among them, voxels, points after the voxel grid, points after the outlier filter; routes 1 and 2); out[7] = points
- * out; out[8] = chain calls on this context so far; out[9] = calls served device-driven so far. */
+ * NONE, VOXELGRID or APPROX_VOXELGRID -> NONE or RADIUS, and VOXELGRID -> STATISTICAL with statistical_mean_k in 1..63; STATISTICAL behind NONE or
+ * APPROX_VOXELGRID stays on route 0), 2 the device-driven chain attempted and handed back to the host-driven passes (same output); out[1] = the
+ * device-driven chain's anomaly word (routes 1 and 2): 1 a stage in front of another one left no (finite) point, 2 PCL's "leaf size too small"
+ * pass-through, 4 no voxel, 8 a sum of the statistical filter's threshold could have depended on the order of addition, 16 the host's re-check of
+ * that threshold differs from the device's, 32 a non-finite point reached the outlier filter (distance filter off and no VOXELGRID in front of it),
+ * 256 the outlier filter's search grid needs more cells than its table — an EMPTY RESULT is no anomaly (route 1, 0 points); out[2..6] = its stage counts
+ * (points after the distance filter, finite among them, voxels, points after the downsample — both the emitted centroids with APPROX_VOXELGRID, both
+ * out[2] without a downsample —, points after the outlier filter, out[5] again without one; routes 1 and 2); out[7] = points out; out[8] = chain calls
+ * on this context so far; out[9] = calls served device-driven so far. */
 int mrgfe_ctx_prefilter_stats(mrgfe_ctx* ctx, double out[10]);
 
 /* ---- cloud ingest --------------------------------------------------------------------------------- */
@@ -322,8 +325,8 @@ int  mrgfe_prefilter_device(mrgfe_ctx* ctx, const mrgfe_prefilter_params* params
 /* pcl::fromROSMsg (:119-120) -> deskewing (:125, :231-295) -> pcl_ros::transformPointCloud into base_link_frame (:141-146) -> distance_filter ->
  * downsample -> outlier_removal (:149-151) on the byte payload of a sensor_msgs/PointCloud2.  The payload goes up ONCE as it is; one kernel reads
  * the records, deskews, transforms, stores the packed cloud and (on the usual chains) is the distance filter's first pass; nothing comes down but
- * the chain's status words and, for the host form, the filtered cloud; the usual chains (VOXELGRID + RADIUS, and VOXELGRID + STATISTICAL — the
- * reference's code default — with statistical_mean_k in 1..63) wait for the device once (mrgfe_ctx_prefilter_stats says which route served a call).
+ * the chain's status words and, for the host form, the filtered cloud; every chain but STATISTICAL behind NONE or APPROX_VOXELGRID, or with
+ * statistical_mean_k outside 1..63, waits for the device once (mrgfe_ctx_prefilter_stats says which route served a call).
  * The output equals, bit for bit and in order, mrgfe_ingest_pointcloud2 -> mrgfe_deskew (if `deskew`) -> mrgfe_transform_cloud (if `transform`)
  * -> mrgfe_prefilter[_device] for the same inputs.  The reference's quirks are kept: deskewing counts i and n = width * height over the UNFILTERED
  * cloud (:286), non-finite points included; the transform leaves non-finite points as they are; the distance filter is what drops them. */
@@ -657,6 +660,11 @@ size_t mrgfe_odom_params_size(void);               /* sizeof(mrgfe_odom_params) 
 int    mrgfe_odom_create(mrgfe_reg* reg, const mrgfe_odom_params* params, mrgfe_odom** out);
 void   mrgfe_odom_destroy(mrgfe_odom* odom);
 int    mrgfe_odom_reset(mrgfe_odom* odom);         /* forgets the keyframe: the next frame is a first frame (:197-205).  The registration is not touched. */
+/* What the last completed frame's downsample did (needs no GPU; NULL arguments: MRGFE_ERR_INVALID): out[0] = its route — 0 none or the host-driven filter,
+ * 1 device-driven (one wait), 2 device-driven attempted and handed back; out[1] = the anomaly word (mrgfe_ctx_prefilter_stats: 1 no finite point, 2 PCL's
+ * "leaf size too small" pass-through, 4 no voxel); out[2] = points in; out[3] = points handed to the registration; out[4] = 1 if the source grid was built
+ * in a box the frame handed over; out[5] = frames served device-driven so far. */
+int    mrgfe_odom_stats(const mrgfe_odom* odom, int64_t out[6]);
 
 enum mrgfe_odom_outcome {
     MRGFE_ODOM_FIRST_FRAME = 0,    /* :197-205: the cloud became the keyframe, odom = identity, nothing was aligned          */
@@ -687,7 +695,11 @@ size_t mrgfe_odom_result_size(void); /* sizeof(mrgfe_odom_result) as the library
  *   msf_delta: column-major 4x4 or NULL (the identity, :211).  aligned_xyzi (may be NULL): room for width * height packed points; on ACCEPTED it receives
  *     the WHOLE input cloud, before the downsample, moved by `odom` with the bits of mrgfe_transform_cloud(cloud, odom); other outcomes leave it untouched.
  *   The wire records go up once; one kernel gathers them straight into the buffer the registration takes over (the one mrgfe_reg_set_source uploads into)
- *     and finds the exact box of the finite points on the way, which the GICP family's source grid is built in (no bounding-box pass of its own).  The
+ *     and finds the exact box of the finite points on the way, which the GICP family's source grid is built in (no bounding-box pass of its own).
+ *     With a downsample the prefilter chain's downsample stage runs directly behind that kernel: the voxel parameters come from its per-tile boxes (device
+ *     form: from a pass over the cloud), ONE wait brings down the kept count, the kept points' exact box, the finite count and an anomaly word, and that
+ *     box serves the source grid when every kept point is finite; an anomaly (PCL's "leaf size too small" pass-through, no finite point, no voxel) goes
+ *     through the host-driven filter, same result (mrgfe_odom_stats).  The stage leaves mrgfe_ctx_prefilter_stats and the remembered chain output alone.  The
  *     registration owns every cloud it keeps: `data` is free when the call returns, and a keyframe never aliases caller memory.
  *   A failing call (a bad layout, a short payload, a NULL argument: MRGFE_ERR_INVALID; a cloud with nothing left after the downsample: MRGFE_ERR_EMPTY; an
  *     alignment or target build that returns an error code: that code) leaves the handle's state and the registration's source and target as they were:

@@ -73,10 +73,14 @@ int mrgfe_dbg_node_ndt_rounds(const mrgfe_node* node, int member, int cap, uint3
  * MRGFE_FIT_SWEEP sets the initial value), 0 = round 2's pyramid walk for every queued query.  Any other value only asks.  Returns the
  * setting in effect.  Both give the exact nearest distances (tests/test_gpu_fitness_passes.py). */
 int mrgfe_dbg_set_fit_sweep(int mode);
-/* mrgfe_prefilter / mrgfe_prefilter_device with VoxelGrid + RadiusOutlierRemoval or VoxelGrid + StatisticalOutlierRemoval (mean_k in 1..63): 1 (default)
+/* The prefilter chains the device-driven form serves (mrgfe_ctx_prefilter_stats lists them) and the downsample of mrgfe_odom_frame[_device]: 1 (default)
  * the stages' point counts stay on the device and the call waits once at its end, 0 every stage reports its count to the host (round 3; also what an
- * unusual scan falls back to); other values query.  Same outputs either way (mrgfe_ctx_prefilter_stats reports the route a call took). */
+ * unusual scan falls back to); other values query.  Same outputs either way (mrgfe_ctx_prefilter_stats and mrgfe_odom_stats report the route a call took). */
 int mrgfe_dbg_set_prefilter_device_driven(int mode);
+/* What the last prefilter chain call on this context left for mrgfe_reg_set_source_from_prefilter: *remembered = 1 with the point count and the box
+ * (min xyz, max xyz) when a device-driven chain's output stayed in the caller's device buffer and its box is known to enclose finite points only, else 0
+ * (n, box may be NULL; box is written only when remembered). */
+int mrgfe_dbg_prefilter_output(mrgfe_ctx* ctx, int* remembered, size_t* n, float box[6]);
 /* StatisticalOutlierRemoval's threshold from the mean distances dist[n] and the flags valid[n] (1: all mean_k neighbours were found): out[0] = sum of
  * dist, out[1] = sum of float(dist * dist), out[2] = sum of valid, out[3] = mean + stddev_mul * sqrt(variance) as the reference computes it, out[4] = 1
  * iff both sums are certified to have the same bits in every order of addition (csrc/sor_threshold.h: the sum is below 2^(q + 52) for 2^q the lowest

@@ -21,6 +21,7 @@ FIT_EXACT, FIT_PRUNED, FIT_ABOVE_CAP, FIT_SKIPPED = 0, 1, 2, 3  # enum mrgfe_fit
 SEARCH = {"KDTREE": 0, "DIRECT26": 1, "DIRECT7": 2, "DIRECT1": 3}
 # bits of the device-driven prefilter chain's anomaly word (mrgfe_ctx_prefilter_stats out[1])
 PF_ANOMALY_EMPTY, PF_ANOMALY_OVERFLOW, PF_ANOMALY_NO_VOXEL, PF_ANOMALY_CERTIFICATE, PF_ANOMALY_RECHECK, PF_ANOMALY_CELLS = 1, 2, 4, 8, 16, 256
+PF_ANOMALY_NON_FINITE = 32  # a non-finite point reached the outlier filter
 
 
 def layout(stride: int, xyz_offset: int = 0, intensity_offset: int = 12) -> int:
@@ -339,6 +340,7 @@ SIGNATURES = {
     "mrgfe_odom_create": (C.c_int, [_vp, C.POINTER(OdomParams), C.POINTER(_vp)]),
     "mrgfe_odom_destroy": (None, [_vp]),
     "mrgfe_odom_reset": (C.c_int, [_vp]),
+    "mrgfe_odom_stats": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mrgfe_odom_frame": (C.c_int, [_vp, C.POINTER(KeyframeParams), _vp, C.c_size_t, C.c_double, _fp, C.c_int, _fp, C.POINTER(OdomResult)]),
     "mrgfe_odom_frame_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_double, _fp, C.c_int, _fp, C.POINTER(OdomResult)]),
     "mrgfe_batch_create": (C.c_int, [_vp, C.POINTER(RegParams), C.POINTER(_vp)]),
@@ -430,6 +432,7 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_node_ndt_rounds": (C.c_int, [_vp, C.c_int, C.c_int, _u32p, _u32p]),
     "mrgfe_dbg_set_fit_sweep": (C.c_int, [C.c_int]),
     "mrgfe_dbg_set_prefilter_device_driven": (C.c_int, [C.c_int]),
+    "mrgfe_dbg_prefilter_output": (C.c_int, [_vp, _ip, _szp, _fp]),
     "mrgfe_dbg_sor_threshold": (C.c_int, [_vp, _fp, _u32p, C.c_size_t, C.c_double, C.c_int, _dp]),
     "mrgfe_dbg_floor_ransac": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(C.c_int), _fp, _ip, _szp, _ip, _ip]),
     "mrgfe_dbg_floor_normals": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, C.c_double, _fp, C.POINTER(C.c_uint8)]),

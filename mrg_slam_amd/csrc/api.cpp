@@ -1469,6 +1469,16 @@ int mrgfe_dbg_select_prune(int n_pairs, const double* lower, const double* upper
 }
 int mrgfe_dbg_set_prefilter_device_driven(int mode) { return prefilter_set_device_driven(mode); }
 
+int mrgfe_dbg_prefilter_output(mrgfe_ctx* ctx, int* remembered, size_t* n, float box[6])
+{
+    if (!ctx || !remembered) { set_error("mrgfe_dbg_prefilter_output: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(ctx);
+    *remembered = ctx->pf_out_valid ? 1 : 0;
+    if (n) *n = ctx->pf_out_valid ? ctx->pf_out_n : 0;
+    if (box && ctx->pf_out_valid) std::memcpy(box, ctx->pf_out_box, sizeof(ctx->pf_out_box));
+    return MRGFE_OK;
+}
+
 int mrgfe_dbg_sor_threshold(mrgfe_ctx* ctx, const float* dist, const uint32_t* valid, size_t n, double stddev_mul, int on_device, double out[6])
 {
     if (!out || (n && (!dist || !valid)) || (on_device && !ctx)) { set_error("mrgfe_dbg_sor_threshold: NULL argument"); return MRGFE_ERR_INVALID; }

@@ -1,6 +1,7 @@
 // csrc/filters.h — prefilter chain launchers (filters.hip). Device-pointer forms chain without leaving HBM; the
 // host-pointer forms back the C ABI (include/mrgfe.h).
 #pragma once
+#include "cellsort.h"
 #include "common.h"
 
 namespace mrgfe {
@@ -32,9 +33,19 @@ struct PrefilterChain {
     int    mean_k = 30;
     double stddev_mul = 1.2;
 };
-// 1: the usual chains (voxel grid + radius filter, voxel grid + statistical filter with mean_k in 1..63) keep their point counts on the device and wait
-// once (default); 0: host-driven stages; < 0: query
+// 1: the chains keep their point counts on the device and wait once (default; every chain but the statistical filter behind anything other than a voxel
+// grid, or with mean_k outside 1..63), and so does the odometry frame's downsample; 0: host-driven stages; < 0: query
 int prefilter_set_device_driven(int mode);
+// The chain's downsample stage alone, behind a caller's own head kernel (the odometry frame; filters.hip): method 1 VoxelGrid, 2 ApproximateVoxelGrid.
+struct DownsampleReport {
+    int      route;        // 0 the switch is off (nothing was launched), 1 served, 2 an anomaly: the caller runs the host-driven filter
+    uint32_t anomaly;      // the chain's anomaly word
+    uint32_t n_finite_in;  // finite points of the input
+    uint32_t kept;         // points in d_out (route 1)
+    uint32_t kept_finite;  // ... finite among them
+    float    box[6];       // ... and their box: min xyz, max xyz
+};
+int downsample_device_driven(mrgfe_ctx* ctx, int method, const float4* d_in, size_t n, const BBox* d_tile_boxes, float leaf, int min_pts, float4* d_out, DownsampleReport* rep);
 // mrgfe_dbg_sor_threshold (include/mrgfe_debug.h): the statistical filter's sums, threshold and certificate, host loop or the chain's kernels
 int sor_threshold_debug(mrgfe_ctx* ctx, const float* dist, const uint32_t* valid, size_t n, double stddev_mul, int on_device, double out[6]);
 // the three passes back to back on the device (one upload, one download)

@@ -226,7 +226,9 @@ __device__ __forceinline__ void avg_cell3(const float4& p, float inv, int c[3])
 #pragma clang fp contract(off)
     c[0] = avg_cell(p.x * inv); c[1] = avg_cell(p.y * inv); c[2] = avg_cell(p.z * inv);
 }
-__global__ __launch_bounds__(256) void avg_keys_kernel(const float4* __restrict__ in, uint32_t n, float inv, uint32_t* __restrict__ keys)
+// The five passes take the point count as an argument (the single filter: the host knows it) or read it from a Slice in device memory (the
+// device-driven chain, whose launches are sized for the input and skip what lies beyond the live count): one body each.
+__device__ __forceinline__ void avg_keys_body(const float4* __restrict__ in, uint32_t n, float inv, uint32_t* __restrict__ keys)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
@@ -235,8 +237,8 @@ __global__ __launch_bounds__(256) void avg_keys_kernel(const float4* __restrict_
     keys[i] = (static_cast<uint32_t>(c[0]) * 7171u + static_cast<uint32_t>(c[1]) * 3079u + static_cast<uint32_t>(c[2]) * 4231u) & 511u;
 }
 // sorted position j starts a stretch iff its entry or its cell differs from position j - 1's; the first point of a stretch that is not its entry's first flushes
-__global__ __launch_bounds__(256) void avg_heads_kernel(const float4* __restrict__ in, const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv, uint32_t n, float inv,
-                                                         uint32_t* __restrict__ head, uint32_t* __restrict__ flusher)
+__device__ __forceinline__ void avg_heads_body(const float4* __restrict__ in, const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv, uint32_t n, float inv,
+                                               uint32_t* __restrict__ head, uint32_t* __restrict__ flusher)
 {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j >= n) return;
@@ -252,16 +254,16 @@ __global__ __launch_bounds__(256) void avg_heads_kernel(const float4* __restrict
     }
     head[j] = h;
 }
-__global__ __launch_bounds__(256) void avg_segments_kernel(const uint32_t* __restrict__ head, const uint32_t* __restrict__ ord, uint32_t n, const uint32_t* __restrict__ n_runs,
-                                                            uint32_t* __restrict__ seg_start)
+__device__ __forceinline__ void avg_segments_body(const uint32_t* __restrict__ head, const uint32_t* __restrict__ ord, uint32_t n, const uint32_t* __restrict__ n_runs,
+                                                  uint32_t* __restrict__ seg_start)
 {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j >= n) return;
     if (head[j]) seg_start[ord[j]] = j;
     if (j + 1 == n) seg_start[*n_runs] = n;
 }
-// rank of every entry among the occupied ones (their last stretches close the output in entry order)
-__global__ __launch_bounds__(512) void avg_entry_ranks_kernel(const uint32_t* __restrict__ sk, uint32_t n, uint32_t* __restrict__ rank)
+// rank of every entry among the occupied ones (their last stretches close the output in entry order); the binary search runs over the first n sorted keys
+__device__ __forceinline__ void avg_entry_ranks_body(const uint32_t* __restrict__ sk, uint32_t n, uint32_t* __restrict__ rank)
 {
     __shared__ uint32_t lds[16];
     const uint32_t b = threadIdx.x;
@@ -274,9 +276,9 @@ __global__ __launch_bounds__(512) void avg_entry_ranks_kernel(const uint32_t* __
     uint32_t total;
     rank[b] = block_exclusive_scan<512>(occupied, lds, &total);
 }
-__global__ __launch_bounds__(256) void avg_emit_kernel(const float4* __restrict__ in, const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv, uint32_t n,
-                                                        const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ totals /* runs, flushing points */,
-                                                        const uint32_t* __restrict__ fpos, const uint32_t* __restrict__ entry_rank, float4* __restrict__ out)
+__device__ __forceinline__ void avg_emit_body(const float4* __restrict__ in, const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv, uint32_t n,
+                                              const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ totals /* runs, flushing points */,
+                                              const uint32_t* __restrict__ fpos, const uint32_t* __restrict__ entry_rank, float4* __restrict__ out)
 {
 #pragma clang fp contract(off)
     const uint32_t r = blockIdx.x * 256u + threadIdx.x;
@@ -291,6 +293,49 @@ __global__ __launch_bounds__(256) void avg_emit_kernel(const float4* __restrict_
     const uint32_t entry = sk[b];
     const uint32_t op = (e < n && sk[e] == entry) ? fpos[sv[e]] : totals[1] + entry_rank[entry];
     out[op] = make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
+}
+__global__ __launch_bounds__(256) void avg_keys_kernel(const float4* __restrict__ in, uint32_t n, float inv, uint32_t* __restrict__ keys) { avg_keys_body(in, n, inv, keys); }
+__global__ __launch_bounds__(256) void avg_heads_kernel(const float4* __restrict__ in, const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv, uint32_t n, float inv,
+                                                         uint32_t* __restrict__ head, uint32_t* __restrict__ flusher)
+{
+    avg_heads_body(in, sk, sv, n, inv, head, flusher);
+}
+__global__ __launch_bounds__(256) void avg_segments_kernel(const uint32_t* __restrict__ head, const uint32_t* __restrict__ ord, uint32_t n, const uint32_t* __restrict__ n_runs,
+                                                            uint32_t* __restrict__ seg_start)
+{
+    avg_segments_body(head, ord, n, n_runs, seg_start);
+}
+__global__ __launch_bounds__(512) void avg_entry_ranks_kernel(const uint32_t* __restrict__ sk, uint32_t n, uint32_t* __restrict__ rank) { avg_entry_ranks_body(sk, n, rank); }
+__global__ __launch_bounds__(256) void avg_emit_kernel(const float4* __restrict__ in, const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv, uint32_t n,
+                                                        const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ totals, const uint32_t* __restrict__ fpos,
+                                                        const uint32_t* __restrict__ entry_rank, float4* __restrict__ out)
+{
+    avg_emit_body(in, sk, sv, n, seg_start, totals, fpos, entry_rank, out);
+}
+// the device-driven forms: the live count is sl->n (the chain's PfState::sl_in); the numbers of stretches and of flushing points stay in `totals`
+__global__ __launch_bounds__(256) void avg_keys_dd_kernel(const float4* __restrict__ in, const Slice* __restrict__ sl, float inv, uint32_t* __restrict__ keys)
+{
+    avg_keys_body(in, sl->n, inv, keys);
+}
+__global__ __launch_bounds__(256) void avg_heads_dd_kernel(const float4* __restrict__ in, const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv, const Slice* __restrict__ sl,
+                                                            float inv, uint32_t* __restrict__ head, uint32_t* __restrict__ flusher)
+{
+    avg_heads_body(in, sk, sv, sl->n, inv, head, flusher);
+}
+__global__ __launch_bounds__(256) void avg_segments_dd_kernel(const uint32_t* __restrict__ head, const uint32_t* __restrict__ ord, const Slice* __restrict__ sl,
+                                                               const uint32_t* __restrict__ n_runs, uint32_t* __restrict__ seg_start)
+{
+    avg_segments_body(head, ord, sl->n, n_runs, seg_start);
+}
+__global__ __launch_bounds__(512) void avg_entry_ranks_dd_kernel(const uint32_t* __restrict__ sk, const Slice* __restrict__ sl, uint32_t* __restrict__ rank)
+{
+    avg_entry_ranks_body(sk, sl->n, rank);
+}
+__global__ __launch_bounds__(256) void avg_emit_dd_kernel(const float4* __restrict__ in, const uint32_t* __restrict__ sk, const uint32_t* __restrict__ sv, const Slice* __restrict__ sl,
+                                                           const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ totals, const uint32_t* __restrict__ fpos,
+                                                           const uint32_t* __restrict__ entry_rank, float4* __restrict__ out)
+{
+    avg_emit_body(in, sk, sv, sl->n, seg_start, totals, fpos, entry_rank, out);
 }
 
 int filter_approx_voxelgrid_device(mrgfe_ctx* ctx, const float4* d_in, size_t n, float leaf, float4* d_out, size_t* out_n)
@@ -441,23 +486,29 @@ static int host_wrap(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride,
 // The same chain serves distance filter -> VoxelGrid -> StatisticalOutlierRemoval, the reference's code default: behind the voxel grid's compaction
 // the k-NN mean distances on a grid that sizes itself (nn_knn_mean_device_driven) and PCL's threshold from certified tree sums (sor_threshold.h)
 // take the radius filter's place (tests/test_gpu_prefilter_statistical.py).
+// The chain is three stages (pf_stage_head / _downsample / _outlier below), so the other chains the parameters express are served the same way: the
+// approximate grid's passes over the live count or no downsample at all in the middle, the radius filter or only a finish at the end
+// (tests/test_gpu_prefilter_chains.py); the downsample stage alone serves the odometry frame (downsample_device_driven).
 struct PfState {
-    const float4* cp[2];  // cloud read by the voxel grid / by the radius filter
+    const float4* cp[2];  // cloud read by the downsample stage / by the outlier stage
     Slice       sl_in;    // points after the distance filter
     Slice       sl_vox;   // voxel runs (their centroids are compacted by the min-points flags)
-    Slice       sl_rad;   // points after the voxel grid
+    Slice       sl_rad;   // points after the downsample stage
     uint32_t    nv, pad0;
     VoxelParams vp;
     LeafSlice   ls;
-    uint32_t    counts[6];  // after the distance filter, finite among them, voxels, after the voxel grid, after the outlier filter (radius or statistical)
+    // after the distance filter, finite among them, voxels, after the downsample stage (APPROX_VOXELGRID: both the emitted centroids; no downsample: both
+    // counts[0]), after the outlier filter (none: counts[3])
+    uint32_t    counts[6];
     uint32_t    anomaly;
     uint32_t    pad1;
-    uint32_t    bb_n[2];    // partial bounding boxes (one per tile of the producer's INPUT) of the cloud the voxel grid / the radius filter reads
+    uint32_t    bb_n[2];    // partial bounding boxes (one per tile the producer left) of the cloud the downsample stage / the outlier stage reads
     sor::Result sor;        // StatisticalOutlierRemoval: the sums, the threshold and their certificate (sor_finish_kernel)
 };
 constexpr uint32_t kPfAnomalyEmpty = 1u, kPfAnomalyOverflow = 2u, kPfAnomalyNoVoxel = 4u;
 constexpr uint32_t kPfAnomalyCertificate = 8u;  // a tree sum of the statistical filter is not certified to be the sequential one (sor_threshold.h)
 constexpr uint32_t kPfAnomalyRecheck = 16u;     // set by the HOST behind the wait: its own build of the threshold's tail gives other bits than the device's
+constexpr uint32_t kPfAnomalyNonFinite = 32u;   // a non-finite point reached the outlier stage (distance filter off and no VoxelGrid in front of it)
 // the pinned status record the host reads behind its one wait: words 0..4 the stage counts, 5 the anomaly word, 6 the completion mark; the box of the
 // voxel centroids at word 8 (28 bytes); the statistical filter's result at byte 64
 constexpr size_t kPfStatusSorOffset = 64, kPfStatusBytes = kPfStatusSorOffset + sizeof(sor::Result);
@@ -750,6 +801,54 @@ __global__ __launch_bounds__(256) void voxel_centroid_dd_kernel(const float4* __
     centroids[s] = make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
     keep[s] = (e - b) >= static_cast<uint32_t>(min_pts) ? 1u : 0u;
 }
+// ---- the single-workgroup kernels between the stages of the chains without a VoxelGrid or without an outlier filter ----------------------------------
+// downsample NONE: the outlier stage reads the cloud, the count and the boxes the head left
+__global__ __launch_bounds__(256) void pf_no_downsample_kernel(PfState* __restrict__ st, const BBox* __restrict__ partial, int outlier_follows)
+{
+    const BBox bb = block_merge_partials(partial, st->bb_n[0]);
+    if (threadIdx.x) return;
+    const uint32_t n = st->sl_in.n;
+    st->counts[1] = bb.n_finite;
+    st->counts[2] = n;
+    st->counts[3] = n;
+    st->sl_rad = st->sl_in;
+    st->bb_n[1] = st->bb_n[0];
+    if (outlier_follows && n == 0) st->anomaly |= kPfAnomalyEmpty;
+    if (outlier_follows && bb.n_finite != n) st->anomaly |= kPfAnomalyNonFinite;
+}
+// APPROX_VOXELGRID: the emitted centroids (totals[0], left by the scan of the stretch heads) become the outlier stage's count; their boxes follow
+// (bounding_box_partials over sl_rad: one per tile of the OUTPUT)
+__global__ __launch_bounds__(256) void pf_approx_done_kernel(PfState* __restrict__ st, const BBox* __restrict__ partial_in, const uint32_t* __restrict__ totals)
+{
+    const BBox bb = block_merge_partials(partial_in, st->bb_n[0]);
+    if (threadIdx.x) return;
+    const uint32_t runs = totals[0];
+    st->counts[1] = bb.n_finite;
+    st->counts[2] = runs;
+    st->counts[3] = runs;
+    st->sl_rad = pf_slice(runs);
+    st->bb_n[1] = st->sl_rad.nblk;
+    if (st->sl_in.n == 0) st->anomaly |= kPfAnomalyEmpty;
+}
+// the approximate grid's centroids are non-finite where its points were: the outlier stage hands such a cloud back
+__global__ __launch_bounds__(256) void pf_finite_check_kernel(PfState* __restrict__ st, const BBox* __restrict__ partial)
+{
+    const BBox bb = block_merge_partials(partial, st->bb_n[1]);
+    if (threadIdx.x == 0 && bb.n_finite != st->sl_rad.n) st->anomaly |= kPfAnomalyNonFinite;
+}
+// A chain without an outlier filter ends here: the count and the merged box of the downsample stage's output (nn_build_device_driven reports that box
+// where an outlier filter follows) and the host's status words, as pf_compact_kernel<2> writes them.
+__global__ __launch_bounds__(256) void pf_finish_kernel(PfState* __restrict__ st, const BBox* __restrict__ partial, uint32_t* __restrict__ h_status, BBox* __restrict__ h_box)
+{
+    const BBox bb = block_merge_partials(partial, st->bb_n[1]);
+    if (threadIdx.x) return;
+    st->counts[4] = st->counts[3];
+    *h_box = bb;
+    for (int k = 0; k < 5; ++k) h_status[k] = st->counts[k];
+    h_status[5] = st->anomaly;
+    __threadfence_system();
+    h_status[6] = 0x600df00du;
+}
 // ---- StatisticalOutlierRemoval's threshold without a host round trip (sor_threshold.h) --------------------------------------------------------------
 // The reference's two f64 sums are sequential over the points; a dependent chain of n additions on one lane would cost as much as the rest of the chain.
 // They are added in a tree instead — per thread, per wavefront, per tile of 2048 points, over the tiles — together with the minimum lowest-bit exponent
@@ -911,11 +1010,17 @@ static NnDeviceDrivenGrid& pf_grid(mrgfe_ctx* ctx)
     return *ctx->pf_grid;
 }
 
-// the chains the device-driven form serves (the others, and its anomalies, go through the host-driven passes)
+// The chains the device-driven form serves (the others, and its anomalies, go through the host-driven passes): every [distance] -> downsample ->
+// outlier chain the parameters express, except the statistical filter behind anything but a VoxelGrid (without a leaf there is no rule for the k-NN
+// grid's cell edge that the host could know: sor_cell_edge) and mean_k beyond a wavefront's list.
+static int  chain_downsample(const PrefilterChain& ch) { return ch.approx_voxelgrid ? 2 : (ch.voxelgrid ? 1 : 0); }
 static bool device_driven_applies(const PrefilterChain& ch, uint32_t n)
 {
-    const bool outlier_served = ch.outlier == 1 || (ch.outlier == 2 && ch.mean_k >= 1 && ch.mean_k <= 63);  // (mean_k + 1 entries must fit a wavefront's list)
-    return prefilter_device_driven_mode() && !ch.approx_voxelgrid && ch.voxelgrid && outlier_served && n != 0 && ch.leaf > 0;
+    if (!prefilter_device_driven_mode() || n == 0) return false;
+    const int down = chain_downsample(ch);
+    if (down != 0 && !(ch.leaf > 0)) return false;
+    if (ch.outlier == 2) return down == 1 && ch.mean_k >= 1 && ch.mean_k <= 63;  // (mean_k + 1 entries must fit a wavefront's list)
+    return true;
 }
 
 // The cell edge of the statistical filter's k-NN grid.  Search results do not depend on it, only the time does, and the host cannot run NnGrid::build's
@@ -933,26 +1038,179 @@ constexpr uint32_t kSorCellsCap = (1u << 24) - 1u;  // 24 key bits: three radix 
 #endif
 static float sor_cell_edge(const PrefilterChain& ch) { return std::max(MRGFE_SOR_CELL_LEAVES * ch.leaf, 0.2f); }
 
-// A chain the device-driven form serves (device_driven_applies).  The packed input is in d_in already, or — `head` and its uploaded records `d_raw` —
-// the scan head kernel writes it there as the chain's first launch.  Returns MRGFE_OK with *used = true when it produced the output, *used = false
-// (an anomaly) when the caller has to run the host-driven passes over d_in.
-static int filter_chain_device_driven(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHead* head, const void* d_raw, float4* d_in, uint32_t n, float4* d_work, float4* d_final,
-                                      size_t* out_n, bool* used)
+// ---- the chain as three stages ----------------------------------------------------------------------------------------------------------------------
+// head / distance -> downsample (NONE, VOXELGRID, APPROX_VOXELGRID) -> outlier (NONE, RADIUS, STATISTICAL).  A stage hands the next one its live count
+// (PfState::sl_in, then sl_rad), its cloud (cp[0], then cp[1]) and one box per tile of that cloud (bb_n[0], then bb_n[1] entries) — nothing through the
+// host.  The last stage writes the pinned status record; pf_run_stages waits once behind it.
+// Buffers: three besides the scratch slots — the packed input, the work buffer the caller gets the result in, and a third one.  Each stage writes where
+// its reader expects it (s1_out: the downsample stage's input; s2_out: the outlier stage's input, the work buffer itself when no outlier filter follows).
+struct PfRun {
+    mrgfe_ctx*            ctx;
+    const PrefilterChain* ch;
+    int                   down;  // chain_downsample
+    uint32_t              n;     // points of the input: every launch is sized for it
+    SliceTable            tab;
+    PfState*              d_st;
+    uint32_t*             h_status;
+    BBox*                 h_box;
+    BBox*                 d_part;      // scratch for the per-tile boxes
+    const BBox*           boxes_in;    // the boxes of the downsample stage's input: d_part, or the ones the caller's own head kernel left
+    uint32_t*             d_blk;
+    const float4*         s1_out;
+    float4 *              s2_out, *d_work;
+    dim3                  g256, gtiles;
+};
+// what the host reads behind the wait
+struct PfReport {
+    uint32_t counts[5];
+    uint32_t anomaly;
+    BBox     box;  // of the outlier stage's input, or (no outlier filter) of the output
+};
+
+// Stage 1.  The packed input is in d_in already, or — `head` and its uploaded records `d_raw` — the scan head kernel writes it there as the chain's first
+// launch; `d_head_boxes`: the caller's own head kernel has left one box per tile of d_in (the odometry frame), no distance filter.
+static int pf_stage_head(PfRun& r, const ScanHead* head, const void* d_raw, float4* d_in, const BBox* d_head_boxes)
 {
-    *used = false;
-    hipStream_t st = ctx->stream;
-    SliceTable  tab;
-    tab.build(&n, 1);
+    mrgfe_ctx*            ctx = r.ctx;
+    const PrefilterChain& ch = *r.ch;
+    hipStream_t           st = ctx->stream;
+    const dim3            b256(256);
+    uint32_t*             d_flags = ctx->scratch[7].as<uint32_t>();
+    float4*               dist_out = const_cast<float4*>(r.s1_out);
+    if (head) {  // (with the distance filter on, the head is pf_distance_tiles_kernel too)
+        const ScanHeadFlags fl{ch.near_t, ch.far_t, d_flags, r.d_blk, r.d_st, r.s1_out, r.s2_out};
+        MRGFE_TRY(launch_scan_head(ctx, *head, d_raw, d_in, ch.distance ? &fl : nullptr));
+    }
+    r.boxes_in = r.d_part;
+    if (ch.distance) {
+        // flags + tile counts (and the state's first values), compaction with the count and the kept points' boxes
+        if (!head) hipLaunchKernelGGL(pf_distance_tiles_kernel, r.gtiles, b256, 0, st, d_in, r.n, ch.near_t, ch.far_t, d_flags, r.d_blk, r.d_st, r.s1_out, r.s2_out);
+        hipLaunchKernelGGL(pf_compact_kernel<0>, r.gtiles, b256, 0, st, d_in, d_flags, r.d_blk, r.n, dist_out, r.d_st, r.h_status, r.d_part);
+    } else {
+        if (r.s1_out != d_in) MRGFE_HIP_CHECK(hipMemcpyAsync(dist_out, d_in, size_t(r.n) * 16, hipMemcpyDeviceToDevice, st));  // (no stage at all: the output is the input)
+        hipLaunchKernelGGL(pf_init_kernel, dim3(1), dim3(1), 0, st, r.d_st, r.s1_out, r.s2_out, r.n);
+        if (d_head_boxes) r.boxes_in = d_head_boxes;
+        else MRGFE_TRY(bounding_box_partials(ctx, &r.d_st->cp[0], &r.d_st->sl_in, r.tab, r.d_part));
+    }
+    MRGFE_HIP_CHECK(hipGetLastError());
+    return MRGFE_OK;
+}
+
+// Stage 2: sl_in points at cp[0] -> sl_rad points at cp[1] with bb_n[1] boxes in d_part
+static int pf_stage_downsample(PfRun& r)
+{
+    mrgfe_ctx*            ctx = r.ctx;
+    const PrefilterChain& ch = *r.ch;
+    hipStream_t           st = ctx->stream;
+    const dim3            b256(256);
+    const uint32_t        n = r.n;
+    PfState*              d_st = r.d_st;
+    DevBuf &dk = ctx->scratch[2], &dv = ctx->scratch[3], &dkt = ctx->scratch[4], &dvt = ctx->scratch[5], &dh = ctx->scratch[6], &dseg = ctx->scratch[9], &dcent = ctx->scratch[10],
+           &dkeep = ctx->scratch[11];
+    uint32_t *sk, *sv;
+    if (r.down == 0) {
+        hipLaunchKernelGGL(pf_no_downsample_kernel, dim3(1), b256, 0, st, d_st, r.boxes_in, ch.outlier != 0 ? 1 : 0);
+    } else if (r.down == 1) {
+        // VoxelGrid: voxel parameters from the boxes (device), keys, stable sort (32 key bits: the host does not know the cell count), runs, centroids
+        hipLaunchKernelGGL(pf_voxel_params_kernel, dim3(1), b256, 0, st, d_st, r.boxes_in, ch.leaf);
+        MRGFE_TRY(ndt_launch_cellkeys(ctx, &d_st->cp[0], &d_st->sl_in, r.tab, &d_st->vp, dk.as<uint32_t>(), dh.as<uint32_t>()));
+        MRGFE_TRY(radix_sort_pairs(ctx, dk.as<uint32_t>(), dv.as<uint32_t>(), dkt.as<uint32_t>(), dvt.as<uint32_t>(), &d_st->sl_in, r.tab, 32, dh.as<uint32_t>(), &sk, &sv, true, true));
+        MRGFE_TRY(run_head_tile_counts(ctx, sk, &d_st->sl_in, r.tab, &d_st->nv, r.d_blk));
+        hipLaunchKernelGGL(pf_leaves_kernel, dim3(1), b256, 0, st, d_st, r.d_blk);
+        uint32_t* d_seg = dseg.as<uint32_t>();
+        int32_t*  d_segkey = reinterpret_cast<int32_t*>(d_seg + size_t(n) + 4);
+        MRGFE_TRY(ndt_launch_segments(ctx, sk, &d_st->sl_in, r.tab, &d_st->nv, r.d_blk, &d_st->ls, d_seg, d_segkey));
+        hipLaunchKernelGGL(voxel_centroid_dd_kernel, r.g256, b256, 0, st, r.s1_out, sv, d_seg, &d_st->sl_vox, ch.min_pts, dcent.as<float4>(), dkeep.as<uint32_t>());
+        MRGFE_TRY(tile_sums(ctx, dkeep.as<uint32_t>(), &d_st->sl_vox, r.tab, r.d_blk));
+        hipLaunchKernelGGL(pf_compact_kernel<1>, r.gtiles, b256, 0, st, dcent.as<float4>(), dkeep.as<uint32_t>(), r.d_blk, 0u, r.s2_out, d_st, r.h_status, r.d_part);
+    } else {
+        // ApproximateVoxelGrid (filter_approx_voxelgrid_device's passes over the live count): entry keys, 9-bit stable sort, stretch heads and flushing
+        // points, their two scans, the entry ranks, one centroid per stretch at its place in the sequential loop's output
+        DevBuf &dhead = ctx->scratch[7], &dfpos = dcent, &dflush = dkeep, &dord = ctx->scratch[12], &drank = ctx->scratch[14];
+        const Slice* sl = &d_st->sl_in;
+        const float  inv = 1.0f / ch.leaf;  // inverse_leaf_size_ = Array3f::Ones() / leaf_size_
+        uint32_t*    d_tot = r.d_blk + r.tab.total_blks;  // [0] stretches, [1] flushing points
+        hipLaunchKernelGGL(avg_keys_dd_kernel, r.g256, b256, 0, st, r.s1_out, sl, inv, dk.as<uint32_t>());
+        MRGFE_TRY(radix_sort_pairs(ctx, dk.as<uint32_t>(), dv.as<uint32_t>(), dkt.as<uint32_t>(), dvt.as<uint32_t>(), sl, r.tab, 9, dh.as<uint32_t>(), &sk, &sv, true));
+        MRGFE_HIP_CHECK(hipMemsetAsync(dflush.p, 0, size_t(n) * 4, st));
+        hipLaunchKernelGGL(avg_heads_dd_kernel, r.g256, b256, 0, st, r.s1_out, sk, sv, sl, inv, dhead.as<uint32_t>(), dflush.as<uint32_t>());
+        MRGFE_TRY(exclusive_scan(ctx, dhead.as<uint32_t>(), dord.as<uint32_t>(), sl, r.tab, r.d_blk, d_tot));
+        hipLaunchKernelGGL(avg_segments_dd_kernel, r.g256, b256, 0, st, dhead.as<uint32_t>(), dord.as<uint32_t>(), sl, d_tot, dseg.as<uint32_t>());
+        MRGFE_TRY(exclusive_scan(ctx, dflush.as<uint32_t>(), dfpos.as<uint32_t>(), sl, r.tab, r.d_blk, d_tot + 1));
+        hipLaunchKernelGGL(avg_entry_ranks_dd_kernel, dim3(1), dim3(512), 0, st, sk, sl, drank.as<uint32_t>());
+        hipLaunchKernelGGL(avg_emit_dd_kernel, r.g256, b256, 0, st, r.s1_out, sk, sv, sl, dseg.as<uint32_t>(), d_tot, dfpos.as<uint32_t>(), drank.as<uint32_t>(), r.s2_out);
+        hipLaunchKernelGGL(pf_approx_done_kernel, dim3(1), b256, 0, st, d_st, r.boxes_in, d_tot);
+        MRGFE_TRY(bounding_box_partials(ctx, &d_st->cp[1], &d_st->sl_rad, r.tab, r.d_part));
+        if (ch.outlier != 0) hipLaunchKernelGGL(pf_finite_check_kernel, dim3(1), b256, 0, st, d_st, r.d_part);
+    }
+    MRGFE_HIP_CHECK(hipGetLastError());
+    return MRGFE_OK;
+}
+
+// Stage 3: the outlier filter over sl_rad points at s2_out into the work buffer, or the finish of a chain without one; either writes the status record
+static int pf_stage_outlier(PfRun& r)
+{
+    mrgfe_ctx*            ctx = r.ctx;
+    const PrefilterChain& ch = *r.ch;
+    hipStream_t           st = ctx->stream;
+    const dim3            b256(256);
+    const uint32_t        n = r.n;
+    PfState*              d_st = r.d_st;
+    if (ch.outlier == 0) {
+        hipLaunchKernelGGL(pf_finish_kernel, dim3(1), b256, 0, st, d_st, r.d_part, r.h_status, r.h_box);
+        MRGFE_HIP_CHECK(hipGetLastError());
+        return MRGFE_OK;
+    }
+    // a grid that sizes itself (from the boxes of the stage's input), flags, compaction
+    NnDeviceDrivenGrid& grid = pf_grid(ctx);
+    uint32_t*           d_flags = ctx->scratch[7].as<uint32_t>();
+    if (ch.outlier == 1) {
+        // RadiusOutlierRemoval: inlier iff #{q: (double)sqdist <= radius*radius} >= min_neighbors + 1 (the point itself counts)
+        const float cell = static_cast<float>(ch.radius);
+        MRGFE_TRY(nn_build_device_driven(ctx, &d_st->cp[1], &d_st->sl_rad, n, r.d_part, &d_st->bb_n[1], cell, 1u << 22, grid, &d_st->anomaly, r.h_box));
+        MRGFE_TRY(nn_radius_flags_device_driven(ctx, grid, r.s2_out, &d_st->sl_rad, n, ch.radius * ch.radius, ch.radius_min_neighbors + 1, cell, d_flags));
+    } else {
+        // StatisticalOutlierRemoval: mean distance to the mean_k nearest (the exact wave-per-query search, its lists consumed in registers), the threshold
+        // from the certified tree sums, inlier iff (double)mean distance <= threshold
+        float*       d_dist = ctx->scratch[12].as<float>();
+        uint32_t*    d_valid = reinterpret_cast<uint32_t*>(d_dist + n);
+        sor::Result* h_sor = reinterpret_cast<sor::Result*>(ctx->pf_status.as<char>() + kPfStatusSorOffset);
+        MRGFE_TRY(nn_build_device_driven(ctx, &d_st->cp[1], &d_st->sl_rad, n, r.d_part, &d_st->bb_n[1], sor_cell_edge(ch), kSorCellsCap, grid, &d_st->anomaly, r.h_box));
+        MRGFE_TRY(nn_knn_mean_device_driven(ctx, grid, r.s2_out, &d_st->sl_rad, n, ch.mean_k + 1, d_dist, d_valid));
+        MRGFE_TRY(sor_threshold_launch(ctx, d_dist, d_valid, &d_st->sl_rad.n, n, ch.stddev_mul, ctx->scratch[14].as<SorPartial>(), &d_st->sor, h_sor, &d_st->anomaly));
+        hipLaunchKernelGGL(sor_flags_dd_kernel, r.g256, b256, 0, st, d_dist, &d_st->sl_rad.n, &d_st->sor.thr, d_flags);
+    }
+    MRGFE_TRY(tile_sums(ctx, d_flags, &d_st->sl_rad, r.tab, r.d_blk));
+    hipLaunchKernelGGL(pf_compact_kernel<2>, r.gtiles, b256, 0, st, r.s2_out, d_flags, r.d_blk, 0u, r.d_work, d_st, r.h_status, r.d_part);
+    MRGFE_HIP_CHECK(hipGetLastError());
+    return MRGFE_OK;
+}
+
+// The three stages and the chain's one wait.  d_work receives the result (capacity n); d_third: a buffer of n points wherever a stage needs one that is
+// neither the input nor the work buffer (an outlier filter, or the distance filter in front of the approximate grid), else unused.
+static int pf_run_stages(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHead* head, const void* d_raw, float4* d_in, uint32_t n, float4* d_work, float4* d_third,
+                         const BBox* d_head_boxes, PfReport* rep)
+{
+    PfRun r;
+    r.ctx = ctx;
+    r.ch = &ch;
+    r.down = chain_downsample(ch);
+    r.n = n;
+    r.tab.build(&n, 1);
     MRGFE_TRY(ctx->pf_state.ensure(sizeof(PfState)));
     MRGFE_TRY(ctx->pf_status.ensure(kPfStatusBytes));
-    PfState*  d_st = ctx->pf_state.as<PfState>();
-    uint32_t* h_status = ctx->pf_status.as<uint32_t>();
-    h_status[6] = 0;
-    const bool statistical = ch.outlier == 2;
-    DevBuf &dsor = ctx->scratch[12], &dsorp = ctx->scratch[14];  // the statistical filter's mean distances and flags of validity, its tiles' sums
-    if (statistical) {
-        MRGFE_TRY(dsor.ensure(size_t(n) * 8));
-        MRGFE_TRY(dsorp.ensure(sizeof(SorPartial) * (size_t(tab.total_blks) + 1)));
+    r.d_st = ctx->pf_state.as<PfState>();
+    r.h_status = ctx->pf_status.as<uint32_t>();
+    r.h_status[6] = 0;
+    r.h_box = reinterpret_cast<BBox*>(r.h_status + 8);
+    const SliceTable& tab = r.tab;
+    if (ch.outlier == 2) {  // the statistical filter's mean distances and flags of validity, its tiles' sums
+        MRGFE_TRY(ctx->scratch[12].ensure(size_t(n) * 8));
+        MRGFE_TRY(ctx->scratch[14].ensure(sizeof(SorPartial) * (size_t(tab.total_blks) + 1)));
+    }
+    if (r.down == 2) {  // the approximate grid's stretch ordinals and its 512 entry ranks
+        MRGFE_TRY(ctx->scratch[12].ensure(size_t(n) * 4));
+        MRGFE_TRY(ctx->scratch[14].ensure(sizeof(uint32_t) * 512));
     }
     DevBuf &dbb = ctx->scratch[1], &dk = ctx->scratch[2], &dv = ctx->scratch[3], &dkt = ctx->scratch[4], &dvt = ctx->scratch[5], &dh = ctx->scratch[6], &dfl = ctx->scratch[7],
            &dblk = ctx->scratch[8], &dseg = ctx->scratch[9], &dcent = ctx->scratch[10], &dkeep = ctx->scratch[11];
@@ -964,80 +1222,91 @@ static int filter_chain_device_driven(mrgfe_ctx* ctx, const PrefilterChain& ch, 
     MRGFE_TRY(dseg.ensure(sizeof(uint32_t) * (size_t(n) + 4) + sizeof(int32_t) * size_t(n)));
     MRGFE_TRY(dcent.ensure(sizeof(float4) * size_t(n)));
     MRGFE_TRY(dkeep.ensure(sizeof(uint32_t) * size_t(n)));
-    const dim3 g256((n + 255) / 256), b256(256);
-    BBox*      d_part = dbb.as<BBox>();  // one box per tile of the stage that made the cloud
-    // ---- distance filter: flags + tile counts (and the state's first values), compaction into the work buffer with the count and the kept points' boxes
-    const float4* vox_in = ch.distance ? d_work : d_in;
-    const dim3    gtiles(std::max<uint32_t>(1, tab.total_blks));
-    uint32_t*     d_blk = dblk.as<uint32_t>();
-    if (head) {  // (with the distance filter on, the head is pf_distance_tiles_kernel too)
-        const ScanHeadFlags fl{ch.near_t, ch.far_t, dfl.as<uint32_t>(), d_blk, d_st, vox_in, d_final};
-        MRGFE_TRY(launch_scan_head(ctx, *head, d_raw, d_in, ch.distance ? &fl : nullptr));
-    }
-    if (ch.distance) {
-        if (!head) hipLaunchKernelGGL(pf_distance_tiles_kernel, gtiles, b256, 0, st, d_in, n, ch.near_t, ch.far_t, dfl.as<uint32_t>(), d_blk, d_st, vox_in, d_final);
-        hipLaunchKernelGGL(pf_compact_kernel<0>, gtiles, b256, 0, st, d_in, dfl.as<uint32_t>(), d_blk, n, d_work, d_st, h_status, d_part);
+    r.d_part = dbb.as<BBox>();
+    r.d_blk = dblk.as<uint32_t>();
+    r.g256 = dim3((n + 255) / 256);
+    r.gtiles = dim3(std::max<uint32_t>(1, tab.total_blks));
+    r.d_work = d_work;
+    const bool outlier = ch.outlier != 0;
+    if (r.down == 0) {  // the outlier filter reads what the head left; without one that is the result
+        r.s1_out = outlier ? (ch.distance ? d_third : d_in) : d_work;
+        r.s2_out = const_cast<float4*>(r.s1_out);
     } else {
-        hipLaunchKernelGGL(pf_init_kernel, dim3(1), dim3(1), 0, st, d_st, vox_in, d_final, n);
-        MRGFE_TRY(bounding_box_partials(ctx, &d_st->cp[0], &d_st->sl_in, tab, d_part));
+        r.s2_out = outlier ? d_third : d_work;
+        // (the voxel grid's centroids pass through a scratch slot: it may read the buffer its compaction writes; the approximate grid emits in place)
+        if (!ch.distance) r.s1_out = d_in;
+        else r.s1_out = (r.down == 2 && !outlier) ? d_third : d_work;
     }
-    // ---- VoxelGrid: voxel parameters from the boxes (device), keys, stable sort (32 key bits: the host does not know the cell count), runs, centroids
-    hipLaunchKernelGGL(pf_voxel_params_kernel, dim3(1), b256, 0, st, d_st, d_part, ch.leaf);
-    MRGFE_TRY(ndt_launch_cellkeys(ctx, &d_st->cp[0], &d_st->sl_in, tab, &d_st->vp, dk.as<uint32_t>(), dh.as<uint32_t>()));
-    uint32_t *sk, *sv;
-    MRGFE_TRY(radix_sort_pairs(ctx, dk.as<uint32_t>(), dv.as<uint32_t>(), dkt.as<uint32_t>(), dvt.as<uint32_t>(), &d_st->sl_in, tab, 32, dh.as<uint32_t>(), &sk, &sv, true, true));
-    MRGFE_TRY(run_head_tile_counts(ctx, sk, &d_st->sl_in, tab, &d_st->nv, d_blk));
-    hipLaunchKernelGGL(pf_leaves_kernel, dim3(1), b256, 0, st, d_st, d_blk);
-    uint32_t* d_seg = dseg.as<uint32_t>();
-    int32_t*  d_segkey = reinterpret_cast<int32_t*>(d_seg + size_t(n) + 4);
-    MRGFE_TRY(ndt_launch_segments(ctx, sk, &d_st->sl_in, tab, &d_st->nv, d_blk, &d_st->ls, d_seg, d_segkey));
-    hipLaunchKernelGGL(voxel_centroid_dd_kernel, g256, b256, 0, st, vox_in, sv, d_seg, &d_st->sl_vox, ch.min_pts, dcent.as<float4>(), dkeep.as<uint32_t>());
-    MRGFE_TRY(tile_sums(ctx, dkeep.as<uint32_t>(), &d_st->sl_vox, tab, d_blk));
-    // (the voxel grid's output goes to d_final for now: the radius filter reads it there and compacts into the work buffer ...)
-    hipLaunchKernelGGL(pf_compact_kernel<1>, gtiles, b256, 0, st, dcent.as<float4>(), dkeep.as<uint32_t>(), d_blk, 0u, d_final, d_st, h_status, d_part);
-    // ---- the outlier filter: a grid that sizes itself (from the boxes of the centroids kept), flags, compaction
-    NnDeviceDrivenGrid& grid = pf_grid(ctx);
-    BBox* h_box = reinterpret_cast<BBox*>(h_status + 8);  // the box of the voxel centroids: it encloses what the outlier filter keeps of them
-    sor::Result* h_sor = reinterpret_cast<sor::Result*>(ctx->pf_status.as<char>() + kPfStatusSorOffset);
-    if (!statistical) {
-        // RadiusOutlierRemoval: inlier iff #{q: (double)sqdist <= radius*radius} >= min_neighbors + 1 (the point itself counts)
-        const float cell = static_cast<float>(ch.radius);
-        MRGFE_TRY(nn_build_device_driven(ctx, &d_st->cp[1], &d_st->sl_rad, n, d_part, &d_st->bb_n[1], cell, 1u << 22, grid, &d_st->anomaly, h_box));
-        MRGFE_TRY(nn_radius_flags_device_driven(ctx, grid, d_final, &d_st->sl_rad, n, ch.radius * ch.radius, ch.radius_min_neighbors + 1, cell, dfl.as<uint32_t>()));
-    } else {
-        // StatisticalOutlierRemoval: mean distance to the mean_k nearest (the exact wave-per-query search, its lists consumed in registers), the threshold
-        // from the certified tree sums, inlier iff (double)mean distance <= threshold
-        float*    d_dist = dsor.as<float>();
-        uint32_t* d_valid = reinterpret_cast<uint32_t*>(d_dist + n);
-        MRGFE_TRY(nn_build_device_driven(ctx, &d_st->cp[1], &d_st->sl_rad, n, d_part, &d_st->bb_n[1], sor_cell_edge(ch), kSorCellsCap, grid, &d_st->anomaly, h_box));
-        MRGFE_TRY(nn_knn_mean_device_driven(ctx, grid, d_final, &d_st->sl_rad, n, ch.mean_k + 1, d_dist, d_valid));
-        MRGFE_TRY(sor_threshold_launch(ctx, d_dist, d_valid, &d_st->sl_rad.n, n, ch.stddev_mul, dsorp.as<SorPartial>(), &d_st->sor, h_sor, &d_st->anomaly));
-        hipLaunchKernelGGL(sor_flags_dd_kernel, g256, b256, 0, st, d_dist, &d_st->sl_rad.n, &d_st->sor.thr, dfl.as<uint32_t>());
-    }
-    MRGFE_TRY(tile_sums(ctx, dfl.as<uint32_t>(), &d_st->sl_rad, tab, d_blk));
-    hipLaunchKernelGGL(pf_compact_kernel<2>, gtiles, b256, 0, st, d_final, dfl.as<uint32_t>(), d_blk, 0u, d_work, d_st, h_status, d_part);
-    MRGFE_HIP_CHECK(hipGetLastError());
-    MRGFE_HIP_CHECK(hipStreamSynchronize(st));  // the chain's one wait
-    if (h_status[6] != 0x600df00du) { set_error("prefilter: the device-driven chain did not report"); return MRGFE_ERR_HIP; }
+    MRGFE_TRY(pf_stage_head(r, head, d_raw, d_in, d_head_boxes));
+    MRGFE_TRY(pf_stage_downsample(r));
+    MRGFE_TRY(pf_stage_outlier(r));
+    MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the chain's one wait
+    if (r.h_status[6] != 0x600df00du) { set_error("prefilter: the device-driven chain did not report"); return MRGFE_ERR_HIP; }
+    for (int k = 0; k < 5; ++k) rep->counts[k] = r.h_status[k];
+    rep->anomaly = r.h_status[5];
+    rep->box = *r.h_box;
+    return MRGFE_OK;
+}
+
+// A chain the device-driven form serves (device_driven_applies).  Returns MRGFE_OK with *used = true when it produced the output, *used = false
+// (an anomaly) when the caller has to run the host-driven passes over d_in.
+static int filter_chain_device_driven(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHead* head, const void* d_raw, float4* d_in, uint32_t n, float4* d_work, float4* d_final,
+                                      size_t* out_n, bool* used)
+{
+    *used = false;
+    PfReport rep;
+    MRGFE_TRY(pf_run_stages(ctx, ch, head, d_raw, d_in, n, d_work, d_final, nullptr, &rep));
     PrefilterStats& ps = ctx->pf_stats;
-    ps.anomaly = h_status[5];
-    for (int k = 0; k < 5; ++k) ps.counts[k] = h_status[k];
-    if (statistical) {
-        ctx->knn_stats.queries = h_status[3];  // (the live count of the k-NN launch)
+    ps.anomaly = rep.anomaly;
+    for (int k = 0; k < 5; ++k) ps.counts[k] = rep.counts[k];
+    if (ch.outlier == 2) {
+        const sor::Result* h_sor = reinterpret_cast<const sor::Result*>(ctx->pf_status.as<char>() + kPfStatusSorOffset);
+        ctx->knn_stats.queries = rep.counts[3];  // (the live count of the k-NN launch)
         // the host's own build of the threshold's tail on the reported sums: the result must not depend on how the device library rounds an f64 divide or
         // square root (it costs nothing here)
         if (!sor::same_bits(sor::threshold(h_sor->sum, h_sor->sq_sum, h_sor->valid, ch.stddev_mul), h_sor->thr)) ps.anomaly |= kPfAnomalyRecheck;
     }
     if (ps.anomaly != 0) return MRGFE_OK;  // something unusual: the host-driven chain decides what the reference does with it
-    *out_n = h_status[4];
+    *out_n = rep.counts[4];
     *used = true;
-    if (h_box->n_finite > 0 && *out_n > 0) {  // (remembered for mrgfe_reg_set_source_from_prefilter; filter_chain says whether d_work is the caller's buffer)
-        for (int a = 0; a < 3; ++a) { ctx->pf_out_box[a] = h_box->mn[a]; ctx->pf_out_box[3 + a] = h_box->mx[a]; }
+    // remembered for mrgfe_reg_set_source_from_prefilter (filter_chain says whether d_work is the caller's buffer): behind an outlier filter the box of its
+    // input, which encloses what it keeps; else the output's own box, which must not leave a non-finite point out
+    const bool boxed = rep.box.n_finite > 0 && *out_n > 0 && (ch.outlier != 0 || rep.box.n_finite == *out_n);
+    if (boxed) {
+        for (int a = 0; a < 3; ++a) { ctx->pf_out_box[a] = rep.box.mn[a]; ctx->pf_out_box[3 + a] = rep.box.mx[a]; }
         ctx->pf_out_ptr = d_work;
         ctx->pf_out_n = *out_n;
         ctx->pf_out_valid = true;
     }
     return MRGFE_OK;  // the result is in d_work
+}
+
+// The downsample stage alone behind a caller's own head kernel (the odometry frame): VoxelGrid (method 1) or ApproximateVoxelGrid (2) of the n points at
+// d_in into d_out (capacity n), one wait.  `d_tile_boxes`: one box per 2048-point tile of d_in as the caller's head left them, or NULL (a pass over d_in
+// makes them).  rep->route: 0 the switch is off, 1 served (rep->kept points, their exact box and finite count), 2 an anomaly (rep->anomaly: no finite
+// point, PCL's "leaf size too small" pass-through, no voxel) — on 0 and 2 the caller runs filter_[approx_]voxelgrid_device.  Leaves the chain's
+// statistics and remembered output (mrgfe_ctx_prefilter_stats, mrgfe_reg_set_source_from_prefilter) alone: those describe chain calls.
+int downsample_device_driven(mrgfe_ctx* ctx, int method, const float4* d_in, size_t n, const BBox* d_tile_boxes, float leaf, int min_pts, float4* d_out, DownsampleReport* rep)
+{
+    std::memset(rep, 0, sizeof(*rep));
+    if (!prefilter_device_driven_mode() || n == 0 || n > 0x7fffffffu || !(leaf > 0) || (method != 1 && method != 2)) return MRGFE_OK;
+    PrefilterChain ch;
+    ch.distance = false;
+    ch.voxelgrid = method == 1;
+    ch.approx_voxelgrid = method == 2;
+    ch.leaf = leaf;
+    ch.min_pts = min_pts;
+    ch.outlier = 0;
+    PfReport pr;
+    MRGFE_TRY(pf_run_stages(ctx, ch, nullptr, nullptr, const_cast<float4*>(d_in), static_cast<uint32_t>(n), d_out, nullptr, d_tile_boxes, &pr));
+    rep->anomaly = pr.anomaly;
+    rep->route = pr.anomaly ? 2 : 1;
+    rep->n_finite_in = pr.counts[1];
+    if (pr.anomaly) return MRGFE_OK;
+    rep->kept = pr.counts[4];
+    rep->kept_finite = pr.box.n_finite;
+    for (int a = 0; a < 3; ++a) { rep->box[a] = pr.box.mn[a]; rep->box[3 + a] = pr.box.mx[a]; }
+    return MRGFE_OK;
 }
 
 // Where the chain's packed input comes from — the only difference between the two entry families: a host cloud in one of the C ABI's layouts

@@ -47,6 +47,9 @@ struct mrgfe_odom {
     size_t            last_n = 0;
     float             last_box[6] = {0, 0, 0, 0, 0, 0};
     uint32_t          last_n_finite = 0xffffffffu;
+    // mrgfe_odom_stats: the downsample route and anomaly word of the last completed frame, its points in and handed on, whether the source grid got a box,
+    // frames whose downsample was served device-driven
+    int64_t           stats[6] = {0, 0, 0, 0, 0, 0};
 };
 struct mrgfe_dbg_odom_ctl { OdomController c; };
 
@@ -110,8 +113,10 @@ int odom_frame_impl(const char* fn, mrgfe_odom* o, const FrameInput& in, double 
     const size_t n = in.n;
     const bool   downsample = o->p.downsample_method != 0;
     const bool   first = !o->ctl.has_keyframe();
-    // the head kernel's box serves the source grid of the engines that compute k-NN covariances (GicpEngine::compute_covariances); NDT and ICP_HIP build none
-    const bool   wants_box = !first && !downsample && reg->gicp && keeps_covariances(reg->params);
+    // a box serves the source grid of the engines that compute k-NN covariances (GicpEngine::compute_covariances); NDT and ICP_HIP build none.  Without a
+    // downsample it is the head kernel's (wants_box: read at a wait of its own), with one the device-driven downsample stage reports the kept points'
+    const bool   takes_box = !first && reg->gicp && keeps_covariances(reg->params);
+    const bool   wants_box = takes_box && !downsample;
 
     // ---- 1. the frame's cloud into the spare buffer (nothing of the registration is touched yet) ----
     MRGFE_TRY(o->spare.ensure(n * 16));
@@ -143,11 +148,25 @@ int odom_frame_impl(const char* fn, mrgfe_odom* o, const FrameInput& in, double 
             }
         }
     }
-    if (o->p.downsample_method == 1) {
-        MRGFE_TRY(filter_voxelgrid_device(ctx, d_whole, n, o->p.downsample_resolution, o->p.downsample_min_points_per_voxel, d_stage, &m, nullptr));  // (waits)
-    } else if (o->p.downsample_method == 2) {
-        MRGFE_TRY(filter_approx_voxelgrid_device(ctx, d_whole, n, o->p.downsample_resolution, d_stage, &m));  // (waits)
-    } else if (!in.device && wants_box) {
+    DownsampleReport ds;
+    std::memset(&ds, 0, sizeof(ds));
+    if (downsample) {
+        // the prefilter chain's downsample stage directly behind the head kernel, whose per-tile boxes give it the voxel parameters (device form: a pass
+        // over the cloud makes them): ONE wait brings down the kept count, the kept points' exact box, the finite count and the anomaly word
+        MRGFE_TRY(downsample_device_driven(ctx, o->p.downsample_method, d_whole, n, in.device ? nullptr : o->box.as<BBox>(), o->p.downsample_resolution,
+                                           o->p.downsample_min_points_per_voxel, d_stage, &ds));
+        if (ds.route == 1) {
+            m = ds.kept;
+            if (takes_box && m > 0 && ds.kept_finite == m) {  // (a voxel grid's centroids always are; the approximate grid's where its points were)
+                std::memcpy(hint, ds.box, sizeof(hint));
+                box_hint = hint;
+            }
+        }
+    }
+    if (downsample && ds.route != 1) {  // the switch is off, or an anomaly (PCL's pass-through, no finite point, no voxel): the host-driven filter decides
+        if (o->p.downsample_method == 1) MRGFE_TRY(filter_voxelgrid_device(ctx, d_whole, n, o->p.downsample_resolution, o->p.downsample_min_points_per_voxel, d_stage, &m, nullptr));  // (waits)
+        else MRGFE_TRY(filter_approx_voxelgrid_device(ctx, d_whole, n, o->p.downsample_resolution, d_stage, &m));  // (waits)
+    } else if (!downsample && !in.device && wants_box) {
         MRGFE_HIP_CHECK(hipStreamSynchronize(st));  // the frame's first wait: the box is on the host
     }
     // (otherwise the box is not needed before the call's next wait — the downsample's, the alignment's or the first frame's — and is read behind it)
@@ -260,6 +279,12 @@ int odom_frame_impl(const char* fn, mrgfe_odom* o, const FrameInput& in, double 
     o->last_n = m;
     std::memcpy(o->last_box, head_box, sizeof(o->last_box));
     o->last_n_finite = head_finite;
+    o->stats[0] = ds.route;
+    o->stats[1] = ds.anomaly;
+    o->stats[2] = static_cast<int64_t>(n);
+    o->stats[3] = static_cast<int64_t>(m);
+    o->stats[4] = (!first && reg->gicp && box_hint) ? 1 : 0;
+    o->stats[5] += ds.route == 1 ? 1 : 0;
     return MRGFE_OK;
 }
 
@@ -316,6 +341,14 @@ int mrgfe_odom_reset(mrgfe_odom* o)
     if (!o) { set_error("mrgfe_odom_reset: NULL argument"); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(o->ctx);
     o->ctl.reset();
+    return MRGFE_OK;
+}
+
+int mrgfe_odom_stats(const mrgfe_odom* o, int64_t out[6])
+{
+    if (!o || !out) { set_error("mrgfe_odom_stats: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(o->ctx);
+    std::memcpy(out, o->stats, sizeof(o->stats));
     return MRGFE_OK;
 }
 

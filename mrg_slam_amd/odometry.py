@@ -219,6 +219,18 @@ class HipOdometry:
 
         _lib.check(_lib.lib().mrgfe_odom_reset(self._handle()))
 
+    def stats(self) -> dict:
+        """What the last completed frame's downsample did (``mrgfe_odom_stats``, no GPU work): ``route`` 0 none or host-driven, 1 device-driven (one wait),
+        2 device-driven attempted and handed back; ``anomaly`` the stage's word (``_lib.PF_ANOMALY_*``); ``points_in``; ``points_out`` handed to the
+        registration; ``boxed`` the source grid was built in a box the frame handed over; ``served`` frames served device-driven so far."""
+        import ctypes as C
+
+        from . import _lib
+
+        v = (C.c_int64 * 6)()
+        _lib.check(_lib.lib().mrgfe_odom_stats(self._handle(), v))
+        return {"route": int(v[0]), "anomaly": int(v[1]), "points_in": int(v[2]), "points_out": int(v[3]), "boxed": bool(v[4]), "served": int(v[5])}
+
     def state(self):
         """The controller's state (``_lib.OdomState``: keyframe pose and stamp, prev_trans, the rejection counter)."""
         import ctypes as C
