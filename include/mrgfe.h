@@ -171,6 +171,12 @@ int mrgfe_ctx_knn_stats(mrgfe_ctx* ctx, double out[5]);
  * out[2] without a downsample —, points after the outlier filter, out[5] again without one; routes 1 and 2); out[7] = points out; out[8] = chain calls
  * on this context so far; out[9] = calls served device-driven so far. */
 int mrgfe_ctx_prefilter_stats(mrgfe_ctx* ctx, double out[10]);
+/* The record stage of the last mrgfe_scan_callback_records / mrgfe_prefilter_records / mrgfe_cloud_records_device on this context (no device is touched):
+ * out[0] = 1 the record kernel wrote into the caller's page-locked buffer, 0 into the context's pinned buffer; out[1] = launches of the record stage (route 2:
+ * the one that found the anomaly word set and wrote nothing, and the one behind the host-driven passes); out[2] = stream waits the call made in addition to
+ * the chain's own (0 on route 1; mrgfe_cloud_records_device: its one); out[3] = record bytes that reached the host; out[4] = bytes of them copied by the
+ * host (0 when direct); out[5] = such calls on this context so far.  mrgfe_ctx_prefilter_stats keeps reporting the chain itself. */
+int mrgfe_ctx_egress_stats(mrgfe_ctx* ctx, int64_t out[6]);
 
 /* ---- cloud ingest --------------------------------------------------------------------------------- */
 /* replaces pcl::fromROSMsg(*cloud_msg, *cloud) (apps/prefiltering_component.cpp:119-120, scan_matching_odometry_component.cpp:144-145):
@@ -320,6 +326,11 @@ int  mrgfe_prefilter(mrgfe_ctx* ctx, const mrgfe_prefilter_params* params, const
 /* the same with the result left in device memory (packed float4, capacity >= n points) for mrgfe_reg_set_source_device /
  * mrgfe_batch_add_*_device: the filtered scan goes from the prefiltering callback to the scan matcher without leaving HBM */
 int  mrgfe_prefilter_device(mrgfe_ctx* ctx, const mrgfe_prefilter_params* params, const float* xyzi, size_t n, size_t stride_bytes, void* d_out_xyzi, size_t* out_n);
+/* the same with the result as the records of the message the component publishes (point_step 32 or 16, capacity_bytes >= n * point_step) and, with
+ * d_out_xyzi non-NULL, left in device memory as mrgfe_prefilter_device leaves it: see mrgfe_scan_callback_records below for the records, the destination
+ * and the refusals — the points, their order, their bits and *out_n are mrgfe_prefilter's */
+int  mrgfe_prefilter_records(mrgfe_ctx* ctx, const mrgfe_prefilter_params* params, const float* xyzi, size_t n, size_t stride_bytes, int point_step, void* records,
+                             size_t capacity_bytes, void* d_out_xyzi, size_t* out_n);
 
 /* ---- the scan callback in one call (PrefilteringComponent::cloud_callback, apps/prefiltering_component.cpp:116-156) --- */
 /* pcl::fromROSMsg (:119-120) -> deskewing (:125, :231-295) -> pcl_ros::transformPointCloud into base_link_frame (:141-146) -> distance_filter ->
@@ -353,6 +364,33 @@ int    mrgfe_scan_callback(mrgfe_ctx* ctx, const mrgfe_scan_params* params, cons
 /* the same with the filtered scan left in device memory (packed float4, room for width * height points): what mrgfe_prefilter_device leaves,
  * mrgfe_reg_set_source_from_prefilter(reg, d_out_xyzi, *out_n) included */
 int    mrgfe_scan_callback_device(mrgfe_ctx* ctx, const mrgfe_scan_params* params, const uint8_t* data, void* d_out_xyzi, size_t* out_n);
+/* The callback to its end: pcl::toROSMsg(*filtered, filtered_ros) (apps/prefiltering_component.cpp:152-155).  The filtered scan comes down as the `data` of
+ * the message the component publishes, written on the device:
+ *   point_step 32: x, y, z, 1.0f, intensity, 0, 0, 0 — the pcl::PointXYZI in memory, which toROSMsg copies as it is (fields x@0 y@4 z@8 intensity@16);
+ *   point_step 16: x, y, z, intensity (intensity@12)
+ * the two layouts of mrgfe_map_store_publish, and as there the message's other members are the caller's (width = *out_n, height 1, row_step = *out_n *
+ * point_step, is_dense false, little endian, FLOAT32 fields).  The points, their order, their bits (a NaN's payload included) and *out_n are those of
+ * mrgfe_scan_callback for the same inputs; every refusal of that call is kept, and an empty message is MRGFE_OK with *out_n = 0 and no byte written.
+ * records: room for capacity_bytes >= width * height * point_step (the "room for width * height points" of out_xyzi); only its first *out_n * point_step bytes
+ * are ever written.  MRGFE_ERR_INVALID before anything is launched, `records` untouched: a NULL ctx / params / records / out_n (data: of a message that is
+ * not empty), a point_step other than 16 or 32, a capacity_bytes below that.
+ * d_out_xyzi non-NULL (device memory, room for width * height packed points): the packed scan is left there as well, exactly as mrgfe_scan_callback_device
+ * leaves it, mrgfe_reg_set_source_from_prefilter(reg, d_out_xyzi, *out_n) included — the prefiltering and odometry components of one container get the message
+ * and the device cloud from one call.  NULL: an internal buffer, nothing is remembered.
+ * On the chains that wait once (mrgfe_ctx_prefilter_stats route 1) the record kernel runs behind the last stage from the count the device holds, in front of
+ * that one wait: the call has no other.  If `records` starts at a multiple of 16 bytes and both ends of [records, records + capacity_bytes) lie in
+ * page-locked host memory (mrgfe_pin_host_buffer, hipHostMalloc, hipHostRegister), the kernel writes the caller's buffer itself; otherwise it writes a pinned
+ * buffer of the context and the host copies *out_n * point_step bytes out behind the wait.  A route-1 VOXELGRID -> STATISTICAL chain always takes the
+ * second way (the host re-checks that chain's threshold behind the wait and may still hand the call back: the caller's buffer must not have been written
+ * beyond the final *out_n by then).  On routes 0 and 2 the host-driven passes make the cloud and mrgfe_cloud_records_device's kernel follows with the host's
+ * count, behind one more wait.  mrgfe_ctx_egress_stats says what a call did. */
+int    mrgfe_scan_callback_records(mrgfe_ctx* ctx, const mrgfe_scan_params* params, const uint8_t* data, int point_step, void* records, size_t capacity_bytes,
+                                   void* d_out_xyzi, size_t* out_n);
+/* The n packed 16-byte points at d_xyzi (device memory of the context's GPU: what mrgfe_scan_callback_device, mrgfe_prefilter_device, mrgfe_floor_detect_device's
+ * caller or a keyframe callback's caller hold) as the same records: one launch, one wait, the same destination rule; capacity_bytes >= n * point_step.
+ * MRGFE_ERR_INVALID, nothing read or written: a NULL argument, another point_step, too little capacity, a d_xyzi that is not device memory of the context's
+ * GPU (as mrgfe_keyframe_callback_device refuses it).  n = 0 is MRGFE_OK. */
+int    mrgfe_cloud_records_device(mrgfe_ctx* ctx, const void* d_xyzi, size_t n, int point_step, void* records, size_t capacity_bytes);
 
 /* replaces PrefilteringComponent::distance_filter (:206-229): keep iff near < |p| < far */
 int mrgfe_distance_filter(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride_bytes, double near_thresh, double far_thresh,

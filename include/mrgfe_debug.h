@@ -81,6 +81,10 @@ int mrgfe_dbg_set_prefilter_device_driven(int mode);
  * (min xyz, max xyz) when a device-driven chain's output stayed in the caller's device buffer and its box is known to enclose finite points only, else 0
  * (n, box may be NULL; box is written only when remembered). */
 int mrgfe_dbg_prefilter_output(mrgfe_ctx* ctx, int* remembered, size_t* n, float box[6]);
+/* A context with no device behind it: the record alone, made without a HIP call, so that a machine without a GPU can hold the checks an entry point makes
+ * before it touches the device, and the statistics calls, against a real handle.  Every call that reaches the device fails on it with MRGFE_ERR_HIP;
+ * mrgfe_ctx_destroy frees it. */
+int mrgfe_dbg_ctx_create_detached(mrgfe_ctx** out);
 /* StatisticalOutlierRemoval's threshold from the mean distances dist[n] and the flags valid[n] (1: all mean_k neighbours were found): out[0] = sum of
  * dist, out[1] = sum of float(dist * dist), out[2] = sum of valid, out[3] = mean + stddev_mul * sqrt(variance) as the reference computes it, out[4] = 1
  * iff both sums are certified to have the same bits in every order of addition (csrc/sor_threshold.h: the sum is below 2^(q + 52) for 2^q the lowest

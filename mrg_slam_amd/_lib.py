@@ -305,6 +305,10 @@ SIGNATURES = {
     "mrgfe_scan_params_size": (C.c_size_t, []),
     "mrgfe_scan_callback": (C.c_int, [_vp, C.POINTER(ScanParams), C.POINTER(C.c_uint8), _fp, C.POINTER(C.c_size_t)]),
     "mrgfe_scan_callback_device": (C.c_int, [_vp, C.POINTER(ScanParams), C.POINTER(C.c_uint8), _vp, C.POINTER(C.c_size_t)]),
+    "mrgfe_scan_callback_records": (C.c_int, [_vp, C.POINTER(ScanParams), C.POINTER(C.c_uint8), C.c_int, _vp, C.c_size_t, _vp, C.POINTER(C.c_size_t)]),
+    "mrgfe_prefilter_records": (C.c_int, [_vp, C.POINTER(PrefilterParams), _fp, C.c_size_t, C.c_size_t, C.c_int, _vp, C.c_size_t, _vp, C.POINTER(C.c_size_t)]),
+    "mrgfe_cloud_records_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t]),
+    "mrgfe_ctx_egress_stats": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mrgfe_floor_default_params": (None, [C.POINTER(FloorParams)]),
     "mrgfe_floor_detect": (C.c_int, [_vp, C.POINTER(FloorParams), _fp, C.c_size_t, C.c_size_t, C.POINTER(FloorResult), _fp, _fp]),
     "mrgfe_floor_detect_device": (C.c_int, [_vp, C.POINTER(FloorParams), _vp, C.c_size_t, C.POINTER(FloorResult), _fp, _fp]),
@@ -433,6 +437,7 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_set_fit_sweep": (C.c_int, [C.c_int]),
     "mrgfe_dbg_set_prefilter_device_driven": (C.c_int, [C.c_int]),
     "mrgfe_dbg_prefilter_output": (C.c_int, [_vp, _ip, _szp, _fp]),
+    "mrgfe_dbg_ctx_create_detached": (C.c_int, [C.POINTER(_vp)]),
     "mrgfe_dbg_sor_threshold": (C.c_int, [_vp, _fp, _u32p, C.c_size_t, C.c_double, C.c_int, _dp]),
     "mrgfe_dbg_floor_ransac": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(C.c_int), _fp, _ip, _szp, _ip, _ip]),
     "mrgfe_dbg_floor_normals": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, C.c_double, _fp, C.POINTER(C.c_uint8)]),
@@ -594,6 +599,14 @@ class Context:
         v = (C.c_double * 10)()
         check(lib().mrgfe_ctx_prefilter_stats(self._h, v))
         return {"route": int(v[0]), "anomaly": int(v[1]), "counts": [int(x) for x in v[2:7]], "points_out": int(v[7]), "calls": int(v[8]), "served": int(v[9])}
+
+    def egress_stats(self) -> dict:
+        """The record stage of the last ``scan_callback_records`` / ``prefilter_records`` / ``cloud_records_from_device`` on this context
+        (``mrgfe_ctx_egress_stats``): ``direct`` the kernel wrote the caller's page-locked buffer, ``launches`` of the record stage, ``waits`` beyond the
+        chain's own (0 on the one-wait route), ``bytes`` of records that reached the host, ``copied`` of them by the host, ``calls`` so far."""
+        v = (C.c_int64 * 6)()
+        check(lib().mrgfe_ctx_egress_stats(self._h, v))
+        return {"direct": bool(v[0]), "launches": int(v[1]), "waits": int(v[2]), "bytes": int(v[3]), "copied": int(v[4]), "calls": int(v[5])}
 
     def close(self):
         if getattr(self, "_h", None):

@@ -621,7 +621,8 @@ void mrgfe_prefilter_default_params(mrgfe_prefilter_params* p)
     p->statistical_mean_k = 30;
     p->statistical_stddev = 1.2;
 }
-static int prefilter_impl(mrgfe_ctx* ctx, const mrgfe_prefilter_params* p, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool on_device);
+static int prefilter_impl(mrgfe_ctx* ctx, const mrgfe_prefilter_params* p, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool on_device,
+                          const RecordSink* rec = nullptr);
 int mrgfe_prefilter(mrgfe_ctx* ctx, const mrgfe_prefilter_params* p, const float* xyzi, size_t n, size_t stride, float* out, size_t* out_n)
 {
     MRGFE_TRY(check_count(n, "mrgfe_prefilter"));
@@ -653,14 +654,40 @@ static int chain_from_params(const char* fn, const mrgfe_prefilter_params* p, Pr
     *out = ch;
     return MRGFE_OK;
 }
-static int prefilter_impl(mrgfe_ctx* ctx, const mrgfe_prefilter_params* p, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool on_device)
+static int prefilter_impl(mrgfe_ctx* ctx, const mrgfe_prefilter_params* p, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool on_device, const RecordSink* rec)
 {
-    if (!ctx || !p || !out_n || (n && (!xyzi || !out))) { set_error("mrgfe_prefilter: NULL argument"); return MRGFE_ERR_INVALID; }
+    if (!ctx || !p || !out_n || (n && (!xyzi || (!out && !rec)))) { set_error("mrgfe_prefilter: NULL argument"); return MRGFE_ERR_INVALID; }
     PrefilterChain ch;
     MRGFE_TRY(chain_from_params("mrgfe_prefilter", p, &ch));
     MRGFE_LOCK(ctx);
     MRGFE_TRY(ctx->bind());
-    return filter_chain(ctx, ch, xyzi, n, stride, out, out_n, on_device);
+    return filter_chain(ctx, ch, xyzi, n, stride, out, out_n, on_device, rec);
+}
+// What the record calls refuse before anything of the context is touched (mrgfe_scan_callback_records, mrgfe_prefilter_records,
+// mrgfe_cloud_records_device): a NULL destination, a point_step other than the two of record_store.h, no room for one record per input point
+static int check_record_sink(const char* fn, int point_step, void* records, size_t capacity_bytes, size_t n_in, RecordSink* sink)
+{
+    if (!records) { set_error("%s: NULL records", fn); return MRGFE_ERR_INVALID; }
+    if (point_step != 16 && point_step != 32) { set_error("%s: point_step %d (16: x y z intensity, 32: pcl::PointXYZI)", fn, point_step); return MRGFE_ERR_INVALID; }
+    if (capacity_bytes / size_t(point_step) < n_in) {
+        set_error("%s: capacity_bytes %zu, %zu input points of %d bytes need room", fn, capacity_bytes, n_in, point_step);
+        return MRGFE_ERR_INVALID;
+    }
+    sink->point_step = point_step;
+    sink->records = records;
+    sink->capacity = capacity_bytes;
+    return MRGFE_OK;
+}
+int mrgfe_prefilter_records(mrgfe_ctx* ctx, const mrgfe_prefilter_params* p, const float* xyzi, size_t n, size_t stride, int point_step, void* records, size_t capacity_bytes,
+                            void* d_out_xyzi, size_t* out_n)
+{
+    static const char* fn = "mrgfe_prefilter_records";
+    return abi_guard(fn, [&]() -> int {
+        MRGFE_TRY(check_count(n, fn));
+        RecordSink sink;
+        MRGFE_TRY(check_record_sink(fn, point_step, records, capacity_bytes, n, &sink));
+        return prefilter_impl(ctx, p, xyzi, n, stride, d_out_xyzi, out_n, d_out_xyzi != nullptr, &sink);
+    });
 }
 
 // ---- the scan callback: PointCloud2 bytes -> filtered scan (PrefilteringComponent::cloud_callback :116-156 in one call) -----------------------------
@@ -677,15 +704,20 @@ void mrgfe_scan_default_params(mrgfe_scan_params* p)
     p->T[0] = p->T[5] = p->T[10] = p->T[15] = 1.0f;
     mrgfe_prefilter_default_params(&p->filters);
 }
-static int scan_callback_impl(const char* fn, mrgfe_ctx* ctx, const mrgfe_scan_params* p, const uint8_t* data, void* out, size_t* out_n, bool on_device)
+// rec_step != 0: the record form — `records` / `capacity_bytes` are checked (check_record_sink) and `out` is the caller's device buffer or NULL
+static int scan_callback_impl(const char* fn, mrgfe_ctx* ctx, const mrgfe_scan_params* p, const uint8_t* data, void* out, size_t* out_n, bool on_device, bool as_records = false,
+                              int rec_step = 0, void* records = nullptr, size_t capacity_bytes = 0)
 {
     return abi_guard(fn, [&]() -> int {
         if (!ctx || !p || !out_n) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
         *out_n = 0;
+        RecordSink sink;
+        if (as_records) MRGFE_TRY(check_record_sink(fn, rec_step, records, capacity_bytes, size_t(p->width) * p->height, &sink));
+        const RecordSink* rec = as_records ? &sink : nullptr;
         PrefilterChain ch;
         MRGFE_TRY(chain_from_params(fn, &p->filters, &ch));
         if (size_t(p->width) * p->height == 0) return MRGFE_OK;  // where the reference returns early (:121-123)
-        if (!data || !out) { set_error("%s: NULL data / output", fn); return MRGFE_ERR_INVALID; }
+        if (!data || (!out && !rec)) { set_error("%s: NULL data / output", fn); return MRGFE_ERR_INVALID; }
         ScanHead h;
         h.data = data;
         h.width = p->width; h.height = p->height; h.point_step = p->point_step; h.row_step = p->row_step;
@@ -700,7 +732,7 @@ static int scan_callback_impl(const char* fn, mrgfe_ctx* ctx, const mrgfe_scan_p
         std::memcpy(h.T, Tr, sizeof(h.T));
         MRGFE_LOCK(ctx);
         MRGFE_TRY(ctx->bind());
-        return scan_chain(ctx, ch, h, out, out_n, on_device);
+        return scan_chain(ctx, ch, h, out, out_n, on_device, rec);
     });
 }
 int mrgfe_scan_callback(mrgfe_ctx* ctx, const mrgfe_scan_params* p, const uint8_t* data, float* out_xyzi, size_t* out_n)
@@ -710,6 +742,10 @@ int mrgfe_scan_callback(mrgfe_ctx* ctx, const mrgfe_scan_params* p, const uint8_
 int mrgfe_scan_callback_device(mrgfe_ctx* ctx, const mrgfe_scan_params* p, const uint8_t* data, void* d_out_xyzi, size_t* out_n)
 {
     return scan_callback_impl("mrgfe_scan_callback_device", ctx, p, data, d_out_xyzi, out_n, true);
+}
+int mrgfe_scan_callback_records(mrgfe_ctx* ctx, const mrgfe_scan_params* p, const uint8_t* data, int point_step, void* records, size_t capacity_bytes, void* d_out_xyzi, size_t* out_n)
+{
+    return scan_callback_impl("mrgfe_scan_callback_records", ctx, p, data, d_out_xyzi, out_n, d_out_xyzi != nullptr, true, point_step, records, capacity_bytes);
 }
 int mrgfe_calc_fitness_score(mrgfe_ctx* ctx, const float* cloud1, size_t n1, const float* cloud2, size_t n2, size_t stride, const double relpose[16], double max_range, double* out)
 {
@@ -1208,6 +1244,21 @@ static int check_device_cloud(const mrgfe_ctx* ctx, const char* fn, const void* 
         }
     }
     return MRGFE_OK;
+}
+int mrgfe_cloud_records_device(mrgfe_ctx* ctx, const void* d_xyzi, size_t n, int point_step, void* records, size_t capacity_bytes)
+{
+    static const char* fn = "mrgfe_cloud_records_device";
+    return abi_guard(fn, [&]() -> int {
+        MRGFE_TRY(check_count(n, fn));
+        if (!ctx || (n && !d_xyzi)) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        RecordSink sink;
+        MRGFE_TRY(check_record_sink(fn, point_step, records, capacity_bytes, n, &sink));
+        if (n == 0) return MRGFE_OK;  // (nothing to ask of the device, as for an empty message)
+        MRGFE_LOCK(ctx);
+        MRGFE_TRY(ctx->bind());
+        MRGFE_TRY(check_device_cloud(ctx, fn, d_xyzi, n));
+        return cloud_records_device(ctx, static_cast<const float4*>(d_xyzi), n, sink);
+    });
 }
 int mrgfe_keyframe_callback_device(mrgfe_map_store* s, uint64_t key, const void* d_xyzi, size_t n, const float* centres, int n_centres, float radius_sqr, float* kept,
                                    size_t* n_kept, float* removed, size_t* n_removed)

@@ -606,6 +606,24 @@ int mrgfe_ctx_prefilter_stats(mrgfe_ctx* ctx, double out[10])
     return MRGFE_OK;
 }
 
+int mrgfe_ctx_egress_stats(mrgfe_ctx* ctx, int64_t out[6])
+{
+    if (!ctx || !out) { mrgfe::set_error("mrgfe_ctx_egress_stats: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(ctx);
+    const mrgfe::ScanEgressStats& e = ctx->eg_stats;
+    out[0] = e.direct; out[1] = e.launches; out[2] = e.waits; out[3] = e.bytes; out[4] = e.copied; out[5] = e.calls;
+    return MRGFE_OK;
+}
+
+// mrgfe_dbg_ctx_create_detached (include/mrgfe_debug.h): the record of a context with no device behind it — no HIP call is made here
+int mrgfe_dbg_ctx_create_detached(mrgfe_ctx** out)
+{
+    if (!out) { mrgfe::set_error("mrgfe_dbg_ctx_create_detached: out is NULL"); return MRGFE_ERR_INVALID; }
+    *out = new (std::nothrow) mrgfe_ctx();
+    if (!*out) { mrgfe::set_error("mrgfe_dbg_ctx_create_detached: out of host memory"); return MRGFE_ERR_INVALID; }
+    return MRGFE_OK;
+}
+
 int mrgfe_ctx_fitness_stats(mrgfe_ctx* ctx, double out[11])
 {
     if (!ctx || !out) { mrgfe::set_error("mrgfe_ctx_fitness_stats: NULL argument"); return MRGFE_ERR_INVALID; }

@@ -224,6 +224,15 @@ struct PrefilterStats {
     uint32_t counts[5] = {0, 0, 0, 0, 0};  // its five stage counts
     uint64_t out_n = 0, calls = 0, served = 0;
 };
+// the record stage of the last scan-egress call on a context and the calls so far (mrgfe_ctx_egress_stats)
+struct ScanEgressStats {
+    int64_t direct = 0;    // 1: the record kernel wrote into the caller's page-locked buffer, 0: into the context's pinned buffer
+    int64_t launches = 0;  // launches of the record stage
+    int64_t waits = 0;     // stream waits the call made in addition to the chain's own
+    int64_t bytes = 0;     // record bytes that reached the host
+    int64_t copied = 0;    // ... of them copied by the host (0 when direct)
+    int64_t calls = 0;
+};
 }  // namespace mrgfe
 
 struct mrgfe_ctx {
@@ -272,6 +281,8 @@ struct mrgfe_ctx {
     float        pf_out_box[6] = {0, 0, 0, 0, 0, 0};  // min xyz, max xyz
     bool         pf_out_valid = false;
     mrgfe::PrefilterStats pf_stats;
+    mrgfe::PinBuf rec_pin;                      // scan egress (filters.hip): the records of a call whose destination is not page-locked, copied out behind the wait
+    mrgfe::ScanEgressStats eg_stats;
     int          cu_count = 256;
     mrgfe::DevBuf fl_buf[11];                   // floor detection (floor.hip): clouds, flags, k-NN lists, RANSAC state / hypotheses / counts
     mrgfe::PinBuf fl_pin;                       // ... and the hypothesis records and counts the host reads after each RANSAC wave

@@ -48,8 +48,21 @@ struct DownsampleReport {
 int downsample_device_driven(mrgfe_ctx* ctx, int method, const float4* d_in, size_t n, const BBox* d_tile_boxes, float leaf, int min_pts, float4* d_out, DownsampleReport* rep);
 // mrgfe_dbg_sor_threshold (include/mrgfe_debug.h): the statistical filter's sums, threshold and certificate, host loop or the chain's kernels
 int sor_threshold_debug(mrgfe_ctx* ctx, const float* dist, const uint32_t* valid, size_t n, double stddev_mul, int on_device, double out[6]);
-// the three passes back to back on the device (one upload, one download)
-int filter_chain(mrgfe_ctx* ctx, const PrefilterChain& chain, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool out_on_device = false);
+// Where a call's records go (mrgfe_scan_callback_records, mrgfe_prefilter_records, mrgfe_cloud_records_device).  The entry point has checked point_step
+// (16 or 32: record_store.h) and that `capacity` holds one record per INPUT point; the chain decides the rest: a range whose two ends lie in page-locked
+// host memory (upload_cloud's test) and that starts at a multiple of 16 bytes is written by the record kernel itself, anything else through the context's
+// pinned buffer and one memcpy of the kept records behind the wait.
+struct RecordSink {
+    int    point_step = 32;
+    void*  records = nullptr;
+    size_t capacity = 0;
+};
+// the three passes back to back on the device (one upload, one download).  `rec`: the result goes to the host as records instead of packed points —
+// `out` is then device memory for n points (out_on_device) or NULL (an internal buffer; nothing is remembered for mrgfe_reg_set_source_from_prefilter)
+int filter_chain(mrgfe_ctx* ctx, const PrefilterChain& chain, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool out_on_device = false,
+                 const RecordSink* rec = nullptr);
+// the n packed points at d_xyzi (device memory of the context's GPU) as records: one launch, one wait
+int cloud_records_device(mrgfe_ctx* ctx, const float4* d_xyzi, size_t n, const RecordSink& rec);
 
 // What PrefilteringComponent::cloud_callback does to a scan BEFORE its filters (apps/prefiltering_component.cpp:119-146), as the scan head kernel's work
 // order: read the x / y / z / intensity fields out of the wire records of a sensor_msgs/PointCloud2 (validated: ingest.h check_pointcloud2_layout),
@@ -67,7 +80,7 @@ struct ScanHead {
 // the same chain fed by the wire records of a scan: they go up once, and the scan head kernel writes the chain's packed input (and, in front of the
 // device-driven chain, the distance filter's flags and tile counts with it) — same output as mrgfe_ingest_pointcloud2 -> mrgfe_deskew ->
 // mrgfe_transform_cloud -> filter_chain, bit for bit
-int scan_chain(mrgfe_ctx* ctx, const PrefilterChain& chain, const ScanHead& head, void* out, size_t* out_n, bool out_on_device);
+int scan_chain(mrgfe_ctx* ctx, const PrefilterChain& chain, const ScanHead& head, void* out, size_t* out_n, bool out_on_device, const RecordSink* rec = nullptr);
 
 int filter_distance(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, double near_t, double far_t, float* out, size_t* out_n);
 int filter_voxelgrid(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, float leaf, int min_pts, float* out, size_t* out_n, int* overflow);

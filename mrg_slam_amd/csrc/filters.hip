@@ -18,6 +18,7 @@
 #include "ingest.h"
 #include "ndt_build.h"
 #include "nn_grid.h"
+#include "record_store.h"
 #include "scan_point.h"
 #include "sor_threshold.h"
 
@@ -849,6 +850,26 @@ __global__ __launch_bounds__(256) void pf_finish_kernel(PfState* __restrict__ st
     __threadfence_system();
     h_status[6] = 0x600df00du;
 }
+// ---- the filtered scan as wire records (pcl::toROSMsg(*filtered, filtered_ros), apps/prefiltering_component.cpp:152-155) ------------------------------------
+// Behind the chain's last stage and in front of its one wait: record i of the work buffer for i < counts[4], the count the last stage left in the state.
+// The launch is sized for the input; a chain that reports an anomaly (the host-driven passes will make the cloud) writes nothing.  One 16-byte store per
+// lane at point_step 16, two at 32 (record_store.h): a wavefront writes 1024 / 2048 contiguous bytes, into the caller's page-locked buffer or the
+// context's pinned one.  i < counts[4] <= the input count, and `out` has room for the input count (RecordSink).
+template <int kStep>
+__global__ __launch_bounds__(256) void pf_records_dd_kernel(const float4* __restrict__ in, const PfState* __restrict__ st, float4* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (st->anomaly != 0u || i >= st->counts[4]) return;
+    store_record<kStep>(out, i, in[i], EgressOffsets{});
+}
+// the same with the count known to the host: behind the host-driven passes, and for any packed device cloud (mrgfe_cloud_records_device)
+template <int kStep>
+__global__ __launch_bounds__(256) void cloud_records_kernel(const float4* __restrict__ in, uint32_t n, float4* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    store_record<kStep>(out, i, in[i], EgressOffsets{});
+}
 // ---- StatisticalOutlierRemoval's threshold without a host round trip (sor_threshold.h) --------------------------------------------------------------
 // The reference's two f64 sums are sequential over the points; a dependent chain of n additions on one lane would cost as much as the rest of the chain.
 // They are added in a tree instead — per thread, per wavefront, per tile of 2048 points, over the tiles — together with the minimum lowest-bit exponent
@@ -1038,6 +1059,80 @@ constexpr uint32_t kSorCellsCap = (1u << 24) - 1u;  // 24 key bits: three radix 
 #endif
 static float sor_cell_edge(const PrefilterChain& ch) { return std::max(MRGFE_SOR_CELL_LEAVES * ch.leaf, 0.2f); }
 
+// ---- where a call's records go (RecordSink, filters.h) ----------------------------------------------------------------------------------------------
+// a sink resolved for one call: the record kernel's destination as the device sees it
+struct RecordDest {
+    const RecordSink* sink = nullptr;
+    float4*           d_dst = nullptr;
+    bool              direct = false;  // d_dst is the caller's buffer
+};
+static bool page_locked(const void* p)
+{
+    hipPointerAttribute_t a;
+    return hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost;
+}
+static void egress_begin(mrgfe_ctx* ctx)
+{
+    ScanEgressStats& e = ctx->eg_stats;
+    e.direct = e.launches = e.waits = e.bytes = e.copied = 0;
+    e.calls += 1;
+}
+// n_in: the points the record kernel may write at the most.  allow_direct false: the context's pinned buffer whatever the caller's memory is.
+static int record_dest_open(mrgfe_ctx* ctx, const RecordSink& s, size_t n_in, bool allow_direct, RecordDest* d)
+{
+    d->sink = &s;
+    d->d_dst = nullptr;
+    d->direct = false;
+    char* first = static_cast<char*>(s.records);
+    if (allow_direct && s.capacity && (reinterpret_cast<uintptr_t>(first) & 15u) == 0) {
+        // BOTH ends of the range in page-locked memory, as upload_cloud asks of a cloud it reads in place
+        void* dev = nullptr;
+        if (page_locked(first) && page_locked(first + s.capacity - 1) && hipHostGetDevicePointer(&dev, s.records, 0) == hipSuccess && dev) {
+            d->d_dst = static_cast<float4*>(dev);
+            d->direct = true;
+        }
+        (void)hipGetLastError();  // (an unregistered pointer is an error to the query, not to us)
+    }
+    if (!d->direct) {
+        MRGFE_TRY(ctx->rec_pin.ensure(n_in * size_t(s.point_step)));
+        d->d_dst = ctx->rec_pin.as<float4>();
+    }
+    ctx->eg_stats.direct = d->direct ? 1 : 0;
+    return MRGFE_OK;
+}
+// behind the wait that covers the record kernel: the m records are in the destination; a staged destination is copied out
+static void record_dest_close(mrgfe_ctx* ctx, const RecordDest& d, size_t m)
+{
+    const size_t bytes = m * size_t(d.sink->point_step);
+    if (!d.direct && bytes) {
+        std::memcpy(d.sink->records, ctx->rec_pin.p, bytes);
+        ctx->eg_stats.copied = static_cast<int64_t>(bytes);
+    }
+    ctx->eg_stats.bytes = static_cast<int64_t>(bytes);
+}
+// the m packed points at d_in as records, the count known to the host: one launch, queued
+static int launch_cloud_records(mrgfe_ctx* ctx, const float4* d_in, uint32_t m, const RecordDest& d)
+{
+    if (m == 0) return MRGFE_OK;
+    const auto kern = d.sink->point_step == 16 ? cloud_records_kernel<16> : cloud_records_kernel<32>;
+    hipLaunchKernelGGL(kern, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, d_in, m, d.d_dst);
+    MRGFE_HIP_CHECK(hipGetLastError());
+    ctx->eg_stats.launches += 1;
+    return MRGFE_OK;
+}
+int cloud_records_device(mrgfe_ctx* ctx, const float4* d_xyzi, size_t n, const RecordSink& rec)
+{
+    egress_begin(ctx);
+    if (n == 0) return MRGFE_OK;
+    RecordDest d;
+    MRGFE_TRY(record_dest_open(ctx, rec, n, true, &d));
+    MRGFE_TRY(launch_cloud_records(ctx, d_xyzi, static_cast<uint32_t>(n), d));
+    MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    ctx->eg_stats.waits += 1;
+    record_dest_close(ctx, d, n);
+    return MRGFE_OK;
+}
+
 // ---- the chain as three stages ----------------------------------------------------------------------------------------------------------------------
 // head / distance -> downsample (NONE, VOXELGRID, APPROX_VOXELGRID) -> outlier (NONE, RADIUS, STATISTICAL).  A stage hands the next one its live count
 // (PfState::sl_in, then sl_rad), its cloud (cp[0], then cp[1]) and one box per tile of that cloud (bb_n[0], then bb_n[1] entries) — nothing through the
@@ -1187,9 +1282,10 @@ static int pf_stage_outlier(PfRun& r)
 }
 
 // The three stages and the chain's one wait.  d_work receives the result (capacity n); d_third: a buffer of n points wherever a stage needs one that is
-// neither the input nor the work buffer (an outlier filter, or the distance filter in front of the approximate grid), else unused.
+// neither the input nor the work buffer (an outlier filter, or the distance filter in front of the approximate grid), else unused.  `rec`: the record kernel
+// follows the last stage, in front of the wait.
 static int pf_run_stages(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHead* head, const void* d_raw, float4* d_in, uint32_t n, float4* d_work, float4* d_third,
-                         const BBox* d_head_boxes, PfReport* rep)
+                         const BBox* d_head_boxes, PfReport* rep, const RecordDest* rec = nullptr)
 {
     PfRun r;
     r.ctx = ctx;
@@ -1240,6 +1336,12 @@ static int pf_run_stages(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHea
     MRGFE_TRY(pf_stage_head(r, head, d_raw, d_in, d_head_boxes));
     MRGFE_TRY(pf_stage_downsample(r));
     MRGFE_TRY(pf_stage_outlier(r));
+    if (rec) {
+        const auto kern = rec->sink->point_step == 16 ? pf_records_dd_kernel<16> : pf_records_dd_kernel<32>;
+        hipLaunchKernelGGL(kern, r.g256, dim3(256), 0, ctx->stream, r.d_work, r.d_st, rec->d_dst);
+        MRGFE_HIP_CHECK(hipGetLastError());
+        ctx->eg_stats.launches += 1;
+    }
     MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the chain's one wait
     if (r.h_status[6] != 0x600df00du) { set_error("prefilter: the device-driven chain did not report"); return MRGFE_ERR_HIP; }
     for (int k = 0; k < 5; ++k) rep->counts[k] = r.h_status[k];
@@ -1251,11 +1353,11 @@ static int pf_run_stages(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHea
 // A chain the device-driven form serves (device_driven_applies).  Returns MRGFE_OK with *used = true when it produced the output, *used = false
 // (an anomaly) when the caller has to run the host-driven passes over d_in.
 static int filter_chain_device_driven(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHead* head, const void* d_raw, float4* d_in, uint32_t n, float4* d_work, float4* d_final,
-                                      size_t* out_n, bool* used)
+                                      size_t* out_n, bool* used, const RecordDest* rec)
 {
     *used = false;
     PfReport rep;
-    MRGFE_TRY(pf_run_stages(ctx, ch, head, d_raw, d_in, n, d_work, d_final, nullptr, &rep));
+    MRGFE_TRY(pf_run_stages(ctx, ch, head, d_raw, d_in, n, d_work, d_final, nullptr, &rep, rec));
     PrefilterStats& ps = ctx->pf_stats;
     ps.anomaly = rep.anomaly;
     for (int k = 0; k < 5; ++k) ps.counts[k] = rep.counts[k];
@@ -1317,9 +1419,10 @@ struct ChainInput {
     const ScanHead* head = nullptr;
 };
 
-static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const ChainInput& in, size_t n, void* out, size_t* out_n, bool out_on_device)
+static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const ChainInput& in, size_t n, void* out, size_t* out_n, bool out_on_device, const RecordSink* rec)
 {
     *out_n = 0;
+    if (rec) egress_begin(ctx);
     ctx->pf_out_valid = false;
     PrefilterStats& ps = ctx->pf_stats;  // (mrgfe_ctx_prefilter_stats: which route serves this call)
     ps.route = 0;
@@ -1332,7 +1435,11 @@ static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const Cha
     DevBuf &a = ctx->pf_buf[0], &b = ctx->pf_buf[1];  // ping-pong, kept between calls (grow-only: a hipMalloc / hipFree pair per scan is a device-wide wait)
     const void* d_raw = nullptr;
     const bool  device_driven = device_driven_applies(ch, static_cast<uint32_t>(n));
-    int rc = a.ensure(n * 16);
+    // The records of a device-driven STATISTICAL chain are staged whatever the caller's memory is: the host re-checks that chain's threshold behind the wait
+    // (kPfAnomalyRecheck) and may hand the call back after the record kernel has run, and a caller's buffer must never hold a record beyond *out_n.
+    RecordDest dest;
+    int rc = rec ? record_dest_open(ctx, *rec, n, !(device_driven && ch.outlier == 2), &dest) : MRGFE_OK;
+    if (rc == MRGFE_OK) rc = a.ensure(n * 16);
     if (rc == MRGFE_OK) rc = b.ensure(n * 16);
     if (rc == MRGFE_OK && !in.head) rc = upload_cloud(ctx, in.xyzi, n, in.stride, a.p);
     if (rc == MRGFE_OK && in.head) rc = upload_raw_records(ctx, in.head->data, size_t(in.head->height - 1) * in.head->row_step + size_t(in.head->width) * in.head->point_step, &d_raw);
@@ -1345,12 +1452,13 @@ static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const Cha
         float4* final_buf = out_on_device ? b.as<float4>() : nullptr;
         DevBuf& c = ctx->scratch[13];
         if (!out_on_device) { rc = c.ensure(n * 16); final_buf = c.as<float4>(); }
-        if (rc == MRGFE_OK) rc = filter_chain_device_driven(ctx, ch, in.head, d_raw, a.as<float4>(), static_cast<uint32_t>(n), work, final_buf, &m, &used);
+        if (rc == MRGFE_OK) rc = filter_chain_device_driven(ctx, ch, in.head, d_raw, a.as<float4>(), static_cast<uint32_t>(n), work, final_buf, &m, &used, rec ? &dest : nullptr);
         if (rc != MRGFE_OK) return rc;
         ps.route = used ? 1 : 2;
         if (used) {
             if (!out_on_device) ctx->pf_out_valid = false;  // (the cloud went to the host: nothing of the caller's stays on the device)
-            if (!out_on_device) rc = download(ctx, work, m, static_cast<float*>(out));
+            if (rec) record_dest_close(ctx, dest, m);  // (the record kernel ran in front of the chain's wait)
+            else if (!out_on_device) rc = download(ctx, work, m, static_cast<float*>(out));
             if (rc == MRGFE_OK) { *out_n = m; ps.out_n = m; ps.served += 1; }
             return rc;
         }
@@ -1368,7 +1476,16 @@ static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const Cha
     else if (ch.voxelgrid) pass([&](const float4* i, size_t ni, float4* o, size_t* k) { int overflow = 0; return filter_voxelgrid_device(ctx, i, ni, ch.leaf, ch.min_pts, o, k, &overflow); });
     if (ch.outlier == 1) pass([&](const float4* i, size_t ni, float4* o, size_t* k) { return filter_radius_outlier_device(ctx, i, ni, ch.radius, ch.radius_min_neighbors, o, k); });
     if (ch.outlier == 2) pass([&](const float4* i, size_t ni, float4* o, size_t* k) { return filter_statistical_outlier_device(ctx, i, ni, ch.mean_k, ch.stddev_mul, o, k); });
-    if (rc == MRGFE_OK) {
+    if (rc == MRGFE_OK && rec) {
+        // the host-driven passes made the cloud: its records with the host's count, the caller's device copy beside them, one more wait
+        rc = launch_cloud_records(ctx, cur, static_cast<uint32_t>(m), dest);
+        if (rc == MRGFE_OK && m && (out_on_device && hipMemcpyAsync(out, cur, m * 16, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)) { set_error("prefilter: device copy failed"); rc = MRGFE_ERR_HIP; }
+        if (rc == MRGFE_OK && m) {
+            if (hipStreamSynchronize(ctx->stream) != hipSuccess) { set_error("prefilter: the record kernel failed"); rc = MRGFE_ERR_HIP; }
+            ctx->eg_stats.waits += 1;
+        }
+        if (rc == MRGFE_OK) record_dest_close(ctx, dest, m);
+    } else if (rc == MRGFE_OK) {
         if (!out_on_device) {
             rc = download(ctx, cur, m, static_cast<float*>(out));
         } else if (m && (hipMemcpyAsync(out, cur, m * 16, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)) {
@@ -1380,18 +1497,18 @@ static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const Cha
     return rc;
 }
 
-int filter_chain(mrgfe_ctx* ctx, const PrefilterChain& ch, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool out_on_device)
+int filter_chain(mrgfe_ctx* ctx, const PrefilterChain& ch, const float* xyzi, size_t n, size_t stride, void* out, size_t* out_n, bool out_on_device, const RecordSink* rec)
 {
     ChainInput in;
     in.xyzi = xyzi;
     in.stride = stride;
-    return filter_chain_from(ctx, ch, in, n, out, out_n, out_on_device);
+    return filter_chain_from(ctx, ch, in, n, out, out_n, out_on_device, rec);
 }
-int scan_chain(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHead& head, void* out, size_t* out_n, bool out_on_device)
+int scan_chain(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHead& head, void* out, size_t* out_n, bool out_on_device, const RecordSink* rec)
 {
     ChainInput in;
     in.head = &head;
-    return filter_chain_from(ctx, ch, in, size_t(head.width) * head.height, out, out_n, out_on_device);
+    return filter_chain_from(ctx, ch, in, size_t(head.width) * head.height, out, out_n, out_on_device, rec);
 }
 
 int filter_distance(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, double near_t, double far_t, float* out, size_t* out_n)

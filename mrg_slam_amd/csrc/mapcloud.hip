@@ -18,6 +18,7 @@
 #include "dev_utils.h"
 #include "filters.h"
 #include "ingest.h"
+#include "record_store.h"
 #include "scan_point.h"
 
 namespace mrgfe {
@@ -261,23 +262,8 @@ int map_cloud_device(mrgfe_ctx* ctx, const float4* d_cat, const uint32_t* kf_off
 // the other (:1106-1115 add zero_utm, then zero_enu, to the filtered cloud), then
 //   point_step 32: x, y, z, 1.0f | intensity, 0, 0, 0   the pcl::PointXYZI in memory, which is what toROSMsg copies (two 16-byte stores)
 //   point_step 16: x, y, z, intensity                   the body of a binary PCD (one 16-byte store)
-// Without offsets no arithmetic touches the point: its bits, a NaN's payload included, are those of the generator.
-struct EgressOffsets { int32_t n; float v[2][3]; };
-template <int kStep>
-__device__ __forceinline__ void store_record(float4* __restrict__ out, size_t at, float4 p, const EgressOffsets& o)
-{
-#pragma clang fp contract(off)
-    for (int k = 0; k < o.n; ++k) {
-        p.x = p.x + o.v[k][0];
-        p.y = p.y + o.v[k][1];
-        p.z = p.z + o.v[k][2];
-    }
-    if (kStep == 16) out[at] = p;
-    else {
-        out[2 * at] = make_float4(p.x, p.y, p.z, 1.0f);
-        out[2 * at + 1] = make_float4(p.w, 0.0f, 0.0f, 0.0f);
-    }
-}
+// Without offsets no arithmetic touches the point: its bits, a NaN's payload included, are those of the generator.  (store_record: record_store.h,
+// shared with the scan egress of filters.hip.)
 // flags / pos: the keep flags and their exclusive scan; both nullptr: every point is kept where it stands
 template <int kStep>
 __global__ __launch_bounds__(256) void egress_records_kernel(const float4* __restrict__ in, const uint32_t* __restrict__ flags, const uint32_t* __restrict__ pos, uint32_t n,

@@ -308,6 +308,63 @@ def scan_callback_to_device(data, width: int, height: int, point_step: int, fiel
     return m.value
 
 
+RECORD_FIELDS = {32: {"x": 0, "y": 4, "z": 8, "intensity": 16}, 16: {"x": 0, "y": 4, "z": 8, "intensity": 12}}  # field offsets of the two record layouts
+
+
+def _records_destination(n: int, record_step: int, out):
+    """The ``uint8`` buffer the records of ``n`` input points go to: the caller's ``out`` (C-contiguous uint8, at least n * record_step bytes — page-locked
+    and 16-byte aligned, the kernel writes it itself) or a fresh array."""
+    if record_step not in RECORD_FIELDS:
+        raise ValueError(f"record point_step {record_step}: 16 or 32")
+    if out is None:
+        return np.empty(max(n, 1) * record_step, dtype=np.uint8)
+    if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.ndim == 1 and out.flags.c_contiguous and out.flags.writeable):
+        raise ValueError("out: a writeable one-dimensional C-contiguous uint8 array")
+    if out.nbytes < n * record_step:
+        raise ValueError(f"records buffer too small: {out.nbytes} bytes, {n} points of {record_step} bytes need room")
+    return out
+
+
+def scan_callback_records(data, width: int, height: int, point_step: int, fields, record_step: int = 32, out=None, dev_ptr: int = 0, row_step: int = 0, ang_v=None,
+                          scan_period: float = 0.1, T=None, params: dict | None = None, ctx: Context | None = None) -> np.ndarray:
+    """:func:`scan_callback` to the end of the callback (``mrgfe_scan_callback_records``): the filtered scan as the ``data`` of the message the component
+    publishes, ``pcl::toROSMsg`` records of ``record_step`` 32 (or packed ones of 16) written on the device — a ``uint8`` array of ``n_points * record_step``
+    bytes, a view of ``out`` when the caller gives its own buffer (room for width * height records).  With ``dev_ptr`` (device memory for width * height
+    packed points) the packed scan is left there too, as :func:`scan_callback_to_device` leaves it."""
+    from .io import pointcloud2_payload
+
+    ctx = ctx or default_context()
+    buf = pointcloud2_payload(data, width, height, point_step, row_step)
+    q, m = _scan_params(width, height, point_step, fields, row_step, ang_v, scan_period, T, params, ctx), C.c_size_t(0)
+    rec = _records_destination(int(width) * int(height), record_step, out)
+    check(lib().mrgfe_scan_callback_records(ctx._h, C.byref(q), buf.ctypes.data_as(C.POINTER(C.c_uint8)), int(record_step), rec.ctypes.data_as(C.c_void_p), rec.nbytes,
+                                            C.c_void_p(dev_ptr) if dev_ptr else None, C.byref(m)))
+    return rec[: m.value * record_step]
+
+
+def prefilter_records(cloud, record_step: int = 32, out=None, dev_ptr: int = 0, params: dict | None = None, ctx: Context | None = None) -> np.ndarray:
+    """:func:`prefilter` with the result as records (``mrgfe_prefilter_records``): see :func:`scan_callback_records`; ``dev_ptr``: device memory for
+    len(cloud) packed points, filled as :func:`prefilter_to_device` fills it."""
+    p = dict(_PREFILTER_DEFAULTS)
+    p.update(params or {})
+    c = _cloud(cloud)
+    ctx = ctx or default_context()
+    q, m = _prefilter_params(p), C.c_size_t(0)
+    rec = _records_destination(len(c), record_step, out)
+    check(lib().mrgfe_prefilter_records(ctx._h, C.byref(q), c.ctypes.data_as(_fp), len(c), 16, int(record_step), rec.ctypes.data_as(C.c_void_p), rec.nbytes,
+                                        C.c_void_p(dev_ptr) if dev_ptr else None, C.byref(m)))
+    return rec[: m.value * record_step]
+
+
+def cloud_records_from_device(dev_ptr: int, n: int, record_step: int = 32, out=None, ctx: Context | None = None) -> np.ndarray:
+    """The ``n`` packed points at ``dev_ptr`` (device memory of the context's GPU: a filtered scan, floor detection's clouds, a keyframe callback's input)
+    as the same records (``mrgfe_cloud_records_device``): one launch, one wait."""
+    ctx = ctx or default_context()
+    rec = _records_destination(int(n), record_step, out)
+    check(lib().mrgfe_cloud_records_device(ctx._h, C.c_void_p(dev_ptr), int(n), int(record_step), rec.ctypes.data_as(C.c_void_p), rec.nbytes))
+    return rec[: int(n) * record_step]
+
+
 def prefilter(cloud, params: dict | None = None, ctx: Context | None = None) -> np.ndarray:
     """The chain of PrefilteringComponent::cloud_callback (:149-151) with the reference's parameter names and YAML
     defaults (config/mrg_slam.yaml:41-64): distance_filter -> downsample -> outlier_removal."""

@@ -42,9 +42,17 @@ class HipOps:
         the result stays on the device and the count is returned."""
         return self.scan_pointcloud2(memoryview(cloud).cast("B"), len(cloud), 1, 16, {"x": 0, "y": 4, "z": 8, "intensity": 12}, 0, ang_v, scan_period, T, p, dev_ptr)
 
-    def scan_pointcloud2(self, data, width, height, point_step, fields, row_step, ang_v, scan_period, T, p, dev_ptr: int = 0):
-        from .filters import scan_callback, scan_callback_to_device
+    def scan_pointcloud2(self, data, width, height, point_step, fields, row_step, ang_v, scan_period, T, p, dev_ptr: int = 0, records: int = 0, records_out=None):
+        """``records`` 32 or 16 (default 0: off): the filtered scan as the message the component publishes (``mrgfe_scan_callback_records``, the
+        ``pcl::toROSMsg`` + publish of :152-155) — a dict with the message's ``data`` (uint8; a view of ``records_out`` when given), ``point_step``, ``fields``
+        (name -> offset), ``width``, ``height`` 1, ``row_step``, ``is_dense`` False, ``is_bigendian`` False; with ``dev_ptr`` the packed scan stays on the
+        device as well."""
+        from .filters import RECORD_FIELDS, scan_callback, scan_callback_records, scan_callback_to_device
 
+        if records:
+            rec = scan_callback_records(data, width, height, point_step, fields, records, records_out, dev_ptr, row_step, ang_v, scan_period, T, p, ctx=self.ctx)
+            return {"height": 1, "width": len(rec) // records, "is_dense": False, "is_bigendian": False, "point_step": records, "row_step": len(rec),
+                    "fields": dict(RECORD_FIELDS[records]), "data": rec}
         if dev_ptr:
             return scan_callback_to_device(data, width, height, point_step, fields, dev_ptr, int(width) * int(height), row_step, ang_v, scan_period, T, p, ctx=self.ctx)
         return scan_callback(data, width, height, point_step, fields, row_step, ang_v, scan_period, T, p, ctx=self.ctx)
@@ -159,15 +167,19 @@ class PrefilteringComponent:
         return self.ops.filters(src, self.p)
 
     def pointcloud2_callback(self, data, width: int, height: int, point_step: int, fields, row_step: int = 0, stamp: float = 0.0, frame_id: str = "",
-                             dev_ptr: int = 0):
+                             dev_ptr: int = 0, records: int = 0, records_out=None):
         """``cloud_callback`` from the wire message (the payload and layout of a sensor_msgs/PointCloud2): pcl::fromROSMsg happens in the same
         GPU call as the rest.  ``fields``: a ``{name: offset}`` dict or the message's field list ``(name, offset, datatype, count)``, as
         ``io.layout_from_fields`` takes them (the list switches the context to byte layouts when the records need it: Velodyne's 22-byte points).  Returns the filtered cloud, or — with ``dev_ptr`` (device memory for width * height packed points) — leaves it
-        there and returns its point count; None where the reference returns early.  Needs point operations with ``scan_pointcloud2`` (HipOps)."""
+        there and returns its point count; None where the reference returns early.  Needs point operations with ``scan_pointcloud2`` (HipOps).
+        ``records`` 32 or 16 (default 0: off): the callback to its publish (:152-155) — returns the filtered message (``HipOps.scan_pointcloud2``: its
+        ``data``, ``point_step`` and ``fields``; ``records_out``: the caller's, ideally page-locked, buffer) and, with ``dev_ptr``, leaves the device cloud too."""
         if int(width) * int(height) == 0:
             return None
         ang_v = self._take_imu(stamp)
         ok, T = self._lookup(frame_id)
         if not ok:
             return None
+        if records:
+            return self.ops.scan_pointcloud2(data, width, height, point_step, fields, row_step, ang_v, self.p["scan_period"], T, self.p, dev_ptr, records, records_out)
         return self.ops.scan_pointcloud2(data, width, height, point_step, fields, row_step, ang_v, self.p["scan_period"], T, self.p, dev_ptr)
