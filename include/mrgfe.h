@@ -145,6 +145,14 @@ int  mrgfe_ctx_set_byte_layouts(mrgfe_ctx* ctx, int on);
  * methods as it always did ("offered for single registrations only").  Contexts made like this one (mrgfe_ctx_create_like) inherit the switch.
  * mrgfe_node_create makes its own contexts and keeps refusing the two methods: nodes of BFGS batches are not offered. */
 int  mrgfe_ctx_set_bfgs_batches(mrgfe_ctx* ctx, int on);
+/* STATISTICAL outlier removal behind downsample NONE or APPROX_VOXELGRID on the device-driven prefilter chain (off by default).  on = 1: from the next
+ * chain call on this context (mrgfe_prefilter[_device | _records], mrgfe_scan_callback[_device | _records]) those chains wait for the device once, as
+ * VOXELGRID -> STATISTICAL does (statistical_mean_k in 1..63): without a voxel leaf to take it from, the cell edge of the filter's k-NN grid is chosen ON THE
+ * DEVICE from the cloud's own density, in a fixed sequence of launches (mrgfe_ctx_sor_grid_stats reports the choice).  The search does not depend on the
+ * edge: the output is that of the host-driven passes bit for bit, and an unusual scan is handed back to them (mrgfe_ctx_prefilter_stats route 2).  Off:
+ * those chains run the host-driven passes (route 0) as they always did.  VOXELGRID -> STATISTICAL is the same either way.  Contexts made like this one
+ * (mrgfe_ctx_create_like) inherit the switch.  NULL ctx: MRGFE_ERR_INVALID. */
+int  mrgfe_ctx_set_statistical_chains(mrgfe_ctx* ctx, int on);
 /* HIP stream of the context as an opaque pointer (hipStream_t), for callers that order their own work after it */
 void* mrgfe_ctx_stream(mrgfe_ctx* ctx);
 /* Measurement hook ("1-NN fitness on hash grid: N (16 + 27*8 + m*16)"): what the last getFitnessScore pass on this context
@@ -162,7 +170,7 @@ int mrgfe_ctx_knn_stats(mrgfe_ctx* ctx, double out[5]);
 /* Which route served the last prefilter chain call on this context (mrgfe_prefilter[_device], mrgfe_scan_callback[_device]):
  * out[0] = route — 0 the host-driven passes (every stage hands its point count to the host), 1 the device-driven chain (one wait; [distance filter] ->
  * NONE, VOXELGRID or APPROX_VOXELGRID -> NONE or RADIUS, and VOXELGRID -> STATISTICAL with statistical_mean_k in 1..63; STATISTICAL behind NONE or
- * APPROX_VOXELGRID stays on route 0), 2 the device-driven chain attempted and handed back to the host-driven passes (same output); out[1] = the
+ * APPROX_VOXELGRID stays on route 0 unless mrgfe_ctx_set_statistical_chains is on), 2 the device-driven chain attempted and handed back to the host-driven passes (same output); out[1] = the
  * device-driven chain's anomaly word (routes 1 and 2): 1 a stage in front of another one left no (finite) point, 2 PCL's "leaf size too small"
  * pass-through, 4 no voxel, 8 a sum of the statistical filter's threshold could have depended on the order of addition, 16 the host's re-check of
  * that threshold differs from the device's, 32 a non-finite point reached the outlier filter (distance filter off and no VOXELGRID in front of it),
@@ -171,6 +179,12 @@ int mrgfe_ctx_knn_stats(mrgfe_ctx* ctx, double out[5]);
  * out[2] without a downsample —, points after the outlier filter, out[5] again without one; routes 1 and 2); out[7] = points out; out[8] = chain calls
  * on this context so far; out[9] = calls served device-driven so far. */
 int mrgfe_ctx_prefilter_stats(mrgfe_ctx* ctx, double out[10]);
+/* The statistical filter's k-NN grid of the last prefilter chain call on this context (no device is touched): out[0] = 1 when that call's statistical
+ * stage sized its grid on the device (mrgfe_ctx_set_statistical_chains on, downsample NONE or APPROX_VOXELGRID, routes 1 and 2), else 0 and the rest 0;
+ * out[1] = the start edge used, in metres (the rule's start edge, doubled until the cloud's box fits the cell table); out[2] = the chosen edge = out[1]
+ * * 2^-out[3]; out[3] = halvings; out[4] = the crowding last measured (population of the cell an average point sits in, at the edge in front of the last
+ * decision; 0: no counting pass measured); out[5] = cells of the built grid. */
+int mrgfe_ctx_sor_grid_stats(mrgfe_ctx* ctx, double out[6]);
 /* The record stage of the last mrgfe_scan_callback_records / mrgfe_prefilter_records / mrgfe_cloud_records_device on this context (no device is touched):
  * out[0] = 1 the record kernel wrote into the caller's page-locked buffer, 0 into the context's pinned buffer; out[1] = launches of the record stage (route 2:
  * the one that found the anomaly word set and wrote nothing, and the one behind the host-driven passes); out[2] = stream waits the call made in addition to
@@ -336,8 +350,8 @@ int  mrgfe_prefilter_records(mrgfe_ctx* ctx, const mrgfe_prefilter_params* param
 /* pcl::fromROSMsg (:119-120) -> deskewing (:125, :231-295) -> pcl_ros::transformPointCloud into base_link_frame (:141-146) -> distance_filter ->
  * downsample -> outlier_removal (:149-151) on the byte payload of a sensor_msgs/PointCloud2.  The payload goes up ONCE as it is; one kernel reads
  * the records, deskews, transforms, stores the packed cloud and (on the usual chains) is the distance filter's first pass; nothing comes down but
- * the chain's status words and, for the host form, the filtered cloud; every chain but STATISTICAL behind NONE or APPROX_VOXELGRID, or with
- * statistical_mean_k outside 1..63, waits for the device once (mrgfe_ctx_prefilter_stats says which route served a call).
+ * the chain's status words and, for the host form, the filtered cloud; every chain but STATISTICAL behind NONE or APPROX_VOXELGRID (unless
+ * mrgfe_ctx_set_statistical_chains is on), or with statistical_mean_k outside 1..63, waits for the device once (mrgfe_ctx_prefilter_stats says which route served a call).
  * The output equals, bit for bit and in order, mrgfe_ingest_pointcloud2 -> mrgfe_deskew (if `deskew`) -> mrgfe_transform_cloud (if `transform`)
  * -> mrgfe_prefilter[_device] for the same inputs.  The reference's quirks are kept: deskewing counts i and n = width * height over the UNFILTERED
  * cloud (:286), non-finite points included; the transform leaves non-finite points as they are; the distance filter is what drops them. */
@@ -380,7 +394,7 @@ int    mrgfe_scan_callback_device(mrgfe_ctx* ctx, const mrgfe_scan_params* param
  * On the chains that wait once (mrgfe_ctx_prefilter_stats route 1) the record kernel runs behind the last stage from the count the device holds, in front of
  * that one wait: the call has no other.  If `records` starts at a multiple of 16 bytes and both ends of [records, records + capacity_bytes) lie in
  * page-locked host memory (mrgfe_pin_host_buffer, hipHostMalloc, hipHostRegister), the kernel writes the caller's buffer itself; otherwise it writes a pinned
- * buffer of the context and the host copies *out_n * point_step bytes out behind the wait.  A route-1 VOXELGRID -> STATISTICAL chain always takes the
+ * buffer of the context and the host copies *out_n * point_step bytes out behind the wait.  A route-1 STATISTICAL chain always takes the
  * second way (the host re-checks that chain's threshold behind the wait and may still hand the call back: the caller's buffer must not have been written
  * beyond the final *out_n by then).  On routes 0 and 2 the host-driven passes make the cloud and mrgfe_cloud_records_device's kernel follows with the host's
  * count, behind one more wait.  mrgfe_ctx_egress_stats says what a call did. */

@@ -77,6 +77,12 @@ int mrgfe_dbg_set_fit_sweep(int mode);
  * the stages' point counts stay on the device and the call waits once at its end, 0 every stage reports its count to the host (round 3; also what an
  * unusual scan falls back to); other values query.  Same outputs either way (mrgfe_ctx_prefilter_stats and mrgfe_odom_stats report the route a call took). */
 int mrgfe_dbg_set_prefilter_device_driven(int mode);
+/* The rule by which the device sizes the statistical filter's k-NN grid behind NONE / APPROX_VOXELGRID (mrgfe_ctx_set_statistical_chains), during the
+ * following chain calls of this process: the start edge in metres, the crowding target (population of the cell an average point sits in) and the most
+ * halvings of the start edge.  All three zero restores the defaults; otherwise a start edge or a target of zero stands for its default and
+ * max_halvings is taken as given (0: the start grid stands).  The filter's output does not depend on the rule, only its time does
+ * (tests/test_gpu_prefilter_statistical_chains.py); mrgfe_ctx_sor_grid_stats reports what a call chose.  Returns MRGFE_OK. */
+int mrgfe_dbg_set_sor_grid_rule(float start_edge, double crowding_target, int max_halvings);
 /* What the last prefilter chain call on this context left for mrgfe_reg_set_source_from_prefilter: *remembered = 1 with the point count and the box
  * (min xyz, max xyz) when a device-driven chain's output stayed in the caller's device buffer and its box is known to enclose finite points only, else 0
  * (n, box may be NULL; box is written only when remembered). */

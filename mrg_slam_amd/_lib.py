@@ -240,6 +240,8 @@ SIGNATURES = {
     "mrgfe_ctx_set_zero_copy_uploads": (C.c_int, [_vp, C.c_int]),
     "mrgfe_ctx_set_byte_layouts": (C.c_int, [_vp, C.c_int]),
     "mrgfe_ctx_set_bfgs_batches": (C.c_int, [_vp, C.c_int]),
+    "mrgfe_ctx_set_statistical_chains": (C.c_int, [_vp, C.c_int]),
+    "mrgfe_ctx_sor_grid_stats": (C.c_int, [_vp, _dp]),
     "mrgfe_ctx_stream": (_vp, [_vp]),
     "mrgfe_ctx_fitness_stats": (C.c_int, [_vp, _dp]),
     "mrgfe_ctx_knn_stats": (C.c_int, [_vp, _dp]),
@@ -436,6 +438,7 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_node_ndt_rounds": (C.c_int, [_vp, C.c_int, C.c_int, _u32p, _u32p]),
     "mrgfe_dbg_set_fit_sweep": (C.c_int, [C.c_int]),
     "mrgfe_dbg_set_prefilter_device_driven": (C.c_int, [C.c_int]),
+    "mrgfe_dbg_set_sor_grid_rule": (C.c_int, [C.c_float, C.c_double, C.c_int]),
     "mrgfe_dbg_prefilter_output": (C.c_int, [_vp, _ip, _szp, _fp]),
     "mrgfe_dbg_ctx_create_detached": (C.c_int, [C.POINTER(_vp)]),
     "mrgfe_dbg_sor_threshold": (C.c_int, [_vp, _fp, _u32p, C.c_size_t, C.c_double, C.c_int, _dp]),
@@ -579,6 +582,18 @@ class Context:
         """``mrgfe_ctx_set_bfgs_batches``: ``BatchMatcher`` on this context takes PCL_GICP_HIP and PCL_GICP_OMP_HIP (the candidates' BFGS loops in lock
         step, records bit-identical to :class:`PclGicpHip`).  Off, the default, such a batch is refused as it always was."""
         check(lib().mrgfe_ctx_set_bfgs_batches(self._h, int(bool(on))))
+
+    def set_statistical_chains(self, on: bool = True):
+        """``mrgfe_ctx_set_statistical_chains``: the prefilter chains NONE -> STATISTICAL and APPROX_VOXELGRID -> STATISTICAL on this context wait for the
+        device once (route 1), the k-NN grid's cell edge chosen on the device; off, the default, they run the host-driven passes.  Same output."""
+        check(lib().mrgfe_ctx_set_statistical_chains(self._h, int(bool(on))))
+
+    def sor_grid_stats(self) -> dict:
+        """The statistical filter's k-NN grid of the last prefilter chain call on this context (``mrgfe_ctx_sor_grid_stats``): ``sized`` the device chose
+        its edge, ``start_edge``, ``edge`` = start_edge * 2^-halvings, ``halvings``, ``crowding`` last measured, ``cells`` of the built grid."""
+        v = (C.c_double * 6)()
+        check(lib().mrgfe_ctx_sor_grid_stats(self._h, v))
+        return {"sized": bool(v[0]), "start_edge": float(v[1]), "edge": float(v[2]), "halvings": int(v[3]), "crowding": float(v[4]), "cells": int(v[5])}
 
     def fitness_stats(self) -> dict:
         """What the last getFitnessScore pass on this context did (``mrgfe_ctx_fitness_stats``)."""

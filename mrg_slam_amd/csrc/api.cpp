@@ -1519,6 +1519,11 @@ int mrgfe_dbg_select_prune(int n_pairs, const double* lower, const double* upper
     return MRGFE_OK;
 }
 int mrgfe_dbg_set_prefilter_device_driven(int mode) { return prefilter_set_device_driven(mode); }
+int mrgfe_dbg_set_sor_grid_rule(float start_edge, double crowding_target, int max_halvings)
+{
+    prefilter_set_sor_grid_rule(start_edge, crowding_target, max_halvings);
+    return MRGFE_OK;
+}
 
 int mrgfe_dbg_prefilter_output(mrgfe_ctx* ctx, int* remembered, size_t* n, float box[6])
 {

@@ -484,6 +484,7 @@ static int ctx_create(int device_id, int high_priority, int reserve_cus, const m
         c->zero_copy_uploads = like->zero_copy_uploads;
         c->byte_layouts.store(like->byte_layouts.load());
         c->bfgs_batches.store(like->bfgs_batches.load());
+        c->statistical_chains.store(like->statistical_chains.load());
     } else if (reserve_cus == MRGFE_RESERVE_AUTO && c->cu_count < 8) {
         // nothing sensible to split off: a plain context
     } else if (reserve_cus > 0 || reserve_cus == MRGFE_RESERVE_AUTO) {
@@ -550,6 +551,24 @@ int mrgfe_ctx_set_bfgs_batches(mrgfe_ctx* ctx, int on)
     if (!ctx) { mrgfe::set_error("mrgfe_ctx_set_bfgs_batches: NULL context"); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(ctx);  // (behind whatever call holds the context: the next mrgfe_batch_create sees the new value)
     ctx->bfgs_batches.store(on != 0);
+    return MRGFE_OK;
+}
+
+int mrgfe_ctx_set_statistical_chains(mrgfe_ctx* ctx, int on)
+{
+    if (!ctx) { mrgfe::set_error("mrgfe_ctx_set_statistical_chains: NULL context"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(ctx);  // (behind whatever call holds the context: the next chain call sees the new value)
+    ctx->statistical_chains.store(on != 0);
+    return MRGFE_OK;
+}
+
+int mrgfe_ctx_sor_grid_stats(mrgfe_ctx* ctx, double out[6])
+{
+    if (!ctx || !out) { mrgfe::set_error("mrgfe_ctx_sor_grid_stats: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(ctx);
+    const mrgfe::SorGridStats& s = ctx->sor_grid;
+    out[0] = s.sized ? 1.0 : 0.0;
+    out[1] = s.start; out[2] = s.edge; out[3] = s.halvings; out[4] = s.crowding; out[5] = s.cells;
     return MRGFE_OK;
 }
 

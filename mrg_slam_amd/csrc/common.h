@@ -224,6 +224,11 @@ struct PrefilterStats {
     uint32_t counts[5] = {0, 0, 0, 0, 0};  // its five stage counts
     uint64_t out_n = 0, calls = 0, served = 0;
 };
+// the statistical filter's k-NN grid of the last prefilter chain call on a context, where the device chose its edge (mrgfe_ctx_sor_grid_stats)
+struct SorGridStats {
+    bool   sized = false;
+    double start = 0, edge = 0, halvings = 0, crowding = 0, cells = 0;
+};
 // the record stage of the last scan-egress call on a context and the calls so far (mrgfe_ctx_egress_stats)
 struct ScanEgressStats {
     int64_t direct = 0;    // 1: the record kernel wrote into the caller's page-locked buffer, 0: into the context's pinned buffer
@@ -254,6 +259,7 @@ struct mrgfe_ctx {
     bool         dma_from_caller = false;     // a zero-copy upload was queued since the last wait for the stream (drain_caller_dma on error paths)
     bool         zero_copy_uploads = false;   // mrgfe_ctx_set_zero_copy_uploads: clouds in page-locked host memory go up by DMA from the caller's buffer
     std::atomic<bool> bfgs_batches{false};    // mrgfe_ctx_set_bfgs_batches: mrgfe_batch_create on this context takes PCL_GICP_HIP / PCL_GICP_OMP_HIP
+    std::atomic<bool> statistical_chains{false};  // mrgfe_ctx_set_statistical_chains: STATISTICAL behind NONE / APPROX_VOXELGRID on the device-driven chain (filters.hip)
     std::atomic<bool> byte_layouts{false};    // mrgfe_ctx_set_byte_layouts: PointCloud2 layouts need not be multiples of 4 (read by check_pointcloud2_layout, before the call takes the lock)
     mrgfe::Event ev_fit[4];                     // around the passes of nn_fitness_batch
     int          priority = 0;                  // > 0: streams at the device's highest priority, < 0: at its lowest (throughput work beside latency-critical rounds)
@@ -281,6 +287,7 @@ struct mrgfe_ctx {
     float        pf_out_box[6] = {0, 0, 0, 0, 0, 0};  // min xyz, max xyz
     bool         pf_out_valid = false;
     mrgfe::PrefilterStats pf_stats;
+    mrgfe::SorGridStats sor_grid;
     mrgfe::PinBuf rec_pin;                      // scan egress (filters.hip): the records of a call whose destination is not page-locked, copied out behind the wait
     mrgfe::ScanEgressStats eg_stats;
     int          cu_count = 256;

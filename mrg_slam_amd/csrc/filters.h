@@ -34,8 +34,11 @@ struct PrefilterChain {
     double stddev_mul = 1.2;
 };
 // 1: the chains keep their point counts on the device and wait once (default; every chain but the statistical filter behind anything other than a voxel
-// grid, or with mean_k outside 1..63), and so does the odometry frame's downsample; 0: host-driven stages; < 0: query
+// grid — unless the context has mrgfe_ctx_set_statistical_chains on —, or with mean_k outside 1..63), and so does the odometry frame's downsample;
+// 0: host-driven stages; < 0: query
 int prefilter_set_device_driven(int mode);
+// mrgfe_dbg_set_sor_grid_rule (include/mrgfe_debug.h): the rule of the statistical filter's device-sized k-NN grid, process-wide; a zero restores that default
+void prefilter_set_sor_grid_rule(float start_edge, double crowding_target, int max_halvings);
 // The chain's downsample stage alone, behind a caller's own head kernel (the odometry frame; filters.hip): method 1 VoxelGrid, 2 ApproximateVoxelGrid.
 struct DownsampleReport {
     int      route;        // 0 the switch is off (nothing was launched), 1 served, 2 an anomaly: the caller runs the host-driven filter

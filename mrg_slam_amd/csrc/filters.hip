@@ -512,7 +512,9 @@ constexpr uint32_t kPfAnomalyRecheck = 16u;     // set by the HOST behind the wa
 constexpr uint32_t kPfAnomalyNonFinite = 32u;   // a non-finite point reached the outlier stage (distance filter off and no VoxelGrid in front of it)
 // the pinned status record the host reads behind its one wait: words 0..4 the stage counts, 5 the anomaly word, 6 the completion mark; the box of the
 // voxel centroids at word 8 (28 bytes); the statistical filter's result at byte 64
-constexpr size_t kPfStatusSorOffset = 64, kPfStatusBytes = kPfStatusSorOffset + sizeof(sor::Result);
+// and behind it what nn_build_device_sized chose for that filter's k-NN grid (NnSizedStatus)
+constexpr size_t kPfStatusSorOffset = 64, kPfStatusGridOffset = (kPfStatusSorOffset + sizeof(sor::Result) + 7) & ~size_t(7);
+constexpr size_t kPfStatusBytes = kPfStatusGridOffset + sizeof(NnSizedStatus);
 static_assert(32 + sizeof(BBox) <= kPfStatusSorOffset, "the box ends before the statistical filter's record");
 
 __device__ __forceinline__ Slice pf_slice(uint32_t n)
@@ -1032,15 +1034,20 @@ static NnDeviceDrivenGrid& pf_grid(mrgfe_ctx* ctx)
 }
 
 // The chains the device-driven form serves (the others, and its anomalies, go through the host-driven passes): every [distance] -> downsample ->
-// outlier chain the parameters express, except the statistical filter behind anything but a VoxelGrid (without a leaf there is no rule for the k-NN
-// grid's cell edge that the host could know: sor_cell_edge) and mean_k beyond a wavefront's list.
+// outlier chain the parameters express, except mean_k beyond a wavefront's list and — unless the context has mrgfe_ctx_set_statistical_chains on — the
+// statistical filter behind anything but a VoxelGrid: without a leaf there is no rule for the k-NN grid's cell edge that the host could know
+// (sor_cell_edge), so with the switch on the device chooses the edge itself (nn_build_device_sized, sor_sized_grid).
 static int  chain_downsample(const PrefilterChain& ch) { return ch.approx_voxelgrid ? 2 : (ch.voxelgrid ? 1 : 0); }
-static bool device_driven_applies(const PrefilterChain& ch, uint32_t n)
+static bool sor_sized_grid(const mrgfe_ctx* ctx, const PrefilterChain& ch)
+{
+    return ch.outlier == 2 && chain_downsample(ch) != 1 && ctx->statistical_chains.load(std::memory_order_relaxed);
+}
+static bool device_driven_applies(const mrgfe_ctx* ctx, const PrefilterChain& ch, uint32_t n)
 {
     if (!prefilter_device_driven_mode() || n == 0) return false;
     const int down = chain_downsample(ch);
     if (down != 0 && !(ch.leaf > 0)) return false;
-    if (ch.outlier == 2) return down == 1 && ch.mean_k >= 1 && ch.mean_k <= 63;  // (mean_k + 1 entries must fit a wavefront's list)
+    if (ch.outlier == 2) return (down == 1 || sor_sized_grid(ctx, ch)) && ch.mean_k >= 1 && ch.mean_k <= 63;  // (mean_k + 1 entries must fit a wavefront's list)
     return true;
 }
 
@@ -1058,6 +1065,37 @@ constexpr uint32_t kSorCellsCap = (1u << 24) - 1u;  // 24 key bits: three radix 
 #define MRGFE_SOR_CELL_LEAVES 8.0f
 #endif
 static float sor_cell_edge(const PrefilterChain& ch) { return std::max(MRGFE_SOR_CELL_LEAVES * ch.leaf, 0.2f); }
+// Without a VoxelGrid in front (downsample NONE or APPROX_VOXELGRID, context switch on) the device sizes the grid: NnGrid::build's halving rule from a start
+// edge, in MRGFE_SOR_GRID_PASSES counting passes (nn_build_device_sized).  The defaults are measured (MI355X, raw 26k-point VLP-16 and 130k-point VLP-64
+// scans, k = 20 and 30; profiles/prefilter_chains_summary.md).  The search is ONE level, so — as behind the voxel grid — the sparse far rings favour
+// larger cells than NnGrid's pyramid does: at the host route's target of 32 (NnGrid::kCrowdingKnn) the device halved the VLP-16 scan to 0.25 m and its
+// k-NN launch took 0.45 ms, at 128 it keeps 1 m and takes 0.08 ms; the VLP-64 scan goes to 0.25 m (0.31 ms; 0.43 ms at 0.125 m, 0.70 ms at 0.5 m) and its
+// APPROX_VOXELGRID(0.1) centroids to 0.5 m.  A target of 64 still halves the VLP-64 scan once too often.  ONE counting pass: a second and a third chose the
+// same edges on both scans and cost 6 - 27 us per call each (a clear, a count and a decision).  Start edge 1 m as on the host route: 2 m costs a halving more.
+#ifndef MRGFE_SOR_GRID_START_EDGE
+#define MRGFE_SOR_GRID_START_EDGE 1.0f
+#endif
+#ifndef MRGFE_SOR_GRID_CROWDING
+#define MRGFE_SOR_GRID_CROWDING 128.0
+#endif
+#ifndef MRGFE_SOR_GRID_MAX_HALVINGS
+#define MRGFE_SOR_GRID_MAX_HALVINGS 4
+#endif
+#ifndef MRGFE_SOR_GRID_PASSES
+#define MRGFE_SOR_GRID_PASSES 1
+#endif
+static_assert(MRGFE_SOR_GRID_PASSES >= 1 && MRGFE_SOR_GRID_PASSES <= 3, "one to three counting passes");
+// mrgfe_dbg_set_sor_grid_rule: the tests' overrides (0 = the default)
+static std::atomic<float>  g_sor_start_edge{0.0f};
+static std::atomic<double> g_sor_crowding{0.0};
+static std::atomic<int>    g_sor_max_halvings{-1};
+void prefilter_set_sor_grid_rule(float start_edge, double crowding_target, int max_halvings)
+{
+    const bool all_default = !(start_edge > 0.0f) && !(crowding_target > 0.0) && max_halvings == 0;
+    g_sor_start_edge.store(start_edge > 0.0f ? start_edge : 0.0f);
+    g_sor_crowding.store(crowding_target > 0.0 ? crowding_target : 0.0);
+    g_sor_max_halvings.store(all_default ? -1 : std::max(max_halvings, 0));
+}
 
 // ---- where a call's records go (RecordSink, filters.h) ----------------------------------------------------------------------------------------------
 // a sink resolved for one call: the record kernel's destination as the device sees it
@@ -1270,7 +1308,16 @@ static int pf_stage_outlier(PfRun& r)
         float*       d_dist = ctx->scratch[12].as<float>();
         uint32_t*    d_valid = reinterpret_cast<uint32_t*>(d_dist + n);
         sor::Result* h_sor = reinterpret_cast<sor::Result*>(ctx->pf_status.as<char>() + kPfStatusSorOffset);
-        MRGFE_TRY(nn_build_device_driven(ctx, &d_st->cp[1], &d_st->sl_rad, n, r.d_part, &d_st->bb_n[1], sor_cell_edge(ch), kSorCellsCap, grid, &d_st->anomaly, r.h_box));
+        if (sor_sized_grid(ctx, ch)) {  // no leaf to take the edge from: the device chooses it from the cloud's density
+            const float  start = g_sor_start_edge.load(std::memory_order_relaxed);
+            const double target = g_sor_crowding.load(std::memory_order_relaxed);
+            const int    halvings = g_sor_max_halvings.load(std::memory_order_relaxed);
+            MRGFE_TRY(nn_build_device_sized(ctx, &d_st->cp[1], &d_st->sl_rad, n, r.d_part, &d_st->bb_n[1], start > 0.0f ? start : MRGFE_SOR_GRID_START_EDGE,
+                                            target > 0.0 ? target : MRGFE_SOR_GRID_CROWDING, halvings >= 0 ? halvings : MRGFE_SOR_GRID_MAX_HALVINGS, MRGFE_SOR_GRID_PASSES,
+                                            kSorCellsCap, grid, &d_st->anomaly, r.h_box, reinterpret_cast<NnSizedStatus*>(ctx->pf_status.as<char>() + kPfStatusGridOffset)));
+        } else {
+            MRGFE_TRY(nn_build_device_driven(ctx, &d_st->cp[1], &d_st->sl_rad, n, r.d_part, &d_st->bb_n[1], sor_cell_edge(ch), kSorCellsCap, grid, &d_st->anomaly, r.h_box));
+        }
         MRGFE_TRY(nn_knn_mean_device_driven(ctx, grid, r.s2_out, &d_st->sl_rad, n, ch.mean_k + 1, d_dist, d_valid));
         MRGFE_TRY(sor_threshold_launch(ctx, d_dist, d_valid, &d_st->sl_rad.n, n, ch.stddev_mul, ctx->scratch[14].as<SorPartial>(), &d_st->sor, h_sor, &d_st->anomaly));
         hipLaunchKernelGGL(sor_flags_dd_kernel, r.g256, b256, 0, st, d_dist, &d_st->sl_rad.n, &d_st->sor.thr, d_flags);
@@ -1304,7 +1351,10 @@ static int pf_run_stages(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHea
         MRGFE_TRY(ctx->scratch[12].ensure(size_t(n) * 8));
         MRGFE_TRY(ctx->scratch[14].ensure(sizeof(SorPartial) * (size_t(tab.total_blks) + 1)));
     }
-    if (r.down == 2) {  // the approximate grid's stretch ordinals and its 512 entry ranks
+    if (r.down == 2) {
+        // the approximate grid's stretch ordinals and its 512 entry ranks.  Behind it the statistical filter may use the same two slots: both sizes are ensured
+        // here, before the first launch (grow-only buffers: the larger demand holds), and the approximate grid's last reader of either (avg_emit_dd_kernel) is
+        // queued on the one stream in front of the statistical stage's first writer (nn_knn_mean_dd_kernel, sor_threshold_launch)
         MRGFE_TRY(ctx->scratch[12].ensure(size_t(n) * 4));
         MRGFE_TRY(ctx->scratch[14].ensure(sizeof(uint32_t) * 512));
     }
@@ -1367,6 +1417,16 @@ static int filter_chain_device_driven(mrgfe_ctx* ctx, const PrefilterChain& ch, 
         // the host's own build of the threshold's tail on the reported sums: the result must not depend on how the device library rounds an f64 divide or
         // square root (it costs nothing here)
         if (!sor::same_bits(sor::threshold(h_sor->sum, h_sor->sq_sum, h_sor->valid, ch.stddev_mul), h_sor->thr)) ps.anomaly |= kPfAnomalyRecheck;
+        if (sor_sized_grid(ctx, ch)) {  // what the device chose for the k-NN grid (mrgfe_ctx_sor_grid_stats)
+            const NnSizedStatus* g = reinterpret_cast<const NnSizedStatus*>(ctx->pf_status.as<char>() + kPfStatusGridOffset);
+            SorGridStats&        s = ctx->sor_grid;
+            s.sized = true;
+            s.start = g->start;
+            s.edge = g->edge;
+            s.halvings = g->halvings;
+            s.crowding = (g->measured && g->n_finite) ? 1.0 + 2.0 * double(g->crowd_sum) / double(g->n_finite) : 0.0;
+            s.cells = g->n_cells;
+        }
     }
     if (ps.anomaly != 0) return MRGFE_OK;  // something unusual: the host-driven chain decides what the reference does with it
     *out_n = rep.counts[4];
@@ -1430,11 +1490,12 @@ static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const Cha
     for (uint32_t& c : ps.counts) c = 0;
     ps.out_n = 0;
     ps.calls += 1;
+    ctx->sor_grid = SorGridStats{};
     if (n == 0) return MRGFE_OK;
     if (n > 0x7fffffffu) { set_error("prefilter: cloud too large"); return MRGFE_ERR_INVALID; }
     DevBuf &a = ctx->pf_buf[0], &b = ctx->pf_buf[1];  // ping-pong, kept between calls (grow-only: a hipMalloc / hipFree pair per scan is a device-wide wait)
     const void* d_raw = nullptr;
-    const bool  device_driven = device_driven_applies(ch, static_cast<uint32_t>(n));
+    const bool  device_driven = device_driven_applies(ctx, ch, static_cast<uint32_t>(n));
     // The records of a device-driven STATISTICAL chain are staged whatever the caller's memory is: the host re-checks that chain's threshold behind the wait
     // (kPfAnomalyRecheck) and may hand the call back after the record kernel has run, and a caller's buffer must never hold a record beyond *out_n.
     RecordDest dest;

@@ -134,11 +134,28 @@ class NnGridSet {
 // nn_knn_mean_device_driven, which reads no occupancy words.
 constexpr uint32_t kNnAnomalyCells = 1u << 8;
 struct NnDeviceDrivenGrid {
-    DevBuf cells, sorted, desc;  // cell table (cells_cap + 8 words), cell-major points (n_cap), the NnBuildDev record
+    DevBuf cells, sorted, desc;  // cell table (cells_cap + 8 words), cell-major points (n_cap), the NnBuildDev record (behind it the state of nn_build_device_sized)
 };
 // d_n_boxes == NULL: d_bbox is the cloud's bounding box; else d_bbox is a list of *d_n_boxes partial boxes that the geometry kernel merges itself
 int nn_build_device_driven(mrgfe_ctx* ctx, const float4* const* d_cloud_ptr, const Slice* d_slice, uint32_t n_cap, const BBox* d_bbox, const uint32_t* d_n_boxes, float cell,
                            uint32_t cells_cap, NnDeviceDrivenGrid& g, uint32_t* d_anomaly, BBox* h_box_out = nullptr);  // h_box_out: pinned; receives the (merged) box
+// The same build with the cell EDGE chosen on the device from the cloud's own density — for a cloud no voxel grid has thinned, where the host knows no
+// edge.  NnGrid::build's adaptive rule as a fixed sequence of launches, no host wait: the geometry at `start_edge` (doubled on the device, at most 8 times,
+// until the box fits cells_cap cells), then `passes` (1..3) counting passes — a clear of the live part of the cell table, which doubles as the count table,
+// the one-atomic-per-distinct-cell counting with its crowding sum, and a one-workgroup decision: crowding = 1 + 2 Σ before / n_finite; settled when it is
+// <= crowding_target, else ceil(log4(crowding / target)) halvings, `max_halvings` in all and never beyond cells_cap cells; a pass whose grid is settled
+// returns at once — and the key / sort / fill launches of nn_build_device_driven at the chosen edge.  The sums are integers: the edge is a function of
+// the cloud.  Every size the kernels read from device memory is clamped there against n_cap and cells_cap; a box that fits at no allowed edge sets
+// kNnAnomalyCells and builds the one-cell empty grid.  *h_status_out (pinned, may be NULL) receives what was chosen, to be read behind the caller's wait.
+struct NnSizedStatus {
+    float              start, edge;        // the start edge used (after the doublings), the chosen edge = start * 2^-halvings
+    uint32_t           halvings, n_cells;  // n_cells: of the built grid
+    unsigned long long crowd_sum;          // Σ before of the last counting pass that measured: its crowding is 1 + 2 crowd_sum / n_finite
+    uint32_t           n_finite, measured; // measured: counting passes that ran (0: the start grid admitted no halving)
+};
+int nn_build_device_sized(mrgfe_ctx* ctx, const float4* const* d_cloud_ptr, const Slice* d_slice, uint32_t n_cap, const BBox* d_bbox, const uint32_t* d_n_boxes, float start_edge,
+                          double crowding_target, int max_halvings, int passes, uint32_t cells_cap, NnDeviceDrivenGrid& g, uint32_t* d_anomaly, BBox* h_box_out = nullptr,
+                          NnSizedStatus* h_status_out = nullptr);
 // flags[i] = 1 iff #{j : sqdist(q_i, p_j) <= r2} >= need for the first d_slice->n points of d_q (the grid's own cloud): nn_radius_flags_kernel with
 // the grid and the count read from device memory
 int nn_radius_flags_device_driven(mrgfe_ctx* ctx, const NnDeviceDrivenGrid& g, const float4* d_q, const Slice* d_slice, uint32_t n_cap, double r2, int need, float cell, uint32_t* d_flags);

@@ -998,6 +998,195 @@ int nn_build_device_driven(mrgfe_ctx* ctx, const float4* const* d_cloud_ptr, con
     return MRGFE_OK;
 }
 
+// ---- the same grid with its cell EDGE chosen on the device (nn_grid.h: nn_build_device_sized) -----------------------------------------------------------
+// NnGrid::build's adaptive halving without its host waits: a fixed sequence of launches — the start geometry, then per counting pass a clear of the live
+// part of the cell table (it doubles as the count table: the fill writes every entry afterwards), nn_cellkey_body's counting with its crowding sum, and a
+// one-workgroup decision that rewrites the NnBuildDev record at the edge it chose.  A pass whose grid is settled returns at once.  The record behind the
+// NnBuildDev in NnDeviceDrivenGrid::desc carries the merged box, the state of the search and the kCrowdSlots counters.
+struct NnSizedDev {
+    BBox               bb;
+    float              start, edge;  // the start edge used (after the doublings), the current edge
+    uint32_t           halvings, settled;
+    uint32_t           measured, pad;  // counting passes that measured
+    unsigned long long crowd_sum;      // sum of `before` of the last pass that measured
+    unsigned long long crowd[kCrowdSlots];
+};
+static_assert(sizeof(NnSizedStatus) == 32, "the pinned words behind the chain's sor::Result");
+constexpr int kNnSizedMaxDoublings = 8;  // the start edge grows to 256 x at the most; a box that needs more is handed back (kNnAnomalyCells)
+
+// does the box fit `cap` cells at edge c?  (a dimension beyond 2^24, an infinite or NaN extent: no)
+__device__ __forceinline__ bool nn_sized_fits(const BBox& bb, float c, uint32_t cap)
+{
+#pragma clang fp contract(off)
+    double prod = 1.0;
+    for (int a = 0; a < 3; ++a) {
+        const float f = floorf((bb.mx[a] - bb.mn[a]) / c) + 1.0f;
+        if (!(f >= 1.0f && f <= 16777216.0f)) return false;
+        prod *= static_cast<double>(f);
+    }
+    return prod <= static_cast<double>(cap);
+}
+
+// pass 0: merges the boxes and takes the start edge; pass >= 1: reads the counters of the counting pass in front of it and applies NnGrid::build's rule.
+// Either writes the whole NnBuildDev record at the current edge (nn_geometry_kernel's arithmetic), so the record is a valid build descriptor at any point
+// of the sequence; the last one leaves the chosen figures in pinned memory.
+__global__ __launch_bounds__(256) void nn_sized_decide_kernel(const float4* const* __restrict__ cloud_ptr, const Slice* __restrict__ slice, const BBox* __restrict__ bbox,
+                                                               const uint32_t* __restrict__ n_boxes, float start_edge, double target, int max_halvings, uint32_t cells_cap,
+                                                               uint32_t n_cap, uint32_t* cell_table, float4* sorted, NnBuildDev* __restrict__ out, NnSizedDev* __restrict__ rec,
+                                                               uint32_t* __restrict__ anomaly, BBox* __restrict__ h_box, NnSizedStatus* __restrict__ h_stat, int pass, int last)
+{
+#pragma clang fp contract(off)
+    BBox bb;
+    if (pass == 0) {
+        if (n_boxes) bb = block_merge_partials(bbox, *n_boxes);  // (uniform)
+        else         bb = *bbox;
+    }
+    if (threadIdx.x) return;
+    float    start, edge;
+    uint32_t halvings = 0, settled = 0, measured = 0;
+    unsigned long long crowd_sum = 0;
+    if (pass == 0) {
+        if (h_box) *h_box = bb;  // (pinned host memory: read behind the caller's stream wait)
+        rec->bb = bb;
+        edge = start_edge;
+        for (int d = 0; d < kNnSizedMaxDoublings && bb.n_finite && !nn_sized_fits(bb, edge, cells_cap); ++d) edge *= 2.0f;
+        start = edge;
+    } else {
+        bb = rec->bb;
+        start = rec->start; edge = rec->edge;
+        halvings = rec->halvings; settled = rec->settled; measured = rec->measured; crowd_sum = rec->crowd_sum;
+    }
+    const bool fits = bb.n_finite == 0 || nn_sized_fits(bb, edge, cells_cap);  // (no finite point: the one-cell empty grid, as nn_geometry_kernel builds it)
+    if (!fits || bb.n_finite == 0) settled = 1;
+    if (pass > 0 && !settled) {
+        // the counting pass in front of this launch measured the grid at `edge`: crowding = population of the cell an average point sits in
+        unsigned long long sum = 0;
+        for (uint32_t k = 0; k < kCrowdSlots; ++k) sum += rec->crowd[k];
+        crowd_sum = sum;
+        measured += 1;
+        const double crowding = 1.0 + 2.0 * static_cast<double>(sum) / static_cast<double>(bb.n_finite);
+        if (crowding <= target) {
+            settled = 1;
+        } else {
+            // ceil(log4(crowding / target)) halvings at once (a scan's surfaces: 4 x per halving), by comparison — no device logarithm decides
+            const int room = max_halvings - static_cast<int>(halvings);  // (>= 1: else the grid was settled)
+            int       step = 1;
+            double    lim = target * 4.0;
+            while (step < room && crowding > lim) { ++step; lim *= 4.0; }
+            while (step > 1 && !nn_sized_fits(bb, edge * ldexpf(1.0f, -step), cells_cap)) --step;
+            edge *= ldexpf(1.0f, -step);
+            halvings += static_cast<uint32_t>(step);
+        }
+    }
+    // a further counting pass only where a further halving may be taken
+    if (!settled && (static_cast<int>(halvings) >= max_halvings || !nn_sized_fits(bb, edge * 0.5f, cells_cap))) settled = 1;
+    if (last) settled = 1;
+    rec->start = start; rec->edge = edge;
+    rec->halvings = halvings; rec->settled = settled; rec->measured = measured; rec->pad = 0; rec->crowd_sum = crowd_sum;
+    for (uint32_t k = 0; k < kCrowdSlots; ++k) rec->crowd[k] = 0ull;  // (for the next counting pass)
+
+    NnBuildDev b;
+    memset(&b, 0, sizeof(b));
+    NnGridDev& lv = b.lv;
+    // (the arithmetic of NnGrid::build_level, float for float)
+    float extent = 0.0f;
+    for (int a = 0; a < 3; ++a) { lv.origin[a] = bb.mn[a]; extent = fmaxf(extent, bb.mx[a] - bb.mn[a]); }
+    lv.cell = edge;
+    lv.slack = 1e-6f * (extent + edge);
+    lv.n = bb.n_finite;
+    unsigned long long cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        lv.dim[a] = (fits && bb.n_finite) ? static_cast<int>(floorf((bb.mx[a] - bb.mn[a]) / edge)) + 1 : 1;  // (fits: every dimension is 1 .. 2^24)
+        lv.bdim[a] = (lv.dim[a] + 3) / 4;
+        cells *= static_cast<unsigned long long>(lv.dim[a]);
+    }
+    if (!fits) atomicOr(anomaly, kNnAnomalyCells);
+    if (cells > cells_cap) cells = cells_cap;  // (cannot be: nn_sized_fits bounds the product; nothing behind this record may index past the table)
+    b.n_cells = static_cast<uint32_t>(cells);
+    b.pts = *cloud_ptr;
+    b.n = fits ? min(slice->n, n_cap) : 0u;
+    b.off = 0;
+    b.active = (fits && bb.n_finite > 0) ? 1u : 0u;
+    b.counts = cell_table;
+    b.crowd = last ? nullptr : rec->crowd;  // (the build's own fill launch measures nothing)
+    b.sorted = sorted;
+    lv.cell_start = cell_table;
+    lv.sorted = sorted;
+    if (!b.active) {  // an empty grid: one cell without points (the search kernels test lv.n first)
+        lv.n = 0;
+        cell_table[0] = 0;
+        cell_table[1] = 0;
+    }
+    *out = b;
+    if (last && h_stat) {
+        NnSizedStatus s;
+        s.start = start; s.edge = edge;
+        s.halvings = halvings; s.n_cells = b.n_cells;
+        s.crowd_sum = crowd_sum;
+        s.n_finite = bb.n_finite; s.measured = measured;
+        *h_stat = s;
+    }
+}
+// the live part of the count table, four entries per store: launched with a fixed number of workgroups, the size read (and clamped) on the device
+constexpr uint32_t kNnSizedClearBlocks = 1024;
+__global__ __launch_bounds__(256) void nn_sized_clear_kernel(const NnBuildDev* __restrict__ d, const NnSizedDev* __restrict__ rec, uint32_t cells_cap)
+{
+    if (rec->settled || !d->active) return;  // uniform
+    const uint32_t quads = (min(d->n_cells, cells_cap) + 3u) / 4u;  // (the table holds cells_cap + 8 words)
+    uint4*         t = reinterpret_cast<uint4*>(d->counts);
+    for (uint32_t q = blockIdx.x * 256u + threadIdx.x; q < quads; q += kNnSizedClearBlocks * 256u) t[q] = make_uint4(0u, 0u, 0u, 0u);
+}
+// one counting pass at the record's current edge; the keys it writes are scratch (the build's own cellkey launch follows the last decision)
+__global__ __launch_bounds__(256) void nn_sized_count_kernel(const NnBuildDev* __restrict__ d, const NnSizedDev* __restrict__ rec, uint32_t* __restrict__ keys,
+                                                              uint32_t* __restrict__ vals, uint32_t n_cap, uint32_t cells_cap)
+{
+    if (rec->settled) return;  // uniform
+    const NnBuildDev& b = *d;
+    const uint32_t    n = min(b.n, n_cap);
+    if (!b.active || blockIdx.x * 256u >= n) return;  // uniform per workgroup
+    nn_cellkey_body(b.pts, n, b.lv, min(b.n_cells, cells_cap), keys, vals, b.counts, b.crowd);
+}
+
+int nn_build_device_sized(mrgfe_ctx* ctx, const float4* const* d_cloud_ptr, const Slice* d_slice, uint32_t n_cap, const BBox* d_bbox, const uint32_t* d_n_boxes, float start_edge,
+                          double crowding_target, int max_halvings, int passes, uint32_t cells_cap, NnDeviceDrivenGrid& g, uint32_t* d_anomaly, BBox* h_box_out,
+                          NnSizedStatus* h_status_out)
+{
+    if (!(start_edge > 0.0f) || !(crowding_target > 0.0) || cells_cap == 0) { set_error("nn_build_device_sized: start edge, crowding target and table must be positive"); return MRGFE_ERR_INVALID; }
+    max_halvings = std::min(std::max(max_halvings, 0), 16);
+    passes = std::min(std::max(passes, 1), 3);
+    hipStream_t st = ctx->stream;
+    SliceTable  tab;
+    tab.build(&n_cap, 1);
+    constexpr size_t at_rec = (sizeof(NnBuildDev) + 15) & ~size_t(15);
+    MRGFE_TRY(g.cells.ensure(sizeof(uint32_t) * (size_t(cells_cap) + 8)));
+    MRGFE_TRY(g.sorted.ensure(sizeof(float4) * std::max<size_t>(n_cap, 1)));
+    MRGFE_TRY(g.desc.ensure(at_rec + sizeof(NnSizedDev)));
+    DevBuf &dk = ctx->scratch[2], &dv = ctx->scratch[3], &dkt = ctx->scratch[4], &dvt = ctx->scratch[5], &dh = ctx->scratch[6];
+    const size_t ne = std::max<size_t>(n_cap, 4);
+    MRGFE_TRY(dk.ensure(ne * 4)); MRGFE_TRY(dv.ensure(ne * 4)); MRGFE_TRY(dkt.ensure(ne * 4)); MRGFE_TRY(dvt.ensure(ne * 4));
+    MRGFE_TRY(dh.ensure(sizeof(uint32_t) * 256 * (tab.total_blks + 1)));
+    NnBuildDev* d_dev = g.desc.as<NnBuildDev>();
+    NnSizedDev* d_rec = reinterpret_cast<NnSizedDev*>(g.desc.as<char>() + at_rec);
+    const dim3  gpts(tab.max_blks * (kTile / 256), 1);
+    for (int pass = 0; pass <= passes; ++pass) {
+        if (pass > 0 && tab.max_blks) {
+            hipLaunchKernelGGL(nn_sized_clear_kernel, dim3(kNnSizedClearBlocks), dim3(256), 0, st, d_dev, d_rec, cells_cap);
+            hipLaunchKernelGGL(nn_sized_count_kernel, gpts, dim3(256), 0, st, d_dev, d_rec, dk.as<uint32_t>(), dv.as<uint32_t>(), n_cap, cells_cap);
+        }
+        hipLaunchKernelGGL(nn_sized_decide_kernel, dim3(1), dim3(256), 0, st, d_cloud_ptr, d_slice, d_bbox, d_n_boxes, start_edge, crowding_target, max_halvings, cells_cap, n_cap,
+                           g.cells.as<uint32_t>(), g.sorted.as<float4>(), d_dev, d_rec, d_anomaly, h_box_out, h_status_out, pass, pass == passes ? 1 : 0);
+    }
+    if (tab.max_blks == 0) { MRGFE_HIP_CHECK(hipGetLastError()); return MRGFE_OK; }
+    hipLaunchKernelGGL(nn_cellkey_many_kernel, gpts, dim3(256), 0, st, d_dev, dk.as<uint32_t>(), dv.as<uint32_t>(), 0);
+    int key_bits = 1;
+    while (key_bits < 32 && (uint64_t(1) << key_bits) <= cells_cap) ++key_bits;  // the key of a non-finite point is n_cells <= cells_cap
+    uint32_t *sk = nullptr, *sv = nullptr;
+    MRGFE_TRY(radix_sort_pairs(ctx, dk.as<uint32_t>(), dv.as<uint32_t>(), dkt.as<uint32_t>(), dvt.as<uint32_t>(), d_slice, tab, key_bits, dh.as<uint32_t>(), &sk, &sv, true));
+    hipLaunchKernelGGL(nn_fill_many_kernel, dim3(tab.max_blks * (kTile / 256) + 1, 1), dim3(256), 0, st, d_dev, sk, sv, 0);
+    MRGFE_HIP_CHECK(hipGetLastError());
+    return MRGFE_OK;
+}
+
 int nn_radius_flags_device_driven(mrgfe_ctx* ctx, const NnDeviceDrivenGrid& g, const float4* d_q, const Slice* d_slice, uint32_t n_cap, double r2, int need, float cell, uint32_t* d_flags)
 {
     if (n_cap == 0) return MRGFE_OK;

@@ -101,7 +101,10 @@ class OracleOps:
 
 
 class PrefilteringComponent:
-    def __init__(self, params: dict | None = None, ops=None, lookup_transform=None):
+    def __init__(self, params: dict | None = None, ops=None, lookup_transform=None, statistical_chains: bool = False):
+        """``statistical_chains``: switch the ops' context to serve ``outlier_removal_method: STATISTICAL`` behind ``downsample_method`` NONE /
+        APPROX_VOXELGRID with one device wait (``Context.set_statistical_chains``; same output).  Ops that hold no context (default: the shared one)
+        get one of their own, so the shared context stays as it is; on ops without a context (the oracle's) the option does nothing."""
         self.p = dict(DEFAULTS)
         self.p.update(params or {})
         if self.p["downsample_method"] not in ("VOXELGRID", "APPROX_VOXELGRID", "NONE"):
@@ -109,6 +112,12 @@ class PrefilteringComponent:
         if self.p["outlier_removal_method"] not in ("RADIUS", "STATISTICAL", "NONE"):
             raise ValueError(f"unknown outlier_removal_method {self.p['outlier_removal_method']!r}")
         self.ops = ops or HipOps()
+        if statistical_chains and hasattr(self.ops, "ctx"):
+            if self.ops.ctx is None:
+                from ._lib import Context
+
+                self.ops.ctx = Context()
+            self.ops.ctx.set_statistical_chains(True)
         self.lookup_transform = lookup_transform
         self.imu_queue: list[tuple[float, np.ndarray]] = []  # (stamp, angular velocity): imu_queue_
 
