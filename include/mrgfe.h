@@ -89,7 +89,7 @@ typedef struct mrgfe_reg_params {
     double max_correspondence_distance;     /* GICP                                     "reg_max_correspondence_distance"   */
     int    max_optimizer_iterations;        /* PCL_GICP_HIP: steps of the inner BFGS    "reg_max_optimizer_iterations"      */
     int    use_reciprocal_correspondences;  /* ICP_HIP (pcl::GICP ignores it upstream)  "reg_use_reciprocal_correspondences"*/
-    int    correspondence_randomness;       /* GICP k neighbours                        "reg_correspondence_randomness"     */
+    int    correspondence_randomness;       /* GICP k neighbours, 4 .. 256              "reg_correspondence_randomness"     */
     double resolution;                      /* NDT / VGICP voxel size                   "reg_resolution"                    */
     int    nn_search_method;                /* enum mrgfe_ndt_search                    "reg_nn_search_method"              */
     double step_size;                       /* NDT More-Thuente step_max (0.1)    */
@@ -302,7 +302,9 @@ double mrgfe_ndt_mean_neighbours(const mrgfe_reg* reg);
 
 /* k nearest neighbours of every query among the points of `cloud` (pcl::search::KdTree::nearestKSearch(pt, k, ...), the
  * search behind fast_gicp's covariances and StatisticalOutlierRemoval): idx / sqd are [nq][k], ascending by (squared
- * distance, index); entries beyond the cloud's size are -1 / -1.  1 <= k <= 64.  Non-finite queries get no neighbours. */
+ * distance, index); entries beyond the cloud's size are -1 / -1.  1 <= k <= 256, the library's limit (anything else is MRGFE_ERR_INVALID): up to
+ * 64 the neighbour list of a query holds one entry per lane of its wavefront, 65 .. 256 run a wide kernel with two to four.  Non-finite queries
+ * get no neighbours. */
 int mrgfe_knn(mrgfe_ctx* ctx, const float* cloud_xyzi, size_t n, const float* query_xyzi, size_t nq, size_t stride_bytes, int k, int32_t* idx, float* sqd);
 
 /* ---- GICP internals exposed for kernel-level parity tests ------------------------------------------------------------ */
@@ -352,6 +354,7 @@ int  mrgfe_prefilter_records(mrgfe_ctx* ctx, const mrgfe_prefilter_params* param
  * the records, deskews, transforms, stores the packed cloud and (on the usual chains) is the distance filter's first pass; nothing comes down but
  * the chain's status words and, for the host form, the filtered cloud; every chain but STATISTICAL behind NONE or APPROX_VOXELGRID (unless
  * mrgfe_ctx_set_statistical_chains is on), or with statistical_mean_k outside 1..63, waits for the device once (mrgfe_ctx_prefilter_stats says which route served a call).
+ * statistical_mean_k 64 .. 255 is served by the host-driven passes (route 0, the wide k-NN kernel); 256 and more is MRGFE_ERR_INVALID.
  * The output equals, bit for bit and in order, mrgfe_ingest_pointcloud2 -> mrgfe_deskew (if `deskew`) -> mrgfe_transform_cloud (if `transform`)
  * -> mrgfe_prefilter[_device] for the same inputs.  The reference's quirks are kept: deskewing counts i and n = width * height over the UNFILTERED
  * cloud (:286), non-finite points included; the transform leaves non-finite points as they are; the distance filter is what drops them. */
@@ -424,7 +427,8 @@ int mrgfe_approx_voxelgrid(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t s
 /* replaces pcl::RadiusOutlierRemoval::filter with setRadiusSearch / setMinNeighborsInRadius (:195-198) */
 int mrgfe_radius_outlier(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride_bytes, double radius, int min_neighbors,
                          float* out_xyzi, size_t* out_n);
-/* replaces pcl::StatisticalOutlierRemoval::filter with setMeanK / setStddevMulThresh (:189-192) */
+/* replaces pcl::StatisticalOutlierRemoval::filter with setMeanK / setStddevMulThresh (:189-192).  1 <= mean_k <= 255: the mean_k + 1 nearest of a
+ * point, itself first, must fit the k-NN search's list of 256 (mrgfe_knn); anything else is MRGFE_ERR_INVALID */
 int mrgfe_statistical_outlier(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride_bytes, int mean_k, double stddev_mul,
                               float* out_xyzi, size_t* out_n);
 /* replaces InformationMatrixCalculator::calc_fitness_score (src/mrg_slam/information_matrix_calculator.cpp:46-81) */

@@ -428,7 +428,7 @@ int mrgfe_knn(mrgfe_ctx* ctx, const float* cloud, size_t n, const float* query, 
     MRGFE_TRY(check_count(n, "mrgfe_knn"));
     MRGFE_TRY(check_count(nq, "mrgfe_knn"));
     if (!ctx || (n && !cloud) || (nq && (!query || !idx || !sqd))) { set_error("mrgfe_knn: NULL argument"); return MRGFE_ERR_INVALID; }
-    if (k < 1 || k > 64) { set_error("mrgfe_knn: k must be in [1, 64]"); return MRGFE_ERR_INVALID; }
+    if (k < 1 || k > 256) { set_error("mrgfe_knn: k must be in [1, 256]"); return MRGFE_ERR_INVALID; }
     if (nq == 0) return MRGFE_OK;
     MRGFE_LOCK(ctx);
     MRGFE_TRY(ctx->bind());
@@ -455,7 +455,7 @@ int mrgfe_dbg_set_gicp_corr_passes(int mode) { return gicp_set_corr_passes(mode)
 int mrgfe_dbg_grid_set_query(mrgfe_ctx* ctx, const float* const* clouds, const size_t* n, int count, const float* query, size_t nq, int k, int rounds, int32_t* idx, float* sqd)
 {
     if (!ctx || count < 1 || !clouds || !n || !query || !idx || !sqd || nq == 0) { set_error("mrgfe_dbg_grid_set_query: bad argument"); return MRGFE_ERR_INVALID; }
-    if (k < 1 || k > 64) { set_error("mrgfe_dbg_grid_set_query: k must be in [1, 64]"); return MRGFE_ERR_INVALID; }
+    if (k < 1 || k > 256) { set_error("mrgfe_dbg_grid_set_query: k must be in [1, 256]"); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(ctx);
     MRGFE_TRY(ctx->bind());
     DevBuf     dd, di, dq;  // (freed in reverse order of declaration: the set, the clouds, then these)
@@ -600,7 +600,7 @@ int mrgfe_statistical_outlier(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_
 {
     MRGFE_TRY(check_count(n, "mrgfe_statistical_outlier"));
     if (!ctx || !out_n || (n && (!xyzi || !out))) { set_error("mrgfe_statistical_outlier: NULL argument"); return MRGFE_ERR_INVALID; }
-    if (mean_k < 1 || mean_k > 63) { set_error("mrgfe_statistical_outlier: mean_k must be in [1, 63]"); return MRGFE_ERR_INVALID; }
+    if (mean_k < 1 || mean_k > 255) { set_error("mrgfe_statistical_outlier: mean_k must be in [1, 255]"); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(ctx);
     MRGFE_TRY(ctx->bind());
     return filter_statistical_outlier(ctx, xyzi, n, stride, mean_k, stddev_mul, out, out_n);
@@ -638,6 +638,8 @@ static int chain_from_params(const char* fn, const mrgfe_prefilter_params* p, Pr
 {
     if (p->downsample_method < 0 || p->downsample_method > 2 || p->outlier_removal_method < 0 || p->outlier_removal_method > 2) { set_error("%s: unknown method", fn); return MRGFE_ERR_INVALID; }
     if (p->downsample_method >= 1 && !(p->downsample_resolution > 0)) { set_error("%s: downsample_resolution must be > 0", fn); return MRGFE_ERR_INVALID; }
+    // (mean_k + 1 entries must fit the widest neighbour list, NnGrid::knn_device's 256)
+    if (p->outlier_removal_method == 2 && p->statistical_mean_k > 255) { set_error("%s: statistical_mean_k must be in [1, 255]", fn); return MRGFE_ERR_INVALID; }
     PrefilterChain ch;
     ch.distance = p->enable_distance_filter != 0;
     ch.near_t = p->distance_near_thresh;

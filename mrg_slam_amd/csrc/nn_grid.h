@@ -85,7 +85,8 @@ class NnGrid {
     int nearest_device(mrgfe_ctx* ctx, const float4* d_q, size_t n, const float* d_T12, int32_t* d_idx, float* d_sqd);
     // flags[i] = 1 iff #{j : sqdist(q_i, p_j) <= r2} >= need   (queries are the device cloud d_q)
     int radius_count_flags(mrgfe_ctx* ctx, const float4* d_q, size_t n, double r2, int need, uint32_t* d_flags);
-    // k nearest neighbours (ascending by (sqdist, index)) of every query: d_idx / d_sqd are [n][k]; missing -> -1
+    // k nearest neighbours (ascending by (sqdist, index)) of every query: d_idx / d_sqd are [n][k]; missing -> -1.  1 <= k <= 256: up to 64 on one
+    // list entry per lane, 65..256 on two to four (the wide kernel)
     int knn_device(mrgfe_ctx* ctx, const float4* d_q, size_t n, int k, int32_t* d_idx, float* d_sqd);
     // become a view of a grid whose device arrays another object owns (NnGridSet); release() then only forgets it
     void adopt(const NnGrid2Dev& h, size_t n) { release(); h_ = h; n_ = n; built_ = true; }

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "dev_float.h"
@@ -2574,6 +2575,8 @@ int NnGrid::radius_count_flags(mrgfe_ctx* ctx, const float4* d_q, size_t n, doub
 // (distance, index) is a total order, so the result does not depend on the visiting order.  A query walks kKnnRings rings
 // of a level and then starts over on the next coarser one (sparse surroundings: the k-th neighbour is many fine cells
 // away); candidates it meets again there are recognised in the list by their (distance, index) and skipped.
+// k <= 64 is the narrow kernel (nn_knn_kernel, one entry per lane); 65 <= k <= 256 runs the same walk on R = ceil(k / 64) entries per lane
+// (nn_knn_wide_kernel<R>, KnnList<R> below).
 constexpr int kKnnRings = 2;
 #ifndef MRGFE_KNN_SORT_MIN
 #define MRGFE_KNN_SORT_MIN 9
@@ -2625,14 +2628,121 @@ __device__ __forceinline__ void knn_sort_merge(float& td, int32_t& ti, float d, 
     for (int stride = 32; stride > 0; stride >>= 1) knn_cmpx(td, ti, stride, true);
 }
 
-// one query per wavefront: the k nearest of p; `done(td, ti, cnt)` consumes the list where it lies — entry j in lane j (td squared distance, ti index), the
-// first cnt (uniform) of them found, ascending by (distance, index); returns the candidates measured
-template <class Epilogue>
-__device__ __forceinline__ uint32_t nn_knn_walk(const NnGrid2Dev& g, const float4 p, int k, Epilogue&& done)
+// f(integral_constant<int, 0>) ... f(integral_constant<int, R - 1>), spelled out at compile time: no loop for the optimiser to unroll (or not), so an
+// index made of the argument is a constant wherever the call is inlined
+template <class F, int... r>
+__device__ __forceinline__ void knn_each_register(F&& f, std::integer_sequence<int, r...>) { (f(std::integral_constant<int, r>{}), ...); }
+template <int R, class F>
+__device__ __forceinline__ void knn_each_register(F&& f) { knn_each_register(f, std::make_integer_sequence<int, R>{}); }
+
+// The running top-k list of a wavefront, R entries per lane: entry j lies in lane j & 63 of register j >> 6, so register r is the sorted run
+// [64 r, 64 r + 64) of the list and R = 1 is the one-entry-per-lane list of the narrow kernel.  k lies in (64 (R - 1), 64 R]: the k-th entry is
+// always in register R - 1.  Every index into d[] / i[] is a compile-time constant (knn_each_register), so the list stays in registers.
+constexpr int kKnnMaxK = 256;  // four entries per lane
+template <int R>
+struct KnnList {
+    float (&d)[R];    // squared distances; (inf, max) marks an empty entry
+    int32_t (&i)[R];  // point indices
+    // (two arrays of the walk, named here: apart, the compiler treats them as it treated the narrow kernel's td / ti before the list had a type)
+
+    __device__ __forceinline__ void clear()
+    {
+        knn_each_register<R>([&](auto r) __attribute__((always_inline)) { d[r] = INFINITY; i[r] = 0x7fffffff; });
+    }
+    // entries k and beyond are emptied again (an insertion or a merge pushed the old k-th entry there)
+    __device__ __forceinline__ void trim(int lane, int k)
+    {
+        knn_each_register<R>([&](auto r) __attribute__((always_inline)) {
+            if (64 * r + lane >= k) { d[r] = INFINITY; i[r] = 0x7fffffff; }
+        });
+    }
+    // the k-th entry as wave-uniform values
+    __device__ __forceinline__ void kth(int k, float& kd, int32_t& ki) const
+    {
+        kd = wave_read(d[R - 1], k - 1 - 64 * (R - 1));
+        ki = wave_read(i[R - 1], k - 1 - 64 * (R - 1));
+    }
+    // lanes that hold (cd, cci) already, in any register
+    __device__ __forceinline__ uint64_t holds(float cd, int32_t cci) const
+    {
+        bool hit = false;
+        knn_each_register<R>([&](auto r) __attribute__((always_inline)) { hit = hit || (d[r] == cd && i[r] == cci); });
+        return __ballot(hit);
+    }
+    // (cd, cci), wave-uniform and not in the list, goes to its sorted place; the entries behind it move one place up, the last one falls out
+    __device__ __forceinline__ void insert(int lane, float cd, int32_t cci)
+    {
+        int pos = 0;  // sorted list: the entries below pos are the smaller ones
+        knn_each_register<R>([&](auto r) __attribute__((always_inline)) { pos += __popcll(__ballot(knn_less(d[r], i[r], cd, cci))); });
+        float   up_d[R];
+        int32_t up_i[R];
+        knn_each_register<R>([&](auto r) __attribute__((always_inline)) {
+            up_d[r] = __shfl_up(d[r], 1);
+            up_i[r] = __shfl_up(i[r], 1);
+            if constexpr (r > 0) {  // lane 0 takes the last entry of the register below
+                const float   carry_d = wave_read(d[r - 1], 63);
+                const int32_t carry_i = wave_read(i[r - 1], 63);
+                if (lane == 0) { up_d[r] = carry_d; up_i[r] = carry_i; }
+            }
+        });
+        knn_each_register<R>([&](auto r) __attribute__((always_inline)) {
+            if (64 * r + lane == pos) { d[r] = cd; i[r] = cci; }
+            else if (64 * r + lane > pos) { d[r] = up_d[r]; i[r] = up_i[r]; }
+        });
+    }
+};
+
+// The 64 R smallest of (sorted list L, empty entries (inf, max)) and (64 unsorted candidates in d/ci, the ones that do not count set to (inf, max)),
+// sorted ascending over L again: bitonic sort of the candidates as in knn_sort_merge, then one register of the list at a time — its elementwise
+// minimum with the reversed candidates holds the 64 smallest of the two runs, the maximum the 64 largest, both bitonic; the minimum is merged into
+// the register (6 stages), the maximum is merged (6 stages) and carried to the next register as its candidates.
+// `empty`: the list holds nothing yet (uniform) — the sorted candidates ARE register 0
+template <int R>
+__device__ __forceinline__ void knn_sort_merge_wide(KnnList<R>& L, float d, int32_t ci, bool empty)
+{
+#pragma unroll
+    for (int size = 2; size <= 64; size <<= 1) {
+        const bool up = (lane_id() & size) == 0 || size == 64;
+#pragma unroll
+        for (int stride = size >> 1; stride > 0; stride >>= 1) knn_cmpx(d, ci, stride, up);
+    }
+    if (empty) {
+        L.d[0] = d;
+        L.i[0] = ci;
+        return;
+    }
+    bool live = true;  // (uniform) the carried run still holds a candidate
+    knn_each_register<R>([&](auto r) __attribute__((always_inline)) {
+        if (live) {
+            const float   rd = __shfl(d, 63 - lane_id());
+            const int32_t ri = __shfl(ci, 63 - lane_id());
+            const bool    less = knn_less(rd, ri, L.d[r], L.i[r]);
+            d = less ? L.d[r] : rd;
+            ci = less ? L.i[r] : ri;
+            if (less) { L.d[r] = rd; L.i[r] = ri; }
+#pragma unroll
+            for (int stride = 32; stride > 0; stride >>= 1) knn_cmpx(L.d[r], L.i[r], stride, true);
+            if constexpr (r + 1 < R) {
+                live = __ballot(ci != 0x7fffffff) != 0;  // (no point has the index max: only empty entries)
+                if (live) {
+#pragma unroll
+                    for (int stride = 32; stride > 0; stride >>= 1) knn_cmpx(d, ci, stride, true);
+                }
+            }
+        }
+    });
+}
+
+// one query per wavefront: the k nearest of p, 64 (R - 1) < k <= 64 R; `done(L, cnt)` consumes the list where it lies (KnnList<R>), the first cnt (uniform)
+// entries found, ascending by (distance, index); returns the candidates measured
+template <int R, class Epilogue>
+__device__ __forceinline__ uint32_t nn_knn_walk_list(const NnGrid2Dev& g, const float4 p, int k, Epilogue&& done)
 {
     const int    lane = lane_id();
-    float        td = INFINITY;     // list entry of this lane
-    int32_t      ti = 0x7fffffff;
+    float        td[R];  // list entries of this lane
+    int32_t      ti[R];
+    KnnList<R>   L{td, ti};
+    L.clear();
     float        kth_d = INFINITY;  // current k-th entry (uniform); (inf, max) while the list is not full
     int32_t      kth_i = 0x7fffffff;
     int          cnt = 0;
@@ -2661,10 +2771,11 @@ __device__ __forceinline__ uint32_t nn_knn_walk(const NnGrid2Dev& g, const float
                 n_cand += static_cast<uint32_t>(__popcll(__ballot(valid)));
                 uint64_t   m = __ballot(beats);
                 if (!again && __popcll(m) >= kKnnSortMin) {  // many at once (the first steps of a query): sort + merge
-                    knn_sort_merge(td, ti, beats ? d : INFINITY, beats ? ci : 0x7fffffff, cnt == 0);
-                    if (lane >= k) { td = INFINITY; ti = 0x7fffffff; }
+                    if constexpr (R == 1) knn_sort_merge(L.d[0], L.i[0], beats ? d : INFINITY, beats ? ci : 0x7fffffff, cnt == 0);
+                    else knn_sort_merge_wide(L, beats ? d : INFINITY, beats ? ci : 0x7fffffff, cnt == 0);
+                    L.trim(lane, k);
                     cnt = min(k, cnt + static_cast<int>(__popcll(m)));
-                    if (cnt == k) { kth_d = wave_read(td, k - 1); kth_i = wave_read(ti, k - 1); }
+                    if (cnt == k) L.kth(k, kth_d, kth_i);
                     m = 0;
                 }
                 while (m) {
@@ -2673,16 +2784,11 @@ __device__ __forceinline__ uint32_t nn_knn_walk(const NnGrid2Dev& g, const float
                     const float   cd = wave_read(d, src);  // (scalar: the candidate is the same for every lane)
                     const int32_t cci = wave_read(ci, src);
                     if (!knn_less(cd, cci, kth_d, kth_i)) continue;  // the k-th entry moved since the ballot
-                    if (again && __ballot(td == cd && ti == cci)) continue;       // met on a finer level already
-                    const bool    mine_less = knn_less(td, ti, cd, cci);
-                    const int     pos = __popcll(__ballot(mine_less));  // sorted list: the lanes below pos hold the smaller entries
-                    const float   up_d = __shfl_up(td, 1);
-                    const int32_t up_i = __shfl_up(ti, 1);
-                    if (lane == pos) { td = cd; ti = cci; }
-                    else if (lane > pos) { td = up_d; ti = up_i; }
-                    if (lane >= k) { td = INFINITY; ti = 0x7fffffff; }
+                    if (again && L.holds(cd, cci)) continue;         // met on a finer level already
+                    L.insert(lane, cd, cci);
+                    L.trim(lane, k);
                     if (cnt < k) ++cnt;
-                    if (cnt == k) { kth_d = wave_read(td, k - 1); kth_i = wave_read(ti, k - 1); }
+                    if (cnt == k) L.kth(k, kth_d, kth_i);
                 }
             };
             // the candidates of up to 64 ranges of lv.sorted, lane j holding range [qb, qb + ql): consumed as ONE list, 64 candidates a step whatever the
@@ -2816,8 +2922,14 @@ __device__ __forceinline__ uint32_t nn_knn_walk(const NnGrid2Dev& g, const float
             }
         }
     }
-    done(td, ti, cnt);
+    done(L, cnt);
     return n_cand;
+}
+// the narrow walk, k <= 64: `done(td, ti, cnt)` consumes the list where it lies — entry j in lane j (td squared distance, ti index)
+template <class Epilogue>
+__device__ __forceinline__ uint32_t nn_knn_walk(const NnGrid2Dev& g, const float4 p, int k, Epilogue&& done)
+{
+    return nn_knn_walk_list<1>(g, p, k, [&](const KnnList<1>& L, int cnt) { done(L.d[0], L.i[0], cnt); });
 }
 // ... written to row i of idx / sqd
 __device__ __forceinline__ uint32_t nn_knn_query(const NnGrid2Dev& g, const float4 p, uint32_t i, int k, int32_t* __restrict__ idx, float* __restrict__ sqd)
@@ -2845,10 +2957,36 @@ __global__ __launch_bounds__(256) void nn_knn_kernel(NnGrid2Dev g, const float4*
     if (stats != nullptr && lane_id() == 0 && n_cand) atomicAdd(stats, static_cast<unsigned long long>(n_cand));
 }
 
+// The wide search, 64 (R - 1) < k <= 64 R for R = 2 .. 4: the same walk on a list of R entries per lane (KnnList<R>); rows as nn_knn_kernel writes them.
+#ifndef MRGFE_KNN_WIDE_WAVES
+#define MRGFE_KNN_WIDE_WAVES 4  // 128 VGPRs: the 2 R list registers, their shifted copies and the merge's carried run beside the walk's state, nothing in scratch
+#endif
+template <int R>
+__attribute__((amdgpu_waves_per_eu(MRGFE_KNN_WIDE_WAVES)))
+__global__ __launch_bounds__(256) void nn_knn_wide_kernel(NnGrid2Dev g, const float4* __restrict__ q, uint32_t n, int k, int32_t* __restrict__ idx, float* __restrict__ sqd,
+                                                           unsigned long long* __restrict__ stats)
+{
+    static_assert(R >= 2 && 64 * R <= kKnnMaxK, "two to four entries per lane");
+    const uint32_t i = (blockIdx.x * 256u + threadIdx.x) >> 6;
+    if (i >= n) return;  // uniform per wave
+    const uint32_t n_cand = nn_knn_walk_list<R>(g, q[i], k, [&](const KnnList<R>& L, int cnt) {
+        const int lane = lane_id();
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int j = 64 * r + lane;
+            if (j < k) {
+                idx[size_t(i) * k + j] = j < cnt ? L.i[r] : -1;
+                sqd[size_t(i) * k + j] = j < cnt ? L.d[r] : -1.0f;
+            }
+        }
+    });
+    if (stats != nullptr && lane_id() == 0 && n_cand) atomicAdd(stats, static_cast<unsigned long long>(n_cand));
+}
+
 int NnGrid::knn_device(mrgfe_ctx* ctx, const float4* d_q, size_t n, int k, int32_t* d_idx, float* d_sqd)
 {
     if (!built_) { set_error("NnGrid::knn before build"); return MRGFE_ERR_STATE; }
-    if (k < 1 || k > 64) { set_error("NnGrid::knn: k must be in [1, 64]"); return MRGFE_ERR_INVALID; }
+    if (k < 1 || k > kKnnMaxK) { set_error("NnGrid::knn: k must be in [1, 256]"); return MRGFE_ERR_INVALID; }
     if (n == 0) return MRGFE_OK;
     if (n > (0xffffffffu >> 6)) { set_error("NnGrid::knn: too many queries"); return MRGFE_ERR_INVALID; }
     const uint32_t nn = static_cast<uint32_t>(n);
@@ -2863,7 +3001,11 @@ int NnGrid::knn_device(mrgfe_ctx* ctx, const float4* d_q, size_t n, int k, int32
         MRGFE_HIP_CHECK(hipMemsetAsync(d_cand, 0, 8, ctx->stream));
     }
     MRGFE_HIP_CHECK(hipEventRecord(ks.ev[0], ctx->stream));
-    hipLaunchKernelGGL(nn_knn_kernel, dim3((nn + 3) / 4), dim3(256), 0, ctx->stream, h_, d_q, nn, k, d_idx, d_sqd, d_cand);
+    const dim3 blocks((nn + 3) / 4);
+    if (k <= 64) hipLaunchKernelGGL(nn_knn_kernel, blocks, dim3(256), 0, ctx->stream, h_, d_q, nn, k, d_idx, d_sqd, d_cand);
+    else if (k <= 128) hipLaunchKernelGGL(nn_knn_wide_kernel<2>, blocks, dim3(256), 0, ctx->stream, h_, d_q, nn, k, d_idx, d_sqd, d_cand);
+    else if (k <= 192) hipLaunchKernelGGL(nn_knn_wide_kernel<3>, blocks, dim3(256), 0, ctx->stream, h_, d_q, nn, k, d_idx, d_sqd, d_cand);
+    else hipLaunchKernelGGL(nn_knn_wide_kernel<4>, blocks, dim3(256), 0, ctx->stream, h_, d_q, nn, k, d_idx, d_sqd, d_cand);
     MRGFE_HIP_CHECK(hipGetLastError());
     MRGFE_HIP_CHECK(hipEventRecord(ks.ev[1], ctx->stream));
     ks.queries = n;

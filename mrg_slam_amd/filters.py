@@ -108,6 +108,7 @@ class StatisticalOutlierRemoval(_Filter):
         self._mean_k, self._stddev = 30, 1.2
 
     def setMeanK(self, k):
+        """1 <= k <= 255 (k + 1 entries, the point itself first, must fit the 256-entry neighbour list); checked by ``filter()``."""
         self._mean_k = int(k)
 
     def setStddevMulThresh(self, s):
@@ -201,7 +202,8 @@ class InformationMatrixCalculator:
 
 def knn(cloud, queries, k: int, ctx: Context | None = None):
     """pcl::search::KdTree::nearestKSearch(pt, k) for a cloud of queries: (indices [nq, k], squared distances [nq, k]),
-    ascending by (distance, index), -1 where the cloud has fewer than k points."""
+    ascending by (distance, index), -1 where the cloud has fewer than k points.  1 <= k <= 256 (the library's limit: up to 64 on the
+    narrow kernel, 65..256 on the wide one); anything else raises ``MrgfeError`` with ``ERR_INVALID``."""
     ctx = ctx or default_context()
     c, q = _cloud(cloud), _cloud(queries)
     idx, sqd = np.empty((len(q), k), dtype=np.int32), np.empty((len(q), k), dtype=np.float32)
