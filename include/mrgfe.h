@@ -147,12 +147,20 @@ int  mrgfe_ctx_set_byte_layouts(mrgfe_ctx* ctx, int on);
 int  mrgfe_ctx_set_bfgs_batches(mrgfe_ctx* ctx, int on);
 /* STATISTICAL outlier removal behind downsample NONE or APPROX_VOXELGRID on the device-driven prefilter chain (off by default).  on = 1: from the next
  * chain call on this context (mrgfe_prefilter[_device | _records], mrgfe_scan_callback[_device | _records]) those chains wait for the device once, as
- * VOXELGRID -> STATISTICAL does (statistical_mean_k in 1..63): without a voxel leaf to take it from, the cell edge of the filter's k-NN grid is chosen ON THE
+ * VOXELGRID -> STATISTICAL does (statistical_mean_k in 1..63, or 1..255 with mrgfe_ctx_set_wide_statistical_chains on as well): without a voxel leaf to take it from, the cell edge of the filter's k-NN grid is chosen ON THE
  * DEVICE from the cloud's own density, in a fixed sequence of launches (mrgfe_ctx_sor_grid_stats reports the choice).  The search does not depend on the
  * edge: the output is that of the host-driven passes bit for bit, and an unusual scan is handed back to them (mrgfe_ctx_prefilter_stats route 2).  Off:
  * those chains run the host-driven passes (route 0) as they always did.  VOXELGRID -> STATISTICAL is the same either way.  Contexts made like this one
  * (mrgfe_ctx_create_like) inherit the switch.  NULL ctx: MRGFE_ERR_INVALID. */
 int  mrgfe_ctx_set_statistical_chains(mrgfe_ctx* ctx, int on);
+/* statistical_mean_k 64..255 on the device-driven prefilter chain (off by default).  on = 1: from the next chain call on this context (mrgfe_prefilter[_device
+ * | _records], mrgfe_scan_callback[_device | _records]) a STATISTICAL chain with statistical_mean_k in 64..255 is served where the same chain with 1..63 is:
+ * behind VOXELGRID always, behind NONE / APPROX_VOXELGRID when mrgfe_ctx_set_statistical_chains is on too.  It then waits for the device once and writes no
+ * [points][mean_k + 1] neighbour rows: the mean distances come out of a search that keeps up to four list entries per lane in registers.  The output is that
+ * of the host-driven passes bit for bit, and an unusual scan is handed back to them (mrgfe_ctx_prefilter_stats route 2), as for 1..63.  Off: such chains run
+ * the host-driven passes (route 0) as they always did.  statistical_mean_k 1..63 is served the same either way; 256 and more stays MRGFE_ERR_INVALID.
+ * Contexts made like this one (mrgfe_ctx_create_like) inherit the switch.  NULL ctx: MRGFE_ERR_INVALID. */
+int  mrgfe_ctx_set_wide_statistical_chains(mrgfe_ctx* ctx, int on);
 /* HIP stream of the context as an opaque pointer (hipStream_t), for callers that order their own work after it */
 void* mrgfe_ctx_stream(mrgfe_ctx* ctx);
 /* Measurement hook ("1-NN fitness on hash grid: N (16 + 27*8 + m*16)"): what the last getFitnessScore pass on this context
@@ -169,7 +177,7 @@ int mrgfe_ctx_fitness_stats(mrgfe_ctx* ctx, double out[11]);
 int mrgfe_ctx_knn_stats(mrgfe_ctx* ctx, double out[5]);
 /* Which route served the last prefilter chain call on this context (mrgfe_prefilter[_device], mrgfe_scan_callback[_device]):
  * out[0] = route — 0 the host-driven passes (every stage hands its point count to the host), 1 the device-driven chain (one wait; [distance filter] ->
- * NONE, VOXELGRID or APPROX_VOXELGRID -> NONE or RADIUS, and VOXELGRID -> STATISTICAL with statistical_mean_k in 1..63; STATISTICAL behind NONE or
+ * NONE, VOXELGRID or APPROX_VOXELGRID -> NONE or RADIUS, and VOXELGRID -> STATISTICAL with statistical_mean_k in 1..63, 64..255 too when mrgfe_ctx_set_wide_statistical_chains is on; STATISTICAL behind NONE or
  * APPROX_VOXELGRID stays on route 0 unless mrgfe_ctx_set_statistical_chains is on), 2 the device-driven chain attempted and handed back to the host-driven passes (same output); out[1] = the
  * device-driven chain's anomaly word (routes 1 and 2): 1 a stage in front of another one left no (finite) point, 2 PCL's "leaf size too small"
  * pass-through, 4 no voxel, 8 a sum of the statistical filter's threshold could have depended on the order of addition, 16 the host's re-check of
@@ -354,7 +362,8 @@ int  mrgfe_prefilter_records(mrgfe_ctx* ctx, const mrgfe_prefilter_params* param
  * the records, deskews, transforms, stores the packed cloud and (on the usual chains) is the distance filter's first pass; nothing comes down but
  * the chain's status words and, for the host form, the filtered cloud; every chain but STATISTICAL behind NONE or APPROX_VOXELGRID (unless
  * mrgfe_ctx_set_statistical_chains is on), or with statistical_mean_k outside 1..63, waits for the device once (mrgfe_ctx_prefilter_stats says which route served a call).
- * statistical_mean_k 64 .. 255 is served by the host-driven passes (route 0, the wide k-NN kernel); 256 and more is MRGFE_ERR_INVALID.
+ * statistical_mean_k 64 .. 255 is served by the host-driven passes (route 0, the wide k-NN kernel) unless mrgfe_ctx_set_wide_statistical_chains is on — then it
+ * waits once like 1..63; 256 and more is MRGFE_ERR_INVALID.
  * The output equals, bit for bit and in order, mrgfe_ingest_pointcloud2 -> mrgfe_deskew (if `deskew`) -> mrgfe_transform_cloud (if `transform`)
  * -> mrgfe_prefilter[_device] for the same inputs.  The reference's quirks are kept: deskewing counts i and n = width * height over the UNFILTERED
  * cloud (:286), non-finite points included; the transform leaves non-finite points as they are; the distance filter is what drops them. */

@@ -91,6 +91,9 @@ int mrgfe_dbg_prefilter_output(mrgfe_ctx* ctx, int* remembered, size_t* n, float
  * before it touches the device, and the statistics calls, against a real handle.  Every call that reaches the device fails on it with MRGFE_ERR_HIP;
  * mrgfe_ctx_destroy frees it. */
 int mrgfe_dbg_ctx_create_detached(mrgfe_ctx** out);
+/* mrgfe_ctx_set_wide_statistical_chains as the context holds it: *on = 1 or 0 (no device is touched).  inherited non-NULL: a context is made like this one
+ * on its device, as the library makes its helper contexts (mrgfe_ctx_create_like), *inherited = the switch it received, and it is destroyed again. */
+int mrgfe_dbg_wide_statistical_chains(mrgfe_ctx* ctx, int* on, int* inherited);
 /* StatisticalOutlierRemoval's threshold from the mean distances dist[n] and the flags valid[n] (1: all mean_k neighbours were found): out[0] = sum of
  * dist, out[1] = sum of float(dist * dist), out[2] = sum of valid, out[3] = mean + stddev_mul * sqrt(variance) as the reference computes it, out[4] = 1
  * iff both sums are certified to have the same bits in every order of addition (csrc/sor_threshold.h: the sum is below 2^(q + 52) for 2^q the lowest

@@ -241,6 +241,7 @@ SIGNATURES = {
     "mrgfe_ctx_set_byte_layouts": (C.c_int, [_vp, C.c_int]),
     "mrgfe_ctx_set_bfgs_batches": (C.c_int, [_vp, C.c_int]),
     "mrgfe_ctx_set_statistical_chains": (C.c_int, [_vp, C.c_int]),
+    "mrgfe_ctx_set_wide_statistical_chains": (C.c_int, [_vp, C.c_int]),
     "mrgfe_ctx_sor_grid_stats": (C.c_int, [_vp, _dp]),
     "mrgfe_ctx_stream": (_vp, [_vp]),
     "mrgfe_ctx_fitness_stats": (C.c_int, [_vp, _dp]),
@@ -441,6 +442,7 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_set_sor_grid_rule": (C.c_int, [C.c_float, C.c_double, C.c_int]),
     "mrgfe_dbg_prefilter_output": (C.c_int, [_vp, _ip, _szp, _fp]),
     "mrgfe_dbg_ctx_create_detached": (C.c_int, [C.POINTER(_vp)]),
+    "mrgfe_dbg_wide_statistical_chains": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mrgfe_dbg_sor_threshold": (C.c_int, [_vp, _fp, _u32p, C.c_size_t, C.c_double, C.c_int, _dp]),
     "mrgfe_dbg_floor_ransac": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(C.c_int), _fp, _ip, _szp, _ip, _ip]),
     "mrgfe_dbg_floor_normals": (C.c_int, [_vp, _fp, C.c_size_t, C.c_size_t, C.c_double, _fp, C.POINTER(C.c_uint8)]),
@@ -587,6 +589,12 @@ class Context:
         """``mrgfe_ctx_set_statistical_chains``: the prefilter chains NONE -> STATISTICAL and APPROX_VOXELGRID -> STATISTICAL on this context wait for the
         device once (route 1), the k-NN grid's cell edge chosen on the device; off, the default, they run the host-driven passes.  Same output."""
         check(lib().mrgfe_ctx_set_statistical_chains(self._h, int(bool(on))))
+
+    def set_wide_statistical_chains(self, on: bool = True):
+        """``mrgfe_ctx_set_wide_statistical_chains``: STATISTICAL chains with ``statistical_mean_k`` 64..255 on this context are served where 1..63 is
+        (behind VOXELGRID; behind NONE / APPROX_VOXELGRID with :meth:`set_statistical_chains` too): one device wait (route 1) and no neighbour rows;
+        off, the default, they run the host-driven passes.  Same output."""
+        check(lib().mrgfe_ctx_set_wide_statistical_chains(self._h, int(bool(on))))
 
     def sor_grid_stats(self) -> dict:
         """The statistical filter's k-NN grid of the last prefilter chain call on this context (``mrgfe_ctx_sor_grid_stats``): ``sized`` the device chose

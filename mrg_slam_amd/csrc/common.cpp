@@ -485,6 +485,7 @@ static int ctx_create(int device_id, int high_priority, int reserve_cus, const m
         c->byte_layouts.store(like->byte_layouts.load());
         c->bfgs_batches.store(like->bfgs_batches.load());
         c->statistical_chains.store(like->statistical_chains.load());
+        c->wide_statistical_chains.store(like->wide_statistical_chains.load());
     } else if (reserve_cus == MRGFE_RESERVE_AUTO && c->cu_count < 8) {
         // nothing sensible to split off: a plain context
     } else if (reserve_cus > 0 || reserve_cus == MRGFE_RESERVE_AUTO) {
@@ -559,6 +560,14 @@ int mrgfe_ctx_set_statistical_chains(mrgfe_ctx* ctx, int on)
     if (!ctx) { mrgfe::set_error("mrgfe_ctx_set_statistical_chains: NULL context"); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(ctx);  // (behind whatever call holds the context: the next chain call sees the new value)
     ctx->statistical_chains.store(on != 0);
+    return MRGFE_OK;
+}
+
+int mrgfe_ctx_set_wide_statistical_chains(mrgfe_ctx* ctx, int on)
+{
+    if (!ctx) { mrgfe::set_error("mrgfe_ctx_set_wide_statistical_chains: NULL context"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(ctx);  // (behind whatever call holds the context: the next chain call sees the new value)
+    ctx->wide_statistical_chains.store(on != 0);
     return MRGFE_OK;
 }
 
@@ -640,6 +649,20 @@ int mrgfe_dbg_ctx_create_detached(mrgfe_ctx** out)
     if (!out) { mrgfe::set_error("mrgfe_dbg_ctx_create_detached: out is NULL"); return MRGFE_ERR_INVALID; }
     *out = new (std::nothrow) mrgfe_ctx();
     if (!*out) { mrgfe::set_error("mrgfe_dbg_ctx_create_detached: out of host memory"); return MRGFE_ERR_INVALID; }
+    return MRGFE_OK;
+}
+
+// mrgfe_dbg_wide_statistical_chains (include/mrgfe_debug.h): the switch as the context holds it and as a context made like it (ctx_create_like) receives it
+int mrgfe_dbg_wide_statistical_chains(mrgfe_ctx* ctx, int* on, int* inherited)
+{
+    if (!ctx || !on) { mrgfe::set_error("mrgfe_dbg_wide_statistical_chains: NULL argument"); return MRGFE_ERR_INVALID; }
+    *on = ctx->wide_statistical_chains.load() ? 1 : 0;
+    if (inherited) {
+        mrgfe_ctx* child = nullptr;
+        MRGFE_TRY(mrgfe::ctx_create_like(ctx, &child));
+        *inherited = child->wide_statistical_chains.load() ? 1 : 0;
+        mrgfe_ctx_destroy(child);
+    }
     return MRGFE_OK;
 }
 

@@ -260,6 +260,7 @@ struct mrgfe_ctx {
     bool         zero_copy_uploads = false;   // mrgfe_ctx_set_zero_copy_uploads: clouds in page-locked host memory go up by DMA from the caller's buffer
     std::atomic<bool> bfgs_batches{false};    // mrgfe_ctx_set_bfgs_batches: mrgfe_batch_create on this context takes PCL_GICP_HIP / PCL_GICP_OMP_HIP
     std::atomic<bool> statistical_chains{false};  // mrgfe_ctx_set_statistical_chains: STATISTICAL behind NONE / APPROX_VOXELGRID on the device-driven chain (filters.hip)
+    std::atomic<bool> wide_statistical_chains{false};  // mrgfe_ctx_set_wide_statistical_chains: statistical_mean_k 64..255 on the device-driven chain (filters.hip device_driven_applies)
     std::atomic<bool> byte_layouts{false};    // mrgfe_ctx_set_byte_layouts: PointCloud2 layouts need not be multiples of 4 (read by check_pointcloud2_layout, before the call takes the lock)
     mrgfe::Event ev_fit[4];                     // around the passes of nn_fitness_batch
     int          priority = 0;                  // > 0: streams at the device's highest priority, < 0: at its lowest (throughput work beside latency-critical rounds)

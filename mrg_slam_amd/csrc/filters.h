@@ -34,7 +34,7 @@ struct PrefilterChain {
     double stddev_mul = 1.2;
 };
 // 1: the chains keep their point counts on the device and wait once (default; every chain but the statistical filter behind anything other than a voxel
-// grid — unless the context has mrgfe_ctx_set_statistical_chains on —, or with mean_k outside 1..63), and so does the odometry frame's downsample;
+// grid — unless the context has mrgfe_ctx_set_statistical_chains on —, or with mean_k outside 1..63, 1..255 with mrgfe_ctx_set_wide_statistical_chains on), and so does the odometry frame's downsample;
 // 0: host-driven stages; < 0: query
 int prefilter_set_device_driven(int mode);
 // mrgfe_dbg_set_sor_grid_rule (include/mrgfe_debug.h): the rule of the statistical filter's device-sized k-NN grid, process-wide; a zero restores that default

@@ -1034,7 +1034,8 @@ static NnDeviceDrivenGrid& pf_grid(mrgfe_ctx* ctx)
 }
 
 // The chains the device-driven form serves (the others, and its anomalies, go through the host-driven passes): every [distance] -> downsample ->
-// outlier chain the parameters express, except mean_k beyond a wavefront's list and — unless the context has mrgfe_ctx_set_statistical_chains on — the
+// outlier chain the parameters express, except — unless the context has mrgfe_ctx_set_wide_statistical_chains on — mean_k beyond one list entry per lane
+// (64..255: nn_knn_mean_dd_wide_kernel<R>) and — unless it has mrgfe_ctx_set_statistical_chains on — the
 // statistical filter behind anything but a VoxelGrid: without a leaf there is no rule for the k-NN grid's cell edge that the host could know
 // (sor_cell_edge), so with the switch on the device chooses the edge itself (nn_build_device_sized, sor_sized_grid).
 static int  chain_downsample(const PrefilterChain& ch) { return ch.approx_voxelgrid ? 2 : (ch.voxelgrid ? 1 : 0); }
@@ -1047,7 +1048,10 @@ static bool device_driven_applies(const mrgfe_ctx* ctx, const PrefilterChain& ch
     if (!prefilter_device_driven_mode() || n == 0) return false;
     const int down = chain_downsample(ch);
     if (down != 0 && !(ch.leaf > 0)) return false;
-    if (ch.outlier == 2) return (down == 1 || sor_sized_grid(ctx, ch)) && ch.mean_k >= 1 && ch.mean_k <= 63;  // (mean_k + 1 entries must fit a wavefront's list)
+    if (ch.outlier == 2) {  // (mean_k + 1 entries must fit a wavefront's list: one per lane, or up to four with the wide switch)
+        const int most = ctx->wide_statistical_chains.load(std::memory_order_relaxed) ? 255 : 63;
+        return (down == 1 || sor_sized_grid(ctx, ch)) && ch.mean_k >= 1 && ch.mean_k <= most;
+    }
     return true;
 }
 
@@ -1060,6 +1064,13 @@ static bool device_driven_applies(const mrgfe_ctx* ctx, const PrefilterChain& ch
 // Never below 0.2 m: a leaf of a few centimetres must not cost a table of 10^8 cells.  A cloud whose box needs more than kSorCellsCap cells at this edge
 // sets kNnAnomalyCells and is handed back; 8^3 leaves per cell and 2^24 cells put that beyond PCL's own limit of 2^31 leaves for every leaf >= 0.025 m.
 // A second, coarser level for the far rings was not tried.
+// mean_k 64..255 (mrgfe_ctx_set_wide_statistical_chains) keeps both rules, this one and the device-sized grid's below.  Behind the voxel grid no other
+// number of leaves was measured for them: at eight the wide launch takes 0.09 / 0.12 / 0.39 ms (mean_k 64 / 100 / 255) on the VLP-16 scan's centroids
+// and 0.15 / 0.18 / 0.44 ms on the VLP-64 scan's, 0.3 to 0.6 of the whole call.  Without a leaf the other rules were measured
+// (profiles/prefilter_statistical_wide_summary.md, k-NN launch ms at mean_k 64 / 100 / 255): the VLP-16 scan at the 1 m the target of 128 keeps
+// 0.14 / 0.17 / 0.39, at 0.5 m 0.16 / 0.22 / 0.61, at 2 m 0.19 / 0.22 / 0.49; the VLP-64 scan at the 0.25 m it is halved to 0.56 / 0.70 / 1.74, at
+// 0.5 m (targets 256 and 512) 1.09 / 1.25 / 2.59, at 1 m (1024) 2.11 / 2.33 / 4.41 — four times the neighbours do not ask for larger cells: a cell of
+// the default rule holds ~100 points of the VLP-16 scan, and the dense scan pays for every candidate it measures.  Edges below 0.25 m were not tried.
 constexpr uint32_t kSorCellsCap = (1u << 24) - 1u;  // 24 key bits: three radix passes, as for the radius filter's 2^22 cells
 #ifndef MRGFE_SOR_CELL_LEAVES
 #define MRGFE_SOR_CELL_LEAVES 8.0f

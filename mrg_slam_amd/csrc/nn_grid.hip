@@ -3064,16 +3064,71 @@ __global__ __launch_bounds__(256) void nn_knn_mean_dd_kernel(const NnBuildDev* _
     });
 }
 
+// The wide form, 64 (R - 1) < k1 <= 64 R for R = 2 .. 4 (mean_k 64 .. 255): the same launch, staging and one-level grid as nn_knn_mean_dd_kernel, the walk on
+// R entries per lane (KnnList<R>) and the same epilogue over its registers — entry j lies in lane j & 63 of register j >> 6, so the f64 additions run
+// register by register, lane by lane: ascending j, the reference's order, at most 255 dependent additions behind a search over R times the list.  No [n][k1] rows
+// here either.  sqrtf is taken per lane once per register in front of the reads (empty entries hold +inf and are read only when all k1 were found), and
+// every index into the list is a compile-time constant (knn_each_register): the list stays in registers.
+template <int R>
+__attribute__((amdgpu_waves_per_eu(MRGFE_KNN_WIDE_WAVES)))
+__global__ __launch_bounds__(256) void nn_knn_mean_dd_wide_kernel(const NnBuildDev* __restrict__ d, const float4* __restrict__ q, const Slice* __restrict__ slice, int k1,
+                                                                   float* __restrict__ dist, uint32_t* __restrict__ valid)
+{
+    static_assert(R >= 2 && 64 * R <= kKnnMaxK, "two to four entries per lane");
+    const uint32_t n = slice->n;
+    if (blockIdx.x * 4u >= n) return;  // uniform
+    __shared__ NnGridDev s_g;
+    static_assert(sizeof(NnGridDev) % 4 == 0 && sizeof(NnGridDev) / 4 <= 256, "one word per thread");
+    if (threadIdx.x < sizeof(NnGridDev) / 4) reinterpret_cast<uint32_t*>(&s_g)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&d->lv)[threadIdx.x];
+    __syncthreads();
+    const uint32_t i = (blockIdx.x * 256u + threadIdx.x) >> 6;
+    if (i >= n) return;  // uniform per wave
+    NnGrid2Dev g;
+    {
+        uint32_t w[sizeof(NnGridDev) / 4];
+#pragma unroll
+        for (uint32_t k = 0; k < sizeof(NnGridDev) / 4; ++k) w[k] = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(reinterpret_cast<const uint32_t*>(&s_g)[k])));
+        memcpy(&g.level[0], w, sizeof(NnGridDev));
+        constexpr size_t cs = offsetof(NnGridDev, cell_start) / 4, so = offsetof(NnGridDev, sorted) / 4;
+        g.level[0].cell_start = (const uint32_t*)(const MRGFE_GLOBAL uint32_t*)(static_cast<uintptr_t>(w[cs]) | static_cast<uintptr_t>(w[cs + 1]) << 32);
+        g.level[0].sorted = (const float4*)(const MRGFE_GLOBAL float4*)(static_cast<uintptr_t>(w[so]) | static_cast<uintptr_t>(w[so + 1]) << 32);
+        g.level[0].occ = g.level[0].occ1 = g.level[0].occ2 = nullptr;
+        g.level[1] = g.level[2] = g.level[0];
+        g.n_levels = 1;
+        g.pad = 0;
+    }
+    nn_knn_walk_list<R>(g, q[i], k1, [&](const KnnList<R>& L, int cnt) {
+        float    dm = 0.0f;
+        uint32_t ok = 0;
+        if (cnt == k1) {  // uniform
+            double sum = 0.0;
+            knn_each_register<R>([&](auto r) __attribute__((always_inline)) {
+                const float s = sqrtf(L.d[r]);
+                const int   end = min(k1 - 64 * r, 64);  // (uniform; entries of this register that count: 64 below the last one)
+                for (int j = r == 0 ? 1 : 0; j < end; ++j) sum += static_cast<double>(wave_read(s, j));  // (entry 0 is the query itself)
+            });
+            dm = static_cast<float>(sum / static_cast<double>(k1 - 1));
+            ok = 1;
+        }
+        if (lane_id() == 0) { dist[i] = dm; valid[i] = ok; }
+    });
+}
+
 int nn_knn_mean_device_driven(mrgfe_ctx* ctx, const NnDeviceDrivenGrid& g, const float4* d_q, const Slice* d_slice, uint32_t n_cap, int k1, float* d_dist, uint32_t* d_valid)
 {
-    if (k1 < 2 || k1 > 64) { set_error("nn_knn_mean_device_driven: k + 1 must be in [2, 64]"); return MRGFE_ERR_INVALID; }
+    if (k1 < 2 || k1 > kKnnMaxK) { set_error("nn_knn_mean_device_driven: k + 1 must be in [2, 256]"); return MRGFE_ERR_INVALID; }
     if (n_cap == 0) return MRGFE_OK;
     if (n_cap > (0xffffffffu >> 6)) { set_error("nn_knn_mean_device_driven: too many queries"); return MRGFE_ERR_INVALID; }
     KnnStats& ks = ctx->knn_stats;  // (mrgfe_ctx_knn_stats: HIP events around the launch, as NnGrid::knn_device records them)
     for (auto& e : ks.ev)
         if (!e) MRGFE_HIP_CHECK(hipEventCreate(&e));
     MRGFE_HIP_CHECK(hipEventRecord(ks.ev[0], ctx->stream));
-    hipLaunchKernelGGL(nn_knn_mean_dd_kernel, dim3((n_cap + 3) / 4), dim3(256), 0, ctx->stream, g.desc.as<NnBuildDev>(), d_q, d_slice, k1, d_dist, d_valid);
+    const dim3        blocks((n_cap + 3) / 4);
+    const NnBuildDev* d_g = g.desc.as<NnBuildDev>();
+    if (k1 <= 64) hipLaunchKernelGGL(nn_knn_mean_dd_kernel, blocks, dim3(256), 0, ctx->stream, d_g, d_q, d_slice, k1, d_dist, d_valid);
+    else if (k1 <= 128) hipLaunchKernelGGL(nn_knn_mean_dd_wide_kernel<2>, blocks, dim3(256), 0, ctx->stream, d_g, d_q, d_slice, k1, d_dist, d_valid);
+    else if (k1 <= 192) hipLaunchKernelGGL(nn_knn_mean_dd_wide_kernel<3>, blocks, dim3(256), 0, ctx->stream, d_g, d_q, d_slice, k1, d_dist, d_valid);
+    else hipLaunchKernelGGL(nn_knn_mean_dd_wide_kernel<4>, blocks, dim3(256), 0, ctx->stream, d_g, d_q, d_slice, k1, d_dist, d_valid);
     MRGFE_HIP_CHECK(hipGetLastError());
     MRGFE_HIP_CHECK(hipEventRecord(ks.ev[1], ctx->stream));
     ks.queries = n_cap;  // (the launch's size: the live count is on the device; the chain puts it here behind its wait)

@@ -101,10 +101,11 @@ class OracleOps:
 
 
 class PrefilteringComponent:
-    def __init__(self, params: dict | None = None, ops=None, lookup_transform=None, statistical_chains: bool = False):
+    def __init__(self, params: dict | None = None, ops=None, lookup_transform=None, statistical_chains: bool = False, wide_statistical_chains: bool = False):
         """``statistical_chains``: switch the ops' context to serve ``outlier_removal_method: STATISTICAL`` behind ``downsample_method`` NONE /
-        APPROX_VOXELGRID with one device wait (``Context.set_statistical_chains``; same output).  Ops that hold no context (default: the shared one)
-        get one of their own, so the shared context stays as it is; on ops without a context (the oracle's) the option does nothing."""
+        APPROX_VOXELGRID with one device wait (``Context.set_statistical_chains``; same output).  ``wide_statistical_chains``: the same for
+        ``statistical_mean_k`` 64..255 wherever 1..63 is served that way (``Context.set_wide_statistical_chains``; same output).  Ops that hold no context
+        (default: the shared one) get one of their own, so the shared context stays as it is; on ops without a context (the oracle's) the options do nothing."""
         self.p = dict(DEFAULTS)
         self.p.update(params or {})
         if self.p["downsample_method"] not in ("VOXELGRID", "APPROX_VOXELGRID", "NONE"):
@@ -112,12 +113,15 @@ class PrefilteringComponent:
         if self.p["outlier_removal_method"] not in ("RADIUS", "STATISTICAL", "NONE"):
             raise ValueError(f"unknown outlier_removal_method {self.p['outlier_removal_method']!r}")
         self.ops = ops or HipOps()
-        if statistical_chains and hasattr(self.ops, "ctx"):
+        if (statistical_chains or wide_statistical_chains) and hasattr(self.ops, "ctx"):
             if self.ops.ctx is None:
                 from ._lib import Context
 
                 self.ops.ctx = Context()
-            self.ops.ctx.set_statistical_chains(True)
+            if statistical_chains:
+                self.ops.ctx.set_statistical_chains(True)
+            if wide_statistical_chains:
+                self.ops.ctx.set_wide_statistical_chains(True)
         self.lookup_transform = lookup_transform
         self.imu_queue: list[tuple[float, np.ndarray]] = []  # (stamp, angular velocity): imu_queue_
 
