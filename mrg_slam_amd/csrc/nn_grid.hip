@@ -2889,8 +2889,12 @@ __device__ __forceinline__ uint32_t nn_knn_walk_list(const NnGrid2Dev& g, const 
                     if (cnt == k && static_cast<double>(kth_d) < b * b * (1.0 - 1e-5)) break;
                 }
                 const int      w = 2 * r + 1;
-                const uint32_t total = 2u * static_cast<uint32_t>(w) * static_cast<uint32_t>(w);
-                for (uint32_t t0 = 0; t0 < total; t0 += 64u) {
+                // of the ring's (2r+1)^2 rows only the z-slabs inside the grid are enumerated (a slab is 2w consecutive t): a ring that lies mostly above and
+                // below a flat grid — a grid a few cells high and thousands long, one isolated point kilometres from the rest — costs its inside part
+                // (such a point spent 12 s in the empty rows of its 1250 rings on the coarsest level, 2 (2r+1)^2 / 64 steps each)
+                const uint32_t t_first = (2u * static_cast<uint32_t>(w) * static_cast<uint32_t>(max(r - c[2], 0))) & ~63u;  // (whole steps: the lanes' shares stay as they were)
+                const uint32_t total = 2u * static_cast<uint32_t>(w) * static_cast<uint32_t>(min(c[2] + r, lv.dim[2] - 1) - c[2] + r + 1);
+                for (uint32_t t0 = t_first; t0 < total; t0 += 64u) {
                     const uint32_t t = t0 + lane;
                     uint32_t       qb = 0, qe = 0;
                     if (t < total) {

@@ -118,7 +118,10 @@ class MapCloudStore:
         try:
             self._release_out()
             if getattr(self, "_h", None):
-                lib().mrgfe_map_store_destroy(self._h)
+                # the store borrows its context: when the collector has finalised that first (members of a reference cycle are finalised in no particular
+                # order) the library call would touch freed memory, so the handle is dropped unfreed instead (as OdomHandle.close does)
+                if getattr(getattr(self, "_ctx", None), "_h", None):
+                    lib().mrgfe_map_store_destroy(self._h)
                 self._h = None
         except Exception:  # noqa: BLE001
             pass

@@ -89,7 +89,10 @@ class HipRegistration:
     def __del__(self):
         try:
             if getattr(self, "_h", None):
-                lib().mrgfe_reg_destroy(self._h)
+                # the registration borrows its context: when the collector has finalised that first (members of a reference cycle are finalised in no
+                # particular order) mrgfe_reg_destroy would read the freed context's device, so the handle is dropped unfreed instead (as OdomHandle.close does)
+                if getattr(getattr(self, "_ctx", None), "_h", None):
+                    lib().mrgfe_reg_destroy(self._h)
                 self._h = None
         except Exception:  # noqa: BLE001
             pass
@@ -450,7 +453,8 @@ class BatchMatcher:
     def __del__(self):
         try:
             if getattr(self, "_h", None):
-                lib().mrgfe_batch_destroy(self._h)
+                if getattr(getattr(self, "_ctx", None), "_h", None):  # (the borrowed context is still there: see HipRegistration.__del__)
+                    lib().mrgfe_batch_destroy(self._h)
                 self._h = None
         except Exception:  # noqa: BLE001
             pass

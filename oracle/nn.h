@@ -103,9 +103,11 @@ struct NnGrid {
         for (int a = 0; a < 3; ++a) m = std::max(m, std::max(c[a], dim[a] - 1 - c[a]));
         return m;
     }
-    // k nearest neighbours sorted by (sqdist, index). returns count found (< k only if n < k).
+    // k nearest neighbours sorted by (sqdist, index). returns count found (< k only if fewer than k finite points; 0 for a
+    // non-finite query: it has no cell, and no distance to compare).
     int knn(float x, float y, float z, int k, int* idx, float* sqd) const
     {
+        if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z)) return 0;
         std::vector<std::pair<float, int>> best;  // kept sorted ascending, size <= k
         int c[3];
         coords(x, y, z, c);

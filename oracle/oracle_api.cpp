@@ -53,7 +53,11 @@ void orc_nn1_brute(const float* target, int nt, const float* query, int nq, int*
 {
     for (int i = 0; i < nq; ++i) {
         int best = -1; float bd = 0;
-        for (int j = 0; j < nt; ++j) {
+        const float* qi = query + 4 * i;
+        const bool q_finite = std::isfinite(qi[0]) && std::isfinite(qi[1]) && std::isfinite(qi[2]);
+        for (int j = 0; q_finite && j < nt; ++j) {  // (a non-finite query has no neighbour: -1, as the grid search answers)
+            const float* tj = target + 4 * j;
+            if (!std::isfinite(tj[0]) || !std::isfinite(tj[1]) || !std::isfinite(tj[2])) continue;  // no candidate: the grids leave such points out
             float d = sqdist_f(target[4 * j], target[4 * j + 1], target[4 * j + 2], query[4 * i], query[4 * i + 1], query[4 * i + 2]);
             if (best < 0 || d < bd) { best = j; bd = d; }
         }

@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import grid_cases as G
 from conftest import small_cloud
 from oracle import oracle as orc
 
@@ -20,24 +21,8 @@ def test_voxelgrid_matches_dict_bruteforce(leaf, min_pts):
     c = small_cloud(4000, 5)
     out, status = orc.voxelgrid(c, leaf, min_pts, orc.ORDER_STABLE)
     assert status == 0
-    inv = np.float32(1.0) / np.float32(leaf)
-    ijk = np.floor(c[:, :3] * inv).astype(np.int64)
-    mn, mx = ijk.min(0), ijk.max(0)
-    div = mx - mn + 1
-    lin = (ijk - mn) @ np.array([1, div[0], div[0] * div[1]])
-    cells = {}
-    for i, k in enumerate(lin):
-        cells.setdefault(int(k), []).append(i)
-    exp = []
-    for k in sorted(cells):
-        idx = cells[k]
-        if len(idx) < min_pts:
-            continue
-        acc = np.zeros(4, dtype=np.float32)
-        for i in idx:
-            acc = acc + c[i]  # float32 running sum in point order
-        exp.append(acc / np.float32(len(idx)))
-    exp = np.asarray(exp, dtype=np.float32).reshape(-1, 4)
+    exp, overflow = G.voxelgrid(c, leaf, min_pts)  # the dictionary voxel grid
+    assert not overflow
     np.testing.assert_array_equal(out, exp)
     # std::sort order (PCL's) may permute the additions inside a voxel: same voxels, centroids within float rounding
     out2, _ = orc.voxelgrid(c, leaf, min_pts, orc.ORDER_STD_SORT)
@@ -55,16 +40,11 @@ def test_voxelgrid_overflow_returns_input():
     assert len(out) == 0
 
 
-def _sqd(a, b):
-    d = a[:, None, :3] - b[None, :, :3]
-    return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]  # float32, FLANN L2_Simple order
-
-
 def test_radius_outlier_matches_bruteforce():
     c = small_cloud(1500, 7)
     c[:20, :3] += 100.0  # isolated points
     out, keep = orc.radius_outlier(c, 0.5, 2)
-    cnt = (_sqd(c, c).astype(np.float64) <= 0.25).sum(1)  # includes the point itself
+    cnt = G.radius_count(c, 0.5)  # inclusive, includes the point itself
     np.testing.assert_array_equal(keep, cnt >= 3)
     np.testing.assert_array_equal(out, c[keep])
     # lattice with spacing exactly r: neighbours at sqdist == r^2 count (inclusive compare)
@@ -77,10 +57,9 @@ def test_radius_outlier_matches_bruteforce():
 def test_knn_matches_bruteforce():
     t, q = small_cloud(2500, 11), small_cloud(300, 12, extent=(30, 20, 5))
     idx, sqd = orc.knn(t, q, 5)
-    D = _sqd(q, t)
-    order = np.lexsort((np.broadcast_to(np.arange(D.shape[1]), D.shape), D), axis=1)[:, :5]
+    order, dist = G.knn(t, q, 5)  # full sort by (distance, index)
     np.testing.assert_array_equal(idx, order)
-    np.testing.assert_array_equal(sqd, np.take_along_axis(D, order, 1))
+    np.testing.assert_array_equal(sqd, dist)
     bi, bd = orc.nn1_brute(t, q)
     np.testing.assert_array_equal(bi, idx[:, 0])
     np.testing.assert_array_equal(bd, sqd[:, 0])
@@ -91,11 +70,8 @@ def test_statistical_outlier_matches_numpy():
     c[:10, :3] += 60.0
     k = 10
     out, keep = orc.statistical_outlier(c, k, 1.2)
-    D = np.sort(_sqd(c, c), axis=1)[:, 1 : k + 1]
-    dist = (np.sqrt(D).astype(np.float64).sum(1) / k).astype(np.float32)
-    s, ss = dist.astype(np.float64).sum(), (dist * dist).astype(np.float64).sum()
     n = len(c)
-    thr = s / n + 1.2 * np.sqrt((ss - s * s / n) / (n - 1))
+    _, _, dist, thr = G.statistical_outlier(c, k, 1.2)
     np.testing.assert_array_equal(keep, ~(dist > thr))
     assert not keep[:10].any() and keep.sum() > 0.9 * n
     np.testing.assert_array_equal(out, c[keep])
@@ -108,10 +84,12 @@ def test_fitness_score_semantics():
     s = orc.calc_fitness_score(t, t, rel)
     _, d = orc.nn1_brute(t, orc.transform_points(rel, t))
     assert s == pytest.approx(d.astype(np.float64).mean(), rel=1e-12)
+    assert s == pytest.approx(G.fitness(t, t, rel), rel=1e-12)
     # squared distance is compared with the UN-squared max_range (reference quirk)
     s2 = orc.calc_fitness_score(t, t, rel, max_range=0.001)
     sel = d.astype(np.float64) <= 0.001
     assert s2 == pytest.approx(d[sel].astype(np.float64).mean(), rel=1e-12)
+    assert s2 == pytest.approx(G.fitness(t, t, rel, 0.001), rel=1e-12)
     assert orc.calc_fitness_score(t, t, np.diag([1, 1, 1, 1.0]) + np.eye(4, k=3) * 500, max_range=1.0) == np.finfo(np.float64).max
 
 
@@ -155,25 +133,7 @@ def test_information_matrix_weights_against_numpy():
     np.testing.assert_array_equal(o_inf, inf)
 
 
-def _approx_voxelgrid_py(c, leaf):
-    """pcl::ApproximateVoxelGrid as a plain Python loop over a dict-backed 512-entry history (independent restatement of SURVEY.md A.1)."""
-    inv = np.float32(1.0) / np.float32(leaf)
-    hist, out = {}, []
-    for p in c:
-        ijk = tuple(int(np.floor(np.float32(p[k]) * inv)) for k in range(3))
-        h = (ijk[0] * 7171 + ijk[1] * 3079 + ijk[2] * 4231) & 511
-        e = hist.get(h)
-        if e is not None and e[0] != ijk:
-            out.append(e[1] / np.float32(e[2]))
-            e = None
-        if e is None:
-            e = [ijk, np.zeros(4, np.float32), 0]
-        e[1] = e[1] + p
-        e[2] += 1
-        hist[h] = e
-    for h in sorted(hist):
-        out.append(hist[h][1] / np.float32(hist[h][2]))
-    return np.array(out, dtype=np.float32).reshape(-1, 4)
+_approx_voxelgrid_py = G.approx_voxelgrid  # pcl::ApproximateVoxelGrid as a plain Python loop (independent restatement of SURVEY.md A.1)
 
 
 @pytest.mark.parametrize("leaf", [0.05, 0.3, 2.0, 50.0])
