@@ -320,6 +320,11 @@ int mrgfe_knn(mrgfe_ctx* ctx, const float* cloud_xyzi, size_t n, const float* qu
  * rotation block first), b, the sum of r^T M r over the correspondences (the variants scale it themselves) and their
  * number.  The Jacobian is the one of the registration's method (fast_gicp: left, small_gicp: right perturbation). */
 int mrgfe_gicp_linearize(mrgfe_reg* reg, const double T[16], double H[36], double b[6], double* sum_errors, int* n_correspondences);
+/* compute_error at the pose T: the sum of r^T M r over the correspondences and Mahalanobis matrices FROZEN by the last mrgfe_gicp_linearize or
+ * alignment on this registration, and the number of its terms — the cost a Levenberg-Marquardt trial is judged by, through the launch the
+ * loop makes.  The raw sum (small_gicp's 1/2 is the controller's).  MRGFE_ERR_STATE when nothing was linearised since the clouds were set,
+ * MRGFE_ERR_INVALID for ICP_HIP and the PCL_GICP methods. */
+int mrgfe_gicp_error(mrgfe_reg* reg, const double T[16], double* sum_errors, int* n_terms);
 /* regularised k-NN covariances (row-major 3x3 per point) of the source (which = 0) or target (1) cloud */
 /* PCL_GICP_HIP (tests): the correspondences and Mahalanobis matrices pcl::GICP's search loop finds at transformation_ = T (column-major, guess
  * = identity), and the cost estimateRigidTransformationBFGS minimises at x = (t, euler ZYX) over them: *f, grad[6], number of correspondences */

@@ -319,6 +319,7 @@ SIGNATURES = {
     "mrgfe_knn": (C.c_int, [_vp, _fp, C.c_size_t, _fp, C.c_size_t, C.c_size_t, C.c_int, _ip, _fp]),
     "mrgfe_pclgicp_evaluate": (C.c_int, [_vp, _fp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     "mrgfe_gicp_linearize": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _ip]),
+    "mrgfe_gicp_error": (C.c_int, [_vp, _dp, _dp, _ip]),
     "mrgfe_gicp_covariances": (C.c_int, [_vp, C.c_int, _dp]),
     "mrgfe_ndt_num_leaves": (C.c_int, [_vp]),
     "mrgfe_ndt_grid": (C.c_int, [_vp, _ip, _ip, _ip]),

@@ -504,6 +504,19 @@ int mrgfe_gicp_linearize(mrgfe_reg* reg, const double T[16], double H[36], doubl
     return reg->gicp->linearize(Tr, H, b, sum_errors, n_correspondences);
 }
 
+int mrgfe_gicp_error(mrgfe_reg* reg, const double T[16], double* sum_errors, int* n_terms)
+{
+    if (!reg || !reg->gicp || !T || !sum_errors || !n_terms) { set_error("mrgfe_gicp_error: needs a GICP registration and non-NULL arguments"); return MRGFE_ERR_INVALID; }
+    if (reg->params.method == MRGFE_ICP_HIP) { set_error("mrgfe_gicp_error: ICP_HIP has no linearised cost"); return MRGFE_ERR_INVALID; }
+    if (reg->params.method == MRGFE_PCL_GICP_HIP || reg->params.method == MRGFE_PCL_GICP_OMP_HIP) { set_error("mrgfe_gicp_error: PCL_GICP_HIP minimises with BFGS (mrgfe_pclgicp_evaluate)"); return MRGFE_ERR_INVALID; }
+    if (!reg->has_target || !reg->has_source) { set_error("error: target / source not set"); return MRGFE_ERR_STATE; }
+    MRGFE_LOCK(reg->ctx);
+    MRGFE_TRY(reg->ctx->bind());
+    double Tr[16];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) Tr[r * 4 + c] = T[c * 4 + r];
+    return reg->gicp->error(Tr, sum_errors, n_terms);
+}
+
 int mrgfe_pclgicp_evaluate(mrgfe_reg* reg, const float T[16], const double x[6], double* f, double grad[6], int* n_correspondences)
 {
     if (!reg || !reg->gicp || !T || !x || !f || !grad || !n_correspondences) { set_error("mrgfe_pclgicp_evaluate: NULL argument"); return MRGFE_ERR_INVALID; }

@@ -1059,6 +1059,7 @@ int GicpEngine::set_target(const void* d, size_t n)
     n_tgt_ = n;
     tgt_grid_valid_ = tgt_cov_valid_ = false;
     tgt_grid_view_ = false;
+    linearized_ = false;
     return MRGFE_OK;
 }
 int GicpEngine::set_source(const void* d, size_t n, const float* enclosing_box)
@@ -1066,6 +1067,7 @@ int GicpEngine::set_source(const void* d, size_t n, const float* enclosing_box)
     d_src_ = static_cast<const float4*>(d);
     n_src_ = n;
     src_cov_valid_ = false;
+    linearized_ = false;
     src_box_valid_ = enclosing_box != nullptr;
     if (enclosing_box) std::memcpy(src_box_, enclosing_box, sizeof(src_box_));
     return MRGFE_OK;
@@ -1080,6 +1082,7 @@ int GicpEngine::source_becomes_target()
     tgt_grid_valid_ = tgt_cov_valid_ = true;
     vox_valid_ = false;
     src_cov_valid_ = false;
+    linearized_ = false;
     return MRGFE_OK;
 }
 
@@ -1151,6 +1154,7 @@ void GicpEngine::voxel_grid(double* res, int32_t cmin[3], int32_t dim[3], uint32
 int GicpEngine::build_voxelmap()
 {
     vox_valid_ = false;
+    linearized_ = false;  // (stored correspondences of VGICP name voxels of the map that goes)
     vox_res_ = prm_.voxel_resolution;
     vox_cells_ = vox_occupied_ = 0;
     for (int a = 0; a < 3; ++a) { vox_cmin_[a] = 0; vox_dim_[a] = 1; }
@@ -1230,6 +1234,7 @@ int GicpEngine::prepare_target()
         if (n_tgt_ == 0) MRGFE_TRY(tgt_grid_.build(ctx_, d_tgt_, 0, 1.0f));
         tgt_cov_valid_ = tgt_grid_valid_ = true;
         vox_valid_ = false;
+        linearized_ = false;
     }
     if (prm_.variant == 2 && !vox_valid_) MRGFE_TRY(build_voxelmap());
     return MRGFE_OK;
@@ -1282,6 +1287,7 @@ int GicpEngine::run_linearize(const double T[16], bool, double H[36], double b[6
     if (n_corr) *n_corr = 0;
     for (int t = 0; t < 36; ++t) H[t] = 0;
     for (int t = 0; t < 6; ++t) b[t] = 0;
+    linearized_ = n_src_ == 0;  // (an empty source has no terms to write; otherwise: once the record below has arrived)
     if (n_src_ == 0) return MRGFE_OK;
     hipStream_t    st = ctx_->stream;
     const uint32_t n = static_cast<uint32_t>(n_src_), nblk = (n + 255) / 256;
@@ -1327,6 +1333,7 @@ int GicpEngine::run_linearize(const double T[16], bool, double H[36], double b[6
     MRGFE_TRY(gicp_wait_record(st, h_rec_.as<double>(), tag));
     double r[kGicpStride];
     std::memcpy(r, h_rec_.p, sizeof(r));
+    linearized_ = true;  // the correspondence and linearize kernels ran to their end: d_corr_ / d_mahal_ are whole
     MRGFE_HIP_CHECK(hipEventSynchronize(ctx_->ev1));  // (long passed: the reduction ran behind it)
     float ms = 0;
     MRGFE_HIP_CHECK(hipEventElapsedTime(&ms, ctx_->ev0, ctx_->ev1));
@@ -1343,10 +1350,11 @@ int GicpEngine::run_linearize(const double T[16], bool, double H[36], double b[6
     return MRGFE_OK;
 }
 
-int GicpEngine::run_error(const double T[16], double* err)
+int GicpEngine::run_error(const double T[16], double* err, int* n_terms)
 {
     ++n_error_;
     *err = 0;
+    if (n_terms) *n_terms = 0;
     if (n_src_ == 0) return MRGFE_OK;
     hipStream_t    st = ctx_->stream;
     const uint32_t n = static_cast<uint32_t>(n_src_), nblk = (n + 255) / 256;
@@ -1362,7 +1370,19 @@ int GicpEngine::run_error(const double T[16], double* err)
     MRGFE_HIP_CHECK(hipGetLastError());
     MRGFE_TRY(gicp_wait_record(st, h_rec_.as<double>(), tag));
     *err = h_rec_.as<double>()[0];
+    if (n_terms) *n_terms = static_cast<int>(h_rec_.as<double>()[28]);
     return MRGFE_OK;
+}
+
+int GicpEngine::error(const double T[16], double* err, int* n_terms)
+{
+    if (prm_.variant > 2) { set_error("GICP: no trial cost for this method"); return MRGFE_ERR_INVALID; }
+    if (!linearized_) { set_error("GICP: nothing linearised since the clouds were set"); return MRGFE_ERR_STATE; }
+    MRGFE_TRY(ctx_->bind());
+    const int evals = n_error_;
+    const int rc = run_error(T, err, n_terms);
+    n_error_ = evals;
+    return rc;
 }
 
 int GicpEngine::linearize(const double T[16], double H[36], double b[6], double* err, int* n_corr)

@@ -65,6 +65,9 @@ class GicpEngine {
     int aligned_cloud(float* out_xyzi_host);
     // update_correspondences + linearize at T (row-major double 4x4): tests
     int linearize(const double T[16], double H[36], double b[6], double* err, int* n_corr);
+    // compute_error at T over the correspondences and Mahalanobis matrices of the last linearisation (linearize() or the last one of an align):
+    // the launch of the LM loop's trials; MRGFE_ERR_STATE when the clouds were set since, or nothing was linearised yet.  Not counted in evaluations().
+    int error(const double T[16], double* err, int* n_terms);
     int covariances(int which, double* out9);  // 0 source, 1 target
 
     // k-NN covariances of a packed device cloud into `out` (6 doubles per point), through `grid` (rebuilt over the cloud)
@@ -109,6 +112,7 @@ class GicpEngine {
     DevBuf d_knn_i_, d_knn_d_;
     bool   tgt_grid_valid_ = false, tgt_cov_valid_ = false, src_cov_valid_ = false;
     bool   src_box_valid_ = false;
+    bool   linearized_ = false;  // d_corr_ / d_mahal_ hold a linearisation of the clouds as they are set now
     bool   tgt_grid_view_ = false;  // tgt_grid_ is a view into a batch's NnGridSet
     float  src_box_[6] = {0, 0, 0, 0, 0, 0};
     DevBuf d_tgt_cov_, d_src_cov_, d_corr_, d_mahal_, d_partial_, d_T_;
@@ -142,7 +146,7 @@ class GicpEngine {
     int ensure_ready();
 
     int run_linearize(const double T[16], bool with_jacobian, double H[36], double b[6], double* err, int* n_corr);
-    int run_error(const double T[16], double* err);
+    int run_error(const double T[16], double* err, int* n_terms = nullptr);
 };
 
 // One Levenberg-Marquardt loop of fast_gicp::LsqRegistration as a resumable state machine: the same decisions, in the

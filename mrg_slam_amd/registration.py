@@ -291,6 +291,13 @@ class GicpHip(HipRegistration):
         check(lib().mrgfe_gicp_linearize(self._h, Tc.ctypes.data_as(_dp), H.ctypes.data_as(_dp), b.ctypes.data_as(_dp), C.byref(e), C.byref(n)))
         return H, b, e.value, n.value
 
+    def error(self, T):
+        """compute_error at T over the correspondences and Mahalanobis matrices of the last linearize / align: (sum of r^T M r, terms)."""
+        Tc = np.ascontiguousarray(np.asarray(T, dtype=np.float64).T)
+        e, n = C.c_double(0), C.c_int(0)
+        check(lib().mrgfe_gicp_error(self._h, Tc.ctypes.data_as(_dp), C.byref(e), C.byref(n)))
+        return e.value, n.value
+
     def covariances(self, which="source"):
         n = self._n_src if which == "source" else self._n_tgt
         out = np.empty((n, 3, 3))

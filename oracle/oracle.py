@@ -129,6 +129,8 @@ def lib():
             "orc_gicp_fitness": (C.c_double, [vp, C.c_double]),
             "orc_gicp_covariances": (None, [vp, C.c_int, dp]),
             "orc_gicp_linearize": (C.c_double, [vp, dp, dp, dp, ip]),
+            "orc_gicp_error": (C.c_double, [vp, dp]),
+            "orc_gicp_evaluations": (C.c_int, [vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -566,6 +568,14 @@ class FastGicp:
         H, b, n = np.empty((6, 6)), np.empty(6), C.c_int(0)
         e = lib().orc_gicp_linearize(self._h, _pd(T), _pd(H), _pd(b), C.byref(n))
         return e, H, b, n.value
+
+    def error(self, T):
+        """compute_error at T over the correspondences and Mahalanobis matrices of the last linearize / align (the raw sum)"""
+        return lib().orc_gicp_error(self._h, _pd(np.ascontiguousarray(T, dtype=np.float64)))
+
+    @property
+    def evals(self):
+        return lib().orc_gicp_evaluations(self._h)
 
 
 class SmallGicp(FastGicp):

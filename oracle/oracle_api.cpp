@@ -239,6 +239,9 @@ double orc_gicp_linearize(void* h, const double T_rowmajor[16], double H_rowmajo
 {
     return static_cast<FastGicp*>(h)->linearize(T_rowmajor, H_rowmajor, b, n_corr);
 }
+// compute_error at T over the correspondences and Mahalanobis matrices of the last linearize (of an align, or of the call above)
+double orc_gicp_error(void* h, const double T_rowmajor[16]) { return static_cast<FastGicp*>(h)->compute_error(T_rowmajor); }
+int    orc_gicp_evaluations(void* h) { FastGicp* g = static_cast<FastGicp*>(h); return g->n_linearize + g->n_error_evals; }
 
 }  // extern "C"
 

@@ -16,7 +16,10 @@ DERIVED here:
     correspondence per source point: the voxel its transformed position falls in;
   * pcl::GICP's functor: f = 1/m sum d^T M d, d = R(x) a + t - b, and its gradient in x = (t, phi, theta, psi) for
     R = Rz(psi) Ry(theta) Rx(phi), from products of elementary rotations and their derivatives;
-  * one ICP step: Kabsch (np.linalg.svd of the cross-covariance) over brute-force correspondences, composed onto the guess.
+  * one ICP step: Kabsch (np.linalg.svd of the cross-covariance) over brute-force correspondences, composed onto the guess; a chain of them,
+    every step from the float pose the one before it left (icp_chain);
+  * the se(3) logarithm (se3_log): the matrix logarithm by inverse scaling and squaring (Denman-Beavers square roots, then the power series of
+    log(I + X)), read off along the six generators — the inverse of se3_exp, with no closed form of either.
 
 TAKEN AS GIVEN (conventions, not arithmetic that could be wrong in an interesting way):
   * which neighbours / which correspondence: float32 squared distances in the kernels' order ((dx dx + dy dy) + dz dz), ascending by
@@ -27,7 +30,8 @@ TAKEN AS GIVEN (conventions, not arithmetic that could be wrong in an interestin
   * the order of the 6-vectors: rotation first for H / b, (t, phi, theta, psi) for pcl::GICP;
   * the scaling of pcl::GICP's cost as its functor defines it (f / m, gradient 2 / m), its Mahalanobis rotation (the rotation of the
     float transformation the correspondences were found at) and the float products in its raw moments;
-  * with fewer than k neighbours in the cloud the sums run over those there are and are still divided by k.
+  * with fewer than k neighbours in the cloud the sums run over those there are and are still divided by k;
+  * pcl::IterativeClosestPoint's cumulative FLOAT transformation: the pose an ICP iteration starts from is the float matrix the one before left.
 """
 import numpy as np
 
@@ -96,6 +100,31 @@ def se3_exp(xi):
     for _ in range(s):
         E = E @ E
     return E
+
+
+def se3_log(T):
+    """xi with exp(sum xi_i G_i) = T (rotation angle below pi): square roots until T^(1 / 2^s) is within 0.25 of I, the series of log(I + X) there,
+    times 2^s, projected on the generators (what a float matrix has off se(3) — its rounding — is dropped by the projection)"""
+    A = np.asarray(T, dtype=np.float64)
+    s = 0
+    while np.abs(A - np.eye(4)).sum(1).max() > 0.25 and s < 40:
+        Y, Z = A, np.eye(4)  # Denman-Beavers: Y -> A^(1/2), Z -> A^(-1/2)
+        for _ in range(50):
+            Yn, Zn = 0.5 * (Y + np.linalg.inv(Z)), 0.5 * (Z + np.linalg.inv(Y))
+            done = np.abs(Yn - Y).max() <= 4e-16 * np.abs(Yn).max()
+            Y, Z = Yn, Zn
+            if done:
+                break
+        A = Y
+        s += 1
+    X = A - np.eye(4)
+    L, P = np.zeros((4, 4)), np.eye(4)
+    for n in range(1, 40):
+        P = P @ X
+        L = L + (P / n if n % 2 else -P / n)
+    L = L * 2.0 ** s
+    G = generators()
+    return np.array([(L * G[i]).sum() / (G[i] * G[i]).sum() for i in range(6)])
 
 
 def adjoint(T):
@@ -275,13 +304,19 @@ def pcl_cost(target, source, cov_target, cov_source, T, x, max_distance=2.0):
 
 
 # ---- ICP ----------------------------------------------------------------------------------------------------------------------------
-def icp_step(target, source, guess, max_distance=2.0, reciprocal=False):
-    """One iteration of point-to-point ICP from `guess`: (T_step guess as float64 4 x 4, correspondences)"""
-    cur = transform_float(guess, source)
+def icp_correspondences(target, source, pose, max_distance=2.0, reciprocal=False):
+    """(float query points at `pose`, index of the target point per source point or -1)"""
+    cur = transform_float(pose, source)
     j, _ = nearest(target, cur, max_distance, strict=False)
     if reciprocal:
         back, _ = nearest(cur, np.asarray(target)[np.maximum(j, 0)], max_distance, strict=False)  # the target point's nearest source point
         j[back != np.arange(len(cur))] = -1
+    return cur, j
+
+
+def icp_step(target, source, guess, max_distance=2.0, reciprocal=False):
+    """One iteration of point-to-point ICP from `guess`: (T_step guess as float64 4 x 4, correspondences)"""
+    cur, j = icp_correspondences(target, source, guess, max_distance, reciprocal)
     keep = np.nonzero(j >= 0)[0]
     P, Q = cur[keep].astype(np.float64), np.asarray(target)[j[keep], :3].astype(np.float64)
     mp, mq = P.mean(0), Q.mean(0)
@@ -290,3 +325,12 @@ def icp_step(target, source, guess, max_distance=2.0, reciprocal=False):
     step = np.eye(4)
     step[:3, :3], step[:3, 3] = R, mq - R @ mp
     return step @ np.asarray(guess).astype(np.float32).astype(np.float64), len(keep)
+
+
+def icp_chain(target, source, guess, steps, max_distance=2.0, reciprocal=False):
+    """`steps` iterations, each from the pose the one before left CAST TO FLOAT (the cumulative float transformation): the float poses
+    T_0 = float(guess), T_1, ... T_steps"""
+    poses = [np.asarray(guess).astype(np.float32)]
+    for _ in range(steps):
+        poses.append(icp_step(target, source, poses[-1], max_distance, reciprocal)[0].astype(np.float32))
+    return poses
