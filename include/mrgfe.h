@@ -145,6 +145,19 @@ int  mrgfe_ctx_set_byte_layouts(mrgfe_ctx* ctx, int on);
  * methods as it always did ("offered for single registrations only").  Contexts made like this one (mrgfe_ctx_create_like) inherit the switch.
  * mrgfe_node_create makes its own contexts and keeps refusing the two methods: nodes of BFGS batches are not offered. */
 int  mrgfe_ctx_set_bfgs_batches(mrgfe_ctx* ctx, int on);
+/* NDT sums in the reference's own order (off by default).  on = 1: every registration, evaluation (mrgfe_ndt_evaluate) and batch of MRGFE_NDT_HIP or
+ * MRGFE_PCL_NDT_HIP that STARTS on this context from now on — and what borrows them: the odometry frame, loop detection over a batch — adds its sums as the
+ * reference's host does instead of in a tree: NDT_HIP per point, then point after point (pclomp), PCL_NDT_HIP pair after pair on one chain
+ * (pcl::NormalDistributionsTransform::computeDerivatives / computeHessian, all 36 Hessian entries: the reference's Hessian is not symmetric in its last bits),
+ * every Newton solve through Eigen's two-sided JacobiSVD.  Every evaluation and every alignment then equals the CPU reference bit for bit; the default tree
+ * moves a sum by ~1e-16 relative, which an optimisation that does not settle can amplify past 1e-4 (2 of 1200 random PCL NDT scenes).  The rounds are
+ * stepped by the host, a record per point (NDT_HIP) or per (point, voxel) pair (PCL_NDT_HIP: up to 1.2 GB per 130k-point evaluation) goes through a
+ * workspace bounded by MRGFE_REF_WORKSPACE_MB (default 16384; a round's evaluations are cut into launches that fit), and every sum is one dependent chain of
+ * additions: a 130k-point PCL_NDT_HIP alignment of 8 iterations takes 1.1 s instead of 1.4 ms, NDT_HIP 75 ms instead of 1.3 ms (one MI355X).  A mode for
+ * verification, not for the robot.  Off: everything is as it always was; the process-wide MRGFE_NDT_REFERENCE_ORDER=1 keeps governing
+ * NDT_HIP only and never touches PCL_NDT_HIP.  Contexts made like this one (mrgfe_ctx_create_like) inherit the switch.  mrgfe_node_create makes its own
+ * contexts: nodes are not offered the mode.  NULL ctx: MRGFE_ERR_INVALID. */
+int  mrgfe_ctx_set_ndt_reference_order(mrgfe_ctx* ctx, int on);
 /* STATISTICAL outlier removal behind downsample NONE or APPROX_VOXELGRID on the device-driven prefilter chain (off by default).  on = 1: from the next
  * chain call on this context (mrgfe_prefilter[_device | _records], mrgfe_scan_callback[_device | _records]) those chains wait for the device once, as
  * VOXELGRID -> STATISTICAL does (statistical_mean_k in 1..63, or 1..255 with mrgfe_ctx_set_wide_statistical_chains on as well): without a voxel leaf to take it from, the cell edge of the filter's k-NN grid is chosen ON THE

@@ -60,6 +60,9 @@ int mrgfe_dbg_set_ndt_reference_order(int mode);
  * max_ppt = MRGFE_MAX_PPT (8).  So a pair's f64 sums are a function of its own points and of the round's ppt, and of nothing else.
  * mrgfe_ndt_evaluate with items of `ppt` tiles (1..64, the range MRGFE_PPT accepts), for NDT_HIP and PCL_NDT_HIP: */
 int mrgfe_dbg_ndt_evaluate_ppt(mrgfe_reg* reg, const float T[16], const double p[6], int mode, int ppt, double* score, double grad[6], double hess[36]);
+/* *neighbours = the (point, voxel) pairs the last mrgfe_ndt_evaluate / mrgfe_dbg_ndt_evaluate_ppt of this registration met: what the neighbourhood search
+ * handed over, pairs the range check of updateDerivatives then dropped included (the reference's nb_total of that evaluation); 0 before the first one. */
+int mrgfe_dbg_ndt_eval_neighbours(const mrgfe_reg* reg, double* neighbours);
 /* wg_target and max_ppt of that rule during the following rounds of this process, for the device's plan kernel and the host's plan alike; 0 restores a
  * default.  With wg_target = 2 a batch of a few thousand points runs through ppt 8, 7, ..., 1 as its pairs finish, as a full-size batch does. */
 int mrgfe_dbg_set_ndt_round_shape(int wg_target, int max_ppt);

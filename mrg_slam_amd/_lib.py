@@ -240,6 +240,7 @@ SIGNATURES = {
     "mrgfe_ctx_set_zero_copy_uploads": (C.c_int, [_vp, C.c_int]),
     "mrgfe_ctx_set_byte_layouts": (C.c_int, [_vp, C.c_int]),
     "mrgfe_ctx_set_bfgs_batches": (C.c_int, [_vp, C.c_int]),
+    "mrgfe_ctx_set_ndt_reference_order": (C.c_int, [_vp, C.c_int]),
     "mrgfe_ctx_set_statistical_chains": (C.c_int, [_vp, C.c_int]),
     "mrgfe_ctx_set_wide_statistical_chains": (C.c_int, [_vp, C.c_int]),
     "mrgfe_ctx_sor_grid_stats": (C.c_int, [_vp, _dp]),
@@ -434,6 +435,7 @@ DEBUG_SIGNATURES = {
     "mrgfe_dbg_set_fused_launch": (C.c_int, [C.c_int]),
     "mrgfe_dbg_set_ndt_reference_order": (C.c_int, [C.c_int]),
     "mrgfe_dbg_ndt_evaluate_ppt": (C.c_int, [_vp, _fp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "mrgfe_dbg_ndt_eval_neighbours": (C.c_int, [_vp, _dp]),
     "mrgfe_dbg_set_ndt_round_shape": (C.c_int, [C.c_int, C.c_int]),
     "mrgfe_dbg_reg_ndt_rounds": (C.c_int, [_vp, C.c_int, _u32p, _u32p]),
     "mrgfe_dbg_batch_ndt_rounds": (C.c_int, [_vp, C.c_int, _u32p, _u32p]),
@@ -585,6 +587,13 @@ class Context:
         """``mrgfe_ctx_set_bfgs_batches``: ``BatchMatcher`` on this context takes PCL_GICP_HIP and PCL_GICP_OMP_HIP (the candidates' BFGS loops in lock
         step, records bit-identical to :class:`PclGicpHip`).  Off, the default, such a batch is refused as it always was."""
         check(lib().mrgfe_ctx_set_bfgs_batches(self._h, int(bool(on))))
+
+    def set_ndt_reference_order(self, on: bool = True):
+        """``mrgfe_ctx_set_ndt_reference_order``: :class:`NdtHip` and :class:`PclNdtHip` registrations, ``evaluate`` calls and batches on this context add
+        their sums in the reference's own order (host-stepped record + chain kernels; a full-size alignment takes 75 ms for NDT_HIP and about a second for
+        PCL_NDT_HIP instead of a millisecond or two: a verification mode): bit-identical to the reference-order oracles.
+        Read when an alignment or evaluation starts.  Off, the default, nothing changes."""
+        check(lib().mrgfe_ctx_set_ndt_reference_order(self._h, int(bool(on))))
 
     def set_statistical_chains(self, on: bool = True):
         """``mrgfe_ctx_set_statistical_chains``: the prefilter chains NONE -> STATISTICAL and APPROX_VOXELGRID -> STATISTICAL on this context wait for the

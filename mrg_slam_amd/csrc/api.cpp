@@ -416,6 +416,13 @@ int mrgfe_dbg_ndt_evaluate_ppt(mrgfe_reg* reg, const float T[16], const double p
 {
     return ndt_evaluate_ppt(reg, T, p, mode, ppt, score, grad, hess);
 }
+int mrgfe_dbg_ndt_eval_neighbours(const mrgfe_reg* reg, double* neighbours)
+{
+    if (!reg || !reg->ndt || !neighbours) { set_error("mrgfe_dbg_ndt_eval_neighbours: needs an NDT registration and a non-NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(reg->ctx);
+    *neighbours = reg->ndt->last_eval_neighbours();
+    return MRGFE_OK;
+}
 int mrgfe_dbg_reg_ndt_rounds(const mrgfe_reg* reg, int cap, uint32_t* n_pairs, uint32_t* n_items)
 {
     if (!reg || !reg->ndt || cap < 0) { set_error("mrgfe_dbg_reg_ndt_rounds: needs an NDT registration"); return MRGFE_ERR_INVALID; }

@@ -484,6 +484,7 @@ static int ctx_create(int device_id, int high_priority, int reserve_cus, const m
         c->zero_copy_uploads = like->zero_copy_uploads;
         c->byte_layouts.store(like->byte_layouts.load());
         c->bfgs_batches.store(like->bfgs_batches.load());
+        c->ndt_reference_order.store(like->ndt_reference_order.load());
         c->statistical_chains.store(like->statistical_chains.load());
         c->wide_statistical_chains.store(like->wide_statistical_chains.load());
     } else if (reserve_cus == MRGFE_RESERVE_AUTO && c->cu_count < 8) {
@@ -552,6 +553,14 @@ int mrgfe_ctx_set_bfgs_batches(mrgfe_ctx* ctx, int on)
     if (!ctx) { mrgfe::set_error("mrgfe_ctx_set_bfgs_batches: NULL context"); return MRGFE_ERR_INVALID; }
     MRGFE_LOCK(ctx);  // (behind whatever call holds the context: the next mrgfe_batch_create sees the new value)
     ctx->bfgs_batches.store(on != 0);
+    return MRGFE_OK;
+}
+
+int mrgfe_ctx_set_ndt_reference_order(mrgfe_ctx* ctx, int on)
+{
+    if (!ctx) { mrgfe::set_error("mrgfe_ctx_set_ndt_reference_order: NULL context"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(ctx);  // (behind whatever call holds the context: the next alignment or evaluation sees the new value)
+    ctx->ndt_reference_order.store(on != 0);
     return MRGFE_OK;
 }
 

@@ -259,6 +259,7 @@ struct mrgfe_ctx {
     bool         dma_from_caller = false;     // a zero-copy upload was queued since the last wait for the stream (drain_caller_dma on error paths)
     bool         zero_copy_uploads = false;   // mrgfe_ctx_set_zero_copy_uploads: clouds in page-locked host memory go up by DMA from the caller's buffer
     std::atomic<bool> bfgs_batches{false};    // mrgfe_ctx_set_bfgs_batches: mrgfe_batch_create on this context takes PCL_GICP_HIP / PCL_GICP_OMP_HIP
+    std::atomic<bool> ndt_reference_order{false};  // mrgfe_ctx_set_ndt_reference_order: NDT_HIP and PCL_NDT_HIP on this context sum in the reference's order (read by NdtEngine when an alignment or evaluation starts)
     std::atomic<bool> statistical_chains{false};  // mrgfe_ctx_set_statistical_chains: STATISTICAL behind NONE / APPROX_VOXELGRID on the device-driven chain (filters.hip)
     std::atomic<bool> wide_statistical_chains{false};  // mrgfe_ctx_set_wide_statistical_chains: statistical_mean_k 64..255 on the device-driven chain (filters.hip device_driven_applies)
     std::atomic<bool> byte_layouts{false};    // mrgfe_ctx_set_byte_layouts: PointCloud2 layouts need not be multiples of 4 (read by check_pointcloud2_layout, before the call takes the lock)

@@ -783,8 +783,12 @@ __device__ __forceinline__ uint32_t ndt_point_neighbours(const NdtGridDev& g, bo
 //                count of point i at i % P
 constexpr int kChainTile = 128;   // points per tile (modes 0 / 1): two LDS buffers of 44 rows = 91 KB
 __host__ __device__ constexpr int ref_tile_points(int nnb) { return nnb == 7 ? 16 : (nnb == 1 ? 64 : 4); }  // 112 / 64 / 108 slots per row
-size_t ndt_ref_record_doubles(int mode, size_t n, int nnb)
+// formulation 1 (PCL_NDT_HIP, ndt_pcl_ref_records_kernel below): tiles of kPclRefTile points, kPclRefSlots pair slots per row, pcl_ref_rows(mode) rows
+constexpr int kPclRefTile = 4, kPclRefSlots = kPclRefTile * 27;
+__host__ __device__ constexpr int pcl_ref_rows(int mode) { return mode == 0 ? kNdtAccum : (mode == 1 ? 8 : 37); }
+size_t ndt_ref_record_doubles(int mode, size_t n, int nnb, int formulation)
 {
+    if (formulation == 1) return (n + kPclRefTile - 1) / kPclRefTile * size_t(kPclRefSlots) * pcl_ref_rows(mode);
     if (mode != 2) return (n + kChainTile - 1) / kChainTile * size_t(kChainTile) * kNdtAccum;
     const size_t P = static_cast<size_t>(ref_tile_points(nnb));
     return (n + P - 1) / P * (P * nnb) * 38;
@@ -1127,12 +1131,226 @@ __global__ __launch_bounds__(kChainThreads) void ndt_ref_chain2_kernel(const Ndt
     if (tid == 36) results[(size_t)job.pair * kNdtPartialStride + kNdtNbIndex] = acc;
 }
 
+// ---- PCL_NDT_HIP in the REFERENCE's summation order (opt-in per context: mrgfe_ctx_set_ndt_reference_order) ---------------------------------
+// pcl::NormalDistributionsTransform adds pair after pair on one thread, in computeDerivatives and in computeHessian alike:
+//     score += -d1 exp(..);   g_i += (q.C J_i) e;   H_ij += e ( -d2 (q.C J_i)(q.C J_j) + q.C PH_ij + J_j.C J_i )
+// over the points in cloud order and each point's voxels in the radius search's (distance, index) order.  The f64 items above factor these sums per
+// point and add in a tree; here every pair's increments are computed in the reference's own expression tree (oracle/pcl_ndt.cpp compute_derivatives /
+// compute_hessian: three-term products left to right, unfused, all nine entries of the inverse covariance, the zero second-derivative vectors included)
+// and a chain kernel adds them slot after slot.  Values that the reference computes twice from the same operands (C J_j, q.C J_j, C PH) are computed
+// once: the same operations on the same doubles.  The reference's Hessian is NOT symmetric in its bits (J_j.C J_i against J_i.C J_j, C not symmetric to
+// the last bit): all 36 entries are kept.
+// rec layout of one job (doubles): tiles of kPclRefTile points, S = kPclRefSlots slots per row, R = pcl_ref_rows(mode) rows;  rec[(tile * R + k) * S + s],
+//   s = 0 .. tot - 1: the tile's CONTRIBUTING pairs in (point, neighbourhood) order (a pair the reference's range check drops adds nothing there either),
+//   tot in the tile's header word (cnt workspace);  k: mode 0 — 0 score, 1..6 gradient, 7..42 Hessian;  mode 1 — 0 score, 1..6 gradient;  mode 2 — 0..35
+//   Hessian;  the last row holds the neighbour count of point i at i % kPclRefTile (rejected pairs included: the radius search found them)
+
+__device__ __forceinline__ double ref_dot3(const double a[3], const double b[3])
+{
+#pragma clang fp contract(off)
+    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+}
+__device__ __forceinline__ void ref_matvec3(const double C[9], const double v[3], double out[3])
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) out[r] = C[r * 3 + 0] * v[0] + C[r * 3 + 1] * v[1] + C[r * 3 + 2] * v[2];
+}
+
+__global__ __launch_bounds__(256) void ndt_pcl_ref_records_kernel(const NdtGridDev* __restrict__ grids, const NdtPairDev* __restrict__ pairs, const NdtEvalDev* __restrict__ evals,
+                                                                  const NdtRefJob* __restrict__ jobs, double* __restrict__ rec_base, uint8_t* __restrict__ cnt_base)
+{
+#pragma clang fp contract(off)
+    constexpr int NNB = 27, kP = kPclRefTile, kS = kPclRefSlots;
+    const NdtRefJob job = jobs[blockIdx.y];
+    const NdtPairDev pr = pairs[job.pair];
+    if (blockIdx.x * 256u >= pr.n_src) return;  // (uniform: the grid is as wide as the job with the most tiles)
+    const NdtEvalDev& ev = evals[job.pair];
+    const NdtGridDev  g = grids[pr.grid];
+    __shared__ float s_T[12];
+    if (threadIdx.x < 12) s_T[threadIdx.x] = ev.T[threadIdx.x];
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool     live = i < pr.n_src;  // (a lane past the end stays: its tile's lanes compact their pairs together)
+    const int      mode = static_cast<int>(job.mode), kR = pcl_ref_rows(mode);
+    double* __restrict__ rec = rec_base + job.rec_off;
+    const float4 p = live ? load_point(pr.src + i) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float xt[3];
+    transform_point(s_T, p.x, p.y, p.z, xt[0], xt[1], xt[2]);
+    int32_t ids[NNB];
+#pragma unroll
+    for (int nb = 0; nb < NNB; ++nb) ids[nb] = -1;
+    const uint32_t cnt = live ? ndt_point_neighbours<NNB>(g, /*kdtree=*/true, xt, ids) : 0u;  // (distance, index) order: VoxelGridCovariance::radiusSearch
+    const double gauss_d1 = ev.gauss_d1, gauss_d2 = ev.gauss_d2;
+    // updateDerivatives / updateHessian up to the range check: false when the pair adds nothing
+    auto weight = [&](uint32_t lid, double (&C)[9], double (&q)[3], double& e_raw, double& e) -> bool {
+        const MRGFE_GLOBAL double* __restrict__ Cg = as_global(g.icov64 + (size_t)lid * 9);
+        const MRGFE_GLOBAL double* __restrict__ mean = as_global(g.leaves[lid].mean);
+#pragma unroll
+        for (int t = 0; t < 9; ++t) C[t] = Cg[t];
+        q[0] = static_cast<double>(xt[0]) - mean[0]; q[1] = static_cast<double>(xt[1]) - mean[1]; q[2] = static_cast<double>(xt[2]) - mean[2];
+        double Cq[3];
+        ref_matvec3(C, q, Cq);
+        e_raw = glibc_exp(-gauss_d2 * ref_dot3(q, Cq) / 2);
+        e = gauss_d2 * e_raw;
+        if (e > 1 || e < 0 || e != e) return false;
+        e *= gauss_d1;
+        return true;
+    };
+    // pass 1: how many of the point's pairs contribute; the tile's lanes agree on where each point's pairs go (inclusive scan over the lane group)
+    uint32_t used = 0;
+#pragma unroll 1
+    for (int nb = 0; nb < NNB; ++nb) {
+        if (ids[nb] < 0) continue;
+        double C[9], q[3], e_raw, e;
+        used += weight(static_cast<uint32_t>(ids[nb]), C, q, e_raw, e) ? 1u : 0u;
+    }
+    uint32_t incl = used;
+#pragma unroll
+    for (int d = 1; d < kP; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, kP);
+        if ((threadIdx.x & (kP - 1)) >= static_cast<uint32_t>(d)) incl += up;
+    }
+    const uint32_t off = incl - used, tot = __shfl(incl, kP - 1, kP);
+    double* __restrict__ tile_rec = rec + (size_t)(i / kP) * (size_t)(kR * kS);
+    // (a tile whose first point lies past the end of the cloud does not exist: nothing of it is written; dead lanes of the last tile write nothing either)
+    if ((threadIdx.x & (kP - 1)) == 0 && live) reinterpret_cast<uint32_t*>(cnt_base + job.cnt_off)[i / kP] = tot;
+    if (live) tile_rec[(kR - 1) * kS + (i % kP)] = static_cast<double>(cnt);
+    if (!used) return;
+    // computePointDerivatives(x): the columns of point_jacobian_ and the vectors of point_hessian_ (zero, a .. f)
+    const double x[3] = {p.x, p.y, p.z};
+    double xj[8], xh[15];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) xj[r] = ev.j_ang_d[r][0] * x[0] + ev.j_ang_d[r][1] * x[1] + ev.j_ang_d[r][2] * x[2];
+#pragma unroll
+    for (int r = 0; r < 15; ++r) xh[r] = ev.h_ang_d[r][0] * x[0] + ev.h_ang_d[r][1] * x[1] + ev.h_ang_d[r][2] * x[2];
+    const double J[6][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}, {0.0, xj[0], xj[1]}, {xj[2], xj[3], xj[4]}, {xj[5], xj[6], xj[7]}};
+    const double PH[7][3] = {{0.0, 0.0, 0.0}, {0.0, xh[0], xh[1]}, {0.0, xh[2], xh[3]}, {0.0, xh[4], xh[5]}, {xh[6], xh[7], xh[8]}, {xh[9], xh[10], xh[11]}, {xh[12], xh[13], xh[14]}};
+    const int h0 = mode == 0 ? 7 : 0;  // first Hessian row
+    uint32_t slot = off;
+#pragma unroll 1
+    for (int nb = 0; nb < NNB; ++nb) {
+        if (ids[nb] < 0) continue;
+        double C[9], q[3], e_raw, e;
+        if (!weight(static_cast<uint32_t>(ids[nb]), C, q, e_raw, e)) continue;
+        if (slot >= static_cast<uint32_t>(kS)) break;  // cannot happen (at most 27 pairs per point); keeps a write inside the tile
+        double cov[6][3], qc[6];  // cov_dxd_pi = C * J_i and q . cov_dxd_pi
+#pragma unroll
+        for (int a = 0; a < 6; ++a) { ref_matvec3(C, J[a], cov[a]); qc[a] = ref_dot3(q, cov[a]); }
+        if (mode != 2) {
+            tile_rec[slot] = -gauss_d1 * e_raw;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) tile_rec[(1 + a) * kS + slot] = qc[a] * e;
+        }
+        if (mode != 1) {
+            double qCH[7];  // q . (C * point_hessian_ block)
+#pragma unroll
+            for (int k = 0; k < 7; ++k) { double CH[3]; ref_matvec3(C, PH[k], CH); qCH[k] = ref_dot3(q, CH); }
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = 0; b < 6; ++b) {
+                    // block (a, b) of point_hessian_, a, b >= 3: a b c / b d e / c e f; zero elsewhere
+                    const int lo = a < b ? a : b, hi = a < b ? b : a;
+                    const int ph = (lo < 3) ? 0 : ((lo == 3) ? (hi - 3 + 1) : (lo == 4 ? (hi - 4 + 4) : 6));
+                    tile_rec[(h0 + a * 6 + b) * kS + slot] = e * (-gauss_d2 * qc[a] * qc[b] + qCH[ph] + ref_dot3(J[b], cov[a]));
+                }
+        }
+        ++slot;
+    }
+}
+
+// acc + v over the contributing pairs, point after point: lane k owns value row k, the lane of the last row the neighbour counts.  The feeder / adder double
+// buffer of ndt_ref_chain2_kernel; what lies behind a tile's pairs is staged as +0.0 up to the next multiple of eight (the sums start at +0 and never become -0:
+// adding +0 is exact).
+__global__ __launch_bounds__(kChainThreads) void ndt_pcl_ref_chain_kernel(const NdtPairDev* __restrict__ pairs, const NdtRefJob* __restrict__ jobs, const double* __restrict__ rec_base,
+                                                                          const uint8_t* __restrict__ cnt_base, double* __restrict__ results)
+{
+    constexpr int P = kPclRefTile, S = kPclRefSlots, kRow = (S + 8) | 1, kMaxRows = kNdtAccum;
+    constexpr int kPer = (kMaxRows * S + kFeeders - 1) / kFeeders;
+    static_assert(((S + 7) & ~7) <= kRow && S + 8 <= kRow, "a row holds its last group of eight");
+    __shared__ double   s_v[2][kMaxRows * kRow];  // 82 KB of the 160
+    __shared__ uint32_t s_tot[2];
+    const NdtRefJob job = jobs[blockIdx.x];
+    const int       R = pcl_ref_rows(static_cast<int>(job.mode));
+    const uint32_t  n = pairs[job.pair].n_src;
+    const MRGFE_GLOBAL double* __restrict__ rec = as_global(rec_base + job.rec_off);
+    const MRGFE_GLOBAL uint32_t* __restrict__ tile_tot = as_global(reinterpret_cast<const uint32_t*>(cnt_base + job.cnt_off));
+    const int  tid = threadIdx.x, f = tid - 64;
+    const bool adder = tid < 64;
+    const uint32_t n_tiles = (n + P - 1) / P;
+    int goff[kPer], loff[kPer], jpos[kPer], rowk[kPer];
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+        const int e = f + u * kFeeders, c = e / S, j = e % S;
+        goff[u] = (!adder && c < R) ? e : -1;
+        loff[u] = c * kRow + j;
+        jpos[u] = j;
+        rowk[u] = c;
+    }
+    double   pa[kPer], pb[kPer];
+    uint32_t ta = 0, tb = 0;
+    double   acc = 0.0;
+    auto fetch = [&](uint32_t tile, double (&pre)[kPer], uint32_t& tot) {
+        tot = 0;
+        if (tile >= n_tiles) return;
+        const MRGFE_GLOBAL double* __restrict__ t0 = rec + (size_t)tile * (size_t)(R * S);
+        tot = min(tile_tot[tile], static_cast<uint32_t>(S));
+        const uint32_t left = n - tile * P;
+        // predicated loads: what lies behind the tile's pairs was never written
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) {
+            const bool want = goff[u] >= 0 && (rowk[u] < R - 1 ? static_cast<uint32_t>(jpos[u]) < tot : (jpos[u] < P && static_cast<uint32_t>(jpos[u]) < left));
+            pre[u] = want ? t0[goff[u]] : 0.0;
+        }
+    };
+    auto stage = [&](int buf, const double (&pre)[kPer], uint32_t tot) {
+        const uint32_t tot8 = (tot + 7u) & ~7u;
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) {
+            if (goff[u] >= 0 && (rowk[u] < R - 1 ? static_cast<uint32_t>(jpos[u]) < tot8 : jpos[u] < ((P + 7) & ~7))) s_v[buf][loff[u]] = pre[u];
+        }
+        for (int t = f; t < R * 8; t += kFeeders) s_v[buf][(t / 8) * kRow + S + t % 8] = 0.0;  // (S is no multiple of eight: the last group runs past the S fetched entries)
+        if (f == 0) s_tot[buf] = tot;
+    };
+    auto step = [&](uint32_t tile, const double (&next)[kPer], uint32_t next_tot, double (&after)[kPer], uint32_t& after_tot) {
+        const int buf = static_cast<int>(tile & 1u);
+        if (adder) {
+            if (tid < R - 1)       acc = ref_chain_row<false>(acc, &s_v[buf][tid * kRow], nullptr, static_cast<int>((s_tot[buf] + 7u) & ~7u));
+            else if (tid == R - 1) acc = ref_chain_row<false>(acc, &s_v[buf][(R - 1) * kRow], nullptr, (P + 7) & ~7);  // neighbour counts (integers: exact)
+        } else {
+            fetch(tile + 2, after, after_tot);
+            if (tile + 1 < n_tiles) stage(buf ^ 1, next, next_tot);
+        }
+        __syncthreads();
+    };
+    if (!adder) { fetch(0, pa, ta); stage(0, pa, ta); fetch(1, pa, ta); }
+    __syncthreads();
+    for (uint32_t tile = 0; tile < n_tiles; tile += 2) {
+        step(tile, pa, ta, pb, tb);
+        if (tile + 1 < n_tiles) step(tile + 1, pb, tb, pa, ta);
+    }
+    // the record of ndt_reduce_kernel: score, gradient, Hessian (row-major), neighbour count at kNdtNbIndex; what a kind does not deliver is zero
+    if (tid < kNdtPartialStride) results[(size_t)job.pair * kNdtPartialStride + tid] = 0.0;
+    __syncthreads();
+    if (tid < R) {
+        const int k = tid == R - 1 ? kNdtNbIndex : (job.mode == 2 ? 7 + tid : tid);
+        results[(size_t)job.pair * kNdtPartialStride + k] = acc;
+    }
+}
+
 int ndt_launch_ref_round(mrgfe_ctx* ctx, int search, const NdtGridDev* d_grids, const NdtPairDev* d_pairs, const NdtEvalDev* d_evals, const NdtRefJob* d_jobs, uint32_t n_jobs,
-                         uint32_t max_tiles, double* d_rec, uint8_t* d_cnt, double* results, bool any_mode01, bool any_mode2)
+                         uint32_t max_tiles, double* d_rec, uint8_t* d_cnt, double* results, bool any_mode01, bool any_mode2, int formulation)
 {
     if (n_jobs == 0 || max_tiles == 0) return MRGFE_OK;
     const dim3 grid(max_tiles, n_jobs);
-    if (search == MRGFE_DIRECT7)      hipLaunchKernelGGL((ndt_ref_records_kernel<7>), grid, dim3(256), 0, ctx->stream, d_grids, d_pairs, d_evals, d_jobs, d_rec, d_cnt);
+    if (formulation == 1) {  // PCL_NDT_HIP: one record kernel and one chain kernel for all three kinds
+        hipLaunchKernelGGL(ndt_pcl_ref_records_kernel, grid, dim3(256), 0, ctx->stream, d_grids, d_pairs, d_evals, d_jobs, d_rec, d_cnt);
+        hipLaunchKernelGGL(ndt_pcl_ref_chain_kernel, dim3(n_jobs), dim3(kChainThreads), 0, ctx->stream, d_pairs, d_jobs, d_rec, d_cnt, results);
+        MRGFE_HIP_CHECK(hipGetLastError());
+        return MRGFE_OK;
+    }
+    if (search == MRGFE_DIRECT7)     hipLaunchKernelGGL((ndt_ref_records_kernel<7>), grid, dim3(256), 0, ctx->stream, d_grids, d_pairs, d_evals, d_jobs, d_rec, d_cnt);
     else if (search == MRGFE_DIRECT1) hipLaunchKernelGGL((ndt_ref_records_kernel<1>), grid, dim3(256), 0, ctx->stream, d_grids, d_pairs, d_evals, d_jobs, d_rec, d_cnt);
     else                              hipLaunchKernelGGL((ndt_ref_records_kernel<27>), grid, dim3(256), 0, ctx->stream, d_grids, d_pairs, d_evals, d_jobs, d_rec, d_cnt);
     // a workgroup per job in both chain kernels; a job of the other kind returns at once

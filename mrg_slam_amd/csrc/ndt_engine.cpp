@@ -379,6 +379,7 @@ int ndt_set_fused_launch(int mode)
 // MRGFE_NDT_REFERENCE_ORDER=1 / mrgfe_dbg_set_ndt_reference_order(1): NDT_OMP's sums in the reference's own order (ndt_ref_records_kernel + ndt_ref_chain_kernel,
 // ndt_derivatives.hip) — per-point sums, then a point-order chain; computeHessian pair after pair.  Host-stepped (the host cuts a round's evaluations into
 // chunks that fit the record workspace).  Several times slower than the default tree; bit-identical to the reference-order oracle.
+// mrgfe_ctx_set_ndt_reference_order opens the same per context, and PCL_NDT_HIP's counterpart with it (NdtEngine::reference_order_now below).
 static std::atomic<int> g_ref_order{-1};  // -1: not read yet
 static bool reference_order()
 {
@@ -390,6 +391,14 @@ int ndt_set_reference_order(int mode)
 {
     if (mode == 0 || mode == 1) g_ref_order.store(mode, std::memory_order_relaxed);
     return reference_order() ? 1 : 0;
+}
+// The rule, read when an alignment or an evaluation starts: a context with mrgfe_ctx_set_ndt_reference_order on runs BOTH formulations in the reference's order
+// (PCL_NDT_HIP: ndt_pcl_ref_records_kernel / ndt_pcl_ref_chain_kernel, pcl::NormalDistributionsTransform's pair-after-pair sums); the process-wide setting
+// above governs NDT_HIP only, as it always did.
+bool NdtEngine::reference_order_now() const
+{
+    if (ctx_->ndt_reference_order.load(std::memory_order_relaxed)) return true;
+    return reference_order() && prm_.formulation == 0;
 }
 
 constexpr int kHostParallelMinPairs = 48;  // below this the controller steps of a round run on the calling thread
@@ -465,12 +474,15 @@ void NdtEngine::host_plan(std::vector<uint32_t>& plan, uint32_t wg_target, uint3
 // One round of the host-stepped path in the reference's summation order: every pending request (filled into h_evals_ by the caller) becomes a job — its
 // records, then its chain — and the 384-byte result records land in pinned host memory like those of ndt_reduce_kernel<false>.  The record workspace is
 // bounded (MRGFE_REF_WORKSPACE_MB, default 16 GiB of the 288): a round whose jobs need more runs in several launches, one after the other on the stream.
+// PCL_NDT_HIP (formulation 1) keeps a record per contributing PAIR for every kind of evaluation: 108 slots x 44 rows per four points, 1.2 GB for a 130k-point
+// score+gradient+Hessian evaluation at the worst — the default cap holds a dozen of those.
 int NdtEngine::reference_round()
 {
     hipStream_t st = ctx_->stream;
     const uint32_t P = static_cast<uint32_t>(n_pairs());
     const size_t ws_cap = static_cast<size_t>(std::max(1, env_int("MRGFE_REF_WORKSPACE_MB", 16384))) << 20;  // (read per round: tests shrink it to force several launches)
     const size_t nnb = prm_.search == MRGFE_DIRECT7 ? 7 : (prm_.search == MRGFE_DIRECT1 ? 1 : 27);
+    const bool   pcl = prm_.formulation == 1;
     MRGFE_HIP_CHECK(hipMemcpyAsync(d_evals_.p, h_evals_.p, sizeof(NdtEvalDev) * P, hipMemcpyHostToDevice, st));
     std::vector<NdtRefJob> jobs;
     size_t   rec_doubles = 0, cnt_bytes = 0;
@@ -483,7 +495,8 @@ int NdtEngine::reference_round()
         MRGFE_TRY(d_ref_jobs_.ensure(sizeof(NdtRefJob) * jobs.size()));
         MRGFE_TRY(ctx_->stage_h2d(d_ref_jobs_.p, jobs.data(), sizeof(NdtRefJob) * jobs.size(), st));
         MRGFE_TRY(ndt_launch_ref_round(ctx_, prm_.search, d_grids_.as<NdtGridDev>(), d_pairs_.as<NdtPairDev>(), d_evals_.as<NdtEvalDev>(), d_ref_jobs_.as<NdtRefJob>(),
-                                       static_cast<uint32_t>(jobs.size()), max_tiles, d_ref_rec_.as<double>(), d_ref_cnt_.as<uint8_t>(), h_results_.as<double>(), any01, any2));
+                                       static_cast<uint32_t>(jobs.size()), max_tiles, d_ref_rec_.as<double>(), d_ref_cnt_.as<uint8_t>(), h_results_.as<double>(), any01, any2,
+                                       prm_.formulation));
         jobs.clear();
         rec_doubles = cnt_bytes = 0;
         max_tiles = 0;
@@ -495,12 +508,12 @@ int NdtEngine::reference_round()
         if (c.done()) continue;
         const uint32_t mode = static_cast<uint32_t>(c.request_mode());
         const size_t   n = book_->pair(i).n;
-        const size_t   need = ndt_ref_record_doubles(static_cast<int>(mode), n, static_cast<int>(nnb));  // doubles
+        const size_t   need = ndt_ref_record_doubles(static_cast<int>(mode), n, static_cast<int>(nnb), prm_.formulation);  // doubles
         if (!jobs.empty() && (rec_doubles + need) * sizeof(double) > ws_cap) MRGFE_TRY(flush());
         jobs.push_back(NdtRefJob{i, mode, rec_doubles, cnt_bytes});
         (mode == 2 ? any2 : any01) = true;
         rec_doubles += need;
-        if (mode == 2) cnt_bytes += (n + 15) & ~size_t(15);
+        if (mode == 2 || pcl) cnt_bytes += (n + 15) & ~size_t(15);  // a header word per tile of four points or more
         max_tiles = std::max(max_tiles, static_cast<uint32_t>((n + 255) / 256));
     }
     return flush();
@@ -662,7 +675,7 @@ int NdtEngine::align_all(NdtSnapshotPort* port)
     // (13.6 vs 13.0 ms per 256-pair step): the fetches add rounds, and in lock-step rounds every extra launch pays its own tail.
     static const bool split_first = env_int("MRGFE_SPLIT_FIRST", 0) != 0;
     int running = 0;
-    const bool ref_order = reference_order() && prm_.formulation == 0;
+    const bool ref_order = reference_order_now();
     for (int i = 0; i < P; ++i) {
         const PairBook::Pair& p = book_->pair(i);
         NdtController&        c = ctls_[i];
@@ -847,7 +860,7 @@ int NdtEngine::evaluate(int pair, const float T[16], const double p[6], int mode
     ctls_[pair].adopt(s);
     const int keep = forced_ppt_;
     forced_ppt_ = ppt;
-    const int rc = (reference_order() && prm_.formulation == 0) ? reference_round() : enqueue_round(0, false, want, nullptr);
+    const int rc = reference_order_now() ? reference_round() : enqueue_round(0, false, want, nullptr);
     forced_ppt_ = keep;
     for (int i = 0; i < P; ++i) ctls_[i].adopt(saved[i]);
     MRGFE_TRY(rc);
@@ -856,6 +869,7 @@ int NdtEngine::evaluate(int pair, const float T[16], const double p[6], int mode
     *score = res[0];
     for (int k = 0; k < 6; ++k) grad[k] = res[1 + k];
     for (int k = 0; k < 36; ++k) hess[k] = res[7 + k];
+    last_eval_neighbours_ = res[kNdtNbIndex];
     return MRGFE_OK;
 }
 

@@ -95,6 +95,7 @@ class NdtEngine {
     void set_force_hash(bool f) { force_hash_ = f; }  // tests: exercise the hashed lookup on small grids
     mrgfe_ctx* ctx() const { return ctx_; }
     int rounds() const { return rounds_; }  // rounds of the last align_all()
+    double last_eval_neighbours() const { return last_eval_neighbours_; }  // (point, voxel) pairs of the last evaluate() (tests)
     // busy pairs and work items per kind of each of them, [round][3] each, the first `cap` rounds (tests: mrgfe_dbg_*_ndt_rounds); returns rounds()
     int round_info(int cap, uint32_t* n_pairs, uint32_t* n_items) const
     {
@@ -138,6 +139,7 @@ class NdtEngine {
     void host_plan(std::vector<uint32_t>& plan, uint32_t wg_target, uint32_t max_ppt) const;
     std::vector<Event> ev_pool_;          // [round][variant][begin, end]
     int    rounds_ = 0;
+    double last_eval_neighbours_ = 0;
     int      key_bits_hint_ = 0;   // key width of this engine's last single-target build + 1 (0: none yet): lets the next one sort before the host has seen its box
     uint64_t result_tag_ = 0;  // host-stepped single registration: the value its next reduction stores behind the record
     std::vector<NdtRoundInfo> round_info_;  // busy pairs and items per kind of every round of the last align_all
@@ -145,7 +147,8 @@ class NdtEngine {
     int ensure_events(size_t rounds);
     uint32_t derivative_grid(int mode) const;
     int enqueue_round(uint32_t round, bool device_control, const bool want_mode[3], NdtRoundInfo* h_info, double result_tag = 0.0);
-    int reference_round();                // the same round in the reference's summation order (ndt_set_reference_order)
+    int reference_round();                // the same round in the reference's summation order (ndt_set_reference_order / mrgfe_ctx_set_ndt_reference_order)
+    bool reference_order_now() const;     // does the call that starts now run in that order?
     DevBuf d_ref_rec_, d_ref_cnt_, d_ref_jobs_;
     void account(const std::vector<NdtRoundInfo>& info, size_t rounds);
 };

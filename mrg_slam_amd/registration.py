@@ -196,7 +196,10 @@ class HipRegistration:
 
 
 class NdtHip(HipRegistration):
-    """registration_method "NDT_HIP": drop-in for the NDT_OMP branch (registrations.cpp:130-148)."""
+    """registration_method "NDT_HIP": drop-in for the NDT_OMP branch (registrations.cpp:130-148).
+
+    On a context with ``Context.set_ndt_reference_order()`` on (or, process-wide, under ``MRGFE_NDT_REFERENCE_ORDER=1``) the sums are added in pclomp's own
+    order and every evaluation and alignment equals the reference-order oracle bit for bit, some fifty times slower."""
 
     METHOD = NDT_HIP
 
@@ -230,6 +233,13 @@ class NdtHip(HipRegistration):
             check(lib().mrgfe_dbg_ndt_evaluate_ppt(self._h, _colmajor(T).ctypes.data_as(_fp), p.ctypes.data_as(_dp), mode, int(ppt), *out))
         return s.value, g, H
 
+    @property
+    def eval_neighbours(self) -> float:
+        """(point, voxel) pairs the last :meth:`evaluate` met, pairs its range check dropped included (``mrgfe_dbg_ndt_eval_neighbours``)."""
+        v = C.c_double(0)
+        check(lib().mrgfe_dbg_ndt_eval_neighbours(self._h, C.byref(v)))
+        return v.value
+
     def ndt_rounds(self):
         """(n_pairs, n_items), [rounds, 3] each: busy pairs and work items per kernel variant of every round of the last align (``mrgfe_dbg_reg_ndt_rounds``)."""
         return _ndt_rounds(lambda cap, a, b: lib().mrgfe_dbg_reg_ndt_rounds(self._h, cap, a, b))
@@ -252,7 +262,13 @@ class PclNdtHip(NdtHip):
     """registration_method "PCL_NDT_HIP": drop-in for the branch every name without "OMP" in it ends in — "NDT" and any unknown string
     (registrations.cpp:115-129): pcl::NormalDistributionsTransform of PCL 1.12.  Pair terms in f64, the radius search over the voxel
     centroids (its only neighbourhood), PCL's iteration test: the squared translation of the last step against the un-squared
-    transformation_epsilon — with step_size 0.1 and any epsilon >= 0.01 that is ONE Newton iteration (oracle/quirks.h)."""
+    transformation_epsilon — with step_size 0.1 and any epsilon >= 0.01 that is ONE Newton iteration (oracle/quirks.h).
+
+    By default a point's voxel sums are factored and added in a tree (results within f64 rounding of the reference, which an optimisation that does not
+    settle can amplify).  On a context with ``Context.set_ndt_reference_order()`` on, every pair's terms are formed in the reference's expression tree and
+    added pair after pair as pcl::NormalDistributionsTransform does: evaluations and alignments equal the oracle bit for bit (all 36 Hessian entries: the
+    reference's Hessian is not symmetric in its last bits), host-stepped and hundreds of times slower at full size (profiles/pclndt_reforder_summary.md): a
+    verification mode.  The environment variable never touches this class."""
 
     METHOD = PCL_NDT_HIP
 
