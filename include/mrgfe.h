@@ -212,6 +212,10 @@ int mrgfe_ctx_sor_grid_stats(mrgfe_ctx* ctx, double out[6]);
  * the chain's own (0 on route 1; mrgfe_cloud_records_device: its one); out[3] = record bytes that reached the host; out[4] = bytes of them copied by the
  * host (0 when direct); out[5] = such calls on this context so far.  mrgfe_ctx_prefilter_stats keeps reporting the chain itself. */
 int mrgfe_ctx_egress_stats(mrgfe_ctx* ctx, int64_t out[6]);
+/* The same six values for the SECOND record sink of the last call on this context that had one: the coloured cloud of mrgfe_scan_callback_outputs, the removed
+ * cloud of mrgfe_keyframe_callback_records[_device].  out[2] counts the waits that sink added to its call (0 where the call's own wait covered it); out[5] the
+ * calls that had a second sink.  A call without one leaves out[0..4] at 0; mrgfe_ctx_egress_stats never counts a second sink. */
+int mrgfe_ctx_second_egress_stats(mrgfe_ctx* ctx, int64_t out[6]);
 
 /* ---- cloud ingest --------------------------------------------------------------------------------- */
 /* replaces pcl::fromROSMsg(*cloud_msg, *cloud) (apps/prefiltering_component.cpp:119-120, scan_matching_odometry_component.cpp:144-145):
@@ -430,6 +434,36 @@ int    mrgfe_scan_callback_device(mrgfe_ctx* ctx, const mrgfe_scan_params* param
  * count, behind one more wait.  mrgfe_ctx_egress_stats says what a call did. */
 int    mrgfe_scan_callback_records(mrgfe_ctx* ctx, const mrgfe_scan_params* params, const uint8_t* data, int point_step, void* records, size_t capacity_bytes,
                                    void* d_out_xyzi, size_t* out_n);
+/* The callback with its second publish: prefiltering/colored_points, the loop of deskewing() (apps/prefiltering_component.cpp:239-257) — the raw scan as
+ * pcl::PointXYZRGB, the colour saying where a point stands in the point sequence — written on the device from the SAME uploaded payload.
+ *   colored_records NULL: the call is mrgfe_scan_callback_records(ctx, params, data, point_step, records, capacity_bytes, d_out_xyzi, out_n), bit for bit:
+ *     results, refusals, mrgfe_ctx_prefilter_stats, mrgfe_ctx_egress_stats.
+ *   colored_records non-NULL (colored_capacity_bytes >= 32 * width * height): it receives n = width * height records of 32 bytes in message order, non-finite
+ *     points included, of the cloud as pcl::fromROSMsg left it (:119-120) — before deskewing, before the transform, before any filter (:125 hands deskewing()
+ *     the unpacked cloud) — and *out_n_colored = n.  One more kernel reads the wire records of the raw device buffer the scan's head kernel reads (the same
+ *     reader, the byte-aligned one for a layout of mrgfe_ctx_set_byte_layouts).  [UPSTREAM-RECALL] the record is the pcl::PointXYZRGB in memory, which
+ *     pcl::toROSMsg copies as it is (fields x@0 y@4 z@8 rgb@16, point_step 32):
+ *       bytes 0..11 the bits of x, y, z as read (a NaN's payload included); 12..15 1.0f; 16 b, 17 g = 128, 18 r, 19 a = 255; 20..31 zero
+ *     with t = (double)i / (double)n, r = (uint8_t)(255 * t), b = (uint8_t)(255 * (1 - t)): IEEE f64, a real division, truncated toward zero (:248-252).
+ *     The kernel is queued in front of the chain: on route 1 the chain's one wait covers it and the call gains none; on routes 0 and 2 it is waited for behind
+ *     the host-driven passes.  The destination rule is that of `records`; what is staged goes through a second pinned buffer of the context, so the filtered
+ *     records keep their own path (a route-1 STATISTICAL chain's stay staged).  mrgfe_ctx_second_egress_stats says what the colour stage did.
+ *   records NULL: no filtered records are wanted; with d_out_xyzi non-NULL the call is mrgfe_scan_callback_device plus the coloured records, with d_out_xyzi
+ *     NULL as well only the coloured records are made (no chain runs, *out_n = 0, mrgfe_ctx_prefilter_stats untouched).
+ *   Whether to publish is the caller's decision — a subscriber and a non-empty IMU queue (:234,239); the call colours whenever it is asked.
+ *   MRGFE_ERR_INVALID before anything is launched, no byte written: a NULL ctx / params / outputs / out_n / out_n_colored, records and colored_records both NULL,
+ *     colored_capacity_bytes < 32 * width * height, and every refusal of mrgfe_scan_callback_records.  An empty message is MRGFE_OK with both counts 0. */
+typedef struct mrgfe_scan_outputs {
+    int    point_step;                 /* 16 or 32: the filtered scan's records, as mrgfe_scan_callback_records (ignored when records is NULL) */
+    void*  records;                    /* may be NULL: no filtered records wanted                                                           */
+    size_t capacity_bytes;
+    void*  colored_records;            /* may be NULL; 32-byte records only                                                                 */
+    size_t colored_capacity_bytes;
+    void*  d_out_xyzi;                 /* may be NULL, as mrgfe_scan_callback_records                                                       */
+} mrgfe_scan_outputs;
+size_t mrgfe_scan_outputs_size(void); /* sizeof(mrgfe_scan_outputs) as the library was compiled */
+int    mrgfe_scan_callback_outputs(mrgfe_ctx* ctx, const mrgfe_scan_params* params, const uint8_t* data, const mrgfe_scan_outputs* outputs, size_t* out_n,
+                                   size_t* out_n_colored);
 /* The n packed 16-byte points at d_xyzi (device memory of the context's GPU: what mrgfe_scan_callback_device, mrgfe_prefilter_device, mrgfe_floor_detect_device's
  * caller or a keyframe callback's caller hold) as the same records: one launch, one wait, the same destination rule; capacity_bytes >= n * point_step.
  * MRGFE_ERR_INVALID, nothing read or written: a NULL argument, another point_step, too little capacity, a d_xyzi that is not device memory of the context's
@@ -610,6 +644,24 @@ int    mrgfe_keyframe_callback(mrgfe_map_store* store, uint64_t key, const mrgfe
  * has no new entry and its byte count is unchanged. */
 int    mrgfe_keyframe_callback_device(mrgfe_map_store* store, uint64_t key, const void* d_xyzi, size_t n, const float* centres_xyz, int n_centres,
                                       float radius_sqr, float* kept_xyzi, size_t* n_kept, float* removed_xyzi, size_t* n_removed);
+/* The callback to its two publishes: the keyframe's cloud_msg_filtered (pcl::toROSMsg of the kept cloud, apps/mrg_slam_component.cpp:432-435) and
+ * other_robots_removed_points (:437-443) come down as the `data` of those messages, written on the device — point_step 32 or 16, the two layouts of
+ * mrgfe_scan_callback_records, the same destination rule per sink (the removed cloud's staging and statistics are the second sink's:
+ * mrgfe_ctx_second_egress_stats).  The stored cloud, both counts, mrgfe_map_store_bytes, the refusals and "no new entry after a failure" are
+ * mrgfe_keyframe_callback[_device]'s; the records hold the points of that call's kept_xyzi / removed_xyzi, same order, same bits.
+ * kept_records / removed_records: room for width * height (device form: n) records each; either may be NULL (not written; the counts are still returned);
+ * only the first *n_kept / *n_removed records are ever written.  One record kernel runs directly behind the partition over the two compacted clouds — the
+ * stored cloud and the removed points — in ONE launch: at most the two waits of mrgfe_keyframe_callback (the counts, then the records).
+ * n_centres == 0: nothing is removed and the reference keeps the original message (:396,436): *n_removed = 0, and a kept_records sink still receives the
+ * whole cloud as records (one gather, one record launch, one wait).
+ * MRGFE_ERR_INVALID, nothing launched, no new entry: what mrgfe_keyframe_callback[_device] refuses, a point_step other than 16 or 32 (when a sink is given),
+ * a capacity below width * height * point_step of a sink that is given, a NULL n_kept. */
+int    mrgfe_keyframe_callback_records(mrgfe_map_store* store, uint64_t key, const mrgfe_keyframe_params* layout, const void* data, size_t data_bytes,
+                                       const float* centres_xyz, int n_centres, float radius_sqr, int point_step, void* kept_records, size_t kept_capacity_bytes,
+                                       size_t* n_kept, void* removed_records, size_t removed_capacity_bytes, size_t* n_removed);
+int    mrgfe_keyframe_callback_records_device(mrgfe_map_store* store, uint64_t key, const void* d_xyzi, size_t n, const float* centres_xyz, int n_centres,
+                                              float radius_sqr, int point_step, void* kept_records, size_t kept_capacity_bytes, size_t* n_kept,
+                                              void* removed_records, size_t removed_capacity_bytes, size_t* n_removed);
 
 /* ---- the graph database's keyframe and edge loops in one call each (src/mrg_slam/graph_database.cpp) ---- */
 /* Many keyframe messages at once: the point work of GraphDatabase::add_static_keyframes (:181-182), flush_graph_queue (:294-295, another robot's whole
@@ -795,6 +847,20 @@ int mrgfe_odom_frame(mrgfe_odom* odom, const mrgfe_keyframe_params* layout, cons
  * otherwise the registration's own bounding-box pass runs. */
 int mrgfe_odom_frame_device(mrgfe_odom* odom, const void* d_xyzi, size_t n, double stamp_seconds, const float* msf_delta, int want_status, float* aligned_xyzi,
                             mrgfe_odom_result* out);
+/* The frame to its publish: scan_matching_odometry/aligned_points, pcl::transformPointCloud(*cloud, *aligned, odom) and pcl::toROSMsg
+ * (apps/scan_matching_odometry_component.cpp:341-347).  Everything about the frame is mrgfe_odom_frame[_device], field for field: state, decisions,
+ * hand-over, failure atomicity, mrgfe_odom_stats.  On MRGFE_ODOM_ACCEPTED aligned_records receives the WHOLE input cloud, before the downsample, moved by
+ * `odom`, as records of point_step 32 or 16 (the layouts and the destination rule of mrgfe_scan_callback_records) and *n_aligned = width * height (device
+ * form: n); ONE kernel transforms and writes the records in one pass over the input cloud — no intermediate cloud, no copy command — and the call has the one
+ * wait the aligned_xyzi path of mrgfe_odom_frame has.  The point bits are those of mrgfe_transform_cloud(cloud, odom): a non-finite point stays as it is,
+ * the intensity is copied.  On every other outcome *n_aligned = 0 and the buffer is untouched.
+ * MRGFE_ERR_INVALID with the state left as it was: a point_step other than 16 or 32, capacity_bytes < width * height * point_step, a NULL aligned_records or
+ * n_aligned, and what mrgfe_odom_frame[_device] refuses. */
+int mrgfe_odom_frame_records(mrgfe_odom* odom, const mrgfe_keyframe_params* layout, const void* data, size_t data_bytes, double stamp_seconds,
+                             const float* msf_delta, int want_status, int point_step, void* aligned_records, size_t capacity_bytes, size_t* n_aligned,
+                             mrgfe_odom_result* out);
+int mrgfe_odom_frame_records_device(mrgfe_odom* odom, const void* d_xyzi, size_t n, double stamp_seconds, const float* msf_delta, int want_status, int point_step,
+                                    void* aligned_records, size_t capacity_bytes, size_t* n_aligned, mrgfe_odom_result* out);
 
 /* ---- batched candidate matching (LoopDetector::matching candidate loop, src/mrg_slam/loop_detector.cpp:126-145) ---- */
 typedef struct mrgfe_pair_result {

@@ -56,6 +56,13 @@ class ScanParams(C.Structure):
                 ("T", C.c_float * 16), ("filters", PrefilterParams)]
 
 
+class ScanOutputs(C.Structure):
+    """struct mrgfe_scan_outputs: where ``mrgfe_scan_callback_outputs`` leaves the filtered scan's records, the coloured cloud's records and the device cloud."""
+
+    _fields_ = [("point_step", C.c_int), ("records", C.c_void_p), ("capacity_bytes", C.c_size_t), ("colored_records", C.c_void_p), ("colored_capacity_bytes", C.c_size_t),
+                ("d_out_xyzi", C.c_void_p)]
+
+
 class KeyframeParams(C.Structure):
     """struct mrgfe_keyframe_params: the layout of the sensor_msgs/PointCloud2 payload ``mrgfe_keyframe_callback`` reads."""
 
@@ -292,6 +299,9 @@ SIGNATURES = {
     "mrgfe_pointcloud2_layout": (C.c_int, [C.POINTER(PointField), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(KeyframeParams), C.POINTER(C.c_int)]),
     "mrgfe_keyframe_callback": (C.c_int, [_vp, C.c_uint64, C.POINTER(KeyframeParams), _vp, C.c_size_t, _fp, C.c_int, C.c_float, _fp, _szp, _fp, _szp]),
     "mrgfe_keyframe_callback_device": (C.c_int, [_vp, C.c_uint64, _vp, C.c_size_t, _fp, C.c_int, C.c_float, _fp, _szp, _fp, _szp]),
+    "mrgfe_keyframe_callback_records": (C.c_int, [_vp, C.c_uint64, C.POINTER(KeyframeParams), _vp, C.c_size_t, _fp, C.c_int, C.c_float, C.c_int, _vp, C.c_size_t, _szp, _vp,
+                                                  C.c_size_t, _szp]),
+    "mrgfe_keyframe_callback_records_device": (C.c_int, [_vp, C.c_uint64, _vp, C.c_size_t, _fp, C.c_int, C.c_float, C.c_int, _vp, C.c_size_t, _szp, _vp, C.c_size_t, _szp]),
     "mrgfe_keyframe_msg_size": (C.c_size_t, []),
     "mrgfe_map_store_add_keyframes": (C.c_int, [_vp, C.c_int, C.POINTER(KeyframeMsg), C.POINTER(C.c_uint8)]),
     "mrgfe_graph_edge_size": (C.c_size_t, []),
@@ -310,9 +320,12 @@ SIGNATURES = {
     "mrgfe_scan_callback": (C.c_int, [_vp, C.POINTER(ScanParams), C.POINTER(C.c_uint8), _fp, C.POINTER(C.c_size_t)]),
     "mrgfe_scan_callback_device": (C.c_int, [_vp, C.POINTER(ScanParams), C.POINTER(C.c_uint8), _vp, C.POINTER(C.c_size_t)]),
     "mrgfe_scan_callback_records": (C.c_int, [_vp, C.POINTER(ScanParams), C.POINTER(C.c_uint8), C.c_int, _vp, C.c_size_t, _vp, C.POINTER(C.c_size_t)]),
+    "mrgfe_scan_outputs_size": (C.c_size_t, []),
+    "mrgfe_scan_callback_outputs": (C.c_int, [_vp, C.POINTER(ScanParams), C.POINTER(C.c_uint8), C.POINTER(ScanOutputs), _szp, _szp]),
     "mrgfe_prefilter_records": (C.c_int, [_vp, C.POINTER(PrefilterParams), _fp, C.c_size_t, C.c_size_t, C.c_int, _vp, C.c_size_t, _vp, C.POINTER(C.c_size_t)]),
     "mrgfe_cloud_records_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, _vp, C.c_size_t]),
     "mrgfe_ctx_egress_stats": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "mrgfe_ctx_second_egress_stats": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mrgfe_floor_default_params": (None, [C.POINTER(FloorParams)]),
     "mrgfe_floor_detect": (C.c_int, [_vp, C.POINTER(FloorParams), _fp, C.c_size_t, C.c_size_t, C.POINTER(FloorResult), _fp, _fp]),
     "mrgfe_floor_detect_device": (C.c_int, [_vp, C.POINTER(FloorParams), _vp, C.c_size_t, C.POINTER(FloorResult), _fp, _fp]),
@@ -352,6 +365,8 @@ SIGNATURES = {
     "mrgfe_odom_stats": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mrgfe_odom_frame": (C.c_int, [_vp, C.POINTER(KeyframeParams), _vp, C.c_size_t, C.c_double, _fp, C.c_int, _fp, C.POINTER(OdomResult)]),
     "mrgfe_odom_frame_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_double, _fp, C.c_int, _fp, C.POINTER(OdomResult)]),
+    "mrgfe_odom_frame_records": (C.c_int, [_vp, C.POINTER(KeyframeParams), _vp, C.c_size_t, C.c_double, _fp, C.c_int, C.c_int, _vp, C.c_size_t, _szp, C.POINTER(OdomResult)]),
+    "mrgfe_odom_frame_records_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_double, _fp, C.c_int, C.c_int, _vp, C.c_size_t, _szp, C.POINTER(OdomResult)]),
     "mrgfe_batch_create": (C.c_int, [_vp, C.POINTER(RegParams), C.POINTER(_vp)]),
     "mrgfe_batch_destroy": (None, [_vp]),
     "mrgfe_batch_clear": (C.c_int, [_vp]),
@@ -539,7 +554,8 @@ def lib() -> C.CDLL:
         for fn, mirror in (("mrgfe_pointcloud2_field_size", PointField), ("mrgfe_keyframe_msg_size", KeyframeMsg), ("mrgfe_graph_edge_size", GraphEdge), ("mrgfe_odom_params_size", OdomParams),
                            ("mrgfe_odom_result_size", OdomResult), ("mrgfe_loop_params_size", LoopParams), ("mrgfe_loop_keyframe_size", LoopKeyframe),
                            ("mrgfe_loop_result_size", LoopResult), ("mrgfe_ground_fill_params_size", GroundFillParams), ("mrgfe_ground_fill_result_size", GroundFillResult),
-                           ("mrgfe_map_publish_params_size", MapPublishParams), ("mrgfe_map_publish_result_size", MapPublishResult)):
+                           ("mrgfe_map_publish_params_size", MapPublishParams), ("mrgfe_map_publish_result_size", MapPublishResult),
+                           ("mrgfe_scan_outputs_size", ScanOutputs)):
             if hasattr(L, fn) and getattr(L, fn)() != C.sizeof(mirror):
                 raise RuntimeError(f"libmrgfe.so was built with a {fn[:-5]} of {getattr(L, fn)()} bytes, the binding mirrors {C.sizeof(mirror)}")
         _lib = L
@@ -639,6 +655,13 @@ class Context:
         chain's own (0 on the one-wait route), ``bytes`` of records that reached the host, ``copied`` of them by the host, ``calls`` so far."""
         v = (C.c_int64 * 6)()
         check(lib().mrgfe_ctx_egress_stats(self._h, v))
+        return {"direct": bool(v[0]), "launches": int(v[1]), "waits": int(v[2]), "bytes": int(v[3]), "copied": int(v[4]), "calls": int(v[5])}
+
+    def second_egress_stats(self) -> dict:
+        """The same for the SECOND record sink of the last call on this context that had one (``mrgfe_ctx_second_egress_stats``): the coloured cloud of
+        ``scan_callback_outputs``, the removed cloud of the keyframe callback's record form."""
+        v = (C.c_int64 * 6)()
+        check(lib().mrgfe_ctx_second_egress_stats(self._h, v))
         return {"direct": bool(v[0]), "launches": int(v[1]), "waits": int(v[2]), "bytes": int(v[3]), "copied": int(v[4]), "calls": int(v[5])}
 
     def close(self):

@@ -727,19 +727,24 @@ void mrgfe_scan_default_params(mrgfe_scan_params* p)
     mrgfe_prefilter_default_params(&p->filters);
 }
 // rec_step != 0: the record form — `records` / `capacity_bytes` are checked (check_record_sink) and `out` is the caller's device buffer or NULL
+// colored != NULL (mrgfe_scan_callback_outputs): the coloured cloud's 32-byte records beside whatever else the call makes; then `out` and `records` may both be
+// NULL (no chain runs) and *out_n_colored receives width * height
 static int scan_callback_impl(const char* fn, mrgfe_ctx* ctx, const mrgfe_scan_params* p, const uint8_t* data, void* out, size_t* out_n, bool on_device, bool as_records = false,
-                              int rec_step = 0, void* records = nullptr, size_t capacity_bytes = 0)
+                              int rec_step = 0, void* records = nullptr, size_t capacity_bytes = 0, void* colored = nullptr, size_t colored_capacity_bytes = 0,
+                              size_t* out_n_colored = nullptr)
 {
     return abi_guard(fn, [&]() -> int {
         if (!ctx || !p || !out_n) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
         *out_n = 0;
-        RecordSink sink;
+        RecordSink sink, colored_sink;
         if (as_records) MRGFE_TRY(check_record_sink(fn, rec_step, records, capacity_bytes, size_t(p->width) * p->height, &sink));
+        if (colored) MRGFE_TRY(check_record_sink(fn, 32, colored, colored_capacity_bytes, size_t(p->width) * p->height, &colored_sink));
         const RecordSink* rec = as_records ? &sink : nullptr;
+        const RecordSink* col = colored ? &colored_sink : nullptr;
         PrefilterChain ch;
         MRGFE_TRY(chain_from_params(fn, &p->filters, &ch));
         if (size_t(p->width) * p->height == 0) return MRGFE_OK;  // where the reference returns early (:121-123)
-        if (!data || (!out && !rec)) { set_error("%s: NULL data / output", fn); return MRGFE_ERR_INVALID; }
+        if (!data || (!out && !rec && !col)) { set_error("%s: NULL data / output", fn); return MRGFE_ERR_INVALID; }
         ScanHead h;
         h.data = data;
         h.width = p->width; h.height = p->height; h.point_step = p->point_step; h.row_step = p->row_step;
@@ -754,7 +759,10 @@ static int scan_callback_impl(const char* fn, mrgfe_ctx* ctx, const mrgfe_scan_p
         std::memcpy(h.T, Tr, sizeof(h.T));
         MRGFE_LOCK(ctx);
         MRGFE_TRY(ctx->bind());
-        return scan_chain(ctx, ch, h, out, out_n, on_device, rec);
+        if (!out && !rec) MRGFE_TRY(scan_colored_records(ctx, h, *col));  // (the coloured cloud alone: no chain)
+        else MRGFE_TRY(scan_chain(ctx, ch, h, out, out_n, on_device, rec, col));
+        if (col) *out_n_colored = size_t(h.width) * h.height;
+        return MRGFE_OK;
     });
 }
 int mrgfe_scan_callback(mrgfe_ctx* ctx, const mrgfe_scan_params* p, const uint8_t* data, float* out_xyzi, size_t* out_n)
@@ -768,6 +776,18 @@ int mrgfe_scan_callback_device(mrgfe_ctx* ctx, const mrgfe_scan_params* p, const
 int mrgfe_scan_callback_records(mrgfe_ctx* ctx, const mrgfe_scan_params* p, const uint8_t* data, int point_step, void* records, size_t capacity_bytes, void* d_out_xyzi, size_t* out_n)
 {
     return scan_callback_impl("mrgfe_scan_callback_records", ctx, p, data, d_out_xyzi, out_n, d_out_xyzi != nullptr, true, point_step, records, capacity_bytes);
+}
+size_t mrgfe_scan_outputs_size(void) { return sizeof(mrgfe_scan_outputs); }
+int mrgfe_scan_callback_outputs(mrgfe_ctx* ctx, const mrgfe_scan_params* p, const uint8_t* data, const mrgfe_scan_outputs* o, size_t* out_n, size_t* out_n_colored)
+{
+    static const char* fn = "mrgfe_scan_callback_outputs";
+    if (!o || !out_n_colored) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+    *out_n_colored = 0;
+    if (!o->colored_records) {  // the call is mrgfe_scan_callback_records (which refuses NULL records)
+        return scan_callback_impl(fn, ctx, p, data, o->d_out_xyzi, out_n, o->d_out_xyzi != nullptr, true, o->point_step, o->records, o->capacity_bytes);
+    }
+    return scan_callback_impl(fn, ctx, p, data, o->d_out_xyzi, out_n, o->d_out_xyzi != nullptr, o->records != nullptr, o->point_step, o->records, o->capacity_bytes,
+                              o->colored_records, o->colored_capacity_bytes, out_n_colored);
 }
 int mrgfe_calc_fitness_score(mrgfe_ctx* ctx, const float* cloud1, size_t n1, const float* cloud2, size_t n2, size_t stride, const double relpose[16], double max_range, double* out)
 {
@@ -1184,7 +1204,8 @@ void mrgfe_keyframe_default_params(mrgfe_keyframe_params* p)
 // The callback behind its argument checks, for both forms (the caller holds the context's lock and has bound its device; `l` has passed
 // check_pointcloud2_layout): `d_records` NULL: `raw_bytes` of `data` go up through the raw staging path first; else the records are read where they are.
 static int keyframe_callback_locked(const char* fn, mrgfe_map_store* s, uint64_t key, const KeyframeLayout& l, const void* data, size_t raw_bytes, const void* d_records,
-                                    const float* centres, int n_centres, float radius_sqr, float* kept, size_t* n_kept, float* removed, size_t* n_removed)
+                                    const float* centres, int n_centres, float radius_sqr, float* kept, size_t* n_kept, float* removed, size_t* n_removed,
+                                    bool as_records = false, const RecordSink* kept_rec = nullptr, const RecordSink* removed_rec = nullptr)
 {
     const size_t n = size_t(l.width) * l.height;
     if (s->clouds.count(key)) { set_error("%s: keyframe %llu is already stored", fn, static_cast<unsigned long long>(key)); return MRGFE_ERR_STATE; }
@@ -1197,6 +1218,20 @@ static int keyframe_callback_locked(const char* fn, mrgfe_map_store* s, uint64_t
         auto run = [&]() -> int {
             const void* d_raw = d_records;
             if (!d_raw) MRGFE_TRY(upload_raw_records(ctx, data, raw_bytes, &d_raw));
+            if (as_records) {
+                // the record form (mrgfe_keyframe_callback_records): the same gather or split, then ONE record launch over the stored cloud and the removed
+                // points and the wait behind it — without centres the call's only one, else its second
+                if (n_centres == 0) {
+                    MRGFE_TRY(keyframe_gather_device(ctx, d_raw, l, static_cast<float4*>(p)));
+                    nk = n;
+                } else {
+                    if (removed_rec) MRGFE_TRY(drem.ensure(n * 16));
+                    MRGFE_TRY(keyframe_split_device(ctx, d_raw, l, centres, n_centres, radius_sqr, static_cast<float4*>(p), &nk, removed_rec ? drem.as<float4>() : nullptr, &nr));  // (the first wait)
+                }
+                if ((kept_rec && nk) || (removed_rec && nr)) return cloud_pair_records_device(ctx, static_cast<const float4*>(p), nk, kept_rec, drem.as<float4>(), nr, removed_rec);
+                if (n_centres == 0) MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (no record is wanted: the gather is still waited for)
+                return MRGFE_OK;
+            }
             if (n_centres == 0) {
                 MRGFE_TRY(keyframe_gather_device(ctx, d_raw, l, static_cast<float4*>(p)));
                 nk = n;
@@ -1302,6 +1337,61 @@ int mrgfe_keyframe_callback_device(mrgfe_map_store* s, uint64_t key, const void*
         MRGFE_TRY(s->ctx->bind());
         if (n) MRGFE_TRY(check_device_cloud(s->ctx, fn, d_xyzi, n));
         return keyframe_callback_locked(fn, s, key, l, nullptr, 0, n ? d_xyzi : nullptr, centres, n_centres, radius_sqr, kept, n_kept, removed, n_removed);
+    });
+}
+// the two sinks of the record forms: each one that is given is checked as every record sink is (check_record_sink), a NULL one stays NULL
+static int keyframe_record_sinks(const char* fn, int point_step, size_t n, void* kept_records, size_t kept_capacity, void* removed_records, size_t removed_capacity,
+                                 RecordSink* kept, RecordSink* removed, const RecordSink** kept_rec, const RecordSink** removed_rec)
+{
+    *kept_rec = *removed_rec = nullptr;
+    if (kept_records) { MRGFE_TRY(check_record_sink(fn, point_step, kept_records, kept_capacity, n, kept)); *kept_rec = kept; }
+    if (removed_records) { MRGFE_TRY(check_record_sink(fn, point_step, removed_records, removed_capacity, n, removed)); *removed_rec = removed; }
+    return MRGFE_OK;
+}
+int mrgfe_keyframe_callback_records(mrgfe_map_store* s, uint64_t key, const mrgfe_keyframe_params* lay, const void* data, size_t data_bytes, const float* centres, int n_centres,
+                                    float radius_sqr, int point_step, void* kept_records, size_t kept_capacity_bytes, size_t* n_kept, void* removed_records,
+                                    size_t removed_capacity_bytes, size_t* n_removed)
+{
+    static const char* fn = "mrgfe_keyframe_callback_records";
+    return abi_guard(fn, [&]() -> int {
+        if (!s || !lay || !n_kept) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        *n_kept = 0;
+        if (n_removed) *n_removed = 0;
+        MRGFE_TRY(keyframe_callback_check(fn, key, centres, n_centres));
+        KeyframeLayout l{lay->width, lay->height, lay->point_step, lay->row_step, lay->off_x, lay->off_y, lay->off_z, lay->off_intensity};
+        MRGFE_TRY(check_pointcloud2_layout(s->ctx, fn, l.width, l.height, l.point_step, &l.row_step, l.off_x, l.off_y, l.off_z, l.off_intensity));
+        const size_t n = size_t(l.width) * l.height;
+        const size_t raw_bytes = n ? size_t(l.height - 1) * l.row_step + size_t(l.width) * l.point_step : 0;
+        if (n && !data) { set_error("%s: NULL data", fn); return MRGFE_ERR_INVALID; }
+        if (data_bytes < raw_bytes) { set_error("%s: the payload has %zu bytes, the layout needs %zu", fn, data_bytes, raw_bytes); return MRGFE_ERR_INVALID; }
+        RecordSink        kept, removed;
+        const RecordSink *kept_rec, *removed_rec;
+        MRGFE_TRY(keyframe_record_sinks(fn, point_step, n, kept_records, kept_capacity_bytes, removed_records, removed_capacity_bytes, &kept, &removed, &kept_rec, &removed_rec));
+        MRGFE_LOCK(s->ctx);
+        MRGFE_TRY(s->ctx->bind());
+        return keyframe_callback_locked(fn, s, key, l, data, raw_bytes, nullptr, centres, n_centres, radius_sqr, nullptr, n_kept, nullptr, n_removed, true, kept_rec, removed_rec);
+    });
+}
+int mrgfe_keyframe_callback_records_device(mrgfe_map_store* s, uint64_t key, const void* d_xyzi, size_t n, const float* centres, int n_centres, float radius_sqr, int point_step,
+                                           void* kept_records, size_t kept_capacity_bytes, size_t* n_kept, void* removed_records, size_t removed_capacity_bytes, size_t* n_removed)
+{
+    static const char* fn = "mrgfe_keyframe_callback_records_device";
+    return abi_guard(fn, [&]() -> int {
+        if (!n_kept) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        *n_kept = 0;
+        if (n_removed) *n_removed = 0;
+        MRGFE_TRY(keyframe_callback_check(fn, key, centres, n_centres));
+        MRGFE_TRY(check_count(n, fn));
+        if (n && !d_xyzi) { set_error("%s: NULL cloud", fn); return MRGFE_ERR_INVALID; }
+        if (!s) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        RecordSink        kept, removed;
+        const RecordSink *kept_rec, *removed_rec;
+        MRGFE_TRY(keyframe_record_sinks(fn, point_step, n, kept_records, kept_capacity_bytes, removed_records, removed_capacity_bytes, &kept, &removed, &kept_rec, &removed_rec));
+        const KeyframeLayout l{static_cast<uint32_t>(n), 1, 16, static_cast<uint32_t>(n * 16), 0, 4, 8, 12};  // (as mrgfe_keyframe_callback_device)
+        MRGFE_LOCK(s->ctx);
+        MRGFE_TRY(s->ctx->bind());
+        if (n) MRGFE_TRY(check_device_cloud(s->ctx, fn, d_xyzi, n));
+        return keyframe_callback_locked(fn, s, key, l, nullptr, 0, n ? d_xyzi : nullptr, centres, n_centres, radius_sqr, nullptr, n_kept, nullptr, n_removed, true, kept_rec, removed_rec);
     });
 }
 

@@ -651,6 +651,14 @@ int mrgfe_ctx_egress_stats(mrgfe_ctx* ctx, int64_t out[6])
     out[0] = e.direct; out[1] = e.launches; out[2] = e.waits; out[3] = e.bytes; out[4] = e.copied; out[5] = e.calls;
     return MRGFE_OK;
 }
+int mrgfe_ctx_second_egress_stats(mrgfe_ctx* ctx, int64_t out[6])
+{
+    if (!ctx || !out) { mrgfe::set_error("mrgfe_ctx_second_egress_stats: NULL argument"); return MRGFE_ERR_INVALID; }
+    MRGFE_LOCK(ctx);
+    const mrgfe::ScanEgressStats& e = ctx->eg2_stats;
+    out[0] = e.direct; out[1] = e.launches; out[2] = e.waits; out[3] = e.bytes; out[4] = e.copied; out[5] = e.calls;
+    return MRGFE_OK;
+}
 
 // mrgfe_dbg_ctx_create_detached (include/mrgfe_debug.h): the record of a context with no device behind it — no HIP call is made here
 int mrgfe_dbg_ctx_create_detached(mrgfe_ctx** out)

@@ -292,6 +292,8 @@ struct mrgfe_ctx {
     mrgfe::SorGridStats sor_grid;
     mrgfe::PinBuf rec_pin;                      // scan egress (filters.hip): the records of a call whose destination is not page-locked, copied out behind the wait
     mrgfe::ScanEgressStats eg_stats;
+    mrgfe::PinBuf rec_pin2;                     // ... of a call's SECOND record sink (the coloured scan, the removed cloud): rec_pin keeps serving the first
+    mrgfe::ScanEgressStats eg2_stats;           // ... and its record stage (mrgfe_ctx_second_egress_stats)
     int          cu_count = 256;
     mrgfe::DevBuf fl_buf[11];                   // floor detection (floor.hip): clouds, flags, k-NN lists, RANSAC state / hypotheses / counts
     mrgfe::PinBuf fl_pin;                       // ... and the hypothesis records and counts the host reads after each RANSAC wave

@@ -66,6 +66,15 @@ int filter_chain(mrgfe_ctx* ctx, const PrefilterChain& chain, const float* xyzi,
                  const RecordSink* rec = nullptr);
 // the n packed points at d_xyzi (device memory of the context's GPU) as records: one launch, one wait
 int cloud_records_device(mrgfe_ctx* ctx, const float4* d_xyzi, size_t n, const RecordSink& rec);
+// A call with TWO record sinks (the scan callback's coloured cloud beside its filtered scan, the keyframe callback's removed cloud beside its kept one)
+// resolves the second by the same rule; what is staged of it goes through a pinned buffer of its own (mrgfe_ctx::rec_pin2) and its record stage is counted
+// apart (mrgfe_ctx_second_egress_stats), so the first sink's path and mrgfe_ctx_egress_stats are those of the call without the second.
+// Two packed device clouds as records in ONE launch behind ONE wait (mrgfe_keyframe_callback_records: the kept and the removed cloud); either sink may be
+// NULL (that cloud is not read), both sinks have one point_step.
+int cloud_pair_records_device(mrgfe_ctx* ctx, const float4* d_first, size_t n_first, const RecordSink* first, const float4* d_second, size_t n_second, const RecordSink* second);
+// pcl::transformPointCloud(cloud, odom) and pcl::toROSMsg in one pass (mrgfe_odom_frame_records): point i of d_xyzi moved by T (row-major, the body of
+// transform_cloud_kernel: scan_point.h) and stored as record i; one launch, one wait, no intermediate cloud
+int transformed_records_device(mrgfe_ctx* ctx, const float4* d_xyzi, size_t n, const float T_rowmajor[16], const RecordSink& rec);
 
 // What PrefilteringComponent::cloud_callback does to a scan BEFORE its filters (apps/prefiltering_component.cpp:119-146), as the scan head kernel's work
 // order: read the x / y / z / intensity fields out of the wire records of a sensor_msgs/PointCloud2 (validated: ingest.h check_pointcloud2_layout),
@@ -83,7 +92,13 @@ struct ScanHead {
 // the same chain fed by the wire records of a scan: they go up once, and the scan head kernel writes the chain's packed input (and, in front of the
 // device-driven chain, the distance filter's flags and tile counts with it) — same output as mrgfe_ingest_pointcloud2 -> mrgfe_deskew ->
 // mrgfe_transform_cloud -> filter_chain, bit for bit
-int scan_chain(mrgfe_ctx* ctx, const PrefilterChain& chain, const ScanHead& head, void* out, size_t* out_n, bool out_on_device, const RecordSink* rec = nullptr);
+// `colored` (mrgfe_scan_callback_outputs; 32-byte records, room for width * height of them): the raw scan as pcl::PointXYZRGB records, colour = position in
+// the point sequence (apps/prefiltering_component.cpp:239-257) — one kernel over the uploaded wire records, queued in front of the chain, so the chain's one
+// wait covers it (routes 0 and 2: a wait of its own behind the host-driven passes)
+int scan_chain(mrgfe_ctx* ctx, const PrefilterChain& chain, const ScanHead& head, void* out, size_t* out_n, bool out_on_device, const RecordSink* rec = nullptr,
+               const RecordSink* colored = nullptr);
+// the coloured records alone: the payload goes up, the one kernel, one wait; no chain runs and mrgfe_ctx_prefilter_stats / mrgfe_ctx_egress_stats stay as they were
+int scan_colored_records(mrgfe_ctx* ctx, const ScanHead& head, const RecordSink& colored);
 
 int filter_distance(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, double near_t, double far_t, float* out, size_t* out_n);
 int filter_voxelgrid(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, float leaf, int min_pts, float* out, size_t* out_n, int* overflow);

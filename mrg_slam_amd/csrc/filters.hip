@@ -872,6 +872,49 @@ __global__ __launch_bounds__(256) void cloud_records_kernel(const float4* __rest
     if (i >= n) return;
     store_record<kStep>(out, i, in[i], EgressOffsets{});
 }
+// two packed clouds in one launch (the keyframe callback's kept and removed points, mrgfe_keyframe_callback_records): thread i < na writes record i of the
+// first, na <= i < na + nb record i - na of the second; launched with ceil((na + nb) / 256) workgroups, each output has room for its own count
+template <int kStep>
+__global__ __launch_bounds__(256) void cloud_pair_records_kernel(const float4* __restrict__ a, uint32_t na, float4* __restrict__ out_a, const float4* __restrict__ b, uint32_t nb,
+                                                                  float4* __restrict__ out_b)
+{
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (i < na) store_record<kStep>(out_a, i, a[i], EgressOffsets{});
+    else if (i - na < nb) store_record<kStep>(out_b, i - na, b[i - na], EgressOffsets{});
+}
+// pcl::transformPointCloud(*cloud, *aligned, odom) and pcl::toROSMsg(*aligned, ...) in one pass (apps/scan_matching_odometry_component.cpp:341-347,
+// mrgfe_odom_frame_records): transform_cloud_kernel's body (scan_point.h) feeding the record store, so the bits are those of the two launches
+struct RecordTransform { float m[12]; };
+template <int kStep>
+__global__ __launch_bounds__(256) void transform_records_kernel(const float4* __restrict__ in, uint32_t n, RecordTransform T, float4* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    store_record<kStep>(out, i, transform_finite_point(T.m, in[i]), EgressOffsets{});
+}
+// ---- prefiltering/colored_points (apps/prefiltering_component.cpp:239-257, mrgfe_scan_callback_outputs) -----------------------------------------------------
+// The raw scan as the records of pcl::toROSMsg(*colored, ...): point i of the wire records, read as the scan head kernel reads it (load_point_record_as,
+// kBytes chosen by the same rule), before deskewing, transform and filters.  [UPSTREAM-RECALL] pcl::PointXYZRGB in memory, 32 bytes, which toROSMsg copies
+// as it is (fields x@0 y@4 z@8 rgb@16): x y z 1.0f | b g r a | 12 zero bytes — `colored->resize` leaves data[3] = 1 and a = 255, getVector4fMap copies
+// the PointXYZI's own 1.0f (:249).  t = (double)i / n, r = 255 * t and b = 255 * (1 - t) converted to uint8_t (:248-252): f64, a real division, truncated;
+// 255 * t < 255 and 255 * (1 - t) <= 255, so the conversion never wraps.  No arithmetic touches x, y, z: a NaN's payload survives.
+struct ColoredArgs {
+    const uint8_t* raw;
+    float4*        out;  // room for n records of 32 bytes
+    uint32_t       n, width, row_step, point_step, ox, oy, oz;
+};
+template <bool kBytes>
+__global__ __launch_bounds__(256) void colored_records_kernel(const ColoredArgs a)
+{
+#pragma clang fp contract(off)
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= a.n) return;
+    const float4   p = load_point_record_as<kBytes>(a.raw, i, a.width, a.row_step, a.point_step, a.ox, a.oy, a.oz, -1);
+    const double   t = static_cast<double>(i) / static_cast<double>(a.n);
+    const uint32_t r = static_cast<uint32_t>(255.0 * t), b = static_cast<uint32_t>(255.0 * (1.0 - t));
+    a.out[2 * size_t(i)] = make_float4(p.x, p.y, p.z, 1.0f);
+    a.out[2 * size_t(i) + 1] = make_float4(__uint_as_float(b | (128u << 8) | (r << 16) | (255u << 24)), 0.0f, 0.0f, 0.0f);
+}
 // ---- StatisticalOutlierRemoval's threshold without a host round trip (sor_threshold.h) --------------------------------------------------------------
 // The reference's two f64 sums are sequential over the points; a dependent chain of n additions on one lane would cost as much as the rest of the chain.
 // They are added in a tree instead — per thread, per wavefront, per tile of 2048 points, over the tiles — together with the minimum lowest-bit exponent
@@ -1114,7 +1157,10 @@ struct RecordDest {
     const RecordSink* sink = nullptr;
     float4*           d_dst = nullptr;
     bool              direct = false;  // d_dst is the caller's buffer
+    bool              second = false;  // the call's second sink: staged through rec_pin2, counted in eg2_stats
 };
+static PinBuf&          dest_pin(mrgfe_ctx* ctx, const RecordDest& d) { return d.second ? ctx->rec_pin2 : ctx->rec_pin; }
+static ScanEgressStats& dest_stats(mrgfe_ctx* ctx, const RecordDest& d) { return d.second ? ctx->eg2_stats : ctx->eg_stats; }
 static bool page_locked(const void* p)
 {
     hipPointerAttribute_t a;
@@ -1125,13 +1171,23 @@ static void egress_begin(mrgfe_ctx* ctx)
     ScanEgressStats& e = ctx->eg_stats;
     e.direct = e.launches = e.waits = e.bytes = e.copied = 0;
     e.calls += 1;
+    ScanEgressStats& e2 = ctx->eg2_stats;  // (a call without a second sink reports none)
+    e2.direct = e2.launches = e2.waits = e2.bytes = e2.copied = 0;
+}
+// a call's second sink, where it has one (behind egress_begin when the call has a first one too)
+static void egress_second_begin(mrgfe_ctx* ctx)
+{
+    ScanEgressStats& e = ctx->eg2_stats;
+    e.direct = e.launches = e.waits = e.bytes = e.copied = 0;
+    e.calls += 1;
 }
 // n_in: the points the record kernel may write at the most.  allow_direct false: the context's pinned buffer whatever the caller's memory is.
-static int record_dest_open(mrgfe_ctx* ctx, const RecordSink& s, size_t n_in, bool allow_direct, RecordDest* d)
+static int record_dest_open(mrgfe_ctx* ctx, const RecordSink& s, size_t n_in, bool allow_direct, RecordDest* d, bool second = false)
 {
     d->sink = &s;
     d->d_dst = nullptr;
     d->direct = false;
+    d->second = second;
     char* first = static_cast<char*>(s.records);
     if (allow_direct && s.capacity && (reinterpret_cast<uintptr_t>(first) & 15u) == 0) {
         // BOTH ends of the range in page-locked memory, as upload_cloud asks of a cloud it reads in place
@@ -1143,21 +1199,23 @@ static int record_dest_open(mrgfe_ctx* ctx, const RecordSink& s, size_t n_in, bo
         (void)hipGetLastError();  // (an unregistered pointer is an error to the query, not to us)
     }
     if (!d->direct) {
-        MRGFE_TRY(ctx->rec_pin.ensure(n_in * size_t(s.point_step)));
-        d->d_dst = ctx->rec_pin.as<float4>();
+        PinBuf& pin = dest_pin(ctx, *d);
+        MRGFE_TRY(pin.ensure(n_in * size_t(s.point_step)));
+        d->d_dst = pin.as<float4>();
     }
-    ctx->eg_stats.direct = d->direct ? 1 : 0;
+    dest_stats(ctx, *d).direct = d->direct ? 1 : 0;
     return MRGFE_OK;
 }
 // behind the wait that covers the record kernel: the m records are in the destination; a staged destination is copied out
 static void record_dest_close(mrgfe_ctx* ctx, const RecordDest& d, size_t m)
 {
-    const size_t bytes = m * size_t(d.sink->point_step);
+    const size_t     bytes = m * size_t(d.sink->point_step);
+    ScanEgressStats& e = dest_stats(ctx, d);
     if (!d.direct && bytes) {
-        std::memcpy(d.sink->records, ctx->rec_pin.p, bytes);
-        ctx->eg_stats.copied = static_cast<int64_t>(bytes);
+        std::memcpy(d.sink->records, dest_pin(ctx, d).p, bytes);
+        e.copied = static_cast<int64_t>(bytes);
     }
-    ctx->eg_stats.bytes = static_cast<int64_t>(bytes);
+    e.bytes = static_cast<int64_t>(bytes);
 }
 // the m packed points at d_in as records, the count known to the host: one launch, queued
 static int launch_cloud_records(mrgfe_ctx* ctx, const float4* d_in, uint32_t m, const RecordDest& d)
@@ -1178,6 +1236,79 @@ int cloud_records_device(mrgfe_ctx* ctx, const float4* d_xyzi, size_t n, const R
     MRGFE_TRY(launch_cloud_records(ctx, d_xyzi, static_cast<uint32_t>(n), d));
     MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     ctx->eg_stats.waits += 1;
+    record_dest_close(ctx, d, n);
+    return MRGFE_OK;
+}
+int transformed_records_device(mrgfe_ctx* ctx, const float4* d_xyzi, size_t n, const float T_rowmajor[16], const RecordSink& rec)
+{
+    egress_begin(ctx);
+    if (n == 0) return MRGFE_OK;
+    RecordDest d;
+    MRGFE_TRY(record_dest_open(ctx, rec, n, true, &d));
+    RecordTransform T;
+    std::memcpy(T.m, T_rowmajor, sizeof(T.m));
+    const uint32_t nn = static_cast<uint32_t>(n);
+    hipLaunchKernelGGL(rec.point_step == 16 ? transform_records_kernel<16> : transform_records_kernel<32>, dim3((nn + 255) / 256), dim3(256), 0, ctx->stream, d_xyzi, nn, T, d.d_dst);
+    MRGFE_HIP_CHECK(hipGetLastError());
+    ctx->eg_stats.launches += 1;
+    MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    ctx->eg_stats.waits += 1;
+    record_dest_close(ctx, d, n);
+    return MRGFE_OK;
+}
+int cloud_pair_records_device(mrgfe_ctx* ctx, const float4* d_first, size_t n_first, const RecordSink* first, const float4* d_second, size_t n_second, const RecordSink* second)
+{
+    egress_begin(ctx);
+    if (second) egress_second_begin(ctx);
+    const uint32_t na = first ? static_cast<uint32_t>(n_first) : 0u, nb = second ? static_cast<uint32_t>(n_second) : 0u;
+    if (size_t(na) + nb == 0) return MRGFE_OK;
+    RecordDest da, db;
+    if (na) MRGFE_TRY(record_dest_open(ctx, *first, na, true, &da));
+    if (nb) MRGFE_TRY(record_dest_open(ctx, *second, nb, true, &db, true));
+    const int  step = na ? first->point_step : second->point_step;
+    const auto kern = step == 16 ? cloud_pair_records_kernel<16> : cloud_pair_records_kernel<32>;
+    const uint32_t blocks = static_cast<uint32_t>((uint64_t(na) + nb + 255) / 256);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, ctx->stream, d_first, na, da.d_dst, d_second, nb, db.d_dst);
+    MRGFE_HIP_CHECK(hipGetLastError());
+    if (na) ctx->eg_stats.launches += 1;
+    if (nb) ctx->eg2_stats.launches += 1;  // (the one launch serves both sinks)
+    MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (na) ctx->eg_stats.waits += 1;
+    else ctx->eg2_stats.waits += 1;  // (the second sink adds a wait only where it is alone)
+    if (na) record_dest_close(ctx, da, na);
+    if (nb) record_dest_close(ctx, db, nb);
+    return MRGFE_OK;
+}
+// the coloured records of a scan whose wire records are at d_raw: one launch, queued
+static int launch_colored_records(mrgfe_ctx* ctx, const ScanHead& h, const void* d_raw, const RecordDest& d)
+{
+    ColoredArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.raw = static_cast<const uint8_t*>(d_raw);
+    a.out = d.d_dst;
+    a.n = h.width * h.height;
+    a.width = h.width; a.row_step = h.row_step; a.point_step = h.point_step;
+    a.ox = h.off_x; a.oy = h.off_y; a.oz = h.off_z;
+    const bool strict = layout_is_strict(h.point_step, h.row_step, h.off_x, h.off_y, h.off_z, h.off_intensity);  // (the head kernel's choice)
+    hipLaunchKernelGGL(strict ? colored_records_kernel<false> : colored_records_kernel<true>, dim3((a.n + 255) / 256), dim3(256), 0, ctx->stream, a);
+    MRGFE_HIP_CHECK(hipGetLastError());
+    ctx->eg2_stats.launches += 1;
+    return MRGFE_OK;
+}
+static size_t scan_raw_bytes(const ScanHead& h) { return size_t(h.height - 1) * h.row_step + size_t(h.width) * h.point_step; }
+int scan_colored_records(mrgfe_ctx* ctx, const ScanHead& head, const RecordSink& colored)
+{
+    egress_second_begin(ctx);
+    const size_t n = size_t(head.width) * head.height;
+    if (n == 0) return MRGFE_OK;
+    if (n > 0x7fffffffu) { set_error("scan callback: cloud too large"); return MRGFE_ERR_INVALID; }
+    RecordDest  d;
+    const void* d_raw = nullptr;
+    MRGFE_TRY(record_dest_open(ctx, colored, n, true, &d, true));
+    MRGFE_TRY(upload_raw_records(ctx, head.data, scan_raw_bytes(head), &d_raw));
+    MRGFE_TRY(launch_colored_records(ctx, head, d_raw, d));
+    MRGFE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    ctx->eg2_stats.waits += 1;
     record_dest_close(ctx, d, n);
     return MRGFE_OK;
 }
@@ -1490,10 +1621,12 @@ struct ChainInput {
     const ScanHead* head = nullptr;
 };
 
-static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const ChainInput& in, size_t n, void* out, size_t* out_n, bool out_on_device, const RecordSink* rec)
+static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const ChainInput& in, size_t n, void* out, size_t* out_n, bool out_on_device, const RecordSink* rec,
+                             const RecordSink* col = nullptr)
 {
     *out_n = 0;
     if (rec) egress_begin(ctx);
+    if (col) egress_second_begin(ctx);
     ctx->pf_out_valid = false;
     PrefilterStats& ps = ctx->pf_stats;  // (mrgfe_ctx_prefilter_stats: which route serves this call)
     ps.route = 0;
@@ -1515,6 +1648,23 @@ static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const Cha
     if (rc == MRGFE_OK) rc = b.ensure(n * 16);
     if (rc == MRGFE_OK && !in.head) rc = upload_cloud(ctx, in.xyzi, n, in.stride, a.p);
     if (rc == MRGFE_OK && in.head) rc = upload_raw_records(ctx, in.head->data, size_t(in.head->height - 1) * in.head->row_step + size_t(in.head->width) * in.head->point_step, &d_raw);
+    // The coloured records (col: only with a scan's wire records) are queued here, in front of the chain: the device-driven chain's one wait covers the kernel;
+    // behind the host-driven passes colored_done waits for it.  They do not depend on the chain, so a chain that is handed back leaves them valid, and a direct
+    // destination is final.  After a failure nothing may still write the caller's buffer: colored_done waits then, too.
+    RecordDest cdest;
+    bool       colored_queued = false;
+    if (rc == MRGFE_OK && col) rc = record_dest_open(ctx, *col, n, true, &cdest, true);
+    if (rc == MRGFE_OK && col) { rc = launch_colored_records(ctx, *in.head, d_raw, cdest); colored_queued = rc == MRGFE_OK; }
+    auto colored_done = [&](int rc_in, bool waited) -> int {
+        if (!colored_queued) return rc_in;
+        if (rc_in != MRGFE_OK) { (void)hipStreamSynchronize(ctx->stream); return rc_in; }
+        if (!waited) {
+            if (hipStreamSynchronize(ctx->stream) != hipSuccess) { set_error("prefilter: the colour kernel failed"); return MRGFE_ERR_HIP; }
+            ctx->eg2_stats.waits += 1;
+        }
+        record_dest_close(ctx, cdest, n);
+        return MRGFE_OK;
+    };
     if (rc == MRGFE_OK && in.head && !device_driven) rc = launch_scan_head(ctx, *in.head, d_raw, a.as<float4>(), nullptr);  // (the device-driven chain launches it itself)
     if (rc == MRGFE_OK && device_driven) {
         // the usual chain with its counts on the device: input a, work buffer = the caller's device buffer (capacity n) or b, result in the work buffer
@@ -1525,12 +1675,13 @@ static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const Cha
         DevBuf& c = ctx->scratch[13];
         if (!out_on_device) { rc = c.ensure(n * 16); final_buf = c.as<float4>(); }
         if (rc == MRGFE_OK) rc = filter_chain_device_driven(ctx, ch, in.head, d_raw, a.as<float4>(), static_cast<uint32_t>(n), work, final_buf, &m, &used, rec ? &dest : nullptr);
-        if (rc != MRGFE_OK) return rc;
+        if (rc != MRGFE_OK) return colored_done(rc, false);
         ps.route = used ? 1 : 2;
         if (used) {
             if (!out_on_device) ctx->pf_out_valid = false;  // (the cloud went to the host: nothing of the caller's stays on the device)
             if (rec) record_dest_close(ctx, dest, m);  // (the record kernel ran in front of the chain's wait)
             else if (!out_on_device) rc = download(ctx, work, m, static_cast<float*>(out));
+            rc = colored_done(rc, true);  // (the colour kernel ran in front of the chain's wait, too)
             if (rc == MRGFE_OK) { *out_n = m; ps.out_n = m; ps.served += 1; }
             return rc;
         }
@@ -1565,6 +1716,7 @@ static int filter_chain_from(mrgfe_ctx* ctx, const PrefilterChain& ch, const Cha
             rc = MRGFE_ERR_HIP;
         }
     }
+    rc = colored_done(rc, false);
     if (rc == MRGFE_OK) { *out_n = m; ps.out_n = m; }
     return rc;
 }
@@ -1576,11 +1728,11 @@ int filter_chain(mrgfe_ctx* ctx, const PrefilterChain& ch, const float* xyzi, si
     in.stride = stride;
     return filter_chain_from(ctx, ch, in, n, out, out_n, out_on_device, rec);
 }
-int scan_chain(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHead& head, void* out, size_t* out_n, bool out_on_device, const RecordSink* rec)
+int scan_chain(mrgfe_ctx* ctx, const PrefilterChain& ch, const ScanHead& head, void* out, size_t* out_n, bool out_on_device, const RecordSink* rec, const RecordSink* colored)
 {
     ChainInput in;
     in.head = &head;
-    return filter_chain_from(ctx, ch, in, size_t(head.width) * head.height, out, out_n, out_on_device, rec);
+    return filter_chain_from(ctx, ch, in, size_t(head.width) * head.height, out, out_n, out_on_device, rec, colored);
 }
 
 int filter_distance(mrgfe_ctx* ctx, const float* xyzi, size_t n, size_t stride, double near_t, double far_t, float* out, size_t* out_n)

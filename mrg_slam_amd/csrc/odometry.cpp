@@ -102,7 +102,9 @@ struct FrameInput {
     size_t                n = 0;             // points of the input cloud, > 0
 };
 
-int odom_frame_impl(const char* fn, mrgfe_odom* o, const FrameInput& in, double stamp, const float* msf_delta, int want_status, float* aligned_xyzi, mrgfe_odom_result* out)
+// aligned_rec (the record forms): the aligned cloud as records instead of packed points, *n_aligned their count
+int odom_frame_impl(const char* fn, mrgfe_odom* o, const FrameInput& in, double stamp, const float* msf_delta, int want_status, float* aligned_xyzi, mrgfe_odom_result* out,
+                    const RecordSink* aligned_rec = nullptr, size_t* n_aligned = nullptr)
 {
     mrgfe_reg* reg = o->reg;
     mrgfe_ctx* ctx = o->ctx;
@@ -273,6 +275,13 @@ int odom_frame_impl(const char* fn, mrgfe_odom* o, const FrameInput& in, double 
         MRGFE_HIP_CHECK(hipMemcpyAsync(aligned_xyzi, o->spare.p, n * 16, hipMemcpyDeviceToHost, st));
         MRGFE_HIP_CHECK(hipStreamSynchronize(st));
     }
+    if (aligned_rec && d.outcome == ODOM_ACCEPTED) {
+        // :341-347 in one pass over the input cloud: transform and record in one kernel, into the caller's page-locked buffer or the context's pinned one
+        float odom_rm[16];
+        col2row(d.odom, odom_rm);
+        MRGFE_TRY(transformed_records_device(ctx, d_whole, n, odom_rm, *aligned_rec));  // (the one wait of the aligned_xyzi path)
+        *n_aligned = n;
+    }
     if (!in.device && !wants_box) read_head_box();  // (at least one wait lies behind the copy by now)
     o->ctl = trial;
     o->last_cloud = first ? reg->d_tgt : reg->d_src;
@@ -382,6 +391,58 @@ int mrgfe_odom_frame_device(mrgfe_odom* o, const void* d_xyzi, size_t n, double 
         in.d_xyzi = d_xyzi;
         in.n = n;
         return odom_frame_impl(fn, o, in, stamp, msf_delta, want_status, aligned_xyzi, out);
+    });
+}
+
+// what the record forms refuse before the frame is looked at: a NULL destination or count, a point_step other than the two of record_store.h, no room for one
+// record per input point
+static int check_aligned_sink(const char* fn, int point_step, void* records, size_t capacity_bytes, size_t* n_aligned, size_t n, RecordSink* sink)
+{
+    if (!records || !n_aligned) { set_error("%s: NULL aligned_records / n_aligned", fn); return MRGFE_ERR_INVALID; }
+    *n_aligned = 0;
+    if (point_step != 16 && point_step != 32) { set_error("%s: point_step %d (16: x y z intensity, 32: pcl::PointXYZI)", fn, point_step); return MRGFE_ERR_INVALID; }
+    if (capacity_bytes / size_t(point_step) < n) { set_error("%s: capacity_bytes %zu, %zu input points of %d bytes need room", fn, capacity_bytes, n, point_step); return MRGFE_ERR_INVALID; }
+    sink->point_step = point_step;
+    sink->records = records;
+    sink->capacity = capacity_bytes;
+    return MRGFE_OK;
+}
+
+int mrgfe_odom_frame_records(mrgfe_odom* o, const mrgfe_keyframe_params* lay, const void* data, size_t data_bytes, double stamp, const float* msf_delta, int want_status,
+                             int point_step, void* aligned_records, size_t capacity_bytes, size_t* n_aligned, mrgfe_odom_result* out)
+{
+    static const char* fn = "mrgfe_odom_frame_records";
+    return abi_guard(fn, [&]() -> int {
+        if (!o || !lay || !data || !out) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        FrameInput in;
+        in.lay = *lay;
+        MRGFE_TRY(check_pointcloud2_layout(o->ctx, fn, in.lay.width, in.lay.height, in.lay.point_step, &in.lay.row_step, in.lay.off_x, in.lay.off_y, in.lay.off_z, in.lay.off_intensity));
+        in.n = size_t(in.lay.width) * in.lay.height;
+        RecordSink sink;
+        MRGFE_TRY(check_aligned_sink(fn, point_step, aligned_records, capacity_bytes, n_aligned, in.n, &sink));
+        if (in.n == 0) { set_error("%s: an empty message", fn); return MRGFE_ERR_INVALID; }
+        in.raw_bytes = size_t(in.lay.height - 1) * in.lay.row_step + size_t(in.lay.width) * in.lay.point_step;
+        if (data_bytes < in.raw_bytes) { set_error("%s: the payload has %zu bytes, the layout needs %zu", fn, data_bytes, in.raw_bytes); return MRGFE_ERR_INVALID; }
+        in.data = data;
+        return odom_frame_impl(fn, o, in, stamp, msf_delta, want_status, nullptr, out, &sink, n_aligned);
+    });
+}
+
+int mrgfe_odom_frame_records_device(mrgfe_odom* o, const void* d_xyzi, size_t n, double stamp, const float* msf_delta, int want_status, int point_step, void* aligned_records,
+                                    size_t capacity_bytes, size_t* n_aligned, mrgfe_odom_result* out)
+{
+    static const char* fn = "mrgfe_odom_frame_records_device";
+    return abi_guard(fn, [&]() -> int {
+        if (!o || !d_xyzi || !out) { set_error("%s: NULL argument", fn); return MRGFE_ERR_INVALID; }
+        MRGFE_TRY(check_count(n, fn));
+        RecordSink sink;
+        MRGFE_TRY(check_aligned_sink(fn, point_step, aligned_records, capacity_bytes, n_aligned, n, &sink));
+        if (n == 0) { set_error("%s: an empty cloud", fn); return MRGFE_ERR_INVALID; }
+        FrameInput in;
+        in.device = true;
+        in.d_xyzi = d_xyzi;
+        in.n = n;
+        return odom_frame_impl(fn, o, in, stamp, msf_delta, want_status, nullptr, out, &sink, n_aligned);
     });
 }
 

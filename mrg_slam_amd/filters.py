@@ -344,6 +344,40 @@ def scan_callback_records(data, width: int, height: int, point_step: int, fields
     return rec[: m.value * record_step]
 
 
+COLORED_FIELDS = {"x": 0, "y": 4, "z": 8, "rgb": 16}  # field offsets of the coloured cloud's 32-byte records (pcl::PointXYZRGB)
+
+
+def scan_callback_outputs(data, width: int, height: int, point_step: int, fields, record_step: int = 32, out=None, colored_out=None, dev_ptr: int = 0, row_step: int = 0,
+                          ang_v=None, scan_period: float = 0.1, T=None, params: dict | None = None, records: bool = True, colored: bool = True,
+                          ctx: Context | None = None):
+    """:func:`scan_callback_records` with the callback's second publish (``mrgfe_scan_callback_outputs``): ``(records, colored_records, n_points)``, the second the
+    ``data`` of ``prefiltering/colored_points`` — the RAW scan (before deskewing, transform and filters, width * height points, non-finite ones included) as
+    32-byte ``pcl::PointXYZRGB`` records (:data:`COLORED_FIELDS`), the colour saying where a point stands in the point sequence — written on the device from
+    the one uploaded payload.  ``colored=False``: the call is :func:`scan_callback_records` and the second value is ``None``; ``records=False``: no filtered
+    records are made and the first value is ``None`` (with ``dev_ptr`` the filtered scan is still left on the device, ``n_points`` of it).  ``colored_out``: the caller's own
+    buffer, as ``out``."""
+    from .io import pointcloud2_payload
+
+    if not records and not colored:
+        raise ValueError("neither the filtered records nor the coloured records are wanted")
+    ctx = ctx or default_context()
+    buf = pointcloud2_payload(data, width, height, point_step, row_step)
+    q, m, mc = _scan_params(width, height, point_step, fields, row_step, ang_v, scan_period, T, params, ctx), C.c_size_t(0), C.c_size_t(0)
+    n = int(width) * int(height)
+    o = _lib.ScanOutputs()
+    o.point_step = int(record_step)
+    rec = col = None
+    if records:
+        rec = _records_destination(n, record_step, out)
+        o.records, o.capacity_bytes = rec.ctypes.data, rec.nbytes
+    if colored:
+        col = _records_destination(n, 32, colored_out)
+        o.colored_records, o.colored_capacity_bytes = col.ctypes.data, col.nbytes
+    o.d_out_xyzi = dev_ptr or None
+    check(lib().mrgfe_scan_callback_outputs(ctx._h, C.byref(q), buf.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(o), C.byref(m), C.byref(mc)))
+    return (rec[: m.value * record_step] if records else None), (col[: mc.value * 32] if colored else None), m.value
+
+
 def prefilter_records(cloud, record_step: int = 32, out=None, dev_ptr: int = 0, params: dict | None = None, ctx: Context | None = None) -> np.ndarray:
     """:func:`prefilter` with the result as records (``mrgfe_prefilter_records``): see :func:`scan_callback_records`; ``dev_ptr``: device memory for
     len(cloud) packed points, filled as :func:`prefilter_to_device` fills it."""

@@ -103,11 +103,11 @@ class HipOps:
     def __init__(self, store):
         self.store = store
 
-    def keyframe(self, key, msg, centres_sensor, radius, want_removed):
-        return self.store.keyframe_callback(key, msg, centres_sensor, radius, want_kept=len(centres_sensor) > 0, want_removed=want_removed)
+    def keyframe(self, key, msg, centres_sensor, radius, want_removed, records: int = 0):
+        return self.store.keyframe_callback(key, msg, centres_sensor, radius, want_kept=len(centres_sensor) > 0, want_removed=want_removed, records=records)
 
-    def keyframe_device(self, key, dev_ptr, n, centres_sensor, radius, want_removed):
-        return self.store.keyframe_callback_device(key, dev_ptr, n, centres_sensor, radius, want_kept=len(centres_sensor) > 0, want_removed=want_removed)
+    def keyframe_device(self, key, dev_ptr, n, centres_sensor, radius, want_removed, records: int = 0):
+        return self.store.keyframe_callback_device(key, dev_ptr, n, centres_sensor, radius, want_kept=len(centres_sensor) > 0, want_removed=want_removed, records=records)
 
 
 @dataclasses.dataclass
@@ -118,6 +118,7 @@ class KeyframeResult:
     odom: np.ndarray
     kept: np.ndarray | None     # the keyframe's cloud; None: no other robot, the message's own cloud is the keyframe's (:373,396)
     removed: np.ndarray | None  # the points that hit other robots; None unless asked for (get_subscription_count() > 0, :437)
+    # (with ``records`` both are the ``data`` of the messages of :432-443 instead: uint8 records written on the device)
     centres_sensor: np.ndarray = None
 
 
@@ -135,7 +136,7 @@ class KeyframeCallback:
         self.others_odom_poses: dict = {}  # robot name -> position x, y, z in the map frame (others_odom_poses_), :386-393
         self.next_key = 1
 
-    def _keyframe(self, odom, key, removed_points_wanted, point_work):
+    def _keyframe(self, odom, key, removed_points_wanted, point_work, records: int = 0):
         """:358-447 around the point work: ``point_work(key, centres, radius, want_removed)`` returns ``(kept, removed)``."""
         odom = np.array(odom, dtype=np.float64)
         update_required = self.updater.update(odom)  # :367
@@ -157,16 +158,24 @@ class KeyframeCallback:
         if not len(centres):
             kept = None
             if removed_points_wanted and removed is None:
-                removed = np.empty((0, 4), dtype=np.float32)  # removed_cloud stays empty, :395
+                removed = np.empty(0, dtype=np.uint8) if records else np.empty((0, 4), dtype=np.float32)  # removed_cloud stays empty, :395
         return KeyframeResult(key, accum_d, odom, kept, removed if removed_points_wanted else None, centres)
 
-    def cloud_callback(self, odom, msg, key: int | None = None, removed_points_wanted: bool = False):
-        """:358-447.  Returns a :class:`KeyframeResult`, or None when the pose starts no keyframe."""
+    def cloud_callback(self, odom, msg, key: int | None = None, removed_points_wanted: bool = False, records: int = 0):
+        """:358-447.  Returns a :class:`KeyframeResult`, or None when the pose starts no keyframe.  ``records`` 32 or 16 (default 0: off; needs ops that
+        take it, :class:`HipOps`): ``kept`` and ``removed`` come back as the ``data`` of ``cloud_msg_filtered`` and ``other_robots_removed_points``
+        (:432-443), written on the device (``mrgfe_keyframe_callback_records``)."""
+        if records:
+            return self._keyframe(odom, key, removed_points_wanted, lambda k, centres, radius, want_removed: self.ops.keyframe(k, msg, centres, radius, want_removed, records),
+                                  records)
         return self._keyframe(odom, key, removed_points_wanted, lambda k, centres, radius, want_removed: self.ops.keyframe(k, msg, centres, radius, want_removed))
 
-    def cloud_callback_device(self, odom, dev_ptr: int, n: int, key: int | None = None, removed_points_wanted: bool = False):
+    def cloud_callback_device(self, odom, dev_ptr: int, n: int, key: int | None = None, removed_points_wanted: bool = False, records: int = 0):
         """The same callback — the same :class:`KeyframeUpdater` decision, the same centres — for a filtered scan that is already in HBM (all
         components in one container): ``n`` packed float4 points at ``dev_ptr`` on the store's device (``ops.keyframe_device``)."""
+        if records:
+            return self._keyframe(odom, key, removed_points_wanted,
+                                  lambda k, centres, radius, want_removed: self.ops.keyframe_device(k, dev_ptr, n, centres, radius, want_removed, records), records)
         return self._keyframe(odom, key, removed_points_wanted, lambda k, centres, radius, want_removed: self.ops.keyframe_device(k, dev_ptr, n, centres, radius, want_removed))
 
 

@@ -130,17 +130,25 @@ class MapCloudStore:
         c = _cloud(cloud)
         check(lib().mrgfe_map_store_add(self._h, key, c.ctypes.data_as(_fp), len(c), 16))
 
-    def keyframe_callback(self, key: int, payload_or_msg, centres_sensor=None, radius: float = 2.0, want_kept: bool = True, want_removed: bool = True):
+    def keyframe_callback(self, key: int, payload_or_msg, centres_sensor=None, radius: float = 2.0, want_kept: bool = True, want_removed: bool = True, records: int = 0,
+                          kept_out=None, removed_out=None):
         """``mrgfe_keyframe_callback``: the point work of MrgSlamComponent::cloud_callback (apps/mrg_slam_component.cpp:372, 396-430) on a
         sensor_msgs/PointCloud2 — a dict with ``data``, ``width``, ``height``, ``point_step``, ``fields`` (name -> byte offset) and optionally
         ``row_step``, or a packed [n, 4] float32 cloud — in one call: the payload goes up once, every point closer than ``radius`` to one of
         ``centres_sensor`` (K x 3, sensor frame, K <= 64; robot_radius_sqr is float(radius * radius), :406-407) is split off, and the kept cloud
-        becomes keyframe ``key`` of this store.  Returns ``(kept, removed)``; an output that is not wanted is None and is not downloaded."""
+        becomes keyframe ``key`` of this store.  Returns ``(kept, removed)``; an output that is not wanted is None and is not downloaded.
+        ``records`` 32 or 16 (default 0: off): the callback to its publishes (``mrgfe_keyframe_callback_records``, :432-443) — ``kept`` and ``removed`` are
+        the ``data`` of ``cloud_msg_filtered`` and ``other_robots_removed_points`` (uint8, ``count * records`` bytes, written on the device; views of
+        ``kept_out`` / ``removed_out`` when the caller gives its own, ideally page-locked, buffers)."""
         msg = payload_or_msg if isinstance(payload_or_msg, dict) else pointcloud2_from_xyzi(payload_or_msg)
         p = keyframe_params(msg, self._ctx)
         n = int(p.width) * int(p.height)
         buf = np.frombuffer(msg["data"], dtype=np.uint8) if n else np.zeros(0, dtype=np.uint8)
         ctr = np.ascontiguousarray(np.asarray(centres_sensor if centres_sensor is not None else np.zeros((0, 3)), dtype=np.float32).reshape(-1, 3))
+        if records:
+            return self._callback_records(n, records, want_kept, want_removed, kept_out, removed_out, lambda *tail: lib().mrgfe_keyframe_callback_records(
+                self._h, int(key), C.byref(p), buf.ctypes.data_as(C.c_void_p) if n else None, buf.nbytes, ctr.ctypes.data_as(_fp) if len(ctr) else None, len(ctr),
+                float(np.float32(float(radius) * float(radius))), *tail))
         kept = np.empty((n, 4), dtype=np.float32) if want_kept else None
         removed = np.empty((n, 4), dtype=np.float32) if want_removed and len(ctr) else None
         nk, nr = C.c_size_t(0), C.c_size_t(0)
@@ -152,13 +160,29 @@ class MapCloudStore:
             removed = np.empty((0, 4), dtype=np.float32)  # (no other robot: nothing was removed)
         return (kept[: nk.value] if kept is not None else None), (removed[: nr.value] if removed is not None else None)
 
-    def keyframe_callback_device(self, key: int, dev_ptr: int, n: int, centres_sensor=None, radius: float = 0.0, want_kept: bool = True, want_removed: bool = False):
+    def _callback_records(self, n, records, want_kept, want_removed, kept_out, removed_out, call):
+        """the record tail of both callback forms: ``call(point_step, kept, kept capacity, n_kept, removed, removed capacity, n_removed)``"""
+        from .filters import _records_destination
+
+        kept = _records_destination(n, records, kept_out) if want_kept else None
+        removed = _records_destination(n, records, removed_out) if want_removed else None
+        nk, nr = C.c_size_t(0), C.c_size_t(0)
+        check(call(int(records), kept.ctypes.data_as(C.c_void_p) if kept is not None else None, kept.nbytes if kept is not None else 0, C.byref(nk),
+                   removed.ctypes.data_as(C.c_void_p) if removed is not None else None, removed.nbytes if removed is not None else 0, C.byref(nr)))
+        return (kept[: nk.value * records] if kept is not None else None), (removed[: nr.value * records] if removed is not None else None)
+
+    def keyframe_callback_device(self, key: int, dev_ptr: int, n: int, centres_sensor=None, radius: float = 0.0, want_kept: bool = True, want_removed: bool = False,
+                                 records: int = 0, kept_out=None, removed_out=None):
         """``mrgfe_keyframe_callback_device``: :meth:`keyframe_callback` for a filtered scan that is already in HBM (all components in one container) —
         ``n`` packed float4 points at ``dev_ptr`` on the store's device, complete when the call is made (``scan_callback_to_device`` and the other
         ``*_device`` producers return only after their wait).  No upload: the same kernels read the buffer where it is; it is only read and is free
-        on return.  Returns ``(kept, removed)`` as :meth:`keyframe_callback` does."""
+        on return.  Returns ``(kept, removed)`` as :meth:`keyframe_callback` does; ``records``: as there (``mrgfe_keyframe_callback_records_device``)."""
         n = int(n)
         ctr = np.ascontiguousarray(np.asarray(centres_sensor if centres_sensor is not None else np.zeros((0, 3)), dtype=np.float32).reshape(-1, 3))
+        if records:
+            return self._callback_records(n, records, want_kept, want_removed, kept_out, removed_out, lambda *tail: lib().mrgfe_keyframe_callback_records_device(
+                self._h, int(key), C.c_void_p(int(dev_ptr)) if dev_ptr else None, n, ctr.ctypes.data_as(_fp) if len(ctr) else None, len(ctr),
+                float(np.float32(float(radius) * float(radius))), *tail))
         kept = np.empty((n, 4), dtype=np.float32) if want_kept else None
         removed = np.empty((n, 4), dtype=np.float32) if want_removed and len(ctr) else None
         nk, nr = C.c_size_t(0), C.c_size_t(0)

@@ -250,10 +250,14 @@ class HipOdometry:
         d = np.ascontiguousarray(np.asarray(msf_delta, dtype=np.float32).T)
         return d, d.ctypes.data_as(C.POINTER(C.c_float))
 
-    def frame(self, msg_or_cloud, stamp: float, msf_delta=None, want_status: bool = False, want_aligned: bool = False) -> OdomFrame:
+    def frame(self, msg_or_cloud, stamp: float, msf_delta=None, want_status: bool = False, want_aligned: bool = False, aligned_records: int = 0,
+              records_out=None) -> OdomFrame:
         """One frame from a PointCloud2 dict (``data``, ``width``, ``height``, ``point_step``, ``row_step``, ``fields``: name -> offset, or the
         message's field list as ``io.layout_from_fields`` takes it) or from an
-        N x 4 float32 cloud (sent as the packed 16-byte message)."""
+        N x 4 float32 cloud (sent as the packed 16-byte message).
+        ``aligned_records`` 32 or 16 (default 0: off): the frame to its publish (``mrgfe_odom_frame_records``, :341-347) — on an accepted frame
+        ``OdomFrame.aligned`` is the ``data`` of ``scan_matching_odometry/aligned_points`` (uint8, ``n * aligned_records`` bytes, written on the device; a
+        view of ``records_out`` when the caller gives its own, ideally page-locked, buffer), else None."""
         import ctypes as C
 
         from . import _lib
@@ -280,13 +284,22 @@ class HipOdometry:
         keep, dptr = self._delta(msf_delta)
         out = _lib.OdomResult()
         buf = (C.c_char * len(data)).from_buffer_copy(data) if len(data) else None
+        if aligned_records:
+            from .filters import _records_destination
+
+            rec, m = _records_destination(n, aligned_records, records_out), C.c_size_t(0)
+            _lib.check(_lib.lib().mrgfe_odom_frame_records(h, C.byref(lay), C.cast(buf, C.c_void_p) if buf is not None else None, len(data), float(stamp), dptr,
+                                                             int(bool(want_status)), int(aligned_records), rec.ctypes.data_as(C.c_void_p), rec.nbytes, C.byref(m), C.byref(out)))
+            return OdomFrame(out, rec[: m.value * aligned_records] if out.outcome == _lib.ODOM_ACCEPTED else None)
         _lib.check(_lib.lib().mrgfe_odom_frame(h, C.byref(lay), C.cast(buf, C.c_void_p) if buf is not None else None, len(data), float(stamp), dptr, int(bool(want_status)),
                                                  None if aligned is None else aligned.ctypes.data_as(C.POINTER(C.c_float)), C.byref(out)))
         return OdomFrame(out, aligned if (aligned is not None and out.outcome == _lib.ODOM_ACCEPTED) else None)
 
-    def frame_device(self, dev_ptr: int, n: int, stamp: float, msf_delta=None, want_status: bool = False, want_aligned: bool = False) -> OdomFrame:
+    def frame_device(self, dev_ptr: int, n: int, stamp: float, msf_delta=None, want_status: bool = False, want_aligned: bool = False, aligned_records: int = 0,
+                     records_out=None) -> OdomFrame:
         """One frame from a packed cloud of ``n`` points already in HBM at ``dev_ptr`` (the output of ``scan_callback_to_device`` / ``prefilter_to_device``
-        on the registration's context); the buffer may be overwritten as soon as this returns."""
+        on the registration's context); the buffer may be overwritten as soon as this returns.  ``aligned_records``: as :meth:`frame`
+        (``mrgfe_odom_frame_records_device``)."""
         import ctypes as C
 
         from . import _lib
@@ -295,6 +308,13 @@ class HipOdometry:
         aligned = np.empty((int(n), 4), dtype=np.float32) if want_aligned else None
         keep, dptr = self._delta(msf_delta)
         out = _lib.OdomResult()
+        if aligned_records:
+            from .filters import _records_destination
+
+            rec, m = _records_destination(int(n), aligned_records, records_out), C.c_size_t(0)
+            _lib.check(_lib.lib().mrgfe_odom_frame_records_device(h, C.c_void_p(dev_ptr), int(n), float(stamp), dptr, int(bool(want_status)), int(aligned_records),
+                                                                    rec.ctypes.data_as(C.c_void_p), rec.nbytes, C.byref(m), C.byref(out)))
+            return OdomFrame(out, rec[: m.value * aligned_records] if out.outcome == _lib.ODOM_ACCEPTED else None)
         _lib.check(_lib.lib().mrgfe_odom_frame_device(h, C.c_void_p(dev_ptr), int(n), float(stamp), dptr, int(bool(want_status)),
                                                         None if aligned is None else aligned.ctypes.data_as(C.POINTER(C.c_float)), C.byref(out)))
         return OdomFrame(out, aligned if (aligned is not None and out.outcome == _lib.ODOM_ACCEPTED) else None)

@@ -42,13 +42,28 @@ class HipOps:
         the result stays on the device and the count is returned."""
         return self.scan_pointcloud2(memoryview(cloud).cast("B"), len(cloud), 1, 16, {"x": 0, "y": 4, "z": 8, "intensity": 12}, 0, ang_v, scan_period, T, p, dev_ptr)
 
-    def scan_pointcloud2(self, data, width, height, point_step, fields, row_step, ang_v, scan_period, T, p, dev_ptr: int = 0, records: int = 0, records_out=None):
+    def scan_pointcloud2(self, data, width, height, point_step, fields, row_step, ang_v, scan_period, T, p, dev_ptr: int = 0, records: int = 0, records_out=None,
+                         colored: bool = False, colored_out=None):
         """``records`` 32 or 16 (default 0: off): the filtered scan as the message the component publishes (``mrgfe_scan_callback_records``, the
         ``pcl::toROSMsg`` + publish of :152-155) — a dict with the message's ``data`` (uint8; a view of ``records_out`` when given), ``point_step``, ``fields``
         (name -> offset), ``width``, ``height`` 1, ``row_step``, ``is_dense`` False, ``is_bigendian`` False; with ``dev_ptr`` the packed scan stays on the
-        device as well."""
-        from .filters import RECORD_FIELDS, scan_callback, scan_callback_records, scan_callback_to_device
+        device as well.
+        ``colored`` (needs ``records`` or ``dev_ptr``): the call also makes ``prefiltering/colored_points`` (:239-257, ``mrgfe_scan_callback_outputs``) and
+        returns ``(result, colored message)``: ``width`` / ``height`` the input's, ``point_step`` 32, ``fields`` x y z rgb, ``data`` the raw scan's coloured
+        records (a view of ``colored_out`` when given)."""
+        from .filters import COLORED_FIELDS, RECORD_FIELDS, scan_callback, scan_callback_outputs, scan_callback_records, scan_callback_to_device
 
+        if colored:
+            if not (records or dev_ptr):
+                raise ValueError("colored: with records or dev_ptr")
+            rec, col, m = scan_callback_outputs(data, width, height, point_step, fields, records or 32, records_out, colored_out, dev_ptr, row_step, ang_v, scan_period, T, p,
+                                             records=bool(records), ctx=self.ctx)
+            cmsg = {"height": int(height), "width": int(width), "is_dense": False, "is_bigendian": False, "point_step": 32, "row_step": 32 * int(width),
+                    "fields": dict(COLORED_FIELDS), "data": col}
+            if not records:
+                return m, cmsg
+            return {"height": 1, "width": len(rec) // records, "is_dense": False, "is_bigendian": False, "point_step": records, "row_step": len(rec),
+                    "fields": dict(RECORD_FIELDS[records]), "data": rec}, cmsg
         if records:
             rec = scan_callback_records(data, width, height, point_step, fields, records, records_out, dev_ptr, row_step, ang_v, scan_period, T, p, ctx=self.ctx)
             return {"height": 1, "width": len(rec) // records, "is_dense": False, "is_bigendian": False, "point_step": records, "row_step": len(rec),
@@ -180,19 +195,27 @@ class PrefilteringComponent:
         return self.ops.filters(src, self.p)
 
     def pointcloud2_callback(self, data, width: int, height: int, point_step: int, fields, row_step: int = 0, stamp: float = 0.0, frame_id: str = "",
-                             dev_ptr: int = 0, records: int = 0, records_out=None):
+                             dev_ptr: int = 0, records: int = 0, records_out=None, colored: bool = False, colored_out=None):
         """``cloud_callback`` from the wire message (the payload and layout of a sensor_msgs/PointCloud2): pcl::fromROSMsg happens in the same
         GPU call as the rest.  ``fields``: a ``{name: offset}`` dict or the message's field list ``(name, offset, datatype, count)``, as
         ``io.layout_from_fields`` takes them (the list switches the context to byte layouts when the records need it: Velodyne's 22-byte points).  Returns the filtered cloud, or — with ``dev_ptr`` (device memory for width * height packed points) — leaves it
         there and returns its point count; None where the reference returns early.  Needs point operations with ``scan_pointcloud2`` (HipOps).
         ``records`` 32 or 16 (default 0: off): the callback to its publish (:152-155) — returns the filtered message (``HipOps.scan_pointcloud2``: its
-        ``data``, ``point_step`` and ``fields``; ``records_out``: the caller's, ideally page-locked, buffer) and, with ``dev_ptr``, leaves the device cloud too."""
+        ``data``, ``point_step`` and ``fields``; ``records_out``: the caller's, ideally page-locked, buffer) and, with ``dev_ptr``, leaves the device cloud too.
+        ``colored`` (a subscriber on ``prefiltering/colored_points``; with ``records`` or ``dev_ptr``): returns ``(result, colored message)`` — the second the
+        message of :239-257 from the same GPU call (``HipOps.scan_pointcloud2``), or None when the IMU queue was empty: the reference returns from
+        ``deskewing`` before it colours (:234-236)."""
         if int(width) * int(height) == 0:
             return None
         ang_v = self._take_imu(stamp)
         ok, T = self._lookup(frame_id)
         if not ok:
             return None
+        if colored:
+            if ang_v is None:
+                return self.ops.scan_pointcloud2(data, width, height, point_step, fields, row_step, ang_v, self.p["scan_period"], T, self.p, dev_ptr, records, records_out), None
+            return self.ops.scan_pointcloud2(data, width, height, point_step, fields, row_step, ang_v, self.p["scan_period"], T, self.p, dev_ptr, records, records_out, True,
+                                             colored_out)
         if records:
             return self.ops.scan_pointcloud2(data, width, height, point_step, fields, row_step, ang_v, self.p["scan_period"], T, self.p, dev_ptr, records, records_out)
         return self.ops.scan_pointcloud2(data, width, height, point_step, fields, row_step, ang_v, self.p["scan_period"], T, self.p, dev_ptr)
